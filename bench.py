@@ -10,7 +10,10 @@ torch.distributed.run, or by the caller (WORLD_SIZE must then equal --gpus) -- u
 collective; the only collective is the RCCL broadcast of the weight blob.
 Defaults: the receiver kernel with two streams per CU (k_rx_sync2) and three batches in flight.
 
-Prints ONE JSON line on rank 0 (see the task contract): value = whole-job frames/s.
+Prints ONE JSON line on rank 0 (see the task contract): value = whole-job frames/s, ms_per_step = wall time of one timed step.
+A plain run sets up, warms up, times exactly --steps steps once and prints the line.  `--full` adds what takes runs of its own: the
+roofline legs, the oracle parity sample on the timed workload, config 2 and the CPU baselines (and times the K steps --repeats 3 times).
+`--dump-outputs DIR` writes what the last timed step computed (features, EOO bits, receiver status, a sample of the received IQ) as .npy files.
 `--config 2` instead measures BASELINE.json configs[1] (one stream through the rade_core.h-level encoder / decoder,
 latency-bound by construction) and prints its own line.
 
@@ -131,7 +134,7 @@ def sync_peers(world, env):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--repeats", type=int, default=3, help="the timed K-step loop is run this many times (barrier-bracketed each); value = the median repeat")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed K-step loop is run this many times (barrier-bracketed each); value = the median repeat (default 1; 3 with --full)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--streams", type=int, default=256, help="utterances per GPU")
@@ -139,13 +142,19 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=(2, 3), help="3: the headline batch workload; 2: single-stream core encoder/decoder latency")
     ap.add_argument("--pipeline", type=int, default=3, help="batches in flight: engines + HIP streams + host threads that take the steps in turn (1 = one batch at a time)")
     ap.add_argument("--two-pass-channel", action="store_true", help="rade_batch_tx + rade_batch_channel as two calls (k_chan_power + k_chan_apply) instead of rade_batch_tx_channel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also run the legs that take runs of their own: roofline (per-kernel HIP-event timing), the oracle "
+                    "parity sample, config 2 and the CPU baselines (each can be left out with its --no-* switch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no config 2 leg and no CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline leg")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity sample")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB; see dump_outputs())")
     ap.add_argument("--as-shard", type=str, default=None, metavar="R/N", help="developer mode: a single process takes the utterance shard rank R of an N-rank job would own (its results must equal that rank's)")
     ap.add_argument("--oversubscribe-device", type=int, default=None, metavar="D",
                     help="developer mode: run the --gpus N ranks of an N-GPU job all on HIP device D (gloo for the two collectives): what N processes x 3 engines cost the HOST; not a scaling measurement")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.pipeline > 3:                # HIP multiplexes a process's streams onto 4 hardware queues per device by default; streams that share one serialise
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
@@ -275,7 +284,7 @@ def main():
         barrier()
         ru0 = resource.getrusage(resource.RUSAGE_SELF)
         t0 = time.perf_counter()
-        fo, st, _, rx_last = run_steps(args.steps, 1)
+        fo, st, eoo_last, rx_last = run_steps(args.steps, 1)
         barrier()
         dt_local = time.perf_counter() - t0
         if gc_was: gc.enable()
@@ -351,16 +360,19 @@ def main():
                        "RADE_SYNC": os.environ.get("RADE_SYNC", "auto"), "RADE_SYNC_PEERS": int(os.environ.get("RADE_SYNC_PEERS", "1"))}
         out["decoded_modem_frames_per_stream"] = {"min": int(nv.min()), "mean": float(nv.mean()), "max": int(nv.max())}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, fo, st, eoo_last, rx_last)
+
+    if rank == 0 and args.full and not args.no_roofline:
         out["roofline"] = roofline_leg(eng, step, args.steps, B, T, value, world)
         out["roofline"]["rx_kernel"] = "k_rx_sync2 (256 threads / at most 80 KB of LDS per stream: two streams per CU)"
         if depth > 1 and out["roofline"].get("kernel") == "rx_sync":
             pipelined_roofline(out["roofline"], engs, run_steps, min(args.steps, 24), dev)
         if out["roofline"].get("kernel") == "rx_sync":
             two_per_cu_leg(out["roofline"], B, T, n_mf, local, blob, feats, G, sigma, n_pre, n_post)
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         out["parity_sample"] = parity_leg(feats_np, fo, st, rx_last, blob, local, B)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # configs[1] (single stream through rade_core_encoder / rade_core_decoder) beside the headline workload, so the driver's record carries it
         # too: `python bench.py --config 2` prints the full line.  Ahead of the CPU baselines: the all-cores leg runs the container's CPU quota dry,
         # and a call of this latency measurement that started in the same scheduler period was then throttled for 35-60 ms (`decoder_call_max` of two
@@ -369,7 +381,7 @@ def main():
         out["config2"] = {"workload": c2["config"]["workload"], "ms_per_step": c2["ms_per_step"], "frames_per_s": c2["value"], "latency_ms": c2["latency_ms"],
                           "cpu_frames_per_s": c2["cpu_baseline"]["value"], "cpu_sample": c2["cpu_baseline"]["sample"], "speedup_vs_one_core": c2["value"] / c2["cpu_baseline"]["value"],
                           "parity": c2["parity"]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(feats_np, T)
         out["cpu_baseline_allcores"] = cpu_baseline_allcores(T)
 
@@ -381,6 +393,48 @@ def main():
         import torch.distributed as dist
         dist.barrier()                   # rank 0 may still be in its extra legs: leave the group together
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 63 * 1000 * 1000        # --dump-outputs: 64 MB in all, less room for the .npy headers
+DUMP_IQ_STREAMS = 4
+
+
+def dump_outputs(d, fo, st, eoo, rx):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy, so that two builds can be compared output for output (the
+    inputs and the channel's Philox noise are fixed by the command line).  Contents past status.n_valid / without status.has_eoo are undefined in the
+    C ABI (the caller-owned buffers keep what they held), so they are written as zeroes.
+      features.npy        float32 [S, R, row]  decoded rows of streams feature_streams (R = the largest n_valid of the step; all streams unless that
+                                               would exceed the budget, then a fixed, seeded sample of them)
+      feature_streams.npy float64 [S]          stream indices of features.npy
+      eoo_bits.npy        float32 [B, 180]     end-of-over bits (zero for a stream without has_eoo)
+      status_<field>.npy  float64 [B]          RxStatus of every stream (consumed, n_calls, n_valid, has_eoo, nin, sync, snr_dB, state)
+      rx_iq_sample.npy    float32 [k, N, 2]    received samples (re, im) of rx_iq_streams, a fixed sample of DUMP_IQ_STREAMS streams
+      rx_iq_streams.npy   float64 [k]"""
+    os.makedirs(d, exist_ok=True)
+    B = fo.shape[0]
+    nv = np.array([s.n_valid for s in st])
+    arrays = {}
+    for name, _ in type(st[0])._fields_:
+        arrays["status_" + name] = np.array([getattr(s, name) for s in st], dtype=np.float64)
+    has_eoo = np.array([s.has_eoo for s in st], dtype=bool)
+    arrays["eoo_bits"] = np.where(has_eoo[:, None], eoo.cpu().numpy(), 0.0).astype(np.float32)
+    iq_idx = np.sort(np.random.default_rng(7).choice(B, min(B, DUMP_IQ_STREAMS), replace=False))
+    arrays["rx_iq_streams"] = iq_idx.astype(np.float64)
+    arrays["rx_iq_sample"] = torch.view_as_real(rx[torch.as_tensor(iq_idx, device=rx.device)]).cpu().numpy().astype(np.float32)
+    used = sum(a.nbytes for a in arrays.values())
+    R, row = max(int(nv.max()), 1), fo.shape[2]
+    per_stream = R * row * 4 + 8
+    if B * per_stream <= DUMP_BUDGET_BYTES - used:
+        f_idx = np.arange(B)
+    else:
+        f_idx = np.sort(np.random.default_rng(11).choice(B, max(1, (DUMP_BUDGET_BYTES - used) // per_stream), replace=False))
+    f = fo[torch.as_tensor(f_idx, device=fo.device), :R].cpu().numpy()
+    f[np.arange(R)[None, :] >= nv[f_idx][:, None]] = 0.0
+    arrays["features"] = f.astype(np.float32)
+    arrays["feature_streams"] = f_idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {"dir": d, "files": sorted(n + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())), "feature_streams": len(f_idx)}
 
 
 def roofline_leg(eng, step, steps, B, T, value, world):

@@ -91,3 +91,42 @@ def test_oversubscribe_developer_mode_plan():
     with pytest.raises(SystemExit):
         bench.launch_plan(8, {}, 0, [], oversubscribe=0)
     assert bench.launch_plan(1, {}, 1, [], oversubscribe=0) == ("inprocess", None)
+
+
+def test_dump_outputs_writes_the_last_step_within_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` (CPU tensors standing in for the device buffers): float32 / float64 .npy files only, rows past n_valid and the EOO bits
+    of a stream without has_eoo written as zeroes (the C ABI leaves them undefined), every stream's features while they fit, a fixed seeded sample of
+    streams once they would not, and the same files for the same step."""
+    import numpy as np
+    import torch
+    from radae_amd.engine import RxStatus
+    B, cap, row = 6, 9, 432
+    g = torch.Generator().manual_seed(5)
+    fo = torch.randn((B, cap, row), generator=g)
+    eoo = torch.randn((B, 180), generator=g)
+    rx = torch.randn((B, 2000), dtype=torch.complex64, generator=g)
+    st = [RxStatus(consumed=2000, n_calls=20 + b, n_valid=b + 2, has_eoo=b % 2, nin=960, sync=1, snr_dB=3, state=2) for b in range(B)]
+    r = bench.dump_outputs(str(tmp_path / "a"), fo, st, eoo, rx)
+    load = lambda d, n: np.load(os.path.join(str(tmp_path), d, n + ".npy"))
+    f = load("a", "features")
+    assert f.dtype == np.float32 and f.shape == (B, B + 1, row) and r["feature_streams"] == B
+    for b in range(B):
+        assert np.array_equal(f[b, :b + 2], fo[b, :b + 2].numpy()) and not f[b, b + 2:].any()
+    e = load("a", "eoo_bits")
+    assert np.array_equal(e[1::2], eoo[1::2].numpy()) and not e[0::2].any()
+    assert np.array_equal(load("a", "status_n_valid"), np.arange(B) + 2.0) and load("a", "status_n_calls").dtype == np.float64
+    k = load("a", "rx_iq_streams").astype(int)
+    iq = load("a", "rx_iq_sample")
+    assert iq.dtype == np.float32 and iq.shape == (len(k), 2000, 2) and np.array_equal(iq[..., 0] + 1j * iq[..., 1], rx[k].numpy())
+    for name in r["files"]:
+        assert load("a", name[:-4]).dtype in (np.float32, np.float64)
+    assert r["bytes"] == sum(load("a", n[:-4]).nbytes for n in r["files"]) <= bench.DUMP_BUDGET_BYTES
+    # over the budget: a fixed sample of whole streams
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", r["bytes"] - 2 * (B + 1) * row * 4)
+    r2 = bench.dump_outputs(str(tmp_path / "b"), fo, st, eoo, rx)
+    r3 = bench.dump_outputs(str(tmp_path / "c"), fo, st, eoo, rx)
+    s = load("b", "feature_streams").astype(int)
+    assert 0 < r2["feature_streams"] == len(s) < B and r2["bytes"] <= bench.DUMP_BUDGET_BYTES
+    assert np.array_equal(load("b", "features"), f[s])
+    for name in r2["files"]:
+        assert np.array_equal(load("b", name[:-4]), load("c", name[:-4]))

@@ -1561,6 +1561,27 @@ def test_config4_sharding_two_ranks_on_one_device():
     assert job["job_last_step"]["decoded_frames"] > 0
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run times --steps steps once and runs none of the --full legs; --dump-outputs writes what its last timed step decoded: the
+    sha256 the line carries over every stream's valid feature rows is reproduced from the dumped files."""
+    import hashlib, json, subprocess, sys
+    d = str(tmp_path / "dump")
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--streams", "16", "--frames", "240", "--steps", "4", "--warmup", "1", "--dump-outputs", d],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 4 and len(line["timed_region_s_repeats"]) == 1 and abs(line["ms_per_step"] - 1e3 * line["timed_region_s"] / 4) < 1e-9
+    assert not {"roofline", "parity_sample", "config2", "cpu_baseline", "cpu_baseline_allcores"} & set(line)
+    load = lambda n: np.load(os.path.join(d, n + ".npy"))
+    f, nv = load("features"), load("status_n_valid").astype(int)
+    assert line["dump_outputs"]["feature_streams"] == 16 and f.dtype == np.float32 and f.shape[0] == 16 and nv.max() > 0
+    dig = hashlib.sha256()
+    for b in range(16):
+        dig.update(np.ascontiguousarray(f[b, :nv[b]]).tobytes())
+    assert dig.hexdigest() == line["last_step_features_sha256_rank0"]
+    assert load("rx_iq_sample").shape[1:] == (8000 + 20 * 960 + 1152 + 1152, 2)
+
+
 def test_python_cli_filters_like_the_reference_tools(golden, tmp_path):
     """`python -m radae_amd.cli txe | rxe` in place of `python3 radae_txe.py | radae_rxe.py` (radae_txe.py:146-180, radae_rxe.py:332-371), three of the reference's pipelines:
     (i) ctest radae_eoo_data_py (CMakeLists.txt:578-583): features -> txe --eoo_data_test -> rxe --eoo_data_test prints the BER line and PASS, eoo_tx.f32 is written;

@@ -12,10 +12,10 @@ the FIRST variant (the baseline), the PAIRED per-round difference: its median, i
 A variant is a library (`name=path/to/lib.so`, loaded through $RADE_LIBRADEHIP), optionally with environment switches (`name=path.so,VAR=value,...`;
 `name=,VAR=value` = the default library with a switch) and a command prefix (`name=,VAR=value,@taskset -c 0,1`: everything after the `@` is put in front of the
 command -- note that the prefix may contain commas, so it must come last).  What is measured is chosen by --metric:
-    bench    bench.py --no-cpu-baseline --no-roofline --no-parity --steps S  ->  M frames/s (higher is better)          [default]
+    bench    bench.py --repeats 3 --steps S  ->  M frames/s, the median of three timed K-step loops (higher is better)  [default]
     rx512    tools/rx_only.py 8 2 512 -> ms of ONE receiver launch of 512 streams (lower is better)
     cycles   tools/stream_cycles.py -> mean per-stream cycles of the receiver launch (lower is better)
-    class:X  bench.py's roofline leg, per_class_ms_per_step[X] (e.g. class:gemm) -> ms (lower is better)
+    class:X  bench.py --full's roofline leg, per_class_ms_per_step[X] (e.g. class:gemm) -> ms (lower is better)
 
 usage: python tools/ab_bench.py --rounds 10 base=ab/base.so new=radae_amd/libradehip.so [--metric bench] [--steps 60] [--out profiles/r05_ab_x.txt] [-- extra bench args]
 """
@@ -41,13 +41,13 @@ def run_one(metric, lib, envs, steps, extra, prefix=()):
         env["RADE_LIBRADEHIP"] = lib if os.path.isabs(lib) else os.path.join(R, lib)
     env.update(envs)
     if metric == "bench":
-        cmd = list(prefix) + [sys.executable, os.path.join(R, "bench.py"), "--no-cpu-baseline", "--no-roofline", "--no-parity", "--steps", str(steps)] + extra
+        cmd = list(prefix) + [sys.executable, os.path.join(R, "bench.py"), "--repeats", "3", "--steps", str(steps)] + extra
         out = subprocess.run(cmd, env=env, capture_output=True, text=True).stdout
         d = json.loads(out.strip().splitlines()[-1])
         run_one.last_host = d.get("host")
         return d["value"] / 1e6
     if metric.startswith("class:"):
-        cmd = [sys.executable, os.path.join(R, "bench.py"), "--no-cpu-baseline", "--no-parity", "--steps", str(steps)] + extra
+        cmd = [sys.executable, os.path.join(R, "bench.py"), "--full", "--no-cpu-baseline", "--no-parity", "--steps", str(steps)] + extra
         out = subprocess.run(cmd, env=env, capture_output=True, text=True).stdout
         d = json.loads(out.strip().splitlines()[-1])
         return float(d["roofline"]["per_class_ms_per_step"][metric.split(":", 1)[1]])

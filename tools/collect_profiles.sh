@@ -8,14 +8,14 @@ TAG=${1:-r06}
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$TAG; rm -rf $O; mkdir -p $O
-# 1. the plain bench line (un-profiled) that the roofline block is quoted from
-python $R/bench.py --steps 100 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err
+# 1. the bench line with --full (un-profiled) that the roofline block is quoted from
+python $R/bench.py --steps 100 --warmup 5 --full > $O/bench_line.json 2> $O/bench_line.err
 # 2. rocprofv3 --kernel-trace --stats of the same command (shorter: the trace of 100 steps is large)
 #    --pipeline 1: kernel durations with one batch in flight, which is how bench.py's roofline leg times them (HIP events); the
 #    second pass is the default command (two batches in flight: a launch's duration then includes CUs shared with the other batch)
-CMD="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-parity --pipeline 1"
+CMD="python $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-parity --pipeline 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $CMD > $O/bench_under_rocprof.json 2> $O/stats.err
-CMD="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-roofline"
+CMD="python $R/bench.py --steps 20 --warmup 3 --repeats 3"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_pipe -o bench -- $CMD > $O/bench_pipelined_under_rocprof.json 2> $O/stats_pipe.err
 # 3. counters, one pass each
 CMD1="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-parity"
@@ -29,8 +29,8 @@ pass l2 TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum
 # 3b. the other configurations and variants (plain lines, no profiler): configs[1] alone, other pipeline depths, the two-call channel, configs 1 and 5 rates,
 #     the C host, the single-stream ABI, rocprofv3 stats of the single-stream step kernels
 python $R/bench.py --config 2 > $O/bench_config2.json 2> $O/bench_config2.err
-for p in 1 2 4; do python $R/bench.py --steps 60 --pipeline $p --no-cpu-baseline --no-parity --no-roofline > $O/bench_p$p.json 2> /dev/null; done
-python $R/bench.py --steps 60 --two-pass-channel --no-cpu-baseline --no-parity --no-roofline > $O/bench_two_pass_channel.json 2> /dev/null
+for p in 1 2 4; do python $R/bench.py --steps 60 --repeats 3 --pipeline $p > $O/bench_p$p.json 2> /dev/null; done
+python $R/bench.py --steps 60 --repeats 3 --two-pass-channel > $O/bench_two_pass_channel.json 2> /dev/null
 python $R/tools/config_rates.py > $O/config_rates.txt 2>&1; cp $R/gpurun_out/config_rates.json $O/ 2>/dev/null
 (cd $R && ./hosts/rade_multi_bench --gpus 1 --steps 100 --warmup 420 > $O/c_host_pipeline3.json 2> /dev/null)    # (the warm-up is the 1.5 s of pre-warm bench.py does)
 python $R/tools/single_stream_latency.py > $O/single_stream_latency.txt 2>&1

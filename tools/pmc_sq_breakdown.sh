@@ -5,7 +5,9 @@ rocprofv3() { timeout -k 10 ${RP_TIMEOUT:-420} "$(which rocprofv3)" "$@"; }
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/sq; rm -rf $O; mkdir -p $O
-CMD="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline"
+# a plain bench run: the sums cover the bench steps' launches only.  Summaries made before bench.py had --full (profiles/r06_* and older) also count
+# the 4-stream receiver launch of its parity replay; `--full --no-cpu-baseline --no-roofline` reproduces that command
+CMD="python $R/bench.py --steps 1 --warmup 1 --repeats 3"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM --output-format csv -d $O/p1 -o pmc -- $CMD > /dev/null 2> $O/p1.err
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_SCA --output-format csv -d $O/p2 -o pmc -- $CMD > /dev/null 2> $O/p2.err
 python - <<PY
