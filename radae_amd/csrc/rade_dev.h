@@ -155,15 +155,6 @@ typedef struct {
     const float *xin; int Kin; const float *Wp;     /* rd_launch_encf_dense1 only: float32 input rows [B][T][Kin], rd_pack_weights copy of dense_1 */
 } rd_encf_args;
 int rd_launch_encf_gemm(const rd_encf_args *a, rd_stream_t s);
-/* conv_l (2 x cin -> 96 columns at column cin of xf, taps dil steps apart, tanh) and the product over the cin + 96 columns that then exist (the next GRU's input
- * projection: Ng = 192, one-plane weights; z_dense: Ng = 80, two planes) in one launch; y float32 rows */
-typedef struct {
-    unsigned short *xf; int NQ; int B, T, cin, dil;
-    const unsigned short *Wc; const float *Wc_scale, *Wc_bias;
-    const unsigned short *Wg; const float *Wg_scale, *Wg_bias; int Ng, g_act;
-    float *y; long y_sb, y_st;
-} rd_encf_fused_args;
-int rd_launch_encf_fused(const rd_encf_fused_args *a, rd_stream_t s);
 int rd_launch_encf_dense1(const rd_encf_args *a, rd_stream_t s);
 /* conv history between calls: dir 0 = the float32 history rows (x32 + b * x32_sb, 2 x RD_ENC_W) -> the history tile; dir 1 = steps T - 2, T - 1 -> history tile and float32 rows */
 int rd_launch_encf_hist(unsigned short *xf, int NQ, float *x32, long x32_sb, int B, int T, int dir, rd_stream_t s);
@@ -227,7 +218,6 @@ typedef struct {
     float *features_out; long feat_stride;               /* [B][cap][432] */
     int feat_cap;                                        /* valid modem frames features_out holds per stream: a stream stops making calls once it has produced that many */
     int bypass_dec;                                      /* radae_rxe.py --bypass_dec (:300-302, :315): rows of features_out are the 240 latents of a valid modem frame, no decoder, no UW accounting */
-    const unsigned short *corr16;                        /* rd_corr16_table_fill(): [5][10][2][64][8] binary16 (the one-stage correlator: -DRX2_ONE_STAGE builds) */
     const unsigned short *corrq16, *corra16;             /* rd_corrq16_table_fill() [2][10][2][64][8] / rd_corra16_table_fill() [5][2][64][8]: the two-stage pilot correlator */
     float *zrows;                                        /* [B][dec_rows][80] */
     float *dtcache;                                      /* [B][960][40] |Dt2| surface of the previous detect_pilots call */
@@ -244,7 +234,7 @@ typedef struct {
 } rd_sync_args;
 int rd_launch_rx_sync(const rd_sync_args *a, rd_stream_t s);
 /* once per device before the first launch (rade_batch_open): raises the kernel's dynamic-LDS limit; returns the bytes to launch with, < 0 on error */
-int rd_rx_sync_prepare(int solo);
+int rd_rx_sync_prepare(void);
 
 /* complex_bpf.bpf (dsp.py:63-102) over n samples of every stream in one pass (rade_rx.hip: k_bpf_chain + k_bpf_fir [+ k_bpf_advance]): the receiver's
  * input filter ahead of the receiver launches of an invocation, and the transmitter's optional output filter (radae_txe.py:74-83).  Streams are cut into

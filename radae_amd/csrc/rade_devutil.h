@@ -70,9 +70,6 @@ __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y
 // e^{-j angle(c)} = conj(c)/|c| (np.exp(-1j*np.angle(c)) without atan2 / sincos); angle(0) = 0
 __device__ __forceinline__ float2 unit_conj(float2 c)
 {
-#ifdef RD_NO_UNITCONJ
-    { const float ang = atan2f(c.y, c.x); float sn, cs; sincosf(-ang, &sn, &cs); return make_float2(cs, sn); }
-#endif
     const float n2 = c.x * c.x + c.y * c.y;
     if (n2 == 0.0f) return make_float2(1.0f, 0.0f);
     const float inv = 1.0f / sqrtf(n2);
@@ -81,13 +78,9 @@ __device__ __forceinline__ float2 unit_conj(float2 c)
 // (cos, sin) of a double angle: reduced to [-pi, pi] in double, evaluated in float (the results are used as float32)
 __device__ __forceinline__ float2 cis_reduced(double ang)
 {
-#ifdef RD_NO_CIS
-    double sd, cd; sincos(ang, &sd, &cd); return make_float2((float)cd, (float)sd);
-#else
     const double r = ang - 6.283185307179586476925 * rint(ang * 0.15915494309189533577);
     float sn, cs; sincosf((float)r, &sn, &cs);
     return make_float2(cs, sn);
-#endif
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 // thread index through an opaque asm: inside the receiver's per-call loop this keeps the compiler from hoisting every

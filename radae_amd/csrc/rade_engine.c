@@ -76,7 +76,7 @@ struct rade_batch {
     int B, max_tx_mf, device, flags, trace_cap, Tcap;
     int R, dec_rows;                      /* do_radae_rx calls per stream per sync launch; 3R decoder slots */
     int unsync_off_after;                 /* int(disable_unsync * Fs / Nmf) or -1 */
-    unsigned short *corr16, *corrq16, *corra16, *wfwd16, *bpf16; double *vm; int rx_lds, rx_census;   /* dynamic LDS of a receiver launch; phase mask of the -DRX2_CENSUS developer build */
+    unsigned short *corrq16, *corra16, *wfwd16, *bpf16; double *vm; int rx_lds, rx_census;   /* dynamic LDS of a receiver launch; phase mask of the -DRX2_CENSUS developer build */
     int feat_in, enc_kpad, bottleneck1;   /* 84 (model19: 4x21) or 80 (model05/bbfm: 4x20); tanh on z when bottleneck 1 */
     float *dec2_x, *dec2_gi, *dec2_hbuf, *dec2_h[5];   /* stand-alone decoder (rade_batch_decode) */
     rd_tables *d_tab;
@@ -86,7 +86,7 @@ struct rade_batch {
     unsigned short *dec_whq[5]; float *dec_whs[5];      /* decoder W_hh as matrix-core fragments (int8-exact) + row scales; NULL when the blob's recurrent weights are not int8 x scale */
     /* transmit side */
     float *enc_xin, *enc_x, *enc_gi, *enc_h[5], *enc_z, *eoo, *eoo_bits;
-    unsigned short *enc_xf; int enc_nq, enc_unfused, enc_seq_taps, enc_no_pair;
+    unsigned short *enc_xf; int enc_nq, enc_seq_taps, enc_no_pair;
     int enc_hist_frag;                   /* the history tile of enc_xf holds what enc_x's two float32 history rows hold (set by a fragment pass, cleared by a reset or a float32-row pass) */   /* the concat buffer as matrix-core operand fragments (rade_enc.hip: [B][enc_nq][RD_EF_TILE] binary16), engines with enough rows for the batched GEMMs only */
     /* optional Tx band-pass filter + clip (RADE_BATCH_TX_BPF; radae_txe.py:74-83): filter state per stream, its initial value, the modulator's raw output, block phases */
     int bypass_dec;                          /* RADE_BATCH_BYPASS_DEC */
@@ -108,8 +108,6 @@ struct rade_batch {
     /* optional: absolute start / end of every profiled launch relative to a caller-supplied event (launches of several engines on one time axis) */
     hipEvent_t prof_ref; int iv_n; int iv_cls[RADE_PROF_MAXIV]; float iv_t0[RADE_PROF_MAXIV], iv_t1[RADE_PROF_MAXIV];
     long rx_calls_search, rx_calls_sync;
-    /* encoder in two time chunks on two HIP streams (encode_core): the side stream and the events that order the chunks */
-    int enc_chunks; hipStream_t enc_side; hipEvent_t ev_fork, ev_join, ev_scan[5];
     hipEvent_t ev_block;             /* the event rade_batch_rx sleeps on (sleep_until_event) when the host has fewer CPUs than engines (sync_blocking_now) */
     long n_sync_block, n_sync_spin;  /* waits of either kind so far (rade_batch_sync_counts) */
     double wait_est_us;              /* how long the sleeping wait of rade_batch_rx lasted lately (running average): the next one sleeps through most of that before it polls */
@@ -156,7 +154,7 @@ static int upload_lin(dev_lin *d, const float *w, const float *b, const float *r
         unsigned short *p16 = malloc(sizeof(unsigned short) * n16);
         float *sc = calloc((size_t)((N + 31) / 32) * 32, sizeof(float));
         long nq = -1;
-        if (p16 && sc && row_scale && !getenv("RADE_NO_INT8_EXACT")) nq = rd_pack_weights_q16(wsrc, row_scale, N, Kpad, p16, sc);
+        if (p16 && sc && row_scale) nq = rd_pack_weights_q16(wsrc, row_scale, N, Kpad, p16, sc);
         if (nq > 0) {
             d->wp16 = dev_upload(p16, sizeof(unsigned short) * nq);
             d->wscale16 = dev_upload(sc, sizeof(float) * (size_t)((N + 31) / 32) * 32);
@@ -175,7 +173,7 @@ static int upload_lin(dev_lin *d, const float *w, const float *b, const float *r
         unsigned short *pa = malloc(sizeof(unsigned short) * na);
         float *sc = malloc(sizeof(float) * (size_t)((N + 15) / 16) * 16);
         long nq = -1;
-        if (pa && sc && row_scale && !getenv("RADE_NO_INT8_EXACT")) nq = rd_pack_weights_q16_a16(wsrc, row_scale, N, Kpad, pa, sc);
+        if (pa && sc && row_scale) nq = rd_pack_weights_q16_a16(wsrc, row_scale, N, Kpad, pa, sc);
         if (nq > 0) {                      /* int8 in the blob: the integers themselves in ONE binary16 plane (exact), scales apart: half the bytes to stream */
             d->wa16 = dev_upload(pa, sizeof(unsigned short) * nq);
             d->wscale = dev_upload(sc, sizeof(float) * (size_t)((N + 15) / 16) * 16);
@@ -263,11 +261,7 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     rd_tables *tab = malloc(sizeof *tab);
     rd_tables_fill(tab);
     h->d_tab = dev_upload(tab, sizeof *tab);
-    {
-        unsigned short *c16 = malloc(sizeof(unsigned short) * 5 * 10 * 2 * 64 * 8);
-        if (c16) { rd_corr16_table_fill(tab, c16); h->corr16 = dev_upload(c16, sizeof(unsigned short) * 5 * 10 * 2 * 64 * 8); free(c16); }
-    }
-    {   /* the same correlator in two stages: 16 polynomial moments, then their expansion to the 40 frequencies (rade_host.c) */
+    {   /* the pilot correlator in two stages: 16 polynomial moments, then their expansion to the 40 frequencies (rade_host.c) */
         unsigned short *q16 = malloc(sizeof(unsigned short) * 2 * 10 * 2 * 64 * 8), *a16 = malloc(sizeof(unsigned short) * 5 * 2 * 64 * 8);
         if (q16 && a16) {
             rd_corrq16_table_fill(tab, q16); h->corrq16 = dev_upload(q16, sizeof(unsigned short) * 2 * 10 * 2 * 64 * 8);
@@ -290,11 +284,10 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
         h->vm = dev_upload(vm, sizeof vm);
     }
     /* the receiver kernel asks for more dynamic LDS than the 64 KB default: raised here, once per engine and before any launch (the
-     * attribute belongs to the device's code object; setting it again from another engine's thread is harmless).  RADE_RX2_SOLO=1
-     * (developer switch) asks for more than half a CU's LDS, i.e. one workgroup per CU. */
-    h->rx_lds = rd_rx_sync_prepare(getenv("RADE_RX2_SOLO") != NULL);
+     * attribute belongs to the device's code object; setting it again from another engine's thread is harmless) */
+    h->rx_lds = rd_rx_sync_prepare();
     h->rx_census = getenv("RADE_RX2_CENSUS") ? atoi(getenv("RADE_RX2_CENSUS")) : 0;      /* only acts in -DRX2_CENSUS builds */
-    if (!h->d_tab || !h->corr16 || !h->corrq16 || !h->corra16 || !h->vm || !h->wfwd16 || !h->bpf16 || h->rx_lds <= 0) goto fail;
+    if (!h->d_tab || !h->corrq16 || !h->corra16 || !h->vm || !h->wfwd16 || !h->bpf16 || h->rx_lds <= 0) goto fail;
 
     int err = 0;
     h->feat_in = m.enc_dense1.n_in; h->enc_kpad = (h->feat_in + 15) & ~15; h->bottleneck1 = (cfg->flags & RADE_BATCH_BOTTLENECK1) != 0;
@@ -312,7 +305,7 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
         h->enc_bhh[l] = dev_upload(m.enc_gru[l].b_hh, sizeof(float) * 192);
         h->dec_whh[l] = dev_upload(m.dec_gru[l].w_hh, sizeof(float) * 288 * 96);
         h->dec_bhh[l] = dev_upload(m.dec_gru[l].b_hh, sizeof(float) * 288);
-        if (m.dec_gru[l].s_hh && !getenv("RADE_NO_SCAN_MFMA")) {
+        if (m.dec_gru[l].s_hh) {
             unsigned short *pa = malloc(sizeof(unsigned short) * rd_packed16a_size(288, 96)); float *scl = malloc(sizeof(float) * 288);
             const long nq = (pa && scl) ? rd_pack_weights_q16_a16(m.dec_gru[l].w_hh, m.dec_gru[l].s_hh, 288, 96, pa, scl) : -1;
             if (nq > 0) { h->dec_whq[l] = dev_upload(pa, sizeof(unsigned short) * nq); h->dec_whs[l] = dev_upload(scl, sizeof(float) * 288); }
@@ -326,10 +319,6 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     h->enc_x = dev_zeros(sizeof(float) * B * (2 + T) * RD_ENC_W);
     h->enc_gi = dev_zeros(sizeof(float) * B * T * 192);
     h->enc_nq = 1 + (h->Tcap + 31) / 32;
-    /* conv_l and the product behind it as separate launches, unless $RADE_ENCF_FUSED (read per engine) asks for k_encf_fused: 7 launches instead of 12 and 6 % less GEMM time
-     * alone, but 4-wavefront workgroups with 12 KB of LDS that find fewer places beside the receivers: -1.1 % +- 1.2 (124 registers) / -2.8 % +- 1.2 (152) frames/s in the
-     * pipelined bench against the separate launches (profiles/r05_ab_enc_fragments.txt) */
-    h->enc_unfused = getenv("RADE_ENCF_FUSED") == NULL;
     h->enc_seq_taps = getenv("RADE_ENCF_SEQ_TAPS") != NULL;    /* developer switches, read per engine (rade_enc.hip: k_encf_gemm) */
     h->enc_no_pair = getenv("RADE_ENCF_NO_PAIR") != NULL;
     if (B * T > 16384 && !getenv("RADE_ENC_ROWS")) {       /* $RADE_ENC_ROWS: the float32-row path (k_gemm16p) for every size: A/B and the equality test */
@@ -393,13 +382,6 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     if (!h->d_lcg_seeds) goto fail;
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) CHK(hipEventCreate(&h->prof_ev[i]));
     CHK(hipEventCreateWithFlags(&h->ev_block, hipEventBlockingSync | hipEventDisableTiming));
-    h->enc_chunks = getenv("RADE_ENC_CHUNKS") ? atoi(getenv("RADE_ENC_CHUNKS")) : 1;     /* measured (profiles/r03_tx_side_ab.json): 2 chunks gain 3 % with one batch in flight, lose 7 % with two (the default) */
-    if (h->enc_chunks != 1) {
-        h->enc_chunks = 2;
-        CHK(hipStreamCreateWithFlags(&h->enc_side, hipStreamNonBlocking));
-        CHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming)); CHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        for (int l = 0; l < 5; l++) CHK(hipEventCreateWithFlags(&h->ev_scan[l], hipEventDisableTiming));
-    }
     rade_batch_rx_reset(h);
     if (rd_launch_eoo_build(h->d_tab, NULL, h->eoo, h->B, NULL)) goto fail;
     CHK(hipDeviceSynchronize());
@@ -430,7 +412,7 @@ void rade_batch_close(rade_batch *h)
     if (!h) return;
     ON_DEV(h);
     void *bufs[] = { h->d_tab, h->enc_xin, h->enc_x, h->enc_xf, h->enc_gi, h->enc_z, h->eoo, h->eoo_bits, h->chan_scratch, h->rx_st, h->rx_round, h->rx_avail,
-                     h->rx_progress /* + rx_acc, rx_status */, h->wg_cycles, h->zrows, h->dec_x, h->dec_gi, h->dec_hbuf, h->feat84, h->trace, h->trace_z, h->d_lcg_seeds, h->dtcache, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->rx_filt, h->bpf_chain, h->bpf16, h->tx_bpf, h->tx_bpf_init, h->tx_raw, h->tx_chain, h->eoo_filt, h->corr16, h->corrq16, h->corra16, h->vm, h->chan_mp, h->wfwd16 };
+                     h->rx_progress /* + rx_acc, rx_status */, h->wg_cycles, h->zrows, h->dec_x, h->dec_gi, h->dec_hbuf, h->feat84, h->trace, h->trace_z, h->d_lcg_seeds, h->dtcache, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->rx_filt, h->bpf_chain, h->bpf16, h->tx_bpf, h->tx_bpf_init, h->tx_raw, h->tx_chain, h->eoo_filt, h->corrq16, h->corra16, h->vm, h->chan_mp, h->wfwd16 };
     for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; i++) if (bufs[i]) hipFree(bufs[i]);
     free_lin(&h->enc_dense1); free_lin(&h->enc_zdense); free_lin(&h->dec_dense1); free_lin(&h->dec_output);
     for (int l = 0; l < 5; l++) {
@@ -441,10 +423,6 @@ void rade_batch_close(rade_batch *h)
     if (h->h_small) hipHostFree(h->h_small);
     if (h->ev_block) hipEventDestroy(h->ev_block);
     __atomic_sub_fetch(&g_engines_open, 1, __ATOMIC_RELAXED);
-    if (h->enc_side) hipStreamDestroy(h->enc_side);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->ev_join) hipEventDestroy(h->ev_join);
-    for (int l = 0; l < 5; l++) if (h->ev_scan[l]) hipEventDestroy(h->ev_scan[l]);
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) if (h->prof_ev[i]) hipEventDestroy(h->prof_ev[i]);
     free(h->lcg_seeds);
     free(h);
@@ -518,14 +496,13 @@ static int gemm(rade_batch *hh, const dev_lin *w, const float *a1, long a1_sb, l
 }
 
 /* ---- CoreEncoderStatefull.forward over T steps for all streams (radae_base.py:260-286); xin = [B][T][enc_kpad] ----
- * Layer by layer over all B x T rows: the feed-forward pieces are GEMMs, the five W_hh recurrences serial scans (one workgroup of four
- * wavefronts per stream: latency-bound, most of the chip idle).  With enough rows the T steps are cut into two time chunks that run
- * the same layer sequence on two HIP streams, the second chunk one recurrence behind the first (it needs that layer's GRU state and
- * the conv history rows the first chunk leaves): chunk 0's GEMMs of layer l+1 then fill the chip while chunk 1's scan of layer l
- * waits on its serial chain, and vice versa.  No extra passes, same kernels, same arithmetic per row: results are bit-identical to
- * the one-chunk order ($RADE_ENC_CHUNKS=1). */
+ * Layer by layer over all B x T rows, in one pass on the caller's stream: the feed-forward pieces are GEMMs, the five W_hh recurrences
+ * serial scans (one workgroup of four wavefronts per stream: latency-bound, most of the chip idle).  Measured and not kept
+ * (profiles/r03_tx_side_ab.json): the steps cut into two time chunks on two HIP streams, one recurrence apart, gain 3 % with one batch
+ * in flight and lose 7 % with two. */
 /* The same pass with the concat buffer kept as matrix-core operand fragments (rade_enc.hip): taken when the call has enough rows for the batched GEMMs
- * (the float32-row path below serves short calls with k_gemm_splitk); the conv history crosses calls in enc_x's two float32 rows either way. */
+ * (the float32-row path below serves short calls with k_gemm_splitk); the conv history crosses calls in enc_x's two float32 rows either way.  conv_l and
+ * the product behind it are separate launches: one fused launch was slower in the pipelined bench. */
 static int encf_gemm(rade_batch *h, const dev_lin *w, int K1, int K0, int dil, float *y, long y_sb, long y_st, int ycol, int T, int act, void *stream)
 {
     rd_encf_args g;
@@ -554,30 +531,14 @@ static int encode_core_frag(rade_batch *h, int T, float *z, void *stream)
         g.xin = h->enc_xin; g.Kin = h->enc_kpad; g.Wp = h->enc_dense1.wp;
         PROF_BEGIN(h, stream); e |= rd_launch_encf_dense1(&g, stream); PROF_END(h, stream, RADE_PROF_GEMM, 2.0 * (double)B * T * h->enc_kpad * 64);
     }
-    const int unfused = h->enc_unfused;
     e |= encf_gemm(h, &h->enc_gin[0], ENC_IN[0], 0, 0, h->enc_gi, (long)T * 192, 192, 0, T, 0, stream);
     for (int l = 0; l < 5 && !e; l++) {
         const int in = ENC_IN[l], cin = in + 64;
         rd_scan_args s = { h->enc_gi, (long)T * 192, 192, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], NULL, 0, 0, NULL, 0, NULL, B, T, 64, h->enc_xf, h->enc_nq, in };
         PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * 192 * 64);
-        const dev_lin *nx = l < 4 ? &h->enc_gin[l + 1] : &h->enc_zdense;          /* what reads the conv's output next */
-        if (unfused) {
-            e |= encf_gemm(h, &h->enc_conv[l], cin, cin, ENC_DIL[l], NULL, 0, 0, cin, T, 1, stream);
-            if (l < 4) e |= encf_gemm(h, nx, ENC_IN[l + 1], 0, 0, h->enc_gi, (long)T * 192, 192, 0, T, 0, stream);
-            else e |= encf_gemm(h, nx, 864, 0, 0, z, (long)T * RD_LATENT, RD_LATENT, 0, T, h->bottleneck1 ? 1 : 0, stream);
-            continue;
-        }
-        rd_encf_fused_args f;
-        memset(&f, 0, sizeof f);
-        f.xf = h->enc_xf; f.NQ = h->enc_nq; f.B = B; f.T = T; f.cin = cin; f.dil = ENC_DIL[l];
-        f.Wc = h->enc_conv[l].wp16; f.Wc_scale = h->enc_conv[l].wscale16; f.Wc_bias = h->enc_conv[l].bias;
-        f.Wg = nx->wp16; f.Wg_scale = nx->wscale16; f.Wg_bias = nx->bias; f.Ng = nx->N;
-        if (l < 4) { f.y = h->enc_gi; f.y_sb = (long)T * 192; f.y_st = 192; }
-        else { f.y = z; f.y_sb = (long)T * RD_LATENT; f.y_st = RD_LATENT; f.g_act = h->bottleneck1 ? 1 : 0; }
-        if (h->enc_conv[l].K != 2 * cin || nx->K != cin + 96 || !f.Wc || !f.Wg) { fprintf(stderr, "rade: internal GEMM shape error (fused layer %d)\n", l); return -1; }
-        PROF_BEGIN(h, stream);
-        e |= rd_launch_encf_fused(&f, stream);
-        PROF_END(h, stream, RADE_PROF_GEMM, 2.0 * (double)B * T * ((double)2 * cin * 96 + (double)(cin + 96) * nx->N));
+        e |= encf_gemm(h, &h->enc_conv[l], cin, cin, ENC_DIL[l], NULL, 0, 0, cin, T, 1, stream);
+        if (l < 4) e |= encf_gemm(h, &h->enc_gin[l + 1], ENC_IN[l + 1], 0, 0, h->enc_gi, (long)T * 192, 192, 0, T, 0, stream);
+        else e |= encf_gemm(h, &h->enc_zdense, 864, 0, 0, z, (long)T * RD_LATENT, RD_LATENT, 0, T, h->bottleneck1 ? 1 : 0, stream);
     }
     e |= rd_launch_encf_hist(h->enc_xf, h->enc_nq, h->enc_x, (long)(2 + h->Tcap) * RD_ENC_W, B, T, 1, stream);
     h->enc_hist_frag = !e;
@@ -587,39 +548,24 @@ static int encode_core_frag(rade_batch *h, int T, float *z, void *stream)
 static int encode_core(rade_batch *h, int T, float *z, void *stream)
 {
     const int B = h->B, W = RD_ENC_W;
-    if (h->enc_xf && (long)B * T > 16384 && h->enc_chunks != 2) return encode_core_frag(h, T, z, stream);
+    if (h->enc_xf && (long)B * T > 16384) return encode_core_frag(h, T, z, stream);
     h->enc_hist_frag = 0;
     const long xsb = (long)(2 + h->Tcap) * W;
     float *x0 = h->enc_x + 2 * W;              /* time row 0 of each stream; rows -2,-1 hold the conv history */
-    hipStream_t S[2] = { (hipStream_t)stream, h->enc_side };
-    /* small jobs (single-stream ABI, tests with a handful of rows) stay on one stream: nothing to overlap, and rade_tx() captures its
-     * launches into a hipGraph on the caller's stream */
-    const int nC = (h->enc_chunks == 2 && (long)B * T > 16384 && T >= 16) ? 2 : 1;
-    const int tsplit = nC == 2 ? ((T / 2 + 3) & ~3) : T;
-    const int t0[2] = { 0, tsplit }, tn[2] = { tsplit, T - tsplit };
     int e = 0;
-    if (nC == 2) { if (hipEventRecord(h->ev_fork, S[0]) != hipSuccess || hipStreamWaitEvent(S[1], h->ev_fork, 0) != hipSuccess) return -1; }
     /* dense1 reads raw features: the one encoder operand that is not tanh-bounded, so it stays on the f32 matrix cores
      * (the 2^8-scaled binary16 planes of the split-f16 kernels overflow beyond +-255.9) */
     dev_lin d1 = h->enc_dense1; d1.wp16 = NULL; d1.wscale16 = NULL;
-    for (int c = 0; c < nC; c++)
-        e |= gemm(h, &d1, h->enc_xin + (long)t0[c] * h->enc_kpad, (long)T * h->enc_kpad, h->enc_kpad, h->enc_kpad, NULL, 0, 0, 0, NULL, NULL, x0 + (long)t0[c] * W, xsb, W, B, tn[c], 1, S[c]);
+    e |= gemm(h, &d1, h->enc_xin, (long)T * h->enc_kpad, h->enc_kpad, h->enc_kpad, NULL, 0, 0, 0, NULL, NULL, x0, xsb, W, B, T, 1, stream);
     for (int l = 0; l < 5 && !e; l++) {
         const int in = ENC_IN[l], cin = in + 64;
-        for (int c = 0; c < nC && !e; c++) {
-            float *x = x0 + (long)t0[c] * W, *gi = h->enc_gi + (long)t0[c] * 192;
-            e |= gemm(h, &h->enc_gin[l], x, xsb, W, in, NULL, 0, 0, 0, NULL, NULL, gi, (long)T * 192, 192, B, tn[c], 0, S[c]);
-            if (c == 1 && hipStreamWaitEvent(S[1], h->ev_scan[l], 0) != hipSuccess) return -1;      /* GRU state + history rows of chunk 0 */
-            rd_scan_args s = { gi, (long)T * 192, 192, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], x + in, xsb, W, NULL, 0, NULL, B, tn[c], 64 };
-            PROF_BEGIN(h, S[c]); e |= rd_launch_gru_scan(&s, S[c]); PROF_END(h, S[c], RADE_PROF_SCAN, 2.0 * B * tn[c] * 192 * 64);
-            if (c == 0 && nC == 2 && hipEventRecord(h->ev_scan[l], S[0]) != hipSuccess) return -1;
-            e |= gemm(h, &h->enc_conv[l], x, xsb, W, cin, x - (long)ENC_DIL[l] * W, xsb, W, cin, NULL, NULL, x + cin, xsb, W, B, tn[c], 1, S[c]);
-        }
+        e |= gemm(h, &h->enc_gin[l], x0, xsb, W, in, NULL, 0, 0, 0, NULL, NULL, h->enc_gi, (long)T * 192, 192, B, T, 0, stream);
+        rd_scan_args s = { h->enc_gi, (long)T * 192, 192, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], x0 + in, xsb, W, NULL, 0, NULL, B, T, 64 };
+        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * 192 * 64);
+        e |= gemm(h, &h->enc_conv[l], x0, xsb, W, cin, x0 - (long)ENC_DIL[l] * W, xsb, W, cin, NULL, NULL, x0 + cin, xsb, W, B, T, 1, stream);
     }
     /* bottleneck 1: z = tanh(z_dense) (radae_base.py:281-284); bottleneck 3: linear */
-    for (int c = 0; c < nC; c++)
-        e |= gemm(h, &h->enc_zdense, x0 + (long)t0[c] * W, xsb, W, 864, NULL, 0, 0, 0, NULL, NULL, z + (long)t0[c] * RD_LATENT, (long)T * RD_LATENT, RD_LATENT, B, tn[c], h->bottleneck1 ? 1 : 0, S[c]);
-    if (nC == 2) { if (hipEventRecord(h->ev_join, S[1]) != hipSuccess || hipStreamWaitEvent(S[0], h->ev_join, 0) != hipSuccess) return -1; }
+    e |= gemm(h, &h->enc_zdense, x0, xsb, W, 864, NULL, 0, 0, 0, NULL, NULL, z, (long)T * RD_LATENT, RD_LATENT, B, T, h->bottleneck1 ? 1 : 0, stream);
     e |= rd_launch_carry_rows(h->enc_x, B, h->Tcap, W, 2, T, NULL, stream);
     return e;
 }
@@ -938,7 +884,7 @@ int rade_batch_rx(rade_batch *h, const void *rx_dev, long rx_stride, const int *
     memset(&sa, 0, sizeof sa);
     sa.tab = h->d_tab; sa.st = h->rx_st; sa.round = h->rx_round; sa.rx = rx_dev; sa.rx_stride = rx_stride; sa.rxf = h->rx_filt; sa.rxf_stride = h->filt_cap; sa.bpf16 = h->bpf16; sa.bpf_chain = h->bpf_chain; sa.chain_stride = h->chain_stride; sa.avail = h->rx_avail; sa.acc = h->rx_acc;
     sa.max_calls = max_calls; sa.round_calls = h->R; sa.dec_rows = h->dec_rows; sa.unsync_off_after = h->unsync_off_after;
-    sa.corr16 = h->corr16; sa.corrq16 = h->corrq16; sa.corra16 = h->corra16; sa.zrows = h->zrows; sa.status = h->rx_status; sa.eoo_out = eoo_out_dev; sa.dtcache = h->dtcache;
+    sa.corrq16 = h->corrq16; sa.corra16 = h->corra16; sa.zrows = h->zrows; sa.status = h->rx_status; sa.eoo_out = eoo_out_dev; sa.dtcache = h->dtcache;
     sa.trace = h->trace; sa.trace_z = h->trace_z; sa.trace_cap = h->trace_cap; sa.progress = h->rx_progress; sa.wg_cycles = h->wg_cycles; sa.B = B; sa.vm = h->vm; sa.wfwd16 = h->wfwd16; sa.variant = h->rx_census << 8; sa.lds_bytes = h->rx_lds;
     fill_dec_args(h, &sa.dec); sa.features_out = features_out_dev; sa.feat_stride = feat_stride;
     sa.bypass_dec = h->bypass_dec;

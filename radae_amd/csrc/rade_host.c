@@ -456,25 +456,6 @@ long rd_pack_weights_q16_a16(const float *W, const float *row_scale, int N, int 
     return (long)nks * nct * 64 * 8;
 }
 
-/* check_pilots rows on the f16 matrix cores: the realified pilot table Pm[n = 2f + c', k = 2m + c] = {pr, pi; pi, -pr}[c'][c]
- * of p_w[m][f] (dsp.py:207-208 as a real GEMM), split in two binary16 planes and laid out as the A operands of
- * v_mfma_f32_16x16x32_f16: out[nt][s][plane][lane][j] = plane(2^12 Pm[16 nt + lane%16][32 s + 8 (lane/16) + j]) */
-void rd_corr16_table_fill(const rd_tables *T, unsigned short *out /* [5][10][2][64][8] */)
-{
-    for (int nt = 0; nt < 5; nt++)
-        for (int s = 0; s < 10; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int n = 16 * nt + (lane & 15), f = n >> 1, cp = n & 1;
-                    const int k = 32 * s + 8 * (lane >> 4) + j, m = k >> 1, c = k & 1;
-                    const float pr = T->p_w[m][f][0], pi = T->p_w[m][f][1];
-                    const float v = 4096.0f * (cp == 0 ? (c == 0 ? pr : pi) : (c == 0 ? pi : -pr));     /* 2^12: low plane stays normal */
-                    const unsigned short hi = f32_to_f16(v), lo = f32_to_f16(v - f16_to_f32(hi));
-                    unsigned short *o = out + ((((size_t)nt * 10 + s) * 2) * 64 + lane) * 8 + j;
-                    o[0] = hi; o[64 * 8] = lo;
-                }
-}
-
 /* ---- the pilot correlator in two stages (round 5) -------------------------------------------------------------------------------------------
  * p_w[m][f] = p[m] e^{j w_f m} for the 40 coarse frequencies |f| <= 50 Hz spans a window of 160 samples: the phase e^{j w_f (m - 79.5)} moves by at most
  * +-pi across it, i.e. as a function of x = (m - 79.5) / 80 it is band-limited to a time-bandwidth product of 2 and is reproduced to 1.7e-10 by its
@@ -483,8 +464,8 @@ void rd_corr16_table_fill(const rd_tables *T, unsigned short *out /* [5][10][2][
  * so Dt[t][f] = sum_m conj(rx[t + m]) p_w[m][f] = sum_r alpha[r][f] Mom_r[t] with the 16 "moments" Mom_r[t] = sum_m conj(rx[t + m]) s_r[m]: the big
  * product (K = 320 real) has 32 rows (two 16-row tiles) instead of 80 (five), and a second product with K = 32 expands the moments to the 40 frequencies.
  * On v_mfma_f32_16x16x32_f16: 2 x 10 x 3 + 5 x 5 = 85 matrix instructions per tile of 16 timings instead of 5 x 10 x 3 = 150.
- * rd_corrq16_table_fill: stage 1, the realified s_r (rows n' = 2 r + c', k = 2 m + c as in rd_corr16_table_fill), 2^12-scaled, two binary16 planes,
- *                        A-operand order: out[tile][s][plane][lane][j]
+ * rd_corrq16_table_fill: stage 1, the realified s_r (rows n' = 2 r + c', k = 2 m + c: {sr, si; si, -sr}[c'][c]), 2^12-scaled, two binary16 planes,
+ *                        A-operand order: out[tile][s][plane][lane][j] = plane(S[16 tile + lane % 16][32 s + 8 (lane / 16) + j])
  * rd_corra16_table_fill: stage 2, A2[n = 2 f + c''][n'] = {ar, -ai; ai, ar} of alpha[r][f], 2^10-scaled, two planes.  Its K axis is ordered the way
  *                        stage 1's accumulators lie in a lane (C layout of two 16-row tiles: lane group g holds rows 4 g .. 4 g + 3 of either tile), so that
  *                        the moments go from accumulator registers to B-operand registers without leaving the lane:

@@ -28,7 +28,6 @@ int rd_model_parse(const void *blob, size_t len, rd_model *m);
 void rd_model_free(rd_model *m);
 
 long rd_packed16_size(int N, int K);
-void rd_corr16_table_fill(const rd_tables *T, unsigned short *out);
 void rd_corrq16_table_fill(const rd_tables *T, unsigned short *out);     /* [2][10][2][64][8]: stage 1 of the two-stage pilot correlator (rade_host.c) */
 void rd_corra16_table_fill(const rd_tables *T, unsigned short *out);     /* [5][2][64][8]: stage 2 */
 double rd_corr_tables_check(const rd_tables *T);

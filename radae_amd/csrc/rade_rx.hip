@@ -2056,9 +2056,9 @@ extern "C" int rd_launch_rx_sync(const rd_sync_args *a, rd_stream_t s)
     return (int)hipGetLastError();
 }
 // dynamic LDS of the receiver kernel (above the 64 KB default): set once per device by rade_batch_open, before any launch
-extern "C" int rd_rx_sync_prepare(int solo)
+extern "C" int rd_rx_sync_prepare(void)
 {
-    const int l = solo ? 100 * 1024 : (int)sizeof(RxShared2);          // solo (developer switch): more than half the LDS = one workgroup per CU
+    const int l = (int)sizeof(RxShared2);
     if (hipFuncSetAttribute((const void *)k_rx_sync2, hipFuncAttributeMaxDynamicSharedMemorySize, l) != hipSuccess) return -1;
     return l;
 }

@@ -209,7 +209,7 @@ def test_two_stage_pilot_correlator_tables(lib, golden):
             g = lane >> 4
             for j in range(8):
                 A2[16 * tile + (lane & 15), (4 * g + j) if j < 4 else (16 + 4 * g + j - 4)] = (ta[tile, 0, lane, j] + ta[tile, 1, lane, j]) / 1024.0
-    # the product of the two real matrices is the realified p_w: rows (f, re | im), columns (m, re | im) as in rd_corr16_table_fill
+    # the product of the two real matrices is the realified p_w: rows (f, re | im) as stage 2 writes them, columns (m, re | im) as stage 1 reads the window
     pw = c["acq_p_w"].astype(np.complex128)                        # [m][f]
     P = np.zeros((80, 320)); P[0::2, 0::2] = pw.real.T; P[0::2, 1::2] = pw.imag.T; P[1::2, 0::2] = pw.imag.T; P[1::2, 1::2] = -pw.real.T
     assert np.abs(A2 @ Q1 - P).max() < 4e-7 * np.abs(P).max()
