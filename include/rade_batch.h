@@ -17,6 +17,7 @@
  *                          stream = the reference's batch-1 behaviour) + inference.py:263-284 (EOO / noise framing)
  *   rade_batch_rx          radae_rxe.py:171-330 (do_radae_rx) looped like radae_rxe.py:349-356 /
  *                          src/radae_rx.c:42-53, incl. rade_api.c:480-513 decoder + UW accounting
+ *   rade_batch_rx_ideal    radae.py:312-420, :590-657 (the ideal-timing receiver of RADAE.forward / RADAE.receiver, ber_test)
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -43,11 +44,17 @@ typedef struct rade_batch rade_batch;
  * never summed in this mode (sum_uw_errors sits behind the decoder), so a UW failure cannot end sync; everything else of do_radae_rx is unchanged. */
 #define RADE_BATCH_BYPASS_DEC 0x800
 
+/* The bottleneck-1 rate-Fs waveform (model05 numerology, radae.py:195-199, :545-548): rade_batch_tx, rade_batch_tx_latents and rade_batch_tx_channel send the pilots at
+ * unit gain and skip the tanh limiter, and rade_batch_rx_ideal scales coarse_mag without the bottleneck-3 factor.  Paths that cannot honour it fail instead of limiting:
+ * rade_batch_open with RADE_BATCH_TX_BPF, rade_open (rade_api.h: single-stream frame kernels), rade_batch_tx_eoo and rade_batch_channel with_eoo.
+ * Noise for this waveform: rade_sigma_from_EbNodB_bn1. */
+#define RADE_BATCH_TX_LINEAR 0x1000
+
 typedef struct {
     int n_streams;        /* B */
     int max_tx_mf;        /* largest n_mf a single rade_batch_tx call may carry */
     int device;           /* HIP device ordinal */
-    int flags;            /* RADE_FOFF_TEST from rade_api.h is honoured; RADE_BATCH_BOTTLENECK1: z = tanh(.) (model05, bbfm); RADE_BATCH_TX_BPF; RADE_BATCH_BYPASS_DEC */
+    int flags;            /* RADE_FOFF_TEST from rade_api.h is honoured; RADE_BATCH_BOTTLENECK1: z = tanh(.) (model05, bbfm); RADE_BATCH_TX_BPF; RADE_BATCH_BYPASS_DEC; RADE_BATCH_TX_LINEAR */
     int rx_trace_calls;   /* >0: keep a per-call trace of this many do_radae_rx calls per stream (tests) */
     float disable_unsync; /* test mode of radae_rxe.py --disable_unsync (:277-281, :337): after this many seconds in sync the receiver no longer
                            * drops back to search (pilot loss, end-of-over, UW failure); 0 = normal operation */
@@ -142,6 +149,8 @@ int rade_batch_multipath_gen(rade_batch *h, const float *fir_taps_host, int n_ta
 int rade_batch_multipath_h(rade_batch *h, const void *G_dev, int n_g, int fs_over_rs, int n_sym, int Nc, float delay_s, float Rs, int want_complex,
                            float *H_out_dev, void *stream);
 float rade_sigma_from_EbNodB(float EbNodB);
+/* bottleneck 1 (radae.py:574-576): sigma = (EbNo M)^-0.5, M = 160 */
+float rade_sigma_from_EbNodB_bn1(float EbNodB);
 
 /* ---- receive --------------------------------------------------------------------------------
  * rx_dev + b*rx_stride points at the first sample stream b has NOT yet consumed; n_avail_host[b]
@@ -171,6 +180,25 @@ void rade_batch_reset(rade_batch *h, void *stream);
 /* seed of the documented LCG that picks the 48 rows check_pilots refreshes (dsp.py:291-295 uses an
  * unseeded np.random.randint); seeds_host[B] or NULL for all-ones */
 void rade_batch_rx_set_lcg(rade_batch *h, const unsigned *seeds_host);
+
+/* ---- the ideal-timing ("genie") receiver of RADAE.forward / RADAE.receiver (radae.py:312-420, :590-657) -------------------------------
+ * Known timing: every stream's n_mf modem frames start at rx_dev + b * rx_stride (n_mf * 960 samples readable, n_mf >= 2).  Per stream the known frequency offset is
+ * optionally removed (rx * conj(lin_phase), the phase recurrence of rade_batch_channel, so that its output cancels), the DFT window [Ncp + time_offset, Ncp + time_offset + M)
+ * of each symbol goes through the 160 -> 30 DFT, the pilots are estimated (eq) and interpolated in phase between a frame's pilot and the next one's (the last frame
+ * keeps the reference's last slope), and the data symbols are demapped to z_hat_dev [B][3 n_mf][80].  coarse_mag divides by the RMS pilot magnitude (times
+ * |P[0]| / pilot_gain unless the engine has RADE_BATCH_TX_LINEAR).  With z_ref_dev ([B][3 n_mf][80]) n_errors_host[b] = #(-z * z_hat > 0) (ber_test; the call then
+ * synchronises `stream`).  features_out_dev [B][3 n_mf][feature width of the blob]: the stateless decoder (rade_batch_decode with reset_state = 1; 3 n_mf <= 3 max_tx_mf),
+ * or NULL.  The streaming receiver's state is not touched.  Returns n_mf or <0. */
+enum { RADE_EQ_LS = 0, RADE_EQ_MEAN6 = 1, RADE_EQ_MEAN_ALL = 2, RADE_EQ_NONE = 3 };
+typedef struct {
+    int time_offset;                  /* samples, -32..0 (inference.py --time_offset) */
+    int eq;                           /* RADE_EQ_LS (--eq_ls), RADE_EQ_MEAN6 (the default of RADAE), RADE_EQ_MEAN_ALL (per_carrier_eq = False), RADE_EQ_NONE (no --pilot_eq) */
+    int coarse_mag;                   /* --coarse_mag (ignored with RADE_EQ_NONE, as in the reference) */
+    const float *freq_offset_host, *df_dt_host;   /* [B] Hz, Hz/s: --correct_freq_offset; NULL = no correction (df_dt NULL = 0); a stream with freq_offset 0 is not corrected */
+    const float *z_ref_dev; long *n_errors_host;  /* optional BER count */
+} rade_ideal_rx_params;
+int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n_mf, const rade_ideal_rx_params *p,
+                        float *z_hat_dev, float *features_out_dev, void *stream);
 
 /* per-call trace record (tests): mirrors what radae_rxe.py prints per frame at -v 2 */
 typedef struct {

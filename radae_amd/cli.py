@@ -104,10 +104,15 @@ def _inference(argv):
     channel from a `g_file` (multipath_samples' format: gain sample, then ..G1G2..), AWGN at the Eb/No, frequency offset / drift, the write_rx tail.  The model-shape switches
     (--rate_Fs --pilots --pilot_eq --eq_ls --cp --bottleneck --time_offset --auxdata --correct_freq_offset --coarse_mag --latent-dim) are accepted and must describe model19_check3's
     waveform, the only one this path implements.  `features_hat` receives what the STREAMING receiver (radae_rxe's) decodes from the written samples -- the reference runs its
-    stateless receiver with ideal timing there; the ctests of this path pass /dev/null.  Noise: the device's Philox generator (--seed), not torch's."""
+    stateless receiver with ideal timing there; the ctests of this path pass /dev/null.  Noise: the device's Philox generator (--seed), not torch's.
+
+    The reference's ideal-timing receiver (radae.py:312-420, :590-657; rade_batch_rx_ideal) runs on the signal part of the channel output when asked for: `--ideal_rx` takes
+    features_hat and the loss from it, honouring --pilot_eq / --eq_ls / --coarse_mag / --time_offset / --correct_freq_offset; `--ber_test` sends random +-1 latents instead
+    of the encoder's and prints `n_bits: N BER: x.xxx` (radae.py:653-657); `--write_latent` writes its z_hat.  `--bottleneck 1` takes a bottleneck-1 blob (weights/model05.bin):
+    the linear rate-Fs waveform (RADE_BATCH_TX_LINEAR) at sigma = (EbNo M)^-0.5, received by the ideal-timing receiver (the streaming one is model19_check3's)."""
     import torch
     from . import engine, wire
-    from .loss import find_loss
+    from .loss import distortion_loss, find_loss
     ap = argparse.ArgumentParser(prog="radae_amd.cli inference")
     ap.add_argument("model_name"); ap.add_argument("features"); ap.add_argument("features_hat")
     ap.add_argument("--EbNodB", type=float, default=100.0); ap.add_argument("--g_file", type=str, default=""); ap.add_argument("--write_rx", type=str, default="")
@@ -115,20 +120,40 @@ def _inference(argv):
     ap.add_argument("--df_dt", type=float, default=0.0); ap.add_argument("--prepend_noise", type=float, default=0.0); ap.add_argument("--append_noise", type=float, default=0.0)
     ap.add_argument("--end_of_over", action="store_true"); ap.add_argument("--sine_amp", type=float, default=0.0); ap.add_argument("--sine_freq", type=float, default=1000.0)
     ap.add_argument("--loss_test", type=float, default=0.0); ap.add_argument("--seed", type=int, default=1)
-    for flag in ("--rate_Fs", "--pilots", "--pilot_eq", "--eq_ls", "--auxdata", "--correct_freq_offset", "--coarse_mag"):
+    ap.add_argument("--write_latent", type=str, default="", help="z_hat of the ideal-timing receiver, .f32")
+    for flag in ("--rate_Fs", "--pilots", "--pilot_eq", "--eq_ls", "--auxdata", "--correct_freq_offset", "--coarse_mag", "--ber_test", "--ideal_rx"):
         ap.add_argument(flag, action="store_true")
     ap.add_argument("--cp", type=float, default=0.004); ap.add_argument("--bottleneck", type=int, default=3); ap.add_argument("--time_offset", type=int, default=-16)
     ap.add_argument("--latent-dim", type=int, default=80)
     args = ap.parse_args(argv)
-    if args.bottleneck != 3 or abs(args.cp - 0.004) > 1e-9 or args.time_offset != -16 or args.latent_dim != 80:
-        raise SystemExit("radae_amd.cli inference: only model19_check3's waveform (--rate_Fs --pilots --pilot_eq --eq_ls --cp 0.004 --bottleneck 3 --time_offset -16 --auxdata) is implemented")
+    genie = args.ideal_rx or args.ber_test or bool(args.write_latent) or args.bottleneck == 1
+    if args.bottleneck not in (1, 3) or abs(args.cp - 0.004) > 1e-9 or args.latent_dim != 80 or not -32 <= args.time_offset <= 0 or \
+            (args.time_offset != -16 and not genie):
+        raise SystemExit("radae_amd.cli inference: only the waveforms of model19_check3 (--rate_Fs --pilots --pilot_eq --eq_ls --cp 0.004 --bottleneck 3 --time_offset -16 --auxdata) "
+                         "and of a bottleneck-1 blob (--bottleneck 1, ideal-timing receiver, --time_offset -32..0) are implemented")
+    if args.bottleneck == 1 and args.end_of_over:
+        raise SystemExit("radae_amd.cli inference: --end_of_over needs the bottleneck-3 waveform")
     blob = args.model_name if args.model_name.endswith(".bin") else None
+    if args.bottleneck == 1 and not blob:
+        raise SystemExit("radae_amd.cli inference: --bottleneck 1 needs a bottleneck-1 DNNw blob, e.g. weights/model05.bin")
     feats = wire.read_features(args.features)
     n_mf = len(feats) // 12                                   # whole modem frames (radae.py:303-310)
     feats = np.ascontiguousarray(feats[:12 * n_mf])
+    if genie and n_mf < 2:
+        raise SystemExit("radae_amd.cli inference: the ideal-timing receiver needs at least two modem frames")
     dev = torch.device("cuda", 0)
-    eng = engine.BatchEngine(1, max_tx_mf=n_mf, blob=blob)
-    iq = eng.tx(torch.tensor(feats[None], device=dev))
+    bn1 = args.bottleneck == 1
+    eng = engine.BatchEngine(1, max_tx_mf=n_mf, blob=blob, flags=(engine.BOTTLENECK1 | engine.TX_LINEAR) if bn1 else 0)
+    feat_dim = 20 if bn1 else 21
+    z = None
+    if args.ber_test:                                         # radae.py:477-478: random +-1 latents in place of the encoder's
+        g = torch.Generator().manual_seed(args.seed)
+        z = torch.sign(torch.rand((1, 3 * n_mf, 80), generator=g) - 0.5).to(dev)
+        iq = eng.tx_latents(z)
+    elif bn1:                                                 # model05: 4 x 20 features per latent, tanh bottleneck (RADE_BATCH_BOTTLENECK1)
+        iq = eng.tx_latents(eng.encode(torch.tensor(np.ascontiguousarray(feats[:, :20]).reshape(1, 3 * n_mf, 80), device=dev)))
+    else:
+        iq = eng.tx(torch.tensor(feats[None], device=dev))
     n_sig = n_mf * engine.NMF
     G = None
     if args.g_file:
@@ -137,7 +162,7 @@ def _inference(argv):
         if len(g) < n_sig:
             raise SystemExit("Multipath Doppler spread file too short")
         G = torch.tensor(np.ascontiguousarray(g[:n_sig])[None], device=dev)
-    sigma = engine.sigma_from_EbNodB(args.EbNodB)
+    sigma = engine.sigma_from_EbNodB(args.EbNodB, bottleneck=args.bottleneck)
     n_pre, n_post = int(8000 * args.prepend_noise), int(8000 * args.append_noise)
     rx = eng.channel(iq, sigma, args.freq_offset, n_pre=n_pre, n_post=n_post, with_eoo=args.end_of_over, G=G, seed=args.seed, df_dt=args.df_dt,
                      sine_amp=args.sine_amp, sine_freq=args.sine_freq, rx_gain=args.rx_gain)
@@ -152,6 +177,33 @@ def _inference(argv):
         rx.cpu().numpy()[0].astype(np.complex64).tofile(args.write_rx)
     if args.write_tx:
         tx.astype(np.complex64).tofile(args.write_tx)
+    if genie:                                                 # the ideal-timing receiver inside RADAE.forward sees the signal before the write_rx tail
+        rs = rx[:, n_pre:n_pre + n_sig]
+        if args.rx_gain != 1.0:
+            rs = rs / args.rx_gain
+        fo_ = (args.freq_offset, args.df_dt) if args.correct_freq_offset else (None, None)
+        fi, z_hat, n_err = eng.rx_ideal(rs.contiguous(), n_mf, time_offset=args.time_offset, eq="ls" if args.eq_ls else ("mean6" if args.pilot_eq else "none"),
+                                        coarse_mag=args.coarse_mag, freq_offset=fo_[0], df_dt=fo_[1], z_ref=z, feat_width=4 * feat_dim)
+        if args.ber_test:
+            n_bits = 3 * n_mf * 80
+            print(f"n_bits: {n_bits:d} BER: {int(n_err[0]) / n_bits:5.3f}")
+        if args.write_latent:
+            z_hat.cpu().numpy()[0].astype(np.float32).tofile(args.write_latent)
+    if genie and (args.ideal_rx or bn1):
+        fh = fi.cpu().numpy()[0].reshape(-1, feat_dim)
+        out = np.zeros((len(fh), 36), np.float32); out[:, :20] = fh[:, :20]          # inference.py:234-236
+        if args.features_hat != "/dev/null":
+            out.tofile(args.features_hat)
+        if not args.ber_test:
+            ft = feats[:, :21].copy()
+            if not bn1:
+                ft[:, 20] = -1.0                              # the aux symbol the transmitter appended
+            loss = distortion_loss(ft[:, :feat_dim], fh)
+            print(f"loss: {loss:5.3f} (ideal-timing receiver)")
+            if args.loss_test > 0.0:
+                print("PASS" if loss < args.loss_test else "FAIL")
+        eng.close()
+        return 0
     fo, st, _ = eng.rx(rx if args.rx_gain == 1.0 else rx.clone())
     nv = st[0].n_valid
     fh = fo.cpu().numpy()[0, :nv].reshape(-1, 36)

@@ -165,13 +165,27 @@ int rd_launch_pad_rows(const float *src, float *dst, long R, int K, int Kpad, rd
 int rd_launch_chan_symbol(const float *z, const float *H, const float *noise, float *out, long n_real, int mode, float p0, float p1, unsigned long long seed, rd_stream_t s);
 /* x is [B][nhist+Tcap][W]: copy time rows [T, T+nhist) (or [n_rows[b], ..)) of each stream to rows [0, nhist) */
 int rd_launch_carry_rows(float *x, int B, int Tcap, int W, int nhist, int T, const int *n_rows, rd_stream_t s);
-/* z [B][n_mf*3][80] -> tx [b*stride + mf*960 ...] (transmitter_one, dsp.py:340-378) */
-int rd_launch_ofdm_mod(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, rd_stream_t s);
+/* z [B][n_mf*3][80] -> tx [b*stride + mf*960 ...] (transmitter_one, dsp.py:340-378); linear: the bottleneck-1 waveform (unit pilot gain, no limiter) */
+int rd_launch_ofdm_mod(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, int linear, rd_stream_t s);
 /* the same with the two-path multipath model applied on the way out: mp [B][n_mf*960] c64, part [B][n_mf][2] sums of |tx|^2, |mp|^2; tx optional */
-int rd_launch_ofdm_mod_mp(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, const void *G, void *mp, double *part, rd_stream_t s);
+int rd_launch_ofdm_mod_mp(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, const void *G, void *mp, double *part, int linear, rd_stream_t s);
 /* EOO data symbols: bits [B][180] -> eoo frames [B][1152] (radae.py:441-455); bits NULL = defaults */
 int rd_launch_eoo_build(const rd_tables *tab, const float *bits, float *eoo, int B, rd_stream_t s);
 int rd_launch_copy_eoo(const float *eoo, void *out, long stride, int B, rd_stream_t s);
+
+/* the ideal-timing receiver of RADAE.forward / RADAE.receiver (rade_irx.hip): k_irx_demod per (modem frame, stream), then k_irx_scale per stream
+ * when coarse_mag (eq != NONE) or a BER count is asked for */
+enum { RD_IRX_LS = 0, RD_IRX_MEAN6 = 1, RD_IRX_ALL = 2, RD_IRX_NONE = 3 };
+typedef struct {
+    const rd_tables *tab; const void *rx; long rx_stride;      /* complex64, stream b at rx + b * rx_stride samples, n_mf * 960 readable */
+    const float *foff;                                           /* optional [2][B]: freq_offset, df_dt per stream (Hz, Hz/s); a stream with freq_offset 0 is not corrected */
+    int n_mf, time_offset, eq, coarse_mag, B;
+    float mag_scale;                                             /* coarse_mag factor: |P[0]| / pilot_gain (bottleneck 3) or 1 */
+    float *z_hat;                                                /* [B][n_mf * 3][80] */
+    double *part;                                                /* [B][n_mf] sum_c |pilot estimate|^2 */
+    const float *z_ref; long long *n_err;                        /* optional BER count: [B][n_mf * 3][80] reference latents, [B] errors */
+} rd_irx_args;
+int rd_launch_irx(const rd_irx_args *a, rd_stream_t s);
 
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;

@@ -66,6 +66,13 @@ __device__ __forceinline__ f32x2 idft_term(f32x2 acc, float2 sy, float2 w)
 }
 
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+// phase of the channel's frequency offset at sample i (k_chan_apply) and of its correction in the ideal-timing receiver (k_irx_demod)
+__device__ __forceinline__ double chan_phase_acc(int i, float f0, float df_dt)
+{   // sum_{k<=i} omega_k, omega_k = float32(freq_k*2*pi/Fs) summed in double (torch.cumsum on CPU)
+    if (df_dt == 0.0f) { const float om = ((f0 * 2.0f) * (float)PI_D) / 8000.0f; return (double)(i + 1) * (double)om; }
+    const double n = (double)(i + 1);
+    return (2.0 * PI_D / 8000.0) * (n * (double)f0 + ((double)df_dt / 8000.0) * 0.5 * (double)i * n);
+}
 __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
 // e^{-j angle(c)} = conj(c)/|c| (np.exp(-1j*np.angle(c)) without atan2 / sincos); angle(0) = 0
 __device__ __forceinline__ float2 unit_conj(float2 c)

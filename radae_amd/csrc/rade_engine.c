@@ -90,6 +90,8 @@ struct rade_batch {
     int enc_hist_frag;                   /* the history tile of enc_xf holds what enc_x's two float32 history rows hold (set by a fragment pass, cleared by a reset or a float32-row pass) */   /* the concat buffer as matrix-core operand fragments (rade_enc.hip: [B][enc_nq][RD_EF_TILE] binary16), engines with enough rows for the batched GEMMs only */
     /* optional Tx band-pass filter + clip (RADE_BATCH_TX_BPF; radae_txe.py:74-83): filter state per stream, its initial value, the modulator's raw output, block phases */
     int bypass_dec;                          /* RADE_BATCH_BYPASS_DEC */
+    int tx_linear;                           /* RADE_BATCH_TX_LINEAR */
+    double *irx_part; long irx_part_cap; float *irx_foff; long long *irx_err;   /* rade_batch_rx_ideal: per-frame pilot power [B][cap], offsets [2][B], error counts [B] */
     rd_bpf_state *tx_bpf, *tx_bpf_init; void *tx_raw; float *tx_chain; float *eoo_filt;   /* eoo_filt [B][Neoo] c64: the end-of-over frame as transmitted (filtered + clipped) for the channel's with_eoo */
     void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
     /* receive side */
@@ -331,6 +333,8 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     h->eoo = dev_zeros(sizeof(float) * B * RD_NEOO * 2);
     h->eoo_bits = dev_zeros(sizeof(float) * B * RD_NEOOBITS);
     h->bypass_dec = (cfg->flags & RADE_BATCH_BYPASS_DEC) != 0;
+    h->tx_linear = (cfg->flags & RADE_BATCH_TX_LINEAR) != 0;
+    if (h->tx_linear && (cfg->flags & RADE_BATCH_TX_BPF)) { fprintf(stderr, "rade: RADE_BATCH_TX_LINEAR cannot be combined with RADE_BATCH_TX_BPF (the filter clips)\n"); goto fail; }
     if (cfg->flags & RADE_BATCH_TX_BPF) {
         const long nraw = (long)(cfg->max_tx_mf > 2 ? cfg->max_tx_mf : 2) * RD_NMF;          /* (>= the 1152-sample end-of-over frame) */
         rd_bpf_state *init = calloc(B, sizeof *init);
@@ -412,7 +416,8 @@ void rade_batch_close(rade_batch *h)
     if (!h) return;
     ON_DEV(h);
     void *bufs[] = { h->d_tab, h->enc_xin, h->enc_x, h->enc_xf, h->enc_gi, h->enc_z, h->eoo, h->eoo_bits, h->chan_scratch, h->rx_st, h->rx_round, h->rx_avail,
-                     h->rx_progress /* + rx_acc, rx_status */, h->wg_cycles, h->zrows, h->dec_x, h->dec_gi, h->dec_hbuf, h->feat84, h->trace, h->trace_z, h->d_lcg_seeds, h->dtcache, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->rx_filt, h->bpf_chain, h->bpf16, h->tx_bpf, h->tx_bpf_init, h->tx_raw, h->tx_chain, h->eoo_filt, h->corrq16, h->corra16, h->vm, h->chan_mp, h->wfwd16 };
+                     h->rx_progress /* + rx_acc, rx_status */, h->wg_cycles, h->zrows, h->dec_x, h->dec_gi, h->dec_hbuf, h->feat84, h->trace, h->trace_z, h->d_lcg_seeds, h->dtcache, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->rx_filt, h->bpf_chain, h->bpf16, h->tx_bpf, h->tx_bpf_init, h->tx_raw, h->tx_chain, h->eoo_filt, h->corrq16, h->corra16, h->vm, h->chan_mp, h->wfwd16,
+                     h->irx_part, h->irx_foff, h->irx_err };
     for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; i++) if (bufs[i]) hipFree(bufs[i]);
     free_lin(&h->enc_dense1); free_lin(&h->enc_zdense); free_lin(&h->dec_dense1); free_lin(&h->dec_output);
     for (int l = 0; l < 5; l++) {
@@ -597,7 +602,7 @@ int rade_batch_tx(rade_batch *h, const float *features_dev, int n_mf, void *iq_o
     e |= rd_launch_enc_pack(features_dev, h->enc_xin, B, T, stream);
     e |= encode_core(h, T, z, stream);
     void *mod_out = h->tx_bpf ? h->tx_raw : iq_out_dev; const long mod_stride = h->tx_bpf ? (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF : iq_stride;
-    PROF_BEGIN(h, stream); e |= rd_launch_ofdm_mod(h->d_tab, z, mod_out, mod_stride, B, n_mf, stream); PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
+    PROF_BEGIN(h, stream); e |= rd_launch_ofdm_mod(h->d_tab, z, mod_out, mod_stride, B, n_mf, h->tx_linear, stream); PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
     if (h->tx_bpf) e |= tx_bpf_pass(h, n_mf * RD_NMF, RD_NMF, iq_out_dev, iq_stride, stream);
     return e ? -1 : n_mf * RD_NMF;
 }
@@ -610,7 +615,7 @@ int rade_batch_tx_latents(rade_batch *h, const float *z_dev, int n_mf, void *iq_
     const int B = h->B;
     int e = 0;
     void *mod_out = h->tx_bpf ? h->tx_raw : iq_out_dev; const long mod_stride = h->tx_bpf ? (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF : iq_stride;
-    PROF_BEGIN(h, stream); e |= rd_launch_ofdm_mod(h->d_tab, z_dev, mod_out, mod_stride, B, n_mf, stream); PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
+    PROF_BEGIN(h, stream); e |= rd_launch_ofdm_mod(h->d_tab, z_dev, mod_out, mod_stride, B, n_mf, h->tx_linear, stream); PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
     if (h->tx_bpf) e |= tx_bpf_pass(h, n_mf * RD_NMF, RD_NMF, iq_out_dev, iq_stride, stream);
     return e ? -1 : n_mf * RD_NMF;
 }
@@ -636,6 +641,7 @@ int rade_batch_tx_set_eoo_bits(rade_batch *h, const float *bits_host)
 int rade_batch_tx_eoo(rade_batch *h, void *iq_out_dev, long iq_stride, void *stream)
 {
     ON_DEV(h);
+    if (h->tx_linear) return -1;           /* the end-of-over frame is built with the bottleneck-3 pilot gain and limiter */
     if (!h->tx_bpf) return rd_launch_copy_eoo(h->eoo, iq_out_dev, iq_stride, h->B, stream) ? -1 : RD_NEOO;
     int e = rd_launch_copy_eoo(h->eoo, h->tx_raw, (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF, h->B, stream);
     e |= tx_bpf_pass(h, RD_NEOO, RD_NEOO, iq_out_dev, iq_stride, stream);
@@ -649,9 +655,16 @@ float rade_sigma_from_EbNodB(float EbNodB)
     return powf(8000.0f / (EbNo * Rb), 0.5f);
 }
 
+float rade_sigma_from_EbNodB_bn1(float EbNodB)
+{   /* radae.py:574-576 (bottleneck 1): sigma = (EbNo*M)^-0.5 */
+    const float EbNo = powf(10.0f, EbNodB / 10.0f);
+    return powf(EbNo * (float)RD_M, -0.5f);
+}
+
 int rade_batch_channel(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride, const rade_channel_params *p, void *stream)
 {
     ON_DEV(h);
+    if (h->tx_linear && p->with_eoo) return -1;
     rd_chan_args a;
     memset(&a, 0, sizeof a);
     a.tab = h->d_tab; a.tx = tx_dev; a.tx_stride = tx_stride; a.rx = rx_out_dev; a.rx_stride = rx_stride; a.G = p->G_dev; a.noise = p->noise_dev;
@@ -679,7 +692,7 @@ int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, vo
                           const rade_channel_params *p, void *stream)
 {
     ON_DEV(h);
-    if (!h || !p || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84 || p->n_sig != n_mf * RD_NMF || !rx_out_dev) return -1;
+    if (!h || !p || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84 || p->n_sig != n_mf * RD_NMF || !rx_out_dev || (h->tx_linear && p->with_eoo)) return -1;
     if (!p->G_dev || h->tx_bpf) {          /* (the Tx band-pass filter sits between the modulator and the channel: the two calls back to back) */
         if (!iq_out_dev) return -1;
         if (rade_batch_tx(h, features_dev, n_mf, iq_out_dev, iq_stride, NULL, stream) != p->n_sig) return -1;
@@ -690,7 +703,7 @@ int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, vo
     int e = rd_launch_enc_pack(features_dev, h->enc_xin, B, T, stream);
     e |= encode_core(h, T, h->enc_z, stream);
     PROF_BEGIN(h, stream);
-    e |= rd_launch_ofdm_mod_mp(h->d_tab, h->enc_z, iq_out_dev, iq_stride, B, n_mf, p->G_dev, h->chan_mp, (double *)h->chan_scratch + 2 * (size_t)B, stream);
+    e |= rd_launch_ofdm_mod_mp(h->d_tab, h->enc_z, iq_out_dev, iq_stride, B, n_mf, p->G_dev, h->chan_mp, (double *)h->chan_scratch + 2 * (size_t)B, h->tx_linear, stream);
     PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
     if (e) return -1;
     rd_chan_args a;
@@ -785,6 +798,44 @@ int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *fea
     int e = decoder_layers(h, z_dev, n_steps, n_steps, h->Tcap, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->dec2_h, NULL, NULL, features_out_dev, stream);
     e |= rd_launch_carry_rows(h->dec2_x, h->B, h->Tcap, RD_DEC_W, 1, n_steps, NULL, stream);
     return e ? -1 : n_steps;
+}
+
+/* ---- the ideal-timing receiver (radae.py:312-420, :590-657) ---------------------------------------------------------------- */
+int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n_mf, const rade_ideal_rx_params *p,
+                        float *z_hat_dev, float *features_out_dev, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !rx_dev || !p || !z_hat_dev || n_mf < 2 || rx_stride < (long)n_mf * RD_NMF || p->time_offset < -RD_NCP || p->time_offset > 0 ||
+        p->eq < RADE_EQ_LS || p->eq > RADE_EQ_NONE || (features_out_dev && 3 * n_mf > h->Tcap) || (p->n_errors_host && !p->z_ref_dev)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_mf > h->irx_part_cap) {
+        if (h->irx_part) { hipStreamSynchronize(st); hipFree(h->irx_part); }
+        h->irx_part = dev_zeros(sizeof(double) * (size_t)B * n_mf);
+        h->irx_part_cap = h->irx_part ? n_mf : 0;
+        if (!h->irx_part) return -1;
+    }
+    if (!h->irx_foff && !(h->irx_foff = dev_zeros(sizeof(float) * 2 * B))) return -1;
+    if (!h->irx_err && !(h->irx_err = dev_zeros(sizeof(long long) * B))) return -1;
+    if (p->freq_offset_host) {
+        float *f = (float *)h->h_small;          /* pinned scratch, >= 8 B ints */
+        for (int b = 0; b < B; b++) { f[b] = p->freq_offset_host[b]; f[B + b] = p->df_dt_host ? p->df_dt_host[b] : 0.0f; }
+        if (hipMemcpyAsync(h->irx_foff, f, sizeof(float) * 2 * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    }
+    rd_irx_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.rx = rx_dev; a.rx_stride = rx_stride; a.foff = p->freq_offset_host ? h->irx_foff : NULL;
+    a.n_mf = n_mf; a.time_offset = p->time_offset; a.eq = p->eq; a.coarse_mag = p->coarse_mag; a.B = B;
+    a.mag_scale = h->tx_linear ? 1.0f : (float)(sqrt(2.0) / ((pow(10.0, -2.0 / 20.0) * RD_M) / sqrt((double)RD_NC)));   /* |P[0]| / pilot_gain, radae.py:196-199, :379-380 */
+    a.z_hat = z_hat_dev; a.part = h->irx_part; a.z_ref = p->z_ref_dev; a.n_err = p->z_ref_dev ? h->irx_err : NULL;
+    if (rd_launch_irx(&a, stream)) return -1;
+    if (p->n_errors_host) {
+        long long *e = (long long *)h->h_small;
+        if (hipMemcpyAsync(e, h->irx_err, sizeof(long long) * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        for (int b = 0; b < B; b++) p->n_errors_host[b] = (long)e[b];
+    }
+    if (features_out_dev && rade_batch_decode(h, z_hat_dev, 3 * n_mf, features_out_dev, 1, stream) != 3 * n_mf) return -1;
+    return n_mf;
 }
 
 int rade_batch_channel_symbol(rade_batch *h, const float *z_dev, const float *H_dev, const float *noise_dev, float *z_hat_dev, int n_steps,

@@ -630,12 +630,15 @@ extern "C" int rd_launch_carry_rows(float *x, int B, int Tcap, int W, int nhist,
 // tanh(|x|) * exp(j*angle(x))   (radae.py:218, dsp.py:377)
 
 // one workgroup per (modem frame, stream): 5 symbols x 160 samples, 30-term IDFT per sample
+// LINEAR (RADE_BATCH_TX_LINEAR): the bottleneck-1 rate-Fs waveform (radae.py:195-199, :545-548): pilots at unit gain, no limiter
+template <bool LINEAR>
 __global__ __launch_bounds__(192) void k_ofdm_mod(const rd_tables *tab, const float *z, float2 *tx, long tx_stride, int n_mf)
 {
     __shared__ float2 sym[RD_NS + 1][RD_NC];
     const int mf = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float *zf = z + ((size_t)b * n_mf + mf) * RD_ZMF;
-    if (tid < RD_NC) sym[0][tid] = make_float2(tab->P[tid] * tab->pilot_gain, 0.0f * tab->pilot_gain);
+    const float pg = LINEAR ? 1.0f : tab->pilot_gain;
+    if (tid < RD_NC) sym[0][tid] = make_float2(tab->P[tid] * pg, 0.0f * pg);
     if (tid < 120) sym[1 + tid / RD_NC][tid % RD_NC] = make_float2(zf[2 * tid], zf[2 * tid + 1]);
     __syncthreads();
     float2 *out = tx + (size_t)b * tx_stride + (size_t)mf * RD_NMF;
@@ -651,16 +654,17 @@ __global__ __launch_bounds__(192) void k_ofdm_mod(const rd_tables *tab, const fl
         }
 #pragma unroll
         for (int s = 0; s <= RD_NS; s++) {
-            const float2 v = pa_limit(make_float2(acc[s][0], acc[s][1]));
+            const float2 v = LINEAR ? make_float2(acc[s][0], acc[s][1]) : pa_limit(make_float2(acc[s][0], acc[s][1]));
             out[s * RD_SYM + RD_NCP + tid] = v;
             if (tid >= RD_M - RD_NCP) out[s * RD_SYM + tid - (RD_M - RD_NCP)] = v;
         }
     }
 }
-extern "C" int rd_launch_ofdm_mod(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, rd_stream_t s)
+extern "C" int rd_launch_ofdm_mod(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, int linear, rd_stream_t s)
 {
     if (B <= 0 || n_mf <= 0) return 0;
-    hipLaunchKernelGGL(k_ofdm_mod, dim3(n_mf, B), dim3(192), 0, (hipStream_t)s, tab, z, (float2 *)tx, tx_stride, n_mf);
+    if (linear) hipLaunchKernelGGL(k_ofdm_mod<true>, dim3(n_mf, B), dim3(192), 0, (hipStream_t)s, tab, z, (float2 *)tx, tx_stride, n_mf);
+    else hipLaunchKernelGGL(k_ofdm_mod<false>, dim3(n_mf, B), dim3(192), 0, (hipStream_t)s, tab, z, (float2 *)tx, tx_stride, n_mf);
     return (int)hipGetLastError();
 }
 
@@ -669,6 +673,7 @@ extern "C" int rd_launch_ofdm_mod(const rd_tables *tab, const float *z, void *tx
 // multipath model mp[i] = tx[i] G1[i] + tx[i-16] G2[i-16] while they are there (the 16 samples it needs from the frame before are
 // re-synthesised: 16 x 30 terms) and leaves per-frame sums of |tx|^2 and |mp|^2 for the power normalisation.  tx never makes a round
 // trip through HBM, k_chan_power disappears, and k_chan_apply reads 8 bytes per sample (mp) instead of 24 (tx + G).
+template <bool LINEAR>
 __global__ __launch_bounds__(192) void k_ofdm_mod_mp(const rd_tables *tab, const float *z, float2 *tx, long tx_stride, int n_mf, const float2 *G, float2 *mp, double *part)
 {
     __shared__ float2 sym[RD_NS + 1][RD_NC];
@@ -677,7 +682,8 @@ __global__ __launch_bounds__(192) void k_ofdm_mod_mp(const rd_tables *tab, const
     __shared__ double red[2][4];
     const int mf = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float *zf = z + ((size_t)b * n_mf + mf) * RD_ZMF;
-    if (tid < RD_NC) sym[0][tid] = make_float2(tab->P[tid] * tab->pilot_gain, 0.0f * tab->pilot_gain);
+    const float pg = LINEAR ? 1.0f : tab->pilot_gain;
+    if (tid < RD_NC) sym[0][tid] = make_float2(tab->P[tid] * pg, 0.0f * pg);
     if (tid < 120) sym[1 + tid / RD_NC][tid % RD_NC] = make_float2(zf[2 * tid], zf[2 * tid + 1]);
     if (tid >= 128 && tid < 128 + RD_NC && mf > 0) { const int c = tid - 128; prevsym[c] = make_float2(zf[-RD_ZMF + 2 * (90 + c)], zf[-RD_ZMF + 2 * (90 + c) + 1]); }   // last data symbol of frame mf - 1
     __syncthreads();
@@ -693,14 +699,14 @@ __global__ __launch_bounds__(192) void k_ofdm_mod_mp(const rd_tables *tab, const
         }
 #pragma unroll
         for (int s = 0; s <= RD_NS; s++) {
-            const float2 v = pa_limit(make_float2(acc[s][0], acc[s][1]));
+            const float2 v = LINEAR ? make_float2(acc[s][0], acc[s][1]) : pa_limit(make_float2(acc[s][0], acc[s][1]));
             fr[16 + s * RD_SYM + RD_NCP + tid] = v;
             if (tid >= RD_M - RD_NCP) fr[16 + s * RD_SYM + tid - (RD_M - RD_NCP)] = v;
         }
     } else if (tid < RD_M + 16) {                          // samples 944..959 of the previous frame = the last 16 of its last symbol
         const int n = RD_M - 16 + (tid - RD_M);
         float2 a = make_float2(0.0f, 0.0f);
-        if (mf > 0) { f32x2 ac = { 0.0f, 0.0f }; for (int c = 0; c < RD_NC; c++) ac = idft_term(ac, prevsym[c], ld2(tab->Winv[c], n)); a = pa_limit(make_float2(ac[0], ac[1])); }
+        if (mf > 0) { f32x2 ac = { 0.0f, 0.0f }; for (int c = 0; c < RD_NC; c++) ac = idft_term(ac, prevsym[c], ld2(tab->Winv[c], n)); a = LINEAR ? make_float2(ac[0], ac[1]) : pa_limit(make_float2(ac[0], ac[1])); }
         fr[tid - RD_M] = a;                                // frame 0: the signal starts here, nothing before it (chan_mp: i >= 16)
     }
     __syncthreads();
@@ -741,10 +747,11 @@ __global__ __launch_bounds__(192) void k_ofdm_mod_mp(const rd_tables *tab, const
     __syncthreads();
     if (tid == 0) { part[((size_t)b * n_mf + mf) * 2] = (red[0][0] + red[0][1]) + red[0][2]; part[((size_t)b * n_mf + mf) * 2 + 1] = (red[1][0] + red[1][1]) + red[1][2]; }
 }
-extern "C" int rd_launch_ofdm_mod_mp(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, const void *G, void *mp, double *part, rd_stream_t s)
+extern "C" int rd_launch_ofdm_mod_mp(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, const void *G, void *mp, double *part, int linear, rd_stream_t s)
 {
     if (B <= 0 || n_mf <= 0) return 0;
-    hipLaunchKernelGGL(k_ofdm_mod_mp, dim3(n_mf, B), dim3(192), 0, (hipStream_t)s, tab, z, (float2 *)tx, tx_stride, n_mf, (const float2 *)G, (float2 *)mp, part);
+    if (linear) hipLaunchKernelGGL(k_ofdm_mod_mp<true>, dim3(n_mf, B), dim3(192), 0, (hipStream_t)s, tab, z, (float2 *)tx, tx_stride, n_mf, (const float2 *)G, (float2 *)mp, part);
+    else hipLaunchKernelGGL(k_ofdm_mod_mp<false>, dim3(n_mf, B), dim3(192), 0, (hipStream_t)s, tab, z, (float2 *)tx, tx_stride, n_mf, (const float2 *)G, (float2 *)mp, part);
     return (int)hipGetLastError();
 }
 
@@ -836,13 +843,6 @@ __device__ __forceinline__ float2 gauss_pair(uint32_t u0, uint32_t u1)
     const float a = ((float)u0 + 0.5f) * (1.0f / 4294967296.0f), bq = ((float)u1 + 0.5f) * (1.0f / 4294967296.0f);
     const float rad = __builtin_amdgcn_sqrtf(-1.38629436112f * __builtin_amdgcn_logf(a));       // -2 ln a = -2 ln 2 log2 a
     return make_float2(rad * __builtin_amdgcn_cosf(bq), rad * __builtin_amdgcn_sinf(bq));
-}
-
-__device__ __forceinline__ double chan_phase_acc(int i, float f0, float df_dt)
-{   // sum_{k<=i} omega_k, omega_k = float32(freq_k*2*pi/Fs) summed in double (torch.cumsum on CPU)
-    if (df_dt == 0.0f) { const float om = ((f0 * 2.0f) * (float)PI_D) / 8000.0f; return (double)(i + 1) * (double)om; }
-    const double n = (double)(i + 1);
-    return (2.0 * PI_D / 8000.0) * (n * (double)f0 + ((double)df_dt / 8000.0) * 0.5 * (double)i * n);
 }
 
 // per stream, ahead of k_chan_apply: the power-normalising gain and the phase the frequency offset has reached at the end of the signal, from the

@@ -18,7 +18,8 @@ LIB_PATH = os.environ.get("RADE_LIBRADEHIP") or os.path.join(_HERE, "libradehip.
 DEFAULT_BLOB = os.path.join(os.path.dirname(_HERE), "weights", "model19_check3.bin")
 
 NMF, NEOO, NIN_MAX, FEAT_MF, NEOO_BITS, ZMF = 960, 1152, 1120, 432, 180, 240
-BOTTLENECK1, TX_BPF, BYPASS_DEC = 0x100, 0x400, 0x800          # include/rade_batch.h flags
+BOTTLENECK1, TX_BPF, BYPASS_DEC, TX_LINEAR = 0x100, 0x400, 0x800, 0x1000          # include/rade_batch.h flags
+EQ_MODES = {"ls": 0, "mean6": 1, "all": 2, "none": 3}                              # rade_ideal_rx_params.eq
 
 
 class BatchConfig(C.Structure):
@@ -29,6 +30,11 @@ class ChannelParams(C.Structure):
     _fields_ = [("n_sig", C.c_int), ("n_pre", C.c_int), ("n_post", C.c_int), ("with_eoo", C.c_int), ("sigma", C.c_float), ("freq_offset", C.c_float),
                 ("df_dt", C.c_float), ("G_dev", C.c_void_p), ("noise_dev", C.c_void_p), ("seed", C.c_ulonglong),
                 ("sine_amp", C.c_float), ("sine_freq", C.c_float), ("rx_gain", C.c_float)]
+
+
+class IdealRxParams(C.Structure):
+    _fields_ = [("time_offset", C.c_int), ("eq", C.c_int), ("coarse_mag", C.c_int), ("freq_offset_host", C.c_void_p), ("df_dt_host", C.c_void_p),
+                ("z_ref_dev", C.c_void_p), ("n_errors_host", C.c_void_p)]
 
 
 class RxStatus(C.Structure):
@@ -68,6 +74,9 @@ def load_library() -> C.CDLL:
     L.rade_batch_multipath_gen.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, vp, C.c_ulonglong, vp, vp]
     L.rade_batch_multipath_h.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
     L.rade_sigma_from_EbNodB.restype = C.c_float; L.rade_sigma_from_EbNodB.argtypes = [C.c_float]
+    if hasattr(L, "rade_batch_rx_ideal"):         # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
+        L.rade_sigma_from_EbNodB_bn1.restype = C.c_float; L.rade_sigma_from_EbNodB_bn1.argtypes = [C.c_float]
+        L.rade_batch_rx_ideal.argtypes = [vp, vp, C.c_long, C.c_int, C.POINTER(IdealRxParams), vp, vp, vp]
     L.rade_batch_rx.argtypes = [vp, vp, C.c_long, C.POINTER(C.c_int), C.c_int, vp, C.c_long, vp, C.POINTER(RxStatus), vp]
     L.rade_batch_rx_reset.argtypes = [vp]
     L.rade_batch_encode.argtypes = [vp, vp, C.c_int, vp, vp]
@@ -102,11 +111,18 @@ EXPORTED_SYMBOLS = [
     "rade_batch_rx_stream_cycles", "rade_batch_rx_filtered", "rade_host_cpu_quota", "rade_sync_policy", "rade_batch_sync_counts",
     "rade_multi_open", "rade_multi_close", "rade_multi_n_devices", "rade_multi_transport", "rade_multi_engine", "rade_multi_shard", "rade_multi_foreach",
     "rade_multi_allreduce_sum",
+    "rade_batch_rx_ideal", "rade_sigma_from_EbNodB_bn1",
 ]
 
 
-def sigma_from_EbNodB(EbNodB: float) -> float:
-    return float(load_library().rade_sigma_from_EbNodB(EbNodB))
+def sigma_from_EbNodB(EbNodB: float, bottleneck: int = 3) -> float:
+    """AWGN standard deviation of the rate-Fs channel: bottleneck 3 (radae.py:567-573) or bottleneck 1 (:574-576, the waveform of TX_LINEAR)."""
+    L = load_library()
+    if bottleneck == 1:
+        return float(L.rade_sigma_from_EbNodB_bn1(EbNodB))
+    if bottleneck != 3:
+        raise ValueError("rate-Fs noise is defined for bottleneck 1 or 3")
+    return float(L.rade_sigma_from_EbNodB(EbNodB))
 
 
 def _stream_ptr():
@@ -376,6 +392,40 @@ class BatchEngine:
         if r:
             raise RuntimeError("rade_batch_rx failed")
         return features_out, list(status), eoo
+
+    def rx_ideal(self, rx, n_mf: int, time_offset: int = -16, eq: str = "ls", coarse_mag: bool = True, freq_offset=None, df_dt=None, z_ref=None,
+                 feat_width: int = 84):
+        """The ideal-timing receiver of RADAE.forward / RADAE.receiver (rade_batch_rx_ideal): rx complex64 [B, >= n_mf*960], every stream's first modem frame at
+        sample 0.  eq: "ls" (--eq_ls), "mean6", "all" (per_carrier_eq off) or "none" (no --pilot_eq).  freq_offset / df_dt: per-stream known offsets (a scalar
+        is taken for every stream) removed before the DFT (--correct_freq_offset).  z_ref [B, n_mf*3, 80]: count bit errors (ber_test).  feat_width: the blob's
+        decoder output per step (84 model19_check3, 80 model05), 0 = no decoder.
+        Returns (features [B, n_mf*3, feat_width] or None, z_hat [B, n_mf*3, 80], n_errors np.int64 [B] or None)."""
+        import torch
+        assert rx.is_cuda and rx.dtype == torch.complex64 and rx.dim() == 2 and rx.shape[0] == self.B and rx.stride(1) == 1 and rx.shape[1] >= n_mf * NMF
+        z_hat = torch.empty((self.B, n_mf * 3, 80), dtype=torch.float32, device=rx.device)
+        feats = None
+        if feat_width:
+            feats = torch.empty((self.B, n_mf * 3, feat_width), dtype=torch.float32, device=rx.device)
+        keep = []
+
+        def per_stream(v):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (self.B,)))
+            keep.append(a)
+            return a.ctypes.data
+        p = IdealRxParams(int(time_offset), EQ_MODES[eq], int(coarse_mag), per_stream(freq_offset), per_stream(df_dt), None, None)
+        n_err = None
+        if z_ref is not None:
+            assert z_ref.is_cuda and z_ref.dtype == torch.float32 and z_ref.is_contiguous() and tuple(z_ref.shape) == (self.B, n_mf * 3, 80)
+            n_err = np.zeros(self.B, np.int64)     # C long
+            p.z_ref_dev = z_ref.data_ptr(); p.n_errors_host = n_err.ctypes.data
+        stride = rx.stride(0) if self.B > 1 else rx.shape[1]       # (a one-row tensor may carry any stride in its first dimension, e.g. 0 from numpy's [None])
+        r = self.lib.rade_batch_rx_ideal(self.h, rx.data_ptr(), stride, n_mf, C.byref(p), z_hat.data_ptr(), feats.data_ptr() if feats is not None else None,
+                                         _stream_ptr())
+        if r != n_mf:
+            raise RuntimeError("rade_batch_rx_ideal failed (n_mf >= 2, time_offset in [-32, 0], 3 n_mf <= 3 max_tx_mf with decode)")
+        return feats, z_hat, n_err
 
     def rx_filtered(self, b: int, n: int) -> np.ndarray:
         """The first n band-pass filtered samples stream b's receiver read in the most recent rx() invocation (complex_bpf.bpf output)."""
