@@ -71,8 +71,8 @@ int rade_batch_n_streams(const rade_batch *h);
  * serve smaller calls ($RADE_ENCF_SEQ_TAPS restores the sequential order, $RADE_ENC_ROWS the row kernels for every size).  Both are inside every parity bar (latents
  * < 2e-5 of full scale against the float32 oracle, tests/test_hip_parity.py), but the same stream encoded in a batch of 32 and in a batch of 256 is not bit-identical.
  * The batched path also keeps one bit of HOST state per engine (whether the history tile of its fragment buffer is current): rade_batch_tx / rade_batch_encode are
- * stream-ordered but not capturable into a hipGraph that is replayed across resets or mixed with short calls (rade_tx() of rade_api.h, which IS captured, always takes
- * the row path). */
+ * stream-ordered but not capturable into a hipGraph that is replayed across resets or mixed with short calls (rade_tx() of rade_api.h, which IS captured on a handle
+ * opened with the Tx band-pass filter, always takes the row path). */
 /* ---- transmit ------------------------------------------------------------------------------
  * features_dev : [B][n_mf*12][36] float32 (first 20 of each 36 used; aux symbol -1 added inside)
  * iq_out_dev   : stream b written at iq_out_dev + b*iq_stride (units: complex samples), n_mf*960 samples

@@ -30,11 +30,11 @@ struct rade {
     int flags, nin, sync, snr, device;
     float *d_feat_in, *d_feat_out, *d_eoo; void *d_iq, *d_rx;
     pthread_mutex_t lock;
-    /* rade_tx is ~20 short launches for one stream (launch-bound): after the first call the sequence
-     * [features H2D, encoder + modulator kernels, samples D2H] is captured once and replayed as a hipGraph */
+    void *txc;                               /* rade_tx as ONE launch per frame (rade_core.c: rd_core_tx_*); NULL: the batched engine's launch sequence below */
+    /* without txc (a handle with the Tx band-pass filter, or a failed rd_core_tx_open) rade_tx is ~20 short launches for one stream (launch-bound):
+     * after the first call the sequence [features H2D, encoder + modulator kernels, samples D2H] is captured once and replayed as a hipGraph */
     hipStream_t gs; hipGraphExec_t tx_graph; int tx_calls, tx_graph_off;
     float *h_feat; RADE_COMP *h_iq;          /* pinned staging buffers the graph copies from / to */
-    void *txc;                               /* rade_tx as ONE launch per frame (rade_core.c: rd_core_tx_*); NULL: the batched engine's launch sequence above */
 };
 
 void rade_initialize(void) { /* reference: Py_InitializeEx (rade_api.c:329-332); HIP initialises lazily */ }
@@ -71,28 +71,29 @@ struct rade *rade_open(char model_file[], int flags)
     const char *path = rd_find_default_model(model_file, buf, sizeof buf);
     if (!path) { fprintf(stderr, "rade_open: no DNNw weight blob found (tried \"%s\", $RADE_MODEL_FILE, weights/model19_check3.bin)\n", model_file ? model_file : ""); return NULL; }
     if (flags & RADE_BATCH_TX_LINEAR) { fprintf(stderr, "rade_open: RADE_BATCH_TX_LINEAR is not available on the single-stream frame path\n"); return NULL; }
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "rade: cannot open weight blob %s\n", path); return NULL; }
+    fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
+    void *blob = n > 0 ? malloc((size_t)n) : NULL;
+    const int read_ok = blob && fread(blob, 1, (size_t)n, f) == (size_t)n;
+    fclose(f);
+    if (!read_ok) { free(blob); return NULL; }
     struct rade *r = calloc(1, sizeof *r);
     rade_batch_config cfg = { 1, 1, 0, flags, 0, 0.0f };
     const char *dev = getenv("RADE_DEVICE");
     if (dev) cfg.device = atoi(dev);
-    r->eng = rade_batch_open(path, &cfg);
-    if (!r->eng) { free(r); return NULL; }
+    r->eng = rade_batch_open_mem(blob, (size_t)n, &cfg);
+    if (!r->eng) { free(blob); free(r); return NULL; }
     r->flags = flags; r->nin = RD_NMF; r->device = cfg.device;
-    if (!rd_batch_has_tx_bpf(r->eng)) {      /* (the Tx band-pass option filters between modulator and output: that path stays on the engine) */
-        FILE *f = fopen(path, "rb");
-        if (f) {
-            fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
-            void *blob = n > 0 ? malloc((size_t)n) : NULL;
-            if (blob && fread(blob, 1, (size_t)n, f) == (size_t)n) r->txc = rd_core_tx_open(blob, (int)n, rd_batch_tables(r->eng));
-            free(blob); fclose(f);
-        }
-    }
+    /* (the Tx band-pass option filters between modulator and output: that path stays on the engine) */
+    if (!rd_batch_has_tx_bpf(r->eng)) r->txc = rd_core_tx_open(blob, (int)n, rd_batch_tables(r->eng));
+    free(blob);
     if (hipMalloc((void **)&r->d_feat_in, sizeof(float) * RD_FEAT_MF) || hipMalloc((void **)&r->d_feat_out, sizeof(float) * RD_FEAT_MF) ||
         hipMalloc((void **)&r->d_eoo, sizeof(float) * RD_NEOOBITS) || hipMalloc(&r->d_iq, sizeof(RADE_COMP) * RD_NEOO) ||
         hipMalloc(&r->d_rx, sizeof(RADE_COMP) * RD_NINMAX)) { rade_close(r); return NULL; }
     pthread_mutex_init(&r->lock, NULL);
     /* optional fast path of rade_tx (hipGraph replay): any failure here or later simply leaves the plain path in use */
-    if (getenv("RADE_NO_GRAPH") || hipStreamCreate(&r->gs) != hipSuccess || hipHostMalloc((void **)&r->h_feat, sizeof(float) * RD_FEAT_MF, 0) != hipSuccess ||
+    if (hipStreamCreate(&r->gs) != hipSuccess || hipHostMalloc((void **)&r->h_feat, sizeof(float) * RD_FEAT_MF, 0) != hipSuccess ||
         hipHostMalloc((void **)&r->h_iq, sizeof(RADE_COMP) * RD_NMF, 0) != hipSuccess) { r->tx_graph_off = 1; (void)hipGetLastError(); }
     if (!(flags & RADE_VERBOSE_0)) fprintf(stderr, "rade_open: model %s, HIP back end\n", path);
     return r;

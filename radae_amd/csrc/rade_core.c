@@ -1,7 +1,7 @@
 /*
- * rade_core.c -- include/rade_core.h on top of the batched HIP engine: one engine with a single stream per encoder /
+ * rade_core.c -- include/rade_core.h on the single-stream HIP kernels (rade_core_step.hip): one device-resident state per encoder /
  * decoder state, one 40 ms step per call (the call granularity of /root/reference/src/rade_enc.c:55-114 and
- * rade_dec.c:50-102), host buffers in and out.  The step itself is rade_batch_encode / rade_batch_decode with B = 1.
+ * rade_dec.c:50-102), host buffers in and out.  The step itself is one launch of k_core_enc_step / k_core_dec_step.
  */
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
@@ -13,7 +13,6 @@
 #include <time.h>
 
 #include "rade_core.h"
-#include "rade_batch.h"
 #include "rade_host.h"
 #include "rade_dev.h"
 
@@ -115,18 +114,13 @@ int init_radedec(RADEDec *model, const WeightArray *arrays, int output_dim)
 }
 
 /* ---- device side of one state ------------------------------------------------------------------------------------
- * One step = ONE launch of k_core_step (rade_core_step.hip): the whole layer stack for the stream's next 40 ms in a single
- * workgroup, weights row-major in HBM / L2 (int8 layers as one binary16 plane of integers + row scales), GRU and conv state in
- * HBM between calls, input and output in pinned host memory the kernel reads / writes directly (no copy nodes).
- * $RADE_CORE_LAYERWISE=1 selects the previous implementation instead (the batched layer-wise engine with B = 1 replayed as a
- * hipGraph: ~20 dependent launches per step) -- kept for A/B measurements, same results to rounding. */
+ * One step = ONE launch of k_core_enc_step / k_core_dec_step (rade_core_step.hip): the whole layer stack for the stream's next 40 ms
+ * in a single workgroup, weights chunk-major in HBM / L2 (int8 layers as one binary16 plane of integers + row scales), GRU and conv state in
+ * HBM between calls, input and output in pinned host memory the kernel reads / writes directly (no copy nodes). */
 #define CORE_MAXBUF 64
 typedef struct {
-    int dim, layerwise;
-    /* single-launch path */
+    int dim;
     rd_core_args a; void *bufs[CORE_MAXBUF]; int n_bufs; hipStream_t gs; float *h_in, *h_out; int device;
-    /* layer-wise path */
-    rade_batch *eng; float *d_in, *d_out; hipGraphExec_t graph; int calls, graph_off;
 } core_dev;
 
 static void *core_upload(core_dev *d, const void *src, size_t bytes)
@@ -176,14 +170,10 @@ static int core_layer(core_dev *d, rd_mv *L, const float *w, const float *bias, 
 static void dev_close(core_dev *d)
 {
     if (!d) return;
-    if (d->graph) hipGraphExecDestroy(d->graph);
     if (d->h_in) hipHostFree(d->h_in);
     if (d->h_out) hipHostFree(d->h_out);
     if (d->gs) hipStreamDestroy(d->gs);
     for (int i = 0; i < d->n_bufs; i++) hipFree(d->bufs[i]);
-    if (d->eng) rade_batch_close(d->eng);
-    if (d->d_in) hipFree(d->d_in);
-    if (d->d_out) hipFree(d->d_out);
     free(d);
 }
 
@@ -195,15 +185,6 @@ static core_dev *dev_open(const void *blob, int len, int dim, int enc)
     d->device = dv ? atoi(dv) : 0; d->dim = dim;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fprintf(stderr, "rade_core: no HIP device available -- this library has no CPU fallback\n"); free(d); return NULL; }
-    if (getenv("RADE_CORE_LAYERWISE")) {
-        rade_batch_config cfg = { 1, 1, 0, 0, 0, 0.0f };
-        cfg.device = d->device; d->layerwise = 1;
-        d->eng = rade_batch_open_mem(blob, (size_t)len, &cfg);
-        if (!d->eng || hipMalloc((void **)&d->d_in, sizeof(float) * 96) != hipSuccess || hipMalloc((void **)&d->d_out, sizeof(float) * 96) != hipSuccess) { dev_close(d); return NULL; }
-        if (getenv("RADE_NO_GRAPH") || hipStreamCreate(&d->gs) != hipSuccess || hipHostMalloc((void **)&d->h_in, sizeof(float) * 96, 0) != hipSuccess ||
-            hipHostMalloc((void **)&d->h_out, sizeof(float) * 96, 0) != hipSuccess) { d->graph_off = 1; (void)hipGetLastError(); }
-        return d;
-    }
     rd_model m;
     if (hipSetDevice(d->device) != hipSuccess || rd_model_parse(blob, (size_t)len, &m)) { free(d); return NULL; }
     static const int ENC_DIL_[5] = { 1, 2, 2, 2, 2 };
@@ -270,7 +251,7 @@ static int wait_done(volatile unsigned *done, unsigned seq, hipStream_t st)
     return 0;
 }
 
-/* ---- internal (rade_api.c): rade_tx() on the single-stream kernels -- one launch per modem frame (k_tx_frame: three encoder steps + the OFDM
+/* ---- internal (rade_api.c): rade_tx() on the single-stream kernels -- one launch per modem frame (k_tx_frame3: three encoder steps + the OFDM
  * modulator), features and samples in pinned host memory the kernel reads / writes directly, completion by a polled word ------------------------- */
 typedef struct { core_dev *d; float *h_in, *h_iq; unsigned *done; rd_core_args *a_dev; } tx_dev;
 void rd_core_tx_close(void *p)
@@ -285,7 +266,6 @@ void rd_core_tx_close(void *p)
 }
 void *rd_core_tx_open(const void *blob, int len, const rd_tables *d_tab)
 {
-    if (getenv("RADE_CORE_LAYERWISE") || getenv("RADE_TX_LAYERWISE")) return NULL;
     tx_dev *t = calloc(1, sizeof *t);
     if (!t) return NULL;
     t->d = dev_open(blob, len, 84, 1);
@@ -302,14 +282,6 @@ void *rd_core_tx_open(const void *blob, int len, const rd_tables *d_tab)
     /* the kernel reads the layer table through a pointer: the record goes to device memory once (every pointer in it is fixed from here on) */
     if (hipMalloc((void **)&t->a_dev, sizeof *a) != hipSuccess || hipMemcpy(t->a_dev, a, sizeof *a, hipMemcpyHostToDevice) != hipSuccess) { rd_core_tx_close(t); return NULL; }
     return t;
-}
-void rd_core_tx_reset(void *p)
-{
-    tx_dev *t = p; core_dev *d = t->d;
-    (void)hipSetDevice(d->device);
-    (void)hipMemsetAsync(d->a.hist, 0, sizeof(float) * 2 * d->a.W, d->gs);
-    (void)hipMemsetAsync(d->a.h, 0, sizeof(float) * 5 * d->a.H, d->gs);
-    (void)hipStreamSynchronize(d->gs);
 }
 /* features_in: 12 frames x 36 floats (rade_api.c:426-434 packs the first 20 of each + the aux symbol -1 into three rows of 4 x 21); tx_out: 960 complex samples */
 int rd_core_tx_frame(void *p, const float *features_in, float *tx_out)
@@ -339,7 +311,6 @@ static void core_reset(int *initialized, void **dev)
 {
     core_dev *d = *initialized ? *dev : NULL;
     if (!d) return;
-    if (d->layerwise) { dev_close(d); *initialized = 0; *dev = NULL; return; }      /* re-opened by the next step */
     (void)hipSetDevice(d->device);
     (void)hipMemsetAsync(d->a.hist, 0, sizeof(float) * 2 * d->a.W, d->gs);
     (void)hipMemsetAsync(d->a.h, 0, sizeof(float) * 5 * d->a.H, d->gs);
@@ -349,46 +320,16 @@ void rade_reset_encoder(RADEEncState *s) { if (s) core_reset(&s->initialized, &s
 void rade_reset_decoder(RADEDecState *s) { if (s) core_reset(&s->initialized, &s->dev); }
 
 /* one step: in[n_in] (host) -> out[n_out] (host) */
-static int core_step(core_dev *d, int enc, const float *in, int n_in, float *out, int n_out)
+static int core_step(core_dev *d, const float *in, int n_in, float *out, int n_out)
 {
-    if (!d->layerwise) {
-        if (hipSetDevice(d->device) != hipSuccess) return -1;
-        memcpy(d->h_in, in, sizeof(float) * n_in);
-        volatile unsigned *done = (volatile unsigned *)(d->h_out + 96);
-        d->a.seq++;
-        if (rd_launch_core_step(&d->a, d->gs)) return -1;
-        /* the kernel writes its completion word into pinned host memory after the output: polling it returns as soon as the result is
-         * there (a stream synchronisation goes through the runtime's interrupt path: ~100 us of wake-up for a 40 us kernel); a kernel
-         * that has not signalled after RD_POLL_US is waited for the ordinary way, which also surfaces device errors (wait_done) */
-        if (wait_done(done, d->a.seq, d->gs)) return -1;
-        memcpy(out, d->h_out, sizeof(float) * n_out);
-        return 0;
-    }
-    int ok = 0;
-    if (d->calls > 0 && !d->graph_off) {
-        if (!d->graph) {                                       /* second call: record the sequence (nothing runs during capture) */
-            hipGraph_t g = NULL;
-            int c = hipStreamBeginCapture(d->gs, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (c) {
-                c = hipMemcpyAsync(d->d_in, d->h_in, sizeof(float) * n_in, hipMemcpyHostToDevice, d->gs) == hipSuccess &&
-                    (enc ? rade_batch_encode(d->eng, d->d_in, 1, d->d_out, d->gs) : rade_batch_decode(d->eng, d->d_in, 1, d->d_out, 0, d->gs)) == 1 &&
-                    hipMemcpyAsync(d->h_out, d->d_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, d->gs) == hipSuccess;
-                if (hipStreamEndCapture(d->gs, &g) != hipSuccess) c = 0;
-            }
-            if (c && hipGraphInstantiate(&d->graph, g, NULL, NULL, 0) != hipSuccess) { c = 0; d->graph = NULL; }
-            if (g) hipGraphDestroy(g);
-            if (!c) { d->graph_off = 1; (void)hipGetLastError(); }
-        }
-        if (d->graph) {
-            memcpy(d->h_in, in, sizeof(float) * n_in);
-            if (hipGraphLaunch(d->graph, d->gs) == hipSuccess && hipStreamSynchronize(d->gs) == hipSuccess) { memcpy(out, d->h_out, sizeof(float) * n_out); ok = 1; }
-        }
-    }
-    if (!ok) ok = hipMemcpy(d->d_in, in, sizeof(float) * n_in, hipMemcpyHostToDevice) == hipSuccess &&
-                  (enc ? rade_batch_encode(d->eng, d->d_in, 1, d->d_out, NULL) : rade_batch_decode(d->eng, d->d_in, 1, d->d_out, 0, NULL)) == 1 &&
-                  hipMemcpy(out, d->d_out, sizeof(float) * n_out, hipMemcpyDeviceToHost) == hipSuccess;
-    d->calls++;
-    return ok ? 0 : -1;
+    if (hipSetDevice(d->device) != hipSuccess) return -1;
+    memcpy(d->h_in, in, sizeof(float) * n_in);
+    volatile unsigned *done = (volatile unsigned *)(d->h_out + 96);
+    d->a.seq++;
+    if (rd_launch_core_step(&d->a, d->gs)) return -1;
+    if (wait_done(done, d->a.seq, d->gs)) return -1;        /* the completion word the kernel writes after the output */
+    memcpy(out, d->h_out, sizeof(float) * n_out);
+    return 0;
 }
 
 static void die(const char *what) { fprintf(stderr, "%s: device error (this library has no CPU fallback)\n", what); exit(1); }
@@ -396,13 +337,13 @@ static void die(const char *what) { fprintf(stderr, "%s: device error (this libr
 void rade_core_encoder(RADEEncState *s, const RADEEnc *model, float *z, const float *features, int arch, int bottleneck)
 {
     (void)arch;
-    if (!s->initialized) {                        /* first step after rade_init_encoder(): zero state = a fresh engine */
+    if (!s->initialized) {                        /* first step after rade_init_encoder(): zero state = a fresh device state */
         s->dev = dev_open(model->blob, model->blob_len, model->input_dim, 1);
         if (!s->dev) die("rade_core_encoder");
         s->initialized = 1;
     }
     core_dev *d = s->dev;
-    if (core_step(d, 1, features, d->dim, z, RADE_LATENT_DIM)) die("rade_core_encoder");
+    if (core_step(d, features, d->dim, z, RADE_LATENT_DIM)) die("rade_core_encoder");
     if (bottleneck == 1) for (int i = 0; i < RADE_LATENT_DIM; i++) z[i] = tanhf(z[i]);      /* rade_enc.c:113 / radae_base.py:281-284 */
 }
 
@@ -415,5 +356,5 @@ void rade_core_decoder(RADEDecState *s, const RADEDec *model, float *features, c
         s->initialized = 1;
     }
     core_dev *d = s->dev;
-    if (core_step(d, 0, z_hat, RADE_LATENT_DIM, features, d->dim)) die("rade_core_decoder");
+    if (core_step(d, z_hat, RADE_LATENT_DIM, features, d->dim)) die("rade_core_decoder");
 }

@@ -16,7 +16,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include "rade_devutil.h"
 
@@ -25,7 +24,7 @@
 #define CS_PS 320                 // row stride of a partial-sum area: 288 rows padded to 5 x 64
 #define CS_WMAX 864
 
-// weights are read through pointers that k_tx_frame / k_tx_frame3 load from a record in device memory: generic pointers, i.e. flat loads, which count on
+// weights are read through pointers that k_tx_frame3 loads from a record in device memory: generic pointers, i.e. flat loads, which count on
 // the LDS wait counter too -- every LDS wait of a stage then also waited for the weight prefetch of the next.  They ARE global memory: say so.
 template <typename T> __device__ __forceinline__ T cs_gload(const T *p) { return *(const __attribute__((address_space(1))) T *)p; }
 __device__ __forceinline__ float cs_clamp1(float x) { return fminf(fmaxf(x, -1.0f), 1.0f); }
@@ -161,17 +160,15 @@ __device__ __forceinline__ void cs_enc_layer(CsShared *sh, const rd_core_args &a
     CS_SYNC();
 }
 
-// one encoder step; FIRST: conv history and GRU states come from HBM (else they are in LDS, left there by the step before); LASTSTEP: they go back.
+// one encoder step: conv history and GRU states come from HBM and the history goes back there.
 // in: the step's n_in inputs; zout: its 80 latents (any address space the workgroup can write)
-__device__ __forceinline__ void cs_enc_step(CsShared *sh, const rd_core_args &a, const float *in, float *zout, const bool FIRST, const bool LASTSTEP)
+__device__ __forceinline__ void cs_enc_step(CsShared *sh, const rd_core_args &a, const float *in, float *zout)
 {
     const int tid = threadIdx.x, W = 864, H = 64;
     WQ<3, 1> g0, h0;
     cs_issue<3, 1>(a.gin[0], g0); cs_issue<3, 1>(a.ghh[0], h0);
-    if (FIRST) {
-        for (int i = tid; i < 2 * W; i += CS_THREADS) sh->hist[i / W][i % W] = a.hist[i];
-        if (tid < 5 * H) sh->h[tid / H][tid % H] = a.h[tid];
-    }
+    for (int i = tid; i < 2 * W; i += CS_THREADS) sh->hist[i / W][i % W] = a.hist[i];
+    if (tid < 5 * H) sh->h[tid / H][tid % H] = a.h[tid];
     if (tid < 96) sh->vin[tid] = tid < a.n_in ? in[tid] : 0.0f;
     CS_SYNC();
     cs_f32_product<2>(a.dense1, 1, sh->vin, sh->pa);                // dense1 + tanh (radae_base.py:263)
@@ -187,19 +184,10 @@ __device__ __forceinline__ void cs_enc_step(CsShared *sh, const rd_core_args &a,
     cs_enc_layer<9, 19, 11, false>(sh, a, 3, 544, g3, g4);
     cs_enc_layer<11, 24, 11, true>(sh, a, 4, 704, g4, g4);
     cs_f32_product<14>(a.out, 2, sh->x, sh->pa);                    // z_dense, linear (bottleneck 3; the tanh of bottleneck 1 is the caller's)
-    if (LASTSTEP) { for (int i = tid; i < W; i += CS_THREADS) { a.hist[W + i] = sh->hist[0][i]; a.hist[i] = sh->x[i]; } }      // history of the next step
+    for (int i = tid; i < W; i += CS_THREADS) { a.hist[W + i] = sh->hist[0][i]; a.hist[i] = sh->x[i]; }      // history of the next step
     CS_SYNC();
     if (tid < a.n_out) zout[tid] = cs_row(a.out, sh->pa, tid);
-    if (!LASTSTEP) { for (int i = tid; i < W; i += CS_THREADS) { const float v = sh->hist[0][i]; sh->hist[1][i] = v; sh->hist[0][i] = sh->x[i]; } }   // (each thread moves its own columns)
     CS_SYNC();
-}
-
-// the same step as a REAL function for k_tx_frame's loop (one copy of the code with its own register allocation; inlined into the loop the
-// three steps' weight prefetches overlapped and 400 registers spilled).  The layer table is read through a pointer to device memory: a by-value
-// struct handed to a real function would live in scratch memory.
-__device__ __attribute__((noinline)) void cs_enc_step_fn(CsShared *sh, const rd_core_args *ap, int st, float *zs)
-{
-    cs_enc_step(sh, *ap, ap->in + st * ap->n_in, zs + st * RD_LATENT, st == 0, st == 2);
 }
 
 __global__ __launch_bounds__(CS_THREADS) void k_core_enc_step(rd_core_args a)
@@ -207,7 +195,7 @@ __global__ __launch_bounds__(CS_THREADS) void k_core_enc_step(rd_core_args a)
     extern __shared__ __attribute__((aligned(16))) unsigned char cs_raw[];
     CsShared *sh = (CsShared *)cs_raw;
     const int tid = threadIdx.x;
-    cs_enc_step(sh, a, a.in, a.out_vec, true, true);
+    cs_enc_step(sh, a, a.in, a.out_vec);
     if (tid < a.n_out) __threadfence_system();
     CS_SYNC();
     // completion word in the caller's (pinned host) memory: the host polls it instead of going through a stream synchronisation,
@@ -277,47 +265,14 @@ __global__ __launch_bounds__(CS_THREADS) void k_core_dec_step(rd_core_args a)
     if (tid == 0 && a.done) { __threadfence_system(); *(volatile unsigned *)a.done = a.seq; }
 }
 
-// ---- rade_tx() as ONE launch: the three encoder steps of a modem frame (state in LDS between them) and the OFDM modulator (dsp.py:340-378:
-// pilot row + four data rows, 30 -> 160 IDFT, cyclic prefix, tanh limiter) in the same workgroup; a.in = 3 x 84 packed features, a.iq_out = 960
-// complex samples (both pinned host memory the kernel reads / writes directly), then the completion word.  (The reference's rade_tx runs the
-// same sequence through CPython: rade_api.c:403-445, radae_txe.py:108-135.)
-__global__ __launch_bounds__(CS_THREADS) void k_tx_frame(const rd_core_args *ap, unsigned seq)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char cs_raw[];
-    CsShared *sh = (CsShared *)cs_raw;
-    __shared__ float zs[RD_ZMF];
-    const int tid = threadIdx.x;
-#pragma unroll 1
-    for (int st = 0; st < 3; st++) cs_enc_step_fn(sh, ap, st, zs);
-    const rd_tables *tab = ap->tab;
-    float2 *out = (float2 *)ap->iq_out;
-    if (tid < RD_M) {
-        f32x2 acc[RD_NS + 1];
-#pragma unroll
-        for (int s = 0; s <= RD_NS; s++) acc[s] = (f32x2){ 0.0f, 0.0f };
-#pragma unroll 6
-        for (int c = 0; c < RD_NC; c++) {
-            const float2 w = ld2(tab->Winv[c], tid);
-            acc[0] = idft_term(acc[0], make_float2(tab->P[c] * tab->pilot_gain, 0.0f * tab->pilot_gain), w);
-#pragma unroll
-            for (int s = 1; s <= RD_NS; s++) { const int k = (s - 1) * RD_NC + c; acc[s] = idft_term(acc[s], make_float2(zs[2 * k], zs[2 * k + 1]), w); }
-        }
-#pragma unroll
-        for (int s = 0; s <= RD_NS; s++) {
-            const float2 v = pa_limit(make_float2(acc[s][0], acc[s][1]));                  // tanh(|x|) e^{j angle(x)} (radae.py:218, dsp.py:377)
-            out[s * RD_SYM + RD_NCP + tid] = v;
-            if (tid >= RD_M - RD_NCP) out[s * RD_SYM + tid - (RD_M - RD_NCP)] = v;
-        }
-        __threadfence_system();
-    }
-    CS_SYNC();
-    if (tid == 0 && ap->done) { __threadfence_system(); *(volatile unsigned *)ap->done = seq; }
-}
-// ---- rade_tx() with the frame's three encoder steps taken through every layer TOGETHER -----------------------------------------------------------
-// k_tx_frame above runs the step three times: 3 x 17 dependent stages, each worth an L2 round trip for its weights.  Here a layer's weight
-// fragments are fetched ONCE and applied to the three rows of the frame (the feed-forward pieces: dense1, the five input projections, the five
+// ---- rade_tx() as ONE launch: the frame's three encoder steps taken through every layer TOGETHER, then the OFDM modulator (dsp.py:340-378: pilot
+// row + four data rows, 30 -> 160 IDFT, cyclic prefix, tanh limiter) in the same workgroup; a.in = 3 x 84 packed features, a.iq_out = 960 complex
+// samples (both pinned host memory the kernel reads / writes directly), then the completion word.  (The reference's rade_tx runs the same sequence
+// through CPython: rade_api.c:403-445, radae_txe.py:108-135.)
+// Three launches of the step kernel k_core_enc_step would be 3 x 17 dependent stages, each worth an L2 round trip for its weights.  Here a layer's
+// weight fragments are fetched ONCE and applied to the three rows of the frame (the feed-forward pieces: dense1, the five input projections, the five
 // convs, z_dense -- 12 weight stages per frame instead of 51); only the W_hh recurrences stay serial, three short steps per layer on fragments
-// that are already in registers.  Same chunk -> wavefront assignment and the same order of partial sums per row as the step kernel, so the
+// that are already in registers.  Same chunk -> wavefront assignment and the same order of partial sums per row as k_core_enc_step, so the
 // latents are the step kernel's, bit for bit.
 struct CsShared3 {
     __attribute__((aligned(16))) float x[3][CS_WMAX];         // the DenseNet concat rows of the frame's three steps
@@ -565,14 +520,11 @@ extern "C" int rd_launch_tx_frame(const rd_core_args *a_dev, unsigned seq, rd_st
 {
     static int attr_dev[64];
     int dev_ = 0; (void)hipGetDevice(&dev_);
-    static int by_step = -1; if (by_step < 0) by_step = getenv("RADE_TX_FRAME_BY_STEP") ? 1 : 0;      /* A/B: the three-launches-in-one form (k_tx_frame) */
     if (!attr_dev[dev_ & 63]) {
-        (void)hipFuncSetAttribute((const void *)k_tx_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(CsShared));
         (void)hipFuncSetAttribute((const void *)k_tx_frame3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(CsShared3));
         attr_dev[dev_ & 63] = 1;
     }
-    if (by_step) hipLaunchKernelGGL(k_tx_frame, dim3(1), dim3(CS_THREADS), sizeof(CsShared), (hipStream_t)s, a_dev, seq);
-    else hipLaunchKernelGGL(k_tx_frame3, dim3(1), dim3(CS_THREADS), sizeof(CsShared3), (hipStream_t)s, a_dev, seq);
+    hipLaunchKernelGGL(k_tx_frame3, dim3(1), dim3(CS_THREADS), sizeof(CsShared3), (hipStream_t)s, a_dev, seq);
     return (int)hipGetLastError();
 }
 

@@ -783,27 +783,28 @@ def test_replicas_agree_over_many_fresh_launches(Engine, torch_dev):
         eng.close()
 
 
-def test_tx_frame_three_rows_equals_step_kernel(tmp_path):
-    """rade_tx as one launch that takes the frame's three encoder steps through each layer together (k_tx_frame3) against the form that runs the step
-    three times (k_tx_frame, $RADE_TX_FRAME_BY_STEP=1): same chunk -> wavefront assignment, same order of partial sums per row -- the transmit
-    samples of 20 consecutive frames (state carried from frame to frame) are equal bit for bit.  Two processes: the switch is read once per process."""
-    import subprocess, sys
-    script = (
-        "import sys, numpy as np\n"
-        "sys.path.insert(0, %r)\n"
-        "from radae_amd import api\n"
-        "from radae_amd.channel_tools import synth_features\n"
-        "f = synth_features(4242, 240); tx = api.radae_tx(); out = np.zeros((20, 960), np.complex64)\n"
-        "for k in range(20): tx.do_radae_tx(f[12 * k:12 * k + 12].ravel(), out[k])\n"
-        "np.save(sys.argv[1], out)\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for name, extra in (("three", {}), ("step", {"RADE_TX_FRAME_BY_STEP": "1"})):
-        f = str(tmp_path / (name + ".npy"))
-        env = dict(os.environ); env.pop("RADE_TX_FRAME_BY_STEP", None); env.update(extra)
-        subprocess.run([sys.executable, "-c", script, f], check=True, env=env, timeout=300)
-        outs.append(np.load(f))
-    assert np.abs(outs[0]).max() > 0.1
-    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
+def test_tx_frame3_equals_core_step_and_ofdm_mod(Engine, torch_dev):
+    """rade_tx as one launch that takes the frame's three encoder steps through each layer together (k_tx_frame3) against the step kernel
+    (k_core_enc_step, through rade_core.h) followed by the batched engine's modulator (k_ofdm_mod, through rade_batch_tx_latents): same chunk ->
+    wavefront assignment, same order of partial sums per row, the same IDFT term and limiter -- the transmit samples of 20 consecutive frames
+    (state carried from frame to frame) are equal bit for bit."""
+    import torch
+    from radae_amd import api, core
+    from radae_amd.channel_tools import synth_features
+    f = synth_features(4242, 240)
+    tx = api.radae_tx(); out = np.zeros((20, 960), np.complex64)
+    for k in range(20):
+        tx.do_radae_tx(f[12 * k:12 * k + 12].ravel(), out[k])
+    tx.h.close()
+    rows = np.concatenate([f[:, :20], -np.ones((240, 1), np.float32)], 1).reshape(60, 84)      # rade_tx's packing: 4 frames x (20 features, -1) per step
+    enc = core.CoreEncoder()
+    z = np.stack([enc.step(r) for r in rows])
+    enc.close()
+    eng = Engine(1, max_tx_mf=20)
+    ref = eng.tx_latents(torch.tensor(z.reshape(1, 60, 80), device=torch_dev)).cpu().numpy().reshape(20, 960)
+    eng.close()
+    assert np.abs(out).max() > 0.1
+    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
 
 
 def test_single_stream_c_abi(golden):
