@@ -133,6 +133,16 @@ int rade_batch_channel(rade_batch *h, const void *tx_dev, long tx_stride, void *
 int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, void *rx_out_dev, long rx_stride,
                           const rade_channel_params *p, void *stream);
 
+/* per-stream values of rade_channel_params: [B] host arrays; a NULL member = p's scalar for every stream.
+ * Stream b of a call gives what a call with p->sigma, freq_offset, df_dt set to stream b's values gives for stream b, bit for bit (Philox noise is keyed by
+ * (seed, stream)), so a loss-vs-Eb/No curve (points x channels x utterances) is one batch.  The values are copied to the device ahead of the launches (the call
+ * synchronises `stream` once for that); rade_batch_channel / rade_batch_tx_channel are these calls with ps = NULL. */
+typedef struct { const float *sigma, *freq_offset, *df_dt; } rade_channel_streams;
+int rade_batch_channel_streams(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride,
+                               const rade_channel_params *p, const rade_channel_streams *ps, void *stream);
+int rade_batch_tx_channel_streams(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride,
+                                  void *rx_out_dev, long rx_stride, const rade_channel_params *p, const rade_channel_streams *ps, void *stream);
+
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the
  * n_taps Gaussian-PSD FIR (taps designed by the caller, e.g. radae_amd/channel_tools.py), linearly interpolated to
@@ -199,6 +209,22 @@ typedef struct {
 } rade_ideal_rx_params;
 int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n_mf, const rade_ideal_rx_params *p,
                         float *z_hat_dev, float *features_out_dev, void *stream);
+
+/* ---- scoring ----------------------------------------------------------------------------------
+ * loss.py:find_loss (:64-91) over distortion_loss (radae_base.py:50-68, first 20 features), every stream in one launch.
+ * features_dev + b*f_stride: n_in_host[b] rows of f_row floats (f_row >= 20), the transmitted features;
+ * hat_dev + b*h_stride: n_hat_host[b] rows of h_row floats (h_row >= 20), the decoded features
+ *   (rade_batch_rx's features_out is h_row = 36 with 12 rows per valid modem frame).
+ * For a stream with 0 < n_hat <= n_in: loss_host[b] = min of distortion_loss(features[s : s + n_hat], hat) over s = 0 and
+ *   s in [0, n_in - n_hat), the reference's range: s = n_in - n_hat is never tried. The first of equal values wins.
+ *   start_host[b] = that s (acq_time = 0.01 s * start). Any other stream: loss NaN, start -1.
+ *   Bit-equal to the reference's float32 frame terms summed in double in frame order (rade_loss.hip).
+ * frame_loss_dev, optional, [B][fl_stride] float32: loss.py:83-88's per-frame curve, distortion_loss(features[s + f], hat[f])
+ *   for f in [0, n_hat - s) (fl_stride >= every scored n_hat; other entries are not written).
+ * Synchronises `stream`. Returns the number of streams scored, or < 0 on bad arguments. */
+int rade_batch_loss(rade_batch *h, const float *features_dev, long f_stride, int f_row, const int *n_in_host,
+                    const float *hat_dev, long h_stride, int h_row, const int *n_hat_host,
+                    double *loss_host, int *start_host, float *frame_loss_dev, long fl_stride, void *stream);
 
 /* per-call trace record (tests): mirrors what radae_rxe.py prints per frame at -v 2 */
 typedef struct {

@@ -187,12 +187,27 @@ typedef struct {
 } rd_irx_args;
 int rd_launch_irx(const rd_irx_args *a, rd_stream_t s);
 
+/* time-aligned distortion loss of every stream (rade_loss.hip: loss.py:find_loss :64-91 over distortion_loss, radae_base.py:50-68, first 20 features):
+ * k_loss_offsets per (block of RD_LOSS_WG offsets, stream), k_loss_pick per stream, k_loss_frames per (256 frames, stream) when frame_loss is given */
+#define RD_LOSS_WG 64
+typedef struct {
+    const float *feat; long f_stride; int f_row;     /* stream b at feat + b * f_stride, rows f_row floats apart */
+    const float *hat; long h_stride; int h_row;
+    const int *len;                                  /* device [2][B]: n_in, n_hat */
+    double *part_v; int *part_s; int n_blk;          /* [B][n_blk]: best (loss, offset) of each block of offsets; n_blk = 0: no stream is scored */
+    double *loss; int *start;                        /* [B] results: NaN / -1 for a stream without 0 < n_hat <= n_in */
+    float *frame_loss; long fl_stride; int max_hat;  /* optional [B][fl_stride] per-frame curve at the chosen offset; max_hat = largest scored n_hat */
+    int B;
+} rd_loss_args;
+int rd_launch_loss(const rd_loss_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */
     const void *mp;                    /* optional [B][n_sig] c64: the multipath output k_ofdm_mod_mp left (scratch then holds its n_sig / 960 per-frame power sums per stream) */
     int B, n_sig, n_pre, n_post, with_eoo; float sigma, freq_offset, df_dt; unsigned long long seed;
     float sine_amp, sine_freq, rx_gain;
+    const float *ps;                   /* optional [3][B]: sigma, freq_offset, df_dt of every stream (rade_channel_streams), read in place of the three scalars */
 } rd_chan_args;
 int rd_launch_channel(const rd_chan_args *a, rd_stream_t s);
 /* Doppler-spread generator: taps_dev [n_taps] f32, noise optional, G [B][n_out][2] c64 */

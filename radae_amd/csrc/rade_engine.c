@@ -94,6 +94,8 @@ struct rade_batch {
     double *irx_part; long irx_part_cap; float *irx_foff; long long *irx_err;   /* rade_batch_rx_ideal: per-frame pilot power [B][cap], offsets [2][B], error counts [B] */
     rd_bpf_state *tx_bpf, *tx_bpf_init; void *tx_raw; float *tx_chain; float *eoo_filt;   /* eoo_filt [B][Neoo] c64: the end-of-over frame as transmitted (filtered + clipped) for the channel's with_eoo */
     void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
+    float *chan_ps, *chan_ps_host;            /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */
+    int *loss_len; double *loss_res, *loss_part; int loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
     int *rx_avail, *rx_acc, *rx_progress, *rx_status;
@@ -417,7 +419,7 @@ void rade_batch_close(rade_batch *h)
     ON_DEV(h);
     void *bufs[] = { h->d_tab, h->enc_xin, h->enc_x, h->enc_xf, h->enc_gi, h->enc_z, h->eoo, h->eoo_bits, h->chan_scratch, h->rx_st, h->rx_round, h->rx_avail,
                      h->rx_progress /* + rx_acc, rx_status */, h->wg_cycles, h->zrows, h->dec_x, h->dec_gi, h->dec_hbuf, h->feat84, h->trace, h->trace_z, h->d_lcg_seeds, h->dtcache, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->rx_filt, h->bpf_chain, h->bpf16, h->tx_bpf, h->tx_bpf_init, h->tx_raw, h->tx_chain, h->eoo_filt, h->corrq16, h->corra16, h->vm, h->chan_mp, h->wfwd16,
-                     h->irx_part, h->irx_foff, h->irx_err };
+                     h->irx_part, h->irx_foff, h->irx_err, h->chan_ps, h->loss_len, h->loss_res, h->loss_part };
     for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; i++) if (bufs[i]) hipFree(bufs[i]);
     free_lin(&h->enc_dense1); free_lin(&h->enc_zdense); free_lin(&h->dec_dense1); free_lin(&h->dec_output);
     for (int l = 0; l < 5; l++) {
@@ -426,6 +428,7 @@ void rade_batch_close(rade_batch *h)
         for (int i = 0; i < 9; i++) if (p[i]) hipFree(p[i]);
     }
     if (h->h_small) hipHostFree(h->h_small);
+    if (h->chan_ps_host) hipHostFree(h->chan_ps_host);
     if (h->ev_block) hipEventDestroy(h->ev_block);
     __atomic_sub_fetch(&g_engines_open, 1, __ATOMIC_RELAXED);
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) if (h->prof_ev[i]) hipEventDestroy(h->prof_ev[i]);
@@ -661,15 +664,36 @@ float rade_sigma_from_EbNodB_bn1(float EbNodB)
     return powf(EbNo * (float)RD_M, -0.5f);
 }
 
-int rade_batch_channel(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride, const rade_channel_params *p, void *stream)
+/* the [3][B] per-stream sigma, freq_offset, df_dt of a call on the device (rd_chan_args.ps), a NULL member filled with p's scalar; *out = NULL when ps gives none.
+ * Uploaded like rade_batch_rx_ideal's offsets: through pinned memory, the stream synchronised before the staging copy can be reused. */
+static int chan_streams_upload(rade_batch *h, const rade_channel_params *p, const rade_channel_streams *ps, void *stream, const float **out)
 {
-    ON_DEV(h);
+    *out = NULL;
+    if (!ps || (!ps->sigma && !ps->freq_offset && !ps->df_dt)) return 0;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->chan_ps && !(h->chan_ps = dev_zeros(sizeof(float) * 3 * B))) return -1;
+    if (!h->chan_ps_host && hipHostMalloc((void **)&h->chan_ps_host, sizeof(float) * 3 * B, 0) != hipSuccess) { h->chan_ps_host = NULL; return -1; }
+    float *f = h->chan_ps_host;
+    for (int b = 0; b < B; b++) {
+        f[b] = ps->sigma ? ps->sigma[b] : p->sigma;
+        f[B + b] = ps->freq_offset ? ps->freq_offset[b] : p->freq_offset;
+        f[2 * B + b] = ps->df_dt ? ps->df_dt[b] : p->df_dt;
+    }
+    if (hipMemcpyAsync(h->chan_ps, f, sizeof(float) * 3 * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    *out = h->chan_ps;
+    return 0;
+}
+
+/* rade_batch_channel_streams with the per-stream values already on the device (ps_dev, or NULL) */
+static int channel_dev(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride, const rade_channel_params *p, const float *ps_dev, void *stream)
+{
     if (h->tx_linear && p->with_eoo) return -1;
     rd_chan_args a;
     memset(&a, 0, sizeof a);
     a.tab = h->d_tab; a.tx = tx_dev; a.tx_stride = tx_stride; a.rx = rx_out_dev; a.rx_stride = rx_stride; a.G = p->G_dev; a.noise = p->noise_dev;
     a.eoo = h->eoo; a.scratch = h->chan_scratch; a.B = h->B; a.n_sig = p->n_sig; a.n_pre = p->n_pre; a.n_post = p->n_post; a.with_eoo = p->with_eoo;
-    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed;
+    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed; a.ps = ps_dev;
     a.sine_amp = p->sine_amp; a.sine_freq = p->sine_freq; a.rx_gain = p->rx_gain != 0.0f ? p->rx_gain : 1.0f;
     if (h->tx_bpf && p->with_eoo) {        /* what radae_tx --txbpf transmits after the last frame: the end-of-over frame through the Tx band-pass filter and the clip,
                                             * the filter state carried on from the frames before it (radae_txe.py:138-144) */
@@ -685,18 +709,34 @@ int rade_batch_channel(rade_batch *h, const void *tx_dev, long tx_stride, void *
     return p->n_pre + p->n_sig + (p->with_eoo ? RD_NEOO : 0) + p->n_post;
 }
 
+int rade_batch_channel_streams(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride,
+                               const rade_channel_params *p, const rade_channel_streams *ps, void *stream)
+{
+    ON_DEV(h);
+    const float *ps_dev;
+    if (chan_streams_upload(h, p, ps, stream, &ps_dev)) return -1;
+    return channel_dev(h, tx_dev, tx_stride, rx_out_dev, rx_stride, p, ps_dev, stream);
+}
+
+int rade_batch_channel(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride, const rade_channel_params *p, void *stream)
+{
+    return rade_batch_channel_streams(h, tx_dev, tx_stride, rx_out_dev, rx_stride, p, NULL, stream);
+}
+
 /* ---- transmit + channel in one pass (RADAE.forward, radae.py:529-589: latents -> OFDM -> multipath -> noise) -------------------
  * The modulator applies the two-path model while a frame's samples are in LDS and leaves the power sums, so tx is never re-read and
  * k_chan_power does not run; without G (AWGN only) it is the two calls back to back. */
-int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, void *rx_out_dev, long rx_stride,
-                          const rade_channel_params *p, void *stream)
+int rade_batch_tx_channel_streams(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, void *rx_out_dev, long rx_stride,
+                                  const rade_channel_params *p, const rade_channel_streams *ps, void *stream)
 {
     ON_DEV(h);
     if (!h || !p || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84 || p->n_sig != n_mf * RD_NMF || !rx_out_dev || (h->tx_linear && p->with_eoo)) return -1;
+    const float *ps_dev;                   /* (uploaded ahead of the transmit launches: its synchronisation waits only for what the stream held before this call) */
+    if (chan_streams_upload(h, p, ps, stream, &ps_dev)) return -1;
     if (!p->G_dev || h->tx_bpf) {          /* (the Tx band-pass filter sits between the modulator and the channel: the two calls back to back) */
         if (!iq_out_dev) return -1;
         if (rade_batch_tx(h, features_dev, n_mf, iq_out_dev, iq_stride, NULL, stream) != p->n_sig) return -1;
-        return rade_batch_channel(h, iq_out_dev, iq_stride, rx_out_dev, rx_stride, p, stream);
+        return channel_dev(h, iq_out_dev, iq_stride, rx_out_dev, rx_stride, p, ps_dev, stream);
     }
     if (!h->chan_mp && !(h->chan_mp = dev_zeros(sizeof(float) * 2 * (size_t)h->B * h->max_tx_mf * RD_NMF))) return -1;
     const int B = h->B, T = 3 * n_mf;
@@ -710,12 +750,18 @@ int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, vo
     memset(&a, 0, sizeof a);
     a.tab = h->d_tab; a.tx = NULL; a.tx_stride = 0; a.rx = rx_out_dev; a.rx_stride = rx_stride; a.G = p->G_dev; a.noise = p->noise_dev; a.mp = h->chan_mp;
     a.eoo = h->eoo; a.scratch = h->chan_scratch; a.B = B; a.n_sig = p->n_sig; a.n_pre = p->n_pre; a.n_post = p->n_post; a.with_eoo = p->with_eoo;
-    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed;
+    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed; a.ps = ps_dev;
     a.sine_amp = p->sine_amp; a.sine_freq = p->sine_freq; a.rx_gain = p->rx_gain != 0.0f ? p->rx_gain : 1.0f;
     PROF_BEGIN(h, stream);
     if (rd_launch_channel(&a, stream)) return -1;
     PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
     return p->n_pre + p->n_sig + (p->with_eoo ? RD_NEOO : 0) + p->n_post;
+}
+
+int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, void *rx_out_dev, long rx_stride,
+                          const rade_channel_params *p, void *stream)
+{
+    return rade_batch_tx_channel_streams(h, features_dev, n_mf, iq_out_dev, iq_stride, rx_out_dev, rx_stride, p, NULL, stream);
 }
 
 int rade_batch_multipath_gen(rade_batch *h, const float *fir_taps_host, int n_taps, int low_ratio, int n_out,
@@ -836,6 +882,51 @@ int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n
     }
     if (features_out_dev && rade_batch_decode(h, z_hat_dev, 3 * n_mf, features_out_dev, 1, stream) != 3 * n_mf) return -1;
     return n_mf;
+}
+
+/* ---- loss.py:find_loss of every stream (rade_loss.hip) ------------------------------------------------------------------------ */
+int rade_batch_loss(rade_batch *h, const float *features_dev, long f_stride, int f_row, const int *n_in_host,
+                    const float *hat_dev, long h_stride, int h_row, const int *n_hat_host,
+                    double *loss_host, int *start_host, float *frame_loss_dev, long fl_stride, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !features_dev || !hat_dev || !n_in_host || !n_hat_host || !loss_host || !start_host || f_row < 20 || h_row < 20 || f_stride < 0 || h_stride < 0) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    int n_blk = 0, max_hat = 0, n_scored = 0;
+    for (int b = 0; b < B; b++) {
+        const int n = n_in_host[b], m = n_hat_host[b];
+        if (m <= 0 || m > n) continue;
+        const int nb = ((n > m ? n - m : 1) + RD_LOSS_WG - 1) / RD_LOSS_WG;
+        if (nb > n_blk) n_blk = nb;
+        if (m > max_hat) max_hat = m;
+        if (frame_loss_dev && fl_stride < m) return -1;   /* a stream's curve has at most n_hat frames */
+        n_scored++;
+    }
+    if (!h->loss_len && !(h->loss_len = dev_zeros(sizeof(int) * 2 * B))) return -1;
+    if (!h->loss_res && !(h->loss_res = dev_zeros((sizeof(double) + sizeof(int)) * B))) return -1;
+    if (n_blk > h->loss_part_cap) {
+        if (h->loss_part) { hipStreamSynchronize(st); hipFree(h->loss_part); }
+        h->loss_part = dev_zeros((sizeof(double) + sizeof(int)) * (size_t)B * n_blk);
+        h->loss_part_cap = h->loss_part ? n_blk : 0;
+        if (!h->loss_part) return -1;
+    }
+    /* pinned scratch (8 + 8 B ints): the lengths [2][B] ints, then the results [B] doubles + [B] ints; the call synchronises before it returns */
+    int *len = h->h_small;
+    double *res = (double *)(h->h_small + 2 * B);
+    for (int b = 0; b < B; b++) { len[b] = n_in_host[b]; len[B + b] = n_hat_host[b]; }
+    if (hipMemcpyAsync(h->loss_len, len, sizeof(int) * 2 * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    rd_loss_args a;
+    memset(&a, 0, sizeof a);
+    a.feat = features_dev; a.f_stride = f_stride; a.f_row = f_row; a.hat = hat_dev; a.h_stride = h_stride; a.h_row = h_row; a.len = h->loss_len;
+    a.part_v = h->loss_part; a.part_s = h->loss_part ? (int *)(h->loss_part + (size_t)B * h->loss_part_cap) : NULL; a.n_blk = n_blk;
+    a.loss = h->loss_res; a.start = (int *)(h->loss_res + B);
+    a.frame_loss = frame_loss_dev; a.fl_stride = fl_stride; a.max_hat = max_hat; a.B = B;
+    if (rd_launch_loss(&a, stream)) return -1;
+    if (hipMemcpyAsync(res, h->loss_res, (sizeof(double) + sizeof(int)) * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    const int *rs = (const int *)(res + B);
+    for (int b = 0; b < B; b++) { loss_host[b] = res[b]; start_host[b] = rs[b]; }
+    return n_scored;
 }
 
 int rade_batch_channel_symbol(rade_batch *h, const float *z_dev, const float *H_dev, const float *noise_dev, float *z_hat_dev, int n_steps,

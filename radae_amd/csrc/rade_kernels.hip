@@ -856,8 +856,9 @@ __global__ __launch_bounds__(64) void k_chan_gain(rd_chan_args a, const double *
     double p0 = 0.0, p1 = 0.0;
     for (int c = 0; c < n_part; c++) { p0 += part[((size_t)b * n_part + c) * 2]; p1 += part[((size_t)b * n_part + c) * 2 + 1]; }
     const float tx_power = (float)(p0 / a.n_sig), mp_power = (float)(p1 / a.n_sig);
+    const float foff = a.ps ? a.ps[a.B + b] : a.freq_offset, dfdt = a.ps ? a.ps[2 * a.B + b] : a.df_dt;
     float2 fin = make_float2(1.0f, 0.0f);
-    if (a.freq_offset != 0.0f && a.n_sig > 0) { float sn, cs; sincosf((float)chan_phase_acc(a.n_sig - 1, a.freq_offset, a.df_dt), &sn, &cs); fin = make_float2(cs, sn); }
+    if (foff != 0.0f && a.n_sig > 0) { float sn, cs; sincosf((float)chan_phase_acc(a.n_sig - 1, foff, dfdt), &sn, &cs); fin = make_float2(cs, sn); }
     gf[4 * b] = a.G ? powf(tx_power / mp_power, 0.5f) : 1.0f; gf[4 * b + 1] = fin.x; gf[4 * b + 2] = fin.y;
 }
 
@@ -867,6 +868,8 @@ __global__ __launch_bounds__(256) void k_chan_apply(rd_chan_args a, const float 
     const int n_eoo = a.with_eoo ? RD_NEOO : 0;
     const int n_total = a.n_pre + a.n_sig + n_eoo + a.n_post;
     const float gain = gf[4 * b]; const float2 fin = make_float2(gf[4 * b + 1], gf[4 * b + 2]);
+    // the stream's channel condition: one uniform load per workgroup when the call gives per-stream values
+    const float sigma = a.ps ? a.ps[b] : a.sigma, foff = a.ps ? a.ps[a.B + b] : a.freq_offset, dfdt = a.ps ? a.ps[2 * a.B + b] : a.df_dt;
     const float2 *tx = (const float2 *)a.tx + (size_t)b * a.tx_stride;
     const float2 *G = a.G ? (const float2 *)a.G + (size_t)b * a.n_sig * 2 : nullptr;
     const float2 *noise = a.noise ? (const float2 *)a.noise + (size_t)b * n_total : nullptr;
@@ -882,18 +885,18 @@ __global__ __launch_bounds__(256) void k_chan_apply(rd_chan_args a, const float 
             real_noise = false;
             const float2 m = a.mp ? ((const float2 *)a.mp)[(size_t)b * a.n_sig + i] : chan_mp(tx, G, i);
             v = make_float2(m.x * gain, m.y * gain);
-            if (a.freq_offset != 0.0f) { float sn, cs; sincosf((float)chan_phase_acc(i, a.freq_offset, a.df_dt), &sn, &cs); v = cmul(v, make_float2(cs, sn)); }
+            if (foff != 0.0f) { float sn, cs; sincosf((float)chan_phase_acc(i, foff, dfdt), &sn, &cs); v = cmul(v, make_float2(cs, sn)); }
         } else if (i >= a.n_sig && i < a.n_sig + n_eoo) {
             real_noise = false;
             const int e = i - a.n_sig;
-            float sn, cs; sincosf((float)chan_phase_acc(e, a.freq_offset, a.df_dt), &sn, &cs);
+            float sn, cs; sincosf((float)chan_phase_acc(e, foff, dfdt), &sn, &cs);
             v = cmul(cmul(eoo[e], make_float2(cs, sn)), fin);
         }
-        if (noise) { v.x += a.sigma * noise[j].x; v.y += a.sigma * noise[j].y; }
+        if (noise) { v.x += sigma * noise[j].x; v.y += sigma * noise[j].y; }
         else if (a.seed) {
             const float2 g = gauss_pair(u0, u1);
-            if (real_noise) v.x += a.sigma * g.x;                                  // inference.py:277-284: real-valued randn
-            else { v.x += a.sigma * 0.70710678f * g.x; v.y += a.sigma * 0.70710678f * g.y; }   // complex randn: 1/2 per component
+            if (real_noise) v.x += sigma * g.x;                                    // inference.py:277-284: real-valued randn
+            else { v.x += sigma * 0.70710678f * g.x; v.y += sigma * 0.70710678f * g.y; }       // complex randn: 1/2 per component
         }
         if (a.sine_amp != 0.0f) {                                                  // inference.py:285-288, phase taken mod 1 cycle in double
             const double cyc = (double)j * (double)a.sine_freq / 8000.0;

@@ -32,6 +32,10 @@ class ChannelParams(C.Structure):
                 ("sine_amp", C.c_float), ("sine_freq", C.c_float), ("rx_gain", C.c_float)]
 
 
+class ChannelStreams(C.Structure):
+    _fields_ = [("sigma", C.c_void_p), ("freq_offset", C.c_void_p), ("df_dt", C.c_void_p)]
+
+
 class IdealRxParams(C.Structure):
     _fields_ = [("time_offset", C.c_int), ("eq", C.c_int), ("coarse_mag", C.c_int), ("freq_offset_host", C.c_void_p), ("df_dt_host", C.c_void_p),
                 ("z_ref_dev", C.c_void_p), ("n_errors_host", C.c_void_p)]
@@ -94,6 +98,10 @@ def load_library() -> C.CDLL:
         L.rade_batch_sync_counts.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]; L.rade_batch_sync_counts.restype = None
     if hasattr(L, "rade_batch_rx_filtered"):      # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
         L.rade_batch_rx_filtered.argtypes = [vp, C.c_int, vp, C.c_int]
+    if hasattr(L, "rade_batch_loss"):             # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
+        L.rade_batch_channel_streams.argtypes = [vp, vp, C.c_long, vp, C.c_long, C.POINTER(ChannelParams), C.POINTER(ChannelStreams), vp]
+        L.rade_batch_tx_channel_streams.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_long, C.POINTER(ChannelParams), C.POINTER(ChannelStreams), vp]
+        L.rade_batch_loss.argtypes = [vp, vp, C.c_long, C.c_int, vp, vp, C.c_long, C.c_int, vp, vp, vp, vp, C.c_long, vp]
     _lib = L
     return L
 
@@ -112,17 +120,69 @@ EXPORTED_SYMBOLS = [
     "rade_multi_open", "rade_multi_close", "rade_multi_n_devices", "rade_multi_transport", "rade_multi_engine", "rade_multi_shard", "rade_multi_foreach",
     "rade_multi_allreduce_sum",
     "rade_batch_rx_ideal", "rade_sigma_from_EbNodB_bn1",
+    "rade_batch_loss", "rade_batch_channel_streams", "rade_batch_tx_channel_streams",
 ]
 
 
-def sigma_from_EbNodB(EbNodB: float, bottleneck: int = 3) -> float:
-    """AWGN standard deviation of the rate-Fs channel: bottleneck 3 (radae.py:567-573) or bottleneck 1 (:574-576, the waveform of TX_LINEAR)."""
+def sigma_from_EbNodB(EbNodB, bottleneck: int = 3):
+    """AWGN standard deviation of the rate-Fs channel: bottleneck 3 (radae.py:567-573) or bottleneck 1 (:574-576, the waveform of TX_LINEAR).
+    A scalar gives a float; an array of Eb/No points gives a float32 array of the same shape, each value what the scalar form gives (per-stream channels)."""
     L = load_library()
     if bottleneck == 1:
-        return float(L.rade_sigma_from_EbNodB_bn1(EbNodB))
-    if bottleneck != 3:
+        f = L.rade_sigma_from_EbNodB_bn1
+    elif bottleneck == 3:
+        f = L.rade_sigma_from_EbNodB
+    else:
         raise ValueError("rate-Fs noise is defined for bottleneck 1 or 3")
-    return float(L.rade_sigma_from_EbNodB(EbNodB))
+    if np.ndim(EbNodB) == 0:
+        return float(f(EbNodB))
+    e = np.asarray(EbNodB, dtype=np.float32)
+    return np.array([f(float(x)) for x in e.ravel()], dtype=np.float32).reshape(e.shape)
+
+
+def channel_stream_values(B: int, sigma, freq_offset, df_dt):
+    """sigma / freq_offset / df_dt of a channel call, each a scalar (every stream) or a length-B sequence (one value per stream, rade_channel_streams).
+    Returns the three scalars for rade_channel_params (0.0 where a sequence was given) and {name: float32[B]} of the sequences, or None when all are scalars."""
+    scal, per = [], {}
+    for name, v in (("sigma", sigma), ("freq_offset", freq_offset), ("df_dt", df_dt)):
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        if np.ndim(v) == 0:
+            scal.append(float(v))
+            continue
+        a = np.ascontiguousarray(v, dtype=np.float32)
+        if a.ndim != 1 or a.shape[0] != B:
+            raise ValueError(f"{name}: a scalar or {B} per-stream values, got shape {a.shape}")
+        scal.append(0.0)
+        per[name] = a
+    return tuple(scal), (per or None)
+
+
+def _channel_streams(per):
+    return ChannelStreams(*(per[k].ctypes.data if k in per else None for k in ("sigma", "freq_offset", "df_dt")))
+
+
+def loss_lengths(B: int, n_in, n_hat, rows_in: int, rows_hat: int, clip_start: int = 0, clip_end: int = 0):
+    """Per-stream row counts of a rade_batch_loss call: n_in / n_hat each None (every row of the buffer), a scalar or B values; n_hat may also be rx()'s
+    status list (12 x n_valid).  clip_start / clip_end (loss.py's flags) drop decoded rows at either end: the returned n_hat counts the rows after
+    clip_start (0 when none are left).  Counts beyond the buffers' rows are refused: the kernel would read past them."""
+    def per_stream(v, rows, what):
+        if v is None:
+            v = rows
+        elif isinstance(v, (list, tuple, C.Array)) and len(v) and hasattr(v[0], "n_valid"):
+            v = [12 * s.n_valid for s in v]
+        a = np.asarray(v, dtype=np.int64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+            raise ValueError(f"{what}: a scalar or {B} per-stream values, got shape {a.shape}")
+        a = np.broadcast_to(a, (B,))
+        if a.max(initial=0) > rows:
+            raise ValueError(f"{what}: {int(a.max())} rows asked for, the buffer holds {rows}")
+        return a
+    if clip_start < 0 or clip_end < 0:
+        raise ValueError("clip_start / clip_end must be >= 0")
+    ni = per_stream(n_in, rows_in, "n_in")
+    nh = per_stream(n_hat, rows_hat, "n_hat")
+    return ni.astype(np.int32), np.maximum(nh - clip_start - clip_end, 0).astype(np.int32)
 
 
 def _stream_ptr():
@@ -283,14 +343,16 @@ class BatchEngine:
         return out
 
     # ---- channel ----------------------------------------------------------------------------
-    def channel(self, tx, sigma: float, freq_offset: float = 0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
-                G=None, noise=None, seed: int = 0, df_dt: float = 0.0, sine_amp: float = 0.0, sine_freq: float = 0.0, rx_gain: float = 1.0):
+    def channel(self, tx, sigma, freq_offset=0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
+                G=None, noise=None, seed: int = 0, df_dt=0.0, sine_amp: float = 0.0, sine_freq: float = 0.0, rx_gain: float = 1.0):
         """tx complex64 [B, n_sig]; G complex64 [B, n_sig, 2] or None; noise complex64 [B, n_total] or None;
-        sine_amp/sine_freq: complex tone over the whole output, rx_gain: final scale (inference.py:285-289)."""
+        sine_amp/sine_freq: complex tone over the whole output, rx_gain: final scale (inference.py:285-289).
+        sigma / freq_offset / df_dt: a scalar for every stream, or B per-stream values (rade_batch_channel_streams)."""
         import torch
         assert tx.is_cuda and tx.dtype == torch.complex64 and tx.is_contiguous() and tx.shape[0] == self.B
         n_sig = tx.shape[1]
         n_total = n_pre + n_sig + (NEOO if with_eoo else 0) + n_post
+        (sigma, freq_offset, df_dt), per = channel_stream_values(self.B, sigma, freq_offset, df_dt)
         rx = torch.empty((self.B, n_total), dtype=torch.complex64, device=tx.device)
         p = ChannelParams(n_sig, n_pre, n_post, int(with_eoo), sigma, freq_offset, df_dt, None, None, seed, sine_amp, sine_freq, rx_gain)
         if G is not None:
@@ -299,21 +361,26 @@ class BatchEngine:
         if noise is not None:
             assert noise.is_cuda and noise.dtype == torch.complex64 and noise.is_contiguous() and tuple(noise.shape) == (self.B, n_total)
             p.noise_dev = noise.data_ptr()
-        r = self.lib.rade_batch_channel(self.h, tx.data_ptr(), n_sig, rx.data_ptr(), n_total, C.byref(p), _stream_ptr())
+        if per is None:
+            r = self.lib.rade_batch_channel(self.h, tx.data_ptr(), n_sig, rx.data_ptr(), n_total, C.byref(p), _stream_ptr())
+        else:
+            r = self.lib.rade_batch_channel_streams(self.h, tx.data_ptr(), n_sig, rx.data_ptr(), n_total, C.byref(p), C.byref(_channel_streams(per)), _stream_ptr())
         if r != n_total:
             raise RuntimeError("rade_batch_channel failed")
         return rx
 
-    def tx_channel(self, features, sigma: float, freq_offset: float = 0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
-                   G=None, noise=None, seed: int = 0, df_dt: float = 0.0, want_iq: bool = False):
+    def tx_channel(self, features, sigma, freq_offset=0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
+                   G=None, noise=None, seed: int = 0, df_dt=0.0, want_iq: bool = False):
         """Transmit and channel in one pass (RADAE.forward): features [B, n_mf*12, 36] -> rx complex64 [B, n_total] (and iq if wanted).
-        With G the modulator applies the two-path model itself (rade_batch_tx_channel); the whole utterance must fit max_tx_mf."""
+        With G the modulator applies the two-path model itself (rade_batch_tx_channel); the whole utterance must fit max_tx_mf.
+        sigma / freq_offset / df_dt: a scalar for every stream, or B per-stream values (rade_batch_tx_channel_streams)."""
         import torch
         assert features.is_cuda and features.dtype == torch.float32 and features.is_contiguous()
         B, nfr, w = features.shape
         assert B == self.B and w == 36 and nfr % 12 == 0 and nfr // 12 <= self.max_tx_mf
         n_mf = nfr // 12; n_sig = n_mf * NMF
         n_total = n_pre + n_sig + (NEOO if with_eoo else 0) + n_post
+        (sigma, freq_offset, df_dt), per = channel_stream_values(B, sigma, freq_offset, df_dt)
         rx = torch.empty((B, n_total), dtype=torch.complex64, device=features.device)
         iq = torch.empty((B, n_sig), dtype=torch.complex64, device=features.device) if (want_iq or G is None) else None
         p = ChannelParams(n_sig, n_pre, n_post, int(with_eoo), sigma, freq_offset, df_dt, None, None, seed, 0.0, 0.0, 1.0)
@@ -323,7 +390,12 @@ class BatchEngine:
         if noise is not None:
             assert noise.is_cuda and noise.dtype == torch.complex64 and noise.is_contiguous() and tuple(noise.shape) == (B, n_total)
             p.noise_dev = noise.data_ptr()
-        r = self.lib.rade_batch_tx_channel(self.h, features.data_ptr(), n_mf, iq.data_ptr() if iq is not None else None, n_sig, rx.data_ptr(), n_total, C.byref(p), _stream_ptr())
+        iq_ptr = iq.data_ptr() if iq is not None else None
+        if per is None:
+            r = self.lib.rade_batch_tx_channel(self.h, features.data_ptr(), n_mf, iq_ptr, n_sig, rx.data_ptr(), n_total, C.byref(p), _stream_ptr())
+        else:
+            r = self.lib.rade_batch_tx_channel_streams(self.h, features.data_ptr(), n_mf, iq_ptr, n_sig, rx.data_ptr(), n_total, C.byref(p),
+                                                       C.byref(_channel_streams(per)), _stream_ptr())
         if r != n_total:
             raise RuntimeError("rade_batch_tx_channel failed")
         return (rx, iq) if want_iq else rx
@@ -391,7 +463,41 @@ class BatchEngine:
                                    features_out.shape[1] * self.rx_row_floats, eoo.data_ptr(), status, _stream_ptr())
         if r:
             raise RuntimeError("rade_batch_rx failed")
+        self._rx_last = (features_out.data_ptr(), list(status)) if self.rx_row_floats == FEAT_MF else None    # loss()'s default n_hat
         return features_out, list(status), eoo
+
+    # ---- scoring ----------------------------------------------------------------------------
+    def loss(self, features, features_hat, n_in=None, n_hat=None, clip_start: int = 0, clip_end: int = 0, frame_loss: bool = False):
+        """loss.py:find_loss (:64-91) of every stream in one launch (rade_batch_loss): features / features_hat cuda float32 [B, rows, width >= 20]
+        (the first 20 columns of each row are used) or rx()'s [B, n_valid_cap, 432], read as rows of 36.  n_in / n_hat: per-stream row counts (see
+        loss_lengths); n_hat defaults to 12 x n_valid of the rx() call that returned features_hat, else every row.  clip_start / clip_end: loss.py's flags.
+        Returns (loss float64 [B], start int32 [B], frame_loss or None): NaN and -1 for a stream with no decoded rows or more than were sent;
+        acq_time = 0.01 s x start; frame_loss cuda float32 [B, max n_hat] holds loss.py's per-frame curve in [0, n_hat - start) of each row, NaN after."""
+        import torch
+
+        def rows(x, what):
+            assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.B and x.stride(2) == 1, what
+            if x.shape[2] == FEAT_MF and x.stride(1) == FEAT_MF:
+                x = x.as_strided((self.B, x.shape[1] * 12, 36), (x.stride(0), 36, 1))
+            assert x.shape[2] >= 20 and x.stride(1) >= 20, what
+            return x, (x.stride(0) if self.B > 1 else 0), x.stride(1)
+        last = getattr(self, "_rx_last", None)
+        if n_hat is None and last is not None and last[0] == features_hat.data_ptr():
+            n_hat = last[1]
+        f, f_sb, f_row = rows(features, "features")
+        h, h_sb, h_row = rows(features_hat, "features_hat")
+        ni, nh = loss_lengths(self.B, n_in, n_hat, f.shape[1], h.shape[1], clip_start, clip_end)
+        fl = None
+        if frame_loss:
+            fl = torch.full((self.B, max(int(nh.max(initial=0)), 1)), float("nan"), dtype=torch.float32, device=f.device)
+        loss = np.zeros(self.B, np.float64)
+        start = np.zeros(self.B, np.int32)
+        r = self.lib.rade_batch_loss(self.h, f.data_ptr(), f_sb, f_row, ni.ctypes.data, h.data_ptr() + 4 * clip_start * h_row, h_sb, h_row, nh.ctypes.data,
+                                     loss.ctypes.data, start.ctypes.data, fl.data_ptr() if fl is not None else None, fl.shape[1] if fl is not None else 0,
+                                     _stream_ptr())
+        if r < 0:
+            raise RuntimeError("rade_batch_loss failed")
+        return loss, start, fl
 
     def rx_ideal(self, rx, n_mf: int, time_offset: int = -16, eq: str = "ls", coarse_mag: bool = True, freq_offset=None, df_dt=None, z_ref=None,
                  feat_width: int = 84):
