@@ -73,6 +73,8 @@ typedef struct { float *wp, *bias; unsigned short *wp16, *wa16; float *wscale, *
 #define RADE_PROF_MAXEV 256   /* launches recorded per profiled interval before the events are drained */
 #define RADE_PROF_MAXIV 4096  /* launch intervals kept per profiling session (rade_batch_profile_intervals) */
 struct rade_batch {
+    struct owned *owned;                  /* every device / pinned allocation of the engine (own): rade_batch_close frees exactly these */
+    int alloc_failed;                     /* sticky: an allocation the engine cannot do without failed (rade_batch_open_mem checks it) */
     int B, max_tx_mf, device, flags, trace_cap, Tcap;
     int R, dec_rows;                      /* do_radae_rx calls per stream per sync launch; 3R decoder slots */
     int unsync_off_after;                 /* int(disable_unsync * Fs / Nmf) or -1 */
@@ -95,12 +97,12 @@ struct rade_batch {
     rd_bpf_state *tx_bpf, *tx_bpf_init; void *tx_raw; float *tx_chain; float *eoo_filt;   /* eoo_filt [B][Neoo] c64: the end-of-over frame as transmitted (filtered + clipped) for the channel's with_eoo */
     void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
     float *chan_ps, *chan_ps_host;            /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */
-    int *loss_len; double *loss_res, *loss_part; int loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
+    int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
     int *rx_avail, *rx_acc, *rx_progress, *rx_status;
     float *zrows, *dec_x, *dec_gi, *dec_hbuf, *dec_h[5], *feat84, *dtcache;
-    void *rx_filt; float *bpf_chain; long filt_cap; int chain_stride;   /* band-pass pre-pass of an invocation: filtered samples [B][filt_cap] c64 and block phases [B][chain_stride] c64, grown on demand */
+    void *rx_filt; float *bpf_chain; long filt_cap, chain_stride;   /* band-pass pre-pass of an invocation: filtered samples [B][filt_cap] c64 and block phases [B][chain_stride] c64, grown on demand */
     rd_rx_trace *trace; float *trace_z;
     long long *wg_cycles;            /* [B] per-stream cycles of the last receiver launch */
     int *h_small;                    /* pinned host scratch */
@@ -111,7 +113,6 @@ struct rade_batch {
     double prof_ms[RADE_PROF_NCLASS], prof_flops[RADE_PROF_NCLASS]; long prof_n[RADE_PROF_NCLASS];
     /* optional: absolute start / end of every profiled launch relative to a caller-supplied event (launches of several engines on one time axis) */
     hipEvent_t prof_ref; int iv_n; int iv_cls[RADE_PROF_MAXIV]; float iv_t0[RADE_PROF_MAXIV], iv_t1[RADE_PROF_MAXIV];
-    long rx_calls_search, rx_calls_sync;
     hipEvent_t ev_block;             /* the event rade_batch_rx sleeps on (sleep_until_event) when the host has fewer CPUs than engines (sync_blocking_now) */
     long n_sync_block, n_sync_spin;  /* waits of either kind so far (rade_batch_sync_counts) */
     double wait_est_us;              /* how long the sleeping wait of rade_batch_rx lasted lately (running average): the next one sleeps through most of that before it polls */
@@ -120,26 +121,70 @@ struct rade_batch {
 static const int ENC_IN[5] = { 64, 224, 384, 544, 704 };    /* GRU input widths (radae_base.py:240-248) */
 static const int ENC_DIL[5] = { 1, 2, 2, 2, 2 };
 static const int DEC_IN[5] = { 96, 224, 352, 480, 608 };    /* radae_base.py:378-386 */
+/* samples per stream of tx_raw, the modulator's output ahead of the Tx band-pass filter (>= the 1152-sample end-of-over frame) */
+static long tx_raw_stride(const rade_batch *h) { return (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF; }
 
-static void *dev_upload(const void *src, size_t bytes)
+/* ---- the engine's memory: every allocation is recorded on the engine (own), and rade_batch_close releases what was recorded ------------------------ */
+struct owned { struct owned *next; void *p; int pinned; };
+static void *own(rade_batch *h, void *p, int pinned)
+{
+    struct owned *o = p ? malloc(sizeof *o) : NULL;
+    if (p && !o) { if (pinned) hipHostFree(p); else hipFree(p); return NULL; }
+    if (o) { o->next = h->owned; o->p = p; o->pinned = pinned; h->owned = o; }
+    return p;
+}
+static void disown(rade_batch *h, void *p)       /* release one recorded allocation */
+{
+    for (struct owned **q = &h->owned; *q; q = &(*q)->next)
+        if ((*q)->p == p) { struct owned *o = *q; *q = o->next; if (o->pinned) hipHostFree(p); else hipFree(p); free(o); return; }
+}
+/* The non-sticky allocators: NULL is the caller's to handle (an optional buffer, or a call after the open that returns -1).  zero = 0: left as allocated.
+ * The zeros are complete before returning: the memset runs on the null stream, which is not ordered against a caller's non-blocking stream (a buffer
+ * allocated on first use inside a stream-ordered call would otherwise be zeroed on top of what that call's kernels wrote). */
+static void *dev_alloc_opt(rade_batch *h, size_t bytes, int zero)
 {
     void *d = NULL;
     if (hipMalloc(&d, bytes) != hipSuccess) return NULL;
-    if (hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return NULL; }
+    if (zero && (hipMemset(d, 0, bytes) != hipSuccess || hipStreamSynchronize(NULL) != hipSuccess)) { hipFree(d); return NULL; }
+    return own(h, d, 0);
+}
+static void *dev_upload_opt(rade_batch *h, const void *src, size_t bytes)
+{
+    void *d = dev_alloc_opt(h, bytes, 0);
+    if (d && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { disown(h, d); return NULL; }
     return d;
 }
-static void *dev_zeros(size_t bytes)
+static void *pinned_alloc_opt(rade_batch *h, size_t bytes) { void *p = NULL; return hipHostMalloc(&p, bytes, 0) == hipSuccess ? own(h, p, 1) : NULL; }
+static void *must(rade_batch *h, void *p) { if (!p) h->alloc_failed = 1; return p; }      /* the open's: what the engine cannot do without */
+static void *dev_upload(rade_batch *h, const void *src, size_t bytes) { return must(h, dev_upload_opt(h, src, bytes)); }
+static void *dev_zeros(rade_batch *h, size_t bytes) { return must(h, dev_alloc_opt(h, bytes, 1)); }
+
+/* Scratch that follows the largest call seen: the pointer at ptr_addr (of any object type) holds `need` elements of elem_bytes afterwards (*cap = need; cap = NULL:
+ * a fixed size, allocated on first use).  A buffer it replaces is released only once the device is idle: queued work may still read it.  zeroed = 0: left as allocated,
+ * for buffers whose every entry is written on the caller's stream before it is read (the receiver's pre-pass): a memset on the null stream could land on top of that. */
+static int dev_grow(rade_batch *h, void *ptr_addr, long *cap, long need, size_t elem_bytes, int zeroed)
 {
-    void *d = NULL;
-    if (hipMalloc(&d, bytes) != hipSuccess) return NULL;
-    /* complete before returning: the memset runs on the null stream, which is not ordered against a caller's non-blocking stream (buffers
-     * allocated on first use inside a stream-ordered call would otherwise be zeroed on top of what that call's kernels wrote) */
-    if (hipMemset(d, 0, bytes) != hipSuccess || hipStreamSynchronize(NULL) != hipSuccess) { hipFree(d); return NULL; }
+    void *p;
+    memcpy(&p, ptr_addr, sizeof p);
+    if (p && (!cap || need <= *cap)) return 0;
+    if (p) { if (hipDeviceSynchronize() != hipSuccess) return -1; disown(h, p); }
+    p = dev_alloc_opt(h, elem_bytes * (size_t)need, zeroed);
+    memcpy(ptr_addr, &p, sizeof p);
+    if (cap) *cap = p ? need : 0;
+    return p ? 0 : -1;
+}
+
+/* n_halfs binary16 operands written by `fill` from the constant tables, on the device */
+static unsigned short *upload_table16(rade_batch *h, const rd_tables *tab, void (*fill)(const rd_tables *, unsigned short *), size_t n_halfs)
+{
+    unsigned short *t = malloc(sizeof(unsigned short) * n_halfs), *d = NULL;
+    if (t) { fill(tab, t); d = dev_upload(h, t, sizeof(unsigned short) * n_halfs); } else h->alloc_failed = 1;
+    free(t);
     return d;
 }
 
-/* pack W[N][K] (optionally padding K up to Kpad with zero columns) and upload */
-static int upload_lin(dev_lin *d, const float *w, const float *b, const float *row_scale, int N, int K, int Kpad)
+/* pack W[N][K] (optionally padding K up to Kpad with zero columns) and upload; NULL = the layer has no such form (wp16 / wa16, their scales), -1 = it does not fit one */
+static int upload_lin(rade_batch *h, dev_lin *d, const float *w, const float *b, const float *row_scale, int N, int K, int Kpad)
 {
     float *wsrc = (float *)w, *tmp = NULL;
     if (Kpad != K) {
@@ -150,8 +195,8 @@ static int upload_lin(dev_lin *d, const float *w, const float *b, const float *r
     const long n = rd_packed_size(N, Kpad);
     float *packed = malloc(sizeof(float) * n);
     rd_pack_weights(wsrc, N, Kpad, packed);
-    d->wp = dev_upload(packed, sizeof(float) * n);
-    d->bias = b ? dev_upload(b, sizeof(float) * N) : NULL;
+    d->wp = dev_upload(h, packed, sizeof(float) * n);
+    d->bias = b ? dev_upload(h, b, sizeof(float) * N) : NULL;
     d->N = N; d->K = Kpad; d->wp16 = NULL; d->wscale16 = NULL;
     if (Kpad % 16 == 0) {                  /* binary16 copy for the f16 matrix cores (k_gemm16): int8-exact layers as ONE plane of integers + column scales, others as two planes */
         const long n16 = rd_packed16_size(N, Kpad);
@@ -160,14 +205,14 @@ static int upload_lin(dev_lin *d, const float *w, const float *b, const float *r
         long nq = -1;
         if (p16 && sc && row_scale) nq = rd_pack_weights_q16(wsrc, row_scale, N, Kpad, p16, sc);
         if (nq > 0) {
-            d->wp16 = dev_upload(p16, sizeof(unsigned short) * nq);
-            d->wscale16 = dev_upload(sc, sizeof(float) * (size_t)((N + 31) / 32) * 32);
+            d->wp16 = dev_upload(h, p16, sizeof(unsigned short) * nq);
+            d->wscale16 = dev_upload(h, sc, sizeof(float) * (size_t)((N + 31) / 32) * 32);
         } else {
             if (!p16 || rd_pack_weights_f16x2(wsrc, N, Kpad, p16) < 0) {
                 fprintf(stderr, "rade: a weight exceeds the range of the split-binary16 operand planes (|w| < 63.9)\n");
                 free(p16); free(sc); free(packed); free(tmp); return -1;
             }
-            d->wp16 = dev_upload(p16, sizeof(unsigned short) * n16);
+            d->wp16 = dev_upload(h, p16, sizeof(unsigned short) * n16);
         }
         free(p16); free(sc);
     }
@@ -179,11 +224,11 @@ static int upload_lin(dev_lin *d, const float *w, const float *b, const float *r
         long nq = -1;
         if (pa && sc && row_scale) nq = rd_pack_weights_q16_a16(wsrc, row_scale, N, Kpad, pa, sc);
         if (nq > 0) {                      /* int8 in the blob: the integers themselves in ONE binary16 plane (exact), scales apart: half the bytes to stream */
-            d->wa16 = dev_upload(pa, sizeof(unsigned short) * nq);
-            d->wscale = dev_upload(sc, sizeof(float) * (size_t)((N + 15) / 16) * 16);
+            d->wa16 = dev_upload(h, pa, sizeof(unsigned short) * nq);
+            d->wscale = dev_upload(h, sc, sizeof(float) * (size_t)((N + 15) / 16) * 16);
         } else {
             if (!pa || rd_pack_weights_f16x2_a16(wsrc, N, Kpad, pa) < 0) { free(pa); free(sc); free(packed); free(tmp); return -1; }
-            d->wa16 = dev_upload(pa, sizeof(unsigned short) * na);
+            d->wa16 = dev_upload(h, pa, sizeof(unsigned short) * na);
         }
         free(pa); free(sc);
     }
@@ -223,6 +268,7 @@ void rade_batch_reset(rade_batch *h, void *stream) { ON_DEV(h); reset_on(h, 1, 1
 void rade_batch_rx_set_lcg(rade_batch *h, const unsigned *seeds_host)
 {
     ON_DEV(h);
+    if (!h) return;
     for (int b = 0; b < h->B; b++) h->lcg_seeds[b] = seeds_host ? seeds_host[b] : 1u;
     hipMemcpy(h->d_lcg_seeds, h->lcg_seeds, sizeof(unsigned) * h->B, hipMemcpyHostToDevice);
     rade_batch_rx_reset(h);
@@ -264,128 +310,108 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
 
     rd_tables *tab = malloc(sizeof *tab);
     rd_tables_fill(tab);
-    h->d_tab = dev_upload(tab, sizeof *tab);
-    {   /* the pilot correlator in two stages: 16 polynomial moments, then their expansion to the 40 frequencies (rade_host.c) */
-        unsigned short *q16 = malloc(sizeof(unsigned short) * 2 * 10 * 2 * 64 * 8), *a16 = malloc(sizeof(unsigned short) * 5 * 2 * 64 * 8);
-        if (q16 && a16) {
-            rd_corrq16_table_fill(tab, q16); h->corrq16 = dev_upload(q16, sizeof(unsigned short) * 2 * 10 * 2 * 64 * 8);
-            rd_corra16_table_fill(tab, a16); h->corra16 = dev_upload(a16, sizeof(unsigned short) * 5 * 2 * 64 * 8);
-        }
-        free(q16); free(a16);
-    }
-    {   /* the demodulator DFT matrix as matrix-core operands (k_rx_sync2) */
-        unsigned short *w16 = malloc(sizeof(unsigned short) * 2 * 10 * 2 * 64 * 8);
-        if (w16) { rd_wfwd16_table_fill(tab, w16); h->wfwd16 = dev_upload(w16, sizeof(unsigned short) * 2 * 10 * 2 * 64 * 8); free(w16); }
-    }
-    {   /* the band-pass taps as matrix-core operands (k_rx_bpf) */
-        unsigned short *b16 = malloc(sizeof(unsigned short) * 4 * 2 * 64 * 8);
-        if (b16) { rd_bpf16_table_fill(tab, b16); h->bpf16 = dev_upload(b16, sizeof(unsigned short) * 4 * 2 * 64 * 8); free(b16); }
-    }
+    h->d_tab = dev_upload(h, tab, sizeof *tab);
+    /* the pilot correlator in two stages: 16 polynomial moments, then their expansion to the 40 frequencies (rade_host.c) */
+    h->corrq16 = upload_table16(h, tab, rd_corrq16_table_fill, RD_CORRQ16_HALFS);
+    h->corra16 = upload_table16(h, tab, rd_corra16_table_fill, RD_CORRA16_HALFS);
+    h->wfwd16 = upload_table16(h, tab, rd_wfwd16_table_fill, RD_WFWD16_HALFS);    /* the demodulator DFT matrix as matrix-core operands (k_rx_sync2) */
+    h->bpf16 = upload_table16(h, tab, rd_bpf16_table_fill, RD_BPF16_HALFS);       /* the band-pass taps as matrix-core operands (k_rx_bpf) */
     free(tab);
     {   /* ((n - 79.5) / 80)^m, m = 0..7, by repeated multiplication (the order the kernels build their LDS copy in) */
         double vm[8][RD_M];
         for (int n = 0; n < RD_M; n++) { const double nu = ((double)n - 79.5) / 80.0; double v = 1.0; for (int m = 0; m < 8; m++) { vm[m][n] = v; v *= nu; } }
-        h->vm = dev_upload(vm, sizeof vm);
+        h->vm = dev_upload(h, vm, sizeof vm);
     }
     /* the receiver kernel asks for more dynamic LDS than the 64 KB default: raised here, once per engine and before any launch (the
      * attribute belongs to the device's code object; setting it again from another engine's thread is harmless) */
     h->rx_lds = rd_rx_sync_prepare();
     h->rx_census = getenv("RADE_RX2_CENSUS") ? atoi(getenv("RADE_RX2_CENSUS")) : 0;      /* only acts in -DRX2_CENSUS builds */
-    if (!h->d_tab || !h->corrq16 || !h->corra16 || !h->vm || !h->wfwd16 || !h->bpf16 || h->rx_lds <= 0) goto fail;
+    if (h->alloc_failed || h->rx_lds <= 0) goto fail;
 
     int err = 0;
     h->feat_in = m.enc_dense1.n_in; h->enc_kpad = (h->feat_in + 15) & ~15; h->bottleneck1 = (cfg->flags & RADE_BATCH_BOTTLENECK1) != 0;
-    err |= upload_lin(&h->enc_dense1, m.enc_dense1.w, m.enc_dense1.b, NULL, 64, h->feat_in, h->enc_kpad);
-    err |= upload_lin(&h->enc_zdense, m.enc_zdense.w, m.enc_zdense.b, NULL, 80, 864, 864);
-    err |= upload_lin(&h->dec_dense1, m.dec_dense1.w, m.dec_dense1.b, NULL, 96, 80, 80);
-    err |= upload_lin(&h->dec_output, m.dec_output.w, m.dec_output.b, NULL, h->feat_in, 736, 736);
+    err |= upload_lin(h, &h->enc_dense1, m.enc_dense1.w, m.enc_dense1.b, NULL, 64, h->feat_in, h->enc_kpad);
+    err |= upload_lin(h, &h->enc_zdense, m.enc_zdense.w, m.enc_zdense.b, NULL, 80, 864, 864);
+    err |= upload_lin(h, &h->dec_dense1, m.dec_dense1.w, m.dec_dense1.b, NULL, 96, 80, 80);
+    err |= upload_lin(h, &h->dec_output, m.dec_output.w, m.dec_output.b, NULL, h->feat_in, 736, 736);
     for (int l = 0; l < 5 && !err; l++) {
-        err |= upload_lin(&h->enc_gin[l], m.enc_gru[l].w_ih, m.enc_gru[l].b_ih, m.enc_gru[l].s_ih, 192, ENC_IN[l], ENC_IN[l]);
-        err |= upload_lin(&h->dec_gin[l], m.dec_gru[l].w_ih, m.dec_gru[l].b_ih, m.dec_gru[l].s_ih, 288, DEC_IN[l], DEC_IN[l]);
-        err |= upload_lin(&h->enc_conv[l], m.enc_conv[l].w, m.enc_conv[l].b, m.enc_conv[l].row_scale, 96, m.enc_conv[l].n_in, m.enc_conv[l].n_in);
-        err |= upload_lin(&h->dec_conv[l], m.dec_conv[l].w, m.dec_conv[l].b, m.dec_conv[l].row_scale, 32, m.dec_conv[l].n_in, m.dec_conv[l].n_in);
-        err |= upload_lin(&h->dec_glu[l], m.dec_glu[l].w, NULL, m.dec_glu[l].row_scale, 96, 96, 96);
-        h->enc_whh[l] = dev_upload(m.enc_gru[l].w_hh, sizeof(float) * 192 * 64);
-        h->enc_bhh[l] = dev_upload(m.enc_gru[l].b_hh, sizeof(float) * 192);
-        h->dec_whh[l] = dev_upload(m.dec_gru[l].w_hh, sizeof(float) * 288 * 96);
-        h->dec_bhh[l] = dev_upload(m.dec_gru[l].b_hh, sizeof(float) * 288);
+        err |= upload_lin(h, &h->enc_gin[l], m.enc_gru[l].w_ih, m.enc_gru[l].b_ih, m.enc_gru[l].s_ih, 192, ENC_IN[l], ENC_IN[l]);
+        err |= upload_lin(h, &h->dec_gin[l], m.dec_gru[l].w_ih, m.dec_gru[l].b_ih, m.dec_gru[l].s_ih, 288, DEC_IN[l], DEC_IN[l]);
+        err |= upload_lin(h, &h->enc_conv[l], m.enc_conv[l].w, m.enc_conv[l].b, m.enc_conv[l].row_scale, 96, m.enc_conv[l].n_in, m.enc_conv[l].n_in);
+        err |= upload_lin(h, &h->dec_conv[l], m.dec_conv[l].w, m.dec_conv[l].b, m.dec_conv[l].row_scale, 32, m.dec_conv[l].n_in, m.dec_conv[l].n_in);
+        err |= upload_lin(h, &h->dec_glu[l], m.dec_glu[l].w, NULL, m.dec_glu[l].row_scale, 96, 96, 96);
+        h->enc_whh[l] = dev_upload(h, m.enc_gru[l].w_hh, sizeof(float) * 192 * 64);
+        h->enc_bhh[l] = dev_upload(h, m.enc_gru[l].b_hh, sizeof(float) * 192);
+        h->dec_whh[l] = dev_upload(h, m.dec_gru[l].w_hh, sizeof(float) * 288 * 96);
+        h->dec_bhh[l] = dev_upload(h, m.dec_gru[l].b_hh, sizeof(float) * 288);
         if (m.dec_gru[l].s_hh) {
             unsigned short *pa = malloc(sizeof(unsigned short) * rd_packed16a_size(288, 96)); float *scl = malloc(sizeof(float) * 288);
             const long nq = (pa && scl) ? rd_pack_weights_q16_a16(m.dec_gru[l].w_hh, m.dec_gru[l].s_hh, 288, 96, pa, scl) : -1;
-            if (nq > 0) { h->dec_whq[l] = dev_upload(pa, sizeof(unsigned short) * nq); h->dec_whs[l] = dev_upload(scl, sizeof(float) * 288); }
+            if (nq > 0) { h->dec_whq[l] = dev_upload_opt(h, pa, sizeof(unsigned short) * nq); h->dec_whs[l] = dev_upload_opt(h, scl, sizeof(float) * 288); }
             free(pa); free(scl);
         }
-        if (!h->enc_whh[l] || !h->enc_bhh[l] || !h->dec_whh[l] || !h->dec_bhh[l]) err = -1;
     }
-    if (err) { fprintf(stderr, "rade: weight upload failed\n"); goto fail; }
+    if (err || h->alloc_failed) { fprintf(stderr, "rade: weight upload failed\n"); goto fail; }
 
-    h->enc_xin = dev_zeros(sizeof(float) * B * T * RD_ENC_IN);
-    h->enc_x = dev_zeros(sizeof(float) * B * (2 + T) * RD_ENC_W);
-    h->enc_gi = dev_zeros(sizeof(float) * B * T * 192);
+    h->enc_xin = dev_zeros(h, sizeof(float) * B * T * RD_ENC_IN);
+    h->enc_x = dev_zeros(h, sizeof(float) * B * (2 + T) * RD_ENC_W);
+    h->enc_gi = dev_zeros(h, sizeof(float) * B * T * 192);
     h->enc_nq = 1 + (h->Tcap + 31) / 32;
     h->enc_seq_taps = getenv("RADE_ENCF_SEQ_TAPS") != NULL;    /* developer switches, read per engine (rade_enc.hip: k_encf_gemm) */
     h->enc_no_pair = getenv("RADE_ENCF_NO_PAIR") != NULL;
     if (B * T > 16384 && !getenv("RADE_ENC_ROWS")) {       /* $RADE_ENC_ROWS: the float32-row path (k_gemm16p) for every size: A/B and the equality test */
-        h->enc_xf = dev_zeros(sizeof(unsigned short) * B * h->enc_nq * RD_EF_TILE);      /* (NULL = no memory for it: the float32-row kernels serve every call) */
+        h->enc_xf = dev_alloc_opt(h, sizeof(unsigned short) * B * h->enc_nq * RD_EF_TILE, 1);   /* (NULL = no memory for it: the float32-row kernels serve every call) */
         if (!h->enc_xf && !getenv("RADE_VERBOSE_0"))
             fprintf(stderr, "rade: no device memory for the encoder's fragment buffer (%.1f MB): the float32-row kernels serve every call (slower encoder GEMMs, same results to the last bits documented in rade_batch.h)\n",
                     1e-6 * sizeof(unsigned short) * (double)B * h->enc_nq * RD_EF_TILE);
     }
-    h->enc_z = dev_zeros(sizeof(float) * B * T * RD_LATENT);
-    h->eoo = dev_zeros(sizeof(float) * B * RD_NEOO * 2);
-    h->eoo_bits = dev_zeros(sizeof(float) * B * RD_NEOOBITS);
+    h->enc_z = dev_zeros(h, sizeof(float) * B * T * RD_LATENT);
+    h->eoo = dev_zeros(h, sizeof(float) * B * RD_NEOO * 2);
+    h->eoo_bits = dev_zeros(h, sizeof(float) * B * RD_NEOOBITS);
     h->bypass_dec = (cfg->flags & RADE_BATCH_BYPASS_DEC) != 0;
     h->tx_linear = (cfg->flags & RADE_BATCH_TX_LINEAR) != 0;
     if (h->tx_linear && (cfg->flags & RADE_BATCH_TX_BPF)) { fprintf(stderr, "rade: RADE_BATCH_TX_LINEAR cannot be combined with RADE_BATCH_TX_BPF (the filter clips)\n"); goto fail; }
     if (cfg->flags & RADE_BATCH_TX_BPF) {
-        const long nraw = (long)(cfg->max_tx_mf > 2 ? cfg->max_tx_mf : 2) * RD_NMF;          /* (>= the 1152-sample end-of-over frame) */
         rd_bpf_state *init = calloc(B, sizeof *init);
         if (!init) goto fail;
         for (size_t b = 0; b < B; b++) { init[b].mem_len = 100; init[b].phase[0] = 1.0f; }    /* complex_bpf.__init__: dsp.py:54-60 */
-        h->tx_bpf_init = dev_upload(init, sizeof(rd_bpf_state) * B); h->tx_bpf = dev_upload(init, sizeof(rd_bpf_state) * B);
+        h->tx_bpf_init = dev_upload(h, init, sizeof(rd_bpf_state) * B); h->tx_bpf = dev_upload(h, init, sizeof(rd_bpf_state) * B);
         free(init);
-        h->tx_raw = dev_zeros(sizeof(float) * 2 * B * nraw);
-        h->tx_chain = dev_zeros(sizeof(float) * 2 * B * (cfg->max_tx_mf + 8));
-        h->eoo_filt = dev_zeros(sizeof(float) * 2 * B * RD_NEOO);
-        if (!h->tx_bpf_init || !h->tx_bpf || !h->tx_raw || !h->tx_chain || !h->eoo_filt) goto fail;
+        h->tx_raw = dev_zeros(h, sizeof(float) * 2 * B * tx_raw_stride(h));
+        h->tx_chain = dev_zeros(h, sizeof(float) * 2 * B * (cfg->max_tx_mf + 8));
+        h->eoo_filt = dev_zeros(h, sizeof(float) * 2 * B * RD_NEOO);
     }
-    h->chan_scratch = dev_zeros(sizeof(double) * B * (1 + (cfg->max_tx_mf > 64 ? cfg->max_tx_mf : 64)) * 2);   /* rd_chan_args.scratch */
-    h->enc_h[0] = dev_zeros(sizeof(float) * 5 * B * 64); h->dec_h[0] = dev_zeros(sizeof(float) * 5 * B * 96);
-    if (!h->enc_h[0] || !h->dec_h[0]) goto fail;
+    h->chan_scratch = dev_zeros(h, sizeof(double) * B * (1 + (cfg->max_tx_mf > 64 ? cfg->max_tx_mf : 64)) * 2);   /* rd_chan_args.scratch */
+    /* one allocation each: the five layers' states; progress word, per-stream counters and status, in the order of the host copy (rade_batch_rx: one transfer back per invocation) */
+    h->enc_h[0] = dev_zeros(h, sizeof(float) * 5 * B * 64); h->dec_h[0] = dev_zeros(h, sizeof(float) * 5 * B * 96);
+    h->dec2_h[0] = dev_zeros(h, sizeof(float) * 5 * B * 96);
+    h->rx_progress = dev_zeros(h, sizeof(int) * (8 + B * 8));
+    if (h->alloc_failed) { fprintf(stderr, "rade: device allocation failed\n"); goto fail; }
     for (int l = 1; l < 5; l++) { h->enc_h[l] = h->enc_h[0] + (size_t)l * B * 64; h->dec_h[l] = h->dec_h[0] + (size_t)l * B * 96; }
-    h->rx_st = dev_zeros(sizeof(rd_rx_stream) * B);
-    h->rx_round = dev_zeros(sizeof(rd_rx_round) * B);
-    h->rx_avail = dev_zeros(sizeof(int) * B); /* progress word, per-stream counters and status in ONE block, in the order of the host copy (rade_batch_rx: one transfer back per invocation) */
-    h->rx_progress = dev_zeros(sizeof(int) * (8 + B * 8));
-    if (h->rx_progress) { h->rx_acc = h->rx_progress + 8; h->rx_status = h->rx_progress + 8 + 4 * B; }
-    h->wg_cycles = dev_zeros(sizeof(long long) * B);
-    h->zrows = dev_zeros(sizeof(float) * B * DR * RD_LATENT);
-    h->dec_x = dev_zeros(sizeof(float) * B * (1 + DR) * RD_DEC_W);
-    h->dec_gi = dev_zeros(sizeof(float) * B * DR * 288);
-    h->dec_hbuf = dev_zeros(sizeof(float) * B * DR * 96);
-    h->feat84 = dev_zeros(sizeof(float) * B * DR * 84);
-    h->dec2_x = dev_zeros(sizeof(float) * B * (1 + T) * RD_DEC_W);
-    h->dec2_gi = dev_zeros(sizeof(float) * B * T * 288);
-    h->dec2_hbuf = dev_zeros(sizeof(float) * B * T * 96);
-    h->dec2_h[0] = dev_zeros(sizeof(float) * 5 * B * 96);
-    if (!h->dec2_h[0]) goto fail;
     for (int l = 1; l < 5; l++) h->dec2_h[l] = h->dec2_h[0] + (size_t)l * B * 96;
-    if (!h->dec2_x || !h->dec2_gi || !h->dec2_hbuf) goto fail;
-    h->dtcache = dev_zeros(sizeof(float) * B * 2 * RD_NMF * RD_NFC);
-    if (!h->enc_xin || !h->enc_x || !h->enc_gi || !h->enc_z || !h->eoo || !h->eoo_bits || !h->chan_scratch || !h->rx_st || !h->rx_round || !h->rx_avail ||
-        !h->rx_acc || !h->rx_progress || !h->rx_status || !h->zrows || !h->dec_x || !h->dec_gi || !h->dec_hbuf || !h->feat84 || !h->dtcache) {
-        fprintf(stderr, "rade: device allocation failed\n"); goto fail;
-    }
+    h->rx_acc = h->rx_progress + 8; h->rx_status = h->rx_progress + 8 + 4 * B;
+    h->rx_st = dev_zeros(h, sizeof(rd_rx_stream) * B);
+    h->rx_round = dev_zeros(h, sizeof(rd_rx_round) * B);
+    h->rx_avail = dev_zeros(h, sizeof(int) * B);
+    h->wg_cycles = dev_zeros(h, sizeof(long long) * B);
+    h->zrows = dev_zeros(h, sizeof(float) * B * DR * RD_LATENT);
+    h->dec_x = dev_zeros(h, sizeof(float) * B * (1 + DR) * RD_DEC_W);
+    h->dec_gi = dev_zeros(h, sizeof(float) * B * DR * 288);
+    h->dec_hbuf = dev_zeros(h, sizeof(float) * B * DR * 96);
+    h->feat84 = dev_zeros(h, sizeof(float) * B * DR * 84);
+    h->dec2_x = dev_zeros(h, sizeof(float) * B * (1 + T) * RD_DEC_W);
+    h->dec2_gi = dev_zeros(h, sizeof(float) * B * T * 288);
+    h->dec2_hbuf = dev_zeros(h, sizeof(float) * B * T * 96);
+    h->dtcache = dev_zeros(h, sizeof(float) * B * 2 * RD_NMF * RD_NFC);
     if (h->trace_cap > 0) {
-        h->trace = dev_zeros(sizeof(rd_rx_trace) * B * h->trace_cap);
-        h->trace_z = dev_zeros(sizeof(float) * B * h->trace_cap * RD_ZMF);
-        if (!h->trace || !h->trace_z) goto fail;
+        h->trace = dev_zeros(h, sizeof(rd_rx_trace) * B * h->trace_cap);
+        h->trace_z = dev_zeros(h, sizeof(float) * B * h->trace_cap * RD_ZMF);
     }
-    CHK(hipHostMalloc((void **)&h->h_small, sizeof(int) * (8 + B * 8), 0));
+    h->h_small = must(h, pinned_alloc_opt(h, sizeof(int) * (8 + B * 8)));
     h->lcg_seeds = malloc(sizeof(unsigned) * B);
     for (size_t b = 0; b < B; b++) h->lcg_seeds[b] = 1u;
-    h->d_lcg_seeds = dev_upload(h->lcg_seeds, sizeof(unsigned) * B);
-    if (!h->d_lcg_seeds) goto fail;
+    h->d_lcg_seeds = dev_upload(h, h->lcg_seeds, sizeof(unsigned) * B);
+    if (h->alloc_failed) { fprintf(stderr, "rade: device allocation failed\n"); goto fail; }
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) CHK(hipEventCreate(&h->prof_ev[i]));
     CHK(hipEventCreateWithFlags(&h->ev_block, hipEventBlockingSync | hipEventDisableTiming));
     rade_batch_rx_reset(h);
@@ -412,23 +438,11 @@ rade_batch *rade_batch_open(const char *blob_path, const rade_batch_config *cfg)
     return h;
 }
 
-static void free_lin(dev_lin *d) { if (d->wp) hipFree(d->wp); if (d->bias) hipFree(d->bias); if (d->wp16) hipFree(d->wp16); if (d->wa16) hipFree(d->wa16); if (d->wscale) hipFree(d->wscale); if (d->wscale16) hipFree(d->wscale16); }
 void rade_batch_close(rade_batch *h)
 {
     if (!h) return;
     ON_DEV(h);
-    void *bufs[] = { h->d_tab, h->enc_xin, h->enc_x, h->enc_xf, h->enc_gi, h->enc_z, h->eoo, h->eoo_bits, h->chan_scratch, h->rx_st, h->rx_round, h->rx_avail,
-                     h->rx_progress /* + rx_acc, rx_status */, h->wg_cycles, h->zrows, h->dec_x, h->dec_gi, h->dec_hbuf, h->feat84, h->trace, h->trace_z, h->d_lcg_seeds, h->dtcache, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->rx_filt, h->bpf_chain, h->bpf16, h->tx_bpf, h->tx_bpf_init, h->tx_raw, h->tx_chain, h->eoo_filt, h->corrq16, h->corra16, h->vm, h->chan_mp, h->wfwd16,
-                     h->irx_part, h->irx_foff, h->irx_err, h->chan_ps, h->loss_len, h->loss_res, h->loss_part };
-    for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; i++) if (bufs[i]) hipFree(bufs[i]);
-    free_lin(&h->enc_dense1); free_lin(&h->enc_zdense); free_lin(&h->dec_dense1); free_lin(&h->dec_output);
-    for (int l = 0; l < 5; l++) {
-        free_lin(&h->enc_gin[l]); free_lin(&h->dec_gin[l]); free_lin(&h->enc_conv[l]); free_lin(&h->dec_conv[l]); free_lin(&h->dec_glu[l]);
-        void *p[] = { h->enc_whh[l], h->enc_bhh[l], h->dec_whh[l], h->dec_bhh[l], l ? NULL : h->enc_h[0], l ? NULL : h->dec_h[0], l ? NULL : h->dec2_h[0], h->dec_whq[l], h->dec_whs[l] };
-        for (int i = 0; i < 9; i++) if (p[i]) hipFree(p[i]);
-    }
-    if (h->h_small) hipHostFree(h->h_small);
-    if (h->chan_ps_host) hipHostFree(h->chan_ps_host);
+    while (h->owned) disown(h, h->owned->p);
     if (h->ev_block) hipEventDestroy(h->ev_block);
     __atomic_sub_fetch(&g_engines_open, 1, __ATOMIC_RELAXED);
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) if (h->prof_ev[i]) hipEventDestroy(h->prof_ev[i]);
@@ -579,34 +593,45 @@ static int encode_core(rade_batch *h, int T, float *z, void *stream)
 }
 
 /* the optional Tx band-pass filter + magnitude clip (radae_txe.py:130-132, :141-143) over the n samples the modulator left in tx_raw: the receiver's
- * filtering pass with frames as blocks (len0 = the first frame: 960, or the 1152-sample end-of-over frame), every sample consumed */
-static int tx_bpf_pass_adv(rade_batch *h, int n, int len0, void *out, long out_stride, void *stream, int advance)
+ * filtering pass with frames as blocks (len0 = the first frame: 960, or the 1152-sample end-of-over frame), every sample consumed (advance = 0: the filter state is left as it was) */
+static int tx_bpf_pass(rade_batch *h, int n, int len0, void *out, long out_stride, void *stream, int advance)
 {
     rd_bpf_args ba;
     memset(&ba, 0, sizeof ba);
     ba.state = h->tx_bpf; ba.state_stride = sizeof(rd_bpf_state); ba.len0_const = len0; ba.avail_const = n;
-    ba.tab = h->d_tab; ba.bpf16 = h->bpf16; ba.x = h->tx_raw; ba.x_stride = (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF; ba.y = out; ba.y_stride = out_stride;
+    ba.tab = h->d_tab; ba.bpf16 = h->bpf16; ba.x = h->tx_raw; ba.x_stride = tx_raw_stride(h); ba.y = out; ba.y_stride = out_stride;
     ba.chain = h->tx_chain; ba.chain_stride = h->max_tx_mf + 8; ba.n_blocks = 1 + (n > len0 ? (n - len0 + RD_NMF - 1) / RD_NMF : 0); ba.B = h->B; ba.clip = 1; ba.advance = advance;
     PROF_BEGIN(h, stream);
     const int rc = rd_launch_bpf(&ba, stream);
     PROF_END(h, stream, RADE_PROF_BPF, 8.0 * 101.0 * (double)h->B * n);
     return rc;
 }
-static int tx_bpf_pass(rade_batch *h, int n, int len0, void *out, long out_stride, void *stream) { return tx_bpf_pass_adv(h, n, len0, out, out_stride, stream, 1); }
+
+/* the transmitter's front: the features packed into the encoder's input rows (enc_xin), then the core encoder */
+static int encode_features(rade_batch *h, const float *features_dev, int T, float *z, void *stream)
+{
+    const int e = rd_launch_enc_pack(features_dev, h->enc_xin, h->B, T, stream);
+    return e | encode_core(h, T, z, stream);
+}
+/* and its tail: the modulator, into tx_raw and through the Tx band-pass filter where the engine has one */
+static int modulate(rade_batch *h, const float *z, int n_mf, void *iq_out, long iq_stride, void *stream)
+{
+    void *mod_out = h->tx_bpf ? h->tx_raw : iq_out; const long mod_stride = h->tx_bpf ? tx_raw_stride(h) : iq_stride;
+    PROF_BEGIN(h, stream);
+    int e = rd_launch_ofdm_mod(h->d_tab, z, mod_out, mod_stride, h->B, n_mf, h->tx_linear, stream);
+    PROF_END(h, stream, RADE_PROF_MOD, 8.0 * h->B * n_mf * 5 * 30 * 160);
+    if (h->tx_bpf) e |= tx_bpf_pass(h, n_mf * RD_NMF, RD_NMF, iq_out, iq_stride, stream, 1);
+    return e;
+}
 
 /* ---- transmit (radae_txe.py:108-135 for n_mf modem frames and B streams at once) -------------- */
 int rade_batch_tx(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, float *z_out_dev, void *stream)
 {
     ON_DEV(h);
     if (!h || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84) return -1;
-    const int B = h->B, T = 3 * n_mf;
     float *z = z_out_dev ? z_out_dev : h->enc_z;
-    int e = 0;
-    e |= rd_launch_enc_pack(features_dev, h->enc_xin, B, T, stream);
-    e |= encode_core(h, T, z, stream);
-    void *mod_out = h->tx_bpf ? h->tx_raw : iq_out_dev; const long mod_stride = h->tx_bpf ? (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF : iq_stride;
-    PROF_BEGIN(h, stream); e |= rd_launch_ofdm_mod(h->d_tab, z, mod_out, mod_stride, B, n_mf, h->tx_linear, stream); PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
-    if (h->tx_bpf) e |= tx_bpf_pass(h, n_mf * RD_NMF, RD_NMF, iq_out_dev, iq_stride, stream);
+    int e = encode_features(h, features_dev, 3 * n_mf, z, stream);
+    e |= modulate(h, z, n_mf, iq_out_dev, iq_stride, stream);
     return e ? -1 : n_mf * RD_NMF;
 }
 
@@ -615,12 +640,7 @@ int rade_batch_tx_latents(rade_batch *h, const float *z_dev, int n_mf, void *iq_
 {
     ON_DEV(h);
     if (!h || !z_dev || !iq_out_dev || n_mf <= 0 || n_mf > h->max_tx_mf) return -1;
-    const int B = h->B;
-    int e = 0;
-    void *mod_out = h->tx_bpf ? h->tx_raw : iq_out_dev; const long mod_stride = h->tx_bpf ? (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF : iq_stride;
-    PROF_BEGIN(h, stream); e |= rd_launch_ofdm_mod(h->d_tab, z_dev, mod_out, mod_stride, B, n_mf, h->tx_linear, stream); PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
-    if (h->tx_bpf) e |= tx_bpf_pass(h, n_mf * RD_NMF, RD_NMF, iq_out_dev, iq_stride, stream);
-    return e ? -1 : n_mf * RD_NMF;
+    return modulate(h, z_dev, n_mf, iq_out_dev, iq_stride, stream) ? -1 : n_mf * RD_NMF;
 }
 
 /* ---- core encoder / decoder alone (the rade_core_encoder / rade_core_decoder level, src/rade_core.h:42-46) ---- */
@@ -646,8 +666,8 @@ int rade_batch_tx_eoo(rade_batch *h, void *iq_out_dev, long iq_stride, void *str
     ON_DEV(h);
     if (h->tx_linear) return -1;           /* the end-of-over frame is built with the bottleneck-3 pilot gain and limiter */
     if (!h->tx_bpf) return rd_launch_copy_eoo(h->eoo, iq_out_dev, iq_stride, h->B, stream) ? -1 : RD_NEOO;
-    int e = rd_launch_copy_eoo(h->eoo, h->tx_raw, (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF, h->B, stream);
-    e |= tx_bpf_pass(h, RD_NEOO, RD_NEOO, iq_out_dev, iq_stride, stream);
+    int e = rd_launch_copy_eoo(h->eoo, h->tx_raw, tx_raw_stride(h), h->B, stream);
+    e |= tx_bpf_pass(h, RD_NEOO, RD_NEOO, iq_out_dev, iq_stride, stream, 1);
     return e ? -1 : RD_NEOO;
 }
 
@@ -664,49 +684,59 @@ float rade_sigma_from_EbNodB_bn1(float EbNodB)
     return powf(EbNo * (float)RD_M, -0.5f);
 }
 
-/* the [3][B] per-stream sigma, freq_offset, df_dt of a call on the device (rd_chan_args.ps), a NULL member filled with p's scalar; *out = NULL when ps gives none.
- * Uploaded like rade_batch_rx_ideal's offsets: through pinned memory, the stream synchronised before the staging copy can be reused. */
+/* `rows` arrays of B 4-byte values (row r: src[r], or fill[r] where that is NULL, 0 without fill) through pinned `stage` to `dev`; wait = 0: the caller synchronises before it reuses `stage` */
+static int stage_rows(rade_batch *h, void *stage, void *dev, int rows, const void *const *src, const float *fill, int wait, hipStream_t st)
+{
+    float *f = stage;
+    for (int r = 0; r < rows; r++, f += h->B)
+        if (src[r]) memcpy(f, src[r], sizeof(float) * h->B);
+        else for (int b = 0; b < h->B; b++) f[b] = fill ? fill[r] : 0.0f;
+    if (hipMemcpyAsync(dev, stage, sizeof(float) * rows * h->B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    return wait && hipStreamSynchronize(st) != hipSuccess ? -1 : 0;
+}
+
+/* the [3][B] per-stream sigma, freq_offset, df_dt of a call on the device (rd_chan_args.ps), a NULL member filled with p's scalar; *out = NULL when ps gives none */
 static int chan_streams_upload(rade_batch *h, const rade_channel_params *p, const rade_channel_streams *ps, void *stream, const float **out)
 {
     *out = NULL;
     if (!ps || (!ps->sigma && !ps->freq_offset && !ps->df_dt)) return 0;
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->chan_ps && !(h->chan_ps = dev_zeros(sizeof(float) * 3 * B))) return -1;
-    if (!h->chan_ps_host && hipHostMalloc((void **)&h->chan_ps_host, sizeof(float) * 3 * B, 0) != hipSuccess) { h->chan_ps_host = NULL; return -1; }
-    float *f = h->chan_ps_host;
-    for (int b = 0; b < B; b++) {
-        f[b] = ps->sigma ? ps->sigma[b] : p->sigma;
-        f[B + b] = ps->freq_offset ? ps->freq_offset[b] : p->freq_offset;
-        f[2 * B + b] = ps->df_dt ? ps->df_dt[b] : p->df_dt;
-    }
-    if (hipMemcpyAsync(h->chan_ps, f, sizeof(float) * 3 * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    if (dev_grow(h, &h->chan_ps, NULL, 3 * h->B, sizeof(float), 1)) return -1;
+    if (!h->chan_ps_host && !(h->chan_ps_host = pinned_alloc_opt(h, sizeof(float) * 3 * h->B))) return -1;
+    const void *src[3] = { ps->sigma, ps->freq_offset, ps->df_dt };
+    const float fill[3] = { p->sigma, p->freq_offset, p->df_dt };
+    if (stage_rows(h, h->chan_ps_host, h->chan_ps, 3, src, fill, 1, (hipStream_t)stream)) return -1;
     *out = h->chan_ps;
     return 0;
+}
+
+/* one k_channel launch: the signal from tx, or from mp where the fused modulator (k_ofdm_mod_mp) left its multipath output; eoo = the end-of-over frame as transmitted */
+static int channel_launch(rade_batch *h, const rade_channel_params *p, const float *ps_dev, const void *tx, long tx_stride, const void *mp, const float *eoo, void *rx, long rx_stride, void *stream)
+{
+    rd_chan_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.tx = tx; a.tx_stride = tx_stride; a.rx = rx; a.rx_stride = rx_stride; a.G = p->G_dev; a.noise = p->noise_dev; a.mp = mp;
+    a.eoo = eoo; a.scratch = h->chan_scratch; a.B = h->B; a.n_sig = p->n_sig; a.n_pre = p->n_pre; a.n_post = p->n_post; a.with_eoo = p->with_eoo;
+    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed; a.ps = ps_dev;
+    a.sine_amp = p->sine_amp; a.sine_freq = p->sine_freq; a.rx_gain = p->rx_gain != 0.0f ? p->rx_gain : 1.0f;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_channel(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
+    return p->n_pre + p->n_sig + (p->with_eoo ? RD_NEOO : 0) + p->n_post;
 }
 
 /* rade_batch_channel_streams with the per-stream values already on the device (ps_dev, or NULL) */
 static int channel_dev(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride, const rade_channel_params *p, const float *ps_dev, void *stream)
 {
     if (h->tx_linear && p->with_eoo) return -1;
-    rd_chan_args a;
-    memset(&a, 0, sizeof a);
-    a.tab = h->d_tab; a.tx = tx_dev; a.tx_stride = tx_stride; a.rx = rx_out_dev; a.rx_stride = rx_stride; a.G = p->G_dev; a.noise = p->noise_dev;
-    a.eoo = h->eoo; a.scratch = h->chan_scratch; a.B = h->B; a.n_sig = p->n_sig; a.n_pre = p->n_pre; a.n_post = p->n_post; a.with_eoo = p->with_eoo;
-    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed; a.ps = ps_dev;
-    a.sine_amp = p->sine_amp; a.sine_freq = p->sine_freq; a.rx_gain = p->rx_gain != 0.0f ? p->rx_gain : 1.0f;
+    const float *eoo = h->eoo;
     if (h->tx_bpf && p->with_eoo) {        /* what radae_tx --txbpf transmits after the last frame: the end-of-over frame through the Tx band-pass filter and the clip,
                                             * the filter state carried on from the frames before it (radae_txe.py:138-144) */
         /* a pure channel call: the filter state is READ, not advanced (two passes over the same tx -- two SNR points, a two-pass bench -- see the same EOO);
          * tx_raw is the modulator's scratch and holds nothing a caller can see */
-        if (rd_launch_copy_eoo(h->eoo, h->tx_raw, (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF, h->B, stream) ||
-            tx_bpf_pass_adv(h, RD_NEOO, RD_NEOO, h->eoo_filt, RD_NEOO, stream, 0)) return -1;
-        a.eoo = h->eoo_filt;
+        if (rd_launch_copy_eoo(h->eoo, h->tx_raw, tx_raw_stride(h), h->B, stream) || tx_bpf_pass(h, RD_NEOO, RD_NEOO, h->eoo_filt, RD_NEOO, stream, 0)) return -1;
+        eoo = h->eoo_filt;
     }
-    PROF_BEGIN(h, stream);
-    if (rd_launch_channel(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
-    return p->n_pre + p->n_sig + (p->with_eoo ? RD_NEOO : 0) + p->n_post;
+    return channel_launch(h, p, ps_dev, tx_dev, tx_stride, NULL, eoo, rx_out_dev, rx_stride, stream);
 }
 
 int rade_batch_channel_streams(rade_batch *h, const void *tx_dev, long tx_stride, void *rx_out_dev, long rx_stride,
@@ -738,24 +768,14 @@ int rade_batch_tx_channel_streams(rade_batch *h, const float *features_dev, int 
         if (rade_batch_tx(h, features_dev, n_mf, iq_out_dev, iq_stride, NULL, stream) != p->n_sig) return -1;
         return channel_dev(h, iq_out_dev, iq_stride, rx_out_dev, rx_stride, p, ps_dev, stream);
     }
-    if (!h->chan_mp && !(h->chan_mp = dev_zeros(sizeof(float) * 2 * (size_t)h->B * h->max_tx_mf * RD_NMF))) return -1;
-    const int B = h->B, T = 3 * n_mf;
-    int e = rd_launch_enc_pack(features_dev, h->enc_xin, B, T, stream);
-    e |= encode_core(h, T, h->enc_z, stream);
+    if (dev_grow(h, &h->chan_mp, NULL, (long)h->B * h->max_tx_mf * RD_NMF, sizeof(float) * 2, 1)) return -1;
+    const int B = h->B;
+    int e = encode_features(h, features_dev, 3 * n_mf, h->enc_z, stream);
     PROF_BEGIN(h, stream);
     e |= rd_launch_ofdm_mod_mp(h->d_tab, h->enc_z, iq_out_dev, iq_stride, B, n_mf, p->G_dev, h->chan_mp, (double *)h->chan_scratch + 2 * (size_t)B, h->tx_linear, stream);
     PROF_END(h, stream, RADE_PROF_MOD, 8.0 * B * n_mf * 5 * 30 * 160);
     if (e) return -1;
-    rd_chan_args a;
-    memset(&a, 0, sizeof a);
-    a.tab = h->d_tab; a.tx = NULL; a.tx_stride = 0; a.rx = rx_out_dev; a.rx_stride = rx_stride; a.G = p->G_dev; a.noise = p->noise_dev; a.mp = h->chan_mp;
-    a.eoo = h->eoo; a.scratch = h->chan_scratch; a.B = B; a.n_sig = p->n_sig; a.n_pre = p->n_pre; a.n_post = p->n_post; a.with_eoo = p->with_eoo;
-    a.sigma = p->sigma; a.freq_offset = p->freq_offset; a.df_dt = p->df_dt; a.seed = p->seed; a.ps = ps_dev;
-    a.sine_amp = p->sine_amp; a.sine_freq = p->sine_freq; a.rx_gain = p->rx_gain != 0.0f ? p->rx_gain : 1.0f;
-    PROF_BEGIN(h, stream);
-    if (rd_launch_channel(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
-    return p->n_pre + p->n_sig + (p->with_eoo ? RD_NEOO : 0) + p->n_post;
+    return channel_launch(h, p, ps_dev, NULL, 0, h->chan_mp, h->eoo, rx_out_dev, rx_stride, stream);
 }
 
 int rade_batch_tx_channel(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, void *rx_out_dev, long rx_stride,
@@ -769,15 +789,15 @@ int rade_batch_multipath_gen(rade_batch *h, const float *fir_taps_host, int n_ta
 {
     ON_DEV(h);
     if (!h || !fir_taps_host || n_taps <= 0 || n_taps > 1024 || !G_out_dev) return -1;
-    float *taps = dev_upload(fir_taps_host, sizeof(float) * n_taps);
-    if (!taps) return -1;
+    float *taps = NULL;                                 /* (the call's two buffers live for the call only: not recorded on the engine) */
+    if (hipMalloc((void **)&taps, sizeof(float) * n_taps) != hipSuccess || hipMemcpy(taps, fir_taps_host, sizeof(float) * n_taps, hipMemcpyHostToDevice) != hipSuccess) { hipFree(taps); return -1; }
     void *ybuf = NULL;                                  /* more low-rate points than the kernel keeps in LDS (lmr60: Fs / 16): they live in HBM for the call */
     if (rd_multipath_gen_needs_scratch(low_ratio, n_out)) {
         const size_t n_low = (size_t)(n_out + low_ratio - 1) / low_ratio;
         if (hipMalloc(&ybuf, sizeof(double) * 2 * 2 * n_low * h->B) != hipSuccess) { hipFree(taps); return -1; }
     }
     const int rc = rd_launch_multipath_gen(taps, n_taps, low_ratio, n_out, noise_low_dev, seed, G_out_dev, ybuf, h->B, stream);
-    hipStreamSynchronize((hipStream_t)stream);          /* the tap buffer is released right away */
+    hipStreamSynchronize((hipStream_t)stream);          /* the call's two buffers are released right away */
     hipFree(taps);
     if (ybuf) hipFree(ybuf);
     return rc ? -1 : n_out;
@@ -855,18 +875,10 @@ int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n
         p->eq < RADE_EQ_LS || p->eq > RADE_EQ_NONE || (features_out_dev && 3 * n_mf > h->Tcap) || (p->n_errors_host && !p->z_ref_dev)) return -1;
     const int B = h->B;
     hipStream_t st = (hipStream_t)stream;
-    if (n_mf > h->irx_part_cap) {
-        if (h->irx_part) { hipStreamSynchronize(st); hipFree(h->irx_part); }
-        h->irx_part = dev_zeros(sizeof(double) * (size_t)B * n_mf);
-        h->irx_part_cap = h->irx_part ? n_mf : 0;
-        if (!h->irx_part) return -1;
-    }
-    if (!h->irx_foff && !(h->irx_foff = dev_zeros(sizeof(float) * 2 * B))) return -1;
-    if (!h->irx_err && !(h->irx_err = dev_zeros(sizeof(long long) * B))) return -1;
+    if (dev_grow(h, &h->irx_part, &h->irx_part_cap, n_mf, sizeof(double) * B, 1) || dev_grow(h, &h->irx_foff, NULL, 2 * B, sizeof(float), 1) || dev_grow(h, &h->irx_err, NULL, B, sizeof(long long), 1)) return -1;
     if (p->freq_offset_host) {
-        float *f = (float *)h->h_small;          /* pinned scratch, >= 8 B ints */
-        for (int b = 0; b < B; b++) { f[b] = p->freq_offset_host[b]; f[B + b] = p->df_dt_host ? p->df_dt_host[b] : 0.0f; }
-        if (hipMemcpyAsync(h->irx_foff, f, sizeof(float) * 2 * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        const void *src[2] = { p->freq_offset_host, p->df_dt_host };
+        if (stage_rows(h, h->h_small, h->irx_foff, 2, src, NULL, 1, st)) return -1;      /* h_small: pinned scratch, >= 8 B ints */
     }
     rd_irx_args a;
     memset(&a, 0, sizeof a);
@@ -903,19 +915,12 @@ int rade_batch_loss(rade_batch *h, const float *features_dev, long f_stride, int
         if (frame_loss_dev && fl_stride < m) return -1;   /* a stream's curve has at most n_hat frames */
         n_scored++;
     }
-    if (!h->loss_len && !(h->loss_len = dev_zeros(sizeof(int) * 2 * B))) return -1;
-    if (!h->loss_res && !(h->loss_res = dev_zeros((sizeof(double) + sizeof(int)) * B))) return -1;
-    if (n_blk > h->loss_part_cap) {
-        if (h->loss_part) { hipStreamSynchronize(st); hipFree(h->loss_part); }
-        h->loss_part = dev_zeros((sizeof(double) + sizeof(int)) * (size_t)B * n_blk);
-        h->loss_part_cap = h->loss_part ? n_blk : 0;
-        if (!h->loss_part) return -1;
-    }
+    if (dev_grow(h, &h->loss_len, NULL, 2 * B, sizeof(int), 1) || dev_grow(h, &h->loss_res, NULL, B, sizeof(double) + sizeof(int), 1)) return -1;
+    if (n_blk > h->loss_part_cap && dev_grow(h, &h->loss_part, &h->loss_part_cap, n_blk, (sizeof(double) + sizeof(int)) * B, 1)) return -1;
     /* pinned scratch (8 + 8 B ints): the lengths [2][B] ints, then the results [B] doubles + [B] ints; the call synchronises before it returns */
-    int *len = h->h_small;
     double *res = (double *)(h->h_small + 2 * B);
-    for (int b = 0; b < B; b++) { len[b] = n_in_host[b]; len[B + b] = n_hat_host[b]; }
-    if (hipMemcpyAsync(h->loss_len, len, sizeof(int) * 2 * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    const void *len[2] = { n_in_host, n_hat_host };
+    if (stage_rows(h, h->h_small, h->loss_len, 2, len, NULL, 0, st)) return -1;
     rd_loss_args a;
     memset(&a, 0, sizeof a);
     a.feat = features_dev; a.f_stride = f_stride; a.f_row = f_row; a.hat = hat_dev; a.h_stride = h_stride; a.h_row = h_row; a.len = h->loss_len;
@@ -998,15 +1003,9 @@ int rade_batch_rx(rade_batch *h, const void *rx_dev, long rx_stride, const int *
     const int n_blocks = max_avail > 0 ? 2 + (max_avail - 1) / 800 : 0;          /* blocks of >= 800 samples (a first block after a slip), the tail included */
     if (max_avail > h->filt_cap || n_blocks + 3 > h->chain_stride) {
         CHK(hipDeviceSynchronize());
-        if (h->rx_filt) hipFree(h->rx_filt);
-        if (h->bpf_chain) hipFree(h->bpf_chain);
-        h->filt_cap = ((long)max_avail + 1023) & ~1023L; h->chain_stride = (int)(h->filt_cap / 800) + 8;
-        /* (no memset: a hipMemset on the null stream is not ordered against the caller's non-blocking stream and could land on top of the
-         * pre-pass's results; every entry that is read is written by the pre-pass first) */
-        h->rx_filt = NULL; h->bpf_chain = NULL;
-        if (hipMalloc(&h->rx_filt, sizeof(float) * 2 * (size_t)B * h->filt_cap) != hipSuccess) h->rx_filt = NULL;
-        if (hipMalloc((void **)&h->bpf_chain, sizeof(float) * 2 * (size_t)B * h->chain_stride) != hipSuccess) h->bpf_chain = NULL;
-        if (!h->rx_filt || !h->bpf_chain) { h->filt_cap = 0; h->chain_stride = 0; fprintf(stderr, "rade: device allocation failed (receiver pre-pass buffers)\n"); return -1; }
+        const long cap = ((long)max_avail + 1023) & ~1023L;       /* not zeroed: every entry that is read is written by the pre-pass first (dev_grow) */
+        const int e = dev_grow(h, &h->rx_filt, &h->filt_cap, cap, sizeof(float) * 2 * B, 0) || dev_grow(h, &h->bpf_chain, &h->chain_stride, cap / 800 + 8, sizeof(float) * 2 * B, 0);
+        if (e) { fprintf(stderr, "rade: device allocation failed (receiver pre-pass buffers)\n"); return -1; }
     }
     CHK(hipMemcpyAsync(h->rx_avail, n_avail_host, sizeof(int) * B, hipMemcpyHostToDevice, st));
     PROF_BEGIN(h, st);
@@ -1084,7 +1083,7 @@ int rade_batch_rx_filtered(rade_batch *h, int b, void *out_host, int n)
 int rade_batch_rx_get_trace(rade_batch *h, int b, rade_rx_trace *out, float *z_hat_out, int max_calls)
 {
     ON_DEV(h);
-    if (!h->trace || b < 0 || b >= h->B) return -1;
+    if (!h || !h->trace || b < 0 || b >= h->B) return -1;
     rd_rx_stream *tmp = malloc(sizeof *tmp);
     hipMemcpy(tmp, h->rx_st + b, sizeof *tmp, hipMemcpyDeviceToHost);
     int n = tmp->mf - 1;

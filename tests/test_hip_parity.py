@@ -1360,6 +1360,58 @@ def test_tx_channel_one_pass_equals_two_calls(Engine, torch_dev, oracle, oracle_
     e1.close(); e2.close()
 
 
+def test_engine_open_close_returns_device_memory(Engine, torch_dev):
+    """rade_batch_close gives back everything an engine allocated, the buffers allocated on first use included: free device memory after the sixth
+    open / drive / close cycle is not below what it was after the second (the first cycle is warm-up: code objects, the caching allocator's pool).
+    A cycle drives every lazily allocated path of an engine opened with RADE_BATCH_TX_BPF and a receiver trace -- the per-stream channel values and
+    their pinned staging copy, the receiver's pre-pass buffers (grown once: two invocations of different length), the ideal receiver's partials,
+    offsets and error counts, the loss call's lengths, results and partials -- and, on a second engine without the Tx filter, the fused modulator's
+    multipath buffer.
+    Allowance: 0 bytes.  Measured on an MI355X with the close that freed from hand-kept lists and with the one that frees what the engine recorded:
+    all six readings of a run of this body are one number, 308291829760 bytes with either, so the comparison is exact (one-sided: more free memory
+    is no leak).
+    What the reading resolves: this runtime reports free memory in steps of 2 MiB and serves allocations under about 1 MiB from 2 MiB chunks of its
+    own (four 64 KiB hipMallocs do not move the reading, four of 2 MiB move it by 8 MiB).  64 streams put the on-demand buffers that scale with the
+    call above that: the pre-pass samples (2 MiB for the first invocation, 7.3 MB after the growth) and the fused modulator's multipath output
+    (5.9 MB), like most of the engine's fixed buffers; one of these kept per cycle lowers the sixth reading by four times its size.
+    NOT covered by the reading: the on-demand buffers that stay far below a chunk at any practical size -- the pre-pass block phases (13 KB), the
+    ideal receiver's partials, offsets and counts, the loss call's lengths, results and partials, the per-stream channel values (bytes to a few KB)
+    -- and the pinned staging copy, which is host memory.  They are allocated, recorded and released by the same dev_grow / own path as the buffers
+    the reading does cover; a leak of one of them alone would pass here: for these the test does not hold the bound 'one leaked buffer per cycle fails'."""
+    import torch
+    from radae_amd.channel_tools import multipath_g, synth_features
+    from radae_amd.engine import sigma_from_EbNodB
+    B, n_mf = 64, 12                                                         # four distinct utterances and channels, sixteen copies of each
+    feats = torch.tensor(np.tile(np.stack([synth_features(60 + b, 12 * n_mf) for b in range(4)]), (16, 1, 1)), device=torch_dev)
+    G = torch.tensor(np.tile(np.stack([multipath_g("mpp", 8000, n_mf * 960, 80 + b) for b in range(4)]), (16, 1, 1)), device=torch_dev)
+    sigma = [float(sigma_from_EbNodB(4.0 + 0.125 * b)) for b in range(B)]
+
+    def cycle():
+        eng = Engine(B, max_tx_mf=n_mf, flags=0x400, rx_trace_calls=32)      # RADE_BATCH_TX_BPF
+        eng.tx_channel(feats, sigma, 3.0, n_pre=300, n_post=200, with_eoo=True, G=G, seed=5, want_iq=True)
+        eng.tx_reset()
+        iq, z = eng.tx(feats, want_z=True)
+        rx = eng.channel(iq, sigma[2], 3.0, n_pre=300, n_post=200, with_eoo=True, G=G, seed=6)
+        eng.rx(rx, n_avail=np.full(B, 4000, np.int32))
+        eng.rx(rx)
+        aligned = eng.channel(iq, sigma[3], 3.0, G=G, seed=7)
+        fhat, _, n_err = eng.rx_ideal(aligned, n_mf, freq_offset=3.0, z_ref=z)
+        loss, start, curve = eng.loss(feats, fhat, frame_loss=True)
+        assert n_err is not None and np.all(start >= 0) and np.all(np.isfinite(loss)) and curve is not None     # every path ran and scored
+        eng.close()
+        fused = Engine(B, max_tx_mf=n_mf)
+        fused.tx_channel(feats, sigma, 3.0, n_pre=300, n_post=200, with_eoo=True, G=G, seed=5)
+        torch.cuda.synchronize()
+        fused.close()
+
+    free = []
+    for _ in range(6):
+        cycle()
+        torch.cuda.synchronize(); torch.cuda.empty_cache()
+        free.append(torch.cuda.mem_get_info()[0])
+    print("free device memory after each cycle:", free)
+    assert free[5] >= free[1], free
+
 
 
 def test_rx2_replicas_agree_when_two_workgroups_share_a_cu(Engine, torch_dev, golden, monkeypatch):
