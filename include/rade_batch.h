@@ -66,6 +66,39 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
 void rade_batch_close(rade_batch *h);
 int rade_batch_n_streams(const rade_batch *h);
 
+/* ---- Buffers, strides and alignment (pinned by tests/test_buffer_contract_gpu.py) ------------------------------------------------------------------------------
+ * Strides are counted in ELEMENTS of the buffer they belong to: complex64 samples for iq_stride, tx_stride, rx_stride (rade_batch_* and rade_sc_*), floats for
+ * feat_stride, f_stride / f_row, h_stride / h_row and fl_stride.  Stream b's row starts at base + b * stride; stride >= the row length of the call is all a stride
+ * has to satisfy (no multiple of anything; an odd stride is fine) unless an entry below says more.  Buffers without a stride argument are dense:
+ * [B][rows of this call][width], whatever the engine's capacity (max_tx_mf) is.
+ * Writes: a call writes the row [b * stride, b * stride + row) of each output it documents and NOTHING else of the caller's memory -- not the gap up to the next
+ * row, not a byte before row 0 or behind the last row, and never an input buffer.  Inside a row it writes exactly the documented extent: n_total samples of
+ * rx_out, n_valid * 432 (240) floats of features_out, n_hat - start floats of a scored stream's frame_loss row; the rest of the row keeps what it held.
+ * Alignment: every pointer is aligned to its ELEMENT (4 bytes for float buffers, 8 bytes for complex64 buffers, G_dev and noise_low_dev included), and that is
+ * enough -- base pointers at odd element offsets are fine -- except for the four buffers that kernels access as 16-byte words.  Those must be 16-byte aligned,
+ * and the entry returns -1 on the host, before any launch and with nothing written, when they are not:
+ *     rade_batch_tx, rade_batch_encode          z_out_dev     (rade_enc.hip stores the latents of a call of more than 16384 rows as f32x4; refused for every size)
+ *     rade_batch_decode                         z_dev         (the GEMMs read their A rows as f32x4, and the first layer's rows are the caller's)
+ *     rade_batch_rx_ideal                       z_hat_dev     when features_out_dev is given (the decoder then reads it like rade_batch_decode's z_dev)
+ *     rade_batch_tx_channel(_streams)           p->G_dev      (the fused modulator reads (G1[i], G2[i]) as one 16-byte word; rade_batch_channel reads it by element: 8 bytes)
+ * Rows of these buffers are 320 (z) or 16 (G) bytes, so an aligned base aligns every stream.  Handled inside the kernel instead: rx_out_dev of the channel calls
+ * (k_chan_apply stores two samples as one 16-byte word where the stream's row allows it, else as two 8-byte words; any rx_stride, n_pre, n_total parity).
+ * Host arrays ([B] ints, floats, doubles, longs, status records) are read or written for exactly B entries.
+ * Per entry, buffer (element; stride) -- all natural alignment unless listed above:
+ *   rade_batch_tx / _tx_latents / _tx_eoo   features_dev, z_dev (float; dense) in; iq_out_dev (complex64; iq_stride >= 960 n_mf, 1152 for _tx_eoo), z_out_dev (float; dense, 16 B)
+ *   rade_batch_encode / _decode             features / z in (float; dense; _decode's z_dev 16 B); z_out_dev (16 B) / features_out_dev (float; dense)
+ *   rade_batch_channel(_streams)            tx_dev (complex64; tx_stride >= n_sig), G_dev [B][n_sig][2], noise_dev [B][n_total] (complex64; dense) in; rx_out_dev (complex64; rx_stride >= n_total)
+ *   rade_batch_tx_channel(_streams)         as the two above; iq_out_dev optional with G_dev (16 B)
+ *   rade_batch_channel_symbol               z_dev, H_dev, noise_dev in, z_hat_dev out (float; dense)
+ *   rade_batch_multipath_gen / _h           noise_low_dev, G_dev in (complex64; dense); G_out_dev (complex64 [B][n_out][2], n_out >= 1; one sample has no variance to
+ *                                           normalise by: n_out = 1 writes its two values, not finite), H_out_dev (float; dense)
+ *   rade_batch_rx                           rx_dev (complex64; rx_stride >= every n_avail) in; features_out_dev (float; feat_stride >= 432 or 240, capacity = the floor of
+ *                                           feat_stride / that), eoo_out_dev (float [B][180], written only for a stream with has_eoo)
+ *   rade_batch_rx_ideal                     rx_dev (complex64; rx_stride >= 960 n_mf, checked), z_ref_dev in; z_hat_dev (16 B with features_out_dev), features_out_dev (float; dense)
+ *   rade_batch_loss                         features_dev (float; f_stride >= n_in f_row), hat_dev (float; h_stride >= n_hat h_row) in; frame_loss_dev (float; fl_stride >= n_hat, checked)
+ *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
+ *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
+
 /* Arithmetic of the encoder depends on the SIZE of the call, in the last bits only: calls with more than 16384 rows (B x 3 n_mf) run the batched kernels on operand
  * fragments (rade_enc.hip), whose two conv taps alternate per k-block -- another summation order of the same float32 partial products than the float32-row kernels that
  * serve smaller calls ($RADE_ENCF_SEQ_TAPS restores the sequential order, $RADE_ENC_ROWS the row kernels for every size).  Both are inside every parity bar (latents

@@ -19,6 +19,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <stdint.h>
 #include <math.h>
 
 #include "rade_batch.h"
@@ -502,6 +503,10 @@ int rade_batch_profile_get(rade_batch *h, int cls, double *ms, double *work, lon
     return 0;
 }
 
+/* The caller's buffers that a kernel reads or writes as 16-byte words (include/rade_batch.h, "Buffers, strides and alignment"): refused on the host, before
+ * any launch, when they are not 16-byte aligned.  Every other caller buffer is accessed element by element. */
+static int misaligned16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+
 /* ---- one GEMM launch helper ------------------------------------------------------------------ */
 static int gemm(rade_batch *hh, const dev_lin *w, const float *a1, long a1_sb, long a1_st, int K1, const float *a0, long a0_sb, long a0_st, int K0,
                 const int *reset, const int *n_rows, float *y, long y_sb, long y_st, int B, int T, int act, void *stream)
@@ -628,7 +633,8 @@ static int modulate(rade_batch *h, const float *z, int n_mf, void *iq_out, long 
 int rade_batch_tx(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, float *z_out_dev, void *stream)
 {
     ON_DEV(h);
-    if (!h || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84) return -1;
+    if (!h || !features_dev || !iq_out_dev || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84) return -1;
+    if (misaligned16(z_out_dev)) return -1;           /* encf_emit (rade_enc.hip) stores the latents of a large call as f32x4 */
     float *z = z_out_dev ? z_out_dev : h->enc_z;
     int e = encode_features(h, features_dev, 3 * n_mf, z, stream);
     e |= modulate(h, z, n_mf, iq_out_dev, iq_stride, stream);
@@ -647,7 +653,8 @@ int rade_batch_tx_latents(rade_batch *h, const float *z_dev, int n_mf, void *iq_
 int rade_batch_encode(rade_batch *h, const float *features_dev, int n_steps, float *z_out_dev, void *stream)
 {
     ON_DEV(h);
-    if (!h || n_steps <= 0 || n_steps > h->Tcap || !z_out_dev) return -1;
+    if (!h || !features_dev || n_steps <= 0 || n_steps > h->Tcap || !z_out_dev) return -1;
+    if (misaligned16(z_out_dev)) return -1;           /* encf_emit (rade_enc.hip) stores the latents of a large call as f32x4 */
     int e = rd_launch_pad_rows(features_dev, h->enc_xin, (long)h->B * n_steps, h->feat_in, h->enc_kpad, stream);
     e |= encode_core(h, n_steps, z_out_dev, stream);
     return e ? -1 : n_steps;
@@ -663,6 +670,7 @@ int rade_batch_tx_set_eoo_bits(rade_batch *h, const float *bits_host)
 
 int rade_batch_tx_eoo(rade_batch *h, void *iq_out_dev, long iq_stride, void *stream)
 {
+    if (!h || !iq_out_dev) return -1;
     ON_DEV(h);
     if (h->tx_linear) return -1;           /* the end-of-over frame is built with the bottleneck-3 pilot gain and limiter */
     if (!h->tx_bpf) return rd_launch_copy_eoo(h->eoo, iq_out_dev, iq_stride, h->B, stream) ? -1 : RD_NEOO;
@@ -761,6 +769,7 @@ int rade_batch_tx_channel_streams(rade_batch *h, const float *features_dev, int 
 {
     ON_DEV(h);
     if (!h || !p || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84 || p->n_sig != n_mf * RD_NMF || !rx_out_dev || (h->tx_linear && p->with_eoo)) return -1;
+    if (!features_dev || misaligned16(p->G_dev)) return -1;      /* k_ofdm_mod_mp reads (G1[i], G2[i]) as one f32x4 */
     const float *ps_dev;                   /* (uploaded ahead of the transmit launches: its synchronisation waits only for what the stream held before this call) */
     if (chan_streams_upload(h, p, ps, stream, &ps_dev)) return -1;
     if (!p->G_dev || h->tx_bpf) {          /* (the Tx band-pass filter sits between the modulator and the channel: the two calls back to back) */
@@ -855,7 +864,8 @@ static void fill_dec_args(const rade_batch *h, rd_decs_args *d)
 int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *features_out_dev, int reset_state, void *stream)
 {
     ON_DEV(h);
-    if (!h || n_steps <= 0 || n_steps > h->Tcap || !features_out_dev) return -1;
+    if (!h || !z_dev || n_steps <= 0 || n_steps > h->Tcap || !features_out_dev) return -1;
+    if (misaligned16(z_dev)) return -1;               /* the GEMMs read their A rows as f32x4 (rade_kernels.hip), and dense1's rows are z_dev's */
     hipStream_t st = (hipStream_t)stream;
     if (reset_state) {
         hipMemsetAsync(h->dec2_h[0], 0, sizeof(float) * 5 * h->B * 96, st);
@@ -873,6 +883,7 @@ int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n
     ON_DEV(h);
     if (!h || !rx_dev || !p || !z_hat_dev || n_mf < 2 || rx_stride < (long)n_mf * RD_NMF || p->time_offset < -RD_NCP || p->time_offset > 0 ||
         p->eq < RADE_EQ_LS || p->eq > RADE_EQ_NONE || (features_out_dev && 3 * n_mf > h->Tcap) || (p->n_errors_host && !p->z_ref_dev)) return -1;
+    if (features_out_dev && misaligned16(z_hat_dev)) return -1;  /* the decoder then reads z_hat_dev as rade_batch_decode does: f32x4 A rows */
     const int B = h->B;
     hipStream_t st = (hipStream_t)stream;
     if (dev_grow(h, &h->irx_part, &h->irx_part_cap, n_mf, sizeof(double) * B, 1) || dev_grow(h, &h->irx_foff, NULL, 2 * B, sizeof(float), 1) || dev_grow(h, &h->irx_err, NULL, B, sizeof(long long), 1)) return -1;

@@ -620,3 +620,44 @@ def test_eoo_ber_tool(golden, tmp_path, capsys):
     assert wire.main(["eoo_ber", a, b]) == 0
     cap = capsys.readouterr()
     assert cap.out.count("frame received!") == 5 and "EOO frames  received: 5 n_ok_frames: 1" in cap.err and cap.err.strip().endswith("PASS")
+
+
+def test_band_checker_reports_every_planted_fault():
+    """tests/bands.py, the checker behind tests/test_buffer_contract_gpu.py: a clean write passes, and each kind of fault the GPU module looks for is
+    reported (so its assertions there are not vacuous).  Driven on numpy arrays; the torch path shares check()."""
+    import pytest
+    from bands import SENTINEL, Band
+    assert np.isnan(np.array([SENTINEL], np.int32).view(np.float32)[0])
+
+    def clean(written=(7, 7, 7), **kw):
+        bd = Band(3, 7, 11, 8, **kw)                              # complex64 rows of 7 at stride 11
+        vals = np.zeros((3, 7), np.complex64)
+        for b, n in enumerate(written):
+            vals[b, n:] = np.array([SENTINEL, SENTINEL], np.int32).view(np.complex64)[0]
+        return bd.fill(vals), list(written)
+    bd, wr = clean()
+    assert bd.front * 4 >= 4096 and bd.front >= 11 * 2 and bd.n_words - bd.front - 3 * 11 * 2 >= max(1024, 22)
+    bd.check(); bd.check(wr)
+    assert np.array_equal(bd.rows(np.complex64), np.zeros((3, 7), np.complex64))
+    for off in (0, 4, 8, 12):
+        assert Band(2, 5, 9, 4, base_offset_bytes=off).ptr % 16 == off
+    with pytest.raises(AssertionError, match="stream 1, word 14"):          # one word past a row
+        bd, wr = clean(); bd.words[bd.front + 11 * 2 + 14] = 0; bd.check()
+    with pytest.raises(AssertionError, match="1 words before row 0"):       # one word before row 0
+        bd, wr = clean(); bd.words[bd.front - 1] = 0; bd.check()
+    with pytest.raises(AssertionError, match="2 words written outside the rows, the first at stream 0, word 18"):     # into the gap between rows
+        bd, wr = clean(); bd.words[bd.front + 18:bd.front + 20] = 5; bd.check()
+    with pytest.raises(AssertionError, match="outside the rows"):           # behind the last row's stride
+        bd, wr = clean(); bd.words[bd.n_words - 1] = 0; bd.check()
+    with pytest.raises(AssertionError, match="stream 2: 1 words of the written extent .* never written, the first at word 13"):   # an unwritten last element (half of it)
+        bd, wr = clean(); bd.words[bd.front + 2 * 22 + 13] = SENTINEL; bd.check()
+    with pytest.raises(AssertionError, match="stream 1: 2 words written in the part documented as not written, the first at word 8"):
+        bd, wr = clean((7, 4, 0)); bd.words[bd.front + 22 + 8:bd.front + 22 + 10] = 0; bd.check(wr)
+    with pytest.raises(AssertionError, match="stream 2: .* documented as not written"):     # the whole row of a stream that is not scored
+        bd, wr = clean((7, 4, 0)); bd.words[bd.front + 44] = 0; bd.check(wr)
+    bd, wr = clean((7, 4, 0)); bd.check(wr)
+    with pytest.raises(AssertionError, match="never written"):              # ... and the documented extent itself must be written
+        bd.check([7, 5, 0])
+    with pytest.raises(AssertionError):
+        bd, wr = clean(); bd.untouched()
+    Band(3, 7, 11, 8).untouched()
