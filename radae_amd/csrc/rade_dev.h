@@ -216,7 +216,7 @@ int rd_multipath_gen_needs_scratch(int low_ratio, int n_out);
 int rd_launch_multipath_h(const void *G, int n_g, int M, int n_sym, int Nc, float dRs, int want_complex, float *H, int B, rd_stream_t s);
 
 /* CoreDecoderStatefull.forward (radae_base.py:388-430) for the pending rows of one stream, run inside the receiver
- * kernel by the stream's own workgroup (rx_decode_pending -> ds_layers): buffers and weights of that stage. */
+ * kernel by the stream's own workgroup (rx2_decode_pending -> dq2_layers): buffers and weights of that stage. */
 typedef struct { const float *wp, *bias; const unsigned short *wp16, *wa16; const float *wscale; int N, K; } rd_lin;
 /* wp16: rd_pack_weights_f16x2; wa16 (in-kernel decoder): rd_pack_weights_q16_a16 when wscale != NULL (int8-exact layer: one plane of
  * integers + per-column scales), else rd_pack_weights_f16x2_a16 (two planes) */
@@ -236,14 +236,14 @@ typedef struct {
 typedef struct {
     const rd_tables *tab; rd_rx_stream *st; rd_rx_round *round;
     const void *rx; long rx_stride; const int *avail;   /* [B] samples readable at rx + b*stride (raw input: the receiver only reads it to rebuild the filter memory) */
-    void *rxf; long rxf_stride;                          /* band-pass filtered samples of the invocation (k_rx_bpf), same indexing as rx */
+    void *rxf; long rxf_stride;                          /* band-pass filtered samples of the invocation (k_bpf_fir), same indexing as rx */
     const unsigned short *bpf16;                         /* rd_bpf16_table_fill(): [4][2][64][8] binary16, the band-pass taps as matrix-core A operands */
     const void *bpf_chain; int chain_stride;             /* [B][chain_stride] float2: (nin0, mem_len0) + the block phases of the pre-pass */
     int *acc;                                            /* [B][4] this invocation: consumed, calls, valid, eoo */
     int max_calls;                                       /* call budget per stream per invocation */
     int unsync_off_after;                                /* radae_rxe.py:277-281: synced_count beyond which the unsync paths are disabled; < 0 = never */
     int round_calls, dec_rows;                           /* R calls per stream per launch (<= RD_RX_ROUND_MAX), 3R decoder slots */
-    rd_decs_args dec;                                    /* the decoder runs inside the stream's workgroup (rx_decode_pending) */
+    rd_decs_args dec;                                    /* the decoder runs inside the stream's workgroup (rx2_decode_pending) */
     float *features_out; long feat_stride;               /* [B][cap][432] */
     int feat_cap;                                        /* valid modem frames features_out holds per stream: a stream stops making calls once it has produced that many */
     int bypass_dec;                                      /* radae_rxe.py --bypass_dec (:300-302, :315): rows of features_out are the 240 latents of a valid modem frame, no decoder, no UW accounting */

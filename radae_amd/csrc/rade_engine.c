@@ -316,7 +316,7 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     h->corrq16 = upload_table16(h, tab, rd_corrq16_table_fill, RD_CORRQ16_HALFS);
     h->corra16 = upload_table16(h, tab, rd_corra16_table_fill, RD_CORRA16_HALFS);
     h->wfwd16 = upload_table16(h, tab, rd_wfwd16_table_fill, RD_WFWD16_HALFS);    /* the demodulator DFT matrix as matrix-core operands (k_rx_sync2) */
-    h->bpf16 = upload_table16(h, tab, rd_bpf16_table_fill, RD_BPF16_HALFS);       /* the band-pass taps as matrix-core operands (k_rx_bpf) */
+    h->bpf16 = upload_table16(h, tab, rd_bpf16_table_fill, RD_BPF16_HALFS);       /* the band-pass taps as matrix-core operands (k_bpf_fir) */
     free(tab);
     {   /* ((n - 79.5) / 80)^m, m = 0..7, by repeated multiplication (the order the kernels build their LDS copy in) */
         double vm[8][RD_M];
@@ -845,7 +845,7 @@ static int decoder_layers(rade_batch *h, const float *z, int T, int Tio, int Tca
     return e;
 }
 
-/* pointers of the receiver's in-kernel decoder stage (rx_decode_pending -> ds_layers) */
+/* pointers of the receiver's in-kernel decoder stage (rx2_decode_pending -> dq2_layers) */
 static void fill_dec_args(const rade_batch *h, rd_decs_args *d)
 {
     memset(d, 0, sizeof *d);
@@ -1006,7 +1006,7 @@ int rade_batch_rx(rade_batch *h, const void *rx_dev, long rx_stride, const int *
     const int B = h->B;
     hipStream_t st = (hipStream_t)stream;
     int *hs = h->h_small;
-    /* complex_bpf.bpf for every sample of this invocation, ahead of the receiver launches (rade_rx.hip: k_rx_bpf).  The buffers follow the
+    /* complex_bpf.bpf for every sample of this invocation, ahead of the receiver launches (rade_rx.hip: k_bpf_chain + k_bpf_fir).  The buffers follow the
      * largest invocation seen (a few times the input: 8 bytes per sample and stream); growing them waits for the device. */
     int max_avail = 0;
     for (int b = 0; b < B; b++) if (n_avail_host[b] > max_avail) max_avail = n_avail_host[b];

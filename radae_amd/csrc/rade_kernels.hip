@@ -1,22 +1,22 @@
 // rade_kernels.hip -- gfx950 (MI355X) kernels of the RADE hot path + the C launch shims.
 //
 // Kernel inventory (reference op each one replaces):
-//   k_gemm<NT>      f32 MFMA (v_mfma_f32_32x32x2_f32) skinny-N GEMM with fused bias/tanh/GLU epilogue:
-//                   every Linear / GRU-input / Conv1d(k=2) / GLU layer of CoreEncoder / CoreDecoder,
-//                   evaluated for all streams and all time steps of a chunk at once
+//   k_gemm<NT>      f32 MFMA (v_mfma_f32_32x32x2_f32) skinny-N GEMM with fused bias/tanh/GLU epilogue: every Linear / GRU-input /
+//                   Conv1d(k=2) / GLU layer of CoreEncoder / CoreDecoder, for all streams and all time steps of a chunk at once
 //                   (radae_base.py:260-286, :400-416; src/rade_enc.c:55-114; src/rade_dec.c:50-102)
+//   k_gemm16 / k_gemm16p / k_gemm_splitk   the same GEMM on the f16 matrix cores (two binary16 planes), pipelined, and split over K for few rows
 //   k_gru_scan<H>   the serial part of a GRU layer: h_t = f(gi_t, W_hh h_{t-1}); one workgroup per
 //                   stream, W_hh rows held in VGPRs, h in LDS (radae_base.py:97-108)
 //   k_enc_pack      12x36 feature frames -> 3x(4x21) encoder input rows, aux symbol -1 (radae_txe.py:114-121)
-//   k_ofdm_mod      QPSK map, pilot row, 30->160 IDFT, cyclic prefix, tanh PA limiter (dsp.py:340-378)
-//   k_eoo_build     end-of-over frame with 180 data bits (radae.py:208-219, :441-455)
-//   k_chan_power / k_chan_apply   rate-Fs two-path multipath, power normalisation, freq offset, AWGN,
+//   k_pad_rows / k_carry_rows   zero-padding of GEMM inputs to K % 8 == 0; the conv history rows carried to the next chunk
+//   k_ofdm_mod      QPSK map, pilot row, 30->160 IDFT, cyclic prefix, tanh PA limiter (dsp.py:340-378); k_ofdm_mod_mp: with the
+//                   two-path multipath model and the power sums of the channel folded in
+//   k_eoo_build / k_copy_eoo   end-of-over frame with 180 data bits (radae.py:208-219, :441-455)
+//   k_chan_power / k_chan_gain / k_chan_apply   rate-Fs two-path multipath, power normalisation, freq offset, AWGN,
 //                   EOO / noise framing (radae.py:529-589, inference.py:263-284)
-//   k_rx_sync       one workgroup per stream runs do_radae_rx (radae_rxe.py:171-330): BPF (dsp.py:63-102),
-//                   detect_pilots / refine / check_pilots (dsp.py:178-320), sync state machine, frequency
-//                   correction, OFDM demod + 3-pilot LS EQ (dsp.py:418-526)
-//   k_rx_post       decoder output -> 36-float feature frames, aux-bit (UW) error accounting
-//                   (rade_api.c:480-513, radae_rxe.py:300-319)
+//   k_multipath_gen / k_multipath_h   Watterson Doppler-spread samples and the rate-Rs channel matrix (doppler_spread.m, multipath_samples.m)
+//   k_chan_symbol   symbol-domain channels of the non-OFDM configurations (radae.py:604-634, bbfm.py:157-197)
+// The receiver (k_rx_sync2, band-pass pre-pass, k_batch_reset) is rade_rx.hip; the batched encoder rade_enc.hip; single-stream steps rade_core_step.hip.
 //
 // Written for gfx950 only: 64-lane wavefronts, MFMA f32 32x32x2, LDS-resident per-stream working sets.
 #include "rade_devutil.h"

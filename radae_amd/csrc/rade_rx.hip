@@ -1,44 +1,19 @@
 // rade_rx.hip -- THE receiver of the RADE hot path: do_radae_rx (radae_rxe.py:171-330) for one stream per workgroup, all of its calls in one launch.
 //
-//   k_rx_bpf      complex_bpf.bpf (dsp.py:63-102) for every sample of a rade_batch_rx invocation, ahead of the receiver kernel (round 4: the
-//                 band-pass filter does not depend on any sync decision, so it left the per-stream serial chain)
+//   k_bpf_chain / k_bpf_fir / k_bpf_advance   complex_bpf.bpf (dsp.py:63-102) for every sample of a rade_batch_rx invocation, ahead of the receiver kernel
+//                 (round 4: the band-pass filter does not depend on any sync decision, so it left the per-stream serial chain)
 //   k_rx_sync2    acquisition (detect_pilots / refine / check_pilots, dsp.py:178-320), sync state machine, frequency correction, OFDM demod +
 //                 3-pilot LS EQ (dsp.py:418-526), the CoreDecoder stage (radae_base.py:358-430) and UW accounting (rade_api.c:480-513): 256 threads
 //                 and at most 80 KB of LDS per stream, so that two streams share a CU
 //   k_batch_reset radae_rxe.py:128-142 (and the encoder / decoder start-of-utterance state, one launch)
 //
-// Rounds 2-3 carried a second receiver kernel (k_rx_sync: 512 threads, one stream per CU) that this one was forked from; it is gone: one
-// receiver, every fix lands once.
+// ONE translation unit, one file per stage, included below in the order the stages need each other: rade_rx_dec.h (decoder stage), rade_rx_search.h (pilot
+// search, workgroup reductions), rade_rx_refine.h, rade_rx_check.h, rade_bpf.h (band-pass arithmetic).  This file keeps the per-stream state (RxScalars,
+// RxShared2), the developer switches, the decoder hand-over, the kernels and their launch shims.  The band-pass kernels stay in this unit: in a unit of
+// their own they compile to the same code, but k_rx_sync2, left as the only caller of the shared band-pass functions here, does not (tools/codegen_diff.py).
+// Rounds 2-3 carried a second receiver kernel (512 threads, one stream per CU) that this one was forked from; it is gone: one receiver, every fix lands once.
 #include "rade_devutil.h"
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// ---- decoder stage inside the receiver: LDS layout helpers and product descriptors ----
-#define DQ_XB 96                 // 8-half blocks per x row
-#define DQ_HB 16                 // blocks per GRU-output row (12 used)
-#define DQ_PEND_MAX 64           // pending rows a stream can hold (engine: dec_rows <= 63)
-// floats per row of the GRU-input sums in LDS: 288 + 4.  With 288 (= 9 x 32) every row started on the same bank, and the 16-byte accesses of a product's epilogue -- lanes = rows --
-// were 8-way conflicts: two thirds of ALL bank-conflict cycles of the kernel (tools/rx2_lds_conflicts.sh, round 5); with 292 a row starts 16 bytes further on.
-#ifndef DQ_GIS
-#define DQ_GIS 292
-#endif
-// half index of x[logical row t][col] inside a plane; the history row is logical -1 (swizzle key 15), the zero row needs no key
-__device__ __forceinline__ int dq_xoff(int t, int col) { return (t + 1) * (DQ_XB * 8) + ((((col >> 3) ^ (t & 15)) << 3) | (col & 7)); }
-__device__ __forceinline__ int dq_hoff(int t, int col) { return t * (DQ_HB * 8) + ((((col >> 3) ^ (t & 15)) << 3) | (col & 7)); }
-// v in [-1, 1] -> the two planes of 2^8 v
-__device__ __forceinline__ void dq_split(float v, _Float16 &hi, _Float16 &lo) { const float x = 256.0f * v; hi = (_Float16)x; lo = (_Float16)(x - (float)hi); }
-
-enum { DQ_OUT_X = 0, DQ_OUT_GI = 1, DQ_OUT_GLOBAL = 2 };
-struct DqGemm {
-    const unsigned short *wa; int nct;     // rd_pack_weights_f16x2_a16: [K/32][nct][2 planes][64 lanes][8]
-    const float *bias; int N;              // bias may be null; N = valid output columns
-    const float *wscale;                   // non-null: int8-exact layer, ONE plane of integers, wscale[n] = the column's scale; null: two planes of 2^10 w
-    int from_hb;                           // B operand: 0 = the x planes, 1 = the GRU-output planes
-    int ktap;                              // k-steps [0, ktap) read the PREVIOUS row (conv tap 0), the rest the row itself
-    int ks0, nks;                          // k-steps of the weight's K axis this product covers
-    int init_gi;                           // accumulators start from gi[t][n] (fix-up products) instead of zero
-    int out, ocol, act;                    // DQ_OUT_*; first x column (DQ_OUT_X); act 0 none, 1 tanh+clamp, 2 GLU
-    float *gout; int gstride;              // DQ_OUT_GLOBAL
-};
 
 enum { ST_SEARCH = 0, ST_CANDIDATE = 1, ST_SYNC = 2 };
 struct RxScalars {
@@ -47,7 +22,7 @@ struct RxScalars {
     unsigned rxmax_cur, rxmax_h0, rxmax_h1;   // float bits of max |re|,|im| of the filtered samples of this call / the two calls before (check_pilots operand scale)
     int consumed_inv, calls_inv, valid_inv, eoo_inv, n_calls, n_rows, uw_from_row, consumed_round, pending_valid, out_base;
     int tab_ok;               // refine()'s per-frequency constants for the CURRENT fmax are in LDS (left by the previous synchronised call's idle wavefront)
-    int bpf_grid, nin0;       // the stream's calls still follow the block grid of the invocation's band-pass pre-pass (k_rx_bpf); the grid's first block length
+    int bpf_grid, nin0;       // the stream's calls still follow the block grid of the invocation's band-pass pre-pass (k_bpf_fir); the grid's first block length
     int entry;                // this candidate call enters sync (decided by thread 0 before a barrier: see do_entry)
     int go, need_decode, batch_call0, state_before, nin_before, valid_output, endofover, uw_fail, candidate, dt_valid, dt_new, lds_sync;
     float snr_est, mag; float2 bpf_phase;
@@ -55,20 +30,17 @@ struct RxScalars {
     double rph_th;                        // k_rx_sync2: the phase accumulator as an angle in [-pi, pi] (rph_r + j rph_i = e^{j rph_th})
 };
 
-__device__ __forceinline__ float sigma_r_from_sums(double t1, double t2)
-{   // dsp.py:218-220: (mean|Dt1| + mean|Dt2|)/sqrt(pi/2)/2 in float32
-    const float k = (float)sqrt(PI_D / 2.0);
-    const float m1 = (float)(t1 / (RD_NMF * RD_NFC)) / k, m2 = (float)(t2 / (RD_NMF * RD_NFC)) / k;
-    return (m1 + m2) / 2.0f;
-}
-
 __device__ static constexpr uint32_t LCG_A[48] = { 1664525u, 389569705u, 2940799637u, 158984081u, 2862450781u, 3211393721u, 1851289957u, 3934847009u, 2184914861u, 246739401u, 1948736821u, 2941245873u, 4195587069u, 4088025561u, 980655621u, 2001863745u, 657792333u, 65284841u, 1282409429u, 3808694225u, 2968195997u, 2417331449u, 2878627493u, 307989601u, 504219373u, 1897564169u, 2574089845u, 3294562801u, 3478292285u, 2651335705u, 2523738949u, 666245249u, 4137395341u, 2604435753u, 1706708245u, 3963176977u, 3678957277u, 3530469177u, 3858799589u, 629287073u, 3146069549u, 3820924489u, 2403397557u, 2390444593u, 2593868413u, 4291139161u, 1705056389u, 3186638017u };
 __device__ static constexpr uint32_t LCG_C[48] = { 1013904223u, 1196435762u, 3519870697u, 2868466484u, 1649599747u, 2670642822u, 1476291629u, 2748932008u, 2180890343u, 2498801434u, 3421909937u, 3167820124u, 2636375307u, 3801544430u, 28987765u, 2210837584u, 3039689583u, 1338634754u, 1649346937u, 2768872580u, 2254235155u, 2326606934u, 1719328701u, 1061592568u, 53332215u, 1140036074u, 4224358465u, 2629538988u, 1946028059u, 573775550u, 1473591045u, 95141024u, 1592739711u, 1618554578u, 4257218569u, 2685635028u, 2617994019u, 740185638u, 4194465613u, 2426187848u, 967350023u, 366635194u, 2557108433u, 3503432700u, 353185579u, 706247310u, 408928405u, 1855199472u };
 
 #define NT2 256
+#define NW2 (NT2 / 64)
 // thread index rebuilt from the lane counter and the wavefront's index (held in a scalar register): three instructions wherever it
 // is needed, instead of one value that stays live -- and gets spilled -- across the whole receive call (rx_tid() keeps threadIdx.x
-// alive the same way)
+// alive the same way).  RX2_SYNC: a barrier of k_rx_sync2's call loop with `tid` rebuilt behind it, so that no live range of it crosses a barrier
+__device__ __forceinline__ int rx2_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ int rx2_tid(int wv) { int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(l)); return (wv << 6) | l; }
+#define RX2_SYNC() do { __syncthreads(); tid = rx2_tid(wv); } while (0)
 // developer aid (-DRX2_CENSUS, tools/rx2_census.sh): a.variant >> 8 is a mask that skips the decoder stage / its recurrence or runs an idempotent
 // phase twice, so that the per-phase share of the instruction counters (rocprofv3 --pmc SQ_INSTS_*) is the difference between two runs
 #ifdef RX2_CENSUS
@@ -78,9 +50,6 @@ __device__ static constexpr uint32_t LCG_C[48] = { 1013904223u, 1196435762u, 351
 #define CENSUS(bit) 0
 #define CENSUS_REPS(bit) 1
 #endif
-__device__ __forceinline__ int rx2_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-__device__ __forceinline__ int rx2_tid(int wv) { int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(l)); return (wv << 6) | l; }
-#define NW2 (NT2 / 64)
 #ifdef RD_PHASE_TIMING   // developer aid: per-phase shader-clock totals of workgroup 0 (tools/ab_build.sh timing -DRD_PHASE_TIMING; tools/phase_timing2.py)
 __device__ long long g_phase_cycles2[32];
 #define PH2_T0() long long ph2_t_ = clock64()
@@ -92,426 +61,12 @@ extern "C" void rd_debug_phase_cycles2(long long *out) { hipMemcpyFromSymbol(out
 #define PH2(i) do { } while (0)
 #define PH2_RESTART() do { } while (0)
 #endif
-#define DQ2_ROWS 12
-#ifndef RX2_DQ_D3
-#define RX2_DQ_D3 4
-#endif
+#include "rade_rx_dec.h"
 
-struct DecShared2 {
-    __attribute__((aligned(16))) _Float16 xh[DQ2_ROWS + 2][DQ_XB * 8];   // physical row 0: conv history, 1..12: the chunk, 13: zeros
-    __attribute__((aligned(16))) _Float16 xl[DQ2_ROWS + 2][DQ_XB * 8];
-    __attribute__((aligned(16))) float gi[DQ2_ROWS][DQ_GIS];
-    __attribute__((aligned(16))) _Float16 hbh[DQ2_ROWS][DQ_HB * 8], hbl[DQ2_ROWS][DQ_HB * 8];
-    __attribute__((aligned(16))) float hs[2][96];
-    int rst[DQ_PEND_MAX];
-    int err[DQ_PEND_MAX];
-};
-
-// NT adjacent column tiles of a product for rows [0, Tb), Tb <= 12: ONE 16-row tile (k_rx_sync's version carries two).
-// sync_first: the barrier that separates this product from the phase before it is taken HERE, behind the first weight requests (which depend on nothing the phase before
-// wrote): the round trip to L2 (~800 cycles, once per phase: five phases per layer and chunk) runs while the workgroup's other wavefronts arrive, instead of after them
-template <int NT, bool SINGLE>
-__device__ __forceinline__ void dq2_gemm_tiles_(DecShared2 *sh_, const DqGemm g_, int ct_, int Tb_, unsigned rstmask_, int sync_first)
-{
-    constexpr int D = NT == 1 ? 12 : ((NT == 3 && SINGLE) ? RX2_DQ_D3 : 4);   // k-steps of weights in flight (one plane of a three-tile product: 48 registers at 4, 96 at 8)
-    const int ct = uni(ct_), Tb = uni(Tb_); const unsigned rstmask = (unsigned)uni((int)rstmask_);
-    const int nct = uni(g_.nct), N = uni(g_.N), from_hb = uni(g_.from_hb), ktap = uni(g_.ktap), ks0 = uni(g_.ks0), nks = uni(g_.nks), init_gi = uni(g_.init_gi),
-              outk = uni(g_.out), ocol = uni(g_.ocol), act = uni(g_.act), gstride = uni(g_.gstride);
-    DecShared2 *sh = uni_ptr(sh_);
-    glb_u16 *wbase = (glb_u16 *)uni_ptr(g_.wa); glb_cf32 *biasp = (glb_cf32 *)uni_ptr(g_.bias); glb_f32 *gout = (glb_f32 *)uni_ptr(g_.gout);
-    glb_cf32 *wscale = (glb_cf32 *)uni_ptr(g_.wscale);
-    constexpr bool single = SINGLE;
-    const int lane = threadIdx.x & 63, t = lane & 15, gq = lane >> 4;
-    const int r0 = min(t, Tb - 1);                                     // rows beyond Tb repeat the last one (results dropped)
-    const lds_half *bh = (const lds_half *)(from_hb ? &sh->hbh[0][0] : &sh->xh[0][0]), *bl = (const lds_half *)(from_hb ? &sh->hbl[0][0] : &sh->xl[0][0]);
-    const int stride = from_hb ? DQ_HB * 8 : DQ_XB * 8;
-    const int p1a = (from_hb ? r0 : r0 + 1) * stride, k1a = r0 & 15;
-    const int p0a = ((rstmask >> r0) & 1u) ? (DQ2_ROWS + 1) * stride : r0 * stride;
-    const int k0a = (r0 - 1) & 15;
-    const int planes = single ? 1 : 2;
-    glb_u16 *wa = wbase + (((size_t)ks0 * nct + ct) * planes * 64 + lane) * 8;
-    const size_t wstep = (size_t)nct * planes * 64 * 8, tstep = (size_t)planes * 64 * 8;
-    lds_f32 *gi = (lds_f32 *)&sh->gi[0][0];
-    f32x4 acc0[NT];
-#pragma unroll
-    for (int i = 0; i < NT; i++) acc0[i] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f };
-    const int n0 = 16 * ct + 4 * gq;
-    typedef const __attribute__((address_space(1))) f16x8 glb_f16x8;
-    typedef const __attribute__((address_space(3))) f16x8 lds_f16x8;
-    f16x8 wh[D][NT], wl[D][NT];
-    auto fetch = [&](int d, int ks) {
-        const int kq = min(ks, nks - 1);
-#pragma unroll
-        for (int i = 0; i < NT; i++) {
-            wh[d][i] = *(glb_f16x8 *)(wa + kq * wstep + i * tstep);
-            if (!single) wl[d][i] = *(glb_f16x8 *)(wa + kq * wstep + i * tstep + 64 * 8);
-        }
-    };
-#pragma unroll
-    for (int d = 0; d < D; d++) fetch(d, d);
-    if (sync_first) __syncthreads();
-    f16x8 nha, nla;
-    auto rows = [&](int kidx) {
-        const int kk = ks0 + min(kidx, nks - 1);
-        const bool tap0 = kk < ktap;
-        const int cb = 4 * (tap0 ? kk : kk - ktap) + gq;
-        const int oa = (tap0 ? p0a : p1a) + ((cb ^ (tap0 ? k0a : k1a)) << 3);
-        nha = *(lds_f16x8 *)(bh + oa); nla = *(lds_f16x8 *)(bl + oa);
-    };
-    rows(0);
-    auto step = [&](int d, int kidx, bool refill) {
-        const f16x8 xha = nha, xla = nla;
-        rows(kidx + 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < NT; i++) {
-            if (!single) acc0[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[d][i], xha, acc0[i], 0, 0, 0);
-            acc0[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[d][i], xla, acc0[i], 0, 0, 0);
-            acc0[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[d][i], xha, acc0[i], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (refill) fetch(d, kidx + D);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    int ks = 0;
-#pragma unroll 1
-    for (; ks + D <= nks; ks += D) {
-#pragma unroll
-        for (int d = 0; d < D; d++) step(d, ks + d, true);
-    }
-    // bias and row scales are requested here, under the last k-steps: held from the top of the function they cost up to 48 registers
-    // across the K loop, and came back from scratch one s_waitcnt vmcnt(0) at a time in the epilogue
-    f32x4 bias[NT], scl[NT];
-#pragma unroll
-    for (int i = 0; i < NT; i++) {
-        bias[i] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; scl[i] = (f32x4){ 0x1p-18f, 0x1p-18f, 0x1p-18f, 0x1p-18f };
-        if (biasp && !init_gi) {        // (N is a multiple of 4 in every layer: one 16-byte load from a clamped address instead of four guarded dwords)
-            const int nn = n0 + 16 * i;
-            bias[i] = *(const __attribute__((address_space(1))) f32x4 *)(biasp + min(nn, N - 4));
-            if (nn >= N) bias[i] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f };
-        }
-        if (single) scl[i] = *(const __attribute__((address_space(1))) f32x4 *)(wscale + n0 + 16 * i) * 0x1p-8f;
-    }
-#pragma unroll
-    for (int d = 0; d < D; d++) if (ks + d < nks) step(d, ks + d, false);
-    lds_half *xh = (lds_half *)&sh->xh[0][0], *xl = (lds_half *)&sh->xl[0][0];
-    const lds_half *hbh = (const lds_half *)&sh->hbh[0][0], *hbl = (const lds_half *)&sh->hbl[0][0];
-    typedef __attribute__((address_space(3))) f16x4 lds_f16x4;
-    if (t < Tb) {
-#pragma unroll
-        for (int i = 0; i < NT; i++) {
-            const int n = n0 + 16 * i, tt = t;
-            f32x4 v = acc0[i] * scl[i] + bias[i];
-            if (init_gi) v += *(const __attribute__((address_space(3))) f32x4 *)(gi + tt * DQ_GIS + n);
-            if (outk == DQ_OUT_GI) { *(__attribute__((address_space(3))) f32x4 *)(gi + tt * DQ_GIS + n) = v; continue; }
-            if (outk == DQ_OUT_GLOBAL) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) if (n + r < N) gout[(size_t)tt * gstride + n + r] = v[r];
-                continue;
-            }
-            if (act == 2) {
-                const f16x4 hh = *(const lds_f16x4 *)(hbh + dq_hoff(tt, n)), hl = *(const lds_f16x4 *)(hbl + dq_hoff(tt, n));
-#pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = clamp1(((float)hh[r] + (float)hl[r]) * 0x1p-8f * gate_sigmoid(v[r]));
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = clamp1(gate_tanh(v[r]));
-            }
-            f16x4 oh, ol;
-#pragma unroll
-            for (int r = 0; r < 4; r++) { _Float16 a, b; dq_split(v[r], a, b); oh[r] = a; ol[r] = b; }
-            *(lds_f16x4 *)(xh + dq_xoff(tt, ocol + n)) = oh; *(lds_f16x4 *)(xl + dq_xoff(tt, ocol + n)) = ol;
-        }
-    }
-}
-template <int NT>
-__device__ __forceinline__ void dq2_gemm_tiles(DecShared2 *sh, const DqGemm g, int ct, int Tb, unsigned rstmask, int sync_first)
-{
-    if (uni_ptr(g.wscale) != nullptr) dq2_gemm_tiles_<NT, true>(sh, g, ct, Tb, rstmask, sync_first);
-    else dq2_gemm_tiles_<NT, false>(sh, g, ct, Tb, rstmask, sync_first);
-}
-
-// dense1 on the f32 matrix cores (see dq_dense1): three wavefronts, 32 columns each
-__device__ void dq2_dense1(DecShared2 *sh, const float *z, const rd_lin w, int Tb)
-{
-    constexpr int NKB = RD_LATENT / 8;
-    const int lane = threadIdx.x & 63, nt = threadIdx.x >> 6, half = lane >> 5;
-    if (nt >= 3) return;
-    const float *wp = w.wp + ((size_t)nt * 64 + lane) * 4;
-    const size_t wstep = (size_t)3 * 256;
-    const int col = nt * 32 + (lane & 31);
-    const float bias = w.bias[col];
-    const int t = min(lane & 31, Tb - 1);
-    const float *p1 = z + (size_t)t * RD_LATENT + 4 * half;
-    f32x4 av[NKB], bv[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; kb++) { av[kb] = *(const f32x4 *)(p1 + kb * 8); bv[kb] = *(const f32x4 *)(wp + kb * wstep); }
-    f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; j++) acc[j] = 0.0f;
-#pragma unroll
-    for (int kb = 0; kb < NKB; kb++)
-#pragma unroll
-        for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kb][s], bv[kb][s], acc, 0, 0, 0);
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int tt = (j & 3) + 8 * (j >> 2) + 4 * half;
-        if (tt >= Tb) continue;
-        _Float16 a, b; dq_split(clamp1(gate_tanh(acc[j] + bias)), a, b);
-        sh->xh[0][dq_xoff(tt, col)] = a; sh->xl[0][dq_xoff(tt, col)] = b;
-    }
-}
-
-// two plain FMAs (see the FIR in k_rx_sync2 for why this kernel avoids v_pk_fma_f32)
-__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return (f32x2){ fmaf(a[0], b[0], c[0]), fmaf(a[1], b[1], c[1]) }; }
-// GRU recurrence over Tb steps: TWO lanes per hidden unit (192 threads; the fourth wavefront only keeps the barriers)
-__device__ void dq2_scan(DecShared2 *sh, const float *Whh, const float *bhh, float *hstate, int Tb, unsigned rstmask)
-{
-    constexpr int H = 96, KP = H / 2;
-    const int tid = rx_tid();
-    const bool on = tid < 2 * H;
-    const int j = on ? tid >> 1 : 0, p = tid & 1;
-    f32x2 wr[KP / 2], wz[KP / 2], wn[KP / 2];
-    {
-        const float *w0 = Whh + (size_t)j * H + p * KP;
-#pragma unroll
-        for (int k = 0; k < KP; k += 4) {
-            const f32x4 v0 = *(const f32x4 *)(w0 + k), v1 = *(const f32x4 *)(w0 + (size_t)H * H + k), v2 = *(const f32x4 *)(w0 + (size_t)2 * H * H + k);
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                wr[k / 2 + u] = (f32x2){ v0[2 * u], v0[2 * u + 1] }; wz[k / 2 + u] = (f32x2){ v1[2 * u], v1[2 * u + 1] }; wn[k / 2 + u] = (f32x2){ v2[2 * u], v2[2 * u + 1] };
-            }
-        }
-    }
-    const float br = bhh[j], bz = bhh[H + j], bn = bhh[2 * H + j];
-    float hj = hstate[j];
-    __syncthreads();                                   // (the barrier behind the input projection / fix-up that wrote gi: taken behind this function's global loads)
-    if (on && p == 0) sh->hs[0][j] = hj;
-    const float *gi = &sh->gi[0][0] + j;
-    float g0r = gi[0], g0z = gi[H], g0n = gi[2 * H];
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < Tb; t++) {
-        if ((rstmask >> t) & 1u) {                     // uniform over the workgroup
-            hj = 0.0f;
-            __syncthreads();
-            if (on && p == 0) sh->hs[cur][j] = 0.0f;
-            __syncthreads();
-        }
-        const float *gn_ = gi + (size_t)min(t + 1, Tb - 1) * DQ_GIS;
-        const float g1r = gn_[0], g1z = gn_[H], g1n = gn_[2 * H];          // next step's inputs: their LDS latency hides under this step
-        f32x2 ar = { 0.0f, 0.0f }, az = { 0.0f, 0.0f }, an = { 0.0f, 0.0f }, ar2 = { 0.0f, 0.0f }, az2 = { 0.0f, 0.0f }, an2 = { 0.0f, 0.0f };
-        const float *hp = sh->hs[cur] + p * KP;
-#pragma unroll
-        for (int k = 0; k < KP; k += 8) {
-            const f32x4 hv = *(const f32x4 *)(hp + k), hw = *(const f32x4 *)(hp + k + 4);
-            const f32x2 h0 = { hv[0], hv[1] }, h1 = { hv[2], hv[3] }, h2 = { hw[0], hw[1] }, h3 = { hw[2], hw[3] };
-            ar = fma2(wr[k / 2], h0, ar); az = fma2(wz[k / 2], h0, az); an = fma2(wn[k / 2], h0, an);
-            ar2 = fma2(wr[k / 2 + 1], h1, ar2); az2 = fma2(wz[k / 2 + 1], h1, az2); an2 = fma2(wn[k / 2 + 1], h1, an2);
-            ar = fma2(wr[k / 2 + 2], h2, ar); az = fma2(wz[k / 2 + 2], h2, az); an = fma2(wn[k / 2 + 2], h2, an);
-            ar2 = fma2(wr[k / 2 + 3], h3, ar2); az2 = fma2(wz[k / 2 + 3], h3, az2); an2 = fma2(wn[k / 2 + 3], h3, an2);
-        }
-        ar += ar2; az += az2; an += an2;
-        float sr = ar[0] + ar[1], sz = az[0] + az[1], sn = an[0] + an[1];
-        sr += quad_dpp<QUAD_XOR1>(sr); sz += quad_dpp<QUAD_XOR1>(sz); sn += quad_dpp<QUAD_XOR1>(sn);
-        const float r = gate_sigmoid((sr + br) + g0r);
-        const float z = gate_sigmoid((sz + bz) + g0z);
-        const float n = gate_tanh(g0n + (sn + bn) * r);
-        hj = (hj - n) * z + n;
-        if (on && p == 0) {
-            sh->hs[cur ^ 1][j] = hj;
-            _Float16 a, b; dq_split(clamp1(hj), a, b);
-            sh->hbh[0][dq_hoff(t, j)] = a; sh->hbl[0][dq_hoff(t, j)] = b;
-        }
-        g0r = g1r; g0z = g1z; g0n = g1n;
-        cur ^= 1;
-        if (t + 1 < Tb) __syncthreads();               // (the last step's barrier is the consumer's: dq2_gemm_tiles(..., sync_first))
-    }
-    if (on && p == 0) hstate[j] = hj;
-}
-
-// The recurrence with W_hh h on the matrix cores.  Beside another stream's workgroup on the same CU the vector ALU is what the two compete
-// for, and dq2_scan spends 432 vector FMAs per step and hidden unit row on a product the matrix pipe does in a few instructions: W_hh is
-// int8 in the blob, its integers sit in registers as A-operand fragments of v_mfma_f32_16x16x32_f16 (exact in binary16, row scales
-// applied afterwards); h_{t-1} is the B operand, read from LDS as two binary16 planes (2^8 h = hi + lo): EVEN columns of B carry the
-// high plane, ODD columns the low plane, so one instruction per (gate tile, k-step) yields both partial products and a DPP add of
-// neighbouring lanes (quad_perm [1,0,3,2]) joins them -- 9 instructions per block of 16 hidden units instead of 18.  A wavefront
-// owns "unit blocks": the three tiles r / z / n of its units, so the gates are evaluated in registers by the lanes that hold them
-// (lane column c < 4 finalises row c of its lane group).  Four wavefronts: blocks {0,1} {2,3} {4} {5}; the two-block wavefronts issue
-// both blocks' matrix instructions first and then evaluate both blocks' gates in one straight-line region (two independent chains).
-// (In k_rx_sync, alone on its CU, the matrix form was no faster -- the step there is latency, not ALU -- and was not kept.)
-template <int NB>
-__device__ __forceinline__ void dq2_scan_mfma_body(DecShared2 *sh, const unsigned short *whq, const float *whs, const float *bhh, float *hstate, int Tb, unsigned rstmask, int ub0)
-{
-    constexpr int H = 96;
-    const int tid = rx_tid(), lane = tid & 63, c = lane & 15, g = lane >> 4, cs = c & 3, par = c & 1;
-    // every column of a tile's C holds the same sums once neighbouring lanes are added (the planes sit in even / odd columns), so in a two-block wavefront the lanes of
-    // columns 8..15 take block 1 and those of columns 0..7 block 0: ONE pass over the gates (two sigmoids and a tanh: six transcendental instructions and their
-    // latencies, the longest dependent chain of the step) serves both blocks instead of one pass per block
-    const int blk = NB == 2 ? (c >> 3) & 1 : 0;
-    typedef const __attribute__((address_space(1))) f16x8 glb_f16x8_t;
-    f16x8 A[NB][3][3];
-    float sc[3], bb[3];
-    const bool finl = (c & 4) == 0 && (NB == 2 || c < 4);      // the lanes that publish: columns 0..3 (block 0) and, with two blocks, 8..11 (block 1)
-    const int ju = 16 * (ub0 + blk) + 4 * g + cs;
-#pragma unroll
-    for (int k = 0; k < NB; k++)
-#pragma unroll
-        for (int gate = 0; gate < 3; gate++)
-#pragma unroll
-            for (int ks = 0; ks < 3; ks++) A[k][gate][ks] = *(glb_f16x8_t *)(whq + (((size_t)ks * 18 + gate * 6 + ub0 + k) * 64 + lane) * 8);
-#pragma unroll
-    for (int gate = 0; gate < 3; gate++) { sc[gate] = whs[gate * H + ju] * 0x1p-8f; bb[gate] = bhh[gate * H + ju]; }
-    float hj = hstate[ju];
-    __syncthreads();                                   // (the barrier behind the input projection / fix-up that wrote gi: taken behind the 9 / 18 weight fragments' round trip to L2)
-    _Float16 (*hp)[2][H] = (_Float16 (*)[2][H])&sh->hs[0][0];           // [buffer][plane][k]: 2^8 h_{t-1} = hi + lo
-    if (finl) { _Float16 a, b; dq_split(hj, a, b); hp[0][0][ju] = a; hp[0][1][ju] = b; }
-    const float *gi = &sh->gi[0][0];
-    float g0[3];
-#pragma unroll
-    for (int gate = 0; gate < 3; gate++) g0[gate] = gi[gate * H + ju];
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < Tb; t++) {
-        if ((rstmask >> t) & 1u) {                     // uniform over the workgroup
-            __syncthreads();
-            hj = 0.0f; if (finl) { hp[cur][0][ju] = (_Float16)0.0f; hp[cur][1][ju] = (_Float16)0.0f; }
-            __syncthreads();
-        }
-        const float *gn_ = gi + (size_t)min(t + 1, Tb - 1) * DQ_GIS;
-        float g1[3];
-#pragma unroll
-        for (int gate = 0; gate < 3; gate++) g1[gate] = gn_[gate * H + ju];
-        f16x8 bq[3];
-#pragma unroll
-        for (int ks = 0; ks < 3; ks++) bq[ks] = *(const f16x8 *)&hp[cur][par][32 * ks + 8 * g];
-        __builtin_amdgcn_sched_barrier(0);
-        f32x4 acc[NB][3];
-#pragma unroll
-        for (int k = 0; k < NB; k++)
-#pragma unroll
-            for (int gate = 0; gate < 3; gate++) acc[k][gate] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f };
-#pragma unroll
-        for (int ks = 0; ks < 3; ks++)
-#pragma unroll
-            for (int k = 0; k < NB; k++)
-#pragma unroll
-                for (int gate = 0; gate < 3; gate++) acc[k][gate] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[k][gate][ks], bq[ks], acc[k][gate], 0, 0, 0);
-        // C layout: this lane holds rows 4 g + 0..3 of each tile for column c: high-plane product in even columns, low-plane product in odd ones
-        float s3[3];
-#pragma unroll
-        for (int gate = 0; gate < 3; gate++) {
-            float sr[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const float v = NB == 2 ? (blk ? acc[NB - 1][gate][r] : acc[0][gate][r]) : acc[0][gate][r];      // this lane's block
-                sr[r] = v + quad_dpp<QUAD_XOR1>(v); asm volatile("" : "+v"(sr[r]));                               // (computed before the select: no branches)
-            }
-            const float s01 = (cs & 1) ? sr[1] : sr[0], s23 = (cs & 1) ? sr[3] : sr[2];
-            s3[gate] = (cs & 2) ? s23 : s01;
-        }
-        {
-            const float r = gate_sigmoid((s3[0] * sc[0] + bb[0]) + g0[0]);
-            const float z = gate_sigmoid((s3[1] * sc[1] + bb[1]) + g0[1]);
-            const float n = gate_tanh(g0[2] + (s3[2] * sc[2] + bb[2]) * r);
-            hj = (hj - n) * z + n;
-        }
-        if (finl) {
-            _Float16 a, b; dq_split(hj, a, b);
-            hp[cur ^ 1][0][ju] = a; hp[cur ^ 1][1][ju] = b;
-            dq_split(clamp1(hj), a, b);
-            sh->hbh[0][dq_hoff(t, ju)] = a; sh->hbl[0][dq_hoff(t, ju)] = b;
-        }
-#pragma unroll
-        for (int gate = 0; gate < 3; gate++) g0[gate] = g1[gate];
-        cur ^= 1;
-        if (t + 1 < Tb) __syncthreads();               // (the last step's barrier is the consumer's: dq2_gemm_tiles(..., sync_first))
-    }
-    if (finl) hstate[ju] = hj;
-}
-__device__ void dq2_scan_mfma(DecShared2 *sh, const unsigned short *whq, const float *whs, const float *bhh, float *hstate, int Tb, unsigned rstmask)
-{
-    const int wave = rx2_wave();
-    if (wave < 2) dq2_scan_mfma_body<2>(sh, whq, whs, bhh, hstate, Tb, rstmask, 2 * wave);
-    else dq2_scan_mfma_body<1>(sh, whq, whs, bhh, hstate, Tb, rstmask, 2 + wave);
-}
-
-// all decoder layers for rows [0, Tb) (Tb <= 12) of stream b on four wavefronts
-__device__ void dq2_layers(DecShared2 *sh, const rd_decs_args &a, int b, const float *z, float *out, int Tb, unsigned rstmask, int census_noscan)
-{
-    const int tid = rx_tid(), wave = tid >> 6;
-    PH2_T0();
-    {
-        const unsigned *hist = (const unsigned *)(a.x + (size_t)b * a.x_sb - RD_DEC_W);
-        constexpr int NH_ = (RD_DEC_W + NT2 - 1) / NT2;
-        unsigned hu[NH_];                                       // (all requested before the first LDS store: see rx2_load_rxbuf)
-#pragma unroll
-        for (int q = 0; q < NH_; q++) hu[q] = hist[min(tid + q * NT2, RD_DEC_W - 1)];
-#pragma unroll
-        for (int q = 0; q < NH_; q++) {
-            const int c = tid + q * NT2; const unsigned u = hu[q];
-            if (c < RD_DEC_W) { sh->xh[0][dq_xoff(-1, c)] = __builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); sh->xl[0][dq_xoff(-1, c)] = __builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-        }
-        for (int c = tid; c < DQ_XB * 8; c += NT2) { sh->xh[DQ2_ROWS + 1][c] = (_Float16)0.0f; sh->xl[DQ2_ROWS + 1][c] = (_Float16)0.0f; }
-    }
-    dq2_dense1(sh, z, a.dense1, Tb);
-    DqGemm g;
-    // Barriers: every product phase takes the barrier that separates it from the phase before it INSIDE its first dq2_gemm_tiles call (sync_first), behind that call's
-    // first weight requests; the recurrences do the same behind their weight fragments.  A wavefront that has no product in a phase takes the barrier bare.
-    // 18 column tiles of an input projection over four wavefronts: 5 + 5 + 4 + 4
-    const int ct18 = wave < 2 ? 5 * wave : 10 + 4 * (wave - 2);
-    g = (DqGemm){ a.gin[0].wa16, 18, a.gin[0].bias, 288, a.gin[0].wscale, 0, 0, 0, 3, 0, DQ_OUT_GI, 0, 0, nullptr, 0 };
-    if (wave < 2) dq2_gemm_tiles<5>(sh, g, ct18, Tb, rstmask, 1); else dq2_gemm_tiles<4>(sh, g, ct18, Tb, rstmask, 1);
-    PH2(20);
-#pragma unroll 1
-    for (int l = 0; l < 5; l++) {
-        const int in = 96 + 128 * l, cin = in + 96;
-        if (census_noscan) __syncthreads();
-        else if (a.whq[l]) dq2_scan_mfma(sh, a.whq[l], a.whs[l], a.bhh[l], a.h[l] + (size_t)b * 96, Tb, rstmask);
-        else dq2_scan(sh, a.whh[l], a.bhh[l], a.h[l] + (size_t)b * 96, Tb, rstmask);
-        PH2(21);
-        // GLU gates: 6 column tiles, K = 96: 2 + 2 + 1 + 1
-        g = (DqGemm){ a.glu[l].wa16, 6, nullptr, 96, a.glu[l].wscale, 1, 0, 0, 3, 0, DQ_OUT_X, in, 2, nullptr, 0 };
-        if (wave < 2) dq2_gemm_tiles<2>(sh, g, 2 * wave, Tb, rstmask, 1); else dq2_gemm_tiles<1>(sh, g, 2 + wave, Tb, rstmask, 1);
-        PH2(22);
-        // conv (2 tiles, K = 2 cin) beside the columns of the next product that are already final (K = cin): in units of cin k-steps the
-        // conv tiles weigh 2 each, a projection tile 1: wavefronts 0 / 1 = one conv tile + 3 projection tiles, 2 / 3 = 6 projection tiles;
-        // behind the last conv the output layer (6 tiles): one conv tile each on 0 / 1, three output tiles each on 2 / 3
-        const DqGemm gc = (DqGemm){ a.conv[l].wa16, 2, a.conv[l].bias, 32, a.conv[l].wscale, 0, cin / 32, 0, 2 * cin / 32, 0, DQ_OUT_X, cin, 1, nullptr, 0 };
-        const bool last = l == 4;
-        const rd_lin &nx = last ? a.output : a.gin[l + 1];
-        const int nct = last ? 6 : 18;
-        const DqGemm gm = (DqGemm){ nx.wa16, nct, nx.bias, last ? a.out_w : 288, nx.wscale, 0, 0, 0, cin / 32, 0, DQ_OUT_GI, 0, 0, nullptr, 0 };
-        if (wave < 2) {
-            dq2_gemm_tiles<1>(sh, gc, wave, Tb, rstmask, 1);
-            if (!last) dq2_gemm_tiles<3>(sh, gm, 3 * wave, Tb, rstmask, 0);
-        } else if (last) dq2_gemm_tiles<3>(sh, gm, 3 * (wave - 2), Tb, rstmask, 1);
-        else {          // six projection tiles as two calls of three: with six tiles' fragments (4 k-steps x 6 x 4 registers) in flight the K loop spilled -- 20 scratch instructions per k-step
-            dq2_gemm_tiles<3>(sh, gm, 6 + 6 * (wave - 2), Tb, rstmask, 1);
-            dq2_gemm_tiles<3>(sh, gm, 9 + 6 * (wave - 2), Tb, rstmask, 0);
-        }
-        PH2(23);
-        // fix-up: the conv's 32 new columns (one k-step) added onto the staged sums
-        const DqGemm gf = (DqGemm){ nx.wa16, nct, nullptr, last ? a.out_w : 288, nx.wscale, 0, 0, cin / 32, 1, 1, last ? DQ_OUT_GLOBAL : DQ_OUT_GI, 0, 0, out, a.out_w };
-        if (last) { if (wave >= 2) dq2_gemm_tiles<3>(sh, gf, 3 * (wave - 2), Tb, rstmask, 1); else __syncthreads(); }
-        else if (wave < 2) dq2_gemm_tiles<5>(sh, gf, ct18, Tb, rstmask, 1);
-        else dq2_gemm_tiles<4>(sh, gf, ct18, Tb, rstmask, 1);
-        PH2(24);
-    }
-    __syncthreads();                                   // (behind the last fix-up: the history row below reads what the last conv wrote)
-    {
-        unsigned *hist = (unsigned *)(a.x + (size_t)b * a.x_sb - RD_DEC_W);
-        for (int c = tid; c < RD_DEC_W; c += NT2)
-            hist[c] = (unsigned)__builtin_bit_cast(unsigned short, sh->xh[0][dq_xoff(Tb - 1, c)]) | ((unsigned)__builtin_bit_cast(unsigned short, sh->xl[0][dq_xoff(Tb - 1, c)]) << 16);
-    }
-    __syncthreads();
-}
-
-// =====================================================================================================
-// LDS of k_rx_sync2: at most 80 KB, so that two workgroups share a CU
-// =====================================================================================================
+// ---- LDS of k_rx_sync2: at most 80 KB, so that two workgroups share a CU ----
 struct RxShared2 {
     RxScalars S;
+    float rx_unsc; int lcg_next;   // a synchronised call's operand un-scale (rx2_operand_scale) and next LCG state, from the planes phase to check_pilots / the demodulator / thread 0
     double2 rq[4], rzc, rph[24], rrot[24]; double ral[24];   // refine(), in-sync grid: e^{-jw_c 40 q}, e^{-jw_c}, e^{-j(w_k - w_c) 79.5}, e^{-jw_k Nmf}, (w_k - w_c) 80
     int rows48[48];
     double redd[(NW2 + 1) * 10];
@@ -552,458 +107,8 @@ struct RxShared2 {
 };
 static_assert(sizeof(RxShared2) <= 80 * 1024, "two k_rx_sync2 workgroups must fit the 160 KiB LDS of a CU");
 
-// ---- workgroup reductions on four wavefronts (same contracts as block_argmax / block_sum_multi) ------------------------------------
-__device__ void block_argmax2(RxShared2 *sh, float &v, int &k0, int &k1)
-{
-    const int tid = rx_tid(), lane = tid & 63, wave = tid >> 6;
-#define ARGMAX_STEP(CTRL) do { const float ov = quad_dpp<CTRL>(v); const int o0 = quad_dpp_i<CTRL>(k0), o1 = quad_dpp_i<CTRL>(k1); \
-        if (ov > v || (ov == v && (o0 < k0 || (o0 == k0 && o1 < k1)))) { v = ov; k0 = o0; k1 = o1; } } while (0)
-    ARGMAX_STEP(QUAD_XOR1); ARGMAX_STEP(QUAD_XOR2); ARGMAX_STEP(ROW_ROR4); ARGMAX_STEP(ROW_ROR8);
-#undef ARGMAX_STEP
-    {
-        float bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)); int b0 = __builtin_amdgcn_readlane(k0, 0), b1 = __builtin_amdgcn_readlane(k1, 0);
-#pragma unroll
-        for (int r = 1; r < 4; r++) {
-            const float ov = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16 * r)); const int o0 = __builtin_amdgcn_readlane(k0, 16 * r), o1 = __builtin_amdgcn_readlane(k1, 16 * r);
-            if (ov > bv || (ov == bv && (o0 < b0 || (o0 == b0 && o1 < b1)))) { bv = ov; b0 = o0; b1 = o1; }
-        }
-        v = bv; k0 = b0; k1 = b1;
-    }
-    if (lane == 0) { sh->redf[1 + wave] = v; sh->redi[1 + wave] = k0; sh->redj[1 + wave] = k1; }
-    __syncthreads();
-    float bv = sh->redf[1]; int b0 = sh->redi[1], b1 = sh->redj[1];
-#pragma unroll
-    for (int w = 1; w < NW2; w++) {
-        const float ov = sh->redf[1 + w]; const int o0 = sh->redi[1 + w], o1 = sh->redj[1 + w];
-        if (ov > bv || (ov == bv && (o0 < b0 || (o0 == b0 && o1 < b1)))) { bv = ov; b0 = o0; b1 = o1; }
-    }
-    v = bv; k0 = b0; k1 = b1;
-}
-template <int NV>
-__device__ void block_sum_multi2(RxShared2 *sh, double (&v)[NV])
-{
-    const int tid = rx_tid(), lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = wave_sum_f64(v[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) sh->redd[wave * NV + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW2; w++) t += sh->redd[w * NV + k];
-        v[k] = t;
-    }
-}
-__device__ float sigma_r_from_rowsums2(RxShared2 *sh)
-{
-    double v[2] = { 0.0, 0.0 };
-    for (int t = rx_tid(); t < RD_NMF; t += NT2) { v[0] += (double)sh->rowsum1[t]; v[1] += (double)sh->rowsum2[t]; }
-    block_sum_multi2<2>(sh, v);
-    return sigma_r_from_sums(v[0], v[1]);
-}
-
-
-// ---- |Dt| surfaces on the matrix cores ----------------------------------------------------------------------------------------------
-// acquisition.detect_pilots (dsp.py:178-231): Dt[t, f] = sum_m conj(rx[t + m]) p_w[m, f] for all 960 timings x 40 frequencies of a frame: a real GEMM
-// [(row, re | im)] x [320 = (m, re | im)] times the Toeplitz matrix rx[t + m] on v_mfma_f32_16x16x32_f16, both operands in two binary16 planes
-// (hi hi + hi lo + lo hi: 22 bits).
-//   * a wavefront owns 15 timing tiles (240 timings) and walks them in groups of RT = 5;
-//   * the A operands (table) are staged through LDS by the whole workgroup, double-buffered, one barrier per stage;
-//   * the B operand of (timing tile T, k-step s) is the fragment of (T + s, 0): the window slides by one tile per k-step, so a group reads RT + 9 fragments
-//     from the planes instead of 10 RT.
-// (Rounds 3-4 multiplied by the 80 rows of p_w itself: tools/experiments/rx2_search_one_stage.inc.)
-// ---- the pilot correlator in two stages (round 5; the tables and the algebra: rade_host.c, rd_corrq16_table_fill) ----------------------------------
-// Dt[t][f] = sum_r alpha[r][f] Mom_r[t]: stage 1 is the product above with the 32 rows (r, re | im) of the moment table instead of the 80 rows (f, re | im)
-// of p_w -- two row tiles instead of five, 60 matrix instructions per tile of 16 timings instead of 150 --, stage 2 expands the 16 complex moments of a timing
-// tile to the 40 frequencies with ONE k-step (K = 32) per frequency tile.  Stage 1's accumulators ARE stage 2's B operand: the C layout of two 16-row tiles
-// gives lane group g rows 4 g .. 4 g + 3 of either tile, and the host orders stage 2's K axis exactly so (rd_corra16_table_fill) -- the moments are scaled,
-// split into three binary16 planes (33 bits: stage 2 adds nothing to stage 1's rounding) and fed back without leaving the lane.
-struct MomPlanes { f16x8 h, m, l; };
-__device__ __forceinline__ MomPlanes mom_split(const f32x4 a0, const f32x4 a1)
-{
-    MomPlanes p;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {      // |moment| <= 2^8 sqrt(2) x the table row's L1 norm (3545 x 2^... : rade_host.c) -> 2^-7 of it is below 7100, far inside binary16
-        const float v = 0x1p-7f * (j < 4 ? a0[j & 3] : a1[j & 3]);
-        const _Float16 h = (_Float16)v; const float r1 = v - (float)h;
-        const _Float16 m = (_Float16)r1; const float r2 = r1 - (float)m;
-        p.h[j] = h; p.m[j] = m; p.l[j] = (_Float16)r2;
-    }
-    return p;
-}
-// one frequency tile (8 frequencies x (re, im)) of Dt for the 16 timings whose moments are in p: smallest partial products first
-__device__ __forceinline__ f32x4 mom_expand(const f16x8 ah, const f16x8 al, const MomPlanes &p)
-{
-    f32x4 c = { 0.0f, 0.0f, 0.0f, 0.0f };
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, p.l, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, p.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, p.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, p.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, p.h, c, 0, 0, 0);
-    return c;
-}
-// acquisition.detect_pilots' surfaces by the two-stage correlator: same contract as rx2_detect_mfma (outputs: |Dt2| -- and |Dt1| when not cached -- to the stream's
-// cache in HBM, the row sums to rowsum1 / rowsum2, the lane's best (Dt1 + Dt2, t, f)).  rx_unsc undoes the scales of the rx planes and the stage-1 table; the
-// 2^-7 of the moments and the 2^10 of the stage-2 table are undone here.
-__device__ __forceinline__ void rx2_detect_q(RxShared2 *sh, const unsigned short *corrq16_, const unsigned short *corra16_, float *cache_, int cached, int oldb, int newb,
-                                             float rx_unsc_, float &best, int &bt, int &bfi)
-{
-    constexpr int RT = 5, NTF = 5, TPW = 15;
-    static_assert(TPW * NW2 * 16 == RD_NMF && TPW % RT == 0, "timing tiles per wavefront");
-    const int tid = rx_tid(), wave = rx2_wave(), lane = tid & 63, i = lane & 15, g = lane >> 4;
-    const float rx_unsc = rx_unsc_ * 0x1p-3f;
-    // stage 1's table [tile][k-step][plane][lane] (16 B per lane): a stage buffer holds two k-steps of both tiles, chunk u = 256 tile + 128 (k-step & 1) + 64 plane + lane,
-    // i.e. thread tid brings chunks tid and 256 + tid: one lane offset under two uniform bases
-    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corrq16_), 0, 2 * 10 * 2048, 0x00020000);
-    const int vo = tid * 16;
-    u32x4 stg[2];
-    auto stage_load = [&](int sb) {
-        stg[0] = __builtin_amdgcn_raw_buffer_load_b128(qrs, vo, sb * 4096, 0); stg[1] = __builtin_amdgcn_raw_buffer_load_b128(qrs, vo, sb * 4096 + 10 * 2048, 0);
-    };
-    auto stage_store = [&](int buf) { _Float16 *d = &sh->sA[buf][tid * 8]; *(u32x4 *)d = stg[0]; *(u32x4 *)(d + 256 * 8) = stg[1]; };
-    PH2_T0();
-    {   // stage 2's table, whole (640 x 16 B)
-        const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corra16_), 0, 5 * 2048, 0x00020000);
-        const u32x4 t0 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 0, 0), t1 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 4096, 0);
-        u32x4 t2 = { 0u, 0u, 0u, 0u };
-        if (wave < 2) t2 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 8192, 0);
-        stage_load(0);
-        _Float16 *d = &sh->sA2[tid * 8];
-        *(u32x4 *)d = t0; *(u32x4 *)(d + 256 * 8) = t1;
-        if (wave < 2) *(u32x4 *)(d + 512 * 8) = t2;
-        stage_store(0);
-    }
-    float lbest = best; int lkey = 0x7fffffff;
-    int pb = 0;                                                 // the stage buffer being read: flips every stage (five stages per group: the parity runs on across groups)
-    __syncthreads();
-    PH2(15);
-#pragma unroll 1
-    for (int pass = cached ? 1 : 0; pass < 2; pass++) {
-        const unsigned *ph = sh->srxh + pass * RD_NMF + i + 4 * g, *pl = sh->srxl + pass * RD_NMF + i + 4 * g;
-        const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(cache_ + (size_t)(pass ? newb : oldb) * RD_NFC * RD_NMF), 0, RD_NFC * RD_NMF * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(cache_ + (size_t)oldb * RD_NFC * RD_NMF), 0, RD_NFC * RD_NMF * 4, 0x00020000);
-        float *rowsum = pass ? sh->rowsum2 : sh->rowsum1;
-#pragma unroll 1
-        for (int grp = 0; grp < TPW / RT; grp++) {
-            const int T0 = wave * TPW + grp * RT;
-            f32x4 acc1[RT][2];
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++) { acc1[rt][0] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; acc1[rt][1] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; }
-            u32x4 wh[RT + 1], wl[RT + 1];
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) { wh[rt][j] = ph[16 * (T0 + rt) + j]; wl[rt][j] = pl[16 * (T0 + rt) + j]; }
-#pragma unroll
-            for (int sb = 0; sb < 5; sb++) {
-                stage_load(sb == 4 ? 0 : sb + 1);
-#pragma unroll
-                for (int ds = 0; ds < 2; ds++) {
-                    const int sidx = 2 * sb + ds;
-                    // fragment F of the sliding window lives in slot (F - T0) mod (RT + 1): tile rt reads slot (rt + sidx) mod (RT + 1), the fragment the NEXT k-step adds goes
-                    // into the slot the first tile just left (all indices are compile-time: the loops are unrolled).  Rounds 3-4 shifted the window through the registers
-                    // instead: 40 moves per k-step behind the matrix instructions
-                    if (sidx < 9) {
-#pragma unroll
-                        for (int j = 0; j < 4; j++) { wh[(RT + sidx) % (RT + 1)][j] = ph[16 * (T0 + RT + sidx) + j]; wl[(RT + sidx) % (RT + 1)][j] = pl[16 * (T0 + RT + sidx) + j]; }
-                    }
-                    const _Float16 *Ab = &sh->sA[pb][lane * 8];
-                    const f16x8 a0h = *(const f16x8 *)(Ab + ((0 * 2 + ds) * 2 + 0) * 512), a0l = *(const f16x8 *)(Ab + ((0 * 2 + ds) * 2 + 1) * 512);
-                    const f16x8 a1h = *(const f16x8 *)(Ab + ((1 * 2 + ds) * 2 + 0) * 512), a1l = *(const f16x8 *)(Ab + ((1 * 2 + ds) * 2 + 1) * 512);
-                    __builtin_amdgcn_sched_barrier(0);
-#define WSL(rt) (((rt) + sidx) % (RT + 1))
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0l, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][0], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1l, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][1], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0h, __builtin_bit_cast(f16x8, wl[WSL(rt)]), acc1[rt][0], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1h, __builtin_bit_cast(f16x8, wl[WSL(rt)]), acc1[rt][1], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0h, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][0], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1h, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][1], 0, 0, 0);
-#undef WSL
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                stage_store(pb ^ 1);
-                pb ^= 1;
-                __syncthreads();
-            }
-            PH2(16);
-            // ---- stage 2 and the epilogue, one timing tile at a time.  The surfaces in the stream's HBM cache are only ever read back by the lane that wrote them
-            // (|Dt2| of this call is |Dt1| of the next), so their layout is the lane's: per (wavefront, group, timing tile) 64 lanes x 10 values (frequency tile,
-            // then the two frequencies) as two 16-byte vectors [lane] + one 8-byte vector [lane]: fully coalesced.
-            f16x8 A2h[NTF], A2l[NTF];
-#pragma unroll
-            for (int q = 0; q < NTF; q++) { A2h[q] = *(const f16x8 *)&sh->sA2[((q * 2) * 64 + lane) * 8]; A2l[q] = *(const f16x8 *)&sh->sA2[((q * 2 + 1) * 64 + lane) * 8]; }
-            const int gb = (wave * (TPW / RT) + grp) * RT * 2560;         // byte offset of the group's block; 2560 B per timing tile
-            float pv[2][2 * NTF];
-            auto pv_load = [&](int slot, int rt) {
-                const u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(prs, lane * 16, gb + rt * 2560, 0), v1 = __builtin_amdgcn_raw_buffer_load_b128(prs, lane * 16, gb + rt * 2560 + 1024, 0);
-                const u32x2 v2 = __builtin_amdgcn_raw_buffer_load_b64(prs, lane * 8, gb + rt * 2560 + 2048, 0);
-#pragma unroll
-                for (int k = 0; k < 4; k++) { pv[slot][k] = __uint_as_float(v0[k]); pv[slot][4 + k] = __uint_as_float(v1[k]); }
-                pv[slot][8] = __uint_as_float(v2[0]); pv[slot][9] = __uint_as_float(v2[1]);
-            };
-            if (pass) pv_load(0, 0);
-            const int tb = 16 * T0 + i;
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++) {
-                if (pass && rt + 1 < RT) pv_load((rt + 1) & 1, rt + 1);
-                const MomPlanes mp = mom_split(acc1[rt][0], acc1[rt][1]);
-                float dd[2 * NTF], rs = 0.0f;
-#pragma unroll
-                for (int q = 0; q < NTF; q++) {
-                    // C layout: column = lane & 15 (timing), rows 4 g + r = (re, im) of f = 8 q + 2 g and f + 1
-                    const f32x4 c = mom_expand(A2h[q], A2l[q], mp);
-                    const float d0 = rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[0], c[0], c[1] * c[1])), d1 = rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[2], c[2], c[3] * c[3]));
-                    rs += d0; rs += d1;
-                    dd[2 * q] = d0; dd[2 * q + 1] = d1;
-                }
-                {   // the other three lane groups hold the row's other frequencies: v_permlane16/32_swap (vector ALU, no LDS round trip)
-                    const auto p16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(rs), __float_as_uint(rs), false, false);
-                    rs = __uint_as_float(p16[0]) + __uint_as_float(p16[1]);
-                    const auto p32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(rs), __float_as_uint(rs), false, false);
-                    rs = __uint_as_float(p32[0]) + __uint_as_float(p32[1]);
-                }
-                __builtin_amdgcn_raw_buffer_store_b128((u32x4){ __float_as_uint(dd[0]), __float_as_uint(dd[1]), __float_as_uint(dd[2]), __float_as_uint(dd[3]) }, drs, lane * 16, gb + rt * 2560, 0);
-                __builtin_amdgcn_raw_buffer_store_b128((u32x4){ __float_as_uint(dd[4]), __float_as_uint(dd[5]), __float_as_uint(dd[6]), __float_as_uint(dd[7]) }, drs, lane * 16, gb + rt * 2560 + 1024, 0);
-                __builtin_amdgcn_raw_buffer_store_b64((u32x2){ __float_as_uint(dd[8]), __float_as_uint(dd[9]) }, drs, lane * 8, gb + rt * 2560 + 2048, 0);
-                // every lane keeps its own best (t ascending, then f ascending, strict >: the earliest wins); block_argmax2 orders the lanes the same way.  Branch-free,
-                // (t, f) packed in one register
-                const int t = tb + 16 * rt;
-                if (pass) {
-#pragma unroll
-                    for (int q = 0; q < NTF; q++) {
-                        const int k0 = (t << 6) | (8 * q + 2 * g);
-                        const float s0 = pv[rt & 1][2 * q] + dd[2 * q], s1 = pv[rt & 1][2 * q + 1] + dd[2 * q + 1];
-                        const bool c0 = s0 > lbest; lbest = c0 ? s0 : lbest; lkey = c0 ? k0 : lkey;
-                        const bool c1 = s1 > lbest; lbest = c1 ? s1 : lbest; lkey = c1 ? k0 + 1 : lkey;
-                    }
-                }
-                if (g == 0) rowsum[t] = rs;
-            }
-            PH2(17);
-        }
-        __syncthreads();
-        PH2(18);
-    }
-    best = lbest; bt = lkey >> 6; bfi = lkey & 63;
-}
-
-// ---- refine() (dsp.py:233-270): see refine_tile / refine_moments above for the arithmetic ------------------------------------------
-__device__ __forceinline__ f64x4 refine2_tile(const RxShared2 *sh, int mt, int frame, int s0, int ns, int nf, int nt, int lane)
-{
-    const int i = lane & 15, kk = lane >> 4, c = kk & 1, n0 = kk >> 1;
-    const int row = 16 * mt + i, fi = row >> 1, cp = row & 1;
-    const bool rv = fi < nf;
-    const double2 z1 = sh->rtw[rv ? fi : 0];
-    double2 cur = s0 ? sh->rt80[rv ? fi : 0] : make_double2(1.0, 0.0);
-    if (n0) cur = make_double2(cur.x * z1.x - cur.y * z1.y, cur.x * z1.y + cur.y * z1.x);
-    const double c2r = z1.x * z1.x - z1.y * z1.y, c2i = 2.0 * z1.x * z1.y;
-    const double2 prv = make_double2(cur.x * c2r + cur.y * c2i, cur.y * c2r - cur.x * c2i);
-    double xc = cp == c ? cur.x : (cp == 0 ? -cur.y : cur.y), xp = cp == c ? prv.x : (cp == 0 ? -prv.y : prv.y);
-    if (!rv) { xc = 0.0; xp = 0.0; }
-    const double k2 = 2.0 * c2r;
-    const double *xw = (const double *)&sh->xm[0] + 4 * (frame * 176 + (i < nt ? i : 0) + 2 * s0 + n0) + 2 * c;
-    const double2 *pp = &sh->pd[2 * s0 + n0];
-    f64x4 acc0 = { 0.0, 0.0, 0.0, 0.0 }, acc1 = acc0;
-    double2 pn[4]; double a1[4], a2[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) { pn[u] = pp[2 * u]; a1[u] = xw[8 * u]; a2[u] = xw[8 * u + 1]; }
-#pragma unroll 1
-    for (int s = 0; s < ns; s += 4) {
-        double b[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) b[u] = pn[u].x * a1[u];
-#pragma unroll
-        for (int u = 0; u < 4; u++) b[u] = fma(pn[u].y, a2[u], b[u]);
-        __builtin_amdgcn_sched_barrier(0);
-        const int sn = s + 4 < ns ? s + 4 : s;
-#pragma unroll
-        for (int u = 0; u < 4; u++) { pn[u] = pp[2 * (sn + u)]; a1[u] = xw[8 * (sn + u)]; a2[u] = xw[8 * (sn + u) + 1]; }
-        __builtin_amdgcn_sched_barrier(0);
-        const double x1 = fma(k2, xc, -xp), x2 = fma(k2, x1, -xc), x3 = fma(k2, x2, -x1);
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(xc, b[0], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, b[1], acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, b[2], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x3, b[3], acc1, 0, 0, 0);
-        xp = x3; xc = fma(k2, x3, -x2);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return acc0 + acc1;
-}
-__device__ __forceinline__ void refine2_tables(RxShared2 *sh, int k, double fstart, double fstop, double fstep)
-{
-    const int nf = (int)ceil((fstop - fstart) / fstep);
-    const double delta = (fstart + fstep) - fstart;
-    if (k < 0 || k >= 3 * nf) return;
-    const int which = k / nf, fi = k - which * nf;
-    const double w = 2.0 * PI_D * dgrid_nc(fstart, fi, delta) / 8000.0;
-    const double arg = which == 0 ? -w : (which == 1 ? -w * RD_NMF : -w * 80.0);
-    double sn, cs; sincos(arg, &sn, &cs);
-    double2 *dstp = which == 0 ? sh->rtw : (which == 1 ? sh->rrot80 : sh->rt80);
-    dstp[fi] = make_double2(cs, sn);
-}
-__device__ __forceinline__ void refine2_tables_sync(RxShared2 *sh, int k, double fstart, double fstop, double fstep)
-{
-    const int nf = (int)ceil((fstop - fstart) / fstep);
-    const double delta = (fstart + fstep) - fstart;
-    const double wc = 0.5 * (2.0 * PI_D * fstart / 8000.0 + 2.0 * PI_D * dgrid_nc(fstart, nf - 1, delta) / 8000.0);
-    if (k < 0 || k > 52) return;
-    const int kf = k < 24 ? k : k - 24;
-    if (k < 48 && kf >= nf) return;
-    const double w = 2.0 * PI_D * dgrid_nc(fstart, kf, delta) / 8000.0, dw = w - wc;
-    const double arg = k < 24 ? -w * RD_NMF : (k < 48 ? -dw * 79.5 : (k < 52 ? -wc * 40.0 * (k - 48) : -wc));
-    double sn, cs; sincos(arg, &sn, &cs);
-    const double2 v = make_double2(cs, sn);
-    if (k < 24) sh->rrot[k] = v;
-    else if (k < 48) { sh->rph[kf] = v; sh->ral[kf] = dw * 80.0; }
-    else if (k < 52) sh->rq[k - 48] = v;
-    else sh->rzc = v;
-}
-// moments of one quarter q of the samples (20 matrix instructions), added onto acc0 / acc1; the powers ((n - 79.5) / 80)^m come from L2
-__device__ __forceinline__ void refine2_moments(const RxShared2 *sh, const double *vmg, int frame, int q, int nt, int lane, f64x4 &acc0, f64x4 &acc1)
-{
-    const int i = lane & 15, kk = lane >> 4, c = kk & 1, n0 = kk >> 1;
-    const int m = i >> 1, cp = i & 1, s0 = 20 * q;
-    const double2 z1 = sh->rzc;
-    double2 cur = sh->rq[q];
-    if (n0) cur = make_double2(cur.x * z1.x - cur.y * z1.y, cur.x * z1.y + cur.y * z1.x);
-    const double c2r = z1.x * z1.x - z1.y * z1.y, c2i = 2.0 * z1.x * z1.y;
-    const double2 prv = make_double2(cur.x * c2r + cur.y * c2i, cur.y * c2r - cur.x * c2i);
-    double xc = cp == c ? cur.x : (cp == 0 ? -cur.y : cur.y), xp = cp == c ? prv.x : (cp == 0 ? -prv.y : prv.y);
-    const double k2 = 2.0 * c2r;
-    const double *xw = (const double *)&sh->xm[0] + 4 * (frame * 176 + (i < nt ? i : 0) + 2 * s0 + n0) + 2 * c;
-    const double2 *pp = &sh->pd[2 * s0 + n0];
-    // (an explicit global pointer: rx2_refine is a real function, its `vmg` a generic pointer, and the 20 loads below were flat loads, which count on the
-    // LDS wait counter too; as global loads they do not -- measured: no change in the cycles per call, the batch is issued far enough ahead either way)
-    const __attribute__((address_space(1))) double *vp = (const __attribute__((address_space(1))) double *)vmg + m * RD_M + 2 * s0 + n0;
-    double vall[20];                                            // this lane's 20 powers of the quarter: one batch of loads ahead of the loop
-#pragma unroll
-    for (int u = 0; u < 20; u++) vall[u] = vp[2 * u];
-    double2 pn[4]; double a1[4], a2[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) { pn[u] = pp[2 * u]; a1[u] = xw[8 * u]; a2[u] = xw[8 * u + 1]; }
-#pragma unroll
-    for (int s = 0; s < 20; s += 4) {
-        double b[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) b[u] = pn[u].x * a1[u];
-#pragma unroll
-        for (int u = 0; u < 4; u++) b[u] = fma(pn[u].y, a2[u], b[u]);
-        __builtin_amdgcn_sched_barrier(0);
-        const int sn = s + 4 < 20 ? s + 4 : s;
-#pragma unroll
-        for (int u = 0; u < 4; u++) { pn[u] = pp[2 * (sn + u)]; a1[u] = xw[8 * (sn + u)]; a2[u] = xw[8 * (sn + u) + 1]; }
-        __builtin_amdgcn_sched_barrier(0);
-        const double x1 = fma(k2, xc, -xp), x2 = fma(k2, x1, -xc), x3 = fma(k2, x2, -x1);
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(xc * vall[s], b[0], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1 * vall[s + 1], b[1], acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x2 * vall[s + 2], b[2], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x3 * vall[s + 3], b[3], acc1, 0, 0, 0);
-        xp = x3; xc = fma(k2, x3, -x2);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-__device__ void rx2_refine(RxShared2 *sh, const double *vmg, int *tmax, double *fmax, int t0, int nt, double fstart, double fstop, double fstep, bool in_sync)
-{
-    const int tid = rx_tid(), lane = tid & 63, wave = tid >> 6;
-    const int nf = (int)ceil((fstop - fstart) / fstep);
-    const double delta = (fstart + fstep) - fstart;
-    const int ntasks = ((2 * nf + 15) >> 4) * 2;
-    const int i = lane & 15, kk = lane >> 4;
-    PH2_T0();
-    if (!in_sync) refine2_tables(sh, tid, fstart, fstop, fstep);
-    for (int j = tid; j < 2 * 176; j += NT2) {                            // the two windows as doubles: (xr, xi, xi, -xr)
-        const int frame = j / 176, k = j - frame * 176;
-        const float2 x = sh->rxb[min(t0 + frame * RD_NMF + k, RD_RXBUF - 1)];
-        double *d = (double *)&sh->xm[0] + 4 * j;
-        d[0] = (double)x.x; d[1] = (double)x.y; d[2] = (double)x.y; d[3] = -(double)x.x;
-    }
-    __syncthreads();
-    PH2(27);
-    float best = -1.0f; int bf = 0x7fffffff, bt = 0x7fffffff;
-    if (in_sync) {
-        // wavefront w = (half w >> 1 of the samples, frame w & 1): the two quarters of its half accumulate into the same tile
-        {
-            f64x4 a0 = { 0.0, 0.0, 0.0, 0.0 }, a1 = a0;
-            refine2_moments(sh, vmg, wave & 1, 2 * (wave >> 1), nt, lane, a0, a1);
-            refine2_moments(sh, vmg, wave & 1, 2 * (wave >> 1) + 1, nt, lane, a0, a1);
-            const f64x4 part = a0 + a1;
-#pragma unroll
-            for (int r = 0; r < 4; r++) sh->rmom[wave >> 1][wave & 1][lane][r] = part[r];
-        }
-        __syncthreads();
-        PH2(28);
-        for (int o = tid; o < 2 * 64 * 4; o += NT2) {                     // C layout (f64 16x16x4): col = lane & 15 (t), row = (lane >> 4) + 4 * reg
-            const int frame = o >> 8, l = (o >> 2) & 63, r = o & 3;
-            sh->mtot[frame][(l >> 4) + 4 * r][l & 15] = sh->rmom[0][frame][l][r] + sh->rmom[1][frame][l][r];
-        }
-        __syncthreads();
-        PH2(29);
-        for (int o = tid; o < nf * 16; o += NT2) {
-            const int fo = o >> 4, t = o & 15;
-            if (t >= nt) continue;
-            const double al = sh->ral[fo];
-            const double2 ph = sh->rph[fo], rt = sh->rrot[fo];
-            float2 d12[2];
-#pragma unroll
-            for (int frame = 0; frame < 2; frame++) {
-                double re = 0.0, im = 0.0, cm = 1.0;
-#pragma unroll
-                for (int mq = 0; mq < 8; mq++) {
-                    const double mr = sh->mtot[frame][2 * mq][t], mi = sh->mtot[frame][2 * mq + 1][t];
-                    if ((mq & 3) == 0) { re = fma(cm, mr, re); im = fma(cm, mi, im); }
-                    else if ((mq & 3) == 1) { re = fma(cm, mi, re); im = fma(-cm, mr, im); }
-                    else if ((mq & 3) == 2) { re = fma(-cm, mr, re); im = fma(-cm, mi, im); }
-                    else { re = fma(-cm, mi, re); im = fma(cm, mr, im); }
-                    cm = cm * al * (1.0 / (double)(mq + 1));
-                }
-                double xr = re * ph.x - im * ph.y, xi = re * ph.y + im * ph.x;
-                if (frame == 1) { const double tr = xr * rt.x - xi * rt.y; xi = xr * rt.y + xi * rt.x; xr = tr; }
-                d12[frame] = make_float2((float)xr, (float)xi);
-            }
-            const float v = hypotf(d12[0].x + d12[1].x, d12[0].y + d12[1].y);
-            if (v > best || (v == best && (fo < bf || (fo == bf && t < bt)))) { best = v; bf = fo; bt = t; }
-        }
-    } else {
-        auto finish = [&](const f64x4 &acc, int mt, int frame) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const double mine = acc[r], other = __shfl_xor(mine, 16);
-                if ((kk & 1) == 0) {
-                    const int fo = 8 * mt + (kk >> 1) + 2 * r;
-                    double re = mine, im = other;
-                    if (frame == 1 && fo < nf) {
-                        const double2 rt = sh->rrot80[fo];
-                        const double tr = re * rt.x - im * rt.y; im = re * rt.y + im * rt.x; re = tr;
-                    }
-                    if (fo < nf && i < nt) sh->dtr[(frame * nf + fo) * 16 + i] = make_float2((float)re, (float)im);
-                }
-            }
-        };
-        for (int task = wave; task < ntasks; task += NW2) finish(refine2_tile(sh, task >> 1, task & 1, 0, 80, nf, nt, lane), task >> 1, task & 1);
-        __syncthreads();
-        for (int task = tid; task < nf * nt; task += NT2) {
-            const int fi = task / nt, ti = task - fi * nt;
-            const float2 a = sh->dtr[fi * 16 + ti], b = sh->dtr[(nf + fi) * 16 + ti];
-            const float v = hypotf(a.x + b.x, a.y + b.y);
-            if (v > best || (v == best && (fi < bf || (fi == bf && ti < bt)))) { best = v; bf = fi; bt = ti; }
-        }
-    }
-    PH2(30);
-    block_argmax2(sh, best, bf, bt);
-    PH2(31);
-    if (best > 0.0f) { *tmax = t0 + bt; *fmax = dgrid_nc(fstart, bf, delta); }      // (two roundings, like np.arange's elements: rade_devutil.h)
-}
+#include "rade_rx_search.h"
+#include "rade_rx_refine.h"
 
 // rx_buf and the |Dt| row sums from the stream's HBM record into LDS: every load of a thread requested before the first store (as a plain loop
 // the compiler cannot tell that the LDS stores do not alias the record and waits for each load before the next: 13 round trips in a row)
@@ -1021,7 +126,7 @@ __device__ __forceinline__ void rx2_load_rxbuf(RxShared2 *sh, const rd_rx_stream
     for (int q = 0; q < NR_; q++) { const int i = tid + q * NT2; if (i < RD_NMF) { sh->rowsum1[i] = r1[q]; sh->rowsum2[i] = r2[q]; } }
 }
 
-// ---- decoder + output stage for the rows a stream has pending (rx_decode_pending on four wavefronts, chunks of 12 rows) -----------
+// ---- decoder + output stage for the rows a stream has pending (four wavefronts, chunks of 12 rows) -----------
 // rx_buf and the row sums leave LDS for the duration (the stage's 64 KB overlay them): out to the stream's HBM record, back afterwards
 __device__ __forceinline__ void rx2_decode_pending(RxShared2 *sh, const rd_sync_args &a, int b)
 {
@@ -1098,241 +203,8 @@ __device__ __forceinline__ void rx2_bypass_pending(RxShared2 *sh, const rd_sync_
     __syncthreads();
 }
 
-// check_pilots' row refreshes of one modem frame, NRT tiles of 16 row draws per wavefront, by the two-stage correlator (rx2_detect_q's algebra): the three tiles of 16 row draws against the
-// moment table (A fragments straight from L2, two k-steps ahead: 40 KB per call and wavefront instead of 60 + 40 over the two wavefronts a frame had), the moments
-// expanded to the 40 frequencies, |Dt| summed over them in the wavefront -> rowsum1 / rowsum2 directly (rounds 3-4: partial sums of two wavefronts through a table and
-// a second barrier).  The gathers: lane (row draw i, group g) needs samples 16 s + 4 g .. + 3 of its window in k-step s, and the windows start at random offsets, so the
-// lanes of a read hit banks at random whatever the layout.  What the layout decides is how many LDS cycles that costs: with a sample's two plane words side by side
-// one ds_read_b64 (64 banks, 2 cycles conflict-free) brings what took two ds_read_b32 (32 banks, 2 cycles each) -- measured by bank model over random draws: 6.6 against
-// 13.1 LDS cycles per sample and wave-instruction -- and every window is read by ONE wavefront, not two.
-typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
-// pre() runs once behind the first table requests, side(s) behind the matrix instructions of k-step s: work of the caller's that does not depend on this
-// function's results, placed where the wavefront would otherwise wait for table fragments from L2 (6 NRT matrix instructions per k-step cover 100-200 cycles of
-// a round trip of 800)
-template <int NRT, int DA, class Pre, class Side>
-__device__ __forceinline__ void check2_rows_q(RxShared2 *sh, const unsigned short *corrq16_, const unsigned short *corra16_, int frame, int rt0, int lane, float rx_unsc_, Pre pre, Side side)
-{
-    const int i = lane & 15, g = lane >> 4;
-    const float rx_unsc = rx_unsc_ * 0x1p-3f;
-    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corrq16_), 0, 2 * 10 * 2048, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corra16_), 0, 5 * 2048, 0x00020000);
-    // four address registers per row tile that the compiler cannot see through: merged into ds_read2_b64 (or an unaligned ds_read_b128) the reads would run at half rate
-    lds_cu32x2 *px[NRT][4];
-#pragma unroll
-    for (int rt = 0; rt < NRT; rt++) {
-        lds_cu32x2 *b0 = (lds_cu32x2 *)&sh->rxhl[0] + (sh->rows48[(rt0 + rt) * 16 + i] + frame * RD_NMF + 4 * g);
-#pragma unroll
-        for (int j = 0; j < 4; j++) { px[rt][j] = b0 + j; asm volatile("" : "+v"(px[rt][j])); }
-    }
-    f32x4 acc1[NRT][2];
-#pragma unroll
-    for (int rt = 0; rt < NRT; rt++) { acc1[rt][0] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; acc1[rt][1] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; }
-    u32x4 A[DA][4];                                            // [k-step mod DA][2 tile + plane]: DA k-steps of table fragments in flight
-    auto fetchA = [&](int slot, int s) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) A[slot][u] = __builtin_amdgcn_raw_buffer_load_b128(qrs, lane * 16, (((u >> 1) * 10 + s) * 2 + (u & 1)) * 1024, 0);
-    };
-    u32x4 bh[2][NRT], bl[2][NRT];
-    auto rows = [&](int slot, int s) {
-#pragma unroll
-        for (int rt = 0; rt < NRT; rt++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) { const u32x2 v = px[rt][j][16 * s]; bh[slot][rt][j] = v[0]; bl[slot][rt][j] = v[1]; }
-    };
-#pragma unroll
-    for (int d = 0; d < DA; d++) fetchA(d, d);
-    pre();
-    rows(0, 0);
-    u32x4 A2[2 * 5];                                           // stage 2's fragments [2 q + plane]: requested under the last k-steps
-#pragma unroll
-    for (int s = 0; s < 10; s++) {
-        if (s + 1 < 10) rows((s + 1) & 1, s + 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            const f16x8 ah = __builtin_bit_cast(f16x8, A[s % DA][2 * nt]), al = __builtin_bit_cast(f16x8, A[s % DA][2 * nt + 1]);
-#pragma unroll
-            for (int rt = 0; rt < NRT; rt++) acc1[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, __builtin_bit_cast(f16x8, bh[s & 1][rt]), acc1[rt][nt], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < NRT; rt++) acc1[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(f16x8, bl[s & 1][rt]), acc1[rt][nt], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < NRT; rt++) acc1[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(f16x8, bh[s & 1][rt]), acc1[rt][nt], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + DA < 10) fetchA(s % DA, s + DA);
-        if (s == 10 - DA) {
-#pragma unroll
-            for (int u = 0; u < 10; u++) A2[u] = __builtin_amdgcn_raw_buffer_load_b128(ars, lane * 16, u * 1024, 0);
-        }
-        side(s);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    float *rowsum = frame ? sh->rowsum2 : sh->rowsum1;
-#pragma unroll
-    for (int rt = 0; rt < NRT; rt++) {
-        const MomPlanes mp = mom_split(acc1[rt][0], acc1[rt][1]);
-        float s = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 5; q++) {      // C layout: column = lane & 15 (row draw), rows 4 g + r = (re, im) of f = 8 q + 2 g and f + 1
-            const f32x4 c = mom_expand(__builtin_bit_cast(f16x8, A2[2 * q]), __builtin_bit_cast(f16x8, A2[2 * q + 1]), mp);
-            s += rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[0], c[0], c[1] * c[1])) + rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[2], c[2], c[3] * c[3]));
-        }
-        {   // the other three lane groups hold the row's other frequencies
-            const auto p16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
-            s = __uint_as_float(p16[0]) + __uint_as_float(p16[1]);
-            const auto p32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
-            s = __uint_as_float(p32[0]) + __uint_as_float(p32[1]);
-        }
-        // (two draws of the same row compute the same sum from the same samples: whichever store lands last, the value is the same)
-        if (g == 0) rowsum[sh->rows48[(rt0 + rt) * 16 + i]] = s;
-    }
-}
-
-// ---- band-pass filter (complex_bpf, dsp.py:39-102) ahead of the receiver -----------------------------------------------------------------
-// The filter is a stateful streaming FIR of the input: mix down with a running phase, 101 real taps, mix up.  Nothing in it depends on the sync
-// state machine, so it runs as a bulk pre-pass over all the samples of a rade_batch_rx invocation (k_rx_bpf_chain + k_rx_bpf) and the receiver
-// kernel reads filtered samples.  What the reference's arithmetic does depend on is how the stream is cut into calls: the phase is a complex64
-// carried from call to call (phase_vec = phase * phase_vec_exp[0:n], self.phase = phase_vec[-1]: dsp.py:70-71, :99).  The pre-pass therefore
-// follows the reference's own partition: block 0 = the nin the stream's next call will consume (from its state record), every later block Nmf
-// samples -- exact unless a timing slip changes nin INSIDE an invocation; from that call on the stream filters its own samples (rx2_bpf_own)
-// until the invocation ends, and the next invocation's pre-pass starts from the state it left.  Either way every output sample is what
-// complex_bpf.bpf would have produced for the stream's actual sequence of calls, from ONE arithmetic (bpf_stage_planes + bpf_fir_tile, shared by
-// the pre-pass kernel and rx2_bpf_own; mixers without fused multiply-adds: cmul_nc), so cutting a stream into invocations differently cannot move a bit.
-// The same kernels filter the transmit side (radae_txe.py:74-83, :130-132: the optional Tx band-pass filter, there followed by the magnitude clip).
-//   chain[b] (float2 [chain_stride]): entry 0 = (nin0, mem_len0) as integer bits, entry 1 + k = the phase block k starts from.
-// Memory quirk kept (dsp.py:55 against :96): the memory holds Ntap - 1 = 100 samples before the first call and Ntap + 1 = 102 after it while the
-// strided window always starts at index 0, so outputs are delayed by two more samples from the second call on.
-
-// ---- the 101-tap FIR on the matrix cores (shared by the pre-pass kernel and the receiver's own off-grid filtering: one arithmetic) -----------
-// y[i] = sum_t h[t] w[i + t] over a window w of baseband samples is the product of the Toeplitz matrix T[r][m] = h[m - r] (16 x 128, taps padded
-// with zeros) with the Hankel matrix U[m][q] = w[16 q + m]: Y[r][q] = y[16 q + r], one 16 x 16 tile = 256 consecutive outputs.  On
-// v_mfma_f32_16x16x32_f16: T is the A operand (two binary16 planes of 2^10 h, a constant table: rd_bpf16_table_fill), U the B operand -- its
-// fragment for (column q, k-group g, k-step ks) is EIGHT CONSECUTIVE window samples starting at 16 q + 32 ks + 8 g, one aligned 16-byte LDS read
-// from a plane -- real and imaginary parts as separate planes, each split hi + lo (22 bits, one power-of-two scale per block from its largest
-// component): hi hi + hi lo + lo hi in f32, 24 matrix instructions per tile against 51,712 vector FMAs.  The vector FIR was bound by LDS reads
-// (every thread re-read its sliding window); this form reads each plane entry 8 times instead of 101.
-#define BPF_NPL 1408                   /* halfs per plane: five tiles of 256 outputs + the 127 samples the last rows reach beyond */
-#define BPF_TILES(n) (((n) + 255) >> 8)
-struct BpfLds {                        // 11,264 B: exactly the receiver's xm work area
-    __attribute__((aligned(16))) _Float16 rh[BPF_NPL], rl[BPF_NPL], ih[BPF_NPL], il[BPF_NPL];
-};
-// The window [memory (102) | block (n)] into the four planes, entry i of it at plane index i - o (o = 2 before a stream's first call, whose memory is two
-// samples shorter: dsp.py:55; entries below o are dropped): thread tid brings head = entry tid (tid < 102) and body[q] = entry 102 + tid + 256 q, ZERO
-// beyond the block -- all loaded by the caller in one batch, so that a workgroup pays one memory round trip for its window and not one per entry.
-// Returns the factor that undoes the operand scales.  Every thread of the 256-thread workgroup calls this (two barriers inside); maxw is an LDS word.
-#define BPF_NQ 5                       /* body entries per thread: 5 x 256 >= the longest block (1152, the end-of-over frame on the transmit side) */
-__device__ __forceinline__ float bpf_stage_planes(BpfLds *pl, unsigned *maxw, int tid, float2 head, const float2 (&body)[BPF_NQ], int o)
-{
-    float m = tid < 102 ? fmaxf(fabsf(head.x), fabsf(head.y)) : 0.0f;
-#pragma unroll
-    for (int q = 0; q < BPF_NQ; q++) m = fmaxf(m, fmaxf(fabsf(body[q].x), fabsf(body[q].y)));
-    if (tid == 0) *maxw = 0u;
-    __syncthreads();
-    m = wave_max_f32(m);
-    if ((tid & 63) == 0) atomicMax(maxw, __float_as_uint(m));
-    __syncthreads();
-    const int eb = min(max((int)((*maxw >> 23) & 0xffu), 32), 222);
-    const float sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);          // the largest component lands in [2^7, 2^8)
-    auto put = [&](int w, float2 v) {
-        const float xr = v.x * sc, xi = v.y * sc;
-        const _Float16 h0 = (_Float16)xr, h1 = (_Float16)xi;
-        pl->rh[w] = h0; pl->rl[w] = (_Float16)(xr - (float)h0); pl->ih[w] = h1; pl->il[w] = (_Float16)(xi - (float)h1);
-    };
-    if (tid < 102 && tid >= o) put(tid - o, head);
-#pragma unroll
-    for (int q = 0; q < BPF_NQ; q++) put(102 - o + tid + 256 * q, body[q]);
-    if (tid < BPF_NPL - (102 + 256 * BPF_NQ)) put(102 + 256 * BPF_NQ + tid, make_float2(0.0f, 0.0f));      // the tail the last tile's rows reach into
-    if (tid < o) put(BPF_NPL - o + tid, make_float2(0.0f, 0.0f));
-    __syncthreads();
-    return __uint_as_float((unsigned)(eb - 7 - 10) << 23);                            // 2^(E - 7) from the samples, 2^-10 from the taps
-}
-// outputs 256 tile + 16 (lane & 15) + 4 (lane >> 4) + r, r = 0..3, of the staged window: (re[r], im[r]), still in operand scale
-struct BpfTaps { f16x8 h[4], l[4]; };          // the lane's A fragments (rd_bpf16_table_fill): loaded once, ahead of the staging
-__device__ __forceinline__ void bpf_load_taps(BpfTaps &t, const unsigned short *tab16, int lane)
-{
-    typedef const __attribute__((address_space(1))) f16x8 glb_f16x8_t;
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) { t.h[ks] = *(glb_f16x8_t *)(tab16 + (((size_t)ks * 2) * 64 + lane) * 8); t.l[ks] = *(glb_f16x8_t *)(tab16 + (((size_t)ks * 2 + 1) * 64 + lane) * 8); }
-}
-__device__ __forceinline__ void bpf_fir_tile(const BpfLds *pl, const BpfTaps &t, int tile, int lane, f32x4 &re, f32x4 &im)
-{
-    const f16x8 (&Ah)[4] = t.h, (&Al)[4] = t.l;
-    const int w0 = 256 * tile + 16 * (lane & 15) + 8 * (lane >> 4);
-    f32x4 a[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) a[k] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f };
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-        const f16x8 brh = *(const f16x8 *)&pl->rh[w0 + 32 * ks], brl = *(const f16x8 *)&pl->rl[w0 + 32 * ks];
-        const f16x8 bih = *(const f16x8 *)&pl->ih[w0 + 32 * ks], bil = *(const f16x8 *)&pl->il[w0 + 32 * ks];
-        a[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[ks], brh, a[0], 0, 0, 0);
-        a[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], brl, a[1], 0, 0, 0);
-        a[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], brh, a[2], 0, 0, 0);
-        a[3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[ks], bih, a[3], 0, 0, 0);
-        a[4] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], bil, a[4], 0, 0, 0);
-        a[5] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], bih, a[5], 0, 0, 0);
-    }
-    re = (a[0] + a[1]) + a[2]; im = (a[3] + a[4]) + a[5];
-}
-
-// baseband sample q of the invocation (x[q] times the phase of its block), q >= -102: the filter memory a stream needs when it leaves the grid or
-// the launch ends; negative q reaches into the memory the invocation started with
-__device__ __forceinline__ float2 rx2_bpf_mem(const rd_sync_args &a, int b, int nin0, int q)
-{
-    const rd_rx_stream *st = a.st + b;
-    if (q < 0) return make_float2(st->bpf.mem[102 + q][0], st->bpf.mem[102 + q][1]);
-    const float2 *x = (const float2 *)a.rx + (size_t)b * a.rx_stride;
-    const float2 *chain = (const float2 *)a.bpf_chain + (size_t)b * a.chain_stride;
-    const int k = q < nin0 ? 0 : 1 + (q - nin0) / RD_NMF, sk = k ? nin0 + (k - 1) * RD_NMF : 0;
-    return cmul_nc(x[q], cmul_nc(chain[1 + k], ld2(a.tab->bpf_E, q - sk)));
-}
-
-// One call's filtering by the stream's own workgroup (off the grid): the pre-pass's arithmetic on the stream's actual call.  Cold path; the filter
-// memory lives in the stream record between calls.
-__device__ __forceinline__ void rx2_bpf_own(RxShared2 *sh, const rd_sync_args &a, int b, float2 *rxf, int cons0, int nin, int calls0)
-{
-    static_assert(sizeof(BpfLds) <= sizeof(sh->xm), "the planes overlay the xm work area");
-    RxScalars *S = &sh->S;
-    rd_rx_stream *st = a.st + b;
-    const rd_tables *tab = a.tab;
-    const float2 *x = (const float2 *)a.rx + (size_t)b * a.rx_stride;
-    const int tid = rx_tid();
-    const bool leaving = S->bpf_grid != 0;     // leaving the grid at this call: memory = the 102 baseband samples before it, phase = the chain's value at this block boundary
-    const float2 ph = leaving ? ((const float2 *)a.bpf_chain)[(size_t)b * a.chain_stride + 1 + calls0] : S->bpf_phase;
-    const int nin0 = S->nin0;
-    BpfLds *pl = (BpfLds *)&sh->xm[0];
-    const int wave = tid >> 6, lane = tid & 63;
-    BpfTaps taps; bpf_load_taps(taps, a.bpf16, lane);
-    auto mixed = [&](int j) { return cmul_nc(x[cons0 + j], cmul_nc(ph, ld2(tab->bpf_E, j))); };       // baseband sample j of this call
-    float2 head = make_float2(0.0f, 0.0f), body[BPF_NQ];
-    if (tid < 102) head = leaving ? rx2_bpf_mem(a, b, nin0, cons0 - 102 + tid) : make_float2(st->bpf.mem[tid][0], st->bpf.mem[tid][1]);
-#pragma unroll
-    for (int q = 0; q < BPF_NQ; q++) { const int j = tid + 256 * q; body[q] = mixed(min(j, nin - 1)); if (j >= nin) body[q] = make_float2(0.0f, 0.0f); }
-    const float2 memv = mixed(nin - 102 + min(tid, 101));      // new memory = the last 102 of [memory | new] (nin >= 800: all of them new samples)
-    const float unsc = bpf_stage_planes(pl, (unsigned *)&sh->redi[14], tid, head, body, 0);
-    // The outputs go to the stream's slice of the pre-pass buffer (what rade_batch_rx_filtered shows) AND, through LDS, to the caller: the caller's threads
-    // read samples other lanes produced, and a plain global load may hit the vector L1 line the previous call's first-touch loads left there (stale
-    // pre-pass values) -- stores go through to L2 without refreshing it.  xm is free once every wavefront is done with the planes.
-    f32x4 re[2], im[2];
-    for (int u = 0; u < 2; u++) { const int tile = wave + (NT2 / 64) * u; if (tile < BPF_TILES(nin)) bpf_fir_tile(pl, taps, tile, lane, re[u], im[u]); }
-    __syncthreads();
-    for (int u = 0; u < 2; u++) {
-        const int tile = wave + (NT2 / 64) * u;
-        if (tile >= BPF_TILES(nin)) continue;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int i = 256 * tile + 16 * (lane & 15) + 4 * (lane >> 4) + r;
-            if (i < nin) { const float2 y = cmul_nc(make_float2(re[u][r] * unsc, im[u][r] * unsc), cconj(cmul_nc(ph, ld2(tab->bpf_E, i)))); rxf[cons0 + i] = y; sh->xm[i] = y; }
-        }
-    }
-    __syncthreads();
-    if (tid < 102) { st->bpf.mem[tid][0] = memv.x; st->bpf.mem[tid][1] = memv.y; }
-    if (tid == 0) { S->bpf_phase = cmul_nc(ph, ld2(tab->bpf_E, nin - 1)); S->bpf_grid = 0; }
-    __syncthreads();
-}
-
-template <int CTRL> __device__ __forceinline__ float dpp_f32(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true)); }
-#define DPP_ROW_HALF_MIRROR 0x141   /* lane i <-> 7 - i inside every group of eight lanes */
+#include "rade_rx_check.h"
+#include "rade_bpf.h"
 
 #ifndef RX2_WG_PER_CU
 #define RX2_WG_PER_CU 2          /* developer switch: the register budget of a build that would hold three workgroups per CU (168 VGPRs) */
@@ -1384,8 +256,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
         };
         if (it == 0) {
             if (tid == 0) prepare_next();
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
         }
         PH2(1);
         if (S->need_decode) { if (a.bypass_dec) rx2_bypass_pending(sh, a, b); else rx2_decode_pending(sh, a, b); PH2(2); }
@@ -1425,7 +296,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
             S->n_calls = nc + 1; S->calls_inv++;
         };
         const int cons0 = S->consumed_inv, calls0 = S->calls_inv;
-        // ---- complex_bpf.bpf (dsp.py:63-102) ran ahead of this kernel for every sample of the invocation (k_rx_bpf): the filter does not depend on
+        // ---- complex_bpf.bpf (dsp.py:63-102) ran ahead of this kernel for every sample of the invocation (k_bpf_fir): the filter does not depend on
         // any sync decision.  This call's nin filtered samples are rxf[cons0 ..) as long as the stream's calls follow the pre-pass's block grid (first
         // block = the nin the invocation started with, then Nmf each: the reference's own call partition unless nin changes inside an invocation);
         // after such a timing slip the stream filters the rest of the invocation's samples itself (rx2_bpf_own: same arithmetic, cold path).
@@ -1458,8 +329,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
 #pragma unroll
         for (int q = 0; q < NNEW; q++) mloc = fmaxf(mloc, fmaxf(fabsf(nv[q].x), fabsf(nv[q].y)));
         mloc = wave_max_f32(mloc);
-        __syncthreads();
-        tid = rx2_tid(wv);
+        RX2_SYNC();
 #pragma unroll
         for (int q = 0; q < NK; q++) { const int i = tid + q * NT2; if (i + nin < RD_RXBUF) sh->rxb[i] = keep[q]; }
 #pragma unroll
@@ -1469,8 +339,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
             if (state == ST_SYNC) S->lds_sync = 1;
             S->consumed_inv += nin; S->consumed_round += nin;
         }
-        __syncthreads();
-        tid = rx2_tid(wv);
+        RX2_SYNC();
 
         PH2(5);
         if (state == ST_SEARCH || state == ST_CANDIDATE) {
@@ -1488,22 +357,13 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
 #pragma unroll
                 for (int q = 0; q < NR; q++) sh->rowsum1[min(tid + q * NT2, RD_NMF - 1)] = r2[q];   // each thread moves its own slots: no barrier in between
             }
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
             PH2(6);
-            float rx_unsc;
-            {   // operand planes of the whole rx_buf (as for check_pilots in the synchronised state: one power-of-two scale from the running maximum)
-                const unsigned mb = max(max(S->rxmax_cur, S->rxmax_h0), S->rxmax_h1);
-                const int eb = min(max((int)((mb >> 23) & 0xffu), 32), 222);
-                const float rx_sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);
-                rx_unsc = __uint_as_float((unsigned)(127 - 12 - 7 + (eb - 127)) << 23);
-                for (int i = tid; i < RD_RXBUF; i += NT2) {
-                    float2 v = sh->rxb[i]; v.x *= rx_sc; v.y *= rx_sc;
-                    const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y;
-                    const _Float16 l0 = (_Float16)(v.x - (float)h0), l1 = (_Float16)(v.y - (float)h1);
-                    sh->srxh[i] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-                    sh->srxl[i] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-                }
+            float rx_sc, rx_unsc;
+            rx2_operand_scale(S, rx_sc, rx_unsc);
+            for (int i = tid; i < RD_RXBUF; i += NT2) {      // operand planes of the whole rx_buf (as for check_pilots in the synchronised state)
+                float2 v = sh->rxb[i]; v.x *= rx_sc; v.y *= rx_sc;
+                rx2_split16(v, sh->srxh[i], sh->srxl[i]);
             }
             if (CENSUS(512)) { float b_ = -1.0f; int t_ = 0x7fffffff, f_ = 0; rx2_detect_q(sh, a.corrq16, a.corra16, cache, cached ? 1 : 0, oldb, newb, rx_unsc, b_, t_, f_); asm volatile("" :: "v"(b_), "v"(t_), "v"(f_)); }
             rx2_detect_q(sh, a.corrq16, a.corra16, cache, cached ? 1 : 0, oldb, newb, rx_unsc, best, bt, bfi);
@@ -1518,8 +378,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                 S->candidate = S->Dtmax12 > S->Dthresh;
                 S->entry = S->candidate && (abs(S->tmax - S->tmax_candidate) < RD_NCP) && (S->valid_count + 1 > 3);
             }
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
         } else {
             // ---- in sync: refine, check_pilots, slips, UW, frequency correction, demod
             int tm_ref; double fm_ref;
@@ -1527,11 +386,10 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                 const int tm = S->tmax; const double fm = S->fmax;
                 const int t0 = max(0, tm - 8);
                 int tnew = tm; double fhat = fm;
-                {   // check_pilots' operand planes of the whole rx_buf (see k_rx_sync)
-                    const unsigned mb = max(max(S->rxmax_cur, S->rxmax_h0), S->rxmax_h1);
-                    const int eb = min(max((int)((mb >> 23) & 0xffu), 32), 222);
-                    const float rx_sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);
-                    if (tid == 0) sh->redf[12] = __uint_as_float((unsigned)(127 - 12 - 7 + (eb - 127)) << 23);
+                {   // check_pilots' operand planes of the whole rx_buf
+                    float rx_sc, rx_unsc;
+                    rx2_operand_scale(S, rx_sc, rx_unsc);
+                    if (tid == 0) sh->rx_unsc = rx_unsc;
                     if (tid >= NT2 - 64) {
                         // side jobs of the call on the fourth wavefront (they only depend on last call's results): the per-frequency constants of
                         // refine()'s grid, check_pilots' 48 row draws, and the first touch of the NEXT call's filtered samples (HBM + address translation:
@@ -1541,7 +399,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                         const int k = min(l, 47);
                         const uint32_t x = LCG_A[k] * S->lcg + LCG_C[k];
                         if (l < 48) sh->rows48[k] = (int)((x >> 8) % RD_NMF);
-                        if (l == 47) sh->redi[15] = (int)x;
+                        if (l == 47) sh->lcg_next = (int)x;
                         const int rem = min(avail - cons0 - nin, RD_NINMAX);
                         float t = 0.0f;
 #pragma unroll
@@ -1552,16 +410,14 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                     for (int i = tid; i < RD_RXBUF; i += NT2 - 64) {
                         asm volatile("" ::: "memory");
                         float2 v = sh->rxb[i]; v.x *= rx_sc; v.y *= rx_sc;
-                        const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y;
-                        const _Float16 l0 = (_Float16)(v.x - (float)h0), l1 = (_Float16)(v.y - (float)h1);
-                        sh->rxhl[i] = (u32x2){ (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16),
-                                               (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16) };
+                        unsigned hi, lo; rx2_split16(v, hi, lo);
+                        sh->rxhl[i] = (u32x2){ hi, lo };
                     }
                 }
                 if (CENSUS(16)) { int t_ = tm; double f_ = fm; rx2_refine(sh, a.vm, &t_, &f_, t0, tm + 8 - t0, fm - 1.0, fm + 1.0, 0.1, true); __syncthreads(); }
                 rx2_refine(sh, a.vm, &tnew, &fhat, t0, tm + 8 - t0, fm - 1.0, fm + 1.0, 0.1, true);
                 tm_ref = tnew; fm_ref = dlin2_nc(0.9, fm, 0.1, fhat);                  // radae_rxe.py:206, rounded like the reference's doubles (rade_devutil.h)
-                if (tid == 0) { S->tmax = tm_ref; S->fmax = fm_ref; S->lcg = (uint32_t)sh->redi[15]; }
+                if (tid == 0) { S->tmax = tm_ref; S->fmax = fm_ref; S->lcg = (uint32_t)sh->lcg_next; }
             }
             PH2(9);
             // check_pilots (dsp.py:273-320): 48 pseudo-random rows x {Dt1, Dt2} x 40 frequencies on the f16 matrix cores, one
@@ -1569,7 +425,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
             // (tmax, fmax) and the frequency-corrected window the demodulator reads
             {
                 const int wave = tid >> 6, lane = tid & 63;
-                const float rx_unsc = sh->redf[12];
+                const float rx_unsc = sh->rx_unsc;
                 // wavefronts 0 / 1: frame 0 / 1, row tiles 0 and 1; wavefronts 2 / 3: frame 0 / 1, row tile 2, and everything else of the phase -- the four correlations at
                 // (tmax, fmax) behind the first table requests, one slice of the frequency-corrected window behind the matrix instructions of every k-step
                 const int tm = tm_ref; const double w = 2.0 * PI_D * fm_ref / 8000.0;
@@ -1620,10 +476,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                     const int n = 128 * sl + (tid - 128);
                     float2 v = cmul(sh->rxb[t2 - RD_NCP + n], cmul(cA[n >> 6], cB[n & 63]));
                     v.x *= dx_sc; v.y *= dx_sc;
-                    const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y;
-                    const _Float16 l0 = (_Float16)(v.x - (float)h0), l1 = (_Float16)(v.y - (float)h1);
-                    dxh[n + (n >> 5)] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-                    dxl[n + (n >> 5)] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
+                    rx2_split16(v, dxh[n + (n >> 5)], dxl[n + (n >> 5)]);
                 };
                 for (int rep = CENSUS_REPS(32); rep > 0; rep--) {
                     asm volatile("" ::: "memory");
@@ -1633,8 +486,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                 PH2(8);
             }
             PH2(11);
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
             PH2(10);
             // From here to the equaliser ONE phase: the fourth wavefront reduces the row sums to the Rayleigh thresholds, decides candidate /
             // end-of-over / slip, runs the state machine and advances the phase accumulator; the other three run the demodulator DFT
@@ -1679,7 +531,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                 const int sc_ = col < 6 ? col : min(col - 6, 5);
                 const unsigned im_var = col >= 6 ? 0xffffffffu : 0u;       // columns 6..11 (and the unused 12..15): the (im, -re) variant
                 const unsigned *dxh = (const unsigned *)sh->xm, *dxl = dxh + 1200;
-                const float unsc = sh->redf[12];
+                const float unsc = sh->rx_unsc;
                 static_assert(RD_NCP - 16 == 16 && RD_SYM == 192, "padded window index");
                 for (int rep = CENSUS_REPS(256); rep > 0; rep--)
                 if (wave < 2) {
@@ -1724,8 +576,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                 }
             }
             PH2(25);
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
             PH2(12);
             const int endofover = S->endofover, n_rows = n_rows0;
             float *zrow = a.zrows + ((size_t)b * a.dec_rows + n_rows) * RD_LATENT;
@@ -1746,8 +597,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                     }
                     sh->rp[i][c] = cadd(g0, cmul(g1, sh->eqrot[c]));
                 }
-                __syncthreads();
-                tid = rx2_tid(wv);
+                RX2_SYNC();
                 if (tid < 128) {
                     const int c = tid & 63;
                     if (tid < 64) {
@@ -1781,8 +631,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                         }
                     }
                 }
-                __syncthreads();
-                tid = rx2_tid(wv);
+                RX2_SYNC();
                 const float mag = S->mag;
                 if (tid < RD_NS * RD_NC) {
                     const int k = 1 + tid / RD_NC, c = tid % RD_NC;
@@ -1805,8 +654,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                     if (a.trace_z && call_idx0 < a.trace_cap) { float *tz = a.trace_z + ((size_t)b * a.trace_cap + call_idx0) * RD_ZMF; tz[2 * tid] = v.x; tz[2 * tid + 1] = v.y; }
                 }
             }
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
         }
 
         PH2(13);
@@ -1819,8 +667,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
             for (int i = tid; i < RD_M; i += NT2) sh->pd[i] = make_double2(tab->p[i][0], tab->p[i][1]);    // the FFT area is dead: pilot replica for the direct sums
             rx2_refine(sh, a.vm, &tnew, &fnew, t0, tm + 2 - t0, fm - 10.0, fm + 10.0, 0.25, false);
             if (tid == 0) { S->tmax = tnew; S->fmax = fnew + S->foff_err; S->foff_err = 0.0; }
-            __syncthreads();
-            tid = rx2_tid(wv);
+            RX2_SYNC();
         }
         if (tid == 0 && state != ST_SYNC) state_update(do_entry, S->valid_output, S->endofover);
         if (tid == 0 && a.trace) {
@@ -1833,8 +680,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
             }
         }
         if (tid == 0) prepare_next();
-        __syncthreads();
-        tid = rx2_tid(wv);
+        RX2_SYNC();
         PH2(14);
     }
 
@@ -1868,7 +714,6 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
     }
 }
 
-
 // start-of-utterance state of stream blockIdx.x in one launch: the receiver record (radae_rxe.py:128-142), the decoder's / encoder's GRU states and conv
 // history rows -- whichever are given.  (Rounds 1-4 issued a kernel + two memsets + two 2-D memsets per reset: five launches of a batch's stream, each of which
 // waits for a free slot beside the other batches' receiver workgroups.)
@@ -1901,10 +746,6 @@ extern "C" int rd_launch_reset(const rd_reset_args *a, rd_stream_t s)
     return (int)hipGetLastError();
 }
 
-
-__device__ __forceinline__ rd_bpf_state *bpf_state_of(const rd_bpf_args &a, int b) { return (rd_bpf_state *)((char *)a.state + (size_t)b * a.state_stride); }
-__device__ __forceinline__ int bpf_len0_of(const rd_bpf_args &a, int b) { return a.len0 ? *(const int *)((const char *)a.len0 + (size_t)b * a.len0_stride) : a.len0_const; }
-__device__ __forceinline__ int bpf_avail_of(const rd_bpf_args &a, int b) { return a.avail ? a.avail[b] : a.avail_const; }
 // the block phases of an invocation, one thread per stream: P[0] = the phase the stream's last call left, P[k + 1] = P[k] E[len_k - 1] in complex64
 // as complex_bpf does from call to call; also resets the stream's off-grid flag (a new invocation starts on the grid)
 __global__ __launch_bounds__(64) void k_bpf_chain(rd_bpf_args a)
@@ -1932,12 +773,6 @@ __global__ __launch_bounds__(64) void k_bpf_chain(rd_bpf_args a)
         P = cmul_nc(P, k ? e1 : e0);
         start += k ? RD_NMF : nin0;
     }
-}
-// baseband sample q >= 0 of an invocation: x[q] times the phase of its block
-__device__ __forceinline__ float2 bpf_baseband(const float2 *x, const float2 *chain, const rd_tables *tab, int nin0, int q)
-{
-    const int k = q < nin0 ? 0 : 1 + (q - nin0) / RD_NMF, sk = k ? nin0 + (k - 1) * RD_NMF : 0;
-    return cmul_nc(x[q], cmul_nc(chain[1 + k], ld2(tab->bpf_E, q - sk)));
 }
 // after a whole invocation was filtered and consumed (the transmit side: every sample is): the state complex_bpf would hold now (dsp.py:96-99)
 __global__ __launch_bounds__(128) void k_bpf_advance(rd_bpf_args a)

@@ -5,7 +5,7 @@ At a control-flow join the compiler re-enables the lanes that skipped the branch
 When a VGPR spill (`scratch_store`) or reload (`scratch_load`) is placed in that join block *ahead of* the
 `s_or_b64`, it runs with the lanes of the skipped branch still disabled -- with EXEC = 0 when the whole wavefront
 branched around (`s_cbranch_execz`).  The slot then keeps stale data and the later full-EXEC reload hands garbage to
-every lane.  In k_rx_sync this silently corrupted a long-lived f64 polynomial coefficient of sincos() (frequency
+every lane.  In the retired round-3 receiver kernel this silently corrupted a long-lived f64 polynomial coefficient of sincos() (frequency
 estimates off by 0.01 Hz) in builds that differed from the good one only by an unrelated reduction helper.
 
 This script disassembles the gfx950 code objects embedded in a built object / shared library and reports every basic

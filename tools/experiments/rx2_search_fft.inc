@@ -175,7 +175,7 @@ __device__ __forceinline__ void rx2_detect_fft(RxShared2 *sh, const float *G_, c
 
 
 #if 0   /* host side (was rade_host.c): the pilot spectra G[f][k] and the transform twiddles */
-/* Tables of the FFT pilot correlator (k_rx_sync, search state).  Dt[t,f] = sum_m conj(rx[t+m]) p_w[m,f]
+/* Tables of the FFT pilot correlator (the retired round-3 kernel, search state).  Dt[t,f] = sum_m conj(rx[t+m]) p_w[m,f]
  * (dsp.py:207-208) is a correlation along t, so |Dt[.,f]| = |IDFT_2048(DFT_2048(rx) . G_f)| with
  * G_f[k] = (1/2048) sum_m conj(p_w[m,f]) e^{+j 2 pi k m/2048}, evaluated here in double from the float32 p_w the
  * reference correlates with.  tw[q][l] = e^{-j 2 pi l q/2048} is the twiddle between the two radix passes. */

@@ -3,7 +3,7 @@
 // LDS: _Float16 sA[2][5 * 2 * 64 * 8] (one k-step of the table, double-buffered).
 // ---- |Dt| surfaces on the matrix cores ----------------------------------------------------------------------------------------------
 // acquisition.detect_pilots (dsp.py:178-231): Dt[t, f] = sum_m conj(rx[t + m]) p_w[m, f] for all 960 timings x 40 frequencies of a frame.
-// k_rx_sync does this by FFT convolution on the vector ALU (one 2048-point inverse transform per frequency): 52 % of ALL vector
+// The retired round-3 kernel did this by FFT convolution on the vector ALU (one 2048-point inverse transform per frequency): 52 % of ALL vector
 // instructions of a k_rx_sync2 launch on the bench workload although only one call in eight is in the search state (tools/rx2_census.sh),
 // and with two workgroups per CU the vector ALU is the shared resource.  Here the same sums are the real GEMM check_pilots already runs
 // for its 48 rows -- [80 = (f, re | im)] x [320 = (m, re | im)] times the Toeplitz matrix rx[t + m] -- on v_mfma_f32_16x16x32_f16 with both

@@ -20,7 +20,7 @@ for B in (256, 512):
     for n in ("ic", "wt", "ld", "in"):
         f = glob.glob("$O/%s_%d/**/*counter_collection.csv" % (n, B), recursive=True)
         if not f: continue
-        rows = [r for r in csv.DictReader(open(f[0])) if "k_rx_sync" in r["Kernel_Name"]]
+        rows = [r for r in csv.DictReader(open(f[0])) if "k_rx_sync2" in r["Kernel_Name"]]
         names = set(r["Counter_Name"] for r in rows)
         for c in names:
             v = [float(r["Counter_Value"]) for r in rows if r["Counter_Name"] == c]
