@@ -661,3 +661,112 @@ def test_band_checker_reports_every_planted_fault():
     with pytest.raises(AssertionError):
         bd, wr = clean(); bd.untouched()
     Band(3, 7, 11, 8).untouched()
+
+
+# ---- host halves of the kernel unit tests (tests/kernel_ref.py, tests/test_kernel_units_gpu.py) ----------------------------------------------------------------
+@pytest.mark.parametrize("K", [16, 80, 864])
+@pytest.mark.parametrize("N", [32, 80, 96])
+def test_f16_weight_packers_recover_the_matrix(lib, N, K):
+    """rd_pack_weights_f16x2 and rd_pack_weights_q16, decoded by the layout of rade_host.h and by the way k_gemm16 indexes it (lane = column, 8 k per lane):
+    W comes back exactly on the exact grids, to 2^-22 relative on random weights, columns N.. of a ragged tile are zero."""
+    import kernel_ref as kr
+    kr.declare(lib)
+    rng = np.random.default_rng(100 * N + K)
+    for bits in (12, 3):                                           # the weights of the "w12" and "a12" grids
+        W = (rng.integers(1 - 2 ** bits, 2 ** bits, (N, K)) * 2.0 ** -bits).astype(np.float32)
+        hi, lo = kr.unpack16(kr.pack_f16x2(lib, W), N, K, 2)
+        assert np.array_equal((hi[:N] + lo[:N]) * np.float32(2.0 ** -10), W) and not hi[N:].any() and not lo[N:].any()
+        assert lo[:N].any() == (bits == 12), "the 12-bit grid, and only it, uses the low plane"
+    W = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    hi, lo = kr.unpack16(kr.pack_f16x2(lib, W), N, K, 2)
+    back = (hi[:N].astype(np.float64) + lo[:N]) * 2.0 ** -10
+    # 2^-22 relative wherever the low plane is a normal binary16 (11 bits after the high plane's 11); a remainder below 2^-14 is a subnormal low plane with the
+    # absolute step 2^-24, i.e. at most 2^-25 / 2^10 = 2^-35 on the weight, whatever its size
+    err, normal = np.abs(back - W), np.abs(np.float32(1024) * W - hi[:N]) >= 2.0 ** -14
+    assert normal.mean() > 0.9 and np.all(err[normal] <= 2.0 ** -22 * np.abs(W[normal])) and np.all(err[~normal] <= 2.0 ** -35)
+    assert np.array_equal(hi[:N], (np.float32(1024) * W).astype(np.float16).astype(np.float32))       # the high plane is the nearest binary16
+    _, W, scale, _ = kr.exact_gemm_operands(rng, 1, K, N, "int8")
+    plane, sc = kr.pack_q16(lib, W, scale)
+    q = kr.unpack16(plane, N, K, 1)[0]
+    assert np.array_equal(q[:N] * scale[:, None], W) and not q[N:].any()
+    assert np.array_equal(sc[:N], scale) and not sc[N:].any()
+    _, W, scale, _ = kr.random_gemm_operands(rng, 1, K, N, int8=True)
+    plane, sc = kr.pack_q16(lib, W, scale)
+    q = kr.unpack16(plane, N, K, 1)[0]
+    assert np.abs(q).max() == 127 and np.array_equal(q[:N] * scale[:, None], W)
+    bad = W.copy(); bad[N - 1, K - 1] += scale[N - 1] / 2
+    assert kr.pack_q16(lib, bad, scale) is None                      # not q * scale with an integer q
+
+
+def test_fragment_codec_round_trips():
+    """tests/kernel_ref.py's codec of the operand-fragment layout: put / get are inverse, history rows land in rows 30, 31 of tile 0, offsets are unique,
+    the documented positions of rade_dev.h hold for hand-computed elements, and nothing else is written."""
+    import kernel_ref as kr
+    rng = np.random.default_rng(5)
+    B, T, col0, nc = 2, 37, 64, 96
+    steps = np.arange(-2, T)
+    x = rng.uniform(-1, 1, (B, len(steps), nc)).astype(np.float32)
+    buf = kr.frag_new(B, 3); before = buf.copy()
+    idx = kr.frag_put(buf, steps, col0, x)
+    assert len(np.unique(np.concatenate([idx.ravel(), idx.ravel() + 512]))) == 2 * idx.size and idx.max() + 512 < 3 * kr.EF_TILE
+    hi, lo = kr.frag_get(buf, steps, col0, nc)
+    assert np.array_equal(hi, kr.split16(x)[0]) and np.array_equal(lo, kr.split16(x)[1])
+    assert np.all(np.abs(kr.join16(hi, lo).astype(np.float64) - x) <= 2.0 ** -22 * np.abs(x) + 2.0 ** -33)     # 22 bits, or the low plane's subnormal step 2^-24 / 2^8 / 2
+    assert np.array_equal(kr.split16(kr.join16(hi, lo))[0], hi) and np.array_equal(kr.split16(kr.join16(hi, lo))[1], lo)     # splitting the joined value again gives the planes back
+    kr.frag_untouched_except(buf, before, [idx], "codec")
+    with pytest.raises(AssertionError, match="stream 1 at tile 2, offset 7"):
+        buf[1, 2, 7] = 0; kr.frag_untouched_except(buf, before, [idx], "codec")
+    # step 33, column 77 = 64 + 13: tile 2, k-block 4, k-half 1, row 1, element 5; step -1: tile 0 row 31
+    assert idx[2 + 33, 13] == 2 * kr.EF_TILE + 4 * 1024 + 256 + 1 * 8 + 5 and idx[1, 0] == 4 * 1024 + 31 * 8 and idx[0, 0] == 4 * 1024 + 30 * 8
+
+
+@pytest.mark.parametrize("grid,K", [("int8", 1728), ("int8", 128), ("w12", 320), ("a12", 320)])
+def test_exact_grid_sums_do_not_depend_on_the_order(grid, K):
+    """The exact-grid generator's own invariant: float32 accumulation of the products -- the planes' partial products of the binary16 kernels included -- gives
+    identical bits in a few hundred random orders, sequential and as eight partial sums (the split-K kernel), and equals the float64 reference."""
+    import kernel_ref as kr
+    rng = np.random.default_rng(K)
+    a, W, scale, bias = kr.exact_gemm_operands(rng, 2, K, 3, grid)
+    y64, _ = kr.gemm_ref(a, W, bias)
+    want = y64.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), y64)
+    ah, al = (p.view(np.float16).astype(np.float32) for p in kr.split16(a))
+    assert np.array_equal((ah + al) * np.float32(2.0 ** -8), a)
+    wh = (np.float32(1024) * W).astype(np.float16).astype(np.float32); wl = np.float32(1024) * W - wh
+    assert np.array_equal(wl.astype(np.float16).astype(np.float32), wl) and (grid != "w12" or wl.any()) and (grid != "a12" or al.any())
+    for r in range(2):
+        for n in range(3):
+            terms = np.concatenate([al[r] * wh[n], ah[r] * wl[n], ah[r] * wh[n]])                   # lo x W, hi x Wlo, hi x W; lo x lo is zero on these grids
+            assert not (al[r] * wl[n]).any()
+            for terms_, post in ((a[r] * W[n], np.float32(1)), (terms, np.float32(2.0 ** -18))):
+                perm = np.argsort(rng.random((200, terms_.size)), axis=1)
+                seq = np.cumsum(terms_[perm], axis=1, dtype=np.float32)[:, -1]
+                part = terms_[perm][:, :terms_.size // 8 * 8].reshape(200, 8, -1).cumsum(axis=2, dtype=np.float32)[:, :, -1]
+                rest = terms_[perm][:, terms_.size // 8 * 8:].sum(axis=1, dtype=np.float32)
+                split = part.cumsum(axis=1, dtype=np.float32)[:, -1] + rest
+                for got in (seq, split):
+                    assert np.all((got * post + bias[n]).view(np.int32) == want[r, n].view(np.int32))
+    with pytest.raises(AssertionError):
+        kr.exact_gemm_operands(rng, 2, 1024, 3, "w12")               # 1024 x 7 x 4095 leaves the range: refused on the host
+
+
+def test_float64_gru_step_matches_torch_grucell():
+    import torch
+    import kernel_ref as kr
+    torch.manual_seed(0)
+    for H in (64, 96):
+        cell = torch.nn.GRUCell(40, H).double()
+        x, h = torch.randn(5, 40, dtype=torch.float64), torch.rand(5, H, dtype=torch.float64) * 2 - 1
+        with torch.no_grad():
+            want = cell(x, h).numpy()
+            gi = (x @ cell.weight_ih.T + cell.bias_ih).numpy()
+            got, bound = kr.gru_step64(gi, cell.weight_hh.numpy(), cell.bias_hh.numpy(), h.numpy(), kr.EPS_SIG_HW, kr.EPS_TANH_HW)
+        assert np.abs(got - want).max() < 1e-14
+        # the bound is first-order: a float32 evaluation of the same step lies well inside it, and it stays at (2 H + 16) roundings of sums of order 1
+        f = [v.astype(np.float32) for v in (gi, cell.weight_hh.detach().numpy(), cell.bias_hh.detach().numpy(), h.numpy())]
+        s = f[3] @ f[1].T
+        r = 1 / (1 + np.exp(-((s[:, :H] + f[2][:H]) + f[0][:, :H]))); z = 1 / (1 + np.exp(-((s[:, H:2 * H] + f[2][H:2 * H]) + f[0][:, H:2 * H])))
+        n = np.tanh(f[0][:, 2 * H:] + (s[:, 2 * H:] + f[2][2 * H:]) * r)
+        h32 = (f[3] - n) * z + n
+        ref32, b32 = kr.gru_step64(*f)
+        assert np.all(np.abs(h32 - ref32) <= b32 + 4 * kr.U) and bound.max() < 5e-5
