@@ -18,6 +18,8 @@
  *   rade_batch_rx          radae_rxe.py:171-330 (do_radae_rx) looped like radae_rxe.py:349-356 /
  *                          src/radae_rx.c:42-53, incl. rade_api.c:480-513 decoder + UW accounting
  *   rade_batch_rx_ideal    radae.py:312-420, :590-657 (the ideal-timing receiver of RADAE.forward / RADAE.receiver, ber_test)
+ *   rade_batch_channel_rs_pa  radae.py:603-634 with bottleneck 3 (the rate-Rs "hybrid time & frequency domain" channel: IDFT, PA limiter, DFT, |H|, AWGN) +
+ *                          inference.py:213-229 (its Eq / PAPR measurements)
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -90,6 +92,9 @@ int rade_batch_n_streams(const rade_batch *h);
  *   rade_batch_channel(_streams)            tx_dev (complex64; tx_stride >= n_sig), G_dev [B][n_sig][2], noise_dev [B][n_total] (complex64; dense) in; rx_out_dev (complex64; rx_stride >= n_total)
  *   rade_batch_tx_channel(_streams)         as the two above; iq_out_dev optional with G_dev (16 B)
  *   rade_batch_channel_symbol               z_dev, H_dev, noise_dev in, z_hat_dev out (float; dense)
+ *   rade_batch_channel_rs_pa                z_dev [B][n_steps][80], H_dev [B][2 n_steps][20] (float; dense), noise_dev [B][2 n_steps][20] (complex64; dense) in; z_hat_dev
+ *                                           [B][n_steps][80] (float; dense).  Element alignment suffices for all four (the kernel reads and writes z, H, z_hat by float,
+ *                                           noise by complex64); a pointer that is not even that returns -1 before any launch
  *   rade_batch_multipath_gen / _h           noise_low_dev, G_dev in (complex64; dense); G_out_dev (complex64 [B][n_out][2], n_out >= 1; one sample has no variance to
  *                                           normalise by: n_out = 1 writes its two values, not finite), H_out_dev (float; dense)
  *   rade_batch_rx                           rx_dev (complex64; rx_stride >= every n_avail) in; features_out_dev (float; feat_stride >= 432 or 240, capacity = the floor of
@@ -135,6 +140,25 @@ int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *fea
  * or NULL, p0 = CNRdB, p1 = Gfm dB).  noise_dev: [B][n_steps*80] float32 (already scaled per component) or NULL -> Philox(seed) */
 int rade_batch_channel_symbol(rade_batch *h, const float *z_dev, const float *H_dev, const float *noise_dev, float *z_hat_dev, int n_steps,
                               int mode, float p0, float p1, unsigned long long seed, void *stream);
+
+/* The rate-Rs channel of the bottleneck-3 model, RADAE.forward without rate_Fs (radae.py:603-634; what model19 was trained under, and what inference.py runs without
+ * --rate_Fs).  Numerology of RADAE(..., bottleneck = 3) without pilots or cyclic prefix: Nc = 20 carriers at DFT bins 20..39, M = 160, Ns = 6 (the pilot numerology
+ * does not run in the reference without rate_Fs and is not offered).  Latent row r of a stream (80 floats) is 40 QPSK symbols q[k] = z[2k] + j z[2k+1]; OFDM symbol
+ * s = 2r + (k >= 20) takes carriers c = k mod 20, i.e. symbol s is floats [40 s, 40 s + 40) of the stream.  Per symbol:
+ *     tx[m]  = (1/160) sum_c sym[c] e^{+j m w_c}, w_c = 2 pi (20 + c) / 160          tx'[m] = tanh(|tx[m]|) tx[m] / |tx[m]|   (0 -> exactly 0; any finite tx, however large -> magnitude 1)
+ *     Y[c]   = sum_m tx'[m] e^{-j m w_c}                                             Y[c]  *= e^{j phase_offset} H[b][s][c]   (H real magnitudes; NULL = 1)
+ *     R[c]   = Y[c] + sigma_b n[b][s][c]                                             z_hat[40 s + 2c], [40 s + 2c + 1] = Re R[c], Im R[c]
+ * noise_dev: complex, unit variance in total (1/2 per component, torch.randn_like of a complex tensor), or NULL: generated, Philox4x32-10 keyed by (seed, stream) with
+ *   one counter per pair of carriers (words 0-1 -> the even carrier, 2-3 -> the odd one), Box-Muller on the hardware units; seed 0 = no noise.  As for the rate-Fs
+ *   channel the generated sequence is a property of the BUILD; a stream's draw does not depend on B; anything comparable across builds passes noise_dev.
+ * sigma_streams_host: [B] or NULL = `sigma` for every stream.  Stream b gets what a call with the scalar set to its value gives it, bit for bit (the rule of
+ *   rade_channel_streams); the values are copied to the device ahead of the launch (the call synchronises `stream` once for that).
+ * stats_host: [B][3] doubles or NULL: sum |tx'|^2 and max |tx'| over the stream's 320 n_steps samples, sum |Y|^2 over its 40 n_steps symbols after phase and H -- what
+ *   inference.py:215-227 measures (Eq = sum |Y|^2 / (40 n_steps), S = sum |tx'|^2 / (320 n_steps), PAPR = max^2 / S).  Sums are doubles added in a fixed order (no atomics):
+ *   two identical calls give identical bits.  With stats_host the call synchronises `stream`.
+ * Any n_steps >= 1, any engine (the model is not used; no encoder or receiver state is touched).  Returns n_steps or < 0.  Noise level: rade_sigma_from_EbNodB_rs3. */
+int rade_batch_channel_rs_pa(rade_batch *h, const float *z_dev, const float *H_dev, const void *noise_dev, float *z_hat_dev, int n_steps, float sigma,
+                             const float *sigma_streams_host, float phase_offset, unsigned long long seed, double *stats_host, void *stream);
 
 /* ---- channel simulator ---------------------------------------------------------------------- */
 typedef struct {
@@ -194,6 +218,8 @@ int rade_batch_multipath_h(rade_batch *h, const void *G_dev, int n_g, int fs_ove
 float rade_sigma_from_EbNodB(float EbNodB);
 /* bottleneck 1 (radae.py:574-576): sigma = (EbNo M)^-0.5, M = 160 */
 float rade_sigma_from_EbNodB_bn1(float EbNodB);
+/* rate Rs, bottleneck 3 (radae.py:627-630): sigma = M / sqrt(2 Nc EbNo) / sqrt(2), M = 160, Nc = 20 (12.66 at 3 dB: the encoder drives |tx_sym| to about M / sqrt(Nc)) */
+float rade_sigma_from_EbNodB_rs3(float EbNodB);
 
 /* ---- receive --------------------------------------------------------------------------------
  * rx_dev + b*rx_stride points at the first sample stream b has NOT yet consumed; n_avail_host[b]

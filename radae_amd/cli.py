@@ -4,7 +4,8 @@
     python -m radae_amd.cli rxe [--bypass_dec] [--disable_unsync S] [--foff_err HZ] [--eoo_data_test] [--no_stdout] [-v N] [--model_name BLOB]
                                                                                                      IQ.f32 -> features.f32 (or z_hat.f32)  /root/reference/radae_rxe.py:332-371
 
-    python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --EbNodB .. [--g_file g.f32] --write_rx rx.f32 [...]    the channel-simulation run of inference.py (rate Fs)
+    python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --rate_Fs --EbNodB .. [--g_file g.f32] --write_rx rx.f32 [...]    the channel-simulation run of inference.py (rate Fs)
+    python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --bottleneck 3 --auxdata --EbNodB .. [--h_file h.f32] [--mp_test] [--phase_offset rad]          the same without --rate_Fs: the rate-Rs channel
     python -m radae_amd.cli multipath_samples mpp 8000 50 30 10 h.f32 g.f32                                                      multipath_samples.m
     python -m radae_amd.cli bbfm_inference MODEL features.f32 features_hat.f32 [--CNRdB ..] [--h_file h_lmr60.f32] [--write_latent z.f32]    bbfm_inference.py
 
@@ -109,7 +110,9 @@ def _inference(argv):
     The reference's ideal-timing receiver (radae.py:312-420, :590-657; rade_batch_rx_ideal) runs on the signal part of the channel output when asked for: `--ideal_rx` takes
     features_hat and the loss from it, honouring --pilot_eq / --eq_ls / --coarse_mag / --time_offset / --correct_freq_offset; `--ber_test` sends random +-1 latents instead
     of the encoder's and prints `n_bits: N BER: x.xxx` (radae.py:653-657); `--write_latent` writes its z_hat.  `--bottleneck 1` takes a bottleneck-1 blob (weights/model05.bin):
-    the linear rate-Fs waveform (RADE_BATCH_TX_LINEAR) at sigma = (EbNo M)^-0.5, received by the ideal-timing receiver (the streaming one is model19_check3's)."""
+    the linear rate-Fs waveform (RADE_BATCH_TX_LINEAR) at sigma = (EbNo M)^-0.5, received by the ideal-timing receiver (the streaming one is model19_check3's).
+
+    Without `--rate_Fs` and with `--bottleneck 3` the run is inference.py's rate-Rs one (_inference_rate_rs below): the channel model19 was trained under."""
     import torch
     from . import engine, wire
     from .loss import distortion_loss, find_loss
@@ -125,7 +128,14 @@ def _inference(argv):
         ap.add_argument(flag, action="store_true")
     ap.add_argument("--cp", type=float, default=0.004); ap.add_argument("--bottleneck", type=int, default=3); ap.add_argument("--time_offset", type=int, default=-16)
     ap.add_argument("--latent-dim", type=int, default=80)
+    ap.add_argument("--h_file", type=str, default="", help="rate-Rs run: per-carrier magnitudes, float32 [.][20]"); ap.add_argument("--mp_test", action="store_true")
+    ap.add_argument("--phase_offset", type=float, default=0.0, help="rate-Rs run: phase offset in rads")
     args = ap.parse_args(argv)
+    if args.pilots and not args.rate_Fs:
+        raise SystemExit("radae_amd.cli inference: --pilots needs --rate_Fs: the rate-Rs channel has no pilot numerology (the reference does not run this combination "
+                         "either: RADAE.forward fails on tx_sym * H, 5 n_mf against 4 n_mf symbols)")
+    if not args.rate_Fs and args.bottleneck == 3:
+        return _inference_rate_rs(args)
     genie = args.ideal_rx or args.ber_test or bool(args.write_latent) or args.bottleneck == 1
     if args.bottleneck not in (1, 3) or abs(args.cp - 0.004) > 1e-9 or args.latent_dim != 80 or not -32 <= args.time_offset <= 0 or \
             (args.time_offset != -16 and not genie):
@@ -216,6 +226,75 @@ def _inference(argv):
             print("PASS" if loss < args.loss_test else "FAIL")
     else:
         print("loss: n/a (the streaming receiver decoded nothing)")
+    eng.close()
+    return 0
+
+
+def _inference_rate_rs(args):
+    """inference.py without --rate_Fs on a bottleneck-3 model (inference.py:127-153, :213-229; radae.py:603-634): features (+ the aux symbol) -> core encoder -> the rate-Rs
+    channel (IDFT, PA limiter, DFT per OFDM symbol of the no-pilot numerology Nc = 20, M = 160; phase offset, per-carrier magnitudes H, AWGN: rade_batch_channel_rs_pa) ->
+    core decoder -> features_hat.  Needs --auxdata (the blob's 21 features); refuses the options only the rate-Fs run has.  Honours --EbNodB, --h_file (float32 [.][20]), --mp_test, --phase_offset, --write_latent, --loss_test, --ber_test, --seed; prints the
+    reference's Target / Measured lines (Eq/No - 3 dB, SNR3k, Eq, PAPR).  Noise: the device's Philox generator (--seed), not torch's."""
+    import torch
+    from . import engine, wire
+    from .loss import distortion_loss
+    if args.latent_dim != 80:
+        raise SystemExit("radae_amd.cli inference: only --latent-dim 80 is implemented")
+    # what only the rate-Fs run can honour is refused, not ignored: the sample-rate channel, its files and its receivers do not exist at rate Rs
+    fs_only = [("--g_file", args.g_file), ("--write_rx", args.write_rx), ("--write_tx", args.write_tx), ("--freq_offset", args.freq_offset), ("--df_dt", args.df_dt),
+               ("--prepend_noise", args.prepend_noise), ("--append_noise", args.append_noise), ("--end_of_over", args.end_of_over), ("--sine_amp", args.sine_amp),
+               ("--rx_gain", args.rx_gain != 1.0), ("--ideal_rx", args.ideal_rx), ("--correct_freq_offset", args.correct_freq_offset)]
+    given = [name for name, v in fs_only if v]
+    if given:
+        raise SystemExit(f"radae_amd.cli inference: {', '.join(given)} need(s) --rate_Fs: without it the run is the rate-Rs channel (one sample per QPSK symbol), "
+                         "which has no sample-rate signal to write, offset or receive")
+    if not args.auxdata:
+        raise SystemExit("radae_amd.cli inference: the rate-Rs run needs --auxdata: model19_check3's encoder takes 21 features per frame (the aux symbol is appended here, "
+                         "inference.py:115-123)")
+    blob = args.model_name if args.model_name.endswith(".bin") else None
+    feats = wire.read_features(args.features)
+    n_mf = len(feats) // 12                                   # whole modem frames (radae.py:303-310)
+    if n_mf < 1:
+        raise SystemExit("radae_amd.cli inference: less than one modem frame of features")
+    feats = np.ascontiguousarray(feats[:12 * n_mf])
+    print(f"Processing: {12 * n_mf} feature vectors")
+    rows, n_sym, Nc, Rs = 3 * n_mf, 6 * n_mf, 20, 50.0
+    H = None
+    if args.mp_test:                                          # inference.py:134-142: peaks and notches between 2 and 0, constant over time
+        H = np.tile(np.abs(1.0 + np.exp(-2j * np.pi * np.arange(Nc) * 0.002 * Rs)).astype(np.float32), (n_sym, 1))
+    if args.h_file:
+        H = np.fromfile(args.h_file, np.float32).reshape(-1, Nc)
+        if len(H) < n_sym:
+            raise SystemExit("Multipath H file too short")
+        H = np.ascontiguousarray(H[:n_sym])
+    dev = torch.device("cuda", 0)
+    eng = engine.BatchEngine(1, max_tx_mf=n_mf, blob=blob)
+    ft = np.ascontiguousarray(feats[:, :21]); ft[:, 20] = -1.0           # inference.py:115-123: the aux symbol
+    z = eng.encode(torch.tensor(ft.reshape(1, rows, 84), device=dev))
+    if args.ber_test:                                         # radae.py:477-478 (BER 0.5 in this mode: the noise is scaled for the encoder's symbols of magnitude M / sqrt(Nc))
+        g = torch.Generator().manual_seed(args.seed)
+        z = torch.sign(torch.rand((1, rows, 80), generator=g) - 0.5).to(dev)
+    sigma = engine.sigma_from_EbNodB(args.EbNodB, rate_Fs=False)
+    z_hat, st = eng.channel_rs_pa(z, sigma, H=torch.tensor(H[None], device=dev) if H is not None else None, phase_offset=args.phase_offset, seed=args.seed, want_stats=True)
+    if args.ber_test:
+        print(f"n_bits: {rows * 80:d} BER: {int(torch.sum(-z * z_hat > 0)) / (rows * 80):5.3f}")
+    fh = eng.decode(z_hat, 84).cpu().numpy()[0].reshape(-1, 21)
+    EbNo = 10 ** (args.EbNodB / 10); Rb, Bw = 2000.0, 3000.0
+    print("          Eb/No   C/No     SNR3k  Rb'    Eq     PAPR")
+    print(f"Target..: {args.EbNodB:6.2f}  {10 * np.log10(EbNo * Rb):6.2f}  {10 * np.log10(EbNo * Rb / Bw):6.2f}  {int(Rb):d}")
+    Eq = st[0, 2] / (n_sym * Nc); S = st[0, 0] / (n_sym * 160)
+    EqNo = 10 * np.log10(Eq / sigma ** 2)
+    print(f"Measured: {EqNo - 3:6.2f}          {EqNo + 10 * np.log10(Rs * Nc / Bw):6.2f}       {Eq:7.2f} {20 * np.log10(st[0, 1] / np.sqrt(S)):5.2f}")
+    out = np.zeros((len(fh), 36), np.float32); out[:, :20] = fh[:, :20]              # inference.py:231-234
+    if args.features_hat != "/dev/null":
+        out.tofile(args.features_hat)
+    if args.write_latent:
+        z_hat.cpu().numpy()[0].astype(np.float32).tofile(args.write_latent)
+    loss = distortion_loss(ft, fh)
+    ber = float(np.mean(ft[:, 20] * fh[:, 20] < 0))
+    print(f"loss: {loss:5.3f} Auxdata BER: {ber:5.3f}")
+    if args.loss_test > 0.0:
+        print("PASS" if loss < args.loss_test else "FAIL")
     eng.close()
     return 0
 

@@ -201,6 +201,19 @@ typedef struct {
 } rd_loss_args;
 int rd_launch_loss(const rd_loss_args *a, rd_stream_t s);
 
+/* the rate-Rs channel of the bottleneck-3 model (rade_rs.hip; radae.py:603-634): IDFT, limiter, DFT per OFDM symbol of the no-pilot numerology (20 carriers, 160 samples),
+ * then phase offset, |H|, noise.  Every buffer dense: z, z_hat [B][n_steps][80], H [B][2 n_steps][20] float, noise [B][2 n_steps][20] complex64. */
+#define RD_RS_NCH 8                                              /* chunks of symbol tiles per stream: the measurement partials are added in this fixed order */
+typedef struct {
+    const rd_tables *tab; const float *z, *H; const void *noise; float *z_hat;
+    int B, n_steps, has_phase; float sigma, ph_re, ph_im;        /* e^{j phase_offset}, applied when has_phase */
+    const float *sigma_b;                                        /* optional [B]: sigma of every stream, read in place of the scalar */
+    unsigned long long seed;                                     /* noise NULL: Philox keyed by (seed, stream); 0 = no noise */
+    double *part;                                                /* [B][RD_RS_NCH][4]: sum |tx'|^2, max |tx'|^2, sum |Y|^2 of each chunk */
+    double *stats;                                               /* optional [B][3]: sum |tx'|^2, max |tx'|, sum |Y|^2 (k_rs_stats) */
+} rd_rs_args;
+int rd_launch_rs_pa(const rd_rs_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

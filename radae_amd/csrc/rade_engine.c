@@ -98,6 +98,7 @@ struct rade_batch {
     rd_bpf_state *tx_bpf, *tx_bpf_init; void *tx_raw; float *tx_chain; float *eoo_filt;   /* eoo_filt [B][Neoo] c64: the end-of-over frame as transmitted (filtered + clipped) for the channel's with_eoo */
     void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
     float *chan_ps, *chan_ps_host;            /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */
+    float *rs_sigma; double *rs_part, *rs_stats;   /* rade_batch_channel_rs_pa: [B] per-stream sigma, [B][RD_RS_NCH][4] measurement partials, [B][3] measurements, allocated on first use */
     int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
@@ -692,6 +693,12 @@ float rade_sigma_from_EbNodB_bn1(float EbNodB)
     return powf(EbNo * (float)RD_M, -0.5f);
 }
 
+float rade_sigma_from_EbNodB_rs3(float EbNodB)
+{   /* radae.py:627-630 (rate Rs, bottleneck 3): sigma = M / sqrt(2 Nc EbNo) / sqrt(2), Nc = 20 carriers of the no-pilot numerology */
+    const float EbNo = powf(10.0f, EbNodB / 10.0f);
+    return ((float)RD_M / powf(2.0f * 20.0f * EbNo, 0.5f)) / powf(2.0f, 0.5f);
+}
+
 /* `rows` arrays of B 4-byte values (row r: src[r], or fill[r] where that is NULL, 0 without fill) through pinned `stage` to `dev`; wait = 0: the caller synchronises before it reuses `stage` */
 static int stage_rows(rade_batch *h, void *stage, void *dev, int rows, const void *const *src, const float *fill, int wait, hipStream_t st)
 {
@@ -951,6 +958,37 @@ int rade_batch_channel_symbol(rade_batch *h, const float *z_dev, const float *H_
     ON_DEV(h);
     if (!h || n_steps <= 0 || (mode != 0 && mode != 1)) return -1;
     return rd_launch_chan_symbol(z_dev, H_dev, noise_dev, z_hat_dev, (long)h->B * n_steps * RD_LATENT, mode, p0, p1, seed, stream) ? -1 : n_steps;
+}
+
+/* ---- the rate-Rs channel of the bottleneck-3 model (radae.py:603-634; rade_rs.hip) ------------------------------------------------------------ */
+int rade_batch_channel_rs_pa(rade_batch *h, const float *z_dev, const float *H_dev, const void *noise_dev, float *z_hat_dev, int n_steps, float sigma,
+                             const float *sigma_streams_host, float phase_offset, unsigned long long seed, double *stats_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !z_dev || !z_hat_dev || n_steps <= 0) return -1;
+    if (((uintptr_t)z_dev | (uintptr_t)H_dev | (uintptr_t)z_hat_dev) & 3 || ((uintptr_t)noise_dev & 7)) return -1;   /* element alignment is all the kernel needs */
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (dev_grow(h, &h->rs_part, NULL, (long)B * RD_RS_NCH * 4, sizeof(double), 1) || dev_grow(h, &h->rs_stats, NULL, 3L * B, sizeof(double), 1)) return -1;
+    if (sigma_streams_host) {              /* pinned scratch (8 + 8 B ints): the [B] sigmas, behind them the [B][3] measurements on the way back */
+        const void *src[1] = { sigma_streams_host };
+        if (dev_grow(h, &h->rs_sigma, NULL, B, sizeof(float), 1) || stage_rows(h, h->h_small, h->rs_sigma, 1, src, NULL, 1, st)) return -1;
+    }
+    rd_rs_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.z = z_dev; a.H = H_dev; a.noise = noise_dev; a.z_hat = z_hat_dev; a.B = B; a.n_steps = n_steps;
+    a.sigma = sigma; a.sigma_b = sigma_streams_host ? h->rs_sigma : NULL; a.seed = seed;
+    a.has_phase = phase_offset != 0.0f; a.ph_re = cosf(phase_offset); a.ph_im = sinf(phase_offset);      /* radae.py:616-619 */
+    a.part = h->rs_part; a.stats = stats_host ? h->rs_stats : NULL;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_rs_pa(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, 8.0 * B * 2.0 * n_steps * 2 * 20 * RD_M);
+    if (stats_host) {
+        double *res = (double *)(h->h_small + 2 * B);
+        if (hipMemcpyAsync(res, h->rs_stats, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        memcpy(stats_host, res, sizeof(double) * 3 * B);
+    }
+    return n_steps;
 }
 
 /* The wait of rade_batch_rx when the host is short of CPUs (sync_blocking_now): SLEEP until the receiver launch is done.  hipEventSynchronize on a

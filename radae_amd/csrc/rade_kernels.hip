@@ -824,26 +824,7 @@ __global__ __launch_bounds__(256) void k_chan_power(rd_chan_args a, double *part
     if (tid == 0) { part[((size_t)b * CH_NCH + ch) * 2] = red[0][0]; part[((size_t)b * CH_NCH + ch) * 2 + 1] = red[1][0]; }
 }
 
-// Philox4x32-10 counter-based generator (Salmon et al., SC'11) -> two complex N(0,1/2)+jN(0,1/2) samples
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ float2 gauss_pair(uint32_t u0, uint32_t u1)
-{   // Box-Muller, unit variance per component, on the hardware log2 / sqrt / sin / cos units (v_sin_f32 and v_cos_f32 take their argument in
-    // revolutions: exactly what the second uniform is): this generator only feeds the device-noise path (seed != 0: benchmark and
-    // statistics runs; parity tests pass an explicit noise tensor), where the libm versions were most of k_chan_apply's instructions
-    const float a = ((float)u0 + 0.5f) * (1.0f / 4294967296.0f), bq = ((float)u1 + 0.5f) * (1.0f / 4294967296.0f);
-    const float rad = __builtin_amdgcn_sqrtf(-1.38629436112f * __builtin_amdgcn_logf(a));       // -2 ln a = -2 ln 2 log2 a
-    return make_float2(rad * __builtin_amdgcn_cosf(bq), rad * __builtin_amdgcn_sinf(bq));
-}
+// (philox4x32 and gauss_pair, the generated noise of every channel kernel: rade_devutil.h)
 
 // per stream, ahead of k_chan_apply: the power-normalising gain and the phase the frequency offset has reached at the end of the signal, from the
 // stream's partial power sums (added in their fixed order).  As a prologue of every k_chan_apply workgroup -- one thread, a hundred dependent

@@ -102,6 +102,9 @@ def load_library() -> C.CDLL:
         L.rade_batch_channel_streams.argtypes = [vp, vp, C.c_long, vp, C.c_long, C.POINTER(ChannelParams), C.POINTER(ChannelStreams), vp]
         L.rade_batch_tx_channel_streams.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp, C.c_long, C.POINTER(ChannelParams), C.POINTER(ChannelStreams), vp]
         L.rade_batch_loss.argtypes = [vp, vp, C.c_long, C.c_int, vp, vp, C.c_long, C.c_int, vp, vp, vp, vp, C.c_long, vp]
+    if hasattr(L, "rade_batch_channel_rs_pa"):    # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
+        L.rade_sigma_from_EbNodB_rs3.restype = C.c_float; L.rade_sigma_from_EbNodB_rs3.argtypes = [C.c_float]
+        L.rade_batch_channel_rs_pa.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, C.c_float, C.c_ulonglong, vp, vp]
     _lib = L
     return L
 
@@ -121,14 +124,20 @@ EXPORTED_SYMBOLS = [
     "rade_multi_allreduce_sum",
     "rade_batch_rx_ideal", "rade_sigma_from_EbNodB_bn1",
     "rade_batch_loss", "rade_batch_channel_streams", "rade_batch_tx_channel_streams",
+    "rade_batch_channel_rs_pa", "rade_sigma_from_EbNodB_rs3",
 ]
 
 
-def sigma_from_EbNodB(EbNodB, bottleneck: int = 3):
-    """AWGN standard deviation of the rate-Fs channel: bottleneck 3 (radae.py:567-573) or bottleneck 1 (:574-576, the waveform of TX_LINEAR).
+def sigma_from_EbNodB(EbNodB, bottleneck: int = 3, rate_Fs: bool = True):
+    """AWGN standard deviation of the rate-Fs channel: bottleneck 3 (radae.py:567-573) or bottleneck 1 (:574-576, the waveform of TX_LINEAR); with rate_Fs=False
+    of the rate-Rs channel of bottleneck 3 (radae.py:627-630, channel_rs_pa: 12.66 at 3 dB, for symbols of magnitude M / sqrt(Nc)).
     A scalar gives a float; an array of Eb/No points gives a float32 array of the same shape, each value what the scalar form gives (per-stream channels)."""
     L = load_library()
-    if bottleneck == 1:
+    if not rate_Fs:
+        if bottleneck != 3:
+            raise ValueError("rate-Rs noise is offered for bottleneck 3 (bottleneck 1: sigma = 10 ** (-EbNodB / 20), radae.py:632)")
+        f = L.rade_sigma_from_EbNodB_rs3
+    elif bottleneck == 1:
         f = L.rade_sigma_from_EbNodB_bn1
     elif bottleneck == 3:
         f = L.rade_sigma_from_EbNodB
@@ -341,6 +350,29 @@ class BatchEngine:
         if r != n:
             raise RuntimeError("rade_batch_channel_symbol failed")
         return out
+
+    def channel_rs_pa(self, z, sigma, H=None, noise=None, phase_offset: float = 0.0, seed: int = 0, want_stats: bool = False):
+        """The rate-Rs channel of the bottleneck-3 model (rade_batch_channel_rs_pa; radae.py:603-634): z cuda float32 [B, n_steps, 80] -> z_hat of the same shape.
+        Every OFDM symbol (40 floats of z: 20 carriers) through IDFT, PA limiter and DFT, then e^{j phase_offset}, H (float32 [B, 2 n_steps, 20] magnitudes or
+        None = 1) and sigma times noise (complex64 [B, 2 n_steps, 20], unit variance; None -> Philox(seed), seed 0 = no noise).  sigma: a scalar for every
+        stream or B per-stream values (sigma_from_EbNodB(.., rate_Fs=False)).  want_stats: also returns float64 [B, 3] = sum |tx'|^2, max |tx'|, sum |Y|^2 per
+        stream (inference.py:215-227's Eq and PAPR; the call then synchronises)."""
+        import torch
+        assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.dim() == 3 and z.shape[0] == self.B and z.shape[2] == 80 and z.shape[1] >= 1
+        n = z.shape[1]
+        (sigma, _, _), per = channel_stream_values(self.B, sigma, 0.0, 0.0)
+        if H is not None:
+            assert H.is_cuda and H.dtype == torch.float32 and H.is_contiguous() and tuple(H.shape) == (self.B, 2 * n, 20)
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.complex64 and noise.is_contiguous() and tuple(noise.shape) == (self.B, 2 * n, 20)
+        out = torch.empty_like(z)
+        stats = np.zeros((self.B, 3), np.float64) if want_stats else None
+        r = self.lib.rade_batch_channel_rs_pa(self.h, z.data_ptr(), H.data_ptr() if H is not None else None, noise.data_ptr() if noise is not None else None,
+                                              out.data_ptr(), n, sigma, per["sigma"].ctypes.data if per else None, phase_offset, seed,
+                                              stats.ctypes.data if want_stats else None, _stream_ptr())
+        if r != n:
+            raise RuntimeError("rade_batch_channel_rs_pa failed")
+        return (out, stats) if want_stats else out
 
     # ---- channel ----------------------------------------------------------------------------
     def channel(self, tx, sigma, freq_offset=0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
