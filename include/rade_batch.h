@@ -20,6 +20,8 @@
  *   rade_batch_rx_ideal    radae.py:312-420, :590-657 (the ideal-timing receiver of RADAE.forward / RADAE.receiver, ber_test)
  *   rade_batch_channel_rs_pa  radae.py:603-634 with bottleneck 3 (the rate-Rs "hybrid time & frequency domain" channel: IDFT, PA limiter, DFT, |H|, AWGN) +
  *                          inference.py:213-229 (its Eq / PAPR measurements)
+ *   rade_batch_resample    dsp.py:564-575 (sample_clock_offset, the linear mode) and what the ctests radae_rx_dfs / radae_rx_slip_* do with `sox -r 8000 .. -r 8020`:
+ *                          the receiver's sound card running at another rate than the transmitter's, per stream
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -101,6 +103,8 @@ int rade_batch_n_streams(const rade_batch *h);
  *                                           feat_stride / that), eoo_out_dev (float [B][180], written only for a stream with has_eoo)
  *   rade_batch_rx_ideal                     rx_dev (complex64; rx_stride >= 960 n_mf, checked), z_ref_dev in; z_hat_dev (16 B with features_out_dev), features_out_dev (float; dense)
  *   rade_batch_loss                         features_dev (float; f_stride >= n_in f_row), hat_dev (float; h_stride >= n_hat h_row) in; frame_loss_dev (float; fl_stride >= n_hat, checked)
+ *   rade_batch_resample                     x_dev (complex64; x_stride >= every n_in, checked) in; y_dev (complex64; y_stride >= every n_out, checked): n_out[b] samples of row b are written,
+ *                                           8 bytes at a time (any y_stride, any parity of n_out, element alignment); x is read inside [b x_stride, b x_stride + n_in[b]) only
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -199,6 +203,42 @@ int rade_batch_channel_streams(rade_batch *h, const void *tx_dev, long tx_stride
                                const rade_channel_params *p, const rade_channel_streams *ps, void *stream);
 int rade_batch_tx_channel_streams(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride,
                                   void *rx_out_dev, long rx_stride, const rade_channel_params *p, const rade_channel_streams *ps, void *stream);
+
+/* ---- sample-clock offset: a fractional resampler, every stream in one launch (rade_clk.hip) -----------------------------------------------
+ * Output n of stream b (absolute index, n0 <= n < n0 + n_out) is the input interpolated at pos(n) = t0 + n step input samples, step = 1 + ppm 1e-6 (dsp.py:574's
+ * convention: ppm > 0 reads the input faster, fewer outputs per input).  Time base: Q32.32 integers made on the host in double and rounded once,
+ *     step_q = llrint((1 + ppm 1e-6) 2^32)    t0_q = llrint(t0 2^32)    pos_q = t0_q + n step_q (signed 64 bit)    i = pos_q >> 32 (arithmetic)    mu = pos_q & 0xffffffff
+ * so an output's position is a pure function of (t0, ppm, n): the call keeps no state on the device, and a stream resampled in pieces equals the stream resampled
+ * whole, bit for bit, when every piece is handed the inputs its windows cover.  in_base is the absolute index of x[b][0]; input samples outside
+ * [in_base, in_base + n_in) read as zero, at both ends and at negative indices, and nothing outside [b x_stride, b x_stride + n_in) is read.
+ *   RADE_RESAMPLE_LINEAR  dsp.py:569-572: y = (1 - f) x[i] + f x[i + 1], f = mu 2^-32 rounded to float32.
+ *   RADE_RESAMPLE_SINC32  32-tap Kaiser-windowed sinc, 256 phases, linear interpolation between neighbouring phases:
+ *       p = mu >> 24    w = (mu & 0xffffff) 2^-24 (exact in float32)    c[j] = T[p][j] + w (T[p + 1][j] - T[p][j])    y = sum_{j = 0..31} c[j] x[i + j - 15]
+ *     T [257][32] float32, made on the host in double (rade_resample_taps): T[p][j] = g(j - 15 - p / 256) / sum_j g(.), g(t) = sinc(t) I0(10 sqrt(1 - (t / 16)^2)) / I0(10)
+ *     for |t| <= 16, else 0, sinc(t) = sin(pi t) / (pi t).  Every row sums to 1; row 0 is exactly the unit impulse at j = 15 and row 256 the one at j = 16, so ppm = 0 with
+ *     an integer t0 is a bit-exact delay in both modes.  The terms are added in the order j = 0..31 into one float32 accumulator per component (fused multiply-adds).
+ *     Worst error of the definition on unit tones |f| <= 2700 Hz at 8 kHz: 2e-5 (the modem's carriers: 700..2300 Hz).
+ * ppm / t0 / n0 / in_base: [B] host arrays, or NULL = the scalar ppm, 0, 0, 0 for every stream.  Stream b of a call with arrays is what the call with its values as
+ * scalars gives for it, bit for bit (the rule of rade_channel_streams).  The per-stream values are copied to the device in one record per stream ahead of the launch:
+ * the call synchronises `stream` once for that.
+ * Refused with -1 on the host, before any launch and with nothing written: NULL or misaligned (8 bytes) x_dev / y_dev, NULL counts or p, a negative count or n0, a
+ * stride shorter than the row, an unknown mode, |ppm| > 50 000, |t0| > 2^29 or |in_base| > 2^62 (or not a number), (n0 + n_out) step_q past 2^62 (37 h at 8 kHz).
+ * Returns 0.  Any engine (the model is not used; no encoder or receiver state is touched). */
+enum { RADE_RESAMPLE_SINC32 = 0, RADE_RESAMPLE_LINEAR = 1 };
+typedef struct {
+    int mode;
+    double ppm;  const double *ppm_host;          /* [B] or NULL = ppm for every stream */
+    const double *t0_host;                        /* [B] position of output 0 in input samples (fractional, may be negative), NULL = 0 */
+    const long long *n0_host;                     /* [B] index of the first output sample this call writes, NULL = 0 */
+    const long long *in_base_host;                /* [B] absolute index of x[b][0], NULL = 0 */
+} rade_resample_params;
+int rade_batch_resample(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
+                        const rade_resample_params *p, void *stream);
+/* host only: the number of n >= 0 with pos(n) < in_end, i.e. the outputs whose centre tap lies inside an input of in_end samples (-1: ppm or t0 refused as above, or
+ * that many outputs pass the 2^62 limit) */
+long long rade_resample_count(long long in_end, double t0, double ppm);
+/* host only, no handle, no GPU: the table T */
+void rade_resample_taps(float *out /* [257][32] */);
 
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the

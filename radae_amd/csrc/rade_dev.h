@@ -214,6 +214,20 @@ typedef struct {
 } rd_rs_args;
 int rd_launch_rs_pa(const rd_rs_args *a, rd_stream_t s);
 
+/* the fractional resampler of rade_batch_resample (rade_clk.hip; include/rade_batch.h states the arithmetic): k_clk_resample, one workgroup per (tiles of RD_CLK_TILE
+ * consecutive outputs, stream), the tile's input window and the taps in LDS */
+#define RD_CLK_TILE 1024
+#define RD_CLK_PHASES 256
+#define RD_CLK_TAPS 32
+typedef struct { long long step_q, t0_q, n0, in_base; int n_in, n_out; } rd_clk_stream;      /* one record per stream; Q32.32 step and start */
+typedef struct {
+    const void *x; long x_stride; void *y; long y_stride;       /* complex64, stream b at + b * stride samples */
+    const rd_clk_stream *ps;                                    /* device [B] */
+    const float *taps;                                          /* device [RD_CLK_PHASES + 1][RD_CLK_TAPS] (rade_resample_taps) */
+    int mode, B, max_out;                                       /* 0 sinc, 1 linear; max_out = the largest n_out of the call */
+} rd_clk_args;
+int rd_launch_clk_resample(const rd_clk_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

@@ -99,6 +99,7 @@ struct rade_batch {
     void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
     float *chan_ps, *chan_ps_host;            /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */
     float *rs_sigma; double *rs_part, *rs_stats;   /* rade_batch_channel_rs_pa: [B] per-stream sigma, [B][RD_RS_NCH][4] measurement partials, [B][3] measurements, allocated on first use */
+    float *clk_taps; rd_clk_stream *clk_ps, *clk_ps_host;   /* rade_batch_resample: the taps [257][32]; [B] per-stream records on the device and their pinned staging copy, allocated on first use */
     int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
@@ -989,6 +990,49 @@ int rade_batch_channel_rs_pa(rade_batch *h, const float *z_dev, const float *H_d
         memcpy(stats_host, res, sizeof(double) * 3 * B);
     }
     return n_steps;
+}
+
+/* ---- sample-clock offset: the fractional resampler (rade_clk.hip) ------------------------------------------------------------------------------ */
+int rade_batch_resample(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
+                        const rade_resample_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p) return -1;
+    if (((uintptr_t)x_dev | (uintptr_t)y_dev) & 7) return -1;
+    if (p->mode != RADE_RESAMPLE_SINC32 && p->mode != RADE_RESAMPLE_LINEAR) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->clk_ps_host && !(h->clk_ps_host = pinned_alloc_opt(h, sizeof(rd_clk_stream) * B))) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_clk_stream *r = &h->clk_ps_host[b];
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
+        r->n0 = p->n0_host ? p->n0_host[b] : 0; r->in_base = p->in_base_host ? p->in_base_host[b] : 0;
+        if (r->n_in < 0 || r->n_out < 0 || r->n_in > x_stride || r->n_out > y_stride || r->n0 < 0) return -1;
+        if (r->in_base > (1LL << 62) || r->in_base < -(1LL << 62)) return -1;
+        if (rd_resample_q(p->t0_host ? p->t0_host[b] : 0.0, p->ppm_host ? p->ppm_host[b] : p->ppm, &r->step_q, &r->t0_q)) return -1;
+        if (((__int128)r->n0 + r->n_out) * r->step_q > ((__int128)1 << 62)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (p->mode == RADE_RESAMPLE_SINC32 ? 4.0 * 2 * RD_CLK_TAPS : 6.0) * r->n_out;
+    }
+    if (!max_out) return 0;
+    if (!h->clk_taps) {
+        float *t = malloc(sizeof(float) * (RD_CLK_PHASES + 1) * RD_CLK_TAPS);
+        if (t) { rade_resample_taps(t); h->clk_taps = dev_upload_opt(h, t, sizeof(float) * (RD_CLK_PHASES + 1) * RD_CLK_TAPS); }
+        free(t);
+        if (!h->clk_taps) return -1;
+    }
+    if (dev_grow(h, &h->clk_ps, NULL, B, sizeof(rd_clk_stream), 1)) return -1;
+    /* the one small copy ahead of the launch; waited for, since the next call refills the staging records */
+    if (hipMemcpyAsync(h->clk_ps, h->clk_ps_host, sizeof(rd_clk_stream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    rd_clk_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.ps = h->clk_ps; a.taps = h->clk_taps; a.mode = p->mode; a.B = B; a.max_out = max_out;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_clk_resample(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
 }
 
 /* The wait of rade_batch_rx when the host is short of CPUs (sync_blocking_now): SLEEP until the receiver launch is done.  hipEventSynchronize on a

@@ -3,13 +3,15 @@
  *   1. constant tables of the OFDM modem (rd_tables), evaluated with the same float32/float64 steps
  *      NumPy/PyTorch take in the reference so the device kernels see bit-comparable constants;
  *   2. DNNw weight-blob reader -> fp32 matrices (the blob is int8 + per-row scales for most layers);
- *   3. weight packing into the MFMA fragment order k_gemm streams.
+ *   3. weight packing into the MFMA fragment order k_gemm streams;
+ *   4. the fractional resampler's Q32.32 time base and its windowed-sinc taps (rade_batch_resample).
  *
  * Reference: radae/radae.py:128-234 (numerology/DFT/pilots/EOO), radae/dsp.py:40-61 (BPF),
  * :153-176 (p_w), :400-416 (Pmat); blob format src/write_rade_weights.c:51-74 and
  * weight-exchange/wexchange/c_export/common.py:59-69,140-176,263-271,290-293,307-311,360-368.
  */
 #include "rade_host.h"
+#include "rade_batch.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -585,4 +587,53 @@ void rd_bpf16_table_fill(const rd_tables *T, unsigned short *out /* [4][2][64][8
                 unsigned short *o = out + (((size_t)ks * 2) * 64 + lane) * 8 + j;
                 o[0] = hi; o[64 * 8] = lo;
             }
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * 4. the fractional resampler's time base and taps (include/rade_batch.h: rade_batch_resample; rade_clk.hip)
+ * -------------------------------------------------------------------------------------------*/
+/* I0 by its power series sum_k ((x / 2)^k / k!)^2: 40 terms are past double precision for x <= 10 */
+static double bessel_i0(double x)
+{
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < 40; k++) { t *= (x * 0.5) / k; s += t * t; }
+    return s;
+}
+
+/* T[p][j] = g(j - 15 - p / 256) / sum_j g, g(t) = sinc(t) I0(10 sqrt(1 - (t / 16)^2)) / I0(10).  With t = k - f (k = j - 15, f = p / 256, both exact)
+ * sin(pi t) = -(-1)^k sin(pi f), and sin(pi f) = sin(pi (1 - f)) keeps it an exact 0 at f = 1 as at f = 0: rows 0 and 256 are exact impulses. */
+void rade_resample_taps(float *out /* [257][32] */)
+{
+    const double i0b = bessel_i0(10.0);
+    for (int p = 0; p <= 256; p++) {
+        const double f = p / 256.0, sf = sin(PI_D * (p <= 128 ? f : 1.0 - f));
+        double g[32], sum = 0.0;
+        for (int j = 0; j < 32; j++) {
+            const int k = j - 15;
+            const double t = (double)k - f, u = t / 16.0;
+            const double sinc = t == 0.0 ? 1.0 : ((k & 1) ? sf : -sf) / (PI_D * t);
+            g[j] = fabs(t) <= 16.0 ? sinc * bessel_i0(10.0 * sqrt(1.0 - u * u)) / i0b : 0.0;
+            sum += g[j];
+        }
+        for (int j = 0; j < 32; j++) out[p * 32 + j] = (float)(g[j] / sum);
+    }
+}
+
+/* Q32.32 step and start of a stream; -1 where the header refuses (|ppm| > 50 000, a start that does not fit) */
+int rd_resample_q(double t0, double ppm, long long *step_q, long long *t0_q)
+{
+    if (!(fabs(ppm) <= 50000.0) || !(fabs(t0) <= 536870912.0)) return -1;        /* NaN fails both; |t0| <= 2^29 keeps t0_q + n step_q inside 64 bits */
+    *step_q = llrint((1.0 + ppm * 1e-6) * 4294967296.0);
+    *t0_q = llrint(t0 * 4294967296.0);
+    return 0;
+}
+
+long long rade_resample_count(long long in_end, double t0, double ppm)
+{
+    long long step_q, t0_q;
+    if (rd_resample_q(t0, ppm, &step_q, &t0_q)) return -1;
+    const __int128 need = ((__int128)in_end << 32) - t0_q;                        /* pos_q(n) < in_end 2^32  <=>  n step_q < need */
+    if (need <= 0) return 0;
+    const __int128 n = (need + step_q - 1) / step_q;
+    return n * step_q > ((__int128)1 << 62) ? -1 : (long long)n;
 }

@@ -49,6 +49,8 @@ long rd_packed16a_size(int N, int K);
  * Returns the plane's size in halfs, or -1 when W is not q * row_scale with integer |q| <= 127. */
 long rd_pack_weights_q16_a16(const float *W, const float *row_scale, int N, int K, unsigned short *out, float *scale_out);
 long rd_pack_weights_f16x2_a16(const float *W, int N, int K, unsigned short *out);
+/* rade_batch_resample's time base (include/rade_batch.h): step_q = llrint((1 + ppm 1e-6) 2^32), t0_q = llrint(t0 2^32); -1: |ppm| > 50 000 or |t0| > 2^29 (or not a number) */
+int rd_resample_q(double t0, double ppm, long long *step_q, long long *t0_q);
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,10 @@ class IdealRxParams(C.Structure):
                 ("z_ref_dev", C.c_void_p), ("n_errors_host", C.c_void_p)]
 
 
+class ResampleParams(C.Structure):
+    _fields_ = [("mode", C.c_int), ("ppm", C.c_double), ("ppm_host", C.c_void_p), ("t0_host", C.c_void_p), ("n0_host", C.c_void_p), ("in_base_host", C.c_void_p)]
+
+
 class RxStatus(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("consumed", "n_calls", "n_valid", "has_eoo", "nin", "sync", "snr_dB", "state")]
 
@@ -105,6 +109,10 @@ def load_library() -> C.CDLL:
     if hasattr(L, "rade_batch_channel_rs_pa"):    # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
         L.rade_sigma_from_EbNodB_rs3.restype = C.c_float; L.rade_sigma_from_EbNodB_rs3.argtypes = [C.c_float]
         L.rade_batch_channel_rs_pa.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, C.c_float, C.c_ulonglong, vp, vp]
+    if hasattr(L, "rade_batch_resample"):         # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
+        L.rade_batch_resample.argtypes = [vp, vp, C.c_long, vp, vp, C.c_long, vp, C.POINTER(ResampleParams), vp]
+        L.rade_resample_count.restype = C.c_longlong; L.rade_resample_count.argtypes = [C.c_longlong, C.c_double, C.c_double]
+        L.rade_resample_taps.restype = None; L.rade_resample_taps.argtypes = [vp]
     _lib = L
     return L
 
@@ -125,7 +133,40 @@ EXPORTED_SYMBOLS = [
     "rade_batch_rx_ideal", "rade_sigma_from_EbNodB_bn1",
     "rade_batch_loss", "rade_batch_channel_streams", "rade_batch_tx_channel_streams",
     "rade_batch_channel_rs_pa", "rade_sigma_from_EbNodB_rs3",
+    "rade_batch_resample", "rade_resample_count", "rade_resample_taps",
 ]
+
+RESAMPLE_MODES = {"sinc32": 0, "linear": 1}                                        # rade_resample_params.mode
+RESAMPLE_PPM_MAX = 50000.0
+
+
+def ppm_from_rates(fs_tx: float, fs_rx: float) -> float:
+    """The clock offset in ppm of a receiver sampling at fs_rx what was sent at fs_tx (`sox -r 8000 .. -r 8020`): step = fs_tx / fs_rx input samples per output
+    sample, so ppm = (fs_tx / fs_rx - 1) 1e6 (dsp.py:574's convention); ppm_from_rates(8000, 8020) = -2493.77."""
+    return (float(fs_tx) / float(fs_rx) - 1.0) * 1e6
+
+
+def resample_count(in_end: int, t0: float = 0.0, ppm: float = 0.0) -> int:
+    """rade_resample_count: how many outputs n >= 0 have their position t0 + n (1 + ppm 1e-6) below in_end input samples."""
+    n = int(load_library().rade_resample_count(int(in_end), float(t0), float(ppm)))
+    if n < 0:
+        raise ValueError(f"rade_resample_count refuses ppm {ppm!r}, t0 {t0!r}, in_end {in_end!r} (|ppm| <= 50000, |t0| <= 2^29, outputs x step <= 2^62)")
+    return n
+
+
+def resample_taps() -> np.ndarray:
+    """rade_resample_taps: the float32 [257, 32] Kaiser-windowed sinc table of the sinc32 mode (host only)."""
+    t = np.zeros((257, 32), np.float32)
+    load_library().rade_resample_taps(t.ctypes.data)
+    return t
+
+
+def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
+    """a scalar (every stream) or B per-stream values -> a contiguous [B] array"""
+    a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=dtype)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+        raise ValueError(f"{what}: a scalar or {B} per-stream values, got shape {a.shape}")
+    return np.ascontiguousarray(np.broadcast_to(a, (B,)))
 
 
 def sigma_from_EbNodB(EbNodB, bottleneck: int = 3, rate_Fs: bool = True):
@@ -374,6 +415,35 @@ class BatchEngine:
             raise RuntimeError("rade_batch_channel_rs_pa failed")
         return (out, stats) if want_stats else out
 
+    # ---- sample-clock offset -----------------------------------------------------------------
+    def resample(self, x, ppm, t0=0.0, mode: str = "sinc32", n_out=None, n_in=None, n0=0, in_base=0, out=None):
+        """The fractional resampler (rade_batch_resample): x cuda complex64 [B, N] -> (y complex64 [B, max n_out], n_out int32 [B]).  Output n of a stream sits at
+        t0 + n (1 + ppm 1e-6) input samples: ppm_from_rates(8000, 8020) stretches the signal as a sound card at 8020 Hz does.  ppm, t0, n_out, n_in (readable samples of
+        each row, default N), n0 (index of the first output written) and in_base (absolute index of x[b, 0]): scalars or B per-stream values.  n_out defaults to
+        rade_resample_count(in_base + n_in, t0, ppm) - n0: every output whose position lies inside the input.  mode "sinc32" or "linear" (dsp.py:564-575).  Samples
+        of y past a stream's n_out are zeros (left alone in a caller's `out`)."""
+        import torch
+        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == self.B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        B = self.B
+        ppm = _per_stream(B, ppm, np.float64, "ppm"); t0 = _per_stream(B, t0, np.float64, "t0")
+        n0 = _per_stream(B, n0, np.int64, "n0"); in_base = _per_stream(B, in_base, np.int64, "in_base")
+        n_in = _per_stream(B, x.shape[1] if n_in is None else n_in, np.int32, "n_in")
+        if n_in.min() < 0 or n_in.max() > x.shape[1]:
+            raise ValueError(f"n_in: between 0 and the {x.shape[1]} samples of a row")
+        if n_out is None:
+            n_out = np.array([max(resample_count(int(in_base[b]) + int(n_in[b]), t0[b], ppm[b]) - int(n0[b]), 0) for b in range(B)], np.int32)
+        else:
+            n_out = _per_stream(B, n_out, np.int32, "n_out")
+        if out is None:
+            out = torch.zeros((B, max(int(n_out.max()), 1)), dtype=torch.complex64, device=x.device)
+        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n_out.max()
+        p = ResampleParams(RESAMPLE_MODES[mode], 0.0, ppm.ctypes.data, t0.ctypes.data, n0.ctypes.data, in_base.ctypes.data)
+        xs = x.stride(0) if B > 1 else x.shape[1]              # (a one-row tensor may carry any stride in its first dimension)
+        ys = out.stride(0) if B > 1 else out.shape[1]
+        if self.lib.rade_batch_resample(self.h, x.data_ptr(), xs, n_in.ctypes.data, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
+            raise RuntimeError("rade_batch_resample failed (|ppm| <= 50000, n0 >= 0, n_out <= the row of out)")
+        return out, n_out
+
     # ---- channel ----------------------------------------------------------------------------
     def channel(self, tx, sigma, freq_offset=0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
                 G=None, noise=None, seed: int = 0, df_dt=0.0, sine_amp: float = 0.0, sine_freq: float = 0.0, rx_gain: float = 1.0):
@@ -604,3 +674,40 @@ class BatchEngine:
         d["z_hat"] = z[:got][(d["ret"] & 1) == 1]
         d["eoo_out"] = z[:got][(d["ret"] & 2) == 2][:, :NEOO_BITS]
         return d
+
+
+class ClockOffset:
+    """A sample-clock offset applied to streams that arrive in pieces (BatchEngine.resample is stateless: this keeps what the next piece needs).  Per stream the last 32
+    input samples stay on the device; feed() emits the outputs whose whole 32-tap window has arrived, flush() the rest (their windows run into zeros, as at the end of a
+    whole-stream call).  The concatenated outputs of a stream are bit-identical to one resample() call over the whole stream."""
+    HIST = 32
+
+    def __init__(self, engine: BatchEngine, ppm, t0=0.0, mode: str = "sinc32"):
+        import torch
+        self.eng, self.mode = engine, mode
+        self.ppm = _per_stream(engine.B, ppm, np.float64, "ppm"); self.t0 = _per_stream(engine.B, t0, np.float64, "t0")
+        self.tail = torch.zeros((engine.B, self.HIST), dtype=torch.complex64, device=engine.device)      # input samples [n_fed - 32, n_fed); zeros ahead of the stream
+        self.n_fed = 0                                                # input samples taken so far (every stream gets pieces of the same length)
+        self.n_done = np.zeros(engine.B, np.int64)                    # outputs emitted so far
+
+    def _emit(self, buf, in_end: int):
+        """the outputs of positions below in_end that have not been emitted, from buf = input samples [n_fed - 32, ..)"""
+        upto = np.array([resample_count(in_end, self.t0[b], self.ppm[b]) for b in range(self.eng.B)], np.int64)
+        n_out = np.maximum(upto - self.n_done, 0).astype(np.int32)
+        y, _ = self.eng.resample(buf, self.ppm, self.t0, self.mode, n_out=n_out, n0=self.n_done, in_base=self.n_fed - self.HIST)
+        self.n_done += n_out
+        return y, n_out
+
+    def feed(self, x):
+        """x cuda complex64 [B, n]: the next n input samples of every stream -> (y [B, max n_out], n_out int32 [B])"""
+        import torch
+        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == self.eng.B
+        buf = torch.cat([self.tail, x], dim=1)
+        y, n_out = self._emit(buf, self.n_fed + x.shape[1] - 16)      # output n is complete once sample i(n) + 16 has arrived
+        self.tail = buf[:, -self.HIST:].contiguous()
+        self.n_fed += x.shape[1]
+        return y, n_out
+
+    def flush(self):
+        """the outputs whose position lies inside the input fed so far and whose window runs past it"""
+        return self._emit(self.tail, self.n_fed)
