@@ -101,7 +101,7 @@ typedef struct {
     float snrdB_3k_est; float pad2;
 } rd_rx_trace;
 
-/* ---- launch shims (defined in rade_kernels.hip / rade_rx.hip) -------------------------------------------- */
+/* ---- launch shims (defined in rade_kernels.hip and its stage headers / rade_rx.hip) -------------------------------------------- */
 typedef void *rd_stream_t;
 
 /* Y[r, n] = act(sum_k A[r,k] W[n,k] + bias[n]) on f32 MFMA; rows r = b*T + t.

@@ -1,5 +1,5 @@
-// rade_devutil.h -- device-side helpers shared by the HIP translation units (rade_kernels.hip: transmit side, channel, GEMMs, scans;
-// rade_rx.hip: the receiver).  gfx950 only: 64-lane wavefronts, DPP lane exchange, hardware exp2 / rcp.
+// rade_devutil.h -- device-side helpers shared by the HIP translation units (rade_kernels.hip and its stage headers: transmit side, channel, GEMMs,
+// scans; rade_core_step.hip: single-stream steps; rade_rx.hip: the receiver).  gfx950 only: 64-lane wavefronts, DPP lane exchange, hardware exp2 / rcp.
 #ifndef RADE_DEVUTIL_H
 #define RADE_DEVUTIL_H
 #include <hip/hip_runtime.h>
@@ -49,7 +49,8 @@ __device__ __forceinline__ double dgrid_nc(double start, int i, double delta)
 }
 
 // one term of the modulator's 30-term IDFT: acc += s.re (w.re, w.im); acc += s.im (-w.im, w.re), as four fused multiply-adds.  Every place that synthesises a
-// transmit sample uses this one form, so the same sample comes out the same bits wherever it is computed.
+// transmit sample uses this one form, so the same sample comes out the same bits wherever it is computed.  Only the term is shared: the loop around it (carrier
+// order, one Winv load for five symbols) is written out in k_ofdm_mod, k_ofdm_mod_mp (rade_ofdm_mod.h) and k_tx_frame3 (rade_core_step.hip) and kept equal by hand.
 // Round 4 issued the four as two v_pk_fma_f32 (both components of a sample in one instruction, the (s.re, s.re) / (-w.im, w.re) operands formed by the
 // instruction's op_sel / neg_lo modifiers): 10 us faster per modulator launch, and NOT reproducible -- under load (three batches in flight) about one 16-sample
 // block in 15,000 frames came out different from run to run, always lanes 48..63 of a wavefront, always a data symbol, the encoder's latents bit-identical
@@ -182,6 +183,20 @@ __device__ __forceinline__ float2 gauss_pair(uint32_t u0, uint32_t u1)
     const float a = ((float)u0 + 0.5f) * (1.0f / 4294967296.0f), bq = ((float)u1 + 0.5f) * (1.0f / 4294967296.0f);
     const float rad = __builtin_amdgcn_sqrtf(-1.38629436112f * __builtin_amdgcn_logf(a));       // -2 ln a = -2 ln 2 log2 a
     return make_float2(rad * __builtin_amdgcn_cosf(bq), rad * __builtin_amdgcn_sinf(bq));
+}
+
+// a binary32 value as two binary16 planes, x = hi + lo to 22 bits: the operand form of every GEMM on the f16 matrix cores.  (Two outputs: a vector
+// return changed register allocation in the receiver.)
+__device__ __forceinline__ void split16(float x, _Float16 &hi, _Float16 &lo) { hi = (_Float16)x; lo = (_Float16)(x - (float)hi); }
+// an activation v in [-1, 1] as the two planes of 2^8 v: 2^8 (activations) x 2^10 (packed W), so that the low planes stay normal binary16
+__device__ __forceinline__ void split16_act(float v, _Float16 &hi, _Float16 &lo) { split16(256.0f * v, hi, lo); }
+
+// The one HOST-side helper of this header (it needs the kernel's address, so it lives with the kernels): a kernel that asks for more dynamic LDS than the
+// default limit needs the limit raised, per function and per device; done at that kernel's first launch on each device (one flag array per kernel)
+template <auto KERNEL, int BYTES> static inline void rd_dyn_lds_once()
+{
+    static int done[64]; int dev = 0; (void)hipGetDevice(&dev);
+    if (!done[dev & 63]) { (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES); done[dev & 63] = 1; }
 }
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));

@@ -33,7 +33,7 @@ __device__ __forceinline__ void encf_emit(const rd_encf_args &a, int b, int t, i
         _Float16 *o = (_Float16 *)a.yf + ((size_t)b * a.NQ + 1 + (t >> 5)) * EF_TILE + (col >> 4) * 1024 + ((col >> 3) & 1) * 256 + (t & 31) * 8 + (col & 4);
         f16x4 hi, lo;
 #pragma unroll
-        for (int c = 0; c < 4; c++) { const float x = 256.0f * v[c]; const _Float16 h = (_Float16)x; hi[c] = h; lo[c] = (_Float16)(x - (float)h); }
+        for (int c = 0; c < 4; c++) { _Float16 h, l; split16_act(v[c], h, l); hi[c] = h; lo[c] = l; }
         *(f16x4 *)o = hi; *(f16x4 *)(o + 512) = lo;
     } else {
         *(f32x4 *)(a.y + (size_t)b * a.y_sb + (size_t)t * a.y_st + ch0) = v;
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_encf_hist(unsigned short *xf_, int NQ, 
         if (dir == 0) {
             const f32x4 u0 = *(const f32x4 *)(xr + (size_t)k * RD_ENC_W + col), u1 = *(const f32x4 *)(xr + (size_t)k * RD_ENC_W + col + 4);
 #pragma unroll
-            for (int e = 0; e < 8; e++) { const float x = 256.0f * (e < 4 ? u0[e & 3] : u1[e & 3]); const _Float16 h = (_Float16)x; hi[e] = h; lo[e] = (_Float16)(x - (float)h); }
+            for (int e = 0; e < 8; e++) { _Float16 h, l; split16_act(e < 4 ? u0[e & 3] : u1[e & 3], h, l); hi[e] = h; lo[e] = l; }
         } else {
             const int ts = T - 2 + k;                     // source step; negative = still in the history tile (a call of one step)
             const _Float16 *s = ts >= 0 ? sb + (size_t)(1 + (ts >> 5)) * EF_TILE + fo + (ts & 31) * 8 : sb + fo + (32 + ts) * 8;

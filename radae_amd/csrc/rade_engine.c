@@ -873,7 +873,7 @@ int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *fea
 {
     ON_DEV(h);
     if (!h || !z_dev || n_steps <= 0 || n_steps > h->Tcap || !features_out_dev) return -1;
-    if (misaligned16(z_dev)) return -1;               /* the GEMMs read their A rows as f32x4 (rade_kernels.hip), and dense1's rows are z_dev's */
+    if (misaligned16(z_dev)) return -1;               /* the GEMMs read their A rows as f32x4 (rade_gemm.h), and dense1's rows are z_dev's */
     hipStream_t st = (hipStream_t)stream;
     if (reset_state) {
         hipMemsetAsync(h->dec2_h[0], 0, sizeof(float) * 5 * h->B * 96, st);

@@ -14,8 +14,6 @@
 // half index of x[logical row t][col] inside a plane; the history row is logical -1 (swizzle key 15), the zero row needs no key
 __device__ __forceinline__ int dq_xoff(int t, int col) { return (t + 1) * (DQ_XB * 8) + ((((col >> 3) ^ (t & 15)) << 3) | (col & 7)); }
 __device__ __forceinline__ int dq_hoff(int t, int col) { return t * (DQ_HB * 8) + ((((col >> 3) ^ (t & 15)) << 3) | (col & 7)); }
-// v in [-1, 1] -> the two planes of 2^8 v
-__device__ __forceinline__ void dq_split(float v, _Float16 &hi, _Float16 &lo) { const float x = 256.0f * v; hi = (_Float16)x; lo = (_Float16)(x - (float)hi); }
 
 enum { DQ_OUT_X = 0, DQ_OUT_GI = 1, DQ_OUT_GLOBAL = 2 };
 struct DqGemm {
@@ -156,7 +154,7 @@ __device__ __forceinline__ void dq2_gemm_tiles_(DecShared2 *sh_, const DqGemm g_
             }
             f16x4 oh, ol;
 #pragma unroll
-            for (int r = 0; r < 4; r++) { _Float16 a, b; dq_split(v[r], a, b); oh[r] = a; ol[r] = b; }
+            for (int r = 0; r < 4; r++) { _Float16 a, b; split16_act(v[r], a, b); oh[r] = a; ol[r] = b; }
             *(lds_f16x4 *)(xh + dq_xoff(tt, ocol + n)) = oh; *(lds_f16x4 *)(xl + dq_xoff(tt, ocol + n)) = ol;
         }
     }
@@ -194,7 +192,7 @@ __device__ void dq2_dense1(DecShared2 *sh, const float *z, const rd_lin w, int T
     for (int j = 0; j < 16; j++) {
         const int tt = (j & 3) + 8 * (j >> 2) + 4 * half;
         if (tt >= Tb) continue;
-        _Float16 a, b; dq_split(clamp1(gate_tanh(acc[j] + bias)), a, b);
+        _Float16 a, b; split16_act(clamp1(gate_tanh(acc[j] + bias)), a, b);
         sh->xh[0][dq_xoff(tt, col)] = a; sh->xl[0][dq_xoff(tt, col)] = b;
     }
 }
@@ -257,7 +255,7 @@ __device__ void dq2_scan(DecShared2 *sh, const float *Whh, const float *bhh, flo
         hj = (hj - n) * z + n;
         if (on && p == 0) {
             sh->hs[cur ^ 1][j] = hj;
-            _Float16 a, b; dq_split(clamp1(hj), a, b);
+            _Float16 a, b; split16_act(clamp1(hj), a, b);
             sh->hbh[0][dq_hoff(t, j)] = a; sh->hbl[0][dq_hoff(t, j)] = b;
         }
         g0r = g1r; g0z = g1z; g0n = g1n;
@@ -302,7 +300,7 @@ __device__ __forceinline__ void dq2_scan_mfma_body(DecShared2 *sh, const unsigne
     float hj = hstate[ju];
     __syncthreads();                                   // (the barrier behind the input projection / fix-up that wrote gi: taken behind the 9 / 18 weight fragments' round trip to L2)
     _Float16 (*hp)[2][H] = (_Float16 (*)[2][H])&sh->hs[0][0];           // [buffer][plane][k]: 2^8 h_{t-1} = hi + lo
-    if (finl) { _Float16 a, b; dq_split(hj, a, b); hp[0][0][ju] = a; hp[0][1][ju] = b; }
+    if (finl) { _Float16 a, b; split16_act(hj, a, b); hp[0][0][ju] = a; hp[0][1][ju] = b; }
     const float *gi = &sh->gi[0][0];
     float g0[3];
 #pragma unroll
@@ -354,9 +352,9 @@ __device__ __forceinline__ void dq2_scan_mfma_body(DecShared2 *sh, const unsigne
             hj = (hj - n) * z + n;
         }
         if (finl) {
-            _Float16 a, b; dq_split(hj, a, b);
+            _Float16 a, b; split16_act(hj, a, b);
             hp[cur ^ 1][0][ju] = a; hp[cur ^ 1][1][ju] = b;
-            dq_split(clamp1(hj), a, b);
+            split16_act(clamp1(hj), a, b);
             sh->hbh[0][dq_hoff(t, ju)] = a; sh->hbl[0][dq_hoff(t, ju)] = b;
         }
 #pragma unroll

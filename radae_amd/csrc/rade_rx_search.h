@@ -15,8 +15,8 @@ __device__ __forceinline__ void rx2_operand_scale(const RxScalars *S, float &rx_
 // a scaled sample v = hi + lo (22 bits), (re, im) packed in one word per plane; every caller has its own layout for the two words
 __device__ __forceinline__ void rx2_split16(float2 v, unsigned &hi, unsigned &lo)
 {
-    const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y;
-    const _Float16 l0 = (_Float16)(v.x - (float)h0), l1 = (_Float16)(v.y - (float)h1);
+    _Float16 h0, h1, l0, l1;
+    split16(v.x, h0, l0); split16(v.y, h1, l1);
     hi = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
     lo = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
 }

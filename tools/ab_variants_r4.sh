@@ -9,14 +9,14 @@ build() { # name, tree
 }
 fresh() { T=$(mktemp -d); git -C $R archive HEAD radae_amd/csrc include tools/experiments | tar -x -C $T; echo $T; }
 T=$(fresh); build base $T ""; rm -rf $T
-T=$(fresh); sed -i 's/__builtin_amdgcn_s_setprio(3);/;/' $T/radae_amd/csrc/rade_kernels.hip $T/radae_amd/csrc/rade_rx.hip; build noprio $T ""; rm -rf $T
+T=$(fresh); sed -i 's/__builtin_amdgcn_s_setprio(3);/;/' $T/radae_amd/csrc/rade_gru_scan.h $T/radae_amd/csrc/rade_rows.h $T/radae_amd/csrc/rade_chan.h $T/radae_amd/csrc/rade_rx.hip; build noprio $T ""; rm -rf $T
 T=$(fresh)
 python3 - $T <<'PY'
 import sys
 T = sys.argv[1]
 inc = open(T + "/tools/experiments/gemm16c_coalesced.inc").read()
 kern, disp = inc.split("// ---- dispatch (inside rd_launch_gemm, ahead of the k_gemm16p<3, 1, true> branch) ----")
-p = T + "/radae_amd/csrc/rade_kernels.hip"; s = open(p).read()
+p = T + "/radae_amd/csrc/rade_gemm.h"; s = open(p).read()
 s = s.replace('extern "C" int rd_launch_gemm(', kern + '\nextern "C" int rd_launch_gemm(', 1)
 anchor = "            if (a->Wscale) { dim3 g1(gx, ntt / 3); hipLaunchKernelGGL((k_gemm16p<3, 1, true>)"
 assert anchor in s
