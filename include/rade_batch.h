@@ -141,7 +141,10 @@ int rade_batch_encode(rade_batch *h, const float *features_dev, int n_steps, flo
 int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *features_out_dev, int reset_state, void *stream);
 /* symbol-domain channels: mode 0 = rate-Rs AWGN/multipath magnitudes (radae.py:604-634; H_dev [B][n_steps*40] per
  * QPSK symbol or NULL, p0 = sigma); mode 1 = BBFM FM-demodulator SNR model (bbfm.py:157-197; H_dev [B][n_steps*80]
- * or NULL, p0 = CNRdB, p1 = Gfm dB).  noise_dev: [B][n_steps*80] float32 (already scaled per component) or NULL -> Philox(seed) */
+ * or NULL, p0 = CNRdB, p1 = Gfm dB).  noise_dev: [B][n_steps*80] float32 (already scaled per component) or NULL -> Philox(seed).
+ * The generated draw runs over the WHOLE call, not per stream: real symbol i of the flat [B][n_steps][80] index takes counter (i >> 1, 0, 0, 0), words 0-1 only,
+ * the first Gaussian for even i and the second for odd i (mode 0: times 1 / sqrt(2)).  So stream b continues where stream b - 1 ended, a stream's draw depends on B
+ * and n_steps, and with one seed the call draws the words of stream 0 of the rate-Fs channel (third counter word 0 in both): give the two different seeds. */
 int rade_batch_channel_symbol(rade_batch *h, const float *z_dev, const float *H_dev, const float *noise_dev, float *z_hat_dev, int n_steps,
                               int mode, float p0, float p1, unsigned long long seed, void *stream);
 
@@ -179,7 +182,14 @@ typedef struct {
                            * The generated sequence is a property of the BUILD, not of the seed alone: Philox4x32-10 keyed by (seed, stream) with one counter per
                            * PAIR of samples (words 0-1 -> sample 2p, 2-3 -> sample 2p + 1; round 3: one counter per sample), Box-Muller on the hardware
                            * log2 / sqrt / sin / cos units (round 4).  Seeded statistics are reproducible within a build; anything that must be comparable
-                           * across builds (parity tests) passes noise_dev. */
+                           * across builds (parity tests) passes noise_dev.
+                           * Inside the signal and the EOO frame the generated sample is complex, sigma / sqrt(2) per component.  In n_pre and n_post it is REAL-valued:
+                           * the full sigma on the real part (the pair's first Gaussian), imaginary part exactly 0 (inference.py:277-284 adds a real randn there).  An
+                           * explicit noise_dev is added as complex, sigma x noise, everywhere.
+                           * The generated draw, pinned sample by sample by tests/test_device_noise_gpu.py against tests/noise_ref.py: key (seed & 0xffffffff,
+                           * seed >> 32); counter (p, b, 0, 0).  The third counter word names the consumer: 0 here and in rade_batch_channel_symbol, 1 in
+                           * rade_batch_multipath_gen (counter (x, 2 b + path, 1, 0), words 0-1 -> complex low-rate sample x), 2 in rade_batch_channel_rs_pa (counter
+                           * (i >> 1, b, 2, 0), i = 20 s + c).  Uniforms (float(u) + 0.5) 2^-32; (sqrt(-2 ln a) cos 2 pi q, sqrt(-2 ln a) sin 2 pi q). */
     unsigned long long seed;
     float sine_amp, sine_freq;   /* complex tone added over the whole output, inference.py:285-288 (--sine_amp/--sine_freq); 0 = none */
     float rx_gain;               /* final scale, inference.py:289 (--rx_gain); 0 is taken as 1 */

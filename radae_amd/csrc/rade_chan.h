@@ -193,6 +193,36 @@ extern "C" int rd_launch_multipath_h(const void *G, int n_g, int M, int n_sym, i
     return (int)hipGetLastError();
 }
 
+// The generator's two primitives alone, on chosen words (tests/test_device_noise_gpu.py against tests/noise_ref.py): words[i] = philox4x32(ctr[i], key) and
+// g[j] = gauss_pair(u[j]); without u, pair j is words 2 (j & 1), 2 (j & 1) + 1 of counter j >> 1 (m <= 2 n).  No caller in the library.
+__global__ __launch_bounds__(256) void k_noise_probe(const uint32_t *ctr, uint32_t k0, uint32_t k1, const uint32_t *u, uint32_t *words, float2 *g, int n, int m)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        uint32_t r[4];
+        philox4x32(ctr[4 * (size_t)i], ctr[4 * (size_t)i + 1], ctr[4 * (size_t)i + 2], ctr[4 * (size_t)i + 3], k0, k1, r);
+        for (int k = 0; k < 4; k++) words[4 * (size_t)i + k] = r[k];
+    }
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
+        uint32_t u0, u1;
+        if (u) { u0 = u[2 * (size_t)j]; u1 = u[2 * (size_t)j + 1]; }
+        else {
+            const size_t i = (size_t)(j >> 1);
+            uint32_t r[4];
+            philox4x32(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], k0, k1, r);
+            u0 = (j & 1) ? r[2] : r[0]; u1 = (j & 1) ? r[3] : r[1];
+        }
+        g[j] = gauss_pair(u0, u1);
+    }
+}
+extern "C" int rd_launch_noise_probe(const uint32_t *ctr, uint32_t k0, uint32_t k1, const uint32_t *u, uint32_t *words, float *g, int n, int m, rd_stream_t s)
+{
+    if (n < 0 || m < 0 || (n > 0 && (!ctr || !words)) || (m > 0 && (!g || (!u && (!ctr || (long)m > 2L * n))))) return -1;
+    if (n == 0 && m == 0) return 0;
+    int gx = ((n > m ? n : m) + 255) / 256; if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(k_noise_probe, dim3(gx), dim3(256), 0, (hipStream_t)s, ctr, k0, k1, u, words, (float2 *)g, n, m);
+    return (int)hipGetLastError();
+}
+
 // Symbol-domain channels of the non-OFDM configurations.
 //  mode 0 (rate-Rs, radae.py:604-634, bottleneck 1): QPSK symbol k = (z[2k], z[2k+1]) * H[k] + sigma * CN(0,1)
 //  mode 1 (BBFM, bbfm.py:157-197): per real symbol, FM demodulator SNR from the carrier-to-noise ratio:

@@ -240,6 +240,10 @@ int rd_launch_channel(const rd_chan_args *a, rd_stream_t s);
 /* Doppler-spread generator: taps_dev [n_taps] f32, noise optional, G [B][n_out][2] c64 */
 int rd_launch_multipath_gen(const float *taps_dev, int n_taps, int low_ratio, int n_out, const void *noise_low, unsigned long long seed, void *G, void *ybuf, int B, rd_stream_t s);
 int rd_multipath_gen_needs_scratch(int low_ratio, int n_out);
+/* the noise generator's primitives on chosen words (k_noise_probe; tests only): words[i] = Philox4x32-10(ctr[i], (k0, k1)), g[j] = gauss_pair(u[j]); u NULL: pair j is
+ * words 2 (j & 1), 2 (j & 1) + 1 of counter j >> 1, m <= 2 n.  All pointers device memory, 4-byte aligned (g: 8) */
+int rd_launch_noise_probe(const uint32_t *ctr /*[n][4]*/, uint32_t k0, uint32_t k1, const uint32_t *u /*[m][2] or NULL*/, uint32_t *words /*[n][4]*/,
+                          float *g /*[m][2]*/, int n, int m, rd_stream_t s);
 int rd_launch_multipath_h(const void *G, int n_g, int M, int n_sym, int Nc, float dRs, int want_complex, float *H, int B, rd_stream_t s);
 
 /* CoreDecoderStatefull.forward (radae_base.py:388-430) for the pending rows of one stream, run inside the receiver

@@ -22,6 +22,7 @@
 //                   EOO / noise framing (radae.py:529-589, inference.py:263-284)
 //   k_multipath_gen / k_multipath_h   Watterson Doppler-spread samples and the rate-Rs channel matrix (doppler_spread.m, multipath_samples.m)
 //   k_chan_symbol   symbol-domain channels of the non-OFDM configurations (radae.py:604-634, bbfm.py:157-197)
+//   k_noise_probe   philox4x32 and gauss_pair alone on chosen words, for the tests of the generated noise (no caller in the library)
 // The receiver (k_rx_sync2, band-pass pre-pass, k_batch_reset) is rade_rx.hip; the batched encoder rade_enc.hip; single-stream steps rade_core_step.hip.
 //
 // Written for gfx950 only: 64-lane wavefronts, MFMA f32 32x32x2, LDS-resident per-stream working sets.

@@ -140,23 +140,27 @@ def test_ber_awgn_high_snr_is_error_free(torch_dev):
 
 
 def test_ber_awgn_operating_point(torch_dev):
-    """inference_ber_awgn: Eb/No 0 dB, +1 Hz uncorrected: BER < 0.5 erfc(sqrt(10^((0 - 2) / 10))) = 0.131"""
+    """inference_ber_awgn: Eb/No 0 dB, +1 Hz uncorrected: BER < 0.5 erfc(sqrt(10^((0 - 2) / 10))) = 0.131, and above the no-loss theory at the nominal Eb/No,
+    0.5 erfc(1) = 0.0786: the waveform spends 1.76 dB on cyclic prefix and pilots, so a BER below the floor means the generator delivers too little noise"""
     from math import erfc, sqrt
     e, n = ber_run(torch_dev, 0.0, 1.0, False)
     assert n >= 10 ** 6
     bar = 0.5 * erfc(sqrt(10 ** ((0 - 2) / 10)))
-    print(f"AWGN 0 dB: BER {e / n:.4f} over {n} bits (bar {bar:.4f})")
-    assert e / n < bar
+    floor = 0.5 * erfc(1.0)
+    print(f"AWGN 0 dB: BER {e / n:.4f} over {n} bits (floor {floor:.4f}, bar {bar:.4f})")
+    assert floor < e / n < bar
 
 
 def test_ber_mpp_operating_point(torch_dev):
-    """inference_ber_mpp: Eb/No 0 dB, MPP (64 device-generated Doppler realisations), +1 Hz: BER < 0.5 (1 - sqrt(EbNo / (EbNo + 1))) with 2 dB loss = 0.189"""
+    """inference_ber_mpp: Eb/No 0 dB, MPP (64 device-generated Doppler realisations), +1 Hz: BER < 0.5 (1 - sqrt(EbNo / (EbNo + 1))) with 2 dB loss = 0.189,
+    and above the same curve without loss at the nominal Eb/No, 0.5 (1 - sqrt(1 / 2)) = 0.1464"""
     e, n = ber_run(torch_dev, 0.0, 1.0, True)
     assert n >= 10 ** 6
     ebno = 10 ** ((0 - 2) / 10)
     bar = 0.5 * (1 - np.sqrt(ebno / (ebno + 1)))
-    print(f"MPP 0 dB: BER {e / n:.4f} over {n} bits (bar {bar:.4f})")
-    assert e / n < bar
+    floor = 0.5 * (1 - np.sqrt(0.5))
+    print(f"MPP 0 dB: BER {e / n:.4f} over {n} bits (floor {floor:.4f}, bar {bar:.4f})")
+    assert floor < e / n < bar
 
 
 def test_cli_inference_ber_test(tmp_path):
