@@ -22,6 +22,8 @@
  *                          inference.py:213-229 (its Eq / PAPR measurements)
  *   rade_batch_resample    dsp.py:564-575 (sample_clock_offset, the linear mode) and what the ctests radae_rx_dfs / radae_rx_slip_* do with `sox -r 8000 .. -r 8020`:
  *                          the receiver's sound card running at another rate than the transmitter's, per stream
+ *   rade_batch_wire_in     int16tof32.py:40-50 (with --zeropad: a real channel becomes IQ with Q = 0), what every streaming ctest puts in front of the receiver
+ *   rade_batch_wire_out    f32toint16.py:42-54 (--real --scale 8192 feeds the radio), with saturation and level meters
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -105,6 +107,10 @@ int rade_batch_n_streams(const rade_batch *h);
  *   rade_batch_loss                         features_dev (float; f_stride >= n_in f_row), hat_dev (float; h_stride >= n_hat h_row) in; frame_loss_dev (float; fl_stride >= n_hat, checked)
  *   rade_batch_resample                     x_dev (complex64; x_stride >= every n_in, checked) in; y_dev (complex64; y_stride >= every n_out, checked): n_out[b] samples of row b are written,
  *                                           8 bytes at a time (any y_stride, any parity of n_out, element alignment); x is read inside [b x_stride, b x_stride + n_in[b]) only
+ *   rade_batch_wire_in                      in_dev (int16; in_stride >= n or 2 n int16, checked; 2-byte alignment) in; out_dev (complex64; out_stride >= n, checked): n[b] samples of row b
+ *   rade_batch_wire_out                     x_dev (complex64; x_stride >= n, checked) in; out_dev (int16; out_stride >= n or 2 n int16, checked; 2-byte alignment): n[b] samples of row b.
+ *                                           Both move 16-byte words where the int16 row crosses 16-byte boundaries and single elements in front of the first and behind the
+ *                                           last (rade_wire.hip): any stride, any count, element alignment
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -249,6 +255,28 @@ int rade_batch_resample(rade_batch *h, const void *x_dev, long x_stride, const i
 long long rade_resample_count(long long in_end, double t0, double ppm);
 /* host only, no handle, no GPU: the table T */
 void rade_resample_taps(float *out /* [257][32] */);
+
+/* ---- the sound-card wire: int16 samples in and out, every stream in one launch (rade_wire.hip) -------------------------------------------
+ * Counts are in SAMPLES: stream b converts n_host[b] of them.  RADE_WIRE_REAL: one int16 per sample; RADE_WIRE_IQ: two (I, Q).  Strides of the int16 buffers are in int16
+ * elements.  (int16tof32.py drops a trailing odd int16 of a FILE, a property of its 4-byte reads; radae_amd/wire.py keeps that, these calls have no such rule.)
+ * rade_batch_wire_in: out = (gain (float)s, +0.0f) in real mode (`int16tof32.py --zeropad`), (gain (float)I, gain (float)Q) in IQ mode; one float32 multiply per component,
+ *   so gain = 1 gives the bytes of the reference script.
+ * rade_batch_wire_out: per written component v = x * scale (one float32 multiply, rounded once), then
+ *       v is NaN -> 0        v >= 32768 -> 32767        v <= -32769 -> -32768        else (int16)v truncated toward zero (f32toint16.py:48-49; -32768.99 gives -32768: it fits)
+ *   RADE_WIRE_REAL writes (and meters) the I component only (`f32toint16.py --real`), RADE_WIRE_IQ both.
+ *   meters_host [B][4] doubles or NULL, per stream over its written components: [0] the largest |v| (before saturation, +inf included; what an operator sets the drive by),
+ *   [1] sum of v^2 (each v^2 exact in double; RMS = sqrt([1] / components)), [2] components that saturated, [3] NaN components (counted, and in neither [0] nor [1]).
+ *   The sums are added in a fixed order (fixed chunks per stream -- their number depends on B alone --, a tree inside a chunk, no atomics): two identical calls give
+ *   identical bits, and a stream's meters do not depend on the other streams.  With meters_host the call synchronises `stream`; without it, it does not.
+ * Neither call keeps state on the device: a call is a pure function of its arguments (the rule of rade_batch_resample).  The counts travel in one small copy ahead of the
+ * launch, from one of eight staging records used in turn: a call waits for the call eight before it, not for its stream.
+ * Refused with -1 on the host, before any launch and with nothing written: NULL or misaligned pointers (2 bytes for int16, 8 for complex64), NULL counts, a negative count,
+ * a stride shorter than the row, an unknown mode, a gain or scale that is not finite.  Return 0.  Any engine (the model is not used; no encoder or receiver state is touched). */
+enum { RADE_WIRE_REAL = 0, RADE_WIRE_IQ = 1 };
+int rade_batch_wire_in (rade_batch *h, const void *in_dev, long in_stride, const int *n_host, int mode, float gain,
+                        void *out_dev, long out_stride, void *stream);
+int rade_batch_wire_out(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int mode, float scale,
+                        void *out_dev, long out_stride, double *meters_host /* [B][4] or NULL */, void *stream);
 
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the

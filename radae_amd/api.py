@@ -180,8 +180,19 @@ class radae_rx_engine:
 
     def do_radae_rx(self, buffer_complex, floats_out):
         x = np.ascontiguousarray(buffer_complex, dtype=np.complex64)
-        assert x.size >= self._nin and floats_out.dtype == np.float32 and floats_out.size == self.n_floats_out
-        _, st, _ = self.eng.rx(self._torch.tensor(x[None, :self._nin], device=self.dev), max_calls=1, features_out=self._rows, eoo_out=self._eoo)
+        assert x.size >= self._nin
+        return self._rx_dev(self._torch.tensor(x[None, :self._nin], device=self.dev), floats_out)
+
+    def do_radae_rx_int16(self, buffer_i16, floats_out, iq: bool = False):
+        """the same call fed from the sound-card wire: get_nin() int16 samples (iq: pairs ..IQIQ..), converted on the device (BatchEngine.wire_in) ahead of the receiver"""
+        k = 2 if iq else 1
+        s = np.ascontiguousarray(buffer_i16, dtype=np.int16)
+        assert s.size >= k * self._nin
+        return self._rx_dev(self.eng.wire_in(self._torch.tensor(s[None, :k * self._nin], device=self.dev), iq=iq), floats_out)
+
+    def _rx_dev(self, x_dev, floats_out):
+        assert floats_out.dtype == np.float32 and floats_out.size == self.n_floats_out
+        _, st, _ = self.eng.rx(x_dev, max_calls=1, features_out=self._rows, eoo_out=self._eoo)
         s = st[0]
         assert s.n_calls == 1
         self._nin, self._sync, self._snr = s.nin, s.sync, s.snr_dB

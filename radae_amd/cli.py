@@ -1,8 +1,9 @@
 """stdin / stdout filters with the command lines of the reference's Python tools:
 
-    python -m radae_amd.cli txe [--txbpf] [--bypass_enc] [--eoo_data_test] [--model_name BLOB]     features.f32 (or z.f32) -> IQ.f32      /root/reference/radae_txe.py:146-180
-    python -m radae_amd.cli rxe [--bypass_dec] [--disable_unsync S] [--foff_err HZ] [--eoo_data_test] [--no_stdout] [-v N] [--model_name BLOB]
-                                                                                                     IQ.f32 -> features.f32 (or z_hat.f32)  /root/reference/radae_rxe.py:332-371
+    python -m radae_amd.cli txe [--txbpf] [--bypass_enc] [--eoo_data_test] [--model_name BLOB] [--int16_real SCALE]
+                                                                                                     features.f32 (or z.f32) -> IQ.f32 (or I.int16)  /root/reference/radae_txe.py:146-180
+    python -m radae_amd.cli rxe [--bypass_dec] [--disable_unsync S] [--foff_err HZ] [--eoo_data_test] [--no_stdout] [-v N] [--model_name BLOB] [--int16 | --int16_iq]
+                                                                                                     IQ.f32 (or .int16) -> features.f32 (or z_hat.f32)  /root/reference/radae_rxe.py:332-371
 
     python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --rate_Fs --EbNodB .. [--g_file g.f32] --write_rx rx.f32 [...]    the channel-simulation run of inference.py (rate Fs)
     python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --bottleneck 3 --auxdata --EbNodB .. [--h_file h.f32] [--mp_test] [--phase_offset rad]          the same without --rate_Fs: the rate-Rs channel
@@ -30,7 +31,13 @@ def _txe(argv):
     ap.add_argument("--txbpf", action="store_true", help="enable Tx BPF")
     ap.add_argument("--bypass_enc", action="store_true", help="Bypass core encoder, read z from stdin")
     ap.add_argument("--eoo_data_test", action="store_true", help="experimental EOO data test - tx test frame")
+    ap.add_argument("--int16_real", type=float, default=None, metavar="SCALE", help="write int16(I * SCALE) instead of IQ.f32 (`| f32toint16.py --real --scale SCALE`), converted on "
+                    "the device; prints `peak: .. rms: .. clipped: ..` of the written samples on stderr")
     args = ap.parse_args(argv)
+    eng = None
+    if args.int16_real is not None and not args.bypass_enc:  # the last metre to the radio runs on the device (rade_batch_wire_out): any engine serves, the bypass transmitter
+        from . import engine                                 # has one; this one is opened ahead of the rade_api.h handle, whose library must find torch's HIP runtime loaded
+        eng = engine.BatchEngine(1, max_tx_mf=1, blob=args.model_name or None)
     tx = api.radae_tx_bypass_enc(args.model_name, txbpf_en=args.txbpf) if args.bypass_enc else api.radae_tx(args.model_name, txbpf_en=args.txbpf)
     if args.eoo_data_test:                                  # radae_txe.py:157-163: the seeded bits the receiver side regenerates
         rng = np.random.default_rng(65647)
@@ -40,16 +47,29 @@ def _txe(argv):
     n_in = tx.get_n_floats_in()
     tx_out = np.zeros(tx.get_Nmf(), np.complex64)
     inp, out = sys.stdin.buffer, sys.stdout.buffer
+    emit = lambda iq: out.write(iq.tobytes())
+    if args.int16_real is not None:
+        import torch
+        eng = eng or tx.eng
+        level = {"peak": 0.0, "s2": 0.0, "n": 0, "clipped": 0}
+
+        def emit(iq):
+            s, m = eng.wire_out(torch.tensor(iq[None], device="cuda"), scale=args.int16_real, meters=True)
+            out.write(s.cpu().numpy().tobytes())
+            n = iq.size - int(m.nan[0])
+            level["peak"] = max(level["peak"], float(m.peak[0])); level["s2"] += float(m.rms[0]) ** 2 * n; level["n"] += n; level["clipped"] += int(m.clipped[0])
     while True:
         buf = inp.read(n_in * struct.calcsize("f"))
         if len(buf) != n_in * struct.calcsize("f"):
             break
         tx.do_radae_tx(np.frombuffer(buf, np.float32), tx_out)
-        out.write(tx_out.tobytes())
+        emit(tx_out)
     eoo = np.zeros(tx.get_Neoo(), np.complex64)
     tx.do_eoo(eoo)
-    out.write(eoo.tobytes())
+    emit(eoo)
     out.flush()
+    if args.int16_real is not None:
+        print(f"peak: {level['peak']:.1f} rms: {np.sqrt(level['s2'] / max(level['n'], 1)):.1f} clipped: {level['clipped']}", file=sys.stderr)
     return 0
 
 
@@ -62,9 +82,14 @@ def _rxe(argv):
     ap.add_argument("--foff_err", type=float, default=0.0, help="Artifical freq offset error after first sync to test false sync (the C ABI offers the 10 Hz test only)")
     ap.add_argument("--bypass_dec", action="store_true", help="Bypass core decoder, write z_hat to stdout")
     ap.add_argument("--eoo_data_test", action="store_true", help="experimental EOO data test - count bit errors")
+    ap.add_argument("--int16", action="store_true", help="stdin is int16 samples of one real channel (what `int16tof32.py --zeropad` is piped in for), converted on the device")
+    ap.add_argument("--int16_iq", action="store_true", help="stdin is int16 ..IQIQ.. (`int16tof32.py`), converted on the device")
     ap.set_defaults(use_stdout=True)
     args = ap.parse_args(argv)
-    if args.bypass_dec or args.disable_unsync:              # both are switches of the batched engine (rade_api.h has neither)
+    if args.int16 and args.int16_iq:
+        raise SystemExit("radae_amd.cli rxe: --int16 (one real channel) or --int16_iq, not both")
+    wire16 = args.int16 or args.int16_iq                     # the conversion is a call of the batched engine (rade_batch_wire_in)
+    if args.bypass_dec or args.disable_unsync or wire16:              # both are switches of the batched engine (rade_api.h has neither)
         cls = api.radae_rx_bypass_dec if args.bypass_dec else api.radae_rx_engine
         rx = cls(args.model_name, foff_err=args.foff_err, disable_unsync=args.disable_unsync)
     else:
@@ -74,10 +99,11 @@ def _rxe(argv):
     mf = 0
     while True:
         nin = rx.get_nin()
-        buf = inp.read(nin * struct.calcsize("ff"))
-        if len(buf) != nin * struct.calcsize("ff"):
+        n_bytes = nin * struct.calcsize("hh" if args.int16_iq else "h" if args.int16 else "ff")
+        buf = inp.read(n_bytes)
+        if len(buf) != n_bytes:
             break
-        ret = rx.do_radae_rx(np.frombuffer(buf, np.complex64), floats_out)
+        ret = rx.do_radae_rx_int16(np.frombuffer(buf, np.int16), floats_out, iq=args.int16_iq) if wire16 else rx.do_radae_rx(np.frombuffer(buf, np.complex64), floats_out)
         mf += 1
         if args.v >= 2:
             print(f"{mf:3d} sync: {int(rx.get_sync())} nin: {rx.get_nin():4d} SNRdB: {rx.get_snrdB_3k_est():3d} ret: {ret}", file=sys.stderr)

@@ -228,6 +228,20 @@ typedef struct {
 } rd_clk_args;
 int rd_launch_clk_resample(const rd_clk_args *a, rd_stream_t s);
 
+/* the sound-card wire of rade_batch_wire_in / rade_batch_wire_out (rade_wire.hip): int16 rows on one side, complex64 rows on the other; k_wire_in reads i16 and writes
+ * c64, k_wire_out the other way round.  One workgroup per (chunk, stream), n_ch chunks per stream */
+#define RD_WIRE_NCH_MAX 64
+typedef struct {
+    void *i16; long i16_stride;                                 /* stream b at + b * i16_stride int16 elements */
+    void *c64; long c64_stride;                                 /* stream b at + b * c64_stride samples */
+    const int *n;                                               /* device [B]: samples of every stream */
+    int mode, B, n_ch;                                          /* 0 real (one int16 per sample), 1 IQ (two) */
+    float k;                                                    /* gain (in) or scale (out) */
+    double *part, *meters;                                      /* k_wire_out, optional: [B][n_ch][4] partials and [B][4] = peak |v|, sum v^2, clipped, NaN components */
+} rd_wire_args;
+int rd_launch_wire_in(const rd_wire_args *a, rd_stream_t s);
+int rd_launch_wire_out(const rd_wire_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

@@ -73,6 +73,7 @@ typedef struct { float *wp, *bias; unsigned short *wp16, *wa16; float *wscale, *
 
 #define RADE_PROF_MAXEV 256   /* launches recorded per profiled interval before the events are drained */
 #define RADE_PROF_MAXIV 4096  /* launch intervals kept per profiling session (rade_batch_profile_intervals) */
+#define RD_WIRE_SLOTS 8
 struct rade_batch {
     struct owned *owned;                  /* every device / pinned allocation of the engine (own): rade_batch_close frees exactly these */
     int alloc_failed;                     /* sticky: an allocation the engine cannot do without failed (rade_batch_open_mem checks it) */
@@ -100,6 +101,9 @@ struct rade_batch {
     float *chan_ps, *chan_ps_host;            /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */
     float *rs_sigma; double *rs_part, *rs_stats;   /* rade_batch_channel_rs_pa: [B] per-stream sigma, [B][RD_RS_NCH][4] measurement partials, [B][3] measurements, allocated on first use */
     float *clk_taps; rd_clk_stream *clk_ps, *clk_ps_host;   /* rade_batch_resample: the taps [257][32]; [B] per-stream records on the device and their pinned staging copy, allocated on first use */
+    /* rade_batch_wire_in / _out: the [B] sample counts of the last RD_WIRE_SLOTS calls on the device and their pinned staging copies, one slot per call in turn (a call
+     * does not wait for its stream: it waits for the call that used its slot RD_WIRE_SLOTS calls ago); [B][RD_WIRE_NCH_MAX][4] meter partials, [B][4] meters.  First use. */
+    int *wire_n, *wire_n_host; hipEvent_t wire_ev[RD_WIRE_SLOTS]; unsigned wire_used, wire_seq; double *wire_part, *wire_meters;
     int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
@@ -447,6 +451,7 @@ void rade_batch_close(rade_batch *h)
     ON_DEV(h);
     while (h->owned) disown(h, h->owned->p);
     if (h->ev_block) hipEventDestroy(h->ev_block);
+    for (int i = 0; i < RD_WIRE_SLOTS; i++) if (h->wire_ev[i]) hipEventDestroy(h->wire_ev[i]);
     __atomic_sub_fetch(&g_engines_open, 1, __ATOMIC_RELAXED);
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) if (h->prof_ev[i]) hipEventDestroy(h->prof_ev[i]);
     free(h->lcg_seeds);
@@ -1032,6 +1037,83 @@ int rade_batch_resample(rade_batch *h, const void *x_dev, long x_stride, const i
     PROF_BEGIN(h, stream);
     if (rd_launch_clk_resample(&a, stream)) return -1;
     PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- the sound-card wire: int16 <-> complex64 (rade_wire.hip) ---------------------------------------------------------------------------------- */
+/* Checks every stream, then puts the counts on the device in the call's slot and fills the launch record; 1 = nothing to do (no stream has a sample), -1 = refused */
+static int wire_prepare(rade_batch *h, const void *i16, long i16_stride, const void *c64, long c64_stride, const int *n_host, int mode, float k, rd_wire_args *a, int *slot, hipStream_t st)
+{
+    if (!h || !i16 || !c64 || !n_host) return -1;
+    if (((uintptr_t)i16 & 1) || ((uintptr_t)c64 & 7)) return -1;
+    if ((mode != RADE_WIRE_REAL && mode != RADE_WIRE_IQ) || !isfinite(k)) return -1;
+    const int B = h->B;
+    int max_n = 0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        const int n = n_host[b];
+        if (n < 0 || n > c64_stride || (long)n << mode > i16_stride) return -1;
+        if (n > max_n) max_n = n;
+    }
+    if (!h->wire_n_host && !(h->wire_n_host = pinned_alloc_opt(h, sizeof(int) * RD_WIRE_SLOTS * B))) return -1;
+    if (dev_grow(h, &h->wire_n, NULL, (long)RD_WIRE_SLOTS * B, sizeof(int), 1)) return -1;
+    const int s = (int)(h->wire_seq++ % RD_WIRE_SLOTS);
+    if (!h->wire_ev[s] && hipEventCreateWithFlags(&h->wire_ev[s], hipEventDisableTiming) != hipSuccess) { h->wire_ev[s] = NULL; return -1; }
+    if ((h->wire_used >> s & 1) && hipEventSynchronize(h->wire_ev[s]) != hipSuccess) return -1;     /* the slot's previous call has read its counts */
+    h->wire_used &= ~(1u << s);
+    memcpy(h->wire_n_host + (size_t)s * B, n_host, sizeof(int) * B);
+    if (hipMemcpyAsync(h->wire_n + (size_t)s * B, h->wire_n_host + (size_t)s * B, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    memset(a, 0, sizeof *a);
+    a->i16 = (void *)i16; a->i16_stride = i16_stride; a->c64 = (void *)c64; a->c64_stride = c64_stride; a->n = h->wire_n + (size_t)s * B;
+    a->mode = mode; a->B = B; a->k = k;
+    a->n_ch = 4096 / B < 4 ? 4 : 4096 / B > RD_WIRE_NCH_MAX ? RD_WIRE_NCH_MAX : 4096 / B;      /* a function of B alone: a stream's meter sums do not depend on the other streams */
+    *slot = s;
+    return max_n ? 0 : 1;
+}
+/* the slot is busy until what was queued on st up to here has run */
+static int wire_done(rade_batch *h, int slot, hipStream_t st)
+{
+    if (hipEventRecord(h->wire_ev[slot], st) != hipSuccess) return -1;
+    h->wire_used |= 1u << slot;
+    return 0;
+}
+
+int rade_batch_wire_in(rade_batch *h, const void *in_dev, long in_stride, const int *n_host, int mode, float gain, void *out_dev, long out_stride, void *stream)
+{
+    ON_DEV(h);
+    hipStream_t st = (hipStream_t)stream;
+    rd_wire_args a; int slot;
+    const int r = wire_prepare(h, in_dev, in_stride, out_dev, out_stride, n_host, mode, gain, &a, &slot, st);
+    if (r < 0) return -1;
+    if (r == 0) {
+        PROF_BEGIN(h, stream);
+        if (rd_launch_wire_in(&a, stream)) return -1;
+        PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
+    }
+    return wire_done(h, slot, st);
+}
+
+int rade_batch_wire_out(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int mode, float scale, void *out_dev, long out_stride, double *meters_host, void *stream)
+{
+    ON_DEV(h);
+    hipStream_t st = (hipStream_t)stream;
+    rd_wire_args a; int slot;
+    const int r = wire_prepare(h, out_dev, out_stride, x_dev, x_stride, n_host, mode, scale, &a, &slot, st);
+    if (r < 0) return -1;
+    const int B = h->B;
+    if (meters_host) {
+        if (dev_grow(h, &h->wire_part, NULL, (long)B * RD_WIRE_NCH_MAX * 4, sizeof(double), 1) || dev_grow(h, &h->wire_meters, NULL, 4L * B, sizeof(double), 1)) return -1;
+        a.part = h->wire_part; a.meters = h->wire_meters;
+    }
+    if (r == 0) {
+        PROF_BEGIN(h, stream);
+        if (rd_launch_wire_out(&a, stream)) return -1;
+        PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
+    }
+    if (wire_done(h, slot, st)) return -1;
+    if (meters_host) {
+        if (r) { memset(meters_host, 0, sizeof(double) * 4 * B); return 0; }     /* no stream has a sample: nothing was launched */
+        if (hipMemcpyAsync(meters_host, h->wire_meters, sizeof(double) * 4 * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    }
     return 0;
 }
 

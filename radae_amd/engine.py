@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -113,6 +113,9 @@ def load_library() -> C.CDLL:
         L.rade_batch_resample.argtypes = [vp, vp, C.c_long, vp, vp, C.c_long, vp, C.POINTER(ResampleParams), vp]
         L.rade_resample_count.restype = C.c_longlong; L.rade_resample_count.argtypes = [C.c_longlong, C.c_double, C.c_double]
         L.rade_resample_taps.restype = None; L.rade_resample_taps.argtypes = [vp]
+    if hasattr(L, "rade_batch_wire_in"):
+        L.rade_batch_wire_in.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, vp, C.c_long, vp]
+        L.rade_batch_wire_out.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, vp, C.c_long, vp, vp]
     _lib = L
     return L
 
@@ -134,7 +137,18 @@ EXPORTED_SYMBOLS = [
     "rade_batch_loss", "rade_batch_channel_streams", "rade_batch_tx_channel_streams",
     "rade_batch_channel_rs_pa", "rade_sigma_from_EbNodB_rs3",
     "rade_batch_resample", "rade_resample_count", "rade_resample_taps",
+    "rade_batch_wire_in", "rade_batch_wire_out",
 ]
+WIRE_REAL, WIRE_IQ = 0, 1                                                          # rade_batch_wire_in / _out mode
+
+
+class WireMeters(NamedTuple):
+    """Level of what wire_out wrote, one value per stream: the largest |x scale| (before saturation), the RMS of x scale over the written components (NaN components
+    excluded), and how many components saturated / were NaN."""
+    peak: np.ndarray
+    rms: np.ndarray
+    clipped: np.ndarray
+    nan: np.ndarray
 
 RESAMPLE_MODES = {"sinc32": 0, "linear": 1}                                        # rade_resample_params.mode
 RESAMPLE_PPM_MAX = 50000.0
@@ -443,6 +457,45 @@ class BatchEngine:
         if self.lib.rade_batch_resample(self.h, x.data_ptr(), xs, n_in.ctypes.data, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_resample failed (|ppm| <= 50000, n0 >= 0, n_out <= the row of out)")
         return out, n_out
+
+    # ---- the sound-card wire ------------------------------------------------------------------
+    def wire_in(self, i16, n=None, iq: bool = False, gain: float = 1.0):
+        """int16 samples to complex64 on the device (rade_batch_wire_in; `int16tof32.py --zeropad` when real).  i16: cuda int16 [B, N], one real channel, or with iq
+        [B, N, 2] (or [B, 2 N]) ..IQIQ..; n: samples of each stream (a scalar or B values; default N).  Returns complex64 [B, max(n)] = gain * sample, Q = +0 for a real
+        channel; samples past a stream's n are zeros.  gain = 1 gives the reference script's bytes."""
+        import torch
+        assert i16.is_cuda and i16.dtype == torch.int16 and i16.shape[0] == self.B and (i16.dim() == 2 or (iq and i16.dim() == 3 and i16.shape[2] == 2))
+        assert i16.stride(-1) == 1 and (i16.dim() == 2 or i16.stride(1) == 2 or i16.shape[1] <= 1)
+        row = i16.shape[1] if i16.dim() == 3 or not iq else i16.shape[1] // 2
+        n = _per_stream(self.B, row if n is None else n, np.int32, "n")
+        if n.min() < 0 or n.max() > row:
+            raise ValueError(f"n: between 0 and the {row} samples of a row")
+        out = torch.zeros((self.B, max(int(n.max()), 1)), dtype=torch.complex64, device=i16.device)
+        ist = i16.stride(0) if self.B > 1 else row << int(iq)          # (a one-row tensor may carry any stride in its first dimension)
+        if self.lib.rade_batch_wire_in(self.h, i16.data_ptr(), ist, n.ctypes.data, WIRE_IQ if iq else WIRE_REAL, gain, out.data_ptr(), out.shape[1], _stream_ptr()):
+            raise RuntimeError("rade_batch_wire_in failed (a finite gain, rows of at least n samples)")
+        return out
+
+    def wire_out(self, x, n=None, real: bool = True, scale: float = 32767.0, meters: bool = False):
+        """complex64 samples to int16 on the device (rade_batch_wire_out; `f32toint16.py [--real] --scale S`): x cuda complex64 [B, N] -> int16 [B, N] of the I component
+        (real) or [B, N, 2] of I and Q, int16(x * scale) truncated toward zero, saturated to -32768 / 32767 where that does not fit, 0 for NaN.  n: samples of each stream
+        (default N); the rest of a row is zeros.  meters: also returns WireMeters (the call then synchronises)."""
+        import torch
+        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == self.B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        B, N = self.B, x.shape[1]
+        n = _per_stream(B, N if n is None else n, np.int32, "n")
+        if n.min() < 0 or n.max() > N:
+            raise ValueError(f"n: between 0 and the {N} samples of a row")
+        out = torch.zeros((B, N) if real else (B, N, 2), dtype=torch.int16, device=x.device)
+        m = np.zeros((B, 4), np.float64) if meters else None
+        xs = x.stride(0) if B > 1 else N
+        if self.lib.rade_batch_wire_out(self.h, x.data_ptr(), xs, n.ctypes.data, WIRE_REAL if real else WIRE_IQ, scale, out.data_ptr(), N if real else 2 * N,
+                                        m.ctypes.data if meters else None, _stream_ptr()):
+            raise RuntimeError("rade_batch_wire_out failed (a finite scale, rows of at least n samples)")
+        if not meters:
+            return out
+        comps = np.maximum((n.astype(np.float64) * (1 if real else 2)) - m[:, 3], 1.0)
+        return out, WireMeters(m[:, 0].copy(), np.sqrt(m[:, 1] / comps), m[:, 2].astype(np.int64), m[:, 3].astype(np.int64))
 
     # ---- channel ----------------------------------------------------------------------------
     def channel(self, tx, sigma, freq_offset=0.0, n_pre: int = 0, n_post: int = 0, with_eoo: bool = False,
