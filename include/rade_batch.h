@@ -24,6 +24,8 @@
  *                          the receiver's sound card running at another rate than the transmitter's, per stream
  *   rade_batch_wire_in     int16tof32.py:40-50 (with --zeropad: a real channel becomes IQ with Q = 0), what every streaming ctest puts in front of the receiver
  *   rade_batch_wire_out    f32toint16.py:42-54 (--real --scale 8192 feeds the radio), with saturation and level meters
+ *   rade_batch_rate_convert  the `sox .. -r 8000` stage in front of int16tof32.py in every off-air and sound-card pipeline (radae_rx.sh:33,39, README.md:570, evaluate.sh:119,
+ *                          analog_bbfm.sh:37,43): 48 or 44.1 kHz <-> the modem's 8 kHz, a polyphase L / M converter whose anti-alias filter scales with the ratio
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -111,6 +113,9 @@ int rade_batch_n_streams(const rade_batch *h);
  *   rade_batch_wire_out                     x_dev (complex64; x_stride >= n, checked) in; out_dev (int16; out_stride >= n or 2 n int16, checked; 2-byte alignment): n[b] samples of row b.
  *                                           Both move 16-byte words where the int16 row crosses 16-byte boundaries and single elements in front of the first and behind the
  *                                           last (rade_wire.hip): any stride, any count, element alignment
+ *   rade_batch_rate_convert                 x_dev (complex64, or int16 with one or two elements per sample; x_stride >= n_in, 2 n_in for int16 IQ, in elements of x, checked; 8- or
+ *                                           2-byte alignment) in; y_dev (complex64; y_stride >= every n_out, checked): n_out[b] samples of row b are written, 8 bytes at a time (any
+ *                                           y_stride, any parity of n_out, element alignment); x is read inside the n_in[b] samples of row b only
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -277,6 +282,49 @@ int rade_batch_wire_in (rade_batch *h, const void *in_dev, long in_stride, const
                         void *out_dev, long out_stride, void *stream);
 int rade_batch_wire_out(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int mode, float scale,
                         void *out_dev, long out_stride, double *meters_host /* [B][4] or NULL */, void *stream);
+
+/* ---- sample-rate conversion by a ratio L / M: 48 / 44.1 kHz <-> 8 kHz, every stream in one launch (rade_rate.hip) ---------------------------------------
+ * Every stream of a call is converted by the same ratio L / M (L up, M down, both >= 1; 1 / 6: 48 k -> 8 k, 80 / 441: 44.1 k -> 8 k).  The host reduces L and M by their gcd;
+ * everything below is about the reduced pair.
+ * Time base: output n of a stream (absolute index, n0 <= n < n0 + n_out) sits at input position n M / L:
+ *     i = floor(n M / L)    ph = (n M) mod L        64-bit integers, no rounding anywhere
+ * so an output's position is a pure function of (L, M, n): the call keeps no state on the device, and a stream converted in pieces equals the stream converted whole, bit
+ * for bit, when every piece is handed the inputs its windows cover.
+ * Filter: K = ceil(M / L) (integer), W = max(1, M / L) (real), T = 32 K taps per phase, H = 16 K;
+ *     t_j = j - (T / 2 - 1) - ph / L        g(t) = sinc(t / W) I0(10 sqrt(1 - (t / H)^2)) / I0(10) for |t| <= H, else 0        sinc(u) = sin(pi u) / (pi u)
+ *     C[ph][j] = g(t_j) / sum_j g(t_j)      made on the host in double and rounded once to float32; layout [L][T] (rade_rate_taps)
+ *   the Kaiser-windowed sinc of rade_batch_resample with its cut-off at the lower of the two Nyquist rates and its length stretched by the same factor.  For M <= L (W = 1)
+ *   sin(pi t) is formed from the fraction ph / L alone, as rade_resample_taps forms it: row 0 is then exactly the unit impulse at j = 15, L = M = 1 is a bit-exact copy, and
+ *   up-sampling reproduces x[k] at y[k L] bit for bit for finite non-zero samples; with L = M = 1 the table is row 0 of rade_resample_taps.  Every row sums to 1.
+ *   Unit tones |f| <= 2700 Hz are reproduced within 2e-5 at every phase for 1/6, 6/1, 80/441, 441/80, 1/2, 2/3, and the prototype is below -95 dB from 0.6 x the lower of
+ *   the two rates upward (tests/test_rate_host.py).
+ * Sum: y[n] = sum_{j = 0..T-1} C[ph][j] x[i + j - (T / 2 - 1)], one float32 accumulator per component, fused multiply-adds in the order j = 0..T-1.  in_base is the
+ *   absolute index of x[b][0]; samples outside [in_base, in_base + n_in) read as zero, at both ends and at negative indices, and nothing outside the stream's n_in samples
+ *   is read.
+ * Input format: RADE_RATE_C64 complex64; RADE_RATE_S16_REAL one int16 per sample; RADE_RATE_S16_IQ two (I, Q).  The two int16 formats take `gain` (ignored for complex64):
+ *   the operand is gain (float)s, one float32 multiply -- the rule of rade_batch_wire_in, so the fused call equals rade_batch_wire_in followed by the complex64 call, bit for
+ *   bit.  In the real format the output's imaginary part is exactly +0.0f; it is not computed.  Output: complex64, written in 8-byte stores.
+ * n_in_host, n_out_host: [B] counts; p->n0_host [B]: index of the first output written; p->in_base_host [B]; NULL = 0 for every stream.  Strides are in elements of their
+ *   own buffer (int16 IQ: x_stride >= 2 n_in); pointers are aligned to their element.  The per-stream values are copied to the device in one record per stream ahead of the
+ *   launch (the call synchronises `stream` once for that).  The table lives in the engine's device memory, keyed by the reduced (L, M), and is re-made by an upload on
+ *   `stream` when a call asks for another ratio: calls on one stream may alternate between ratios freely.
+ * Refused with -1 on the host, before any launch and with nothing written: NULL or misaligned pointers (8 bytes complex64, 2 bytes int16), NULL counts or p, a negative
+ *   count or n0, a stride shorter than its row, an unknown format, a gain that is not finite (int16 formats), L or M < 1, reduced K > 8, reduced L T > 16384 floats,
+ *   |in_base| > 2^62, (n0 + n_out) M past 2^62.  Admitted: 1/6 and 6/1 (T 192 and 32: 192 floats each), 80/441 (T 192: 15 360 floats), 441/80 (T 32: 14 112), 1/2, 2/3, 3/2.
+ * Returns 0.  Any engine (the model is not used; no encoder or receiver state is touched). */
+enum { RADE_RATE_C64 = 0, RADE_RATE_S16_REAL = 1, RADE_RATE_S16_IQ = 2 };
+typedef struct {
+    int L, M;                                     /* the ratio: output rate / input rate = L / M */
+    const long long *n0_host;                     /* [B] index of the first output sample this call writes, NULL = 0 */
+    const long long *in_base_host;                /* [B] absolute index of x[b][0], NULL = 0 */
+} rade_rate_params;
+int rade_batch_rate_convert(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, int format, float gain, void *y_dev, long y_stride,
+                            const int *n_out_host, const rade_rate_params *p, void *stream);
+/* host only: the number of n >= 0 with n M < in_end L, i.e. the outputs whose centre tap lies inside an input of in_end samples (-1: L or M < 1, or that many outputs pass
+ * the 2^62 limit) */
+long long rade_rate_count(long long in_end, int L, int M);
+/* host only, no handle, no GPU: the table C [L][T] of the reduced pair.  Returns T (-1: a ratio the call refuses); out == NULL only queries */
+int rade_rate_taps(int L, int M, float *out);
 
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the

@@ -1,8 +1,8 @@
 """stdin / stdout filters with the command lines of the reference's Python tools:
 
-    python -m radae_amd.cli txe [--txbpf] [--bypass_enc] [--eoo_data_test] [--model_name BLOB] [--int16_real SCALE]
+    python -m radae_amd.cli txe [--txbpf] [--bypass_enc] [--eoo_data_test] [--model_name BLOB] [--fs HZ] [--int16_real SCALE]
                                                                                                      features.f32 (or z.f32) -> IQ.f32 (or I.int16)  /root/reference/radae_txe.py:146-180
-    python -m radae_amd.cli rxe [--bypass_dec] [--disable_unsync S] [--foff_err HZ] [--eoo_data_test] [--no_stdout] [-v N] [--model_name BLOB] [--int16 | --int16_iq]
+    python -m radae_amd.cli rxe [--bypass_dec] [--disable_unsync S] [--foff_err HZ] [--eoo_data_test] [--no_stdout] [-v N] [--model_name BLOB] [--fs HZ] [--int16 | --int16_iq]
                                                                                                      IQ.f32 (or .int16) -> features.f32 (or z_hat.f32)  /root/reference/radae_rxe.py:332-371
 
     python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --rate_Fs --EbNodB .. [--g_file g.f32] --write_rx rx.f32 [...]    the channel-simulation run of inference.py (rate Fs)
@@ -11,7 +11,8 @@
     python -m radae_amd.cli bbfm_inference MODEL features.f32 features_hat.f32 [--CNRdB ..] [--h_file h_lmr60.f32] [--write_latent z.f32]    bbfm_inference.py
 
 so that the reference's shell pipelines (`cat features_in.f32 | python3 radae_txe.py > rx.f32`, `cat rx.f32 | python3 radae_rxe.py > features_out.f32`: CMakeLists.txt:300-420) run with
-`python3 -m radae_amd.cli txe|rxe` in their place.  Everything computes in libradehip.so on the GPU (radae_amd/api.py over include/rade_api.h; the bypass modes over a one-stream
+`python3 -m radae_amd.cli txe|rxe` in their place; `--fs 48000` (or 44100, ..) takes the place of the `sox .. -r 8000` stage of the off-air pipelines (radae_rx.sh:33,39): the
+rate conversion runs on the device (rade_batch_rate_convert).  Everything computes in libradehip.so on the GPU (radae_amd/api.py over include/rade_api.h; the bypass modes over a one-stream
 batched engine); `--model_name` takes a DNNw blob (the reference's `.pth` checkpoints are not in its tree), default weights/model19_check3.bin.  `--noauxdata` is not offered: model19_check3 has the aux symbol.
 """
 from __future__ import annotations
@@ -25,6 +26,52 @@ import numpy as np
 from . import api
 
 
+def _ratio(fs_out: int, fs_in: int):
+    """(L, M) of a conversion from fs_in to fs_out Hz, reduced"""
+    from math import gcd
+    if fs_out < 1 or fs_in < 1:
+        raise SystemExit("radae_amd.cli: --fs takes a sample rate in Hz")
+    g = gcd(fs_out, fs_in)
+    return fs_out // g, fs_in // g
+
+
+class _RateIn:
+    """stdin at another rate than the modem's: reads what the next receiver call needs, converts it on the device (engine.RateConverter) and hands out 8 kHz samples"""
+
+    def __init__(self, eng, inp, fs, int16, int16_iq):
+        import torch
+        from . import engine
+        self.torch, self.inp = torch, inp
+        self.L, self.M = _ratio(8000, fs)
+        self.rc = engine.RateConverter(eng, self.L, self.M)
+        self.dtype, self.per = (np.int16, 2) if int16_iq else (np.int16, 1) if int16 else (np.complex64, 1)
+        self.iq16 = int16_iq
+        self.buf = torch.zeros((1, 0), dtype=torch.complex64, device="cuda")
+        self.eof = False
+
+    def _take(self, y, n):
+        if y is not None and n[0]:
+            self.buf = self.torch.cat([self.buf, y[:, :n[0]]], dim=1)
+
+    def read(self, nin):
+        """nin samples at 8 kHz as a device tensor [1, nin], or None once stdin cannot supply them"""
+        size = np.dtype(self.dtype).itemsize * self.per
+        while self.buf.shape[1] < nin and not self.eof:
+            want = max(-(-(nin - self.buf.shape[1]) * self.M // self.L), 1)
+            raw = self.inp.read(want * size)
+            n = len(raw) // size
+            if n:
+                x = np.frombuffer(raw[:n * size], self.dtype)
+                self._take(*self.rc.feed(self.torch.tensor(x.reshape(1, n, 2) if self.iq16 else x[None], device="cuda")))
+            if n < want:
+                self.eof = True
+                self._take(*self.rc.flush())
+        if self.buf.shape[1] < nin:
+            return None
+        x, self.buf = self.buf[:, :nin].contiguous(), self.buf[:, nin:]
+        return x
+
+
 def _txe(argv):
     ap = argparse.ArgumentParser(prog="radae_amd.cli txe", description="RADAE streaming transmitter, features.f32 on stdin, IQ.f32 on output")
     ap.add_argument("--model_name", type=str, default="", help="DNNw weight blob (default: weights/model19_check3.bin)")
@@ -33,9 +80,10 @@ def _txe(argv):
     ap.add_argument("--eoo_data_test", action="store_true", help="experimental EOO data test - tx test frame")
     ap.add_argument("--int16_real", type=float, default=None, metavar="SCALE", help="write int16(I * SCALE) instead of IQ.f32 (`| f32toint16.py --real --scale SCALE`), converted on "
                     "the device; prints `peak: .. rms: .. clipped: ..` of the written samples on stderr")
+    ap.add_argument("--fs", type=int, default=8000, metavar="HZ", help="sample rate written (default 8000: no conversion); another rate is made on the device, ahead of --int16_real")
     args = ap.parse_args(argv)
     eng = None
-    if args.int16_real is not None and not args.bypass_enc:  # the last metre to the radio runs on the device (rade_batch_wire_out): any engine serves, the bypass transmitter
+    if (args.int16_real is not None or args.fs != 8000) and not args.bypass_enc:  # the last metre to the radio runs on the device (rade_batch_wire_out): any engine serves, the bypass transmitter
         from . import engine                                 # has one; this one is opened ahead of the rade_api.h handle, whose library must find torch's HIP runtime loaded
         eng = engine.BatchEngine(1, max_tx_mf=1, blob=args.model_name or None)
     tx = api.radae_tx_bypass_enc(args.model_name, txbpf_en=args.txbpf) if args.bypass_enc else api.radae_tx(args.model_name, txbpf_en=args.txbpf)
@@ -47,17 +95,27 @@ def _txe(argv):
     n_in = tx.get_n_floats_in()
     tx_out = np.zeros(tx.get_Nmf(), np.complex64)
     inp, out = sys.stdin.buffer, sys.stdout.buffer
-    emit = lambda iq: out.write(iq.tobytes())
-    if args.int16_real is not None:
+    emit = lambda iq, last=False: out.write(iq.tobytes())
+    if args.int16_real is not None or args.fs != 8000:
         import torch
+        from . import engine
         eng = eng or tx.eng
         level = {"peak": 0.0, "s2": 0.0, "n": 0, "clipped": 0}
+        rc = engine.RateConverter(eng, *_ratio(args.fs, 8000)) if args.fs != 8000 else None
 
-        def emit(iq):
-            s, m = eng.wire_out(torch.tensor(iq[None], device="cuda"), scale=args.int16_real, meters=True)
-            out.write(s.cpu().numpy().tobytes())
-            n = iq.size - int(m.nan[0])
-            level["peak"] = max(level["peak"], float(m.peak[0])); level["s2"] += float(m.rms[0]) ** 2 * n; level["n"] += n; level["clipped"] += int(m.clipped[0])
+        def emit(iq, last=False):
+            x = torch.tensor(iq[None], device="cuda")
+            for y, n_y in ([rc.feed(x)] + ([rc.flush()] if last else [])) if rc else [(x, [iq.size])]:
+                if not n_y[0]:
+                    continue
+                y = y[:, :n_y[0]].contiguous()
+                if args.int16_real is None:
+                    out.write(y.cpu().numpy().tobytes())
+                    continue
+                s, m = eng.wire_out(y, scale=args.int16_real, meters=True)
+                out.write(s.cpu().numpy().tobytes())
+                n = int(n_y[0]) - int(m.nan[0])
+                level["peak"] = max(level["peak"], float(m.peak[0])); level["s2"] += float(m.rms[0]) ** 2 * n; level["n"] += n; level["clipped"] += int(m.clipped[0])
     while True:
         buf = inp.read(n_in * struct.calcsize("f"))
         if len(buf) != n_in * struct.calcsize("f"):
@@ -66,7 +124,7 @@ def _txe(argv):
         emit(tx_out)
     eoo = np.zeros(tx.get_Neoo(), np.complex64)
     tx.do_eoo(eoo)
-    emit(eoo)
+    emit(eoo, last=True)
     out.flush()
     if args.int16_real is not None:
         print(f"peak: {level['peak']:.1f} rms: {np.sqrt(level['s2'] / max(level['n'], 1)):.1f} clipped: {level['clipped']}", file=sys.stderr)
@@ -84,12 +142,14 @@ def _rxe(argv):
     ap.add_argument("--eoo_data_test", action="store_true", help="experimental EOO data test - count bit errors")
     ap.add_argument("--int16", action="store_true", help="stdin is int16 samples of one real channel (what `int16tof32.py --zeropad` is piped in for), converted on the device")
     ap.add_argument("--int16_iq", action="store_true", help="stdin is int16 ..IQIQ.. (`int16tof32.py`), converted on the device")
+    ap.add_argument("--fs", type=int, default=8000, metavar="HZ", help="sample rate of stdin (default 8000: no conversion); another rate, e.g. 48000 or 44100, is brought to 8000 "
+                    "on the device, in place of a `sox .. -r 8000` stage; with --int16, --int16_iq or float IQ")
     ap.set_defaults(use_stdout=True)
     args = ap.parse_args(argv)
     if args.int16 and args.int16_iq:
         raise SystemExit("radae_amd.cli rxe: --int16 (one real channel) or --int16_iq, not both")
     wire16 = args.int16 or args.int16_iq                     # the conversion is a call of the batched engine (rade_batch_wire_in)
-    if args.bypass_dec or args.disable_unsync or wire16:              # both are switches of the batched engine (rade_api.h has neither)
+    if args.bypass_dec or args.disable_unsync or wire16 or args.fs != 8000:   # all are switches or calls of the batched engine (rade_api.h has none of them)
         cls = api.radae_rx_bypass_dec if args.bypass_dec else api.radae_rx_engine
         rx = cls(args.model_name, foff_err=args.foff_err, disable_unsync=args.disable_unsync)
     else:
@@ -97,13 +157,20 @@ def _rxe(argv):
     floats_out = np.zeros(rx.get_n_floats_out(), np.float32)
     inp, out = sys.stdin.buffer, sys.stdout.buffer
     mf = 0
+    rate_in = _RateIn(rx.eng, inp, args.fs, args.int16, args.int16_iq) if args.fs != 8000 else None
     while True:
         nin = rx.get_nin()
-        n_bytes = nin * struct.calcsize("hh" if args.int16_iq else "h" if args.int16 else "ff")
-        buf = inp.read(n_bytes)
-        if len(buf) != n_bytes:
-            break
-        ret = rx.do_radae_rx_int16(np.frombuffer(buf, np.int16), floats_out, iq=args.int16_iq) if wire16 else rx.do_radae_rx(np.frombuffer(buf, np.complex64), floats_out)
+        if rate_in:
+            x = rate_in.read(nin)
+            if x is None:
+                break
+            ret = rx._rx_dev(x, floats_out)
+        else:
+            n_bytes = nin * struct.calcsize("hh" if args.int16_iq else "h" if args.int16 else "ff")
+            buf = inp.read(n_bytes)
+            if len(buf) != n_bytes:
+                break
+            ret = rx.do_radae_rx_int16(np.frombuffer(buf, np.int16), floats_out, iq=args.int16_iq) if wire16 else rx.do_radae_rx(np.frombuffer(buf, np.complex64), floats_out)
         mf += 1
         if args.v >= 2:
             print(f"{mf:3d} sync: {int(rx.get_sync())} nin: {rx.get_nin():4d} SNRdB: {rx.get_snrdB_3k_est():3d} ret: {ret}", file=sys.stderr)

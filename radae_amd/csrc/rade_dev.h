@@ -242,6 +242,33 @@ typedef struct {
 int rd_launch_wire_in(const rd_wire_args *a, rd_stream_t s);
 int rd_launch_wire_out(const rd_wire_args *a, rd_stream_t s);
 
+/* the rational rate converter of rade_batch_rate_convert (rade_rate.hip; include/rade_batch.h states the arithmetic): k_rate_convert, one workgroup per (tiles of
+ * consecutive outputs, stream), the [L][T] table and the tile's input window in LDS.  The window's capacity is fixed (RD_RATE_WIN samples: with the largest table the
+ * header admits, rows one float apart from T, a complex window fills 80 KB exactly); the tile follows from it: rd_rate_tile outputs, whose windows span at most
+ * (tile - 1) M / L + 1 + T <= RD_RATE_WIN - K + 1 samples for every phase of the tile's first output. */
+#define RD_RATE_KMAX 8                                           /* ceil(M / L) of the reduced ratio */
+#define RD_RATE_TABLE_MAX 16384                                  /* floats of the table, L T */
+#define RD_RATE_WIN 1792                                         /* samples of a tile's window */
+#define RD_RATE_TILE_MAX 2048
+static inline int rd_rate_tile(int L, int M, int T)              /* of a reduced ratio the entry admits: a multiple of 64, 192 or more */
+{
+    const int K = (M + L - 1) / L;
+    long long t = (long long)(RD_RATE_WIN - T - K) * L / M + 1;
+    if (t > RD_RATE_TILE_MAX) t = RD_RATE_TILE_MAX;
+    return (int)(t / 64 * 64);
+}
+typedef struct { long long n0, in_base; int n_in, n_out; } rd_rate_stream;    /* one record per stream */
+typedef struct {
+    const void *x; long x_stride;                               /* complex64 or int16, stream b at + b * x_stride elements of the buffer */
+    void *y; long y_stride;                                     /* complex64 */
+    const rd_rate_stream *ps;                                   /* device [B] */
+    const float *taps;                                          /* device [L][T] (rade_rate_taps) */
+    int L, M, T, tile;                                          /* the reduced ratio, its taps per phase, rd_rate_tile */
+    int fmt, B, max_out;                                        /* RADE_RATE_C64 / _S16_REAL / _S16_IQ = 0, 1, 2; max_out = the largest n_out of the call */
+    float gain;                                                 /* of the int16 formats */
+} rd_rate_args;
+int rd_launch_rate_convert(const rd_rate_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

@@ -104,6 +104,9 @@ struct rade_batch {
     /* rade_batch_wire_in / _out: the [B] sample counts of the last RD_WIRE_SLOTS calls on the device and their pinned staging copies, one slot per call in turn (a call
      * does not wait for its stream: it waits for the call that used its slot RD_WIRE_SLOTS calls ago); [B][RD_WIRE_NCH_MAX][4] meter partials, [B][4] meters.  First use. */
     int *wire_n, *wire_n_host; hipEvent_t wire_ev[RD_WIRE_SLOTS]; unsigned wire_used, wire_seq; double *wire_part, *wire_meters;
+    /* rade_batch_rate_convert: the [L][T] table of the reduced ratio (rate_L, rate_M) it was made for, in a buffer of the largest table the entry admits, and its pinned
+     * staging copy; [B] per-stream records on the device and their pinned staging copy.  First use. */
+    float *rate_taps, *rate_taps_host; int rate_L, rate_M; rd_rate_stream *rate_ps, *rate_ps_host;
     int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
@@ -1114,6 +1117,53 @@ int rade_batch_wire_out(rade_batch *h, const void *x_dev, long x_stride, const i
         if (r) { memset(meters_host, 0, sizeof(double) * 4 * B); return 0; }     /* no stream has a sample: nothing was launched */
         if (hipMemcpyAsync(meters_host, h->wire_meters, sizeof(double) * 4 * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
     }
+    return 0;
+}
+
+/* ---- the rational rate converter: 48 / 44.1 kHz <-> 8 kHz (rade_rate.hip) ------------------------------------------------------------------------------ */
+int rade_batch_rate_convert(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, int format, float gain, void *y_dev, long y_stride,
+                            const int *n_out_host, const rade_rate_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p) return -1;
+    if (format != RADE_RATE_C64 && format != RADE_RATE_S16_REAL && format != RADE_RATE_S16_IQ) return -1;
+    if (((uintptr_t)x_dev & (format == RADE_RATE_C64 ? 7 : 1)) || ((uintptr_t)y_dev & 7)) return -1;
+    if (format != RADE_RATE_C64 && !isfinite(gain)) return -1;
+    int L, M, T;
+    if (rd_rate_reduce(p->L, p->M, &L, &M, &T)) return -1;
+    const int B = h->B, per = format == RADE_RATE_S16_IQ ? 2 : 1;         /* elements of x per sample */
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->rate_ps_host && !(h->rate_ps_host = pinned_alloc_opt(h, sizeof(rd_rate_stream) * B))) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_rate_stream *r = &h->rate_ps_host[b];
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
+        r->n0 = p->n0_host ? p->n0_host[b] : 0; r->in_base = p->in_base_host ? p->in_base_host[b] : 0;
+        if (r->n_in < 0 || r->n_out < 0 || (long)r->n_in * per > x_stride || r->n_out > y_stride || r->n0 < 0) return -1;
+        if (r->in_base > (1LL << 62) || r->in_base < -(1LL << 62)) return -1;
+        if (((__int128)r->n0 + r->n_out) * M > ((__int128)1 << 62)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (format == RADE_RATE_S16_REAL ? 2.0 : 4.0) * T * r->n_out;
+    }
+    if (!max_out) return 0;
+    if (!h->rate_taps_host && !(h->rate_taps_host = pinned_alloc_opt(h, sizeof(float) * RD_RATE_TABLE_MAX))) return -1;
+    if (dev_grow(h, &h->rate_taps, NULL, RD_RATE_TABLE_MAX, sizeof(float), 1) || dev_grow(h, &h->rate_ps, NULL, B, sizeof(rd_rate_stream), 1)) return -1;
+    if (h->rate_L != L || h->rate_M != M) {                /* another ratio than the table on the device was made for: re-made, uploaded behind what `stream` holds */
+        h->rate_L = h->rate_M = 0;
+        if (rade_rate_taps(L, M, h->rate_taps_host) != T) return -1;
+        if (hipMemcpyAsync(h->rate_taps, h->rate_taps_host, sizeof(float) * L * T, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    }
+    /* the one small copy ahead of the launch; waited for, since the next call refills the staging records (and may refill the staging table) */
+    if (hipMemcpyAsync(h->rate_ps, h->rate_ps_host, sizeof(rd_rate_stream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    h->rate_L = L; h->rate_M = M;
+    rd_rate_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.ps = h->rate_ps; a.taps = h->rate_taps;
+    a.L = L; a.M = M; a.T = T; a.tile = rd_rate_tile(L, M, T); a.fmt = format; a.B = B; a.max_out = max_out; a.gain = gain;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_rate_convert(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
     return 0;
 }
 

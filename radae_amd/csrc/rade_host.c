@@ -5,6 +5,7 @@
  *   2. DNNw weight-blob reader -> fp32 matrices (the blob is int8 + per-row scales for most layers);
  *   3. weight packing into the MFMA fragment order k_gemm streams;
  *   4. the fractional resampler's Q32.32 time base and its windowed-sinc taps (rade_batch_resample).
+ *   5. the rational rate converter's ratio, taps and output count (rade_batch_rate_convert).
  *
  * Reference: radae/radae.py:128-234 (numerology/DFT/pilots/EOO), radae/dsp.py:40-61 (BPF),
  * :153-176 (p_w), :400-416 (Pmat); blob format src/write_rade_weights.c:51-74 and
@@ -636,4 +637,56 @@ long long rade_resample_count(long long in_end, double t0, double ppm)
     if (need <= 0) return 0;
     const __int128 n = (need + step_q - 1) / step_q;
     return n * step_q > ((__int128)1 << 62) ? -1 : (long long)n;
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * 5. the rational rate converter's ratio, taps and count (include/rade_batch.h: rade_batch_rate_convert; rade_rate.hip)
+ * -------------------------------------------------------------------------------------------*/
+/* L / M reduced by their gcd, K = ceil(M / L), T = 32 K; -1 where the header refuses (L or M < 1, K > 8, L T > 16384 floats) */
+int rd_rate_reduce(int L, int M, int *Lr, int *Mr, int *T)
+{
+    if (L < 1 || M < 1) return -1;
+    int a = L, b = M;
+    while (b) { const int r = a % b; a = b; b = r; }
+    L /= a; M /= a;
+    const int K = (M + L - 1) / L;
+    if (K > RD_RATE_KMAX || (long long)L * 32 * K > RD_RATE_TABLE_MAX) return -1;
+    *Lr = L; *Mr = M; *T = 32 * K;
+    return 0;
+}
+
+/* C[ph][j] = g(t_j) / sum_j g(t_j), t_j = j - (T / 2 - 1) - ph / L, g(t) = sinc(t / W) I0(10 sqrt(1 - (t / H)^2)) / I0(10) for |t| <= H = T / 2, W = max(1, M / L).
+ * M <= L (W = 1): sin(pi t) from the fraction f = ph / L alone, as rade_resample_taps forms it: row 0 is the exact unit impulse at j = 15. */
+int rade_rate_taps(int L, int M, float *out /* [L][T] of the reduced pair, or NULL */)
+{
+    int T;
+    if (rd_rate_reduce(L, M, &L, &M, &T)) return -1;
+    if (!out) return T;
+    const double i0b = bessel_i0(10.0), H = T / 2, W = M > L ? (double)M / (double)L : 1.0;
+    double g[32 * RD_RATE_KMAX];
+    for (int ph = 0; ph < L; ph++) {
+        const double f = (double)ph / (double)L, sf = sin(PI_D * (2 * ph <= L ? f : 1.0 - f));
+        double sum = 0.0;
+        for (int j = 0; j < T; j++) {
+            const int k = j - (T / 2 - 1);
+            const double t = (double)k - f, u = t / H;
+            double sinc;
+            if (t == 0.0) sinc = 1.0;
+            else if (M <= L) sinc = ((k & 1) ? sf : -sf) / (PI_D * t);
+            else sinc = sin(PI_D * t / W) / (PI_D * t / W);
+            g[j] = fabs(t) <= H ? sinc * bessel_i0(10.0 * sqrt(1.0 - u * u)) / i0b : 0.0;
+            sum += g[j];
+        }
+        for (int j = 0; j < T; j++) out[(size_t)ph * T + j] = (float)(g[j] / sum);
+    }
+    return T;
+}
+
+/* the number of n >= 0 with n M < in_end L (any common factor of L and M cancels); -1: L or M < 1, or that many outputs pass the 2^62 limit of the call */
+long long rade_rate_count(long long in_end, int L, int M)
+{
+    if (L < 1 || M < 1) return -1;
+    if (in_end <= 0) return 0;
+    const __int128 n = ((__int128)in_end * L + M - 1) / M;
+    return n * M > ((__int128)1 << 62) ? -1 : (long long)n;
 }

@@ -51,6 +51,8 @@ long rd_pack_weights_q16_a16(const float *W, const float *row_scale, int N, int 
 long rd_pack_weights_f16x2_a16(const float *W, int N, int K, unsigned short *out);
 /* rade_batch_resample's time base (include/rade_batch.h): step_q = llrint((1 + ppm 1e-6) 2^32), t0_q = llrint(t0 2^32); -1: |ppm| > 50 000 or |t0| > 2^29 (or not a number) */
 int rd_resample_q(double t0, double ppm, long long *step_q, long long *t0_q);
+/* rade_batch_rate_convert's ratio: L / M reduced by their gcd, T = 32 ceil(M / L) taps per phase; -1: L or M < 1, ceil(M / L) > RD_RATE_KMAX, L T > RD_RATE_TABLE_MAX */
+int rd_rate_reduce(int L, int M, int *Lr, int *Mr, int *T);
 #ifdef __cplusplus
 }
 #endif

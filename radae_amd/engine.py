@@ -45,6 +45,10 @@ class ResampleParams(C.Structure):
     _fields_ = [("mode", C.c_int), ("ppm", C.c_double), ("ppm_host", C.c_void_p), ("t0_host", C.c_void_p), ("n0_host", C.c_void_p), ("in_base_host", C.c_void_p)]
 
 
+class RateParams(C.Structure):
+    _fields_ = [("L", C.c_int), ("M", C.c_int), ("n0_host", C.c_void_p), ("in_base_host", C.c_void_p)]
+
+
 class RxStatus(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("consumed", "n_calls", "n_valid", "has_eoo", "nin", "sync", "snr_dB", "state")]
 
@@ -116,6 +120,10 @@ def load_library() -> C.CDLL:
     if hasattr(L, "rade_batch_wire_in"):
         L.rade_batch_wire_in.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, vp, C.c_long, vp]
         L.rade_batch_wire_out.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, vp, C.c_long, vp, vp]
+    if hasattr(L, "rade_batch_rate_convert"):     # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
+        L.rade_batch_rate_convert.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, vp, C.c_long, vp, C.POINTER(RateParams), vp]
+        L.rade_rate_count.restype = C.c_longlong; L.rade_rate_count.argtypes = [C.c_longlong, C.c_int, C.c_int]
+        L.rade_rate_taps.argtypes = [C.c_int, C.c_int, vp]
     _lib = L
     return L
 
@@ -138,6 +146,7 @@ EXPORTED_SYMBOLS = [
     "rade_batch_channel_rs_pa", "rade_sigma_from_EbNodB_rs3",
     "rade_batch_resample", "rade_resample_count", "rade_resample_taps",
     "rade_batch_wire_in", "rade_batch_wire_out",
+    "rade_batch_rate_convert", "rade_rate_count", "rade_rate_taps",
 ]
 WIRE_REAL, WIRE_IQ = 0, 1                                                          # rade_batch_wire_in / _out mode
 
@@ -172,6 +181,28 @@ def resample_taps() -> np.ndarray:
     """rade_resample_taps: the float32 [257, 32] Kaiser-windowed sinc table of the sinc32 mode (host only)."""
     t = np.zeros((257, 32), np.float32)
     load_library().rade_resample_taps(t.ctypes.data)
+    return t
+
+
+RATE_C64, RATE_S16_REAL, RATE_S16_IQ = 0, 1, 2                                     # rade_batch_rate_convert format
+
+
+def rate_count(in_end: int, L: int, M: int) -> int:
+    """rade_rate_count: how many outputs n >= 0 have their position n M / L below in_end input samples."""
+    n = int(load_library().rade_rate_count(int(in_end), int(L), int(M)))
+    if n < 0:
+        raise ValueError(f"rade_rate_count refuses L {L!r}, M {M!r}, in_end {in_end!r} (L, M >= 1, outputs x M <= 2^62)")
+    return n
+
+
+def rate_taps(L: int, M: int) -> np.ndarray:
+    """rade_rate_taps: the float32 [L', T] Kaiser-windowed sinc table of the ratio L / M reduced to L' / M' (host only), T = 32 ceil(M' / L')."""
+    lib = load_library()
+    T = int(lib.rade_rate_taps(int(L), int(M), None))
+    if T < 0:
+        raise ValueError(f"rade_rate_taps refuses the ratio {L!r} / {M!r} (L, M >= 1; reduced: ceil(M / L) <= 8, L T <= 16384)")
+    t = np.zeros((int(L) // int(np.gcd(int(L), int(M))), T), np.float32)
+    assert lib.rade_rate_taps(int(L), int(M), t.ctypes.data) == T
     return t
 
 
@@ -456,6 +487,43 @@ class BatchEngine:
         ys = out.stride(0) if B > 1 else out.shape[1]
         if self.lib.rade_batch_resample(self.h, x.data_ptr(), xs, n_in.ctypes.data, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_resample failed (|ppm| <= 50000, n0 >= 0, n_out <= the row of out)")
+        return out, n_out
+
+    # ---- sample-rate conversion --------------------------------------------------------------
+    def rate_convert(self, x, L: int, M: int, n_out=None, n_in=None, n0=0, in_base=0, gain: float = 1.0, out=None):
+        """The rational rate converter (rade_batch_rate_convert): output rate = input rate x L / M (L = 1, M = 6: 48 kHz -> 8 kHz).  x: cuda complex64 [B, N], int16 [B, N]
+        (one real channel: the imaginary part of the output is +0) or int16 [B, N, 2] (I, Q); the int16 forms are scaled by `gain` as wire_in does.  Returns
+        (y complex64 [B, max n_out], n_out int32 [B]).  Output n of a stream sits at input position n M / L.  n_out, n_in (readable samples of each row, default N), n0
+        (index of the first output written) and in_base (absolute index of x[b, 0]): scalars or B per-stream values.  n_out defaults to
+        rade_rate_count(in_base + n_in, L, M) - n0: every output whose position lies inside the input.  Samples of y past a stream's n_out are zeros (left alone in a
+        caller's `out`)."""
+        import torch
+        B = self.B
+        assert x.is_cuda and x.shape[0] == B
+        if x.dtype == torch.complex64:
+            assert x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] <= 1)
+            fmt, per = RATE_C64, 1
+        else:
+            assert x.dtype == torch.int16 and (x.dim() == 2 or (x.dim() == 3 and x.shape[2] == 2)) and x.stride(-1) == 1
+            assert x.dim() == 2 or x.stride(1) == 2 or x.shape[1] <= 1
+            fmt, per = (RATE_S16_REAL, 1) if x.dim() == 2 else (RATE_S16_IQ, 2)
+        N = x.shape[1]
+        n0 = _per_stream(B, n0, np.int64, "n0"); in_base = _per_stream(B, in_base, np.int64, "in_base")
+        n_in = _per_stream(B, N if n_in is None else n_in, np.int32, "n_in")
+        if n_in.min() < 0 or n_in.max() > N:
+            raise ValueError(f"n_in: between 0 and the {N} samples of a row")
+        if n_out is None:
+            n_out = np.array([max(rate_count(int(in_base[b]) + int(n_in[b]), L, M) - int(n0[b]), 0) for b in range(B)], np.int32)
+        else:
+            n_out = _per_stream(B, n_out, np.int32, "n_out")
+        if out is None:
+            out = torch.zeros((B, max(int(n_out.max()), 1)), dtype=torch.complex64, device=x.device)
+        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n_out.max()
+        p = RateParams(int(L), int(M), n0.ctypes.data, in_base.ctypes.data)
+        xs = x.stride(0) if B > 1 else N * per                 # (a one-row tensor may carry any stride in its first dimension)
+        ys = out.stride(0) if B > 1 else out.shape[1]
+        if self.lib.rade_batch_rate_convert(self.h, x.data_ptr(), xs, n_in.ctypes.data, fmt, gain, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
+            raise RuntimeError("rade_batch_rate_convert failed (L, M >= 1 with ceil(M / L) <= 8 and L T <= 16384 after reduction, a finite gain, n0 >= 0, n_out <= the row of out)")
         return out, n_out
 
     # ---- the sound-card wire ------------------------------------------------------------------
@@ -763,4 +831,42 @@ class ClockOffset:
 
     def flush(self):
         """the outputs whose position lies inside the input fed so far and whose window runs past it"""
+        return self._emit(self.tail, self.n_fed)
+
+
+class RateConverter:
+    """A sample-rate conversion by L / M applied to streams that arrive in pieces (BatchEngine.rate_convert is stateless: this keeps what the next piece needs).  Per stream
+    the last T input samples stay on the device, in the format they arrive in; feed() emits the outputs whose whole T-tap window has arrived, flush() the rest (their
+    windows run into zeros, as at the end of a whole-stream call).  The concatenated outputs of a stream are bit-identical to one rate_convert() call over the whole stream."""
+
+    def __init__(self, engine: BatchEngine, L: int, M: int, gain: float = 1.0):
+        self.eng, self.L, self.M, self.gain = engine, int(L), int(M), gain
+        self.T = rate_taps(L, M).shape[1]
+        self.tail = None                                              # input samples [n_fed - T, n_fed); zeros ahead of the stream; made from the first piece
+        self.n_fed = 0                                                # input samples taken so far (every stream gets pieces of the same length)
+        self.n_done = 0                                               # outputs emitted so far (the same for every stream: one ratio, equal pieces)
+
+    def _emit(self, buf, in_end: int):
+        """the outputs of positions below in_end that have not been emitted, from buf = input samples [n_fed - T, ..)"""
+        n_out = max(rate_count(in_end, self.L, self.M) - self.n_done, 0)
+        y, n = self.eng.rate_convert(buf, self.L, self.M, n_out=n_out, n0=self.n_done, in_base=self.n_fed - self.T, gain=self.gain)
+        self.n_done += n_out
+        return y, n
+
+    def feed(self, x):
+        """x cuda complex64 [B, n], int16 [B, n] or int16 [B, n, 2]: the next n input samples of every stream -> (y [B, max n_out], n_out int32 [B])"""
+        import torch
+        if self.tail is None:
+            self.tail = torch.zeros((x.shape[0], self.T) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+        assert x.is_cuda and x.dtype == self.tail.dtype and x.shape[0] == self.eng.B and x.shape[2:] == self.tail.shape[2:]
+        buf = torch.cat([self.tail, x], dim=1)
+        y, n_out = self._emit(buf, self.n_fed + x.shape[1] - self.T // 2)      # output n is complete once sample i(n) + T / 2 has arrived
+        self.tail = buf[:, -self.T:].contiguous()
+        self.n_fed += x.shape[1]
+        return y, n_out
+
+    def flush(self):
+        """the outputs whose position lies inside the input fed so far and whose window runs past it"""
+        if self.tail is None:
+            return None, np.zeros(self.eng.B, np.int32)
         return self._emit(self.tail, self.n_fed)
