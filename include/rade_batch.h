@@ -26,6 +26,8 @@
  *   rade_batch_wire_out    f32toint16.py:42-54 (--real --scale 8192 feeds the radio), with saturation and level meters
  *   rade_batch_rate_convert  the `sox .. -r 8000` stage in front of int16tof32.py in every off-air and sound-card pipeline (radae_rx.sh:33,39, README.md:570, evaluate.sh:119,
  *                          analog_bbfm.sh:37,43): 48 or 44.1 kHz <-> the modem's 8 kHz, a polyphase L / M converter whose anti-alias filter scales with the ratio
+ *   rade_batch_fm_mod      fm.m:74-94 (analog_fm_mod) with the noise of fm.m:171 / :316-322: the analog-FM baseline every BBFM result is compared with (analog_bbfm.sh:37-43)
+ *   rade_batch_fm_demod    fm.m:97-126 (analog_fm_demod): mix, input filter, discriminator, output filter (de-emphasis folded into it)
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -116,6 +118,10 @@ int rade_batch_n_streams(const rade_batch *h);
  *   rade_batch_rate_convert                 x_dev (complex64, or int16 with one or two elements per sample; x_stride >= n_in, 2 n_in for int16 IQ, in elements of x, checked; 8- or
  *                                           2-byte alignment) in; y_dev (complex64; y_stride >= every n_out, checked): n_out[b] samples of row b are written, 8 bytes at a time (any
  *                                           y_stride, any parity of n_out, element alignment); x is read inside the n_in[b] samples of row b only
+ *   rade_batch_fm_mod                       m_dev (float32 or complex64; m_stride >= n, checked; 4- or 8-byte alignment) in; y_dev (complex64; y_stride >= n, checked): n[b]
+ *                                           samples of row b are written, 8 bytes at a time; p->noise_dev (complex64) is dense [B][max n]
+ *   rade_batch_fm_demod                     x_dev (complex64; x_stride >= n_in, checked) in; y_dev (float32 or complex64; y_stride >= n_out, checked; 4- or 8-byte alignment)
+ *                                           and p->bb_out_dev (complex64; bb_stride >= n_out, checked): n_out[b] samples of row b are written, one element at a time
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -325,6 +331,98 @@ int rade_batch_rate_convert(rade_batch *h, const void *x_dev, long x_stride, con
 long long rade_rate_count(long long in_end, int L, int M);
 /* host only, no handle, no GPU: the table C [L][T] of the reduced pair.  Returns T (-1: a ratio the call refuses); out == NULL only queries */
 int rade_rate_taps(int L, int M, float *out);
+
+/* ---- analog FM: modulator and demodulator of fm.m, every stream in one call (rade_fm.hip) ----------------------------------------------------------------
+ * Both calls work on any engine (the model is not used; no encoder or receiver state is touched), keep no state on the device, and obey the buffer rules above.
+ *
+ * The phasor cis(ph) of a 32-bit phase ph (one turn = 2^32), used by both calls: the top two bits of ph choose the quadrant by swapping and negating the two components,
+ * which is exact; the low 30 bits r give an angle in [0, pi / 2): r' = min(r, 2^30 - r) (exact; the two components swapped when the complement was taken), the angle
+ * (pi / 2) 2^-30 r' formed in double and rounded once to float32, sine and cosine of it in float32.  r = 0 gives exactly (1, 0): a carrier at Fs / 4 with no modulation
+ * is exactly (0, 1), (-1, 0), (0, -1), (1, 0), ..  The deviation from the exact phasor measured on the MI355X is 7.8e-8 at worst (EPS_CIS_MEASURED in tests/test_fm_gpu.py).
+ *
+ * rade_batch_fm_mod (fm.m:74-94).  Per stream n[b] modulating samples m (RADE_FM_F32: float32; RADE_FM_C64: complex64 whose real part is used, what
+ *   rade_batch_rate_convert and rade_batch_wire_in hand over) -> complex64.  The phase is a 32-bit NCO, not a float accumulator: with kc = fc / Fs 2^32 and
+ *   kd = fd / Fs 2^32 (doubles made on the host)
+ *       inc[k] = (uint32)(int64) rint(fma((double)m[k], kd, kc))          ph[i] = ph0[b] + sum_{k <= i} inc[k]  mod 2^32          tx[i] = cis(ph[i])
+ *   The sum is inclusive (fm.m:90-92 adds before it takes the exponential).  A sample that is not finite or whose |m| > 2^16 modulates as 0; finite samples are otherwise
+ *   used as they are (|m| > 1 over-deviates, as in fm.m).  Integer sums are associative: a stream modulated in pieces equals the stream modulated whole, bit for bit, when
+ *   each piece is given the phase the previous one ended on (phase0_host [B] or NULL = 0; phase_end_host [B] out or NULL: when given, the call also waits for its own
+ *   kernels, as the wire meters do; like rade_batch_rate_convert, both calls always wait once ahead of their launches for the copy of the per-stream records, and so
+ *   for the work queued on `stream` in front of them).  Against fm.m's float64 accumulate-and-wrap on the same float32 input the phasor differs by 3.4e-9 after 1 s at 48 kHz (tests/test_fm_host.py).
+ *   Three plain launches (tile sums, their scan, apply); no workgroup waits for another.
+ *   Noise, when sigma > 0: from noise_dev (complex64, dense [B][max n]: row b at + b max n, max n the largest count of the call) or, when that is NULL, generated from
+ *   `seed` (non-zero): Philox keyed as in rade_channel_params, counter (p, b, 3, p >> 32) with p = (n0[b] + i) >> 1, words 0-1 for the even sample of the pair and words
+ *   2-3 for the odd one, Box-Muller as everywhere (g0, g1 of unit variance).  (The fourth word carries p >> 32, as the rate-Rs channel's does: it is 0, the counter
+ *   (p, b, 3, 0), for every n0 + i below 2^33, and keeps the draws distinct up to the 2^62 the call admits.)  n0_host [B] is the absolute index of the piece's first sample (NULL = 0), so pieces equal the
+ *   whole bit for bit with noise on as well.
+ *       RADE_FM_OUT_COMPLEX   generated: tx + (float)(sigma / sqrt 2) (g0 + j g1) (fm.m:171);  explicit: tx + (float)sigma noise
+ *       RADE_FM_OUT_REAL      generated: (Re tx + (float)sigma g0, +0.0f) (fm.m:321-324: real noise, the real part kept);  explicit: (Re tx + (float)sigma Re noise, +0.0f)
+ *   each component one float32 product and one float32 sum, rounded separately.  RADE_FM_OUT_REAL is applied with and without noise.  The call does not refuse fc = 0 in
+ *   real mode, but a real signal only carries the modulation when fc >= Bfm / 2.
+ *   Pre-emphasis (fm.m:80-83: a two-tap FIR and a whole-signal peak normalisation) is NOT on the device; radae_amd.engine.fm_pre_emphasis does it on the host.
+ *   Refused (-1, nothing written): NULL or misaligned pointers, a negative count, a stride shorter than its row, an unknown format or mode, Fs <= 0, |fc| > Fs / 2,
+ *   fd <= 0 or fd > Fs / 2, a sigma that is negative or not finite, sigma > 0 with neither noise_dev nor a seed, n0 negative or above 2^62, values that are not finite.
+ *
+ * rade_batch_fm_demod (fm.m:97-126).  complex64 in (a real signal arrives as (x, +0) from rade_batch_wire_in); out float32 (RADE_FM_F32) or complex64 with +0.0f imaginary
+ *   (RADE_FM_C64: feeds rade_batch_rate_convert / rade_batch_wire_out directly); optional second output bb_out_dev (complex64): the filtered baseband of the same samples,
+ *   analog_fm_demod's rx_bb.  x[b][g] is the sample of absolute index in_base[b] + g, 0 <= g < n_in[b]; output i of row b is the sample of absolute index n = n0[b] + i,
+ *   0 <= i < n_out[b] (n0_host NULL: n0 = in_base, one output per input).  Every step is a pure function of n:
+ *     1. mix down    xm[n] = x[n] cis(-(fcq n mod 2^32)), fcq = (uint32) llrint(fc / Fs 2^32): re = fma(x.re, c.re, -(x.im c.im)), im = fma(x.re, c.im, x.im c.re).
+ *                    fc = 0: the factor is exactly (1, 0).  Samples in front of absolute index 0 and samples outside [in_base, in_base + n_in) are zero; nothing outside
+ *                    the stream's n_in samples is read.
+ *     2. input FIR   bb[n] = sum_{k = 0..N1-1} b1[k] xm[n - k] (filter(bin, 1, .), causal): one float32 accumulator per component, fused multiply-adds in the order
+ *                    k = 0..N1-1.
+ *     3. discriminator  d = bb[n] conj(bb[n - 1]): re = fma(p.re, q.re, p.im q.im), im = fma(p.im, q.re, -(p.re q.im)); a = atan2(im, re) evaluated in double and
+ *                    rounded to float32; d = 0 gives a = 0 whatever the signs of its zeros (bb[-1] = 0: sample 0 of a stream gives angle 0, fm.m:110); unless ph_dont_limit, a clamped to [-wd, wd], wd = (float)(2 pi fd / Fs);
+ *                    then one multiply by (float)(1 / wd).
+ *     4. output FIR  y[n] = sum_{k = 0..N2-1} b2[k] a[n - k], ordered like 2.
+ *   b1, b2: host float32 arrays given per call, 1 <= N1, N2 <= 512; they are uploaded into engine memory and uploaded again only when their bytes change.  A one-tap
+ *   table {1.0f} is an exact pass-through (fm.m's output_filter = 0).  The summation order is stated so that a vector-unit form and an f32 matrix-core form over a Toeplitz
+ *   tile would give the same bits; the kernel is the vector-unit form.
+ *   Output n depends on inputs n - (N1 + N2 - 1) .. n: a piece handed that much history (through in_base / n0) equals the whole, bit for bit.
+ *   De-emphasis (fm.m:123-125, filter(1, prede, .)) is a one-pole recurrence and would need state; it is folded into b2 on the host instead (rade_fm_taps):
+ *   b2 = conv(bout, a^k for k < K), a = 1 - 1 / (tc Fs), K the first power with a^K < 2^-30 (39 at 48 kHz, 90 at 96 kHz).  DEVIATION from fm.m: the tail of the
+ *   recurrence below 1e-9 is cut off.
+ *   Refused: what rade_batch_fm_mod refuses of pointers, counts, strides, formats and rates, plus NULL taps, N1 or N2 outside 1..512, taps that are not finite,
+ *   |in_base| or |n0| > 2^62.
+ * Both return 0. */
+enum { RADE_FM_F32 = 0, RADE_FM_C64 = 1 };
+enum { RADE_FM_OUT_COMPLEX = 0, RADE_FM_OUT_REAL = 1 };
+typedef struct {
+    double Fs, fc, fd;                            /* sample rate, carrier, peak deviation, Hz */
+    int in_format, out_mode;                      /* RADE_FM_F32 / RADE_FM_C64; RADE_FM_OUT_COMPLEX / RADE_FM_OUT_REAL */
+    double sigma;                                 /* 0: no noise */
+    unsigned long long seed;                      /* of the generated noise (used when sigma > 0 and noise_dev is NULL) */
+    const void *noise_dev;                        /* complex64 [B][max n] unit noise, or NULL */
+    const unsigned *phase0_host;                  /* [B] phase in front of the first sample, NULL = 0 */
+    unsigned *phase_end_host;                     /* [B] out: phase behind the last sample, or NULL */
+    const long long *n0_host;                     /* [B] absolute index of the first sample (the noise counter), NULL = 0 */
+} rade_fm_mod_params;
+int rade_batch_fm_mod(rade_batch *h, const void *m_dev, long m_stride, const int *n_host, void *y_dev, long y_stride, const rade_fm_mod_params *p, void *stream);
+typedef struct {
+    double Fs, fc, fd;
+    int out_format, ph_dont_limit;                /* RADE_FM_F32 / RADE_FM_C64; non-zero: no clamp of the discriminator's angle */
+    const float *b1; int N1;                      /* input filter, host */
+    const float *b2; int N2;                      /* output filter, host */
+    const long long *in_base_host;                /* [B] absolute index of x[b][0], NULL = 0 */
+    const long long *n0_host;                     /* [B] absolute index of the first output written, NULL = in_base */
+    void *bb_out_dev; long bb_stride;             /* complex64 [B][bb_stride] or NULL */
+} rade_fm_demod_params;
+int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
+                        const rade_fm_demod_params *p, void *stream);
+/* host only, no handle, no GPU.
+ * rade_fm_sigma: sqrt(Fs / (CN Bfm)), CN = 10^(CNdB / 10), Bfm = 2 (fd + fm_max) (fm.m:16,162): the sigma that gives a unit carrier the C/N inside Carson's bandwidth.
+ *   -1: values that are not finite or not positive.
+ * rade_fm_deemph_len: K of the folded de-emphasis (0 for tc = 0; -1: tc < 0, a outside (0, 1), K > 512).
+ * rade_fm_taps: the two least-squares designs of fm.m:41-47 (firls, bands [0, 0.95 fc, 1.05 fc, 1], amplitudes [1, 1, 0.01, 0.01], unit weights; fc = (Bfm / 2) / (Fs / 2)
+ *   for bin, fm_max / (Fs / 2) for bout) in closed form: sinc integrals for the Toeplitz-plus-Hankel normal matrix, linear-ramp integrals for the right side, a dense
+ *   solve in double.  ntaps is odd (type I), 3..511; bin gets ntaps values, bout ntaps + K - 1 (the de-emphasis of time constant de_emp_tc folded in; de_emp_tc = 0:
+ *   ntaps).  Returns the length of bout (-1: refused); bin == bout == NULL only queries.  The default of the callers is 201 taps, the ncoeffs that fm.m:27 computes and
+ *   uses as the filters' delay.  Octave's firls(201, ..) takes its first argument as an ORDER; whether it returns 201, 202 or 203 taps could not be checked (no Octave
+ *   where this was written).  The kernel takes any length.  Equal to scipy.signal.firls(201, ..) within 1e-12 (tests/test_fm_host.py). */
+double rade_fm_sigma(double CNdB, double Fs, double fm_max, double fd);
+int rade_fm_deemph_len(double Fs, double tc);
+int rade_fm_taps(double Fs, double fm_max, double fd, int ntaps, double de_emp_tc, double *bin, double *bout);
 
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the

@@ -9,6 +9,7 @@
     python -m radae_amd.cli inference MODEL features.f32 features_hat.f32 --bottleneck 3 --auxdata --EbNodB .. [--h_file h.f32] [--mp_test] [--phase_offset rad]          the same without --rate_Fs: the rate-Rs channel
     python -m radae_amd.cli multipath_samples mpp 8000 50 30 10 h.f32 g.f32                                                      multipath_samples.m
     python -m radae_amd.cli bbfm_inference MODEL features.f32 features_hat.f32 [--CNRdB ..] [--h_file h_lmr60.f32] [--write_latent z.f32]    bbfm_inference.py
+    python -m radae_amd.cli analog_fm IN.s16 OUT.s16 CNRdB [--seed N]                                                             analog_bbfm.sh:37-43 from the 8 kHz int16 file onward
 
 so that the reference's shell pipelines (`cat features_in.f32 | python3 radae_txe.py > rx.f32`, `cat rx.f32 | python3 radae_rxe.py > features_out.f32`: CMakeLists.txt:300-420) run with
 `python3 -m radae_amd.cli txe|rxe` in their place; `--fs 48000` (or 44100, ..) takes the place of the `sox .. -r 8000` stage of the off-air pipelines (radae_rx.sh:33,39): the
@@ -474,9 +475,50 @@ def _bbfm_inference(argv):
     return 0
 
 
+FM_FS, FM_FC, FM_FD, FM_FMAX = 48000, 12000.0, 5000.0, 3000.0           # fm_mod_file / fm_demod_file (fm.m:292-300, :337-346)
+
+
+def analog_fm_chain(eng, x16, CNRdB: float, seed: int = 1):
+    """The analog-FM baseline of analog_bbfm.sh:37-43 on the device, from 8 kHz int16 speech to 8 kHz int16 speech: x16 cuda int16 [B, n] -> int16 [B, n].
+    rate_convert 8 k -> 48 k (the int16 samples scaled by 1 / 32767 as fm_mod_file reads them), fm_mod (fc 12 kHz, fd 5 kHz, real output with real noise at CNRdB),
+    int16(tx x 16384) and back (the file between fm_mod_file and fm_demod_file), fm_demod (de-emphasis folded in), rate_convert 48 k -> 8 k, int16(y x 20000).
+    Deviations from the script: no int16 file at 48 kHz in front of the modulator and behind the demodulator (the samples stay float32 there), and int16 conversion
+    truncates toward zero where Octave's fwrite rounds."""
+    from . import engine
+    sigma = engine.fm_sigma(CNRdB, FM_FS, FM_FMAX, FM_FD)
+    b1, b2 = engine.fm_taps(FM_FS, FM_FMAX, FM_FD, 201, engine.FM_DE_EMP_TC)
+    up, n_up = eng.rate_convert(x16, 6, 1, gain=1.0 / 32767.0)
+    tx, _ = eng.fm_mod(up, FM_FS, FM_FC, FM_FD, n=n_up, real=True, sigma=sigma, seed=seed, want_phase=False)
+    rx = eng.wire_in(eng.wire_out(tx, n=n_up, real=True, scale=16384.0), n=n_up)
+    y, _, n_y = eng.fm_demod(rx, FM_FS, FM_FC, FM_FD, b1, b2, n_in=n_up, complex_out=True)
+    down, n_down = eng.rate_convert(y, 1, 6, n_in=n_y)
+    return eng.wire_out(down, n=n_down, real=True, scale=20000.0), n_down
+
+
+def _analog_fm(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli analog_fm", description="analog FM baseline (analog_bbfm.sh): 8 kHz int16 speech through an FM modulator, noise at a C/N "
+                                 "and an FM demodulator at 48 kHz, all on the device")
+    ap.add_argument("input", help="8 kHz int16 mono samples (what the sox and `ch` stages of analog_bbfm.sh:37 deliver)")
+    ap.add_argument("output", help="8 kHz int16 mono samples")
+    ap.add_argument("CNRdB", type=float, help="carrier to noise ratio in Carson's bandwidth, dB")
+    ap.add_argument("--seed", type=int, default=1, help="seed of the generated noise (non-zero)")
+    args = ap.parse_args(argv)
+    import torch
+    from . import engine
+    x = np.fromfile(args.input, np.int16)
+    if not x.size:
+        np.zeros(0, np.int16).tofile(args.output)
+        return 0
+    eng = engine.BatchEngine(1, max_tx_mf=1)
+    y, n = analog_fm_chain(eng, torch.tensor(x[None], device="cuda"), args.CNRdB, args.seed)
+    y.cpu().numpy()[0, :int(n[0])].tofile(args.output)
+    eng.close()
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
-    cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference}
+    cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2

@@ -269,6 +269,40 @@ typedef struct {
 } rd_rate_args;
 int rd_launch_rate_convert(const rd_rate_args *a, rd_stream_t s);
 
+/* the analog FM modulator and demodulator of rade_batch_fm_mod / rade_batch_fm_demod (rade_fm.hip; include/rade_batch.h states the arithmetic).  Modulator: three plain
+ * launches (k_fm_sums, k_fm_tile_scan, k_fm_mod) over tiles of RD_FM_TILE samples; demodulator: k_fm_demod, one workgroup per (tiles of RD_FM_TILE outputs, stream),
+ * the mixed window, the filtered baseband, the discriminator values and both tap tables in LDS. */
+#define RD_FM_TILE 2048                                          /* samples of a tile, both directions */
+#define RD_FM_NMAX 512                                           /* taps of either demodulator filter */
+typedef struct { long long n0; unsigned ph0; int n; } rd_fm_stream;           /* modulator: absolute index of the first sample (the noise counter), phase in front of it, count */
+typedef struct {
+    const void *m; long m_stride;                               /* float32 or complex64 (real part used), stream b at + b * m_stride elements */
+    void *y; long y_stride;                                     /* complex64 */
+    const void *noise; long noise_stride;                       /* complex64 [B][noise_stride] or NULL (generated) */
+    const rd_fm_stream *ps;                                     /* device [B] */
+    unsigned *tsum;                                             /* device [B][n_tiles]: tile sums, then the phase in front of each tile */
+    unsigned *ph_end;                                           /* device [B]: the phase behind the last sample */
+    double kc, kd;                                              /* fc / Fs 2^32, fd / Fs 2^32 */
+    unsigned long long seed;
+    float sg;                                                   /* what multiplies the unit noise: sigma / sqrt 2 (generated, complex), sigma (generated real; explicit) */
+    int fmt, real_out, noise_on, B, n_tiles;                    /* fmt: RADE_FM_F32 / RADE_FM_C64 = 0, 1; n_tiles of the longest stream */
+} rd_fm_mod_args;
+int rd_launch_fm_mod(const rd_fm_mod_args *a, rd_stream_t s);
+typedef struct { long long n0, in_base; int n_in, n_out; } rd_fm_dstream;     /* demodulator: absolute index of the first output, of x[b][0]; counts */
+typedef struct {
+    const void *x; long x_stride;                               /* complex64 */
+    void *y; long y_stride;                                     /* float32 or complex64 (imaginary part +0) */
+    void *bb_out; long bb_stride;                               /* complex64 or NULL: the filtered baseband of the outputs */
+    const rd_fm_dstream *ps;                                    /* device [B] */
+    const float *taps;                                          /* device [2][RD_FM_NMAX]: b1, b2 */
+    unsigned fcq;                                               /* (uint32) llrint(fc / Fs 2^32) */
+    float wd, inv_wd;                                           /* (float)(2 pi fd / Fs), (float)(1 / wd) */
+    int N1, N2, fmt, dont_limit, B, max_out;                    /* fmt of y: RADE_FM_F32 / RADE_FM_C64 = 0, 1 */
+} rd_fm_demod_args;
+int rd_launch_fm_demod(const rd_fm_demod_args *a, rd_stream_t s);
+/* tests only: the phasor on n phases (ph, cis_out complex64) and / or the discriminator's atan2 on n complex64 pairs (d, atan_out float32); device pointers, NULL skips */
+int rd_launch_fm_probe(const unsigned *ph, void *cis_out, const void *d, float *atan_out, int n, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

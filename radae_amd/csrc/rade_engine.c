@@ -107,6 +107,11 @@ struct rade_batch {
     /* rade_batch_rate_convert: the [L][T] table of the reduced ratio (rate_L, rate_M) it was made for, in a buffer of the largest table the entry admits, and its pinned
      * staging copy; [B] per-stream records on the device and their pinned staging copy.  First use. */
     float *rate_taps, *rate_taps_host; int rate_L, rate_M; rd_rate_stream *rate_ps, *rate_ps_host;
+    /* rade_batch_fm_mod: [B] per-stream records on the device and their pinned staging copy; [B][fm_tsum_cap / B] tile sums; [B] final phases and their pinned copy.
+     * rade_batch_fm_demod: its [B] records likewise; the two tap tables [2][RD_FM_NMAX] on the device, their pinned staging copy, and the bytes they were made from
+     * (fm_taps_last with fm_N1, fm_N2: uploaded again only when a call brings other bytes).  First use. */
+    rd_fm_stream *fm_ps, *fm_ps_host; unsigned *fm_tsum; long fm_tsum_cap; unsigned *fm_ph_end, *fm_ph_end_host;
+    rd_fm_dstream *fm_dps, *fm_dps_host; float *fm_taps, *fm_taps_host, *fm_taps_last; int fm_N1, fm_N2;
     int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
@@ -1163,6 +1168,117 @@ int rade_batch_rate_convert(rade_batch *h, const void *x_dev, long x_stride, con
     a.L = L; a.M = M; a.T = T; a.tile = rd_rate_tile(L, M, T); a.fmt = format; a.B = B; a.max_out = max_out; a.gain = gain;
     PROF_BEGIN(h, stream);
     if (rd_launch_rate_convert(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- the analog FM modulator and demodulator (rade_fm.hip) -------------------------------------------------------------------------------------------------- */
+static int fm_rates_ok(double Fs, double fc, double fd)
+{
+    return isfinite(Fs) && isfinite(fc) && isfinite(fd) && Fs > 0.0 && fabs(fc) <= Fs / 2.0 && fd > 0.0 && fd <= Fs / 2.0;
+}
+
+int rade_batch_fm_mod(rade_batch *h, const void *m_dev, long m_stride, const int *n_host, void *y_dev, long y_stride, const rade_fm_mod_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !m_dev || !y_dev || !n_host || !p) return -1;
+    if (p->in_format != RADE_FM_F32 && p->in_format != RADE_FM_C64) return -1;
+    if (p->out_mode != RADE_FM_OUT_COMPLEX && p->out_mode != RADE_FM_OUT_REAL) return -1;
+    if (((uintptr_t)m_dev & (p->in_format == RADE_FM_C64 ? 7 : 3)) || ((uintptr_t)y_dev & 7) || ((uintptr_t)p->noise_dev & 7)) return -1;
+    if (!fm_rates_ok(p->Fs, p->fc, p->fd) || !isfinite(p->sigma) || p->sigma < 0.0) return -1;
+    const int noise_on = p->sigma > 0.0;
+    if (noise_on && !p->noise_dev && !p->seed) return -1;             /* a noise level without a source of noise */
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->fm_ps_host && !(h->fm_ps_host = pinned_alloc_opt(h, sizeof(rd_fm_stream) * B))) return -1;
+    if (!h->fm_ph_end_host && !(h->fm_ph_end_host = pinned_alloc_opt(h, sizeof(unsigned) * B))) return -1;
+    int max_n = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_fm_stream *r = &h->fm_ps_host[b];
+        r->n = n_host[b]; r->n0 = p->n0_host ? p->n0_host[b] : 0; r->ph0 = p->phase0_host ? p->phase0_host[b] : 0u;
+        if (r->n < 0 || r->n > m_stride || r->n > y_stride || r->n0 < 0 || r->n0 > (1LL << 62)) return -1;
+        if (r->n > max_n) max_n = r->n;
+        work += 8.0 * r->n;
+    }
+    if (!max_n) {                                                     /* nothing to modulate: the phase stays where it was */
+        if (p->phase_end_host) for (int b = 0; b < B; b++) p->phase_end_host[b] = h->fm_ps_host[b].ph0;
+        return 0;
+    }
+    const int n_tiles = (max_n + RD_FM_TILE - 1) / RD_FM_TILE;
+    if (dev_grow(h, &h->fm_ps, NULL, B, sizeof(rd_fm_stream), 1) || dev_grow(h, &h->fm_ph_end, NULL, B, sizeof(unsigned), 1) ||
+        dev_grow(h, &h->fm_tsum, &h->fm_tsum_cap, (long)B * n_tiles, sizeof(unsigned), 1)) return -1;
+    /* the one small copy ahead of the launches; waited for, since the next call refills the staging records */
+    if (hipMemcpyAsync(h->fm_ps, h->fm_ps_host, sizeof(rd_fm_stream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    rd_fm_mod_args a;
+    memset(&a, 0, sizeof a);
+    a.m = m_dev; a.m_stride = m_stride; a.y = y_dev; a.y_stride = y_stride; a.noise = noise_on ? p->noise_dev : NULL; a.noise_stride = max_n;
+    a.ps = h->fm_ps; a.tsum = h->fm_tsum; a.ph_end = h->fm_ph_end;
+    a.kc = p->fc / p->Fs * 4294967296.0; a.kd = p->fd / p->Fs * 4294967296.0; a.seed = p->seed;
+    a.sg = (float)(a.noise || p->out_mode == RADE_FM_OUT_REAL ? p->sigma : p->sigma / sqrt(2.0));
+    a.fmt = p->in_format; a.real_out = p->out_mode == RADE_FM_OUT_REAL; a.noise_on = noise_on; a.B = B; a.n_tiles = n_tiles;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_fm_mod(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    if (p->phase_end_host) {                                          /* read back like the wire meters: the call waits for `stream` */
+        if (hipMemcpyAsync(h->fm_ph_end_host, h->fm_ph_end, sizeof(unsigned) * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        memcpy(p->phase_end_host, h->fm_ph_end_host, sizeof(unsigned) * B);
+    }
+    return 0;
+}
+
+int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
+                        const rade_fm_demod_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p || !p->b1 || !p->b2) return -1;
+    if (p->out_format != RADE_FM_F32 && p->out_format != RADE_FM_C64) return -1;
+    if (((uintptr_t)x_dev & 7) || ((uintptr_t)y_dev & (p->out_format == RADE_FM_C64 ? 7 : 3)) || ((uintptr_t)p->bb_out_dev & 7)) return -1;
+    if (!fm_rates_ok(p->Fs, p->fc, p->fd)) return -1;
+    if (p->N1 < 1 || p->N1 > RD_FM_NMAX || p->N2 < 1 || p->N2 > RD_FM_NMAX) return -1;
+    for (int k = 0; k < p->N1; k++) if (!isfinite(p->b1[k])) return -1;
+    for (int k = 0; k < p->N2; k++) if (!isfinite(p->b2[k])) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->fm_dps_host && !(h->fm_dps_host = pinned_alloc_opt(h, sizeof(rd_fm_dstream) * B))) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_fm_dstream *r = &h->fm_dps_host[b];
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
+        r->in_base = p->in_base_host ? p->in_base_host[b] : 0; r->n0 = p->n0_host ? p->n0_host[b] : r->in_base;
+        if (r->n_in < 0 || r->n_out < 0 || r->n_in > x_stride || r->n_out > y_stride || (p->bb_out_dev && r->n_out > p->bb_stride)) return -1;
+        if (r->in_base > (1LL << 62) || r->in_base < -(1LL << 62) || r->n0 > (1LL << 62) || r->n0 < -(1LL << 62)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (4.0 * p->N1 + 2.0 * p->N2) * r->n_out;
+    }
+    if (!max_out) return 0;
+    if (!h->fm_taps_host) {                                           /* one pinned block: the staging copy, and behind it the bytes of the last upload */
+        if (!(h->fm_taps_host = pinned_alloc_opt(h, sizeof(float) * 4 * RD_FM_NMAX))) return -1;
+        h->fm_taps_last = h->fm_taps_host + 2 * RD_FM_NMAX;
+        memset(h->fm_taps_last, 0, sizeof(float) * 2 * RD_FM_NMAX);
+    }
+    if (dev_grow(h, &h->fm_taps, NULL, 2 * RD_FM_NMAX, sizeof(float), 1) || dev_grow(h, &h->fm_dps, NULL, B, sizeof(rd_fm_dstream), 1)) return -1;
+    if (h->fm_N1 != p->N1 || h->fm_N2 != p->N2 || memcmp(h->fm_taps_last, p->b1, sizeof(float) * p->N1) ||
+        memcmp(h->fm_taps_last + RD_FM_NMAX, p->b2, sizeof(float) * p->N2)) {            /* other bytes than the tables on the device were made from */
+        h->fm_N1 = h->fm_N2 = 0;
+        memset(h->fm_taps_host, 0, sizeof(float) * 2 * RD_FM_NMAX);
+        memcpy(h->fm_taps_host, p->b1, sizeof(float) * p->N1); memcpy(h->fm_taps_host + RD_FM_NMAX, p->b2, sizeof(float) * p->N2);
+        if (hipMemcpyAsync(h->fm_taps, h->fm_taps_host, sizeof(float) * 2 * RD_FM_NMAX, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    }
+    /* the one small copy ahead of the launch; waited for, since the next call refills the staging records (and may refill the staging tables) */
+    if (hipMemcpyAsync(h->fm_dps, h->fm_dps_host, sizeof(rd_fm_dstream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    if (!h->fm_N1) { memcpy(h->fm_taps_last, h->fm_taps_host, sizeof(float) * 2 * RD_FM_NMAX); h->fm_N1 = p->N1; h->fm_N2 = p->N2; }
+    const double wd = 2.0 * M_PI * p->fd / p->Fs;
+    rd_fm_demod_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.bb_out = p->bb_out_dev; a.bb_stride = p->bb_stride;
+    a.ps = h->fm_dps; a.taps = h->fm_taps;
+    a.fcq = (unsigned)(long long)llrint(p->fc / p->Fs * 4294967296.0);
+    a.wd = (float)wd; a.inv_wd = (float)(1.0 / wd);
+    a.N1 = p->N1; a.N2 = p->N2; a.fmt = p->out_format; a.dont_limit = p->ph_dont_limit != 0; a.B = B; a.max_out = max_out;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_fm_demod(&a, stream)) return -1;
     PROF_END(h, stream, RADE_PROF_CHAN, work);
     return 0;
 }

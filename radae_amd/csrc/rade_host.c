@@ -6,6 +6,7 @@
  *   3. weight packing into the MFMA fragment order k_gemm streams;
  *   4. the fractional resampler's Q32.32 time base and its windowed-sinc taps (rade_batch_resample).
  *   5. the rational rate converter's ratio, taps and output count (rade_batch_rate_convert).
+ *   6. the analog FM stage's noise level, least-squares filter design and folded de-emphasis (rade_batch_fm_mod / rade_batch_fm_demod).
  *
  * Reference: radae/radae.py:128-234 (numerology/DFT/pilots/EOO), radae/dsp.py:40-61 (BPF),
  * :153-176 (p_w), :400-416 (Pmat); blob format src/write_rade_weights.c:51-74 and
@@ -689,4 +690,121 @@ long long rade_rate_count(long long in_end, int L, int M)
     if (in_end <= 0) return 0;
     const __int128 n = ((__int128)in_end * L + M - 1) / M;
     return n * M > ((__int128)1 << 62) ? -1 : (long long)n;
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * 6. the analog FM stage's host side (include/rade_batch.h: rade_batch_fm_mod / rade_batch_fm_demod; rade_fm.hip): the noise level of a C/N, the two
+ *    least-squares filters of fm.m:41-47 in closed form, the de-emphasis pole folded into the output filter
+ * -------------------------------------------------------------------------------------------*/
+/* fm.m:16,162: the sigma of unit-power-carrier noise over the whole band Fs that gives CNdB inside Carson's bandwidth Bfm = 2 (fd + fm_max) */
+double rade_fm_sigma(double CNdB, double Fs, double fm_max, double fd)
+{
+    if (!isfinite(CNdB) || !(Fs > 0.0) || !(fm_max > 0.0) || !(fd > 0.0) || !isfinite(Fs) || !isfinite(fm_max) || !isfinite(fd)) return -1.0;
+    return sqrt(Fs / (pow(10.0, CNdB / 10.0) * 2.0 * (fd + fm_max)));
+}
+
+/* K of the folded de-emphasis: the first power of a = 1 - 1 / (tc Fs) below 2^-30; 0: no de-emphasis (tc <= 0); -1: a outside (0, 1) or K > RD_FM_NMAX */
+int rade_fm_deemph_len(double Fs, double tc)
+{
+    if (!(tc > 0.0)) return tc == 0.0 ? 0 : -1;
+    if (!(Fs > 0.0) || !isfinite(Fs) || !isfinite(tc)) return -1;
+    const double a = 1.0 - 1.0 / (tc * Fs);
+    if (!(a > 0.0) || !(a < 1.0)) return -1;
+    double p = 1.0;
+    for (int K = 1; K <= RD_FM_NMAX; K++) { p *= a; if (p < 0x1p-30) return K; }
+    return -1;
+}
+
+static double fm_sincpi(double x) { return x == 0.0 ? 1.0 : sin(PI_D * x) / (PI_D * x); }
+
+/* firls of a type I filter (n odd) in closed form.  bands [2 nb] are edges in units of the Nyquist rate, amp [2 nb] the desired amplitude at each edge (linear in
+ * between), unit weights.  A(f) = sum_{i = 0..M} c_i cos(pi i f), M = (n - 1) / 2; minimising sum_bands int (A - D)^2 df gives Q c = r with
+ *     Q[i][j] = 1/2 sum_bands [q(i - j) + q(i + j)],   q(k) = int cos(pi k f) df = f1 sinc(k f1) - f0 sinc(k f0)                (Toeplitz plus Hankel)
+ *     r[i]    = sum_bands int (s f + d0) cos(pi i f) df = [(s f + d0) sin(pi i f) / (pi i) + s cos(pi i f) / (pi i)^2]  (i > 0),  [s f^2 / 2 + d0 f]  (i = 0)
+ * solved by Gaussian elimination with partial pivoting in double; h[M] = c_0, h[M +- i] = c_i / 2. */
+static int fm_firls(int n, int nb, const double *bands, const double *amp, double *h)
+{
+    const int M = (n - 1) / 2, D = M + 1;
+    double *Q = (double *)malloc(sizeof(double) * ((size_t)D * D + D + 2 * (size_t)n));
+    if (!Q) return -1;
+    double *r = Q + (size_t)D * D, *q = r + D;                      /* q[k], k = 0..2 M */
+    for (int k = 0; k <= 2 * M; k++) {
+        q[k] = 0.0;
+        for (int s = 0; s < nb; s++) q[k] += bands[2 * s + 1] * fm_sincpi(k * bands[2 * s + 1]) - bands[2 * s] * fm_sincpi(k * bands[2 * s]);
+    }
+    for (int i = 0; i < D; i++) {
+        for (int j = 0; j < D; j++) Q[(size_t)i * D + j] = 0.5 * (q[i > j ? i - j : j - i] + q[i + j]);
+        r[i] = 0.0;
+        for (int s = 0; s < nb; s++) {
+            const double f0 = bands[2 * s], f1 = bands[2 * s + 1], sl = (amp[2 * s + 1] - amp[2 * s]) / (f1 - f0), d0 = amp[2 * s] - sl * f0;
+            if (i == 0) r[i] += (0.5 * sl * f1 * f1 + d0 * f1) - (0.5 * sl * f0 * f0 + d0 * f0);
+            else {
+                const double w = PI_D * i;
+                r[i] += ((sl * f1 + d0) * sin(w * f1) / w + sl * cos(w * f1) / (w * w)) - ((sl * f0 + d0) * sin(w * f0) / w + sl * cos(w * f0) / (w * w));
+            }
+        }
+    }
+    for (int c = 0; c < D; c++) {
+        int piv = c;
+        for (int i = c + 1; i < D; i++) if (fabs(Q[(size_t)i * D + c]) > fabs(Q[(size_t)piv * D + c])) piv = i;
+        if (Q[(size_t)piv * D + c] == 0.0) { free(Q); return -1; }
+        if (piv != c) {
+            for (int j = 0; j < D; j++) { const double t = Q[(size_t)c * D + j]; Q[(size_t)c * D + j] = Q[(size_t)piv * D + j]; Q[(size_t)piv * D + j] = t; }
+            const double t = r[c]; r[c] = r[piv]; r[piv] = t;
+        }
+        for (int i = c + 1; i < D; i++) {
+            const double f = Q[(size_t)i * D + c] / Q[(size_t)c * D + c];
+            if (f == 0.0) continue;
+            for (int j = c; j < D; j++) Q[(size_t)i * D + j] -= f * Q[(size_t)c * D + j];
+            r[i] -= f * r[c];
+        }
+    }
+    for (int i = D - 1; i >= 0; i--) {
+        double s = r[i];
+        for (int j = i + 1; j < D; j++) s -= Q[(size_t)i * D + j] * r[j];
+        r[i] = s / Q[(size_t)i * D + i];
+    }
+    h[M] = r[0];
+    for (int i = 1; i <= M; i++) h[M - i] = h[M + i] = 0.5 * r[i];
+    free(Q);
+    return 0;
+}
+
+/* the two filters of analog_fm_init (fm.m:41-47): bands [0, 0.95 fc, 1.05 fc, 1], amplitudes [1, 1, 0.01, 0.01]; bin: fc = (Bfm / 2) / (Fs / 2), ntaps values;
+ * bout: fc = fm_max / (Fs / 2), convolved with a^k, k < K when de_emp_tc > 0: ntaps + K - 1 values (else ntaps).  Returns the length of bout; bin == bout == NULL only
+ * queries.  -1: ntaps even or outside 3..RD_FM_NMAX, the folded length above RD_FM_NMAX, a band edge 1.05 fc >= 1, values that are not finite or not positive */
+int rade_fm_taps(double Fs, double fm_max, double fd, int ntaps, double de_emp_tc, double *bin, double *bout)
+{
+    if (!(Fs > 0.0) || !(fm_max > 0.0) || !(fd > 0.0) || !isfinite(Fs) || !isfinite(fm_max) || !isfinite(fd) || !isfinite(de_emp_tc) || de_emp_tc < 0.0) return -1;
+    if (ntaps < 3 || ntaps > RD_FM_NMAX || !(ntaps & 1)) return -1;
+    const int K = rade_fm_deemph_len(Fs, de_emp_tc);
+    if (K < 0) return -1;
+    const int N2 = K ? ntaps + K - 1 : ntaps;
+    if (N2 > RD_FM_NMAX) return -1;
+    const double fc1 = (fd + fm_max) / (Fs / 2.0), fc2 = fm_max / (Fs / 2.0);
+    if (!(1.05 * fc1 < 1.0) || !(1.05 * fc2 < 1.0)) return -1;
+    if (!bin && !bout) return N2;
+    const double amp[4] = { 1.0, 1.0, 0.01, 0.01 };
+    if (bin) {
+        const double bands[4] = { 0.0, fc1 * (1.0 - 0.05), fc1 * (1.0 + 0.05), 1.0 };
+        if (fm_firls(ntaps, 2, bands, amp, bin)) return -1;
+    }
+    if (bout) {
+        const double bands[4] = { 0.0, 0.95 * fc2, 1.05 * fc2, 1.0 };
+        double h[RD_FM_NMAX];
+        if (fm_firls(ntaps, 2, bands, amp, h)) return -1;
+        if (!K) memcpy(bout, h, sizeof(double) * ntaps);
+        else {
+            const double a = 1.0 - 1.0 / (de_emp_tc * Fs);
+            double pw[RD_FM_NMAX];
+            pw[0] = 1.0;
+            for (int k = 1; k < K; k++) pw[k] = pw[k - 1] * a;
+            for (int i = 0; i < N2; i++) {
+                double s = 0.0;
+                for (int k = 0; k < K; k++) if (i - k >= 0 && i - k < ntaps) s += pw[k] * h[i - k];
+                bout[i] = s;
+            }
+        }
+    }
+    return N2;
 }

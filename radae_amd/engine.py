@@ -49,6 +49,16 @@ class RateParams(C.Structure):
     _fields_ = [("L", C.c_int), ("M", C.c_int), ("n0_host", C.c_void_p), ("in_base_host", C.c_void_p)]
 
 
+class FmModParams(C.Structure):
+    _fields_ = [("Fs", C.c_double), ("fc", C.c_double), ("fd", C.c_double), ("in_format", C.c_int), ("out_mode", C.c_int), ("sigma", C.c_double),
+                ("seed", C.c_ulonglong), ("noise_dev", C.c_void_p), ("phase0_host", C.c_void_p), ("phase_end_host", C.c_void_p), ("n0_host", C.c_void_p)]
+
+
+class FmDemodParams(C.Structure):
+    _fields_ = [("Fs", C.c_double), ("fc", C.c_double), ("fd", C.c_double), ("out_format", C.c_int), ("ph_dont_limit", C.c_int), ("b1", C.c_void_p), ("N1", C.c_int),
+                ("b2", C.c_void_p), ("N2", C.c_int), ("in_base_host", C.c_void_p), ("n0_host", C.c_void_p), ("bb_out_dev", C.c_void_p), ("bb_stride", C.c_long)]
+
+
 class RxStatus(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("consumed", "n_calls", "n_valid", "has_eoo", "nin", "sync", "snr_dB", "state")]
 
@@ -124,6 +134,12 @@ def load_library() -> C.CDLL:
         L.rade_batch_rate_convert.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, vp, C.c_long, vp, C.POINTER(RateParams), vp]
         L.rade_rate_count.restype = C.c_longlong; L.rade_rate_count.argtypes = [C.c_longlong, C.c_int, C.c_int]
         L.rade_rate_taps.argtypes = [C.c_int, C.c_int, vp]
+    if hasattr(L, "rade_batch_fm_mod"):
+        L.rade_batch_fm_mod.argtypes = [vp, vp, C.c_long, vp, vp, C.c_long, C.POINTER(FmModParams), vp]
+        L.rade_batch_fm_demod.argtypes = [vp, vp, C.c_long, vp, vp, C.c_long, vp, C.POINTER(FmDemodParams), vp]
+        L.rade_fm_sigma.restype = C.c_double; L.rade_fm_sigma.argtypes = [C.c_double] * 4
+        L.rade_fm_deemph_len.argtypes = [C.c_double, C.c_double]
+        L.rade_fm_taps.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, vp, vp]
     _lib = L
     return L
 
@@ -147,6 +163,7 @@ EXPORTED_SYMBOLS = [
     "rade_batch_resample", "rade_resample_count", "rade_resample_taps",
     "rade_batch_wire_in", "rade_batch_wire_out",
     "rade_batch_rate_convert", "rade_rate_count", "rade_rate_taps",
+    "rade_batch_fm_mod", "rade_batch_fm_demod", "rade_fm_sigma", "rade_fm_deemph_len", "rade_fm_taps",
 ]
 WIRE_REAL, WIRE_IQ = 0, 1                                                          # rade_batch_wire_in / _out mode
 
@@ -204,6 +221,48 @@ def rate_taps(L: int, M: int) -> np.ndarray:
     t = np.zeros((int(L) // int(np.gcd(int(L), int(M))), T), np.float32)
     assert lib.rade_rate_taps(int(L), int(M), t.ctypes.data) == T
     return t
+
+
+FM_F32, FM_C64 = 0, 1                                                              # rade_batch_fm_mod input / rade_batch_fm_demod output format
+FM_OUT_COMPLEX, FM_OUT_REAL = 0, 1                                                 # rade_batch_fm_mod output mode
+FM_DE_EMP_TC = 50e-6                                                               # fm.m:17
+
+
+def fm_sigma(CNdB: float, Fs: float, fm_max: float, fd: float) -> float:
+    """rade_fm_sigma: sqrt(Fs / (CN Bfm)), Bfm = 2 (fd + fm_max): the noise sigma that gives a unit carrier the C/N CNdB inside Carson's bandwidth (fm.m:16,162)."""
+    v = float(load_library().rade_fm_sigma(float(CNdB), float(Fs), float(fm_max), float(fd)))
+    if v < 0:
+        raise ValueError(f"rade_fm_sigma refuses CNdB {CNdB!r}, Fs {Fs!r}, fm_max {fm_max!r}, fd {fd!r} (finite, rates > 0)")
+    return v
+
+
+def fm_deemph_len(Fs: float, tc: float = FM_DE_EMP_TC) -> int:
+    """rade_fm_deemph_len: K of the folded de-emphasis, the first power of a = 1 - 1 / (tc Fs) below 2^-30."""
+    K = int(load_library().rade_fm_deemph_len(float(Fs), float(tc)))
+    if K < 0:
+        raise ValueError(f"rade_fm_deemph_len refuses Fs {Fs!r}, tc {tc!r}")
+    return K
+
+
+def fm_taps(Fs: float, fm_max: float, fd: float, ntaps: int = 201, de_emp_tc: float = 0.0):
+    """rade_fm_taps: (bin, bout) as float64 arrays, the two least-squares filters of fm.m:41-47; with de_emp_tc > 0 the de-emphasis pole is folded into bout
+    (ntaps + K - 1 values).  Host only.  fm_demod takes them rounded to float32."""
+    lib = load_library()
+    N2 = int(lib.rade_fm_taps(float(Fs), float(fm_max), float(fd), int(ntaps), float(de_emp_tc), None, None))
+    if N2 < 0:
+        raise ValueError(f"rade_fm_taps refuses Fs {Fs!r}, fm_max {fm_max!r}, fd {fd!r}, ntaps {ntaps!r}, de_emp_tc {de_emp_tc!r} (ntaps odd, 3..511; at most 512 taps folded)")
+    b1, b2 = np.zeros(int(ntaps), np.float64), np.zeros(N2, np.float64)
+    assert lib.rade_fm_taps(float(Fs), float(fm_max), float(fd), int(ntaps), float(de_emp_tc), b1.ctypes.data, b2.ctypes.data) == N2
+    return b1, b2
+
+
+def fm_pre_emphasis(mod: np.ndarray, Fs: float, tc: float = FM_DE_EMP_TC) -> np.ndarray:
+    """fm.m:80-83 on the host (not on the device: the normalisation needs the whole signal): filter([1, -(1 - 1 / (tc Fs))], 1, mod) / max of it, per row."""
+    mod = np.asarray(mod, np.float64)
+    a = 1.0 - 1.0 / (tc * Fs)
+    y = mod.copy()
+    y[..., 1:] -= a * mod[..., :-1]
+    return y / y.max(axis=-1, keepdims=True)
 
 
 def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
@@ -525,6 +584,68 @@ class BatchEngine:
         if self.lib.rade_batch_rate_convert(self.h, x.data_ptr(), xs, n_in.ctypes.data, fmt, gain, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_rate_convert failed (L, M >= 1 with ceil(M / L) <= 8 and L T <= 16384 after reduction, a finite gain, n0 >= 0, n_out <= the row of out)")
         return out, n_out
+
+    # ---- analog FM ----------------------------------------------------------------------------------------------------------
+    def fm_mod(self, m, Fs: float, fc: float, fd: float, n=None, real: bool = False, sigma: float = 0.0, seed: int = 0, noise=None, phase0=0, n0=0, out=None,
+               want_phase: bool = True):
+        """The analog FM modulator (rade_batch_fm_mod, fm.m:74-94).  m: cuda float32 [B, N], or complex64 [B, N] whose real part is used.  Returns
+        (tx complex64 [B, N], phase_end uint32 [B] or None): tx[i] = cis(phase0 + sum_{k <= i} inc[k]), a 32-bit NCO.  n: samples of each row (default N); phase0: the
+        phase in front of the first sample, n0: its absolute index (what the generated noise is counted by): scalars or B per-stream values.  sigma > 0 adds noise:
+        `noise` (cuda complex64 [B, N], unit) or generated from `seed`; real: (Re tx + sigma g, +0) instead of tx + sigma / sqrt 2 (g0 + j g1).  Samples past a
+        stream's n are zeros (left alone in a caller's `out`).  want_phase=False skips the read-back and the wait behind the kernels (the call still waits once, ahead of its launches, for the copy of its per-stream records and so for the work queued in front of it)."""
+        import torch
+        B = self.B
+        assert m.is_cuda and m.dim() == 2 and m.shape[0] == B and (m.stride(1) == 1 or m.shape[1] <= 1)
+        assert m.dtype in (torch.float32, torch.complex64)
+        N = m.shape[1]
+        n = _per_stream(B, N if n is None else n, np.int32, "n")
+        if n.min() < 0 or n.max() > N:
+            raise ValueError(f"n: between 0 and the {N} samples of a row")
+        ph0 = _per_stream(B, phase0, np.uint32, "phase0"); n0 = _per_stream(B, n0, np.int64, "n0")
+        ph_end = np.zeros(B, np.uint32) if want_phase else None
+        if out is None:
+            out = torch.zeros((B, max(N, 1)), dtype=torch.complex64, device=m.device)
+        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n.max()
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.complex64 and noise.dim() == 2 and noise.shape[0] == B and noise.shape[1] >= n.max()
+            noise = noise[:, :int(n.max())].contiguous()              # dense [B][max n]
+        p = FmModParams(float(Fs), float(fc), float(fd), FM_F32 if m.dtype == torch.float32 else FM_C64, FM_OUT_REAL if real else FM_OUT_COMPLEX, float(sigma), int(seed),
+                        noise.data_ptr() if noise is not None else None, ph0.ctypes.data, ph_end.ctypes.data if want_phase else None, n0.ctypes.data)
+        ms = m.stride(0) if B > 1 else N
+        ys = out.stride(0) if B > 1 else out.shape[1]
+        if self.lib.rade_batch_fm_mod(self.h, m.data_ptr(), ms, n.ctypes.data, out.data_ptr(), ys, C.byref(p), _stream_ptr()):
+            raise RuntimeError("rade_batch_fm_mod failed (Fs > 0, |fc| <= Fs / 2, 0 < fd <= Fs / 2, sigma >= 0 with a seed or a noise tensor, n0 >= 0)")
+        return out, ph_end
+
+    def fm_demod(self, x, Fs: float, fc: float, fd: float, b1, b2, n_in=None, n_out=None, in_base=0, n0=None, complex_out: bool = False, ph_dont_limit: bool = False,
+                 want_bb: bool = False):
+        """The analog FM demodulator (rade_batch_fm_demod, fm.m:97-126): mix down by fc, input FIR b1, discriminator (clamped to the deviation unless ph_dont_limit),
+        output FIR b2.  x: cuda complex64 [B, N]; b1, b2: host arrays (rounded to float32), 1..512 taps each.  Returns (y float32 [B, max n_out] -- complex64 with +0
+        imaginary parts when complex_out --, bb complex64 [B, max n_out] or None, n_out int32 [B]).  x[b, g] is the sample of absolute index in_base + g; output i is the
+        sample of absolute index n0 + i (default n0 = in_base, n_out = n_in: one output per input).  Samples past a stream's n_out are zeros."""
+        import torch
+        B = self.B
+        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        N = x.shape[1]
+        b1 = np.ascontiguousarray(b1, dtype=np.float32); b2 = np.ascontiguousarray(b2, dtype=np.float32)
+        n_in = _per_stream(B, N if n_in is None else n_in, np.int32, "n_in")
+        if n_in.min() < 0 or n_in.max() > N:
+            raise ValueError(f"n_in: between 0 and the {N} samples of a row")
+        in_base = _per_stream(B, in_base, np.int64, "in_base")
+        n0 = in_base.copy() if n0 is None else _per_stream(B, n0, np.int64, "n0")
+        if n_out is None:
+            n_out = np.maximum(in_base + n_in - n0, 0).astype(np.int32)
+        else:
+            n_out = _per_stream(B, n_out, np.int32, "n_out")
+        W = max(int(n_out.max()), 1)
+        y = torch.zeros((B, W), dtype=torch.complex64 if complex_out else torch.float32, device=x.device)
+        bb = torch.zeros((B, W), dtype=torch.complex64, device=x.device) if want_bb else None
+        p = FmDemodParams(float(Fs), float(fc), float(fd), FM_C64 if complex_out else FM_F32, int(bool(ph_dont_limit)), b1.ctypes.data, b1.size, b2.ctypes.data, b2.size,
+                          in_base.ctypes.data, n0.ctypes.data, bb.data_ptr() if want_bb else None, W)
+        xs = x.stride(0) if B > 1 else N
+        if self.lib.rade_batch_fm_demod(self.h, x.data_ptr(), xs, n_in.ctypes.data, y.data_ptr(), W, n_out.ctypes.data, C.byref(p), _stream_ptr()):
+            raise RuntimeError("rade_batch_fm_demod failed (Fs > 0, |fc| <= Fs / 2, 0 < fd <= Fs / 2, 1..512 finite taps per filter)")
+        return y, bb, n_out
 
     # ---- the sound-card wire ------------------------------------------------------------------
     def wire_in(self, i16, n=None, iq: bool = False, gain: float = 1.0):
@@ -870,3 +991,43 @@ class RateConverter:
         if self.tail is None:
             return None, np.zeros(self.eng.B, np.int32)
         return self._emit(self.tail, self.n_fed)
+
+
+class FmModulator:
+    """The FM modulator applied to streams that arrive in pieces: carries each stream's NCO phase and absolute sample index (the noise counter) from piece to piece.
+    The concatenated outputs are bit-identical to one fm_mod() call over the whole stream, noise included."""
+
+    def __init__(self, engine: BatchEngine, Fs: float, fc: float, fd: float, real: bool = False, sigma: float = 0.0, seed: int = 0):
+        self.eng, self.Fs, self.fc, self.fd, self.real, self.sigma, self.seed = engine, Fs, fc, fd, real, sigma, seed
+        self.phase = np.zeros(engine.B, np.uint32)
+        self.n0 = 0                                                   # samples taken so far (every stream gets pieces of the same length)
+
+    def feed(self, m, noise=None):
+        """m cuda float32 or complex64 [B, n]: the next n modulating samples of every stream -> tx complex64 [B, n]"""
+        tx, self.phase = self.eng.fm_mod(m, self.Fs, self.fc, self.fd, real=self.real, sigma=self.sigma, seed=self.seed, noise=noise, phase0=self.phase, n0=self.n0)
+        self.n0 += m.shape[1]
+        return tx
+
+
+class FmDemodulator:
+    """The FM demodulator applied to streams that arrive in pieces (BatchEngine.fm_demod is stateless: this keeps what the next piece needs): the last N1 + N2 - 1 input
+    samples of every stream stay on the device.  The concatenated outputs are bit-identical to one fm_demod() call over the whole stream."""
+
+    def __init__(self, engine: BatchEngine, Fs: float, fc: float, fd: float, b1, b2, complex_out: bool = False, ph_dont_limit: bool = False):
+        self.eng, self.Fs, self.fc, self.fd, self.complex_out, self.ph_dont_limit = engine, Fs, fc, fd, complex_out, ph_dont_limit
+        self.b1, self.b2 = np.ascontiguousarray(b1, dtype=np.float32), np.ascontiguousarray(b2, dtype=np.float32)
+        self.H = self.b1.size + self.b2.size - 1                      # output n depends on inputs n - H .. n
+        self.tail = None                                              # input samples [n_fed - H, n_fed); zeros ahead of the stream; made from the first piece
+        self.n_fed = 0
+
+    def feed(self, x, want_bb: bool = False):
+        """x cuda complex64 [B, n]: the next n samples of every stream -> (y [B, n], bb [B, n] or None)"""
+        import torch
+        if self.tail is None:
+            self.tail = torch.zeros((x.shape[0], self.H), dtype=x.dtype, device=x.device)
+        buf = torch.cat([self.tail, x], dim=1)
+        y, bb, _ = self.eng.fm_demod(buf, self.Fs, self.fc, self.fd, self.b1, self.b2, in_base=self.n_fed - self.H, n0=self.n_fed, n_out=x.shape[1],
+                                     complex_out=self.complex_out, ph_dont_limit=self.ph_dont_limit, want_bb=want_bb)
+        self.tail = buf[:, -self.H:].contiguous()
+        self.n_fed += x.shape[1]
+        return y, bb
