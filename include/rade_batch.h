@@ -28,6 +28,8 @@
  *                          analog_bbfm.sh:37,43): 48 or 44.1 kHz <-> the modem's 8 kHz, a polyphase L / M converter whose anti-alias filter scales with the ratio
  *   rade_batch_fm_mod      fm.m:74-94 (analog_fm_mod) with the noise of fm.m:171 / :316-322: the analog-FM baseline every BBFM result is compared with (analog_bbfm.sh:37-43)
  *   rade_batch_fm_demod    fm.m:97-126 (analog_fm_demod): mix, input filter, discriminator, output filter (de-emphasis folded into it)
+ *   rade_batch_cno_est     est_CNo.py:23-73 as ota_test.sh:136-148 (process_rx) runs it over the first 10 s of every stored off-air file: the C/No of the 400-2000 Hz chirp
+ *                          header and the time at which it starts; rade_chirp: chirp.py:50-65, the header itself
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -122,6 +124,8 @@ int rade_batch_n_streams(const rade_batch *h);
  *                                           samples of row b are written, 8 bytes at a time; p->noise_dev (complex64) is dense [B][max n]
  *   rade_batch_fm_demod                     x_dev (complex64; x_stride >= n_in, checked) in; y_dev (float32 or complex64; y_stride >= n_out, checked; 4- or 8-byte alignment)
  *                                           and p->bb_out_dev (complex64; bb_stride >= n_out, checked): n_out[b] samples of row b are written, one element at a time
+ *   rade_batch_cno_est                      x_dev (complex64; x_stride >= every n, checked) in, read inside the n[b] samples of row b only and never written; the results go to
+ *                                           host memory
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -423,6 +427,68 @@ int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const i
 double rade_fm_sigma(double CNdB, double Fs, double fm_max, double fd);
 int rade_fm_deemph_len(double Fs, double tc);
 int rade_fm_taps(double Fs, double fm_max, double fd, int ntaps, double de_emp_tc, double *bin, double *bout);
+
+/* ---- C/No of the chirp header and where it starts: est_CNo.py on the device, every stream in one call (rade_cno.hip) -------------------------------------
+ * ota_test.sh:136-148 cuts the first 10 s of a stored off-air file, runs est_CNo.py over them and trims the file at the time of the best window.  With Fs = 8000 and
+ * hop = Fs // 4 = 2000 (est_CNo.py:23-73):
+ * Windows: N = (int)(8000 window_time) samples, starting at st = 0, 2000, .. while st < n - N (np.arange(0, len - N, hop)): n = N has no window, N + 1 .. N + 2000 one,
+ *   N + 2001 two.
+ * Bins: bph = N / 8000.0 (double); flow_bin = (int)(bph flow), fhigh_bin = (int)(bph fhigh), noise_st = fhigh_bin + (int)(0.1 fhigh_bin), noise_en = noise_st +
+ *   (int)(0.1 fhigh_bin): C truncation toward zero, which is Python's int() (rade_cno_plan; n_bins = the bins of both bands together).
+ * Device: per window two numbers, S_c = sum |X[k]|^2 over [flow_bin, fhigh_bin) and S_n over [noise_st, noise_en), X the N-point DFT of the window's complex64 samples.
+ * Host, in double after the read-back, written as the script writes it (the logarithms are the host's libm):
+ *     No = S_n / ((noise_en - noise_st) / bph)      C = S_c - No (fhigh - flow)      for C > 0: CNodB = 10 log10(C) - 10 log10(No)
+ *   the maximum over the windows with C > 0 by strict >, from max_CNodB = 0 and max_st = 0 (the script's max_time is max_st / 8000); max_SNRdB = max_CNodB - 10 log10(3000).
+ *   bands_host, when given, receives (S_c, S_n) of window w of stream b at [b][w][0..1], rows max_windows windows apart; windows past a stream's own are not written.
+ * How the device forms X (H = 2000, J = N / H, k = J q + r; t[m] = e^{-2 pi i m / N}, ONE table of N complex64 made on the host in double and rounded once per
+ *   component, kept in the engine's device memory and re-made when N changes):
+ *     Y[n]      = x[b H + n] t[r n]                                                       block b, residue r; n = 50 n1 + n2, q = q1 + 40 q2
+ *     A[q1][n2] = t[J n2 q1] sum_{n1 = 0..39} Y[50 n1 + n2] t[(N / 40)((q1 n1) mod 40)]
+ *     B_b[k]    = sum_{n2 = 0..49} A[q1][n2] t[(N / 50)((q2 n2) mod 50)]                   = sum_{n < H} x[b H + n] e^{-2 pi i k n / N}, for the k of the two bands only
+ *     X_w[k]    = sum_{j = 0..J-1} B_{w+j}[k] t[H ((r j) mod J)]                           formed afresh for every window: nothing is carried from window to window
+ *   Summation order: every sum in the order written, one float32 accumulator per component starting from 0, a term acc += y w as four fused multiply-adds (re += y.re w.re,
+ *   re -= y.im w.im, im += y.re w.im, im += y.im w.re); a lone product y w as one rounded multiply and one fused multiply-add per component.  |X|^2 = re re + im im and
+ *   everything behind it in double: per residue a thread adds its bins (i, i + 512, ..) in ascending order, the 64 lanes of a wavefront are added by a fixed exchange
+ *   pattern, the 8 wavefronts in ascending order, and a second launch adds the residues r = 0..J-1 in ascending order.  No atomics: identical calls give identical bits, and
+ *   a stream's numbers do not depend on the other streams of the batch.
+ * Error bound, counted from these roundings (u = 2^-24; every coefficient has modulus 1, so errors propagate through the later stages unamplified): a table entry is off by at
+ *   most u; a lone product adds 2 roundings per component, at most 4 u of the operand's modulus; a sum of m terms is, per component, a 2 m-term real dot product of fused
+ *   multiply-adds, off by at most 2 m u sqrt 2 sum |y_i| per component, 4 m u sum |y_i| in modulus.  Along the path of a bin: (1 + 4) + (1 + 160) + (1 + 4) + (1 + 200) + (1 + 4 J)
+ *   = (372 + 4 J) u, times 1.01 for the terms of second order:
+ *     |X^ - X| <= 1.01 (372 + 4 J) u sum_n |x_n| <= gamma ||x_w||_2,   gamma = 1.01 (372 + 4 J) 2^-24 sqrt N        (J = 16: 2.63e-5 sqrt N)
+ *   and for a band of nb bins with exact sum S: |dS| <= 2 e sqrt(nb S) + nb e^2, e = gamma ||x_w||_2 (Cauchy-Schwarz over the band).  The double sums add nothing that counts
+ *   (nb 2^-53).  A worst-case bound: tests/test_cno_gpu.py records how far below it the device stays.
+ * Input: complex64, 8-byte aligned, x_stride >= every n_host[b]; not written; nothing outside a stream's n_host[b] samples is read (of those, the samples of its windows).
+ * The call copies the counts to the device, launches, reads the band sums back and SYNCHRONISES `stream` before the host arithmetic, as the metered rade_batch_wire_out
+ *   does.  Any engine (the model is not used; no encoder or receiver state is touched); the device memory (table, counts, partial and band sums) belongs to the engine and is
+ *   sized on first use and when a call needs more.
+ * Refused with -1 before any launch and with nothing written: NULL h, x_dev, n_host, p or result_host; x_dev not 8-byte aligned; a negative count or one above x_stride; any
+ *   n_host[b] < N (the script asserts it); values of p that are not finite; DEVIATION from the script, which takes any window length: N must be a positive multiple of 2000 with
+ *   J = N / 2000 <= 32 (window_time a multiple of 0.25 s up to 8 s); flow_bin < 0 (a negative slice index means something else in Python), flow_bin >= fhigh_bin,
+ *   (int)(0.1 fhigh_bin) < 1, noise_en > N (the script would silently sum a clipped slice and still divide by the full width); max_windows smaller than the largest window
+ *   count when bands_host is given; and, a limit of the kernel's LDS ring, J (ceil((fhigh_bin - flow_bin) / J) + ceil((noise_en - noise_st) / J)) > 16000 (the defaults need
+ *   450 J, so every admitted window length passes; it refuses bands that are together wider than about 2000 Hz at J = 32, 4000 Hz at J = 16).
+ * rade_cno_plan: host only; the numbers above for a parameter set, -1 where the call would refuse it.
+ * rade_chirp: host only; chirp.py:50-65 restated in C: freq = flow, delta = (fhigh - flow) / 8000, phase = 0 in double; per sample phase += 2 pi freq / 8000 (the script's
+ *   operation order: (2 pi freq) / 8000), phase -= 2 pi (int)(phase / (2 pi)), freq += delta, then the two turn-around tests (freq > fhigh: delta = -(fhigh - flow) / 8000;
+ *   freq < flow: delta = +(fhigh - flow) / 8000), then iq_out[n] = (amp cos(phase), amp sin(phase)) rounded once to float32.  A sequential recurrence of 36000 steps for the
+ *   header of ota_test.sh:336, whose only per-stream parameter is amp: it stays on the host, as the FM block's pre-emphasis does.  -1: NULL, nsam < 0, values that
+ *   are not finite.  libm's cos / sin against NumPy's may differ in the last place of the double: at most one float32 ulp per component (tests/test_cno_host.py counts them). */
+typedef struct {
+    double window_time;        /* seconds; N = (int)(8000 * window_time)          (est_CNo.py:25) */
+    double flow, fhigh;        /* Hz, the C+N band                                (est_CNo.py:19-20) */
+} rade_cno_params;
+typedef struct { int N, J, n_bins, flow_bin, fhigh_bin, noise_st, noise_en; } rade_cno_plan_t;
+typedef struct {
+    int n_windows, n_positive;                  /* windows evaluated; those with C > 0 */
+    long long max_st;                           /* start sample of the best window (0 when none) */
+    double max_CNodB, max_SNRdB;                /* est_CNo.py:52-55, :71 */
+} rade_cno_result;
+int rade_cno_plan(const rade_cno_params *p, rade_cno_plan_t *out);
+int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, const rade_cno_params *p,
+                       double *bands_host /* [B][max_windows][2] = (C+N, band sum of No) or NULL */, int max_windows,
+                       rade_cno_result *result_host /* [B] */, void *stream);
+int rade_chirp(float *iq_out /* [nsam][2] */, int nsam, double flow, double fhigh, double amp);
 
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the

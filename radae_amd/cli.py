@@ -10,6 +10,8 @@
     python -m radae_amd.cli multipath_samples mpp 8000 50 30 10 h.f32 g.f32                                                      multipath_samples.m
     python -m radae_amd.cli bbfm_inference MODEL features.f32 features_hat.f32 [--CNRdB ..] [--h_file h_lmr60.f32] [--write_latent z.f32]    bbfm_inference.py
     python -m radae_amd.cli analog_fm IN.s16 OUT.s16 CNRdB [--seed N]                                                             analog_bbfm.sh:37-43 from the 8 kHz int16 file onward
+    python -m radae_amd.cli est_cno RX.f32 [--window_time S] [--flow HZ] [--fhigh HZ]                                              est_CNo.py (without --plots); the periodograms on the device
+    python -m radae_amd.cli chirp OUT.f32 NSEC [--flow HZ] [--fhigh HZ] [--amp A]                                                  chirp.py (host)
 
 so that the reference's shell pipelines (`cat features_in.f32 | python3 radae_txe.py > rx.f32`, `cat rx.f32 | python3 radae_rxe.py > features_out.f32`: CMakeLists.txt:300-420) run with
 `python3 -m radae_amd.cli txe|rxe` in their place; `--fs 48000` (or 44100, ..) takes the place of the `sox .. -r 8000` stage of the off-air pipelines (radae_rx.sh:33,39): the
@@ -516,9 +518,54 @@ def _analog_fm(argv):
     return 0
 
 
+def _est_cno(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli est_cno", description="Estimate C/No from a file of samples (est_CNo.py): C+N in a band that holds the signal, No in an "
+                                 "adjacent band, the window with the highest C/No; the periodograms run on the device (rade_batch_cno_est)")
+    ap.add_argument("rx", type=str, help="path to signal + noise input file of rate Fs rx samples in ..IQIQ...f32 format")
+    ap.add_argument("--window_time", type=float, default=4.0, help="size of time domain window (seconds) used for SNR measurement, a multiple of 0.25 up to 8 (default 4.0)")
+    ap.add_argument("--flow", type=float, default=400.0, help="lower freq limit for C+N band (default 400 Hz)")
+    ap.add_argument("--fhigh", type=float, default=2000.0, help="upper limit for C+N band (default 2000 Hz)")
+    args = ap.parse_args(argv)
+    import torch
+    from . import engine
+    Fs = engine.CNO_FS
+    rx = np.fromfile(args.rx, dtype=np.csingle)
+    q = engine.cno_plan(args.window_time, args.flow, args.fhigh)
+    assert len(rx) >= q.N
+    eng = engine.BatchEngine(1, max_tx_mf=1)
+    (res,), bands = eng.cno_est(torch.tensor(rx[None], device="cuda"), window_time=args.window_time, flow=args.flow, fhigh=args.fhigh, bands=True)
+    eng.close()
+    bins_per_Hz = q.N / Fs
+    Nbw = (q.noise_en - q.noise_st) / bins_per_Hz
+    for w in range(res.n_windows):                           # the script's per-window lines, from the band sums by the script's own arithmetic
+        st = w * engine.CNO_HOP
+        No = bands[0, w, 1] / Nbw
+        C = bands[0, w, 0] - No * (args.fhigh - args.flow)
+        if C > 0:
+            CNodB = 10 * np.log10(C) - 10 * np.log10(No)
+            print(f"time: {st:8d} {st/Fs:5.2f} CNodB: {CNodB:5.2f}")
+    print(f"           Time   C/No    SNR3k")
+    print(f"Measured: {res.max_st/Fs:5.2f}  {res.max_CNodB:6.2f}  {res.max_SNRdB:6.2f}")
+    return 0
+
+
+def _chirp(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli chirp", description="Generates a .f32 IQIQI chirp file for HF channel SNR measurement (chirp.py)")
+    ap.add_argument("f32", type=str, help="path to output IQ .f32 file")
+    ap.add_argument("Nsec", type=float, help="output file length in seconds")
+    ap.add_argument("--flow", type=float, default=400.0, help="lower freq limit for chirp (default 400 Hz)")
+    ap.add_argument("--fhigh", type=float, default=2000.0, help="upper limit for chirp (default 2000 Hz)")
+    ap.add_argument("--amp", type=float, default=0.25, help="magnitude of chirp (default 0.25)")
+    args = ap.parse_args(argv)
+    from . import engine
+    engine.chirp(args.Nsec, args.flow, args.fhigh, args.amp).tofile(args.f32)
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
-    cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm}
+    cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm,
+            "est_cno": _est_cno, "chirp": _chirp}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2

@@ -303,6 +303,26 @@ int rd_launch_fm_demod(const rd_fm_demod_args *a, rd_stream_t s);
 /* tests only: the phasor on n phases (ph, cis_out complex64) and / or the discriminator's atan2 on n complex64 pairs (d, atan_out float32); device pointers, NULL skips */
 int rd_launch_fm_probe(const unsigned *ph, void *cis_out, const void *d, float *atan_out, int n, rd_stream_t s);
 
+/* the periodograms of rade_batch_cno_est (rade_cno.hip; include/rade_batch.h states the arithmetic): k_cno_blocks, one workgroup per (residue k mod J, stream), the
+ * wanted bins of the last J blocks in LDS, [J][pitch] complex64; k_cno_sum adds the residues.  pitch = the most wanted bins any residue has (rd_cno_pitch). */
+#define RD_CNO_H 2000                                            /* the hop, Fs // 4, and the length of a block */
+#define RD_CNO_JMAX 32                                           /* blocks per window */
+#define RD_CNO_RING_MAX 16000                                    /* complex64 of the ring, J x pitch */
+static inline int rd_cno_pitch(int J, int flow_bin, int fhigh_bin, int noise_st, int noise_en)
+{   /* a band [lo, hi) holds ceil((hi - r) / J) - ceil((lo - r) / J) bins of residue r (each ceil 0 where its argument is negative): at most ceil((hi - lo) / J) */
+    return (fhigh_bin - flow_bin + J - 1) / J + (noise_en - noise_st + J - 1) / J;
+}
+typedef struct {
+    const void *x; long x_stride;                               /* complex64, stream b at + b * x_stride samples */
+    const int *n;                                               /* device [B] sample counts */
+    const float *tw;                                            /* device [N][2]: e^{-2 pi i m / N} */
+    double *part;                                               /* device [B][max_win][J][2]: a residue's band sums of a window */
+    double *bands;                                              /* device [B][max_win][2] */
+    int N, J, B, max_win;                                       /* max_win: the most windows any stream of the call has; the row length of part and bands */
+    int flow_bin, fhigh_bin, noise_st, noise_en, pitch;
+} rd_cno_args;
+int rd_launch_cno(const rd_cno_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

@@ -112,6 +112,10 @@ struct rade_batch {
      * (fm_taps_last with fm_N1, fm_N2: uploaded again only when a call brings other bytes).  First use. */
     rd_fm_stream *fm_ps, *fm_ps_host; unsigned *fm_tsum; long fm_tsum_cap; unsigned *fm_ph_end, *fm_ph_end_host;
     rd_fm_dstream *fm_dps, *fm_dps_host; float *fm_taps, *fm_taps_host, *fm_taps_last; int fm_N1, fm_N2;
+    /* rade_batch_cno_est: the table e^{-2 pi i m / N} of the window length cno_N it was made for, in a buffer of the longest window the entry admits, and its pinned
+     * staging copy; the [B] sample counts on the device and their pinned copy; [B][cno_cap][RD_CNO_JMAX][2] partial and [B][cno_cap][2] band sums, and the pinned copy the
+     * band sums are read back into.  First use; the three sized by windows grow with the call. */
+    float *cno_tw, *cno_tw_host; int cno_N; int *cno_n, *cno_n_host; double *cno_part, *cno_bands, *cno_bands_host; long cno_cap, cno_bands_cap, cno_host_cap;
     int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
     /* receive side */
     rd_rx_stream *rx_st; rd_rx_round *rx_round;
@@ -1280,6 +1284,67 @@ int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const i
     PROF_BEGIN(h, stream);
     if (rd_launch_fm_demod(&a, stream)) return -1;
     PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- C/No of the chirp header: est_CNo.py over every stream (rade_cno.hip; the arithmetic behind the band sums: rade_host.c) ------------------------------ */
+int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, const rade_cno_params *p, double *bands_host, int max_windows,
+                       rade_cno_result *result_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || !p || !result_host || ((uintptr_t)x_dev & 7)) return -1;
+    rade_cno_plan_t q;
+    if (rade_cno_plan(p, &q)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    int max_win = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride || n < q.N) return -1;
+        const int nw = n > q.N ? (n - q.N + RD_CNO_H - 1) / RD_CNO_H : 0;
+        if (nw > max_win) max_win = nw;
+        if (nw) work += 8.0 * (40.0 + 50.0 * 0.225 + 0.225 * q.J) * RD_CNO_H * (nw + q.J - 1) * q.J;
+    }
+    if (bands_host && max_windows < max_win) return -1;
+    if (max_win) {
+        if (!h->cno_n_host && !(h->cno_n_host = pinned_alloc_opt(h, sizeof(int) * B))) return -1;
+        if (!h->cno_tw_host && !(h->cno_tw_host = pinned_alloc_opt(h, sizeof(float) * 2 * RD_CNO_H * RD_CNO_JMAX))) return -1;
+        if (dev_grow(h, &h->cno_tw, NULL, 2L * RD_CNO_H * RD_CNO_JMAX, sizeof(float), 1) || dev_grow(h, &h->cno_n, NULL, B, sizeof(int), 1)) return -1;
+        if (dev_grow(h, &h->cno_part, &h->cno_cap, max_win, sizeof(double) * 2 * RD_CNO_JMAX * B, 1)) return -1;
+        if (dev_grow(h, &h->cno_bands, &h->cno_bands_cap, max_win, sizeof(double) * 2 * B, 1)) return -1;
+        if (!h->cno_bands_host || h->cno_host_cap < max_win) {
+            if (h->cno_bands_host) { if (hipDeviceSynchronize() != hipSuccess) return -1; disown(h, h->cno_bands_host); h->cno_host_cap = 0; }
+            if (!(h->cno_bands_host = pinned_alloc_opt(h, sizeof(double) * 2 * B * max_win))) return -1;
+            h->cno_host_cap = max_win;
+        }
+        if (h->cno_N != q.N) {             /* another window length than the table on the device was made for: re-made, uploaded behind what `stream` holds */
+            h->cno_N = 0;
+            rd_cno_table(q.N, h->cno_tw_host);
+            if (hipMemcpyAsync(h->cno_tw, h->cno_tw_host, sizeof(float) * 2 * q.N, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        }
+        memcpy(h->cno_n_host, n_host, sizeof(int) * B);
+        if (hipMemcpyAsync(h->cno_n, h->cno_n_host, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        rd_cno_args a;
+        memset(&a, 0, sizeof a);
+        a.x = x_dev; a.x_stride = x_stride; a.n = h->cno_n; a.tw = h->cno_tw; a.part = h->cno_part; a.bands = h->cno_bands;
+        a.N = q.N; a.J = q.J; a.B = B; a.max_win = max_win;
+        a.flow_bin = q.flow_bin; a.fhigh_bin = q.fhigh_bin; a.noise_st = q.noise_st; a.noise_en = q.noise_en;
+        a.pitch = rd_cno_pitch(q.J, q.flow_bin, q.fhigh_bin, q.noise_st, q.noise_en);
+        PROF_BEGIN(h, stream);
+        const int e = rd_launch_cno(&a, stream);
+        PROF_END(h, stream, RADE_PROF_CHAN, work);
+        /* the band sums come back and the stream is waited for (also where the launch failed: the staging copies above are then free again) */
+        const int e2 = e ? 0 : hipMemcpyAsync(h->cno_bands_host, h->cno_bands, sizeof(double) * 2 * B * max_win, hipMemcpyDeviceToHost, st) != hipSuccess;
+        if (hipStreamSynchronize(st) != hipSuccess || e || e2) return -1;
+        h->cno_N = q.N;
+    } else if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    for (int b = 0; b < B; b++) {
+        const int nw = n_host[b] > q.N ? (n_host[b] - q.N + RD_CNO_H - 1) / RD_CNO_H : 0;
+        const double *bands = nw ? h->cno_bands_host + (size_t)b * max_win * 2 : NULL;
+        rd_cno_finish(&q, p, bands, nw, &result_host[b]);
+        if (bands_host && nw) memcpy(bands_host + (size_t)b * max_windows * 2, bands, sizeof(double) * 2 * nw);
+    }
     return 0;
 }
 

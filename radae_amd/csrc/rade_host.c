@@ -7,6 +7,7 @@
  *   4. the fractional resampler's Q32.32 time base and its windowed-sinc taps (rade_batch_resample).
  *   5. the rational rate converter's ratio, taps and output count (rade_batch_rate_convert).
  *   6. the analog FM stage's noise level, least-squares filter design and folded de-emphasis (rade_batch_fm_mod / rade_batch_fm_demod).
+ *   7. the C/No estimator's plan, table and host arithmetic, and the chirp header (rade_batch_cno_est, rade_chirp).
  *
  * Reference: radae/radae.py:128-234 (numerology/DFT/pilots/EOO), radae/dsp.py:40-61 (BPF),
  * :153-176 (p_w), :400-416 (Pmat); blob format src/write_rade_weights.c:51-74 and
@@ -807,4 +808,76 @@ int rade_fm_taps(double Fs, double fm_max, double fd, int ntaps, double de_emp_t
         }
     }
     return N2;
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * 7. the C/No estimator of est_CNo.py and the chirp of chirp.py (include/rade_batch.h: rade_batch_cno_est, rade_chirp; rade_cno.hip)
+ * -------------------------------------------------------------------------------------------*/
+/* N, J and the four bin limits with C's truncation toward zero, which is Python's int(); -1 where rade_batch_cno_est refuses */
+int rade_cno_plan(const rade_cno_params *p, rade_cno_plan_t *out)
+{
+    if (!p || !out) return -1;
+    if (!isfinite(p->window_time) || !isfinite(p->flow) || !isfinite(p->fhigh)) return -1;
+    const double nd = 8000.0 * p->window_time;
+    if (!(nd >= 1.0) || nd >= (double)RD_CNO_H * (RD_CNO_JMAX + 1)) return -1;
+    const int N = (int)nd;
+    if (N % RD_CNO_H || N / RD_CNO_H > RD_CNO_JMAX) return -1;
+    const double bph = N / 8000.0, fl = bph * p->flow, fh = bph * p->fhigh;
+    if (!(fl > -1.0) || !(fh > -1.0) || fl > (double)N || fh > (double)N) return -1;        /* (int)fl == 0 for -1 < fl < 0, as int() has it */
+    rade_cno_plan_t q;
+    q.N = N; q.J = N / RD_CNO_H;
+    q.flow_bin = (int)fl; q.fhigh_bin = (int)fh;
+    const int w = (int)(0.1 * q.fhigh_bin);
+    q.noise_st = q.fhigh_bin + w; q.noise_en = q.noise_st + w;
+    q.n_bins = q.fhigh_bin - q.flow_bin + w;
+    if (q.flow_bin >= q.fhigh_bin || w < 1 || q.noise_en > N) return -1;
+    if ((long)q.J * rd_cno_pitch(q.J, q.flow_bin, q.fhigh_bin, q.noise_st, q.noise_en) > RD_CNO_RING_MAX) return -1;
+    *out = q;
+    return 0;
+}
+
+/* t[m] = e^{-2 pi i m / N}, m = 0..N-1: double, rounded once per component */
+void rd_cno_table(int N, float *out /* [N][2] */)
+{
+    for (int m = 0; m < N; m++) {
+        const double a = 2.0 * PI_D * (double)m / (double)N;
+        out[2 * m] = (float)cos(a); out[2 * m + 1] = (float)(-sin(a));
+    }
+}
+
+/* est_CNo.py:44-55 and :71 over the band sums of one stream's windows, in the script's operation order */
+void rd_cno_finish(const rade_cno_plan_t *q, const rade_cno_params *p, const double *bands /* [n_windows][2] */, int n_windows, rade_cno_result *res)
+{
+    const double bins_per_Hz = q->N / 8000.0;
+    const double Nbw = (q->noise_en - q->noise_st) / bins_per_Hz;
+    rade_cno_result r = { n_windows, 0, 0, 0.0, 0.0 };
+    for (int w = 0; w < n_windows; w++) {
+        const double C_plus_N = bands[2 * w], No = bands[2 * w + 1] / Nbw;
+        const double C = C_plus_N - No * (p->fhigh - p->flow);
+        if (C > 0) {
+            const double CdB = 10 * log10(C), NodB = 10 * log10(No);
+            const double CNodB = CdB - NodB;
+            if (CNodB > r.max_CNodB) { r.max_CNodB = CNodB; r.max_st = (long long)w * RD_CNO_H; }
+            r.n_positive++;
+        }
+    }
+    r.max_SNRdB = r.max_CNodB - 10 * log10(3000);
+    *res = r;
+}
+
+/* chirp.py:50-65 */
+int rade_chirp(float *iq_out, int nsam, double flow, double fhigh, double amp)
+{
+    if (!iq_out || nsam < 0 || !isfinite(flow) || !isfinite(fhigh) || !isfinite(amp)) return -1;
+    const double Fs = 8000;
+    double freq = flow, delta_freq = (fhigh - flow) / Fs, phase = 0;
+    for (int n = 0; n < nsam; n++) {
+        phase += 2 * PI_D * freq / Fs;
+        phase -= 2 * PI_D * (int)(phase / (2 * PI_D));
+        freq += delta_freq;
+        if (freq > fhigh) delta_freq = -(fhigh - flow) / Fs;
+        if (freq < flow) delta_freq = (fhigh - flow) / Fs;
+        iq_out[2 * n] = (float)(amp * cos(phase)); iq_out[2 * n + 1] = (float)(amp * sin(phase));
+    }
+    return 0;
 }

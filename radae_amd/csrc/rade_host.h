@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "rade_dev.h"
+#include "rade_batch.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -53,6 +54,9 @@ long rd_pack_weights_f16x2_a16(const float *W, int N, int K, unsigned short *out
 int rd_resample_q(double t0, double ppm, long long *step_q, long long *t0_q);
 /* rade_batch_rate_convert's ratio: L / M reduced by their gcd, T = 32 ceil(M / L) taps per phase; -1: L or M < 1, ceil(M / L) > RD_RATE_KMAX, L T > RD_RATE_TABLE_MAX */
 int rd_rate_reduce(int L, int M, int *Lr, int *Mr, int *T);
+/* rade_batch_cno_est's table t[m] = e^{-2 pi i m / N} ([N][2] floats) and its host arithmetic over one stream's band sums (est_CNo.py:44-55, :71) */
+void rd_cno_table(int N, float *out);
+void rd_cno_finish(const rade_cno_plan_t *q, const rade_cno_params *p, const double *bands, int n_windows, rade_cno_result *res);
 #ifdef __cplusplus
 }
 #endif

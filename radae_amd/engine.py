@@ -59,6 +59,18 @@ class FmDemodParams(C.Structure):
                 ("b2", C.c_void_p), ("N2", C.c_int), ("in_base_host", C.c_void_p), ("n0_host", C.c_void_p), ("bb_out_dev", C.c_void_p), ("bb_stride", C.c_long)]
 
 
+class CnoParams(C.Structure):
+    _fields_ = [("window_time", C.c_double), ("flow", C.c_double), ("fhigh", C.c_double)]
+
+
+class CnoPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("N", "J", "n_bins", "flow_bin", "fhigh_bin", "noise_st", "noise_en")]
+
+
+class CnoResult(C.Structure):
+    _fields_ = [("n_windows", C.c_int), ("n_positive", C.c_int), ("max_st", C.c_longlong), ("max_CNodB", C.c_double), ("max_SNRdB", C.c_double)]
+
+
 class RxStatus(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("consumed", "n_calls", "n_valid", "has_eoo", "nin", "sync", "snr_dB", "state")]
 
@@ -140,6 +152,10 @@ def load_library() -> C.CDLL:
         L.rade_fm_sigma.restype = C.c_double; L.rade_fm_sigma.argtypes = [C.c_double] * 4
         L.rade_fm_deemph_len.argtypes = [C.c_double, C.c_double]
         L.rade_fm_taps.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, vp, vp]
+    if hasattr(L, "rade_batch_cno_est"):
+        L.rade_batch_cno_est.argtypes = [vp, vp, C.c_long, vp, C.POINTER(CnoParams), vp, C.c_int, vp, vp]
+        L.rade_cno_plan.argtypes = [C.POINTER(CnoParams), C.POINTER(CnoPlan)]
+        L.rade_chirp.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
     _lib = L
     return L
 
@@ -164,6 +180,7 @@ EXPORTED_SYMBOLS = [
     "rade_batch_wire_in", "rade_batch_wire_out",
     "rade_batch_rate_convert", "rade_rate_count", "rade_rate_taps",
     "rade_batch_fm_mod", "rade_batch_fm_demod", "rade_fm_sigma", "rade_fm_deemph_len", "rade_fm_taps",
+    "rade_batch_cno_est", "rade_cno_plan", "rade_chirp",
 ]
 WIRE_REAL, WIRE_IQ = 0, 1                                                          # rade_batch_wire_in / _out mode
 
@@ -263,6 +280,31 @@ def fm_pre_emphasis(mod: np.ndarray, Fs: float, tc: float = FM_DE_EMP_TC) -> np.
     y = mod.copy()
     y[..., 1:] -= a * mod[..., :-1]
     return y / y.max(axis=-1, keepdims=True)
+
+
+CNO_FS, CNO_HOP = 8000, 2000                                                       # est_CNo.py:23, :31 (Fs // 4)
+
+
+def cno_plan(window_time: float = 4.0, flow: float = 400.0, fhigh: float = 2000.0) -> CnoPlan:
+    """rade_cno_plan: N, J = N / 2000, the bins of both bands together and the four bin limits of est_CNo.py:25-42 (host only).  Refused: what rade_batch_cno_est refuses."""
+    q = CnoPlan()
+    if load_library().rade_cno_plan(C.byref(CnoParams(float(window_time), float(flow), float(fhigh))), C.byref(q)):
+        raise ValueError(f"rade_cno_plan refuses window_time {window_time!r}, flow {flow!r}, fhigh {fhigh!r} (window_time a multiple of 0.25 s up to 8 s -- the one deviation "
+                         "from est_CNo.py, which takes any; 0 <= flow_bin < fhigh_bin, a noise band of at least one bin that ends inside the window's N bins)")
+    return q
+
+
+def cno_windows(n: int, N: int) -> int:
+    """len(np.arange(0, n - N, 2000)): the windows est_CNo.py evaluates in n samples"""
+    return max(-(-(int(n) - int(N)) // CNO_HOP), 0)
+
+
+def chirp(nsec: float, flow: float = 400.0, fhigh: float = 2000.0, amp: float = 0.25) -> np.ndarray:
+    """rade_chirp: chirp.py:50-65 on the host, int(nsec * 8000) complex64 samples of the triangular flow .. fhigh sweep."""
+    x = np.zeros(int(nsec * CNO_FS), np.complex64)
+    if load_library().rade_chirp(x.ctypes.data, x.size, float(flow), float(fhigh), float(amp)):
+        raise ValueError(f"rade_chirp refuses flow {flow!r}, fhigh {fhigh!r}, amp {amp!r} (finite values)")
+    return x
 
 
 def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
@@ -584,6 +626,30 @@ class BatchEngine:
         if self.lib.rade_batch_rate_convert(self.h, x.data_ptr(), xs, n_in.ctypes.data, fmt, gain, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_rate_convert failed (L, M >= 1 with ceil(M / L) <= 8 and L T <= 16384 after reduction, a finite gain, n0 >= 0, n_out <= the row of out)")
         return out, n_out
+
+    # ---- C/No of the chirp header ---------------------------------------------------------------
+    def cno_est(self, x, n=None, window_time: float = 4.0, flow: float = 400.0, fhigh: float = 2000.0, bands: bool = False):
+        """est_CNo.py over every stream (rade_batch_cno_est).  x: cuda complex64 [B, S] at 8 kHz; n: samples of each stream (a scalar or B values, default S), each at
+        least N = int(8000 window_time).  Returns a list of B CnoResult (n_windows, n_positive, max_st, max_CNodB, max_SNRdB; the script's max_time is max_st / 8000); with
+        bands=True also a float64 array [B, W, 2] of (C + N, band sum of No) per window, W = the most windows any stream has, zeros past a stream's own.  window_time must
+        be a multiple of 0.25 s up to 8 s: the one deviation from the script.  The call synchronises the current stream."""
+        import torch
+        B = self.B
+        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        S = x.shape[1]
+        n = _per_stream(B, S if n is None else n, np.int32, "n")
+        if n.min() < 0 or n.max() > S:
+            raise ValueError(f"n: between 0 and the {S} samples of a row")
+        q = cno_plan(window_time, flow, fhigh)
+        W = max(max(cno_windows(v, q.N) for v in n), 1)
+        bh = np.zeros((B, W, 2), np.float64) if bands else None
+        res = (CnoResult * B)()
+        p = CnoParams(float(window_time), float(flow), float(fhigh))
+        xs = x.stride(0) if B > 1 else S
+        if self.lib.rade_batch_cno_est(self.h, x.data_ptr(), xs, n.ctypes.data, C.byref(p), bh.ctypes.data if bands else None, W, C.byref(res), _stream_ptr()):
+            raise RuntimeError(f"rade_batch_cno_est failed (every stream needs at least N = {q.N} samples)")
+        out = list(res)
+        return (out, bh) if bands else out
 
     # ---- analog FM ----------------------------------------------------------------------------------------------------------
     def fm_mod(self, m, Fs: float, fc: float, fd: float, n=None, real: bool = False, sigma: float = 0.0, seed: int = 0, noise=None, phase0=0, n0=0, out=None,

@@ -1,0 +1,72 @@
+"""The receive side of the reference's stored-file off-air test on the device: what ota_test.sh:136-163 (process_rx) does to a recording between the `sox -r 8k` stage
+(BatchEngine.rate_convert) and the report, for a batch of recordings at once.
+
+    chirp header (4.5 s sent, >= 4 s received) - 1 s silence - x s SSB - 1 s silence - x s RADAE            ota_test.sh:151, :322-379
+
+process_rx estimates the C/No of the chirp header and the time it starts at (est_CNo.py over the first 10 s: BatchEngine.cno_est), trims the recording there, splits what
+follows by the layout above and hands the last part to the receiver.  The SSB part is only located (its bounds are returned): analog_compressor and the speech path of
+the script are outside this project."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import engine as _engine
+
+FS = 8000
+CHIRP_WINDOW_S = 10                   # ota_test.sh:138: `trim 0 10`
+HEADER_S = 4.5                        # ota_test.sh:336
+
+
+def ota_header(amp: float = 0.25) -> np.ndarray:
+    """the 4.5 s, 400-2000 Hz chirp header as ota_test.sh:336 makes it (`chirp.py .. 4.5 --amp AMP`): complex64; the transmitter sends its real part"""
+    return _engine.chirp(HEADER_S, amp=amp)
+
+
+def nearest_sample(seconds: float) -> int:
+    """seconds -> samples at 8 kHz, to the nearest sample, halves upward.  This is the one rounding of process_rx that is NOT pinned against the reference: the script hands
+    `sox trim` a time printed with six decimals, and how sox rounds it to samples could not be checked (no sox where this was written)."""
+    return int(math.floor(seconds * FS + 0.5))
+
+
+def layout(total: int):
+    """ota_test.sh:151-158 for a trimmed recording of `total` samples: x = (duration - 6) / 2 seconds, the SSB part at 5 s for x s, RADAE from 5 + x s.  Returns
+    (ssb_start, ssb_len, radae_start) in samples from the trim point."""
+    x = (total / FS - 6) / 2
+    if x < 0:
+        raise ValueError(f"{total} samples behind the chirp's start: shorter than the 6 s of header and silences")
+    return 5 * FS, nearest_sample(x), nearest_sample(5 + x)
+
+
+@dataclass
+class OtaResult:
+    max_time: np.ndarray              # [B] seconds: the `Measured:` line's Time
+    CNodB: np.ndarray                 # [B] C/No
+    SNR3kdB: np.ndarray               # [B] SNR3k
+    start: np.ndarray                 # [B] sample at which the recording is trimmed (the best window's start)
+    ssb: np.ndarray                   # [B, 2] first and one-past-last sample of the SSB part, in samples of the untrimmed recording
+    radae_start: np.ndarray           # [B] first sample handed to the receiver, in samples of the untrimmed recording
+    n_radae: np.ndarray               # [B] samples handed to the receiver
+    features: object                  # BatchEngine.rx's three results
+    status: list
+    eoo: object
+
+
+def process_rx(engine, x, n=None, window_time: float = 4.0, flow: float = 400.0, fhigh: float = 2000.0) -> OtaResult:
+    """x: cuda complex64 [B, S], a batch of 8 kHz recordings (a real recording as (x, +0), what wire_in and rate_convert deliver); n: samples of each (default S).
+    cno_est over the first min(n, 80000) samples; start = max_st; the layout of ota_test.sh:151-158 behind it (seconds to samples: nearest_sample, not pinned against
+    sox); the trim as rate_convert with L = M = 1 and n0 = start + radae_start (a bit-exact copy); then the receiver.  Synchronises the current stream."""
+    B = engine.B
+    S = x.shape[1]
+    n = _engine._per_stream(B, S if n is None else n, np.int32, "n")
+    res = engine.cno_est(x, n=np.minimum(n, CHIRP_WINDOW_S * FS), window_time=window_time, flow=flow, fhigh=fhigh)
+    start = np.array([r.max_st for r in res], np.int64)
+    lay = [layout(int(n[b] - start[b])) for b in range(B)]
+    ssb = np.array([[start[b] + s0, start[b] + s0 + sl] for b, (s0, sl, _) in enumerate(lay)], np.int64)
+    radae_start = np.array([start[b] + r0 for b, (_, _, r0) in enumerate(lay)], np.int64)
+    n_radae = (n - radae_start).astype(np.int32)
+    y, n_y = engine.rate_convert(x, 1, 1, n_out=n_radae, n_in=n, n0=radae_start)
+    features, status, eoo = engine.rx(y.contiguous(), n_avail=n_y)
+    return OtaResult(start / FS, np.array([r.max_CNodB for r in res]), np.array([r.max_SNRdB for r in res]), start, ssb, radae_start, n_radae, features, status, eoo)
