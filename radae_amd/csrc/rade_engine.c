@@ -8,10 +8,11 @@
  * The receiver runs one workgroup per stream for a whole rade_batch_rx call; the sync state machine consumes the
  * decoder's aux bits (UW errors, radae_rxe.py:220-224, :306-312), so the decoder runs inside that workgroup
  * right before every unique-word decision (k_rx_sync2 -> rx2_decode_pending, rade_rx.hip).
+ *
+ * This file: the engine (struct rade_batch in rade_engine.h: open, close, the owner of all its memory), the profiler, transmit, channel, receive and scoring.  The
+ * front-end stage calls -- the rate-Rs channel, resampler, wire, rate converter, analog FM and C/No -- and all the state they keep live in rade_stages.c.
  */
 #define _GNU_SOURCE          /* sched_getaffinity / CPU_COUNT */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
 
 #include <pthread.h>
 #include <time.h>
@@ -25,6 +26,7 @@
 #include "rade_batch.h"
 #include "rade_api.h"
 #include "rade_host.h"
+#include "rade_engine.h"
 
 #define CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "rade: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); goto fail; } } while (0)
 
@@ -65,77 +67,6 @@ static int sync_blocking_now(void)
     return g_sync_mode == 2 ? rade_sync_policy(__atomic_load_n(&g_engines_open, __ATOMIC_RELAXED) * g_sync_peers, g_sync_quota) : g_sync_mode;
 }
 
-typedef struct { float *wp, *bias; unsigned short *wp16, *wa16; float *wscale, *wscale16; int N, K; } dev_lin;   /* wscale16: column scales when wp16 is one plane of integers */
-
-/* every public entry point runs on its engine's device, whatever device the calling thread had current (one host thread may
- * drive several engines, and an engine may be called from a thread other than the one that opened it) */
-#define ON_DEV(h) do { if (h) (void)hipSetDevice((h)->device); } while (0)
-
-#define RADE_PROF_MAXEV 256   /* launches recorded per profiled interval before the events are drained */
-#define RADE_PROF_MAXIV 4096  /* launch intervals kept per profiling session (rade_batch_profile_intervals) */
-#define RD_WIRE_SLOTS 8
-struct rade_batch {
-    struct owned *owned;                  /* every device / pinned allocation of the engine (own): rade_batch_close frees exactly these */
-    int alloc_failed;                     /* sticky: an allocation the engine cannot do without failed (rade_batch_open_mem checks it) */
-    int B, max_tx_mf, device, flags, trace_cap, Tcap;
-    int R, dec_rows;                      /* do_radae_rx calls per stream per sync launch; 3R decoder slots */
-    int unsync_off_after;                 /* int(disable_unsync * Fs / Nmf) or -1 */
-    unsigned short *corrq16, *corra16, *wfwd16, *bpf16; double *vm; int rx_lds, rx_census;   /* dynamic LDS of a receiver launch; phase mask of the -DRX2_CENSUS developer build */
-    int feat_in, enc_kpad, bottleneck1;   /* 84 (model19: 4x21) or 80 (model05/bbfm: 4x20); tanh on z when bottleneck 1 */
-    float *dec2_x, *dec2_gi, *dec2_hbuf, *dec2_h[5];   /* stand-alone decoder (rade_batch_decode) */
-    rd_tables *d_tab;
-    /* weights */
-    dev_lin enc_dense1, enc_zdense, dec_dense1, dec_output, enc_gin[5], dec_gin[5], enc_conv[5], dec_conv[5], dec_glu[5];
-    float *enc_whh[5], *enc_bhh[5], *dec_whh[5], *dec_bhh[5];
-    unsigned short *dec_whq[5]; float *dec_whs[5];      /* decoder W_hh as matrix-core fragments (int8-exact) + row scales; NULL when the blob's recurrent weights are not int8 x scale */
-    /* transmit side */
-    float *enc_xin, *enc_x, *enc_gi, *enc_h[5], *enc_z, *eoo, *eoo_bits;
-    unsigned short *enc_xf; int enc_nq, enc_seq_taps, enc_no_pair;
-    int enc_hist_frag;                   /* the history tile of enc_xf holds what enc_x's two float32 history rows hold (set by a fragment pass, cleared by a reset or a float32-row pass) */   /* the concat buffer as matrix-core operand fragments (rade_enc.hip: [B][enc_nq][RD_EF_TILE] binary16), engines with enough rows for the batched GEMMs only */
-    /* optional Tx band-pass filter + clip (RADE_BATCH_TX_BPF; radae_txe.py:74-83): filter state per stream, its initial value, the modulator's raw output, block phases */
-    int bypass_dec;                          /* RADE_BATCH_BYPASS_DEC */
-    int tx_linear;                           /* RADE_BATCH_TX_LINEAR */
-    double *irx_part; long irx_part_cap; float *irx_foff; long long *irx_err;   /* rade_batch_rx_ideal: per-frame pilot power [B][cap], offsets [2][B], error counts [B] */
-    rd_bpf_state *tx_bpf, *tx_bpf_init; void *tx_raw; float *tx_chain; float *eoo_filt;   /* eoo_filt [B][Neoo] c64: the end-of-over frame as transmitted (filtered + clipped) for the channel's with_eoo */
-    void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
-    float *chan_ps, *chan_ps_host;            /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */
-    float *rs_sigma; double *rs_part, *rs_stats;   /* rade_batch_channel_rs_pa: [B] per-stream sigma, [B][RD_RS_NCH][4] measurement partials, [B][3] measurements, allocated on first use */
-    float *clk_taps; rd_clk_stream *clk_ps, *clk_ps_host;   /* rade_batch_resample: the taps [257][32]; [B] per-stream records on the device and their pinned staging copy, allocated on first use */
-    /* rade_batch_wire_in / _out: the [B] sample counts of the last RD_WIRE_SLOTS calls on the device and their pinned staging copies, one slot per call in turn (a call
-     * does not wait for its stream: it waits for the call that used its slot RD_WIRE_SLOTS calls ago); [B][RD_WIRE_NCH_MAX][4] meter partials, [B][4] meters.  First use. */
-    int *wire_n, *wire_n_host; hipEvent_t wire_ev[RD_WIRE_SLOTS]; unsigned wire_used, wire_seq; double *wire_part, *wire_meters;
-    /* rade_batch_rate_convert: the [L][T] table of the reduced ratio (rate_L, rate_M) it was made for, in a buffer of the largest table the entry admits, and its pinned
-     * staging copy; [B] per-stream records on the device and their pinned staging copy.  First use. */
-    float *rate_taps, *rate_taps_host; int rate_L, rate_M; rd_rate_stream *rate_ps, *rate_ps_host;
-    /* rade_batch_fm_mod: [B] per-stream records on the device and their pinned staging copy; [B][fm_tsum_cap / B] tile sums; [B] final phases and their pinned copy.
-     * rade_batch_fm_demod: its [B] records likewise; the two tap tables [2][RD_FM_NMAX] on the device, their pinned staging copy, and the bytes they were made from
-     * (fm_taps_last with fm_N1, fm_N2: uploaded again only when a call brings other bytes).  First use. */
-    rd_fm_stream *fm_ps, *fm_ps_host; unsigned *fm_tsum; long fm_tsum_cap; unsigned *fm_ph_end, *fm_ph_end_host;
-    rd_fm_dstream *fm_dps, *fm_dps_host; float *fm_taps, *fm_taps_host, *fm_taps_last; int fm_N1, fm_N2;
-    /* rade_batch_cno_est: the table e^{-2 pi i m / N} of the window length cno_N it was made for, in a buffer of the longest window the entry admits, and its pinned
-     * staging copy; the [B] sample counts on the device and their pinned copy; [B][cno_cap][RD_CNO_JMAX][2] partial and [B][cno_cap][2] band sums, and the pinned copy the
-     * band sums are read back into.  First use; the three sized by windows grow with the call. */
-    float *cno_tw, *cno_tw_host; int cno_N; int *cno_n, *cno_n_host; double *cno_part, *cno_bands, *cno_bands_host; long cno_cap, cno_bands_cap, cno_host_cap;
-    int *loss_len; double *loss_res, *loss_part; long loss_part_cap;   /* rade_batch_loss: [2][B] n_in, n_hat; [B] losses + [B] starts; [B][cap] block partials (doubles, then ints) */
-    /* receive side */
-    rd_rx_stream *rx_st; rd_rx_round *rx_round;
-    int *rx_avail, *rx_acc, *rx_progress, *rx_status;
-    float *zrows, *dec_x, *dec_gi, *dec_hbuf, *dec_h[5], *feat84, *dtcache;
-    void *rx_filt; float *bpf_chain; long filt_cap, chain_stride;   /* band-pass pre-pass of an invocation: filtered samples [B][filt_cap] c64 and block phases [B][chain_stride] c64, grown on demand */
-    rd_rx_trace *trace; float *trace_z;
-    long long *wg_cycles;            /* [B] per-stream cycles of the last receiver launch */
-    int *h_small;                    /* pinned host scratch */
-    unsigned *lcg_seeds;             /* host copy for resets */
-    unsigned *d_lcg_seeds;
-    /* optional per-kernel-class timing with HIP events (bench.py roofline leg; never on in timed runs) */
-    int prof_on, prof_cnt; hipEvent_t prof_ev[2 * RADE_PROF_MAXEV]; int prof_cls[RADE_PROF_MAXEV]; double prof_fl[RADE_PROF_MAXEV];
-    double prof_ms[RADE_PROF_NCLASS], prof_flops[RADE_PROF_NCLASS]; long prof_n[RADE_PROF_NCLASS];
-    /* optional: absolute start / end of every profiled launch relative to a caller-supplied event (launches of several engines on one time axis) */
-    hipEvent_t prof_ref; int iv_n; int iv_cls[RADE_PROF_MAXIV]; float iv_t0[RADE_PROF_MAXIV], iv_t1[RADE_PROF_MAXIV];
-    hipEvent_t ev_block;             /* the event rade_batch_rx sleeps on (sleep_until_event) when the host has fewer CPUs than engines (sync_blocking_now) */
-    long n_sync_block, n_sync_spin;  /* waits of either kind so far (rade_batch_sync_counts) */
-    double wait_est_us;              /* how long the sleeping wait of rade_batch_rx lasted lately (running average): the next one sleeps through most of that before it polls */
-};
 
 static const int ENC_IN[5] = { 64, 224, 384, 544, 704 };    /* GRU input widths (radae_base.py:240-248) */
 static const int ENC_DIL[5] = { 1, 2, 2, 2, 2 };
@@ -152,7 +83,7 @@ static void *own(rade_batch *h, void *p, int pinned)
     if (o) { o->next = h->owned; o->p = p; o->pinned = pinned; h->owned = o; }
     return p;
 }
-static void disown(rade_batch *h, void *p)       /* release one recorded allocation */
+void disown(rade_batch *h, void *p)       /* release one recorded allocation */
 {
     for (struct owned **q = &h->owned; *q; q = &(*q)->next)
         if ((*q)->p == p) { struct owned *o = *q; *q = o->next; if (o->pinned) hipHostFree(p); else hipFree(p); free(o); return; }
@@ -167,13 +98,13 @@ static void *dev_alloc_opt(rade_batch *h, size_t bytes, int zero)
     if (zero && (hipMemset(d, 0, bytes) != hipSuccess || hipStreamSynchronize(NULL) != hipSuccess)) { hipFree(d); return NULL; }
     return own(h, d, 0);
 }
-static void *dev_upload_opt(rade_batch *h, const void *src, size_t bytes)
+void *dev_upload_opt(rade_batch *h, const void *src, size_t bytes)
 {
     void *d = dev_alloc_opt(h, bytes, 0);
     if (d && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { disown(h, d); return NULL; }
     return d;
 }
-static void *pinned_alloc_opt(rade_batch *h, size_t bytes) { void *p = NULL; return hipHostMalloc(&p, bytes, 0) == hipSuccess ? own(h, p, 1) : NULL; }
+void *pinned_alloc_opt(rade_batch *h, size_t bytes) { void *p = NULL; return hipHostMalloc(&p, bytes, 0) == hipSuccess ? own(h, p, 1) : NULL; }
 static void *must(rade_batch *h, void *p) { if (!p) h->alloc_failed = 1; return p; }      /* the open's: what the engine cannot do without */
 static void *dev_upload(rade_batch *h, const void *src, size_t bytes) { return must(h, dev_upload_opt(h, src, bytes)); }
 static void *dev_zeros(rade_batch *h, size_t bytes) { return must(h, dev_alloc_opt(h, bytes, 1)); }
@@ -181,7 +112,7 @@ static void *dev_zeros(rade_batch *h, size_t bytes) { return must(h, dev_alloc_o
 /* Scratch that follows the largest call seen: the pointer at ptr_addr (of any object type) holds `need` elements of elem_bytes afterwards (*cap = need; cap = NULL:
  * a fixed size, allocated on first use).  A buffer it replaces is released only once the device is idle: queued work may still read it.  zeroed = 0: left as allocated,
  * for buffers whose every entry is written on the caller's stream before it is read (the receiver's pre-pass): a memset on the null stream could land on top of that. */
-static int dev_grow(rade_batch *h, void *ptr_addr, long *cap, long need, size_t elem_bytes, int zeroed)
+int dev_grow(rade_batch *h, void *ptr_addr, long *cap, long need, size_t elem_bytes, int zeroed)
 {
     void *p;
     memcpy(&p, ptr_addr, sizeof p);
@@ -463,7 +394,7 @@ void rade_batch_close(rade_batch *h)
     ON_DEV(h);
     while (h->owned) disown(h, h->owned->p);
     if (h->ev_block) hipEventDestroy(h->ev_block);
-    for (int i = 0; i < RD_WIRE_SLOTS; i++) if (h->wire_ev[i]) hipEventDestroy(h->wire_ev[i]);
+    if (h->stages) rd_stages_free(h->stages);
     __atomic_sub_fetch(&g_engines_open, 1, __ATOMIC_RELAXED);
     for (int i = 0; i < 2 * RADE_PROF_MAXEV; i++) if (h->prof_ev[i]) hipEventDestroy(h->prof_ev[i]);
     free(h->lcg_seeds);
@@ -477,7 +408,7 @@ int rd_batch_has_tx_bpf(const rade_batch *h) { return h->tx_bpf != NULL; }
 /* ---- per-kernel-class timing (HIP events on the launch stream) -------------------------------- */
 /* Events are only recorded while the work is queued and read back afterwards (prof_drain): a profiled step runs back to
  * back like a timed one, without a host synchronisation (and the clock ramp-down that follows it) after every kernel. */
-static void prof_drain(rade_batch *h)
+void prof_drain(rade_batch *h)
 {
     for (int i = 0; i < h->prof_cnt; i++) {
         float ms = 0;
@@ -491,9 +422,6 @@ static void prof_drain(rade_batch *h)
     }
     h->prof_cnt = 0;
 }
-#define PROF_BEGIN(h, st) do { if ((h)->prof_on) { if ((h)->prof_cnt >= RADE_PROF_MAXEV) prof_drain(h); hipEventRecord((h)->prof_ev[2 * (h)->prof_cnt], (hipStream_t)(st)); } } while (0)
-#define PROF_END(h, st, cls, fl) do { if ((h)->prof_on) { hipEventRecord((h)->prof_ev[2 * (h)->prof_cnt + 1], (hipStream_t)(st)); \
-    (h)->prof_cls[(h)->prof_cnt] = (cls); (h)->prof_fl[(h)->prof_cnt] = (fl); (h)->prof_cnt++; } } while (0)
 
 void rade_batch_profile(rade_batch *h, int enable)
 {
@@ -717,15 +645,30 @@ float rade_sigma_from_EbNodB_rs3(float EbNodB)
     return ((float)RD_M / powf(2.0f * 20.0f * EbNo, 0.5f)) / powf(2.0f, 0.5f);
 }
 
-/* `rows` arrays of B 4-byte values (row r: src[r], or fill[r] where that is NULL, 0 without fill) through pinned `stage` to `dev`; wait = 0: the caller synchronises before it reuses `stage` */
-static int stage_rows(rade_batch *h, void *stage, void *dev, int rows, const void *const *src, const float *fill, int wait, hipStream_t st)
+/* `rows` arrays of B 4-byte values (row r: src[r], or fill[r] where that is NULL, 0 without fill) to `dev` through their pinned staging copy *stage ([rows][B], allocated
+ * on first use); wait = 0: the caller synchronises before it returns, since the next call refills the staging copy */
+static int stage_rows(rade_batch *h, void **stage, void *dev, int rows, const void *const *src, const float *fill, int wait, hipStream_t st)
 {
-    float *f = stage;
+    if (!*stage && !(*stage = pinned_alloc_opt(h, sizeof(float) * rows * h->B))) return -1;
+    float *f = *stage;
     for (int r = 0; r < rows; r++, f += h->B)
         if (src[r]) memcpy(f, src[r], sizeof(float) * h->B);
         else for (int b = 0; b < h->B; b++) f[b] = fill ? fill[r] : 0.0f;
-    if (hipMemcpyAsync(dev, stage, sizeof(float) * rows * h->B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    if (hipMemcpyAsync(dev, *stage, sizeof(float) * rows * h->B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     return wait && hipStreamSynchronize(st) != hipSuccess ? -1 : 0;
+}
+
+/* Results on their way to the caller: `bytes` at `dev` into the engine's pinned landing area, and the stream waited for.  One area serves every call that reads
+ * results back (it grows to the largest seen): each of them has waited by the time it returns, so the area is free whenever the next one starts. */
+const void *read_back(rade_batch *h, const void *dev, size_t bytes, hipStream_t st)
+{
+    if (bytes > h->rb_cap) {
+        if (h->rb_host) disown(h, h->rb_host);
+        h->rb_cap = (h->rb_host = pinned_alloc_opt(h, bytes)) ? bytes : 0;
+        if (!h->rb_host) return NULL;
+    }
+    if (hipMemcpyAsync(h->rb_host, dev, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return NULL;
+    return h->rb_host;
 }
 
 /* the [3][B] per-stream sigma, freq_offset, df_dt of a call on the device (rd_chan_args.ps), a NULL member filled with p's scalar; *out = NULL when ps gives none */
@@ -734,10 +677,9 @@ static int chan_streams_upload(rade_batch *h, const rade_channel_params *p, cons
     *out = NULL;
     if (!ps || (!ps->sigma && !ps->freq_offset && !ps->df_dt)) return 0;
     if (dev_grow(h, &h->chan_ps, NULL, 3 * h->B, sizeof(float), 1)) return -1;
-    if (!h->chan_ps_host && !(h->chan_ps_host = pinned_alloc_opt(h, sizeof(float) * 3 * h->B))) return -1;
     const void *src[3] = { ps->sigma, ps->freq_offset, ps->df_dt };
     const float fill[3] = { p->sigma, p->freq_offset, p->df_dt };
-    if (stage_rows(h, h->chan_ps_host, h->chan_ps, 3, src, fill, 1, (hipStream_t)stream)) return -1;
+    if (stage_rows(h, &h->chan_ps_host, h->chan_ps, 3, src, fill, 1, (hipStream_t)stream)) return -1;
     *out = h->chan_ps;
     return 0;
 }
@@ -914,7 +856,7 @@ int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n
     if (dev_grow(h, &h->irx_part, &h->irx_part_cap, n_mf, sizeof(double) * B, 1) || dev_grow(h, &h->irx_foff, NULL, 2 * B, sizeof(float), 1) || dev_grow(h, &h->irx_err, NULL, B, sizeof(long long), 1)) return -1;
     if (p->freq_offset_host) {
         const void *src[2] = { p->freq_offset_host, p->df_dt_host };
-        if (stage_rows(h, h->h_small, h->irx_foff, 2, src, NULL, 1, st)) return -1;      /* h_small: pinned scratch, >= 8 B ints */
+        if (stage_rows(h, &h->irx_foff_host, h->irx_foff, 2, src, NULL, 1, st)) return -1;
     }
     rd_irx_args a;
     memset(&a, 0, sizeof a);
@@ -924,8 +866,8 @@ int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n
     a.z_hat = z_hat_dev; a.part = h->irx_part; a.z_ref = p->z_ref_dev; a.n_err = p->z_ref_dev ? h->irx_err : NULL;
     if (rd_launch_irx(&a, stream)) return -1;
     if (p->n_errors_host) {
-        long long *e = (long long *)h->h_small;
-        if (hipMemcpyAsync(e, h->irx_err, sizeof(long long) * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        const long long *e = read_back(h, h->irx_err, sizeof(long long) * B, st);
+        if (!e) return -1;
         for (int b = 0; b < B; b++) p->n_errors_host[b] = (long)e[b];
     }
     if (features_out_dev && rade_batch_decode(h, z_hat_dev, 3 * n_mf, features_out_dev, 1, stream) != 3 * n_mf) return -1;
@@ -953,10 +895,8 @@ int rade_batch_loss(rade_batch *h, const float *features_dev, long f_stride, int
     }
     if (dev_grow(h, &h->loss_len, NULL, 2 * B, sizeof(int), 1) || dev_grow(h, &h->loss_res, NULL, B, sizeof(double) + sizeof(int), 1)) return -1;
     if (n_blk > h->loss_part_cap && dev_grow(h, &h->loss_part, &h->loss_part_cap, n_blk, (sizeof(double) + sizeof(int)) * B, 1)) return -1;
-    /* pinned scratch (8 + 8 B ints): the lengths [2][B] ints, then the results [B] doubles + [B] ints; the call synchronises before it returns */
-    double *res = (double *)(h->h_small + 2 * B);
-    const void *len[2] = { n_in_host, n_hat_host };
-    if (stage_rows(h, h->h_small, h->loss_len, 2, len, NULL, 0, st)) return -1;
+    const void *len[2] = { n_in_host, n_hat_host };        /* not waited for here: the results are read back below */
+    if (stage_rows(h, &h->loss_len_host, h->loss_len, 2, len, NULL, 0, st)) return -1;
     rd_loss_args a;
     memset(&a, 0, sizeof a);
     a.feat = features_dev; a.f_stride = f_stride; a.f_row = f_row; a.hat = hat_dev; a.h_stride = h_stride; a.h_row = h_row; a.len = h->loss_len;
@@ -964,7 +904,8 @@ int rade_batch_loss(rade_batch *h, const float *features_dev, long f_stride, int
     a.loss = h->loss_res; a.start = (int *)(h->loss_res + B);
     a.frame_loss = frame_loss_dev; a.fl_stride = fl_stride; a.max_hat = max_hat; a.B = B;
     if (rd_launch_loss(&a, stream)) return -1;
-    if (hipMemcpyAsync(res, h->loss_res, (sizeof(double) + sizeof(int)) * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+    const double *res = read_back(h, h->loss_res, (sizeof(double) + sizeof(int)) * B, st);      /* [B] doubles, then [B] ints */
+    if (!res) return -1;
     const int *rs = (const int *)(res + B);
     for (int b = 0; b < B; b++) { loss_host[b] = res[b]; start_host[b] = rs[b]; }
     return n_scored;
@@ -976,376 +917,6 @@ int rade_batch_channel_symbol(rade_batch *h, const float *z_dev, const float *H_
     ON_DEV(h);
     if (!h || n_steps <= 0 || (mode != 0 && mode != 1)) return -1;
     return rd_launch_chan_symbol(z_dev, H_dev, noise_dev, z_hat_dev, (long)h->B * n_steps * RD_LATENT, mode, p0, p1, seed, stream) ? -1 : n_steps;
-}
-
-/* ---- the rate-Rs channel of the bottleneck-3 model (radae.py:603-634; rade_rs.hip) ------------------------------------------------------------ */
-int rade_batch_channel_rs_pa(rade_batch *h, const float *z_dev, const float *H_dev, const void *noise_dev, float *z_hat_dev, int n_steps, float sigma,
-                             const float *sigma_streams_host, float phase_offset, unsigned long long seed, double *stats_host, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !z_dev || !z_hat_dev || n_steps <= 0) return -1;
-    if (((uintptr_t)z_dev | (uintptr_t)H_dev | (uintptr_t)z_hat_dev) & 3 || ((uintptr_t)noise_dev & 7)) return -1;   /* element alignment is all the kernel needs */
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    if (dev_grow(h, &h->rs_part, NULL, (long)B * RD_RS_NCH * 4, sizeof(double), 1) || dev_grow(h, &h->rs_stats, NULL, 3L * B, sizeof(double), 1)) return -1;
-    if (sigma_streams_host) {              /* pinned scratch (8 + 8 B ints): the [B] sigmas, behind them the [B][3] measurements on the way back */
-        const void *src[1] = { sigma_streams_host };
-        if (dev_grow(h, &h->rs_sigma, NULL, B, sizeof(float), 1) || stage_rows(h, h->h_small, h->rs_sigma, 1, src, NULL, 1, st)) return -1;
-    }
-    rd_rs_args a;
-    memset(&a, 0, sizeof a);
-    a.tab = h->d_tab; a.z = z_dev; a.H = H_dev; a.noise = noise_dev; a.z_hat = z_hat_dev; a.B = B; a.n_steps = n_steps;
-    a.sigma = sigma; a.sigma_b = sigma_streams_host ? h->rs_sigma : NULL; a.seed = seed;
-    a.has_phase = phase_offset != 0.0f; a.ph_re = cosf(phase_offset); a.ph_im = sinf(phase_offset);      /* radae.py:616-619 */
-    a.part = h->rs_part; a.stats = stats_host ? h->rs_stats : NULL;
-    PROF_BEGIN(h, stream);
-    if (rd_launch_rs_pa(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, 8.0 * B * 2.0 * n_steps * 2 * 20 * RD_M);
-    if (stats_host) {
-        double *res = (double *)(h->h_small + 2 * B);
-        if (hipMemcpyAsync(res, h->rs_stats, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-        memcpy(stats_host, res, sizeof(double) * 3 * B);
-    }
-    return n_steps;
-}
-
-/* ---- sample-clock offset: the fractional resampler (rade_clk.hip) ------------------------------------------------------------------------------ */
-int rade_batch_resample(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
-                        const rade_resample_params *p, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p) return -1;
-    if (((uintptr_t)x_dev | (uintptr_t)y_dev) & 7) return -1;
-    if (p->mode != RADE_RESAMPLE_SINC32 && p->mode != RADE_RESAMPLE_LINEAR) return -1;
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->clk_ps_host && !(h->clk_ps_host = pinned_alloc_opt(h, sizeof(rd_clk_stream) * B))) return -1;
-    int max_out = 0;
-    double work = 0.0;
-    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
-        rd_clk_stream *r = &h->clk_ps_host[b];
-        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
-        r->n0 = p->n0_host ? p->n0_host[b] : 0; r->in_base = p->in_base_host ? p->in_base_host[b] : 0;
-        if (r->n_in < 0 || r->n_out < 0 || r->n_in > x_stride || r->n_out > y_stride || r->n0 < 0) return -1;
-        if (r->in_base > (1LL << 62) || r->in_base < -(1LL << 62)) return -1;
-        if (rd_resample_q(p->t0_host ? p->t0_host[b] : 0.0, p->ppm_host ? p->ppm_host[b] : p->ppm, &r->step_q, &r->t0_q)) return -1;
-        if (((__int128)r->n0 + r->n_out) * r->step_q > ((__int128)1 << 62)) return -1;
-        if (r->n_out > max_out) max_out = r->n_out;
-        work += (p->mode == RADE_RESAMPLE_SINC32 ? 4.0 * 2 * RD_CLK_TAPS : 6.0) * r->n_out;
-    }
-    if (!max_out) return 0;
-    if (!h->clk_taps) {
-        float *t = malloc(sizeof(float) * (RD_CLK_PHASES + 1) * RD_CLK_TAPS);
-        if (t) { rade_resample_taps(t); h->clk_taps = dev_upload_opt(h, t, sizeof(float) * (RD_CLK_PHASES + 1) * RD_CLK_TAPS); }
-        free(t);
-        if (!h->clk_taps) return -1;
-    }
-    if (dev_grow(h, &h->clk_ps, NULL, B, sizeof(rd_clk_stream), 1)) return -1;
-    /* the one small copy ahead of the launch; waited for, since the next call refills the staging records */
-    if (hipMemcpyAsync(h->clk_ps, h->clk_ps_host, sizeof(rd_clk_stream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-    rd_clk_args a;
-    memset(&a, 0, sizeof a);
-    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.ps = h->clk_ps; a.taps = h->clk_taps; a.mode = p->mode; a.B = B; a.max_out = max_out;
-    PROF_BEGIN(h, stream);
-    if (rd_launch_clk_resample(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, work);
-    return 0;
-}
-
-/* ---- the sound-card wire: int16 <-> complex64 (rade_wire.hip) ---------------------------------------------------------------------------------- */
-/* Checks every stream, then puts the counts on the device in the call's slot and fills the launch record; 1 = nothing to do (no stream has a sample), -1 = refused */
-static int wire_prepare(rade_batch *h, const void *i16, long i16_stride, const void *c64, long c64_stride, const int *n_host, int mode, float k, rd_wire_args *a, int *slot, hipStream_t st)
-{
-    if (!h || !i16 || !c64 || !n_host) return -1;
-    if (((uintptr_t)i16 & 1) || ((uintptr_t)c64 & 7)) return -1;
-    if ((mode != RADE_WIRE_REAL && mode != RADE_WIRE_IQ) || !isfinite(k)) return -1;
-    const int B = h->B;
-    int max_n = 0;
-    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
-        const int n = n_host[b];
-        if (n < 0 || n > c64_stride || (long)n << mode > i16_stride) return -1;
-        if (n > max_n) max_n = n;
-    }
-    if (!h->wire_n_host && !(h->wire_n_host = pinned_alloc_opt(h, sizeof(int) * RD_WIRE_SLOTS * B))) return -1;
-    if (dev_grow(h, &h->wire_n, NULL, (long)RD_WIRE_SLOTS * B, sizeof(int), 1)) return -1;
-    const int s = (int)(h->wire_seq++ % RD_WIRE_SLOTS);
-    if (!h->wire_ev[s] && hipEventCreateWithFlags(&h->wire_ev[s], hipEventDisableTiming) != hipSuccess) { h->wire_ev[s] = NULL; return -1; }
-    if ((h->wire_used >> s & 1) && hipEventSynchronize(h->wire_ev[s]) != hipSuccess) return -1;     /* the slot's previous call has read its counts */
-    h->wire_used &= ~(1u << s);
-    memcpy(h->wire_n_host + (size_t)s * B, n_host, sizeof(int) * B);
-    if (hipMemcpyAsync(h->wire_n + (size_t)s * B, h->wire_n_host + (size_t)s * B, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    memset(a, 0, sizeof *a);
-    a->i16 = (void *)i16; a->i16_stride = i16_stride; a->c64 = (void *)c64; a->c64_stride = c64_stride; a->n = h->wire_n + (size_t)s * B;
-    a->mode = mode; a->B = B; a->k = k;
-    a->n_ch = 4096 / B < 4 ? 4 : 4096 / B > RD_WIRE_NCH_MAX ? RD_WIRE_NCH_MAX : 4096 / B;      /* a function of B alone: a stream's meter sums do not depend on the other streams */
-    *slot = s;
-    return max_n ? 0 : 1;
-}
-/* the slot is busy until what was queued on st up to here has run */
-static int wire_done(rade_batch *h, int slot, hipStream_t st)
-{
-    if (hipEventRecord(h->wire_ev[slot], st) != hipSuccess) return -1;
-    h->wire_used |= 1u << slot;
-    return 0;
-}
-
-int rade_batch_wire_in(rade_batch *h, const void *in_dev, long in_stride, const int *n_host, int mode, float gain, void *out_dev, long out_stride, void *stream)
-{
-    ON_DEV(h);
-    hipStream_t st = (hipStream_t)stream;
-    rd_wire_args a; int slot;
-    const int r = wire_prepare(h, in_dev, in_stride, out_dev, out_stride, n_host, mode, gain, &a, &slot, st);
-    if (r < 0) return -1;
-    if (r == 0) {
-        PROF_BEGIN(h, stream);
-        if (rd_launch_wire_in(&a, stream)) return -1;
-        PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
-    }
-    return wire_done(h, slot, st);
-}
-
-int rade_batch_wire_out(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int mode, float scale, void *out_dev, long out_stride, double *meters_host, void *stream)
-{
-    ON_DEV(h);
-    hipStream_t st = (hipStream_t)stream;
-    rd_wire_args a; int slot;
-    const int r = wire_prepare(h, out_dev, out_stride, x_dev, x_stride, n_host, mode, scale, &a, &slot, st);
-    if (r < 0) return -1;
-    const int B = h->B;
-    if (meters_host) {
-        if (dev_grow(h, &h->wire_part, NULL, (long)B * RD_WIRE_NCH_MAX * 4, sizeof(double), 1) || dev_grow(h, &h->wire_meters, NULL, 4L * B, sizeof(double), 1)) return -1;
-        a.part = h->wire_part; a.meters = h->wire_meters;
-    }
-    if (r == 0) {
-        PROF_BEGIN(h, stream);
-        if (rd_launch_wire_out(&a, stream)) return -1;
-        PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
-    }
-    if (wire_done(h, slot, st)) return -1;
-    if (meters_host) {
-        if (r) { memset(meters_host, 0, sizeof(double) * 4 * B); return 0; }     /* no stream has a sample: nothing was launched */
-        if (hipMemcpyAsync(meters_host, h->wire_meters, sizeof(double) * 4 * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-    }
-    return 0;
-}
-
-/* ---- the rational rate converter: 48 / 44.1 kHz <-> 8 kHz (rade_rate.hip) ------------------------------------------------------------------------------ */
-int rade_batch_rate_convert(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, int format, float gain, void *y_dev, long y_stride,
-                            const int *n_out_host, const rade_rate_params *p, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p) return -1;
-    if (format != RADE_RATE_C64 && format != RADE_RATE_S16_REAL && format != RADE_RATE_S16_IQ) return -1;
-    if (((uintptr_t)x_dev & (format == RADE_RATE_C64 ? 7 : 1)) || ((uintptr_t)y_dev & 7)) return -1;
-    if (format != RADE_RATE_C64 && !isfinite(gain)) return -1;
-    int L, M, T;
-    if (rd_rate_reduce(p->L, p->M, &L, &M, &T)) return -1;
-    const int B = h->B, per = format == RADE_RATE_S16_IQ ? 2 : 1;         /* elements of x per sample */
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->rate_ps_host && !(h->rate_ps_host = pinned_alloc_opt(h, sizeof(rd_rate_stream) * B))) return -1;
-    int max_out = 0;
-    double work = 0.0;
-    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
-        rd_rate_stream *r = &h->rate_ps_host[b];
-        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
-        r->n0 = p->n0_host ? p->n0_host[b] : 0; r->in_base = p->in_base_host ? p->in_base_host[b] : 0;
-        if (r->n_in < 0 || r->n_out < 0 || (long)r->n_in * per > x_stride || r->n_out > y_stride || r->n0 < 0) return -1;
-        if (r->in_base > (1LL << 62) || r->in_base < -(1LL << 62)) return -1;
-        if (((__int128)r->n0 + r->n_out) * M > ((__int128)1 << 62)) return -1;
-        if (r->n_out > max_out) max_out = r->n_out;
-        work += (format == RADE_RATE_S16_REAL ? 2.0 : 4.0) * T * r->n_out;
-    }
-    if (!max_out) return 0;
-    if (!h->rate_taps_host && !(h->rate_taps_host = pinned_alloc_opt(h, sizeof(float) * RD_RATE_TABLE_MAX))) return -1;
-    if (dev_grow(h, &h->rate_taps, NULL, RD_RATE_TABLE_MAX, sizeof(float), 1) || dev_grow(h, &h->rate_ps, NULL, B, sizeof(rd_rate_stream), 1)) return -1;
-    if (h->rate_L != L || h->rate_M != M) {                /* another ratio than the table on the device was made for: re-made, uploaded behind what `stream` holds */
-        h->rate_L = h->rate_M = 0;
-        if (rade_rate_taps(L, M, h->rate_taps_host) != T) return -1;
-        if (hipMemcpyAsync(h->rate_taps, h->rate_taps_host, sizeof(float) * L * T, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    }
-    /* the one small copy ahead of the launch; waited for, since the next call refills the staging records (and may refill the staging table) */
-    if (hipMemcpyAsync(h->rate_ps, h->rate_ps_host, sizeof(rd_rate_stream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-    h->rate_L = L; h->rate_M = M;
-    rd_rate_args a;
-    memset(&a, 0, sizeof a);
-    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.ps = h->rate_ps; a.taps = h->rate_taps;
-    a.L = L; a.M = M; a.T = T; a.tile = rd_rate_tile(L, M, T); a.fmt = format; a.B = B; a.max_out = max_out; a.gain = gain;
-    PROF_BEGIN(h, stream);
-    if (rd_launch_rate_convert(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, work);
-    return 0;
-}
-
-/* ---- the analog FM modulator and demodulator (rade_fm.hip) -------------------------------------------------------------------------------------------------- */
-static int fm_rates_ok(double Fs, double fc, double fd)
-{
-    return isfinite(Fs) && isfinite(fc) && isfinite(fd) && Fs > 0.0 && fabs(fc) <= Fs / 2.0 && fd > 0.0 && fd <= Fs / 2.0;
-}
-
-int rade_batch_fm_mod(rade_batch *h, const void *m_dev, long m_stride, const int *n_host, void *y_dev, long y_stride, const rade_fm_mod_params *p, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !m_dev || !y_dev || !n_host || !p) return -1;
-    if (p->in_format != RADE_FM_F32 && p->in_format != RADE_FM_C64) return -1;
-    if (p->out_mode != RADE_FM_OUT_COMPLEX && p->out_mode != RADE_FM_OUT_REAL) return -1;
-    if (((uintptr_t)m_dev & (p->in_format == RADE_FM_C64 ? 7 : 3)) || ((uintptr_t)y_dev & 7) || ((uintptr_t)p->noise_dev & 7)) return -1;
-    if (!fm_rates_ok(p->Fs, p->fc, p->fd) || !isfinite(p->sigma) || p->sigma < 0.0) return -1;
-    const int noise_on = p->sigma > 0.0;
-    if (noise_on && !p->noise_dev && !p->seed) return -1;             /* a noise level without a source of noise */
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->fm_ps_host && !(h->fm_ps_host = pinned_alloc_opt(h, sizeof(rd_fm_stream) * B))) return -1;
-    if (!h->fm_ph_end_host && !(h->fm_ph_end_host = pinned_alloc_opt(h, sizeof(unsigned) * B))) return -1;
-    int max_n = 0;
-    double work = 0.0;
-    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
-        rd_fm_stream *r = &h->fm_ps_host[b];
-        r->n = n_host[b]; r->n0 = p->n0_host ? p->n0_host[b] : 0; r->ph0 = p->phase0_host ? p->phase0_host[b] : 0u;
-        if (r->n < 0 || r->n > m_stride || r->n > y_stride || r->n0 < 0 || r->n0 > (1LL << 62)) return -1;
-        if (r->n > max_n) max_n = r->n;
-        work += 8.0 * r->n;
-    }
-    if (!max_n) {                                                     /* nothing to modulate: the phase stays where it was */
-        if (p->phase_end_host) for (int b = 0; b < B; b++) p->phase_end_host[b] = h->fm_ps_host[b].ph0;
-        return 0;
-    }
-    const int n_tiles = (max_n + RD_FM_TILE - 1) / RD_FM_TILE;
-    if (dev_grow(h, &h->fm_ps, NULL, B, sizeof(rd_fm_stream), 1) || dev_grow(h, &h->fm_ph_end, NULL, B, sizeof(unsigned), 1) ||
-        dev_grow(h, &h->fm_tsum, &h->fm_tsum_cap, (long)B * n_tiles, sizeof(unsigned), 1)) return -1;
-    /* the one small copy ahead of the launches; waited for, since the next call refills the staging records */
-    if (hipMemcpyAsync(h->fm_ps, h->fm_ps_host, sizeof(rd_fm_stream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-    rd_fm_mod_args a;
-    memset(&a, 0, sizeof a);
-    a.m = m_dev; a.m_stride = m_stride; a.y = y_dev; a.y_stride = y_stride; a.noise = noise_on ? p->noise_dev : NULL; a.noise_stride = max_n;
-    a.ps = h->fm_ps; a.tsum = h->fm_tsum; a.ph_end = h->fm_ph_end;
-    a.kc = p->fc / p->Fs * 4294967296.0; a.kd = p->fd / p->Fs * 4294967296.0; a.seed = p->seed;
-    a.sg = (float)(a.noise || p->out_mode == RADE_FM_OUT_REAL ? p->sigma : p->sigma / sqrt(2.0));
-    a.fmt = p->in_format; a.real_out = p->out_mode == RADE_FM_OUT_REAL; a.noise_on = noise_on; a.B = B; a.n_tiles = n_tiles;
-    PROF_BEGIN(h, stream);
-    if (rd_launch_fm_mod(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, work);
-    if (p->phase_end_host) {                                          /* read back like the wire meters: the call waits for `stream` */
-        if (hipMemcpyAsync(h->fm_ph_end_host, h->fm_ph_end, sizeof(unsigned) * B, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-        memcpy(p->phase_end_host, h->fm_ph_end_host, sizeof(unsigned) * B);
-    }
-    return 0;
-}
-
-int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
-                        const rade_fm_demod_params *p, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p || !p->b1 || !p->b2) return -1;
-    if (p->out_format != RADE_FM_F32 && p->out_format != RADE_FM_C64) return -1;
-    if (((uintptr_t)x_dev & 7) || ((uintptr_t)y_dev & (p->out_format == RADE_FM_C64 ? 7 : 3)) || ((uintptr_t)p->bb_out_dev & 7)) return -1;
-    if (!fm_rates_ok(p->Fs, p->fc, p->fd)) return -1;
-    if (p->N1 < 1 || p->N1 > RD_FM_NMAX || p->N2 < 1 || p->N2 > RD_FM_NMAX) return -1;
-    for (int k = 0; k < p->N1; k++) if (!isfinite(p->b1[k])) return -1;
-    for (int k = 0; k < p->N2; k++) if (!isfinite(p->b2[k])) return -1;
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->fm_dps_host && !(h->fm_dps_host = pinned_alloc_opt(h, sizeof(rd_fm_dstream) * B))) return -1;
-    int max_out = 0;
-    double work = 0.0;
-    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
-        rd_fm_dstream *r = &h->fm_dps_host[b];
-        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
-        r->in_base = p->in_base_host ? p->in_base_host[b] : 0; r->n0 = p->n0_host ? p->n0_host[b] : r->in_base;
-        if (r->n_in < 0 || r->n_out < 0 || r->n_in > x_stride || r->n_out > y_stride || (p->bb_out_dev && r->n_out > p->bb_stride)) return -1;
-        if (r->in_base > (1LL << 62) || r->in_base < -(1LL << 62) || r->n0 > (1LL << 62) || r->n0 < -(1LL << 62)) return -1;
-        if (r->n_out > max_out) max_out = r->n_out;
-        work += (4.0 * p->N1 + 2.0 * p->N2) * r->n_out;
-    }
-    if (!max_out) return 0;
-    if (!h->fm_taps_host) {                                           /* one pinned block: the staging copy, and behind it the bytes of the last upload */
-        if (!(h->fm_taps_host = pinned_alloc_opt(h, sizeof(float) * 4 * RD_FM_NMAX))) return -1;
-        h->fm_taps_last = h->fm_taps_host + 2 * RD_FM_NMAX;
-        memset(h->fm_taps_last, 0, sizeof(float) * 2 * RD_FM_NMAX);
-    }
-    if (dev_grow(h, &h->fm_taps, NULL, 2 * RD_FM_NMAX, sizeof(float), 1) || dev_grow(h, &h->fm_dps, NULL, B, sizeof(rd_fm_dstream), 1)) return -1;
-    if (h->fm_N1 != p->N1 || h->fm_N2 != p->N2 || memcmp(h->fm_taps_last, p->b1, sizeof(float) * p->N1) ||
-        memcmp(h->fm_taps_last + RD_FM_NMAX, p->b2, sizeof(float) * p->N2)) {            /* other bytes than the tables on the device were made from */
-        h->fm_N1 = h->fm_N2 = 0;
-        memset(h->fm_taps_host, 0, sizeof(float) * 2 * RD_FM_NMAX);
-        memcpy(h->fm_taps_host, p->b1, sizeof(float) * p->N1); memcpy(h->fm_taps_host + RD_FM_NMAX, p->b2, sizeof(float) * p->N2);
-        if (hipMemcpyAsync(h->fm_taps, h->fm_taps_host, sizeof(float) * 2 * RD_FM_NMAX, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    }
-    /* the one small copy ahead of the launch; waited for, since the next call refills the staging records (and may refill the staging tables) */
-    if (hipMemcpyAsync(h->fm_dps, h->fm_dps_host, sizeof(rd_fm_dstream) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-    if (!h->fm_N1) { memcpy(h->fm_taps_last, h->fm_taps_host, sizeof(float) * 2 * RD_FM_NMAX); h->fm_N1 = p->N1; h->fm_N2 = p->N2; }
-    const double wd = 2.0 * M_PI * p->fd / p->Fs;
-    rd_fm_demod_args a;
-    memset(&a, 0, sizeof a);
-    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.bb_out = p->bb_out_dev; a.bb_stride = p->bb_stride;
-    a.ps = h->fm_dps; a.taps = h->fm_taps;
-    a.fcq = (unsigned)(long long)llrint(p->fc / p->Fs * 4294967296.0);
-    a.wd = (float)wd; a.inv_wd = (float)(1.0 / wd);
-    a.N1 = p->N1; a.N2 = p->N2; a.fmt = p->out_format; a.dont_limit = p->ph_dont_limit != 0; a.B = B; a.max_out = max_out;
-    PROF_BEGIN(h, stream);
-    if (rd_launch_fm_demod(&a, stream)) return -1;
-    PROF_END(h, stream, RADE_PROF_CHAN, work);
-    return 0;
-}
-
-/* ---- C/No of the chirp header: est_CNo.py over every stream (rade_cno.hip; the arithmetic behind the band sums: rade_host.c) ------------------------------ */
-int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, const rade_cno_params *p, double *bands_host, int max_windows,
-                       rade_cno_result *result_host, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !x_dev || !n_host || !p || !result_host || ((uintptr_t)x_dev & 7)) return -1;
-    rade_cno_plan_t q;
-    if (rade_cno_plan(p, &q)) return -1;
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    int max_win = 0;
-    double work = 0.0;
-    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
-        const int n = n_host[b];
-        if (n < 0 || n > x_stride || n < q.N) return -1;
-        const int nw = n > q.N ? (n - q.N + RD_CNO_H - 1) / RD_CNO_H : 0;
-        if (nw > max_win) max_win = nw;
-        if (nw) work += 8.0 * (40.0 + 50.0 * 0.225 + 0.225 * q.J) * RD_CNO_H * (nw + q.J - 1) * q.J;
-    }
-    if (bands_host && max_windows < max_win) return -1;
-    if (max_win) {
-        if (!h->cno_n_host && !(h->cno_n_host = pinned_alloc_opt(h, sizeof(int) * B))) return -1;
-        if (!h->cno_tw_host && !(h->cno_tw_host = pinned_alloc_opt(h, sizeof(float) * 2 * RD_CNO_H * RD_CNO_JMAX))) return -1;
-        if (dev_grow(h, &h->cno_tw, NULL, 2L * RD_CNO_H * RD_CNO_JMAX, sizeof(float), 1) || dev_grow(h, &h->cno_n, NULL, B, sizeof(int), 1)) return -1;
-        if (dev_grow(h, &h->cno_part, &h->cno_cap, max_win, sizeof(double) * 2 * RD_CNO_JMAX * B, 1)) return -1;
-        if (dev_grow(h, &h->cno_bands, &h->cno_bands_cap, max_win, sizeof(double) * 2 * B, 1)) return -1;
-        if (!h->cno_bands_host || h->cno_host_cap < max_win) {
-            if (h->cno_bands_host) { if (hipDeviceSynchronize() != hipSuccess) return -1; disown(h, h->cno_bands_host); h->cno_host_cap = 0; }
-            if (!(h->cno_bands_host = pinned_alloc_opt(h, sizeof(double) * 2 * B * max_win))) return -1;
-            h->cno_host_cap = max_win;
-        }
-        if (h->cno_N != q.N) {             /* another window length than the table on the device was made for: re-made, uploaded behind what `stream` holds */
-            h->cno_N = 0;
-            rd_cno_table(q.N, h->cno_tw_host);
-            if (hipMemcpyAsync(h->cno_tw, h->cno_tw_host, sizeof(float) * 2 * q.N, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-        }
-        memcpy(h->cno_n_host, n_host, sizeof(int) * B);
-        if (hipMemcpyAsync(h->cno_n, h->cno_n_host, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-        rd_cno_args a;
-        memset(&a, 0, sizeof a);
-        a.x = x_dev; a.x_stride = x_stride; a.n = h->cno_n; a.tw = h->cno_tw; a.part = h->cno_part; a.bands = h->cno_bands;
-        a.N = q.N; a.J = q.J; a.B = B; a.max_win = max_win;
-        a.flow_bin = q.flow_bin; a.fhigh_bin = q.fhigh_bin; a.noise_st = q.noise_st; a.noise_en = q.noise_en;
-        a.pitch = rd_cno_pitch(q.J, q.flow_bin, q.fhigh_bin, q.noise_st, q.noise_en);
-        PROF_BEGIN(h, stream);
-        const int e = rd_launch_cno(&a, stream);
-        PROF_END(h, stream, RADE_PROF_CHAN, work);
-        /* the band sums come back and the stream is waited for (also where the launch failed: the staging copies above are then free again) */
-        const int e2 = e ? 0 : hipMemcpyAsync(h->cno_bands_host, h->cno_bands, sizeof(double) * 2 * B * max_win, hipMemcpyDeviceToHost, st) != hipSuccess;
-        if (hipStreamSynchronize(st) != hipSuccess || e || e2) return -1;
-        h->cno_N = q.N;
-    } else if (hipStreamSynchronize(st) != hipSuccess) return -1;
-    for (int b = 0; b < B; b++) {
-        const int nw = n_host[b] > q.N ? (n_host[b] - q.N + RD_CNO_H - 1) / RD_CNO_H : 0;
-        const double *bands = nw ? h->cno_bands_host + (size_t)b * max_win * 2 : NULL;
-        rd_cno_finish(&q, p, bands, nw, &result_host[b]);
-        if (bands_host && nw) memcpy(bands_host + (size_t)b * max_windows * 2, bands, sizeof(double) * 2 * nw);
-    }
-    return 0;
 }
 
 /* The wait of rade_batch_rx when the host is short of CPUs (sync_blocking_now): SLEEP until the receiver launch is done.  hipEventSynchronize on a

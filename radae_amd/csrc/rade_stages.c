@@ -1,0 +1,458 @@
+/*
+ * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
+ * rate converter, analog FM and the chirp header's C/No.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
+ * its device and pinned memory is on the engine's own list (rade_engine.h).
+ *
+ * The rules of that plumbing are stated once each, below: the record pair, the cached table and the span check here, the read-back in rade_engine.c (read_back).
+ * Every refusal happens before any launch and writes nothing.
+ */
+#include <stdlib.h>
+#include <string.h>
+#include <stdint.h>
+#include <math.h>
+
+#include "rade_engine.h"
+
+/* ---- the record pair: [B] per-stream values of a call on the device and their pinned staging copy, both allocated on first use -----------------------------------
+ * The rule: the staging copy is not refilled until the device has read it.  A call fills pair_host() while it checks its streams and then pushes; with wait = 1 the
+ * push waits for the stream, since the next call refills the staging copy (and may refill a staging table queued ahead of it); with wait = 0 the call itself waits
+ * before it returns (settle, or a read-back). */
+typedef struct { void *host, *dev; } rd_pair;
+static int settle(hipStream_t st) { return hipStreamSynchronize(st) == hipSuccess ? 0 : -1; }
+static void *pair_host(rade_batch *h, rd_pair *p, size_t bytes)
+{
+    if (!p->host) p->host = pinned_alloc_opt(h, bytes);
+    return p->host;
+}
+static int pair_push(rade_batch *h, rd_pair *p, size_t bytes, int wait, hipStream_t st)
+{
+    if (dev_grow(h, &p->dev, NULL, 1, bytes, 1)) return -1;
+    if (hipMemcpyAsync(p->dev, p->host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    return wait ? settle(st) : 0;
+}
+
+/* ---- the cached table: a table on the device that is a function of a key, made again only when a call brings another key ------------------------------------------
+ * Both buffers hold the largest table the stage admits and are allocated on first use.  The protocol: a call whose key is not table_is() fills t->host and calls
+ * table_upload, which clears the key BEFORE it queues the copy behind what the stream holds; table_commit sets the key only AFTER the call has waited for the stream.
+ * A call that fails in between leaves the key cleared, so the next call makes the table again; and the staging table is never refilled while a copy of it is queued.
+ * keep_last: t->last holds the bytes of the committed upload, for a key that includes the table's contents (the FM demodulator's taps). */
+typedef struct { float *host, *dev, *last; size_t cap; int key[2], pending[2]; } rd_table;
+static int table_alloc(rade_batch *h, rd_table *t, size_t cap, int keep_last)
+{
+    if (!t->host) {
+        if (!(t->host = pinned_alloc_opt(h, sizeof(float) * cap * (keep_last ? 2 : 1)))) return -1;
+        t->cap = cap;
+        if (keep_last) { t->last = t->host + cap; memset(t->last, 0, sizeof(float) * cap); }
+    }
+    return dev_grow(h, &t->dev, NULL, (long)cap, sizeof(float), 1);
+}
+static int table_is(const rd_table *t, int k0, int k1) { return t->key[0] == k0 && t->key[1] == k1; }
+static int table_upload(rd_table *t, int k0, int k1, size_t n, hipStream_t st)
+{
+    t->key[0] = t->key[1] = 0; t->pending[0] = k0; t->pending[1] = k1;
+    return hipMemcpyAsync(t->dev, t->host, sizeof(float) * n, hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -1;
+}
+static void table_commit(rd_table *t)       /* after the wait; nothing to do for a call that found its table on the device */
+{
+    if (!t->pending[0]) return;
+    if (t->last) memcpy(t->last, t->host, sizeof(float) * t->cap);
+    t->key[0] = t->pending[0]; t->key[1] = t->pending[1]; t->pending[0] = t->pending[1] = 0;
+}
+
+/* ---- the span check of a stream that reads n_in elements of a row of x_stride and writes n_out of a row of y_stride: the counts against the strides, the index n0
+ * of its first output (>= n0_min) and the absolute index in_base of its first input, both within +-2^62 ----------------------------------------------------------- */
+static int span_bad(long n_in, long x_stride, long n_out, long y_stride, long long n0, long long n0_min, long long in_base)
+{
+    if (n_in < 0 || n_out < 0 || n_in > x_stride || n_out > y_stride || n0 < n0_min) return 1;
+    return n0 > (1LL << 62) || in_base > (1LL << 62) || in_base < -(1LL << 62);
+}
+
+#define RD_WIRE_SLOTS 8
+struct rd_stages {
+    /* rade_batch_channel_rs_pa: [B] per-stream sigma; [B][RD_RS_NCH][4] measurement partials, [B][3] measurements */
+    rd_pair rs_sigma; double *rs_part, *rs_stats;
+    /* rade_batch_resample: the taps [257][32] (made once); [B] per-stream records */
+    float *clk_taps; rd_pair clk_ps;
+    /* rade_batch_wire_in / _out: the [B] sample counts of the last RD_WIRE_SLOTS calls on the device and their pinned staging copies, one slot per call in turn (a call
+     * does not wait for its stream: it waits for the call that used its slot RD_WIRE_SLOTS calls ago); [B][RD_WIRE_NCH_MAX][4] meter partials, [B][4] meters */
+    int *wire_n, *wire_n_host; hipEvent_t wire_ev[RD_WIRE_SLOTS]; unsigned wire_used, wire_seq; double *wire_part, *wire_meters;
+    /* rade_batch_rate_convert: the [L][T] table, key = the reduced ratio (L, M); [B] per-stream records */
+    rd_table rate_taps; rd_pair rate_ps;
+    /* rade_batch_fm_mod: [B] per-stream records; [B][fm_tsum_cap / B] tile sums; [B] final phases.
+     * rade_batch_fm_demod: its [B] records; the two tap tables [2][RD_FM_NMAX], key = (N1, N2) and the bytes they were made from */
+    rd_pair fm_ps; unsigned *fm_tsum; long fm_tsum_cap; unsigned *fm_ph_end;
+    rd_pair fm_dps; rd_table fm_taps;
+    /* rade_batch_cno_est: the table e^{-2 pi i m / N}, key = the window length N; the [B] sample counts; [B][cno_cap][RD_CNO_JMAX][2] partial and [B][cno_bands_cap][2]
+     * band sums, grown with the call */
+    rd_table cno_tw; rd_pair cno_n; double *cno_part, *cno_bands; long cno_cap, cno_bands_cap;
+};
+static struct rd_stages *stages_of(rade_batch *h)
+{
+    if (!h->stages) h->stages = calloc(1, sizeof *h->stages);
+    return h->stages;
+}
+void rd_stages_free(struct rd_stages *s)
+{
+    for (int i = 0; i < RD_WIRE_SLOTS; i++) if (s->wire_ev[i]) hipEventDestroy(s->wire_ev[i]);
+    free(s);
+}
+
+/* ---- the rate-Rs channel of the bottleneck-3 model (radae.py:603-634; rade_rs.hip) ------------------------------------------------------------ */
+int rade_batch_channel_rs_pa(rade_batch *h, const float *z_dev, const float *H_dev, const void *noise_dev, float *z_hat_dev, int n_steps, float sigma,
+                             const float *sigma_streams_host, float phase_offset, unsigned long long seed, double *stats_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !z_dev || !z_hat_dev || n_steps <= 0) return -1;
+    if (((uintptr_t)z_dev | (uintptr_t)H_dev | (uintptr_t)z_hat_dev) & 3 || ((uintptr_t)noise_dev & 7)) return -1;   /* element alignment is all the kernel needs */
+    struct rd_stages *s = stages_of(h);
+    if (!s) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    if (dev_grow(h, &s->rs_part, NULL, (long)B * RD_RS_NCH * 4, sizeof(double), 1) || dev_grow(h, &s->rs_stats, NULL, 3L * B, sizeof(double), 1)) return -1;
+    if (sigma_streams_host) {
+        float *sg = pair_host(h, &s->rs_sigma, sizeof(float) * B);
+        if (!sg) return -1;
+        memcpy(sg, sigma_streams_host, sizeof(float) * B);
+        if (pair_push(h, &s->rs_sigma, sizeof(float) * B, 1, st)) return -1;
+    }
+    rd_rs_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.z = z_dev; a.H = H_dev; a.noise = noise_dev; a.z_hat = z_hat_dev; a.B = B; a.n_steps = n_steps;
+    a.sigma = sigma; a.sigma_b = sigma_streams_host ? s->rs_sigma.dev : NULL; a.seed = seed;
+    a.has_phase = phase_offset != 0.0f; a.ph_re = cosf(phase_offset); a.ph_im = sinf(phase_offset);      /* radae.py:616-619 */
+    a.part = s->rs_part; a.stats = stats_host ? s->rs_stats : NULL;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_rs_pa(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, 8.0 * B * 2.0 * n_steps * 2 * 20 * RD_M);
+    if (stats_host) {
+        const void *res = read_back(h, s->rs_stats, sizeof(double) * 3 * B, st);
+        if (!res) return -1;
+        memcpy(stats_host, res, sizeof(double) * 3 * B);
+    }
+    return n_steps;
+}
+
+/* ---- sample-clock offset: the fractional resampler (rade_clk.hip) ------------------------------------------------------------------------------ */
+int rade_batch_resample(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
+                        const rade_resample_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p) return -1;
+    if (((uintptr_t)x_dev | (uintptr_t)y_dev) & 7) return -1;
+    if (p->mode != RADE_RESAMPLE_SINC32 && p->mode != RADE_RESAMPLE_LINEAR) return -1;
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    rd_clk_stream *ps = s ? pair_host(h, &s->clk_ps, sizeof(rd_clk_stream) * B) : NULL;
+    if (!ps) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_clk_stream *r = &ps[b];
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
+        r->n0 = p->n0_host ? p->n0_host[b] : 0; r->in_base = p->in_base_host ? p->in_base_host[b] : 0;
+        if (span_bad(r->n_in, x_stride, r->n_out, y_stride, r->n0, 0, r->in_base)) return -1;
+        if (rd_resample_q(p->t0_host ? p->t0_host[b] : 0.0, p->ppm_host ? p->ppm_host[b] : p->ppm, &r->step_q, &r->t0_q)) return -1;
+        if (((__int128)r->n0 + r->n_out) * r->step_q > ((__int128)1 << 62)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (p->mode == RADE_RESAMPLE_SINC32 ? 4.0 * 2 * RD_CLK_TAPS : 6.0) * r->n_out;
+    }
+    if (!max_out) return 0;
+    if (!s->clk_taps) {
+        float *t = malloc(sizeof(float) * (RD_CLK_PHASES + 1) * RD_CLK_TAPS);
+        if (t) { rade_resample_taps(t); s->clk_taps = dev_upload_opt(h, t, sizeof(float) * (RD_CLK_PHASES + 1) * RD_CLK_TAPS); }
+        free(t);
+        if (!s->clk_taps) return -1;
+    }
+    if (pair_push(h, &s->clk_ps, sizeof(rd_clk_stream) * B, 1, st)) return -1;       /* the one small copy ahead of the launch */
+    rd_clk_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.ps = s->clk_ps.dev; a.taps = s->clk_taps; a.mode = p->mode; a.B = B; a.max_out = max_out;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_clk_resample(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- the sound-card wire: int16 <-> complex64 (rade_wire.hip) ---------------------------------------------------------------------------------- */
+/* Checks every stream, then puts the counts on the device in the call's slot and fills the launch record; 1 = nothing to do (no stream has a sample), -1 = refused */
+static int wire_prepare(rade_batch *h, const void *i16, long i16_stride, const void *c64, long c64_stride, const int *n_host, int mode, float k, rd_wire_args *a, int *slot, hipStream_t st)
+{
+    if (!h || !i16 || !c64 || !n_host) return -1;
+    if (((uintptr_t)i16 & 1) || ((uintptr_t)c64 & 7)) return -1;
+    if ((mode != RADE_WIRE_REAL && mode != RADE_WIRE_IQ) || !isfinite(k)) return -1;
+    const int B = h->B;
+    int max_n = 0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        const int n = n_host[b];
+        if (n < 0 || n > c64_stride || (long)n << mode > i16_stride) return -1;
+        if (n > max_n) max_n = n;
+    }
+    struct rd_stages *w = stages_of(h);
+    if (!w) return -1;
+    if (!w->wire_n_host && !(w->wire_n_host = pinned_alloc_opt(h, sizeof(int) * RD_WIRE_SLOTS * B))) return -1;
+    if (dev_grow(h, &w->wire_n, NULL, (long)RD_WIRE_SLOTS * B, sizeof(int), 1)) return -1;
+    const int s = (int)(w->wire_seq++ % RD_WIRE_SLOTS);
+    if (!w->wire_ev[s] && hipEventCreateWithFlags(&w->wire_ev[s], hipEventDisableTiming) != hipSuccess) { w->wire_ev[s] = NULL; return -1; }
+    if ((w->wire_used >> s & 1) && hipEventSynchronize(w->wire_ev[s]) != hipSuccess) return -1;     /* the slot's previous call has read its counts */
+    w->wire_used &= ~(1u << s);
+    memcpy(w->wire_n_host + (size_t)s * B, n_host, sizeof(int) * B);
+    if (hipMemcpyAsync(w->wire_n + (size_t)s * B, w->wire_n_host + (size_t)s * B, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    memset(a, 0, sizeof *a);
+    a->i16 = (void *)i16; a->i16_stride = i16_stride; a->c64 = (void *)c64; a->c64_stride = c64_stride; a->n = w->wire_n + (size_t)s * B;
+    a->mode = mode; a->B = B; a->k = k;
+    a->n_ch = 4096 / B < 4 ? 4 : 4096 / B > RD_WIRE_NCH_MAX ? RD_WIRE_NCH_MAX : 4096 / B;      /* a function of B alone: a stream's meter sums do not depend on the other streams */
+    *slot = s;
+    return max_n ? 0 : 1;
+}
+/* the slot is busy until what was queued on st up to here has run */
+static int wire_done(rade_batch *h, int slot, hipStream_t st)
+{
+    if (hipEventRecord(h->stages->wire_ev[slot], st) != hipSuccess) return -1;
+    h->stages->wire_used |= 1u << slot;
+    return 0;
+}
+
+int rade_batch_wire_in(rade_batch *h, const void *in_dev, long in_stride, const int *n_host, int mode, float gain, void *out_dev, long out_stride, void *stream)
+{
+    ON_DEV(h);
+    hipStream_t st = (hipStream_t)stream;
+    rd_wire_args a; int slot;
+    const int r = wire_prepare(h, in_dev, in_stride, out_dev, out_stride, n_host, mode, gain, &a, &slot, st);
+    if (r < 0) return -1;
+    if (r == 0) {
+        PROF_BEGIN(h, stream);
+        if (rd_launch_wire_in(&a, stream)) return -1;
+        PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
+    }
+    return wire_done(h, slot, st);
+}
+
+int rade_batch_wire_out(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int mode, float scale, void *out_dev, long out_stride, double *meters_host, void *stream)
+{
+    ON_DEV(h);
+    hipStream_t st = (hipStream_t)stream;
+    rd_wire_args a; int slot;
+    const int r = wire_prepare(h, out_dev, out_stride, x_dev, x_stride, n_host, mode, scale, &a, &slot, st);
+    if (r < 0) return -1;
+    struct rd_stages *w = h->stages;
+    const int B = h->B;
+    if (meters_host) {
+        if (dev_grow(h, &w->wire_part, NULL, (long)B * RD_WIRE_NCH_MAX * 4, sizeof(double), 1) || dev_grow(h, &w->wire_meters, NULL, 4L * B, sizeof(double), 1)) return -1;
+        a.part = w->wire_part; a.meters = w->wire_meters;
+    }
+    if (r == 0) {
+        PROF_BEGIN(h, stream);
+        if (rd_launch_wire_out(&a, stream)) return -1;
+        PROF_END(h, stream, RADE_PROF_CHAN, 0.0);
+    }
+    if (wire_done(h, slot, st)) return -1;
+    if (meters_host) {                     /* straight into the caller's array, and the stream waited for */
+        if (r) { memset(meters_host, 0, sizeof(double) * 4 * B); return 0; }     /* no stream has a sample: nothing was launched */
+        if (hipMemcpyAsync(meters_host, w->wire_meters, sizeof(double) * 4 * B, hipMemcpyDeviceToHost, st) != hipSuccess || settle(st)) return -1;
+    }
+    return 0;
+}
+
+/* ---- the rational rate converter: 48 / 44.1 kHz <-> 8 kHz (rade_rate.hip) ------------------------------------------------------------------------------ */
+int rade_batch_rate_convert(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, int format, float gain, void *y_dev, long y_stride,
+                            const int *n_out_host, const rade_rate_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p) return -1;
+    if (format != RADE_RATE_C64 && format != RADE_RATE_S16_REAL && format != RADE_RATE_S16_IQ) return -1;
+    if (((uintptr_t)x_dev & (format == RADE_RATE_C64 ? 7 : 1)) || ((uintptr_t)y_dev & 7)) return -1;
+    if (format != RADE_RATE_C64 && !isfinite(gain)) return -1;
+    int L, M, T;
+    if (rd_rate_reduce(p->L, p->M, &L, &M, &T)) return -1;
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B, per = format == RADE_RATE_S16_IQ ? 2 : 1;         /* elements of x per sample */
+    hipStream_t st = (hipStream_t)stream;
+    rd_rate_stream *ps = s ? pair_host(h, &s->rate_ps, sizeof(rd_rate_stream) * B) : NULL;
+    if (!ps) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_rate_stream *r = &ps[b];
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
+        r->n0 = p->n0_host ? p->n0_host[b] : 0; r->in_base = p->in_base_host ? p->in_base_host[b] : 0;
+        if (span_bad((long)r->n_in * per, x_stride, r->n_out, y_stride, r->n0, 0, r->in_base)) return -1;
+        if (((__int128)r->n0 + r->n_out) * M > ((__int128)1 << 62)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (format == RADE_RATE_S16_REAL ? 2.0 : 4.0) * T * r->n_out;
+    }
+    if (!max_out) return 0;
+    if (table_alloc(h, &s->rate_taps, RD_RATE_TABLE_MAX, 0)) return -1;
+    if (!table_is(&s->rate_taps, L, M) && (rade_rate_taps(L, M, s->rate_taps.host) != T || table_upload(&s->rate_taps, L, M, (size_t)L * T, st))) return -1;
+    if (pair_push(h, &s->rate_ps, sizeof(rd_rate_stream) * B, 1, st)) return -1;     /* the one small copy ahead of the launch */
+    table_commit(&s->rate_taps);
+    rd_rate_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.ps = s->rate_ps.dev; a.taps = s->rate_taps.dev;
+    a.L = L; a.M = M; a.T = T; a.tile = rd_rate_tile(L, M, T); a.fmt = format; a.B = B; a.max_out = max_out; a.gain = gain;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_rate_convert(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- the analog FM modulator and demodulator (rade_fm.hip) -------------------------------------------------------------------------------------------------- */
+static int fm_rates_ok(double Fs, double fc, double fd)
+{
+    return isfinite(Fs) && isfinite(fc) && isfinite(fd) && Fs > 0.0 && fabs(fc) <= Fs / 2.0 && fd > 0.0 && fd <= Fs / 2.0;
+}
+
+int rade_batch_fm_mod(rade_batch *h, const void *m_dev, long m_stride, const int *n_host, void *y_dev, long y_stride, const rade_fm_mod_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !m_dev || !y_dev || !n_host || !p) return -1;
+    if (p->in_format != RADE_FM_F32 && p->in_format != RADE_FM_C64) return -1;
+    if (p->out_mode != RADE_FM_OUT_COMPLEX && p->out_mode != RADE_FM_OUT_REAL) return -1;
+    if (((uintptr_t)m_dev & (p->in_format == RADE_FM_C64 ? 7 : 3)) || ((uintptr_t)y_dev & 7) || ((uintptr_t)p->noise_dev & 7)) return -1;
+    if (!fm_rates_ok(p->Fs, p->fc, p->fd) || !isfinite(p->sigma) || p->sigma < 0.0) return -1;
+    const int noise_on = p->sigma > 0.0;
+    if (noise_on && !p->noise_dev && !p->seed) return -1;             /* a noise level without a source of noise */
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    rd_fm_stream *ps = s ? pair_host(h, &s->fm_ps, sizeof(rd_fm_stream) * B) : NULL;
+    if (!ps) return -1;
+    int max_n = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_fm_stream *r = &ps[b];
+        r->n = n_host[b]; r->n0 = p->n0_host ? p->n0_host[b] : 0; r->ph0 = p->phase0_host ? p->phase0_host[b] : 0u;
+        if (r->n < 0 || r->n > m_stride || r->n > y_stride || r->n0 < 0 || r->n0 > (1LL << 62)) return -1;
+        if (r->n > max_n) max_n = r->n;
+        work += 8.0 * r->n;
+    }
+    if (!max_n) {                                                     /* nothing to modulate: the phase stays where it was */
+        if (p->phase_end_host) for (int b = 0; b < B; b++) p->phase_end_host[b] = ps[b].ph0;
+        return 0;
+    }
+    const int n_tiles = (max_n + RD_FM_TILE - 1) / RD_FM_TILE;
+    if (dev_grow(h, &s->fm_ph_end, NULL, B, sizeof(unsigned), 1) || dev_grow(h, &s->fm_tsum, &s->fm_tsum_cap, (long)B * n_tiles, sizeof(unsigned), 1)) return -1;
+    if (pair_push(h, &s->fm_ps, sizeof(rd_fm_stream) * B, 1, st)) return -1;         /* the one small copy ahead of the launches */
+    rd_fm_mod_args a;
+    memset(&a, 0, sizeof a);
+    a.m = m_dev; a.m_stride = m_stride; a.y = y_dev; a.y_stride = y_stride; a.noise = noise_on ? p->noise_dev : NULL; a.noise_stride = max_n;
+    a.ps = s->fm_ps.dev; a.tsum = s->fm_tsum; a.ph_end = s->fm_ph_end;
+    a.kc = p->fc / p->Fs * 4294967296.0; a.kd = p->fd / p->Fs * 4294967296.0; a.seed = p->seed;
+    a.sg = (float)(a.noise || p->out_mode == RADE_FM_OUT_REAL ? p->sigma : p->sigma / sqrt(2.0));
+    a.fmt = p->in_format; a.real_out = p->out_mode == RADE_FM_OUT_REAL; a.noise_on = noise_on; a.B = B; a.n_tiles = n_tiles;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_fm_mod(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    if (p->phase_end_host) {                                          /* the call then waits for `stream` once more */
+        const void *end = read_back(h, s->fm_ph_end, sizeof(unsigned) * B, st);
+        if (!end) return -1;
+        memcpy(p->phase_end_host, end, sizeof(unsigned) * B);
+    }
+    return 0;
+}
+
+int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const int *n_in_host, void *y_dev, long y_stride, const int *n_out_host,
+                        const rade_fm_demod_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_in_host || !n_out_host || !p || !p->b1 || !p->b2) return -1;
+    if (p->out_format != RADE_FM_F32 && p->out_format != RADE_FM_C64) return -1;
+    if (((uintptr_t)x_dev & 7) || ((uintptr_t)y_dev & (p->out_format == RADE_FM_C64 ? 7 : 3)) || ((uintptr_t)p->bb_out_dev & 7)) return -1;
+    if (!fm_rates_ok(p->Fs, p->fc, p->fd)) return -1;
+    if (p->N1 < 1 || p->N1 > RD_FM_NMAX || p->N2 < 1 || p->N2 > RD_FM_NMAX) return -1;
+    for (int k = 0; k < p->N1; k++) if (!isfinite(p->b1[k])) return -1;
+    for (int k = 0; k < p->N2; k++) if (!isfinite(p->b2[k])) return -1;
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    rd_fm_dstream *ps = s ? pair_host(h, &s->fm_dps, sizeof(rd_fm_dstream) * B) : NULL;
+    if (!ps) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_fm_dstream *r = &ps[b];
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b];
+        r->in_base = p->in_base_host ? p->in_base_host[b] : 0; r->n0 = p->n0_host ? p->n0_host[b] : r->in_base;
+        if (span_bad(r->n_in, x_stride, r->n_out, y_stride, r->n0, -(1LL << 62), r->in_base) || (p->bb_out_dev && r->n_out > p->bb_stride)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (4.0 * p->N1 + 2.0 * p->N2) * r->n_out;
+    }
+    if (!max_out) return 0;
+    rd_table *t = &s->fm_taps;             /* [2][RD_FM_NMAX]: b1, b2, zeros behind each */
+    if (table_alloc(h, t, 2 * RD_FM_NMAX, 1)) return -1;
+    if (!table_is(t, p->N1, p->N2) || memcmp(t->last, p->b1, sizeof(float) * p->N1) || memcmp(t->last + RD_FM_NMAX, p->b2, sizeof(float) * p->N2)) {
+        memset(t->host, 0, sizeof(float) * 2 * RD_FM_NMAX);
+        memcpy(t->host, p->b1, sizeof(float) * p->N1); memcpy(t->host + RD_FM_NMAX, p->b2, sizeof(float) * p->N2);
+        if (table_upload(t, p->N1, p->N2, 2 * RD_FM_NMAX, st)) return -1;
+    }
+    if (pair_push(h, &s->fm_dps, sizeof(rd_fm_dstream) * B, 1, st)) return -1;       /* the one small copy ahead of the launch */
+    table_commit(t);
+    const double wd = 2.0 * M_PI * p->fd / p->Fs;
+    rd_fm_demod_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.bb_out = p->bb_out_dev; a.bb_stride = p->bb_stride;
+    a.ps = s->fm_dps.dev; a.taps = t->dev;
+    a.fcq = (unsigned)(long long)llrint(p->fc / p->Fs * 4294967296.0);
+    a.wd = (float)wd; a.inv_wd = (float)(1.0 / wd);
+    a.N1 = p->N1; a.N2 = p->N2; a.fmt = p->out_format; a.dont_limit = p->ph_dont_limit != 0; a.B = B; a.max_out = max_out;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_fm_demod(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- C/No of the chirp header: est_CNo.py over every stream (rade_cno.hip; the arithmetic behind the band sums: rade_host.c) ------------------------------ */
+int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, const rade_cno_params *p, double *bands_host, int max_windows,
+                       rade_cno_result *result_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || !p || !result_host || ((uintptr_t)x_dev & 7)) return -1;
+    rade_cno_plan_t q;
+    if (rade_cno_plan(p, &q)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    int max_win = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride || n < q.N) return -1;
+        const int nw = n > q.N ? (n - q.N + RD_CNO_H - 1) / RD_CNO_H : 0;
+        if (nw > max_win) max_win = nw;
+        if (nw) work += 8.0 * (40.0 + 50.0 * 0.225 + 0.225 * q.J) * RD_CNO_H * (nw + q.J - 1) * q.J;
+    }
+    if (bands_host && max_windows < max_win) return -1;
+    const double *bands_all = NULL;        /* [B][max_win][2], read back */
+    if (max_win) {
+        struct rd_stages *s = stages_of(h);
+        int *n_stage = s ? pair_host(h, &s->cno_n, sizeof(int) * B) : NULL;
+        if (!n_stage || table_alloc(h, &s->cno_tw, 2L * RD_CNO_H * RD_CNO_JMAX, 0)) return -1;
+        if (dev_grow(h, &s->cno_part, &s->cno_cap, max_win, sizeof(double) * 2 * RD_CNO_JMAX * B, 1)) return -1;
+        if (dev_grow(h, &s->cno_bands, &s->cno_bands_cap, max_win, sizeof(double) * 2 * B, 1)) return -1;
+        if (!table_is(&s->cno_tw, q.N, 0)) {
+            rd_cno_table(q.N, s->cno_tw.host);
+            if (table_upload(&s->cno_tw, q.N, 0, 2 * (size_t)q.N, st)) return -1;
+        }
+        memcpy(n_stage, n_host, sizeof(int) * B);
+        if (pair_push(h, &s->cno_n, sizeof(int) * B, 0, st)) return -1;              /* not waited for here: the call waits at its end */
+        rd_cno_args a;
+        memset(&a, 0, sizeof a);
+        a.x = x_dev; a.x_stride = x_stride; a.n = s->cno_n.dev; a.tw = s->cno_tw.dev; a.part = s->cno_part; a.bands = s->cno_bands;
+        a.N = q.N; a.J = q.J; a.B = B; a.max_win = max_win;
+        a.flow_bin = q.flow_bin; a.fhigh_bin = q.fhigh_bin; a.noise_st = q.noise_st; a.noise_en = q.noise_en;
+        a.pitch = rd_cno_pitch(q.J, q.flow_bin, q.fhigh_bin, q.noise_st, q.noise_en);
+        PROF_BEGIN(h, stream);
+        const int e = rd_launch_cno(&a, stream);
+        PROF_END(h, stream, RADE_PROF_CHAN, work);
+        /* the band sums come back and the stream is waited for (also where the launch failed: the staging copies above are then free again) */
+        if (e || !(bands_all = read_back(h, s->cno_bands, sizeof(double) * 2 * B * max_win, st))) { settle(st); return -1; }
+        table_commit(&s->cno_tw);
+    } else if (settle(st)) return -1;
+    for (int b = 0; b < B; b++) {
+        const int nw = n_host[b] > q.N ? (n_host[b] - q.N + RD_CNO_H - 1) / RD_CNO_H : 0;
+        const double *bands = nw ? bands_all + (size_t)b * max_win * 2 : NULL;
+        rd_cno_finish(&q, p, bands, nw, &result_host[b]);
+        if (bands_host && nw) memcpy(bands_host + (size_t)b * max_windows * 2, bands, sizeof(double) * 2 * nw);
+    }
+    return 0;
+}

@@ -315,6 +315,33 @@ def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
     return np.ascontiguousarray(np.broadcast_to(a, (B,)))
 
 
+def _is_rows(t, B: int, dtype) -> bool:
+    """2-D device rows [B, N] of `dtype` with unit inner stride (a row of at most one sample may carry any)"""
+    return t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[0] == B and (t.stride(1) == 1 or t.shape[1] <= 1)
+
+
+def _counts(B: int, v, N: int, what: str) -> np.ndarray:
+    """per-stream counts within a row of N samples (None: the whole row of every stream) -> int32 [B]"""
+    n = _per_stream(B, N if v is None else v, np.int32, what)
+    if n.min() < 0 or n.max() > N:
+        raise ValueError(f"{what}: between 0 and the {N} samples of a row")
+    return n
+
+
+def _row_stride(t, row: int) -> int:
+    """the row stride of a [B, ..] tensor in elements; a one-row tensor may carry any stride in its first dimension (0 from numpy's [None]): its row of `row` elements"""
+    return t.stride(0) if t.shape[0] > 1 else row
+
+
+def _out_rows(out, B: int, n, width: int, device):
+    """complex64 output rows of at least max n: the caller's `out`, checked, or zeros [B, max(width, 1)]"""
+    import torch
+    if out is None:
+        out = torch.zeros((B, max(int(width), 1)), dtype=torch.complex64, device=device)
+    assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n.max()
+    return out
+
+
 def sigma_from_EbNodB(EbNodB, bottleneck: int = 3, rate_Fs: bool = True):
     """AWGN standard deviation of the rate-Fs channel: bottleneck 3 (radae.py:567-573) or bottleneck 1 (:574-576, the waveform of TX_LINEAR); with rate_Fs=False
     of the rate-Rs channel of bottleneck 3 (radae.py:627-630, channel_rs_pa: 12.66 at 3 dB, for symbols of magnitude M / sqrt(Nc)).
@@ -569,24 +596,19 @@ class BatchEngine:
         rade_resample_count(in_base + n_in, t0, ppm) - n0: every output whose position lies inside the input.  mode "sinc32" or "linear" (dsp.py:564-575).  Samples
         of y past a stream's n_out are zeros (left alone in a caller's `out`)."""
         import torch
-        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == self.B and (x.stride(1) == 1 or x.shape[1] <= 1)
         B = self.B
+        assert _is_rows(x, B, torch.complex64)
         ppm = _per_stream(B, ppm, np.float64, "ppm"); t0 = _per_stream(B, t0, np.float64, "t0")
         n0 = _per_stream(B, n0, np.int64, "n0"); in_base = _per_stream(B, in_base, np.int64, "in_base")
-        n_in = _per_stream(B, x.shape[1] if n_in is None else n_in, np.int32, "n_in")
-        if n_in.min() < 0 or n_in.max() > x.shape[1]:
-            raise ValueError(f"n_in: between 0 and the {x.shape[1]} samples of a row")
+        n_in = _counts(B, n_in, x.shape[1], "n_in")
         if n_out is None:
             n_out = np.array([max(resample_count(int(in_base[b]) + int(n_in[b]), t0[b], ppm[b]) - int(n0[b]), 0) for b in range(B)], np.int32)
         else:
             n_out = _per_stream(B, n_out, np.int32, "n_out")
-        if out is None:
-            out = torch.zeros((B, max(int(n_out.max()), 1)), dtype=torch.complex64, device=x.device)
-        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n_out.max()
+        out = _out_rows(out, B, n_out, n_out.max(), x.device)
         p = ResampleParams(RESAMPLE_MODES[mode], 0.0, ppm.ctypes.data, t0.ctypes.data, n0.ctypes.data, in_base.ctypes.data)
-        xs = x.stride(0) if B > 1 else x.shape[1]              # (a one-row tensor may carry any stride in its first dimension)
-        ys = out.stride(0) if B > 1 else out.shape[1]
-        if self.lib.rade_batch_resample(self.h, x.data_ptr(), xs, n_in.ctypes.data, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
+        if self.lib.rade_batch_resample(self.h, x.data_ptr(), _row_stride(x, x.shape[1]), n_in.ctypes.data, out.data_ptr(), _row_stride(out, out.shape[1]), n_out.ctypes.data,
+                                        C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_resample failed (|ppm| <= 50000, n0 >= 0, n_out <= the row of out)")
         return out, n_out
 
@@ -602,7 +624,7 @@ class BatchEngine:
         B = self.B
         assert x.is_cuda and x.shape[0] == B
         if x.dtype == torch.complex64:
-            assert x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] <= 1)
+            assert _is_rows(x, B, torch.complex64)
             fmt, per = RATE_C64, 1
         else:
             assert x.dtype == torch.int16 and (x.dim() == 2 or (x.dim() == 3 and x.shape[2] == 2)) and x.stride(-1) == 1
@@ -610,20 +632,15 @@ class BatchEngine:
             fmt, per = (RATE_S16_REAL, 1) if x.dim() == 2 else (RATE_S16_IQ, 2)
         N = x.shape[1]
         n0 = _per_stream(B, n0, np.int64, "n0"); in_base = _per_stream(B, in_base, np.int64, "in_base")
-        n_in = _per_stream(B, N if n_in is None else n_in, np.int32, "n_in")
-        if n_in.min() < 0 or n_in.max() > N:
-            raise ValueError(f"n_in: between 0 and the {N} samples of a row")
+        n_in = _counts(B, n_in, N, "n_in")
         if n_out is None:
             n_out = np.array([max(rate_count(int(in_base[b]) + int(n_in[b]), L, M) - int(n0[b]), 0) for b in range(B)], np.int32)
         else:
             n_out = _per_stream(B, n_out, np.int32, "n_out")
-        if out is None:
-            out = torch.zeros((B, max(int(n_out.max()), 1)), dtype=torch.complex64, device=x.device)
-        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n_out.max()
+        out = _out_rows(out, B, n_out, n_out.max(), x.device)
         p = RateParams(int(L), int(M), n0.ctypes.data, in_base.ctypes.data)
-        xs = x.stride(0) if B > 1 else N * per                 # (a one-row tensor may carry any stride in its first dimension)
-        ys = out.stride(0) if B > 1 else out.shape[1]
-        if self.lib.rade_batch_rate_convert(self.h, x.data_ptr(), xs, n_in.ctypes.data, fmt, gain, out.data_ptr(), ys, n_out.ctypes.data, C.byref(p), _stream_ptr()):
+        if self.lib.rade_batch_rate_convert(self.h, x.data_ptr(), _row_stride(x, N * per), n_in.ctypes.data, fmt, gain, out.data_ptr(), _row_stride(out, out.shape[1]),
+                                            n_out.ctypes.data, C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_rate_convert failed (L, M >= 1 with ceil(M / L) <= 8 and L T <= 16384 after reduction, a finite gain, n0 >= 0, n_out <= the row of out)")
         return out, n_out
 
@@ -635,18 +652,15 @@ class BatchEngine:
         be a multiple of 0.25 s up to 8 s: the one deviation from the script.  The call synchronises the current stream."""
         import torch
         B = self.B
-        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        assert _is_rows(x, B, torch.complex64)
         S = x.shape[1]
-        n = _per_stream(B, S if n is None else n, np.int32, "n")
-        if n.min() < 0 or n.max() > S:
-            raise ValueError(f"n: between 0 and the {S} samples of a row")
+        n = _counts(B, n, S, "n")
         q = cno_plan(window_time, flow, fhigh)
         W = max(max(cno_windows(v, q.N) for v in n), 1)
         bh = np.zeros((B, W, 2), np.float64) if bands else None
         res = (CnoResult * B)()
         p = CnoParams(float(window_time), float(flow), float(fhigh))
-        xs = x.stride(0) if B > 1 else S
-        if self.lib.rade_batch_cno_est(self.h, x.data_ptr(), xs, n.ctypes.data, C.byref(p), bh.ctypes.data if bands else None, W, C.byref(res), _stream_ptr()):
+        if self.lib.rade_batch_cno_est(self.h, x.data_ptr(), _row_stride(x, S), n.ctypes.data, C.byref(p), bh.ctypes.data if bands else None, W, C.byref(res), _stream_ptr()):
             raise RuntimeError(f"rade_batch_cno_est failed (every stream needs at least N = {q.N} samples)")
         out = list(res)
         return (out, bh) if bands else out
@@ -661,25 +675,18 @@ class BatchEngine:
         stream's n are zeros (left alone in a caller's `out`).  want_phase=False skips the read-back and the wait behind the kernels (the call still waits once, ahead of its launches, for the copy of its per-stream records and so for the work queued in front of it)."""
         import torch
         B = self.B
-        assert m.is_cuda and m.dim() == 2 and m.shape[0] == B and (m.stride(1) == 1 or m.shape[1] <= 1)
-        assert m.dtype in (torch.float32, torch.complex64)
+        assert m.dtype in (torch.float32, torch.complex64) and _is_rows(m, B, m.dtype)
         N = m.shape[1]
-        n = _per_stream(B, N if n is None else n, np.int32, "n")
-        if n.min() < 0 or n.max() > N:
-            raise ValueError(f"n: between 0 and the {N} samples of a row")
+        n = _counts(B, n, N, "n")
         ph0 = _per_stream(B, phase0, np.uint32, "phase0"); n0 = _per_stream(B, n0, np.int64, "n0")
         ph_end = np.zeros(B, np.uint32) if want_phase else None
-        if out is None:
-            out = torch.zeros((B, max(N, 1)), dtype=torch.complex64, device=m.device)
-        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1 and out.shape[1] >= n.max()
+        out = _out_rows(out, B, n, N, m.device)
         if noise is not None:
             assert noise.is_cuda and noise.dtype == torch.complex64 and noise.dim() == 2 and noise.shape[0] == B and noise.shape[1] >= n.max()
             noise = noise[:, :int(n.max())].contiguous()              # dense [B][max n]
         p = FmModParams(float(Fs), float(fc), float(fd), FM_F32 if m.dtype == torch.float32 else FM_C64, FM_OUT_REAL if real else FM_OUT_COMPLEX, float(sigma), int(seed),
                         noise.data_ptr() if noise is not None else None, ph0.ctypes.data, ph_end.ctypes.data if want_phase else None, n0.ctypes.data)
-        ms = m.stride(0) if B > 1 else N
-        ys = out.stride(0) if B > 1 else out.shape[1]
-        if self.lib.rade_batch_fm_mod(self.h, m.data_ptr(), ms, n.ctypes.data, out.data_ptr(), ys, C.byref(p), _stream_ptr()):
+        if self.lib.rade_batch_fm_mod(self.h, m.data_ptr(), _row_stride(m, N), n.ctypes.data, out.data_ptr(), _row_stride(out, out.shape[1]), C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_fm_mod failed (Fs > 0, |fc| <= Fs / 2, 0 < fd <= Fs / 2, sigma >= 0 with a seed or a noise tensor, n0 >= 0)")
         return out, ph_end
 
@@ -691,12 +698,10 @@ class BatchEngine:
         sample of absolute index n0 + i (default n0 = in_base, n_out = n_in: one output per input).  Samples past a stream's n_out are zeros."""
         import torch
         B = self.B
-        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        assert _is_rows(x, B, torch.complex64)
         N = x.shape[1]
         b1 = np.ascontiguousarray(b1, dtype=np.float32); b2 = np.ascontiguousarray(b2, dtype=np.float32)
-        n_in = _per_stream(B, N if n_in is None else n_in, np.int32, "n_in")
-        if n_in.min() < 0 or n_in.max() > N:
-            raise ValueError(f"n_in: between 0 and the {N} samples of a row")
+        n_in = _counts(B, n_in, N, "n_in")
         in_base = _per_stream(B, in_base, np.int64, "in_base")
         n0 = in_base.copy() if n0 is None else _per_stream(B, n0, np.int64, "n0")
         if n_out is None:
@@ -708,8 +713,7 @@ class BatchEngine:
         bb = torch.zeros((B, W), dtype=torch.complex64, device=x.device) if want_bb else None
         p = FmDemodParams(float(Fs), float(fc), float(fd), FM_C64 if complex_out else FM_F32, int(bool(ph_dont_limit)), b1.ctypes.data, b1.size, b2.ctypes.data, b2.size,
                           in_base.ctypes.data, n0.ctypes.data, bb.data_ptr() if want_bb else None, W)
-        xs = x.stride(0) if B > 1 else N
-        if self.lib.rade_batch_fm_demod(self.h, x.data_ptr(), xs, n_in.ctypes.data, y.data_ptr(), W, n_out.ctypes.data, C.byref(p), _stream_ptr()):
+        if self.lib.rade_batch_fm_demod(self.h, x.data_ptr(), _row_stride(x, N), n_in.ctypes.data, y.data_ptr(), W, n_out.ctypes.data, C.byref(p), _stream_ptr()):
             raise RuntimeError("rade_batch_fm_demod failed (Fs > 0, |fc| <= Fs / 2, 0 < fd <= Fs / 2, 1..512 finite taps per filter)")
         return y, bb, n_out
 
@@ -722,12 +726,9 @@ class BatchEngine:
         assert i16.is_cuda and i16.dtype == torch.int16 and i16.shape[0] == self.B and (i16.dim() == 2 or (iq and i16.dim() == 3 and i16.shape[2] == 2))
         assert i16.stride(-1) == 1 and (i16.dim() == 2 or i16.stride(1) == 2 or i16.shape[1] <= 1)
         row = i16.shape[1] if i16.dim() == 3 or not iq else i16.shape[1] // 2
-        n = _per_stream(self.B, row if n is None else n, np.int32, "n")
-        if n.min() < 0 or n.max() > row:
-            raise ValueError(f"n: between 0 and the {row} samples of a row")
+        n = _counts(self.B, n, row, "n")
         out = torch.zeros((self.B, max(int(n.max()), 1)), dtype=torch.complex64, device=i16.device)
-        ist = i16.stride(0) if self.B > 1 else row << int(iq)          # (a one-row tensor may carry any stride in its first dimension)
-        if self.lib.rade_batch_wire_in(self.h, i16.data_ptr(), ist, n.ctypes.data, WIRE_IQ if iq else WIRE_REAL, gain, out.data_ptr(), out.shape[1], _stream_ptr()):
+        if self.lib.rade_batch_wire_in(self.h, i16.data_ptr(), _row_stride(i16, row << int(iq)), n.ctypes.data, WIRE_IQ if iq else WIRE_REAL, gain, out.data_ptr(), out.shape[1], _stream_ptr()):
             raise RuntimeError("rade_batch_wire_in failed (a finite gain, rows of at least n samples)")
         return out
 
@@ -736,15 +737,12 @@ class BatchEngine:
         (real) or [B, N, 2] of I and Q, int16(x * scale) truncated toward zero, saturated to -32768 / 32767 where that does not fit, 0 for NaN.  n: samples of each stream
         (default N); the rest of a row is zeros.  meters: also returns WireMeters (the call then synchronises)."""
         import torch
-        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == self.B and (x.stride(1) == 1 or x.shape[1] <= 1)
+        assert _is_rows(x, self.B, torch.complex64)
         B, N = self.B, x.shape[1]
-        n = _per_stream(B, N if n is None else n, np.int32, "n")
-        if n.min() < 0 or n.max() > N:
-            raise ValueError(f"n: between 0 and the {N} samples of a row")
+        n = _counts(B, n, N, "n")
         out = torch.zeros((B, N) if real else (B, N, 2), dtype=torch.int16, device=x.device)
         m = np.zeros((B, 4), np.float64) if meters else None
-        xs = x.stride(0) if B > 1 else N
-        if self.lib.rade_batch_wire_out(self.h, x.data_ptr(), xs, n.ctypes.data, WIRE_REAL if real else WIRE_IQ, scale, out.data_ptr(), N if real else 2 * N,
+        if self.lib.rade_batch_wire_out(self.h, x.data_ptr(), _row_stride(x, N), n.ctypes.data, WIRE_REAL if real else WIRE_IQ, scale, out.data_ptr(), N if real else 2 * N,
                                         m.ctypes.data if meters else None, _stream_ptr()):
             raise RuntimeError("rade_batch_wire_out failed (a finite scale, rows of at least n samples)")
         if not meters:
@@ -936,8 +934,7 @@ class BatchEngine:
             assert z_ref.is_cuda and z_ref.dtype == torch.float32 and z_ref.is_contiguous() and tuple(z_ref.shape) == (self.B, n_mf * 3, 80)
             n_err = np.zeros(self.B, np.int64)     # C long
             p.z_ref_dev = z_ref.data_ptr(); p.n_errors_host = n_err.ctypes.data
-        stride = rx.stride(0) if self.B > 1 else rx.shape[1]       # (a one-row tensor may carry any stride in its first dimension, e.g. 0 from numpy's [None])
-        r = self.lib.rade_batch_rx_ideal(self.h, rx.data_ptr(), stride, n_mf, C.byref(p), z_hat.data_ptr(), feats.data_ptr() if feats is not None else None,
+        r = self.lib.rade_batch_rx_ideal(self.h, rx.data_ptr(), _row_stride(rx, rx.shape[1]), n_mf, C.byref(p), z_hat.data_ptr(), feats.data_ptr() if feats is not None else None,
                                          _stream_ptr())
         if r != n_mf:
             raise RuntimeError("rade_batch_rx_ideal failed (n_mf >= 2, time_offset in [-32, 0], 3 n_mf <= 3 max_tx_mf with decode)")
@@ -984,7 +981,28 @@ class BatchEngine:
         return d
 
 
-class ClockOffset:
+class _TailCarry:
+    """What a stateless stage needs to be applied to streams that arrive in pieces (every stream gets pieces of the same length): per stream the last `hist` input samples
+    stay on the device, in the format they arrive in.  self.tail = input samples [n_fed - hist, n_fed), zeros ahead of the stream (made from the first piece unless the
+    stage made it); self.n_fed = input samples taken so far.  A piece is joined to the tail and handed to the stage's _emit(buf, in_end) with in_end = n_fed - lag, the
+    "complete up to" rule: an output is emitted once the input sample `lag` past its position has arrived."""
+
+    def _carry(self, hist: int, lag: int, tail=None):
+        self.hist, self.lag, self.tail, self.n_fed = hist, lag, tail, 0
+
+    def _feed(self, x, **kw):
+        import torch
+        if self.tail is None:
+            self.tail = torch.zeros((x.shape[0], self.hist) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+        assert x.is_cuda and x.dtype == self.tail.dtype and x.shape[0] == self.eng.B and x.shape[2:] == self.tail.shape[2:]
+        buf = torch.cat([self.tail, x], dim=1)
+        out = self._emit(buf, self.n_fed + x.shape[1] - self.lag, **kw)
+        self.tail = buf[:, -self.hist:].contiguous()
+        self.n_fed += x.shape[1]
+        return out
+
+
+class ClockOffset(_TailCarry):
     """A sample-clock offset applied to streams that arrive in pieces (BatchEngine.resample is stateless: this keeps what the next piece needs).  Per stream the last 32
     input samples stay on the device; feed() emits the outputs whose whole 32-tap window has arrived, flush() the rest (their windows run into zeros, as at the end of a
     whole-stream call).  The concatenated outputs of a stream are bit-identical to one resample() call over the whole stream."""
@@ -994,8 +1012,7 @@ class ClockOffset:
         import torch
         self.eng, self.mode = engine, mode
         self.ppm = _per_stream(engine.B, ppm, np.float64, "ppm"); self.t0 = _per_stream(engine.B, t0, np.float64, "t0")
-        self.tail = torch.zeros((engine.B, self.HIST), dtype=torch.complex64, device=engine.device)      # input samples [n_fed - 32, n_fed); zeros ahead of the stream
-        self.n_fed = 0                                                # input samples taken so far (every stream gets pieces of the same length)
+        self._carry(self.HIST, 16, torch.zeros((engine.B, self.HIST), dtype=torch.complex64, device=engine.device))      # output n is complete once sample i(n) + 16 has arrived
         self.n_done = np.zeros(engine.B, np.int64)                    # outputs emitted so far
 
     def _emit(self, buf, in_end: int):
@@ -1008,20 +1025,14 @@ class ClockOffset:
 
     def feed(self, x):
         """x cuda complex64 [B, n]: the next n input samples of every stream -> (y [B, max n_out], n_out int32 [B])"""
-        import torch
-        assert x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and x.shape[0] == self.eng.B
-        buf = torch.cat([self.tail, x], dim=1)
-        y, n_out = self._emit(buf, self.n_fed + x.shape[1] - 16)      # output n is complete once sample i(n) + 16 has arrived
-        self.tail = buf[:, -self.HIST:].contiguous()
-        self.n_fed += x.shape[1]
-        return y, n_out
+        return self._feed(x)
 
     def flush(self):
         """the outputs whose position lies inside the input fed so far and whose window runs past it"""
         return self._emit(self.tail, self.n_fed)
 
 
-class RateConverter:
+class RateConverter(_TailCarry):
     """A sample-rate conversion by L / M applied to streams that arrive in pieces (BatchEngine.rate_convert is stateless: this keeps what the next piece needs).  Per stream
     the last T input samples stay on the device, in the format they arrive in; feed() emits the outputs whose whole T-tap window has arrived, flush() the rest (their
     windows run into zeros, as at the end of a whole-stream call).  The concatenated outputs of a stream are bit-identical to one rate_convert() call over the whole stream."""
@@ -1029,8 +1040,7 @@ class RateConverter:
     def __init__(self, engine: BatchEngine, L: int, M: int, gain: float = 1.0):
         self.eng, self.L, self.M, self.gain = engine, int(L), int(M), gain
         self.T = rate_taps(L, M).shape[1]
-        self.tail = None                                              # input samples [n_fed - T, n_fed); zeros ahead of the stream; made from the first piece
-        self.n_fed = 0                                                # input samples taken so far (every stream gets pieces of the same length)
+        self._carry(self.T, self.T // 2)                              # output n is complete once sample i(n) + T / 2 has arrived
         self.n_done = 0                                               # outputs emitted so far (the same for every stream: one ratio, equal pieces)
 
     def _emit(self, buf, in_end: int):
@@ -1042,15 +1052,7 @@ class RateConverter:
 
     def feed(self, x):
         """x cuda complex64 [B, n], int16 [B, n] or int16 [B, n, 2]: the next n input samples of every stream -> (y [B, max n_out], n_out int32 [B])"""
-        import torch
-        if self.tail is None:
-            self.tail = torch.zeros((x.shape[0], self.T) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
-        assert x.is_cuda and x.dtype == self.tail.dtype and x.shape[0] == self.eng.B and x.shape[2:] == self.tail.shape[2:]
-        buf = torch.cat([self.tail, x], dim=1)
-        y, n_out = self._emit(buf, self.n_fed + x.shape[1] - self.T // 2)      # output n is complete once sample i(n) + T / 2 has arrived
-        self.tail = buf[:, -self.T:].contiguous()
-        self.n_fed += x.shape[1]
-        return y, n_out
+        return self._feed(x)
 
     def flush(self):
         """the outputs whose position lies inside the input fed so far and whose window runs past it"""
@@ -1075,7 +1077,7 @@ class FmModulator:
         return tx
 
 
-class FmDemodulator:
+class FmDemodulator(_TailCarry):
     """The FM demodulator applied to streams that arrive in pieces (BatchEngine.fm_demod is stateless: this keeps what the next piece needs): the last N1 + N2 - 1 input
     samples of every stream stay on the device.  The concatenated outputs are bit-identical to one fm_demod() call over the whole stream."""
 
@@ -1083,17 +1085,13 @@ class FmDemodulator:
         self.eng, self.Fs, self.fc, self.fd, self.complex_out, self.ph_dont_limit = engine, Fs, fc, fd, complex_out, ph_dont_limit
         self.b1, self.b2 = np.ascontiguousarray(b1, dtype=np.float32), np.ascontiguousarray(b2, dtype=np.float32)
         self.H = self.b1.size + self.b2.size - 1                      # output n depends on inputs n - H .. n
-        self.tail = None                                              # input samples [n_fed - H, n_fed); zeros ahead of the stream; made from the first piece
-        self.n_fed = 0
+        self._carry(self.H, 0)                                        # and so is complete with input n: one output per input
+
+    def _emit(self, buf, in_end: int, want_bb: bool = False):
+        y, bb, _ = self.eng.fm_demod(buf, self.Fs, self.fc, self.fd, self.b1, self.b2, in_base=self.n_fed - self.H, n0=self.n_fed, n_out=in_end - self.n_fed,
+                                     complex_out=self.complex_out, ph_dont_limit=self.ph_dont_limit, want_bb=want_bb)
+        return y, bb
 
     def feed(self, x, want_bb: bool = False):
         """x cuda complex64 [B, n]: the next n samples of every stream -> (y [B, n], bb [B, n] or None)"""
-        import torch
-        if self.tail is None:
-            self.tail = torch.zeros((x.shape[0], self.H), dtype=x.dtype, device=x.device)
-        buf = torch.cat([self.tail, x], dim=1)
-        y, bb, _ = self.eng.fm_demod(buf, self.Fs, self.fc, self.fd, self.b1, self.b2, in_base=self.n_fed - self.H, n0=self.n_fed, n_out=x.shape[1],
-                                     complex_out=self.complex_out, ph_dont_limit=self.ph_dont_limit, want_bb=want_bb)
-        self.tail = buf[:, -self.H:].contiguous()
-        self.n_fed += x.shape[1]
-        return y, bb
+        return self._feed(x, want_bb=want_bb)

@@ -10,8 +10,6 @@ medians.
 
     python3 tools/time_cno.py [--streams 256] [--samples 80000] [--rounds 5] [--reps 3] [--host_streams 4] [--out FILE.json]
 """
-import argparse
-import json
 import os
 import sys
 import time
@@ -22,11 +20,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
+    import stage_timing as stg
     import torch
     from radae_amd.engine import BatchEngine, CnoParams, CnoResult, cno_plan, cno_windows
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=256); ap.add_argument("--samples", type=int, default=80000); ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3); ap.add_argument("--host_streams", type=int, default=4); ap.add_argument("--out", type=str, default="")
+    ap = stg.parser(rounds=5, reps=3)
+    ap.add_argument("--samples", type=int, default=80000); ap.add_argument("--host_streams", type=int, default=4)
     a = ap.parse_args()
     B, S = a.streams, a.samples
     dev = torch.device("cuda", 0)
@@ -45,39 +43,18 @@ def main():
     def call():
         assert lib.rade_batch_cno_est(h, x.data_ptr(), S, n.ctypes.data, p, None, 0, res, sp()) == 0
 
-    def wall(fn, reps):
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return 1e3 * (time.perf_counter() - t0) / reps
-
-    def events(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / reps
-
-    def kernels(reps):
+    def kernels(fn, reps):
         """the two launches alone, by the engine's HIP-event profiler (class `channel`)"""
         eng.profile(True)
         for _ in range(reps):
-            call()
+            fn()
         eng.profile(False)
         got = eng.profile_get()["channel"]
         return got["ms"] / max(got["launches"], 1)
 
-    copy = lambda: y.copy_(x)
-    for _ in range(2):
-        call(); copy()
-    torch.cuda.synchronize()
-    t = {"call": [], "kernels": [], "copy": []}
-    for _ in range(a.rounds):
-        t["call"].append(wall(call, a.reps))
-        t["kernels"].append(kernels(a.reps))
-        t["copy"].append(events(copy, a.reps))
+    calls = {"call": call, "kernels": call, "copy": lambda: y.copy_(x)}
+    stg.warm(calls)
+    t = stg.rounds(calls, a.rounds, a.reps, clocks={"call": stg.wall, "kernels": kernels})      # the call synchronises its stream: the host clock
 
     # (b) the reference's algorithm on one host core: np.fft.fft of every window in float64 (est_CNo.py:31-45), plus the input across the host link
     Bh = max(min(a.host_streams, B), 1)
@@ -88,19 +65,14 @@ def main():
             Rx = np.abs(np.fft.fft(xh[b, st:st + q.N])) ** 2
             np.sum(Rx[q.flow_bin:q.fhigh_bin]); np.sum(Rx[q.noise_st:q.noise_en])
     host_ms = 1e3 * (time.perf_counter() - t0) * B / Bh
-    stat = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
     out = {"streams": B, "samples": S, "windows_per_stream": n_win, "N": q.N, "J": q.J, "rounds": a.rounds, "reps": a.reps, "host_streams": Bh,
-           "ms_per_call": {k: stat(v) for k, v in t.items()}, "host_numpy_fft_ms_scaled_to_the_batch": host_ms, "input_bytes": 8 * B * S}
+           "ms_per_call": stg.stats(t), "host_numpy_fft_ms_scaled_to_the_batch": host_ms, "input_bytes": 8 * B * S}
     call_ms, k_ms, c_ms = (out["ms_per_call"][k]["median"] for k in ("call", "kernels", "copy"))
     out["call_over_copy"] = call_ms / c_ms
     out["host_over_call"] = host_ms / call_ms
     out["share_behind_the_kernels"] = max(call_ms - k_ms, 0.0) / call_ms
     out["first_result"] = {"max_st": int(res[0].max_st), "max_CNodB": float(res[0].max_CNodB)}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(line + "\n")
+    stg.emit(out, a.out)
     eng.close()
 
 

@@ -10,9 +10,7 @@ not the kernels alone.  DESIGN.md quotes the medians.
 
     python3 tools/time_fm.py [--streams 256] [--seconds 10] [--rounds 5] [--reps 3] [--host_streams 2] [--out FILE.json]
 """
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 import time
@@ -29,10 +27,10 @@ FS, FC, FD, FM_MAX = 48000.0, 12000.0, 5000.0, 3000.0
 def main():
     import torch
     import fm_ref as fr
+    import stage_timing as stg
     from radae_amd.engine import BatchEngine, FmDemodParams, FmModParams, fm_sigma, fm_taps
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=256); ap.add_argument("--seconds", type=int, default=10); ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3); ap.add_argument("--host_streams", type=int, default=2); ap.add_argument("--out", type=str, default="")
+    ap = stg.parser(rounds=5, reps=3)
+    ap.add_argument("--seconds", type=int, default=10); ap.add_argument("--host_streams", type=int, default=2)
     a = ap.parse_args()
     B, n = a.streams, int(FS) * a.seconds
     dev = torch.device("cuda", 0)
@@ -62,24 +60,10 @@ def main():
         n_copy = B * nbytes // 16                                  # the device's copy of as many bytes: 8 read + 8 written per complex64 sample
         calls["copy_" + k], by["copy_" + k] = (lambda c=n_copy: dst[:c].copy_(src[:c])), 16.0 * n_copy / B
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / reps
-
     calls["mod_noise_on"]()                                        # the demodulator's timed input: a modulated carrier with noise at 20 dB
-    for fn in calls.values():                                      # every shape of the timed windows, code objects loaded
-        for _ in range(2):
-            fn()
+    stg.warm(calls)
     calls["mod_noise_on"]()
-    torch.cuda.synchronize()
-    ts = {k: [] for k in calls}
-    for _ in range(a.rounds):
-        for k, fn in calls.items():
-            ts[k].append(timed(fn, a.reps))
+    ts = stg.rounds(calls, a.rounds, a.reps)
 
     # the host path: the float64 restatement on one core, and the copy of its result across the host link
     th = {}
@@ -95,9 +79,8 @@ def main():
         out = np.stack([fr.demod(xh[b], FS, FC, FD, b1, b2)[0] for b in range(Bh)]).astype(np.float32)
         y[:Bh].copy_(torch.from_numpy(out)); torch.cuda.synchronize()
         th["demod"] = 1e3 * (time.perf_counter() - t0) * B / Bh
-    stat = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
     res = {"streams": B, "seconds": a.seconds, "Fs": FS, "N1": int(b1.size), "N2": int(b2.size), "rounds": a.rounds, "reps": a.reps, "host_streams": Bh,
-           "ms_per_call": {k: stat(v) for k, v in ts.items()}, "host_ms_per_call_scaled_to_the_batch": th, "algorithmic_bytes_per_stream": by}
+           "ms_per_call": stg.stats(ts), "host_ms_per_call_scaled_to_the_batch": th, "algorithmic_bytes_per_stream": by}
     med = lambda k: res["ms_per_call"][k]["median"] * 1e-3
     res["TB_per_s"] = {k: by[k] * B / med(k) / 1e12 for k in by}
     flop = (4.0 * b1.size + 2.0 * b2.size) * n * B
@@ -106,11 +89,7 @@ def main():
     res["call_over_copy"] = {k: med(k) / med("copy_" + k) for k in cases}
     res["host_over_device"] = {k: th[k] / (1e3 * med(k)) for k in th}
     res["x_real_time"] = {k: B * a.seconds / med(k) for k in cases}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(line + "\n")
+    stg.emit(res, a.out)
     eng.close()
 
 

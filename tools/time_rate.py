@@ -7,8 +7,6 @@ algorithm has to move: every input sample read once, every output sample written
 
     python3 tools/time_rate.py [--streams 256] [--seconds 10] [--rounds 5] [--reps 3] [--host_streams 8] [--out FILE.json]
 """
-import argparse
-import json
 import os
 import sys
 import time
@@ -16,8 +14,6 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-HBM_TB_S = 6.3          # what a float4 copy achieves on an MI355X (8.0 is the data sheet's figure)
 
 
 def prototype(C):
@@ -30,11 +26,11 @@ def prototype(C):
 
 
 def main():
+    import stage_timing as stg
     import torch
     from radae_amd.engine import BatchEngine, RateParams, rate_count, rate_taps
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=256); ap.add_argument("--seconds", type=int, default=10); ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3); ap.add_argument("--host_streams", type=int, default=8); ap.add_argument("--out", type=str, default="")
+    ap = stg.parser(rounds=5, reps=3)
+    ap.add_argument("--seconds", type=int, default=10); ap.add_argument("--host_streams", type=int, default=8)
     a = ap.parse_args()
     B, S = a.streams, a.seconds
     dev = torch.device("cuda", 0)
@@ -69,22 +65,8 @@ def main():
         n_copy = B * nbytes // 16                                  # the device's copy of as many bytes: 8 read + 8 written per complex64 sample
         calls["copy_" + k], by["copy_" + k] = (lambda n=n_copy: flat_dst[:n].copy_(flat_src[:n])), 16.0 * n_copy / B
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / reps
-
-    for fn in calls.values():                                      # every shape of the timed windows, code objects loaded
-        for _ in range(2):
-            fn()
-    torch.cuda.synchronize()
-    t = {k: [] for k in calls}
-    for _ in range(a.rounds):
-        for k, fn in calls.items():
-            t[k].append(timed(fn, a.reps))
+    stg.warm(calls)
+    t = stg.rounds(calls, a.rounds, a.reps)
 
     # the host path: scipy's polyphase filter on one core with the same prototype, and the copy across the host link (the smaller side of the conversion stays on the
     # host side of the link: the 8 kHz result of a down-conversion goes up, the 48 kHz result of an up-conversion goes up)
@@ -107,20 +89,15 @@ def main():
             n_o = min(out.shape[1], dst.shape[1])
             dst[:Bh, :n_o].copy_(torch.from_numpy(np.ascontiguousarray(out[:, :n_o]))); torch.cuda.synchronize()
             th[k] = 1e3 * (time.perf_counter() - t0) * B / Bh
-    stat = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
     res = {"streams": B, "seconds": S, "rounds": a.rounds, "reps": a.reps, "host_streams": Bh,
-           "ms_per_call": {k: stat(v) for k, v in t.items()}, "host_ms_per_call_scaled_to_the_batch": th,
+           "ms_per_call": stg.stats(t), "host_ms_per_call_scaled_to_the_batch": th,
            "algorithmic_bytes_per_stream": by}
     res["TB_per_s"] = {k: by[k] * B / (res["ms_per_call"][k]["median"] * 1e-3) / 1e12 for k in by}
-    res["share_of_measured_hbm_copy_rate"] = {k: v / HBM_TB_S for k, v in res["TB_per_s"].items()}
+    res["share_of_measured_hbm_copy_rate"] = {k: v / stg.HBM_TB_S for k, v in res["TB_per_s"].items()}
     res["copy_over_call"] = {k: res["ms_per_call"]["copy_" + k]["median"] / res["ms_per_call"][k]["median"] for k in cases}
     res["host_over_device"] = {k: th[k] / res["ms_per_call"][k]["median"] for k in th}
     res["x_real_time"] = {k: 1e3 * B * S / res["ms_per_call"][k]["median"] for k in cases}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(line + "\n")
+    stg.emit(res, a.out)
     eng.close()
 
 

@@ -6,22 +6,18 @@ apply pass for the channel.  Operations of the sinc32 mode: 64 fused multiply-ad
 
     python3 tools/time_resample.py [--streams 256] [--samples 806400] [--ppm -2493.77] [--rounds 7] [--out FILE.json]
 """
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
+    import stage_timing as stg
     import torch
     from radae_amd.engine import BatchEngine, resample_count
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=256); ap.add_argument("--samples", type=int, default=806400); ap.add_argument("--ppm", type=float, default=-2493.77)
-    ap.add_argument("--rounds", type=int, default=7); ap.add_argument("--reps", type=int, default=10); ap.add_argument("--out", type=str, default="")
+    ap = stg.parser(rounds=7, reps=10)
+    ap.add_argument("--samples", type=int, default=806400); ap.add_argument("--ppm", type=float, default=-2493.77)
     a = ap.parse_args()
     B, N = a.streams, a.samples
     assert N % 960 == 0, "the channel call takes whole modem frames"
@@ -41,34 +37,18 @@ def main():
     def chan():
         eng.channel(x, 0.0, 0.0, seed=0)
 
-    def timed(fn, n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / n
-
-    for fn in (sinc, lin, chan):                              # every shape of the timed windows, code objects loaded
-        for _ in range(2):
-            fn()
-    torch.cuda.synchronize()
-    t = {"sinc32": [], "linear": [], "channel": []}
-    for _ in range(a.rounds):
-        t["sinc32"].append(timed(sinc, a.reps)); t["linear"].append(timed(lin, a.reps)); t["channel"].append(timed(chan, a.reps))
+    calls = {"sinc32": sinc, "linear": lin, "channel": chan}
+    stg.warm(calls)
+    t = stg.rounds(calls, a.rounds, a.reps)
     by = {"sinc32": 16.0 * B * n_out, "linear": 16.0 * B * n_out, "channel": 24.0 * B * N}
     res = {"streams": B, "samples_in": N, "samples_out": n_out, "ppm": a.ppm, "rounds": a.rounds, "reps": a.reps,
-           "ms_per_call": {k: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))} for k, v in t.items()},
+           "ms_per_call": stg.stats(t),
            "algorithmic_bytes": by, "algorithmic_flops_sinc32": 2.0 * 128 * B * n_out,
            "calls": {"sinc32": "rade_batch_resample, RADE_RESAMPLE_SINC32", "linear": "rade_batch_resample, RADE_RESAMPLE_LINEAR",
                      "channel": "rade_batch_channel without G, sigma 0, seed 0 (k_chan_power + k_chan_gain + k_chan_apply)"}}
     res["TB_per_s"] = {k: by[k] / (res["ms_per_call"][k]["median"] * 1e-3) / 1e12 for k in by}
     res["sinc32_TFLOP_per_s"] = res["algorithmic_flops_sinc32"] / (res["ms_per_call"]["sinc32"]["median"] * 1e-3) / 1e12
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(line + "\n")
+    stg.emit(res, a.out)
     eng.close()
 
 

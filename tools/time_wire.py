@@ -7,8 +7,6 @@ I also hold Q) + 2 written, IQ out 8 + 4.  DESIGN.md quotes the medians.
 
     python3 tools/time_wire.py [--streams 256] [--samples 806400] [--rounds 10] [--reps 5] [--host_reps 2] [--out FILE.json]
 """
-import argparse
-import json
 import os
 import sys
 import time
@@ -17,16 +15,14 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-HBM_TB_S = 6.3          # what a float4 copy achieves on an MI355X (8.0 is the data sheet's figure)
-
 
 def main():
+    import stage_timing as stg
     import torch
     from radae_amd import wire
     from radae_amd.engine import BatchEngine
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=256); ap.add_argument("--samples", type=int, default=806400); ap.add_argument("--rounds", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5); ap.add_argument("--host_reps", type=int, default=2); ap.add_argument("--out", type=str, default="")
+    ap = stg.parser(rounds=10, reps=5)
+    ap.add_argument("--samples", type=int, default=806400); ap.add_argument("--host_reps", type=int, default=2)
     a = ap.parse_args()
     B, N = a.streams, a.samples
     dev = torch.device("cuda", 0)
@@ -53,22 +49,8 @@ def main():
              "out_real_meters": lambda: w_out(0, True), "out_iq_meters": lambda: w_out(1, True), "copy_c64": copy}
     by = {"in_real": 10.0, "in_iq": 12.0, "out_real": 10.0, "out_iq": 12.0, "out_real_meters": 10.0, "out_iq_meters": 12.0, "copy_c64": 16.0}
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / reps
-
-    for fn in calls.values():                                  # every shape of the timed windows, code objects loaded
-        for _ in range(2):
-            fn()
-    torch.cuda.synchronize()
-    t = {k: [] for k in calls}
-    for _ in range(a.rounds):
-        for k, fn in calls.items():
-            t[k].append(timed(fn, a.reps))
+    stg.warm(calls)
+    t = stg.rounds(calls, a.rounds, a.reps)
 
     # the host path at the same commit (one core, as a service's feeding thread has it)
     s_host = i16.cpu().numpy()
@@ -85,18 +67,13 @@ def main():
             wire.f32_to_int16(x.cpu().numpy().tobytes(), 8192.0, real=mode == 0)
             th[key].append(1e3 * (time.perf_counter() - t0))
     del s_host
-    stat = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
     res = {"streams": B, "samples": N, "rounds": a.rounds, "reps": a.reps, "host_reps": a.host_reps,
-           "ms_per_call": {k: stat(v) for k, v in t.items()}, "host_ms_per_call": {k: stat(v) for k, v in th.items()},
+           "ms_per_call": stg.stats(t), "host_ms_per_call": stg.stats(th),
            "algorithmic_bytes_per_sample": by}
     res["TB_per_s"] = {k: by[k] * B * N / (res["ms_per_call"][k]["median"] * 1e-3) / 1e12 for k in by}
-    res["share_of_measured_hbm_copy_rate"] = {k: v / HBM_TB_S for k, v in res["TB_per_s"].items()}
+    res["share_of_measured_hbm_copy_rate"] = {k: v / stg.HBM_TB_S for k, v in res["TB_per_s"].items()}
     res["host_over_device"] = {k: res["host_ms_per_call"]["host_" + k]["median"] / res["ms_per_call"][k]["median"] for k in ("in_real", "in_iq", "out_real", "out_iq")}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(line + "\n")
+    stg.emit(res, a.out)
     eng.close()
 
 
