@@ -30,6 +30,8 @@
  *   rade_batch_fm_demod    fm.m:97-126 (analog_fm_demod): mix, input filter, discriminator, output filter (de-emphasis folded into it)
  *   rade_batch_cno_est     est_CNo.py:23-73 as ota_test.sh:136-148 (process_rx) runs it over the first 10 s of every stored off-air file: the C/No of the 400-2000 Hz chirp
  *                          header and the time at which it starts; rade_chirp: chirp.py:50-65, the header itself
+ *   rade_batch_specgram    plot_specgram.m:6-16 as ota_test.sh:130-134 and evaluate.sh:112, :153 draw it: the spectrogram of every recording, |X| of a 1280-sample Hann
+ *                          window every 160 samples, normalised by the recording's maximum, as 256 grey levels
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -126,6 +128,8 @@ int rade_batch_n_streams(const rade_batch *h);
  *                                           and p->bb_out_dev (complex64; bb_stride >= n_out, checked): n_out[b] samples of row b are written, one element at a time
  *   rade_batch_cno_est                      x_dev (complex64; x_stride >= every n, checked) in, read inside the n[b] samples of row b only and never written; the results go to
  *                                           host memory
+ *   rade_batch_specgram                     x_dev (complex64 or int16; x_stride >= every n, checked) in, read inside the n[b] samples of row b only; img_dev (bytes; img_stride
+ *                                           >= n_slices n_bins, checked; any alignment) and mag_dev (float; mag_stride >= 1023 n_slices, checked): a stream's own rows only
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -489,6 +493,79 @@ int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const in
                        double *bands_host /* [B][max_windows][2] = (C+N, band sum of No) or NULL */, int max_windows,
                        rade_cno_result *result_host /* [B] */, void *stream);
 int rade_chirp(float *iq_out /* [nsam][2] */, int nsam, double flow, double fhigh, double amp);
+
+/* ---- the spectrogram of a recording: plot_specgram.m on the device, every stream in one call (rade_spec.hip) ------------------------------------------------
+ * ota_test.sh:130-134 draws plot_specgram(s, 8000, 200, 3000) of every stored off-air file, evaluate.sh:112, :153 (utils.sh:66-68) plot_specgram(rx, 8000, 0, 3000).  With
+ * Fs = 8000 (plot_specgram.m:6-16): step = 160 (20 ms; the comment there says 5), window = 1280, fftn = 2048, S = abs(specgram(x, 2048, 8000, 1280, 1120)(2:1024, :)),
+ * S / max(S(:)), clipped to [10^(-20/10), 10^(-3/10)], shown as imagesc(log(S)).
+ * RECALLED, NOT VERIFIED (the signal package's specgram.m and hanning.m were not at hand where this was written): hanning(m) = 0.5 - 0.5 cos(2 pi (1:m)' / (m + 1)), no
+ *   zero end points; specgram turns a scalar window into hanning(window), starts its slices at the one-based offsets 1 : step : length(x) - window, multiplies each by the
+ *   window, zero-pads to the transform and returns rows 1 : n / 2 (bins 0..1023); length(x) <= window is an error.
+ * Geometry: win 1280, step 160, nfft 2048.  DEVIATION: plot_specgram takes any Fs; only the 8 kHz geometry is built.
+ * Slices: starts s = 0, 160, .. while s < n - 1280 (np.arange(0, n - 1280, 160)): n = 1281 .. 1440 one slice, 1441 two (rade_specgram_slices).
+ * Display band: k0 = max(1, ceil(fmin 2048 / 8000)), k1 = min(1023, floor(fmax 2048 / 8000)), n_bins = k1 - k0 + 1 (0-3000 Hz: 1..768; 200-3000 Hz: 52..768).  The band
+ *   only crops the image: the maximum is taken over bins 1..1023 of every slice, as the script takes it.
+ * Window: w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 1281), host, double, rounded once to float32, kept in the engine's device memory (rade_specgram_window).
+ * Operand: v[i] = x.re w[i], one rounded float32 multiply.  The imaginary part of a complex64 input is not read.  Int16 input is gain (float)s first, the rule of
+ *   rade_batch_wire_in: the fused call equals wire_in followed by the complex64 call, bit for bit.
+ * Transform: X_s[k] = sum_{i < 1280} v[i] e^{-2 pi i k i / 2048}, k = 1..1023.  How the device forms it (t[m] = e^{-2 pi i m / 2048}: ONE table of 2048 complex64, host,
+ *   double, rounded once per component):
+ *     z[i] = (v_a[i], v_b[i]) for i < 1280, 0 behind         slices a = 2 m and b = 2 m + 1 of ONE stream are the two parts of one complex transform; a last slice
+ *                                                            without a partner has v_b = +0
+ *     five radix-4 stages, s = 1, 4, 16, 64, 256; butterfly t = q + s p (q < s, t < 512) of a stage reads a_j = y[t + 512 j], j = 0..3 (stage 1: y = z), and writes
+ *       y'[q + s (4 p + m)] = b_m t[m p s], m = 0..3 (m = 0: b_0 itself, no product), where
+ *       e = a_0 + a_2, f = a_1 + a_3, g = a_0 - a_2, d = a_1 - a_3;  b_0 = e + f, b_2 = e - f, b_1 = g - i d = (g.re + d.im, g.im - d.re), b_3 = g + i d = (g.re - d.im, g.im + d.re)
+ *       and a product y w = (fma(-y.im, w.im, y.re w.re), fma(y.im, w.re, y.re w.im)): one rounded multiply and one fused multiply-add per component
+ *     the radix-2 stage: Z[k] = y[k] + y[k + 1024], Z[2048 - k] = y[1024 - k] - y[2048 - k]
+ *     the two slices: X_a[k] = 0.5 (Z[k] + conj Z[2048 - k]): re = 0.5 (Z[k].re + Z[2048 - k].re), im = 0.5 (Z[k].im - Z[2048 - k].im)
+ *                     |X_b[k]| from 0.5 (Z[k] - conj Z[2048 - k]): re = 0.5 (Z[k].re - Z[2048 - k].re), im = 0.5 (Z[k].im + Z[2048 - k].im)     (= i X_b[k]: same modulus)
+ *     mag = sqrtf(fma(re, re, im im)): im im rounded, then one fused multiply-add, then the correctly rounded square root.
+ *   Every addition is one rounded float32 addition per component in the order written.  The zeros of the padding take part as zeros.  A slice's bits are a function of its
+ *   stream's samples, its index and whether it has a partner (n_slices odd and the slice the last) -- not of the batch size, the other streams, the strides or which
+ *   outputs were asked for.  No atomics for the values: identical calls give identical bits.
+ * Error bound, counted from these roundings (u = 2^-24; every factor has modulus 1 and a butterfly's outputs are bounded by the sum of its inputs' moduli, so the errors
+ *   of the stages add, each relative to S = sum_i |z[i]| = sum_i sqrt(v_a[i]^2 + v_b[i]^2)): the window entry u and the operand's multiply u; per radix-4 stage the two
+ *   levels of additions 2 u, the table entry u and the lone product 4 u: 7 u, five stages 35 u; the radix-2 stage u; the separating addition u; the magnitude (a product,
+ *   a fused multiply-add, a square root: relative 2.5 u) 3 u.  42 u, times 1.01 for the terms of second order and rounded up:
+ *     | mag^ - |X_s[k]| | <= 44 u S,   S <= sum_i |v_a[i]| + sum_i |v_b[i]| <= sqrt(1280) sqrt(||v_a||^2 + ||v_b||^2)
+ *   against the float64 X of the double window (tests/specgram_ref.py); barring underflow.  A worst-case bound: tests/test_specgram_gpu.py records how far below it the
+ *   device stays.
+ * Peak: peak[b] = the maximum of the float32 mag over all slices and k = 1..1023 (a maximum does not depend on the order it is taken in; the kernel folds the
+ *   workgroups' maxima with an integer atomic maximum on the bits, which order as the values do).  With peak_in_host the given values are used instead and peak_host
+ *   returns them.
+ * Levels: T[j] = lo (hi / lo)^((j - 0.5) / 255), j = 1..255, double, rounded once to float32 (rade_specgram_levels: out[j - 1]); the level of a cell is the number of j
+ *   with mag >= T[j] peak, T[j] peak one rounded float32 multiply -- no logarithm on the device.  This is what imagesc(log(min(max(S / max, lo), hi))) shows on a
+ *   256-step grey scale when both clips are reached.  The image is an exact function of (mag, peak, table).  A peak of 0 (silence; NaN in the script): every cell is
+ *   level 0 and peak_host[b] = 0.
+ *   DEVIATION: imagesc scales to the data's own minimum and maximum, and the renderer's colour map and the JPEG coding are not reproduced.
+ * Layout: img[b][s][k - k0] at img_dev + b img_stride + s n_bins + (k - k0) bytes; mag[b][s][k - 1] at mag_dev + b mag_stride + 1023 s + (k - 1) floats; rows contiguous.
+ *   n_slices_host[b] is always written.  Nothing outside a stream's n_slices n_bins bytes or n_slices 1023 floats is written and nothing outside its n_host[b] samples is
+ *   read.  img_dev may have any alignment (byte stores), mag_dev is 4-byte aligned, x_dev aligned to its element (8 bytes complex64, x_stride in samples; 2 bytes int16,
+ *   x_stride in int16).  Strides are at least the stream's own extent.
+ * Two passes, because the normaliser is a maximum over the whole recording: transform, magnitude and maximum; then the levels, for which the transforms are computed
+ *   again (rade_spec.hip says why).  With peak_in_host one pass.
+ * Refused with -1 before any launch and with nothing written: NULL h, x_dev, n_host, p, peak_host or n_slices_host; both outputs NULL while peak_in_host is given; misaligned
+ *   pointers; a negative count or one above x_stride; any n_host[b] <= 1280 (specgram raises an error); a stride shorter than the stream's output; an unknown format; a
+ *   gain, fmin, fmax, lo or hi that is not finite; fmin > fmax; k0 > k1; not 0 < lo < hi <= 1; a peak_in_host value that is negative or not finite.
+ * The call copies the counts (and the thresholds) to the device, launches, reads peak back and SYNCHRONISES `stream`, as rade_batch_cno_est does.  Any engine (the model is
+ *   not used; no encoder or receiver state is touched); the device memory (tables, counts, peaks) belongs to the engine and is sized on first use.
+ * rade_specgram_plan, _slices, _window, _levels: host only; the numbers above, -1 where the call would refuse the parameters. */
+enum { RADE_SPEC_C64 = 0, RADE_SPEC_S16_REAL = 1 };
+typedef struct {
+    double fmin, fmax;            /* Hz: the displayed band (plot_specgram's 3rd and 4th argument) */
+    double lo, hi;                /* clips on |X| / peak: 10^(-20/10), 10^(-3/10) */
+    const float *peak_in_host;    /* [B] normaliser per stream, or NULL = the stream's own maximum (the reference) */
+} rade_specgram_params;
+typedef struct { int n_bins, k0, k1, win, step, nfft; } rade_specgram_plan_t;   /* k0..k1 inclusive */
+int rade_specgram_plan(const rade_specgram_params *p, rade_specgram_plan_t *out);
+long long rade_specgram_slices(long long n);                       /* host only: slices of an n-sample stream, 0 for n <= 1280 */
+void rade_specgram_window(float *out /* [1280] */);                /* host only */
+int rade_specgram_levels(double lo, double hi, float *out /* [255] */);   /* host only */
+int rade_batch_specgram(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int format, float gain,
+                        const rade_specgram_params *p,
+                        unsigned char *img_dev, long img_stride,    /* [B][slices][n_bins] levels, img_stride in bytes per stream; or NULL */
+                        float *mag_dev, long mag_stride,            /* [B][slices][1023] |X[1..1023]|, mag_stride in floats per stream; or NULL */
+                        float *peak_host /* [B] */, int *n_slices_host /* [B] */, void *stream);
 
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the

@@ -12,6 +12,7 @@
     python -m radae_amd.cli analog_fm IN.s16 OUT.s16 CNRdB [--seed N]                                                             analog_bbfm.sh:37-43 from the 8 kHz int16 file onward
     python -m radae_amd.cli est_cno RX.f32 [--window_time S] [--flow HZ] [--fhigh HZ]                                              est_CNo.py (without --plots); the periodograms on the device
     python -m radae_amd.cli chirp OUT.f32 NSEC [--flow HZ] [--fhigh HZ] [--amp A]                                                  chirp.py (host)
+    python -m radae_amd.cli specgram IN OUT.png [--fmin HZ] [--fmax HZ]                                                            plot_specgram.m at 8 kHz: the transforms and levels on the device, a grey-scale PNG
 
 so that the reference's shell pipelines (`cat features_in.f32 | python3 radae_txe.py > rx.f32`, `cat rx.f32 | python3 radae_rxe.py > features_out.f32`: CMakeLists.txt:300-420) run with
 `python3 -m radae_amd.cli txe|rxe` in their place; `--fs 48000` (or 44100, ..) takes the place of the `sox .. -r 8000` stage of the off-air pipelines (radae_rx.sh:33,39): the
@@ -562,10 +563,43 @@ def _chirp(argv):
     return 0
 
 
+def _specgram(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli specgram", description="Spectrogram of an 8 kHz recording (plot_specgram.m: 160 ms Hann window every 20 ms, normalised by "
+                                 "the recording's maximum, clipped 20 dB and 3 dB below it) as a grey-scale PNG, time to the right and frequency upward; the transforms and "
+                                 "the 256 levels run on the device (rade_batch_specgram).  No axes, colour map or JPEG")
+    ap.add_argument("input", type=str, help="raw int16 mono (.s16 / .raw, what load_raw reads), ..IQIQ.. .f32 (the real part is drawn) or a 16-bit mono .wav (read through the "
+                    "wave module; load_raw would plot its 44 header bytes as 22 samples)")
+    ap.add_argument("png", type=str, help="path to the output .png")
+    ap.add_argument("--fmin", type=float, default=0.0, help="lower edge of the displayed band (default 0 Hz)")
+    ap.add_argument("--fmax", type=float, default=3000.0, help="upper edge of the displayed band (default 3000 Hz)")
+    args = ap.parse_args(argv)
+    import torch
+    from . import engine, ota
+    name = args.input.lower()
+    if name.endswith(".wav"):
+        import wave
+        with wave.open(args.input, "rb") as wf:
+            if wf.getsampwidth() != 2 or wf.getnchannels() != 1 or wf.getframerate() != engine.CNO_FS:
+                raise SystemExit("radae_amd.cli specgram: a .wav must be 16-bit mono at 8000 Hz")
+            x = np.frombuffer(wf.readframes(wf.getnframes()), dtype="<i2").astype(np.int16)
+    elif name.endswith(".f32"):
+        x = np.fromfile(args.input, dtype=np.csingle)
+    else:
+        x = np.fromfile(args.input, dtype=np.int16)
+    if len(x) <= engine.SPEC_WIN:
+        raise SystemExit(f"radae_amd.cli specgram: {len(x)} samples; more than {engine.SPEC_WIN} are needed (specgram raises an error)")
+    eng = engine.BatchEngine(1, max_tx_mf=1)
+    img, ns, peak = eng.specgram(torch.tensor(x[None], device="cuda"), fmin=args.fmin, fmax=args.fmax)
+    ota.write_png(args.png, img[0], ns[0])
+    eng.close()
+    print(f"{int(ns[0])} slices x {img.shape[2]} bins, peak {float(peak[0]):.6g}", file=sys.stderr)
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm,
-            "est_cno": _est_cno, "chirp": _chirp}
+            "est_cno": _est_cno, "chirp": _chirp, "specgram": _specgram}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2

@@ -323,6 +323,26 @@ typedef struct {
 } rd_cno_args;
 int rd_launch_cno(const rd_cno_args *a, rd_stream_t s);
 
+/* the spectrogram of rade_batch_specgram (rade_spec.hip; include/rade_batch.h states the arithmetic): k_specgram, one workgroup per (run of RD_SPEC_RUN consecutive
+ * slices, stream).  A launch does what its three flags say: mag != NULL writes |X[1..1023]|, do_max folds them into peak[b] (cleared by the caller; not together with
+ * img), img != NULL writes the levels of bins k0..k1 against peak[b]. */
+#define RD_SPEC_WIN 1280
+#define RD_SPEC_STEP 160
+#define RD_SPEC_NFFT 2048
+#define RD_SPEC_RUN 8
+enum { RD_SPEC_C64 = 0, RD_SPEC_S16 = 1 };                      /* RADE_SPEC_C64 / RADE_SPEC_S16_REAL */
+typedef struct {
+    const void *x; long x_stride;                               /* complex64 or int16, stream b at + b * x_stride elements of the buffer */
+    const int *n;                                               /* device [B] sample counts */
+    const float *tw, *win, *lev;                                /* device: e^{-2 pi i m / 2048} [2048][2], the window [1280], the thresholds T[1..255] */
+    float *peak;                                                /* device [B] */
+    unsigned char *img; long img_stride;                        /* [B][slices][k1 - k0 + 1] or NULL; bytes per stream */
+    float *mag; long mag_stride;                                /* [B][slices][1023] or NULL; floats per stream */
+    float gain;                                                 /* of the int16 format */
+    int fmt, k0, k1, do_max, B, max_slices;                     /* max_slices: the most slices any stream of the call has */
+} rd_spec_args;
+int rd_launch_specgram(const rd_spec_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

@@ -881,3 +881,42 @@ int rade_chirp(float *iq_out, int nsam, double flow, double fhigh, double amp)
     }
     return 0;
 }
+
+/* ---------------------------------------------------------------------------------------------
+ * 8. the spectrogram of plot_specgram.m (include/rade_batch.h: rade_batch_specgram; rade_spec.hip): the display band, the slice count, the window, the thresholds
+ * -------------------------------------------------------------------------------------------*/
+/* k0 = max(1, ceil(fmin 2048 / 8000)), k1 = min(1023, floor(fmax 2048 / 8000)); -1 where rade_batch_specgram refuses the parameters */
+int rade_specgram_plan(const rade_specgram_params *p, rade_specgram_plan_t *out)
+{
+    if (!p || !out) return -1;
+    if (!isfinite(p->fmin) || !isfinite(p->fmax) || !isfinite(p->lo) || !isfinite(p->hi)) return -1;
+    if (p->fmin > p->fmax || !(0.0 < p->lo && p->lo < p->hi && p->hi <= 1.0)) return -1;
+    const double half = RD_SPEC_NFFT / 2;
+    double c0 = ceil(p->fmin * RD_SPEC_NFFT / 8000.0), c1 = floor(p->fmax * RD_SPEC_NFFT / 8000.0);
+    if (c0 < 1.0) c0 = 1.0;
+    if (c1 > half - 1.0) c1 = half - 1.0;
+    if (c0 > c1) return -1;
+    rade_specgram_plan_t q = { (int)c1 - (int)c0 + 1, (int)c0, (int)c1, RD_SPEC_WIN, RD_SPEC_STEP, RD_SPEC_NFFT };
+    *out = q;
+    return 0;
+}
+
+/* len(1 : 160 : n - 1280): starts 0, 160, .. while start < n - 1280 */
+long long rade_specgram_slices(long long n)
+{
+    return n > RD_SPEC_WIN ? (n - RD_SPEC_WIN + RD_SPEC_STEP - 1) / RD_SPEC_STEP : 0;
+}
+
+/* hanning(1280): 0.5 - 0.5 cos(2 pi (i + 1) / 1281) in double, rounded once */
+void rade_specgram_window(float *out /* [1280] */)
+{
+    for (int i = 0; i < RD_SPEC_WIN; i++) out[i] = (float)(0.5 - 0.5 * cos(2.0 * PI_D * (double)(i + 1) / (double)(RD_SPEC_WIN + 1)));
+}
+
+/* T[j] = lo (hi / lo)^((j - 0.5) / 255), j = 1..255 -> out[j - 1]: double, rounded once */
+int rade_specgram_levels(double lo, double hi, float *out /* [255] */)
+{
+    if (!out || !isfinite(lo) || !isfinite(hi) || !(0.0 < lo && lo < hi && hi <= 1.0)) return -1;
+    for (int j = 1; j <= 255; j++) out[j - 1] = (float)(lo * pow(hi / lo, ((double)j - 0.5) / 255.0));
+    return 0;
+}

@@ -1,6 +1,6 @@
 /*
  * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
- * rate converter, analog FM and the chirp header's C/No.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * rate converter, analog FM, the chirp header's C/No and the spectrogram.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
  * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
  * its device and pinned memory is on the engine's own list (rade_engine.h).
  *
@@ -86,6 +86,9 @@ struct rd_stages {
     /* rade_batch_cno_est: the table e^{-2 pi i m / N}, key = the window length N; the [B] sample counts; [B][cno_cap][RD_CNO_JMAX][2] partial and [B][cno_bands_cap][2]
      * band sums, grown with the call */
     rd_table cno_tw; rd_pair cno_n; double *cno_part, *cno_bands; long cno_cap, cno_bands_cap;
+    /* rade_batch_specgram: the table e^{-2 pi i m / 2048} and the window behind it (made once); per call [B] counts, [255] thresholds and [B] given peaks in one
+     * record; the [B] peaks */
+    float *spec_tab; rd_pair spec_rec; float *spec_peak;
 };
 static struct rd_stages *stages_of(rade_batch *h)
 {
@@ -453,6 +456,73 @@ int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const in
         const double *bands = nw ? bands_all + (size_t)b * max_win * 2 : NULL;
         rd_cno_finish(&q, p, bands, nw, &result_host[b]);
         if (bands_host && nw) memcpy(bands_host + (size_t)b * max_windows * 2, bands, sizeof(double) * 2 * nw);
+    }
+    return 0;
+}
+
+/* ---- the spectrogram: plot_specgram.m over every stream (rade_spec.hip; the band, the window and the thresholds: rade_host.c) ------------------------------ */
+int rade_batch_specgram(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int format, float gain, const rade_specgram_params *p,
+                        unsigned char *img_dev, long img_stride, float *mag_dev, long mag_stride, float *peak_host, int *n_slices_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || !p || !peak_host || !n_slices_host) return -1;
+    if (format != RADE_SPEC_C64 && format != RADE_SPEC_S16_REAL) return -1;
+    if (((uintptr_t)x_dev & (format == RADE_SPEC_C64 ? 7 : 1)) || ((uintptr_t)mag_dev & 3) || !isfinite(gain)) return -1;
+    if (p->peak_in_host && !img_dev && !mag_dev) return -1;               /* nothing is left to compute */
+    rade_specgram_plan_t q;
+    if (rade_specgram_plan(p, &q)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    long long max_sl = 0, pairs = 0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride || n <= RD_SPEC_WIN) return -1;
+        const long long ns = rade_specgram_slices(n);
+        if ((img_dev && ns * q.n_bins > img_stride) || (mag_dev && ns * (RD_SPEC_NFFT / 2 - 1) > mag_stride)) return -1;
+        if (p->peak_in_host && !(p->peak_in_host[b] >= 0.0f && isfinite(p->peak_in_host[b]))) return -1;
+        if (ns > max_sl) max_sl = ns;
+        pairs += (ns + 1) / 2;
+    }
+    struct rd_stages *s = stages_of(h);
+    if (!s) return -1;
+    const size_t tab_floats = 2 * RD_SPEC_NFFT + RD_SPEC_WIN, rec_bytes = sizeof(int) * B + sizeof(float) * (256 + B);
+    if (!s->spec_tab) {
+        float *t = malloc(sizeof(float) * tab_floats);
+        if (t) { rd_cno_table(RD_SPEC_NFFT, t); rade_specgram_window(t + 2 * RD_SPEC_NFFT); s->spec_tab = dev_upload_opt(h, t, sizeof(float) * tab_floats); }
+        free(t);
+        if (!s->spec_tab) return -1;
+    }
+    int *rec = pair_host(h, &s->spec_rec, rec_bytes);                    /* [B] counts, [256] thresholds (255 used), [B] given peaks */
+    if (!rec || dev_grow(h, &s->spec_peak, NULL, B, sizeof(float), 1)) return -1;
+    float *lev = (float *)(rec + B), *pin = lev + 256;
+    memcpy(rec, n_host, sizeof(int) * B);
+    lev[255] = 0.0f;
+    if (rade_specgram_levels(p->lo, p->hi, lev)) return -1;
+    for (int b = 0; b < B; b++) pin[b] = p->peak_in_host ? p->peak_in_host[b] : 0.0f;
+    if (pair_push(h, &s->spec_rec, rec_bytes, 0, st)) return -1;         /* not waited for here: the call waits at its end */
+    rd_spec_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.n = s->spec_rec.dev; a.tw = s->spec_tab; a.win = s->spec_tab + 2 * RD_SPEC_NFFT; a.lev = (const float *)((const int *)s->spec_rec.dev + B);
+    a.gain = gain; a.fmt = format; a.k0 = q.k0; a.k1 = q.k1; a.B = B; a.max_slices = (int)max_sl;
+    a.img_stride = img_stride; a.mag_stride = mag_stride;
+    const double work = 10.0 * RD_SPEC_NFFT * 11;                        /* of a pair's transform: 5 N log2 N, the textbook count */
+    int e = 0, passes = 0;
+    PROF_BEGIN(h, stream);
+    if (p->peak_in_host) {                                                /* one pass against the given peaks */
+        a.peak = (float *)a.lev + 256; a.img = img_dev; a.mag = mag_dev;
+        e = rd_launch_specgram(&a, stream); passes = 1;
+    } else {
+        a.peak = s->spec_peak; a.mag = mag_dev; a.do_max = 1;             /* pass 1: magnitudes and the maximum */
+        e = hipMemsetAsync(s->spec_peak, 0, sizeof(float) * B, st) != hipSuccess || rd_launch_specgram(&a, stream); passes = 1;
+        if (!e && img_dev) { a.mag = NULL; a.do_max = 0; a.img = img_dev; e = rd_launch_specgram(&a, stream); passes = 2; }     /* pass 2: the levels */
+    }
+    PROF_END(h, stream, RADE_PROF_CHAN, work * pairs * passes);
+    /* the peaks come back and the stream is waited for (also where a launch failed: the staging copy above is then free again) */
+    const float *pk = NULL;
+    if (e || (!p->peak_in_host && !(pk = read_back(h, s->spec_peak, sizeof(float) * B, st))) || (p->peak_in_host && settle(st))) { settle(st); return -1; }
+    for (int b = 0; b < B; b++) {
+        peak_host[b] = p->peak_in_host ? p->peak_in_host[b] : pk[b];
+        n_slices_host[b] = (int)rade_specgram_slices(n_host[b]);
     }
     return 0;
 }

@@ -71,6 +71,14 @@ class CnoResult(C.Structure):
     _fields_ = [("n_windows", C.c_int), ("n_positive", C.c_int), ("max_st", C.c_longlong), ("max_CNodB", C.c_double), ("max_SNRdB", C.c_double)]
 
 
+class SpecgramParams(C.Structure):
+    _fields_ = [("fmin", C.c_double), ("fmax", C.c_double), ("lo", C.c_double), ("hi", C.c_double), ("peak_in_host", C.c_void_p)]
+
+
+class SpecgramPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_bins", "k0", "k1", "win", "step", "nfft")]
+
+
 class RxStatus(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("consumed", "n_calls", "n_valid", "has_eoo", "nin", "sync", "snr_dB", "state")]
 
@@ -156,6 +164,12 @@ def load_library() -> C.CDLL:
         L.rade_batch_cno_est.argtypes = [vp, vp, C.c_long, vp, C.POINTER(CnoParams), vp, C.c_int, vp, vp]
         L.rade_cno_plan.argtypes = [C.POINTER(CnoParams), C.POINTER(CnoPlan)]
         L.rade_chirp.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
+    if hasattr(L, "rade_batch_specgram"):         # (absent from older A/B builds loaded through $RADE_LIBRADEHIP)
+        L.rade_batch_specgram.argtypes = [vp, vp, C.c_long, vp, C.c_int, C.c_float, C.POINTER(SpecgramParams), vp, C.c_long, vp, C.c_long, vp, vp, vp]
+        L.rade_specgram_plan.argtypes = [C.POINTER(SpecgramParams), C.POINTER(SpecgramPlan)]
+        L.rade_specgram_slices.restype = C.c_longlong; L.rade_specgram_slices.argtypes = [C.c_longlong]
+        L.rade_specgram_window.restype = None; L.rade_specgram_window.argtypes = [vp]
+        L.rade_specgram_levels.argtypes = [C.c_double, C.c_double, vp]
     _lib = L
     return L
 
@@ -181,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "rade_batch_rate_convert", "rade_rate_count", "rade_rate_taps",
     "rade_batch_fm_mod", "rade_batch_fm_demod", "rade_fm_sigma", "rade_fm_deemph_len", "rade_fm_taps",
     "rade_batch_cno_est", "rade_cno_plan", "rade_chirp",
+    "rade_batch_specgram", "rade_specgram_plan", "rade_specgram_slices", "rade_specgram_window", "rade_specgram_levels",
 ]
 WIRE_REAL, WIRE_IQ = 0, 1                                                          # rade_batch_wire_in / _out mode
 
@@ -305,6 +320,39 @@ def chirp(nsec: float, flow: float = 400.0, fhigh: float = 2000.0, amp: float = 
     if load_library().rade_chirp(x.ctypes.data, x.size, float(flow), float(fhigh), float(amp)):
         raise ValueError(f"rade_chirp refuses flow {flow!r}, fhigh {fhigh!r}, amp {amp!r} (finite values)")
     return x
+
+
+SPEC_C64, SPEC_S16_REAL = 0, 1                                                     # rade_batch_specgram format
+SPEC_WIN, SPEC_STEP, SPEC_NFFT = 1280, 160, 2048                                   # plot_specgram.m:6-10 at Fs = 8000
+SPEC_LO, SPEC_HI = 10.0 ** (-20 / 10), 10.0 ** (-3 / 10)                           # plot_specgram.m:13-14
+
+
+def specgram_plan(fmin: float = 0.0, fmax: float = 3000.0, lo: float = SPEC_LO, hi: float = SPEC_HI) -> SpecgramPlan:
+    """rade_specgram_plan: the display band k0..k1 (inclusive) of a 2048-point transform at 8 kHz, n_bins = k1 - k0 + 1, and the fixed geometry (host only)."""
+    q = SpecgramPlan()
+    if load_library().rade_specgram_plan(C.byref(SpecgramParams(float(fmin), float(fmax), float(lo), float(hi), None)), C.byref(q)):
+        raise ValueError(f"rade_specgram_plan refuses fmin {fmin!r}, fmax {fmax!r}, lo {lo!r}, hi {hi!r} (finite, fmin <= fmax with a bin of 1..1023 between them, 0 < lo < hi <= 1)")
+    return q
+
+
+def specgram_slices(n: int) -> int:
+    """rade_specgram_slices: len(np.arange(0, n - 1280, 160)), the slices specgram makes of n samples"""
+    return int(load_library().rade_specgram_slices(int(n)))
+
+
+def specgram_window() -> np.ndarray:
+    """rade_specgram_window: hanning(1280) = 0.5 - 0.5 cos(2 pi (i + 1) / 1281) as float32 (host only)"""
+    w = np.zeros(SPEC_WIN, np.float32)
+    load_library().rade_specgram_window(w.ctypes.data)
+    return w
+
+
+def specgram_levels(lo: float = SPEC_LO, hi: float = SPEC_HI) -> np.ndarray:
+    """rade_specgram_levels: the 255 thresholds T[j] = lo (hi / lo)^((j - 0.5) / 255), j = 1..255, as float32 (host only)"""
+    t = np.zeros(255, np.float32)
+    if load_library().rade_specgram_levels(float(lo), float(hi), t.ctypes.data):
+        raise ValueError(f"rade_specgram_levels refuses lo {lo!r}, hi {hi!r} (0 < lo < hi <= 1)")
+    return t
 
 
 def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
@@ -664,6 +712,33 @@ class BatchEngine:
             raise RuntimeError(f"rade_batch_cno_est failed (every stream needs at least N = {q.N} samples)")
         out = list(res)
         return (out, bh) if bands else out
+
+    # ---- the spectrogram ------------------------------------------------------------------------
+    def specgram(self, x, n=None, fmin: float = 0.0, fmax: float = 3000.0, lo: float = SPEC_LO, hi: float = SPEC_HI, peak=None, mag: bool = False, fmt=None,
+                 gain: float = 1.0, img: bool = True):
+        """plot_specgram.m over every stream (rade_batch_specgram).  x: cuda complex64 [B, S] at 8 kHz (the real part is used) or int16 [B, S] (scaled by `gain` as wire_in
+        does); n: samples of each stream (a scalar or B values, default S), each above 1280.  Returns (img, n_slices, peak[, mag]): img uint8 [B, W, n_bins], the levels
+        0..255 of bins k0..k1 (specgram_plan(fmin, fmax)) of every slice, W = the most slices any stream has, zeros past a stream's own (None with img=False); n_slices
+        int32 [B]; peak float32 [B], each stream's largest |X| over bins 1..1023 -- or the values given as `peak` (a scalar or B values), which then normalise the image;
+        with mag=True also float32 [B, W, 1023], |X[1..1023]|.  fmt: SPEC_C64 / SPEC_S16_REAL, default by x's dtype.  The call synchronises the current stream."""
+        import torch
+        B = self.B
+        if fmt is None:
+            fmt = SPEC_S16_REAL if x.dtype == torch.int16 else SPEC_C64
+        assert _is_rows(x, B, torch.int16 if fmt == SPEC_S16_REAL else torch.complex64)
+        S = x.shape[1]
+        n = _counts(B, n, S, "n")
+        q = specgram_plan(fmin, fmax, lo, hi)
+        W = max(max(specgram_slices(v) for v in n), 1)
+        im = torch.zeros((B, W, q.n_bins), dtype=torch.uint8, device=x.device) if img else None
+        mg = torch.zeros((B, W, SPEC_NFFT // 2 - 1), dtype=torch.float32, device=x.device) if mag else None
+        pin = None if peak is None else _per_stream(B, peak, np.float32, "peak")
+        pk, ns = np.zeros(B, np.float32), np.zeros(B, np.int32)
+        p = SpecgramParams(float(fmin), float(fmax), float(lo), float(hi), None if pin is None else pin.ctypes.data)
+        if self.lib.rade_batch_specgram(self.h, x.data_ptr(), _row_stride(x, S), n.ctypes.data, fmt, gain, C.byref(p), im.data_ptr() if img else None, W * q.n_bins,
+                                        mg.data_ptr() if mag else None, W * (SPEC_NFFT // 2 - 1), pk.ctypes.data, ns.ctypes.data, _stream_ptr()):
+            raise RuntimeError("rade_batch_specgram failed (every stream needs more than 1280 samples; a finite gain; given peaks finite and >= 0; an output to write)")
+        return (im, ns, pk, mg) if mag else (im, ns, pk)
 
     # ---- analog FM ----------------------------------------------------------------------------------------------------------
     def fm_mod(self, m, Fs: float, fc: float, fd: float, n=None, real: bool = False, sigma: float = 0.0, seed: int = 0, noise=None, phase0=0, n0=0, out=None,
