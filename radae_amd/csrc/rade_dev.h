@@ -163,7 +163,8 @@ int rd_launch_encf_hist(unsigned short *xf, int NQ, float *x32, long x32_sb, int
 int rd_launch_enc_pack(const float *features, float *xin, int B, int T, rd_stream_t s);
 int rd_launch_pad_rows(const float *src, float *dst, long R, int K, int Kpad, rd_stream_t s);
 int rd_launch_chan_symbol(const float *z, const float *H, const float *noise, float *out, long n_real, int mode, float p0, float p1, unsigned long long seed, rd_stream_t s);
-/* x is [B][nhist+Tcap][W]: copy time rows [T, T+nhist) (or [n_rows[b], ..)) of each stream to rows [0, nhist) */
+/* x is [B][nhist+Tcap][W]: copy time rows [T, T+nhist) (or [n_rows[b], ..)) of each stream to rows [0, nhist); a stream with n_rows[b] <= 0 is left alone.
+ * -1, and nothing launched, for nhist < 1 or nhist * W > 2048 (what a workgroup holds in registers) */
 int rd_launch_carry_rows(float *x, int B, int Tcap, int W, int nhist, int T, const int *n_rows, rd_stream_t s);
 /* z [B][n_mf*3][80] -> tx [b*stride + mf*960 ...] (transmitter_one, dsp.py:340-378); linear: the bottleneck-1 waveform (unit pilot gain, no limiter) */
 int rd_launch_ofdm_mod(const rd_tables *tab, const float *z, void *tx, long tx_stride, int B, int n_mf, int linear, rd_stream_t s);

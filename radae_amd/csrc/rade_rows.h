@@ -57,6 +57,7 @@ __global__ __launch_bounds__(256) void k_carry_rows(float *x, int Tcap, int W, i
 extern "C" int rd_launch_carry_rows(float *x, int B, int Tcap, int W, int nhist, int T, const int *n_rows, rd_stream_t s)
 {
     if (B <= 0) return 0;
+    if (nhist < 1 || (long)nhist * W > 2048) return -1;       // k_carry_rows holds the history in 8 registers x 256 threads
     hipLaunchKernelGGL(k_carry_rows, dim3(B), dim3(256), 0, (hipStream_t)s, x, Tcap, W, nhist, T, n_rows);
     return (int)hipGetLastError();
 }
