@@ -13,34 +13,16 @@ import ctypes as C
 import numpy as np
 
 from . import engine
+from .abi import RADE_FOFF_TEST, RADE_USE_C_DECODER, RADE_USE_C_ENCODER, RADE_VERBOSE_0, load_library  # noqa: F401
 
-RADE_USE_C_ENCODER, RADE_USE_C_DECODER, RADE_FOFF_TEST, RADE_VERBOSE_0 = 0x1, 0x2, 0x4, 0x8
-RADE_BATCH_TX_BPF = 0x400          # include/rade_batch.h: honoured by rade_open() too (the reference's txbpf_en)
-
-
-def _bind():
-    L = engine.load_library()
-    if getattr(L, "_rade_api_bound", False):
-        return L
-    vp = C.c_void_p
-    L.rade_open.restype = vp; L.rade_open.argtypes = [C.c_char_p, C.c_int]
-    L.rade_close.argtypes = [vp]
-    for n in ("rade_n_tx_out", "rade_n_tx_eoo_out", "rade_nin_max", "rade_n_features_in_out", "rade_n_eoo_bits", "rade_nin", "rade_sync", "rade_snrdB_3k_est"):
-        getattr(L, n).argtypes = [vp]
-    L.rade_freq_offset.restype = C.c_float; L.rade_freq_offset.argtypes = [vp]
-    L.rade_tx.argtypes = [vp, vp, vp]
-    L.rade_tx_set_eoo_bits.argtypes = [vp, vp]
-    L.rade_tx_eoo.argtypes = [vp, vp]
-    L.rade_rx.argtypes = [vp, vp, C.POINTER(C.c_int), vp, vp]
-    L._rade_api_bound = True
-    return L
+RADE_BATCH_TX_BPF = engine.TX_BPF        # include/rade_batch.h: honoured by rade_open() too (the reference's txbpf_en)
 
 
 class Rade:
     """Thin RAII wrapper of `struct rade *`."""
 
     def __init__(self, model_file: str = "", flags: int = RADE_VERBOSE_0):
-        self.L = _bind()
+        self.L = load_library()
         self.L.rade_initialize()
         self.flags = flags
         self.r = self.L.rade_open(model_file.encode(), flags)

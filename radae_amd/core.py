@@ -7,34 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import DEFAULT_BLOB, load_library
-
-CORE_SYMBOLS = ["rade_parse_weights", "init_radeenc", "init_radedec", "rade_init_encoder", "rade_core_encoder", "rade_init_decoder",
-                "rade_core_decoder", "rade_free_encoder", "rade_reset_encoder", "rade_reset_decoder", "rade_free_decoder"]
-
-
-class WeightArray(C.Structure):
-    _fields_ = [("name", C.c_char_p), ("type", C.c_int), ("size", C.c_int), ("data", C.c_void_p)]
-
-
-class _Model(C.Structure):       # RADEEnc / RADEDec
-    _fields_ = [("blob", C.c_void_p), ("blob_len", C.c_int), ("dim", C.c_int), ("nb_z", C.c_int)]
-
-
-class _State(C.Structure):       # RADEEncState / RADEDecState
-    _fields_ = [("initialized", C.c_int), ("dev", C.c_void_p)]
-
-
-def _lib():
-    L = load_library()
-    L.rade_parse_weights.argtypes = [C.POINTER(C.POINTER(WeightArray)), C.c_void_p, C.c_int]
-    L.init_radeenc.argtypes = [C.POINTER(_Model), C.POINTER(WeightArray), C.c_int]
-    L.init_radedec.argtypes = [C.POINTER(_Model), C.POINTER(WeightArray), C.c_int]
-    for n in ("rade_init_encoder", "rade_init_decoder", "rade_free_encoder", "rade_reset_encoder", "rade_reset_decoder", "rade_free_decoder"):
-        getattr(L, n).argtypes = [C.POINTER(_State)]; getattr(L, n).restype = None
-    L.rade_core_encoder.argtypes = [C.POINTER(_State), C.POINTER(_Model), C.c_void_p, C.c_void_p, C.c_int, C.c_int]; L.rade_core_encoder.restype = None
-    L.rade_core_decoder.argtypes = [C.POINTER(_State), C.POINTER(_Model), C.c_void_p, C.c_void_p, C.c_int]; L.rade_core_decoder.restype = None
-    return L
+from .abi import CORE_SYMBOLS, DEFAULT_BLOB, WeightArray, _Model, _State, load_library as _lib  # noqa: F401
 
 
 def parse_weights(blob: bytes):

@@ -6,36 +6,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .engine import load_library
+from .abi import SC_SYMBOLS, ScFrame, ScStatus, load_library as _lib  # noqa: F401
 
-
-class ScStatus(C.Structure):
-    _fields_ = [("n_frames", C.c_int), ("consumed", C.c_int), ("state", C.c_int), ("nin", C.c_int), ("fs_s", C.c_int), ("g", C.c_float),
-                ("max_cs_re", C.c_float), ("max_cs_im", C.c_float), ("norm_rx_timing", C.c_float), ("phase_ambiguity", C.c_float)]
-
-
-class ScFrame(C.Structure):
-    _fields_ = [("state", C.c_int), ("nin", C.c_int), ("fs_s", C.c_int), ("pad", C.c_int), ("norm_rx_timing", C.c_float), ("g", C.c_float),
-                ("max_cs_re", C.c_float), ("max_cs_im", C.c_float), ("phase_ambiguity", C.c_float), ("pad2", C.c_float * 3)]
-
-
-SC_SYMBOLS = ["rade_sc_open", "rade_sc_close", "rade_sc_reset", "rade_sc_n_streams", "rade_sc_n_tx_out", "rade_sc_nin_max", "rade_sc_n_payload",
-              "rade_sc_rrc", "rade_sc_tx", "rade_sc_rx"]
 _FRAME_DT = np.dtype([("state", "i4"), ("nin", "i4"), ("fs_s", "i4"), ("pad", "i4"), ("norm_rx_timing", "f4"), ("g", "f4"), ("max_cs_re", "f4"),
                       ("max_cs_im", "f4"), ("phase_ambiguity", "f4"), ("pad2", "f4", 3)])
-
-
-def _lib():
-    L = load_library()
-    vp = C.c_void_p
-    L.rade_sc_open.restype = vp; L.rade_sc_open.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
-    L.rade_sc_close.argtypes = [vp]; L.rade_sc_reset.argtypes = [vp]
-    for n in ("rade_sc_n_streams", "rade_sc_n_tx_out", "rade_sc_nin_max", "rade_sc_n_payload"):
-        getattr(L, n).argtypes = [vp]
-    L.rade_sc_rrc.argtypes = [vp, vp]
-    L.rade_sc_tx.argtypes = [vp, vp, C.c_int, vp, C.c_long, vp]
-    L.rade_sc_rx.argtypes = [vp, vp, C.c_long, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    return L
 
 
 class SingleCarrierBatch:

@@ -1,0 +1,274 @@
+"""radae_amd/abi.py against include/rade_api.h, rade_core.h and rade_batch.h, on the CPU.  The binding states the C ABI once, as ctypes; a `c_int` where the header says
+`long`, or a structure field out of place, fails nowhere on the host and smashes a stack on the device box.  So:
+
+1. every function the headers declare has an entry in abi.PROTOTYPES and the reverse, in the headers' order, with the same number of arguments and the same class
+   (pointer, i32, u32, i64, u64, f32, f64, void) of each argument and of the return value;
+2. every ctypes structure of abi.STRUCTS has the size, field offsets and field sizes the host compiler gives its typedef;
+3. the comparison rejects what it is for: doctored header text is reported as a mismatch that names the function or field;
+4. the names the four binding modules offered before abi.py / stages.py were split off are all still there, and the derived symbol lists kept their members."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from radae_amd import abi
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADERS = ("rade_api.h", "rade_core.h", "rade_batch.h")
+SCALARS = {"void": "void", "int": "i32", "unsigned": "u32", "unsigned int": "u32", "long": "i64", "long long": "i64", "unsigned long": "u64",
+           "unsigned long long": "u64", "size_t": "u64", "float": "f32", "double": "f64"}
+BASE_WORDS = {w for k in SCALARS for w in k.split()}
+
+
+def header_texts():
+    return {h: open(os.path.join(REPO, "include", h)).read() for h in HEADERS}
+
+
+# ================================================================================================================================================================
+# the parser: comments and the preprocessor out, statements split at top-level semicolons, parameters at top-level commas
+# ================================================================================================================================================================
+def statements(text):
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = text.replace('extern "C" {', " ").replace("RADE_EXPORT", " ")
+    out, cur, depth = [], "", 0
+    for ch in text:
+        depth += (ch in "{(") - (ch in "})")
+        if depth < 0:                      # the brace that closes extern "C"
+            depth = 0
+        elif ch == ";" and depth == 0:
+            out.append(" ".join(cur.split())); cur = ""
+        else:
+            cur += ch
+    assert not cur.strip(), f"text behind the last declaration: {cur.strip()[:80]!r}"
+    return [s for s in out if s]
+
+
+def split_top(s, sep=","):
+    out, cur, depth = [], "", 0
+    for ch in s:
+        depth += (ch in "{([") - (ch in "})]")
+        if ch == sep and depth == 0:
+            out.append(cur); cur = ""
+        else:
+            cur += ch
+    return [p.strip() for p in out + [cur] if p.strip()]
+
+
+def type_class(decl, pointer_types, named):
+    """the class of a parameter (named: its name may follow the type) or of a return type; a function pointer or an array parameter is a pointer"""
+    if any(c in decl for c in "*[("):
+        return "ptr"
+    w = [t for t in decl.split() if t not in ("const", "signed")]
+    if named and len(w) > 1 and w[-1] not in BASE_WORDS:
+        w.pop()
+    if len(w) == 1 and w[0] in pointer_types:
+        return "ptr"
+    return SCALARS[" ".join(w)]            # KeyError: the caller names the declaration
+
+
+def parse(text):
+    """(functions {name: (return class, [argument classes])} in the text's order, structures {typedef name: [field names]}); ValueError names what it cannot read"""
+    funcs, structs, pointer_types = {}, {}, set()
+    for s in statements(text):
+        m = re.match(r"typedef struct\s*\w*\s*\{(.*)\}\s*(\w+)$", s)
+        if m:
+            structs[m.group(2)] = [re.search(r"(\w+)\s*(\[[^\]]*\])?$", d).group(1) for f in split_top(m.group(1), ";") for d in split_top(f)]
+            continue
+        m = re.match(r"typedef .*\(\s*\*\s*(\w+)\s*\)\s*\(", s)
+        if m:
+            pointer_types.add(m.group(1))
+            continue
+        if re.match(r"(typedef struct \w+ \w+|struct \w+|enum\s*\{.*\}|extern [^()]*)$", s):      # opaque handles, enumerations, data
+            continue
+        m = re.match(r"(.*?)(\w+)\s*\((.*)\)$", s)
+        try:
+            params = [] if m.group(3).strip() == "void" else split_top(m.group(3))
+            funcs[m.group(2)] = (type_class(m.group(1), pointer_types, False), [type_class(p, pointer_types, True) for p in params])
+        except (AttributeError, KeyError):
+            raise ValueError(f"cannot parse the declaration {s!r}") from None
+    return funcs, structs
+
+
+def ctype_class(t):
+    if t is None:
+        return "void"
+    if issubclass(t, (C._Pointer, C.c_void_p, C.c_char_p, C.Array, C._CFuncPtr)):
+        return "ptr"
+    return {"i": "i32", "I": "u32", "l": "i64", "q": "i64", "L": "u64", "Q": "u64", "f": "f32", "d": "f64"}[t._type_]
+
+
+# ================================================================================================================================================================
+# the comparison: a list of mismatches, each naming its function or field
+# ================================================================================================================================================================
+def compare_functions(texts):
+    bad = []
+    for h in HEADERS:
+        funcs, _ = parse(texts[h])
+        table = abi.PROTOTYPES[h]
+        if list(funcs) != list(table):
+            bad += [f"{h}: {n} is declared and has no table entry" for n in funcs if n not in table]
+            bad += [f"{h}: the table's {n} is not declared" for n in table if n not in funcs]
+            both = zip([n for n in funcs if n in table], [n for n in table if n in funcs])
+            bad += [f"{h}: the table's order differs from the header's at {a} / {b}" for a, b in both if a != b][:1]
+        for n, (ret, args) in funcs.items():
+            if n not in table:
+                continue
+            restype, argtypes = table[n]
+            if ctype_class(restype) != ret:
+                bad.append(f"{n}: returns {ret}, the table says {ctype_class(restype)}")
+            got = [ctype_class(a) for a in argtypes]
+            if len(got) != len(args):
+                bad.append(f"{n}: {len(args)} arguments, the table has {len(got)}")
+            bad += [f"{n}: argument {i} is {a}, the table says {g}" for i, (a, g) in enumerate(zip(args, got)) if a != g]
+    return bad
+
+
+def c_layouts(texts, tmp):
+    """{typedef: (sizeof, [(field, offset, size)])} from the host compiler, for every structure typedef of the texts"""
+    cc = shutil.which("cc")
+    assert cc, "no host C compiler `cc` (build() needs one too)"
+    structs = {}
+    for h in HEADERS:
+        open(os.path.join(tmp, h), "w").write(texts[h])
+        structs.update(parse(texts[h])[1])
+    lines = ["#include <stdio.h>", "#include <stddef.h>"] + [f'#include "{h}"' for h in HEADERS] + ["int main(void) {"]
+    for t, fields in structs.items():
+        lines.append(f'printf("{t} %zu\\n", sizeof({t}));')
+        lines += [f'printf("{t}.{f} %zu %zu\\n", offsetof({t}, {f}), sizeof((({t} *)0)->{f}));' for f in fields]
+    open(os.path.join(tmp, "layout.c"), "w").write("\n".join(lines + ["return 0; }", ""]))
+    subprocess.check_call([cc, "-I", tmp, "-o", os.path.join(tmp, "layout"), os.path.join(tmp, "layout.c")])
+    out = {}
+    for ln in subprocess.check_output([os.path.join(tmp, "layout")], text=True).splitlines():
+        name, *v = ln.split()
+        if "." in name:
+            out[name.split(".")[0]][1].append((name.split(".")[1], int(v[0]), int(v[1])))
+        else:
+            out[name] = (int(v[0]), [])
+    return out
+
+
+def compare_layouts(texts, tmp):
+    want = c_layouts(texts, str(tmp))
+    bad = [f"{t}: abi.STRUCTS has no such typedef in the headers" for t in abi.STRUCTS if t not in want]
+    for t, cls in abi.STRUCTS.items():
+        if t not in want:
+            continue
+        size, fields = want[t]
+        got = [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, *_ in cls._fields_]
+        if C.sizeof(cls) != size or len(got) != len(fields):
+            bad.append(f"{t}: {len(fields)} fields in {size} bytes, ctypes has {len(got)} in {C.sizeof(cls)}")
+        for (cn, co, cs), (pn, po, ps) in zip(fields, got):
+            if not (cn == pn or cn.endswith("_" + pn)) or (co, cs) != (po, ps):     # (RADEEnc.input_dim and RADEDec.output_dim share one mirror: `dim`)
+                bad.append(f"{t}.{cn}: offset {co} size {cs}, ctypes has {pn} at offset {po} size {ps}")
+    return bad
+
+
+# ================================================================================================================================================================
+# 1, 2. the headers as they are
+# ================================================================================================================================================================
+def test_every_prototype_agrees_with_its_header():
+    texts = header_texts()
+    n = sum(len(parse(t)[0]) for t in texts.values())
+    print(f"{n} functions declared in {', '.join(HEADERS)}")
+    assert n >= 106 and n == sum(len(t) for t in abi.PROTOTYPES.values())
+    bad = compare_functions(texts)
+    assert not bad, "\n".join(bad)
+
+
+def test_every_structure_has_the_compilers_layout(tmp_path):
+    structures = {v for v in vars(abi).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert structures == set(abi.STRUCTS.values()), "a ctypes structure of abi.py is missing from abi.STRUCTS"
+    declared = {t for text in header_texts().values() for t in parse(text)[1]}
+    assert declared - {"RADE_COMP"} == set(abi.STRUCTS), "a typedef of the headers has no mirror (RADE_COMP is complex64 memory: numpy's)"
+    bad = compare_layouts(header_texts(), tmp_path)
+    assert not bad, "\n".join(bad)
+
+
+# ================================================================================================================================================================
+# 3. the checker rejects what it is for
+# ================================================================================================================================================================
+def doctored(header, old, new):
+    texts = header_texts()
+    assert texts[header].count(old) == 1, f"{old!r} is not unique in {header}"
+    texts[header] = texts[header].replace(old, new)
+    return texts
+
+
+@pytest.mark.parametrize("header, old, new, needles", [
+    ("rade_batch.h", "int rade_batch_tx_eoo(rade_batch *h, void *iq_out_dev, long iq_stride, void *stream);",
+     "int rade_batch_tx_eoo(rade_batch *h, void *iq_out_dev, void *stream);", ("rade_batch_tx_eoo", "3 arguments")),                 # one parameter dropped
+    ("rade_batch.h", "int rade_batch_tx_latents(rade_batch *h, const float *z_dev, int n_mf, void *iq_out_dev, long iq_stride, void *stream);",
+     "int rade_batch_tx_latents(rade_batch *h, const float *z_dev, int n_mf, void *iq_out_dev, int iq_stride, void *stream);",
+     ("rade_batch_tx_latents", "argument 4 is i32")),                                                                                   # a long turned int
+    ("rade_batch.h", "float rade_sigma_from_EbNodB(float EbNodB);", "float rade_sigma_from_EbNodB(double EbNodB);",
+     ("rade_sigma_from_EbNodB:", "argument 0 is f64")),                                                                                # a float turned double
+    ("rade_api.h", "RADE_EXPORT float rade_freq_offset(struct rade *r);", "RADE_EXPORT double rade_freq_offset(struct rade *r);",
+     ("rade_freq_offset", "returns f64")),
+    ("rade_core.h", "void rade_free_encoder(RADEEncState *enc_state);", "void rade_free_encoder(RADEEncState *enc_state);\nvoid rade_new_entry(int x);",
+     ("rade_new_entry", "no table entry")),
+], ids=["parameter_dropped", "long_turned_int", "float_turned_double", "return_turned_double", "function_added"])
+def test_the_function_check_rejects(header, old, new, needles):
+    bad = compare_functions(doctored(header, old, new))
+    assert bad and all(needles[0] in b for b in bad) and all(n in bad[0] for n in needles), bad
+
+
+def test_the_function_check_names_what_it_cannot_parse():
+    with pytest.raises(ValueError, match="rade_batch_n_streams"):
+        compare_functions(doctored("rade_batch.h", "int rade_batch_n_streams(const rade_batch *h);", "int rade_batch_n_streams(rade_batch h);"))
+
+
+def test_the_layout_check_rejects_swapped_fields(tmp_path):
+    """two adjacent fields of different size: rade_fm_demod_params' `void *bb_out_dev; long bb_stride` are of one size, `const float *b1; int N1` are not"""
+    bad = compare_layouts(doctored("rade_batch.h", "const float *b1; int N1;", "int N1; const float *b1;"), tmp_path)
+    assert bad and all(b.startswith(("rade_fm_demod_params.N1:", "rade_fm_demod_params.b1:")) for b in bad) and len(bad) == 2, bad
+
+
+# ================================================================================================================================================================
+# 4. names: what `dir()` of each module held before the split (imported names left out; the private names other files use kept)
+# ================================================================================================================================================================
+NAMES = {
+    "engine": """BOTTLENECK1 BYPASS_DEC BatchConfig BatchEngine CNO_FS CNO_HOP ChannelParams ChannelStreams ClockOffset CnoParams CnoPlan CnoResult DEFAULT_BLOB EQ_MODES
+        EXPORTED_SYMBOLS FEAT_MF FM_C64 FM_DE_EMP_TC FM_F32 FM_OUT_COMPLEX FM_OUT_REAL FmDemodParams FmDemodulator FmModParams FmModulator IdealRxParams LIB_PATH NEOO NEOO_BITS
+        NIN_MAX NMF RATE_C64 RATE_S16_IQ RATE_S16_REAL RESAMPLE_MODES RESAMPLE_PPM_MAX RateConverter RateParams ResampleParams RxStatus RxTrace SPEC_C64 SPEC_HI SPEC_LO SPEC_NFFT
+        SPEC_S16_REAL SPEC_STEP SPEC_WIN SpecgramParams SpecgramPlan TX_BPF TX_LINEAR WIRE_IQ WIRE_REAL WireMeters ZMF _lib _per_stream _stream_ptr channel_stream_values chirp
+        cno_plan cno_windows fm_deemph_len fm_pre_emphasis fm_sigma fm_taps load_library loss_lengths ppm_from_rates rate_count rate_taps resample_count resample_taps
+        sigma_from_EbNodB specgram_levels specgram_plan specgram_slices specgram_window""",
+    "sc": "SC_SYMBOLS ScFrame ScStatus SingleCarrierBatch _FRAME_DT main sc_rx_stream sc_tx_stream",
+    "core": "CORE_SYMBOLS CoreDecoder CoreEncoder DEFAULT_BLOB WeightArray _Model _lib parse_weights",
+    "api": """RADE_BATCH_TX_BPF RADE_FOFF_TEST RADE_USE_C_DECODER RADE_USE_C_ENCODER RADE_VERBOSE_0 Rade radae_rx radae_rx_bypass_dec radae_rx_engine radae_tx
+        radae_tx_bypass_enc""",
+}
+SYMBOLS = {
+    "EXPORTED_SYMBOLS": """rade_batch_channel rade_batch_channel_rs_pa rade_batch_channel_streams rade_batch_channel_symbol rade_batch_close rade_batch_cno_est rade_batch_decode
+        rade_batch_encode rade_batch_fm_demod rade_batch_fm_mod rade_batch_loss rade_batch_multipath_gen rade_batch_multipath_h rade_batch_n_streams rade_batch_open
+        rade_batch_open_mem rade_batch_profile rade_batch_profile_get rade_batch_profile_intervals rade_batch_profile_ref rade_batch_rate_convert rade_batch_resample
+        rade_batch_reset rade_batch_rx rade_batch_rx_filtered rade_batch_rx_get_trace rade_batch_rx_ideal rade_batch_rx_reset rade_batch_rx_set_lcg rade_batch_rx_stream_cycles
+        rade_batch_specgram rade_batch_sync_counts rade_batch_tx rade_batch_tx_channel rade_batch_tx_channel_streams rade_batch_tx_eoo rade_batch_tx_latents rade_batch_tx_reset
+        rade_batch_tx_set_eoo_bits rade_batch_wire_in rade_batch_wire_out rade_chirp rade_close rade_cno_plan rade_finalize rade_fm_deemph_len rade_fm_sigma rade_fm_taps
+        rade_freq_offset rade_host_cpu_quota rade_initialize rade_multi_allreduce_sum rade_multi_close rade_multi_engine rade_multi_foreach rade_multi_n_devices rade_multi_open
+        rade_multi_shard rade_multi_transport rade_n_eoo_bits rade_n_features_in_out rade_n_tx_eoo_out rade_n_tx_out rade_nin rade_nin_max rade_open rade_rate_count
+        rade_rate_taps rade_resample_count rade_resample_taps rade_rx rade_sigma_from_EbNodB rade_sigma_from_EbNodB_bn1 rade_sigma_from_EbNodB_rs3 rade_snrdB_3k_est
+        rade_specgram_levels rade_specgram_plan rade_specgram_slices rade_specgram_window rade_sync rade_sync_policy rade_tx rade_tx_eoo rade_tx_set_eoo_bits rade_version""",
+    "SC_SYMBOLS": "rade_sc_close rade_sc_n_payload rade_sc_n_streams rade_sc_n_tx_out rade_sc_nin_max rade_sc_open rade_sc_reset rade_sc_rrc rade_sc_rx rade_sc_tx",
+    "CORE_SYMBOLS": """init_radedec init_radeenc rade_core_decoder rade_core_encoder rade_free_decoder rade_free_encoder rade_init_decoder rade_init_encoder
+        rade_parse_weights rade_reset_decoder rade_reset_encoder""",
+}
+
+
+@pytest.mark.parametrize("module", list(NAMES))
+def test_every_earlier_name_is_still_an_attribute(module):
+    import importlib
+    mod = importlib.import_module("radae_amd." + module)
+    missing = [n for n in NAMES[module].split() if not hasattr(mod, n)]
+    assert not missing, f"radae_amd.{module} lost {missing}"
+
+
+def test_the_derived_symbol_lists_kept_their_members():
+    from radae_amd import core, engine, sc
+    for mod, name in ((engine, "EXPORTED_SYMBOLS"), (sc, "SC_SYMBOLS"), (core, "CORE_SYMBOLS")):
+        got = list(getattr(mod, name))
+        assert sorted(got) == sorted(SYMBOLS[name].split()), name
