@@ -567,6 +567,90 @@ int rade_batch_specgram(rade_batch *h, const void *x_dev, long x_stride, const i
                         float *mag_dev, long mag_stride,            /* [B][slices][1023] |X[1..1023]|, mag_stride in floats per stream; or NULL */
                         float *peak_host /* [B] */, int *n_slices_host /* [B] */, void *stream);
 
+/* ---- whole-file pilot acquisition: rx.py's frame loop (rx.py:146-188, --acq_test :164-178, :190-195) over every hop of every stream (rade_acq.hip) -------------------
+ * rx.py walks a stored recording one modem frame at a time: acquisition.detect_pilots (dsp.py:178-231) over 2 Nmf + M + Ncp = 2112 samples, a small state machine, and
+ * acquisition.refine (dsp.py:233-270) where it acquires.  Here every hop of every stream is one call.  Geometry: model19_check3's only, Fs 8000, M 160, Ncp 32, Nmf 960,
+ * the 40 coarse frequencies -50 .. +47.5 Hz in steps of 2.5; p and p_w are the engine's own tables (dsp.py:166-173).
+ * Surface: D[t][f] = sum_{m < 160} conj(x[t + m]) p_w[m][f], x the stream's n complex64 samples.
+ * Hops: hop k exists while n - 961 k >= 2112 (the script drops one tail sample per hop, rx = rx[Nmf:-1]): n = 2111 none, 2112 .. 3072 one, 3073 two (rade_acq_hops).
+ *   DEVIATION: with between 2 Nmf + M and 2 Nmf + M + Ncp samples left the script trips detect_pilots' assert; the loop here stops one hop earlier.
+ *   Hop k starts at sample 960 k: Dt1 = D[960 k + t], Dt2 = D[960 (k + 1) + t], t = 0..959.  Hop k's Dt2 is hop k + 1's Dt1: every row of D is formed once.
+ * Per hop: Dtmax12 = max over (t, f) of |Dt1[t][f]| + |Dt2[t][f]| (one rounded float32 addition of the two float32 magnitudes), tmax and f_ind the cell that has it; of
+ *   equal cells the first in the script's order wins (smallest t, then smallest f: its comparison is a strict >, from 0).  An all-zero hop has Dtmax12 0, tmax 0,
+ *   f_ind 0 and, as in the script, fmax 0.0 (rade_acq_fmax; otherwise fmax = -50 + 2.5 f_ind).
+ *   S1 = sum |Dt1|, S2 = sum |Dt2| over the 38400 cells, in double: a lane adds its 30 cells of a block, the 64 lanes are added by a fixed exchange pattern, and a
+ *   second launch adds the 20 wavefronts of a block in ascending order.  No atomics: identical calls give identical bits, and a stream's results do not depend on the
+ *   other streams of the batch, on B or on the strides.
+ *   Host, in double after the read-back: sigma_r = (S1 + S2) / 38400 / sqrt(pi / 2) / 2, Dthresh = 2 sigma_r sqrt(-ln(Pacq_error1 / 5)), candidate = Dtmax12 > Dthresh.
+ *   (The script's float32 means differ from these double sums by a few 1e-7 of Dthresh.)
+ * How the device forms D: the two-stage correlator of the receiver's search (rade_host.c, rd_corrq16_table_fill), with the engine's own two tables.  p_w[m][f] = sum_{r < 16}
+ *   alpha[r][f] s_r[m], s_r[m] = p[m] q_r(x_m), q_r the 16 polynomials orthonormal on x_m = (m - 79.5) / 80, alpha[r][f] = sum_m q_r(x_m) e^{j w_f m}; so
+ *   D[t][f] = sum_r alpha[r][f] Mom_r[t], Mom_r[t] = sum_m conj(x[t + m]) s_r[m].  Stage 1, the moments: a real GEMM, rows (r, re | im), K = (m, re | im), columns t, on
+ *   v_mfma_f32_16x16x32_f16.  Both operands are two binary16 planes, v = hi + lo with hi = fl16(v), lo = fl16(v - hi), under a power-of-two scale: 2^12 for s_r, and for
+ *   the samples the power of two that puts the largest |component| of the 208 samples a wavefront reads for a block (48 timings) into [2^7, 2^8).  hi x hi is accumulated by
+ *   10 instructions (K = 32 each) into one float32 accumulator, lo x hi and hi x lo by 20 into a second, lo x lo is dropped; one float32 addition joins the two.  Stage 2:
+ *   the joined moments times 2^-7 in three binary16 planes (33 bits) against the two planes of 2^10 alpha, five instructions (K = 32: the 16 complex moments) into one
+ *   accumulator, smallest partial products first.  The power-of-two scales are undone exactly, and |D| = sqrt(fma(re, re, im im)) on the hardware square root (1 ulp).
+ *   85 matrix instructions per 16 timings, where the 80 rows of p_w itself take 150.
+ * Error bound, counted from these roundings.  The matrix instruction's own rounding is not documented; ASSUMED: each instruction returns its 33-term sum within 2^-23 of the
+ *   sum of the terms' moduli (two float32 roundings).  Stage 1, per real component of Mom_r relative to B_r = sum_m |x[t + m]| |p[m]| |q_r(x_m)|: the two planes of either
+ *   operand leave 2^-22 each and the dropped product 2^-22, the hi x hi chain adds 10 x 2^-23, the cross chain 20 x 2^-23 x 2^-10, the joining addition 2^-24: e1 = (0.75 +
+ *   1.25 + 0.02 + 0.0625) 2^-20 = 2.09 x 2^-20, sqrt 2 e1 B_r in modulus.  Stage 2 multiplies the moment r by alpha[r][f], so these errors reach D[t][f] as sqrt 2 e1 sum_r
+ *   |alpha[r][f]| B_r = sqrt 2 e1 A[t][f], with
+ *       A[t][f] = sum_{m < 160} |x[t + m]| |p[m]| G[f][m],   G[f][m] = sum_r |alpha[r][f]| |q_r(x_m)|     (the moment form's gain: 1 at 0 Hz, up to 4.4 at -50 Hz)
+ *   Stage 2's own roundings, relative to sum_r |alpha[r][f]| |Mom_r| <= A[t][f]: the planes of alpha 2^-22 (the moments' three planes and the dropped product: below 2^-32),
+ *   the chain 5 x 2^-23: sqrt 2 (0.25 + 0.625) 2^-20 = 1.24 x 2^-20 in modulus.  The magnitude (a product, a fused multiply-add, the square root): 3 x 2^-24 |D| <= 0.19 x
+ *   2^-20 A.  Sum 4.39, with 1.01 for the terms of second order and rounded up: RADE_ACQ_EPS = 4.5 x 2^-20 = 4.29e-6.  Last, the two tables' product is p_w only within
+ *   RADE_ACQ_TAB = 1e-8 per entry (16 moments of a band-limited phase: 4.8e-9 as built; rd_corr_tables_check, tests/test_host_cpu.py), which adds RADE_ACQ_TAB sum_m |x[t + m]|:
+ *       | |D|^ - |D| | <= RADE_ACQ_EPS A[t][f] + RADE_ACQ_TAB sum_{m < 160} |x[t + m]|
+ *   and the same bound holds for the complex value in dt_dev; barring underflow (a low plane below 2^-24 of the scaled maximum: 2^-32 of the block's largest component
+ *   per term).  Dtmax12's cell: the bounds of its two cells + 2^-24 Dtmax12; S1: the sum of the bounds of the block's 38400 cells (the double sums add nothing that
+ *   counts).  A worst-case bound under the stated assumption: tests/test_acq_gpu.py records how far below it the device stays (under 2 %).
+ * dt_dev (optional): complex64 [B][n_rows][40], D[t0 + r][f] of every stream at [b][r][f], in the script's convention (a hop's 960 rows are what --write_Dt writes).
+ *   Only the rows the hops use exist: t < 960 (n_hops + 1).  Rows beyond that are not written.
+ * Input: complex64, 8-byte aligned, x_stride >= every n_host[b]; not written; nothing outside a stream's n_host[b] samples is read.  Streams with no hop are not an error
+ *   (n_hops 0, nothing written for them).  The call copies the counts to the device, launches, reads the hop records back and SYNCHRONISES `stream` before the host
+ *   arithmetic, as rade_batch_cno_est does.  Any engine (the model is not used; no encoder or receiver state is touched); the device memory (counts, partials, records)
+ *   belongs to the engine and is sized on first use and when a call needs more.
+ * Refused with -1 before any launch and with nothing written: NULL h, x_dev, n_host, hops_host or n_hops_host; x_dev or dt_dev not 8-byte aligned; a negative count or one
+ *   above x_stride; max_hops smaller than the largest hop count; with dt_dev, t0 < 0, n_rows < 1 or t0 + n_rows > x_stride; Pacq_error1 not inside (0, 5).
+ * rade_acq_track: host only; the state machine of rx.py:151-188 over one stream's hop records.  A candidate in `search` moves to `candidate` and stores tmax_candidate with
+ *   valid_count 1; a further candidate with |tmax - tmax_candidate| < 0.02 M increments the count, and when it exceeds 3 the hop is an event {hop, tmax, f_ind}; anything
+ *   else returns to `search`.  acq_test 0: stop at the first event (the script's normal run); 1: go back to `search` and collect every event.  log_out[k] (optional) is
+ *   what the script prints in hop k's line: the state (0 search, 1 candidate), tmax_candidate and valid_count BEFORE the hop's update (0 until first set).  Returns the
+ *   number of events (those beyond max_events are counted, not stored), -1: NULL hops with n_hops > 0, NULL events with max_events > 0, negative counts.
+ * rade_batch_acq_refine: acquisition.refine for a list of (stream, t_abs = 960 hop + tmax, fmax), one workgroup per event.  For the 80 frequencies fmax - 10 + 0.25 i and the
+ *   timings t_abs - 1 .. t_abs + 1: Dt1 = sum_m x[t + m] e^{-j w m} conj(p[m]), Dt2 the same at t + 960 times e^{-j w 960}, w = 2 pi f / 8000; the maximum of
+ *   |Dt1 + Dt2| by strict > from 0 in the script's order (frequency outer, timing inner).  Everything in double, in ascending m.  DIFFERENCE: the script multiplies
+ *   complex64 samples by complex128 phasors and rounds each dot product to complex64 before it adds and compares (relative 6e-8); near-equal cells may order otherwise.
+ *   DEVIATION: the script hands refine the hop's slice x[960 k : n - k] and the timing inside it; here the timing is absolute and its windows are held against the whole
+ *   stream's n (the same samples: a hop's windows always lie inside its slice).  DEVIATION: a timing whose windows leave [0, n) is skipped (the script reads x[-1] for t = -1 and fails behind the end); with no timing left, or an all-zero window,
+ *   t = t_abs, f = fmax, Dmax = 0.  dfine_host (optional) [n_events][80]: |Dt1| of the winning timing over the 80 frequencies (|acq.D_fine|).  Synchronises `stream`.
+ *   Refused: NULLs, misaligned x_dev, n_events < 0, a count outside [0, x_stride], an event whose stream is outside [0, B), whose |t_abs| exceeds 2^40 or whose fmax is
+ *   not finite.
+ * rade_acq_stats: host only; rx.py:134, :170-171, :190-195.  An event passes when |(t - 960 hop) - (Ncp + Ntap / 2)| < 0.0025 Fs and |f - fmax_target| <= 5 (t, f refined;
+ *   Ntap 101 with the input band-pass, 0 without; Ntap / 2 is 50.5).  pfail = fails / (passes + fails) (0 with no event, where the script divides by zero);
+ *   mean_acq_time = (960 (n_hops + 1) / 8000) / passes (the script's mf counter ends one above the hop count), infinity with no pass; passed = pfail < 0.2 and
+ *   mean_acq_time < acq_time_target. */
+#define RADE_ACQ_EPS (4.5 / 1048576.0)
+#define RADE_ACQ_TAB 1e-8
+typedef struct { float Dtmax12; double Dthresh; int tmax, f_ind, candidate; double S1, S2; } rade_acq_hop;
+typedef struct { int hop, tmax, f_ind; } rade_acq_event;
+typedef struct { int state, tmax_candidate, valid_count; } rade_acq_log;
+typedef struct { int stream; long long t_abs; double fmax; } rade_acq_refine_in;
+typedef struct { long long t; double f, Dmax; } rade_acq_refined;
+typedef struct { int passes, fails, passed; double pfail, mean_acq_time; } rade_acq_result;
+int rade_acq_hops(long long n);                                    /* host only */
+double rade_acq_fmax(const rade_acq_hop *hop);                     /* host only */
+int rade_batch_acq_detect(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, double Pacq_error1 /* the script's 1e-5 */,
+                          rade_acq_hop *hops_host /* [B][max_hops] */, int max_hops, int *n_hops_host /* [B] */,
+                          void *dt_dev /* complex64 [B][n_rows][40] or NULL */, long long t0, int n_rows, void *stream);
+int rade_acq_track(const rade_acq_hop *hops, int n_hops, int acq_test, rade_acq_event *events, int max_events, rade_acq_log *log_out /* [n_hops] or NULL */);
+int rade_batch_acq_refine(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, const rade_acq_refine_in *events_host, int n_events,
+                          rade_acq_refined *out_host /* [n_events] */, double *dfine_host /* [n_events][80] or NULL */, void *stream);
+int rade_acq_stats(const rade_acq_event *events, const rade_acq_refined *refined, int n_events, int n_hops, int Ntap, double fmax_target, double acq_time_target,
+                   rade_acq_result *out);
+
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the
  * n_taps Gaussian-PSD FIR (taps designed by the caller, e.g. radae_amd/channel_tools.py), linearly interpolated to

@@ -11,6 +11,7 @@
     python -m radae_amd.cli bbfm_inference MODEL features.f32 features_hat.f32 [--CNRdB ..] [--h_file h_lmr60.f32] [--write_latent z.f32]    bbfm_inference.py
     python -m radae_amd.cli analog_fm IN.s16 OUT.s16 CNRdB [--seed N]                                                             analog_bbfm.sh:37-43 from the 8 kHz int16 file onward
     python -m radae_amd.cli est_cno RX.f32 [--window_time S] [--flow HZ] [--fhigh HZ]                                              est_CNo.py (without --plots); the periodograms on the device
+    python -m radae_amd.cli rx RX.f32 [--no_bpf] [--acq_test] [--fmax_target HZ] [--acq_time_target S] [--write_Dt FILE]             rx.py --pilots up to the acquisition (no decoding): every frame's pilot search in one device call
     python -m radae_amd.cli chirp OUT.f32 NSEC [--flow HZ] [--fhigh HZ] [--amp A]                                                  chirp.py (host)
     python -m radae_amd.cli specgram IN OUT.png [--fmin HZ] [--fmax HZ]                                                            plot_specgram.m at 8 kHz: the transforms and levels on the device, a grey-scale PNG
 
@@ -550,6 +551,61 @@ def _est_cno(argv):
     return 0
 
 
+def _rx(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli rx", description="Pilot acquisition of a stored recording (rx.py --pilots): the input band-pass, detect_pilots over every "
+                                 "modem frame in one device call (rade_batch_acq_detect), the script's state machine and refine; with --acq_test the pass / fail statistics.  "
+                                 "The acquired file is not decoded (rx.py:223-253), and --rx_one, --ber_test and --plots are not offered")
+    ap.add_argument("rx", type=str, help="path to input file of rate Fs rx samples in ..IQIQ...f32 format")
+    ap.add_argument("model_name", nargs="?", default=None, help="accepted and ignored (the script's first argument): the geometry is model19_check3's")
+    ap.add_argument("features_hat", nargs="?", default=None, help="accepted and ignored: nothing is decoded")
+    ap.add_argument("--no_bpf", dest="bpf", action="store_false", help="disable the input band-pass filter")
+    ap.add_argument("--acq_test", action="store_true", help="search again after every acquisition and report passes, fails, P(fail) and the mean acquisition time")
+    ap.add_argument("--fmax_target", type=float, default=0.0, help="acquisition test mode freq offset target (default 0.0)")
+    ap.add_argument("--acq_time_target", type=float, default=1.0, help="acquisition test mode mean acquisition time target (default 1.0)")
+    ap.add_argument("--write_Dt", type=str, default="", help="write Dt1 of every frame, complex64 [frames][960][40]")
+    # the script's waveform flags, accepted where they describe model19_check3
+    ap.add_argument("--pilots", action="store_true"); ap.add_argument("--pilot_eq", action="store_true"); ap.add_argument("--coarse_mag", action="store_true")
+    ap.add_argument("--auxdata", action="store_true"); ap.add_argument("--bottleneck", type=int, default=3); ap.add_argument("--cp", type=float, default=0.004)
+    ap.add_argument("--latent-dim", type=int, default=80); ap.add_argument("--time_offset", type=int, default=-16)
+    args = ap.parse_args(argv)
+    if args.bottleneck != 3 or args.cp != 0.004 or args.latent_dim != 80:
+        raise SystemExit("radae_amd.cli rx: only model19_check3's waveform (--bottleneck 3 --cp 0.004 --latent-dim 80) is built")
+    import torch
+    from . import acq, engine, stages
+    rx = np.fromfile(args.rx, dtype=np.csingle)
+    print(f"samples: {len(rx):d} Nmf: {acq.NMF:d} modem frames: {len(rx)/acq.NMF}")
+    eng = engine.BatchEngine(1, max_tx_mf=1)
+    x = torch.tensor(rx[None], device="cuda")
+    n_hops = stages.acq_hops(len(rx))
+    res = acq.acquire(eng, x, bpf=args.bpf, acq_test=args.acq_test, fmax_target=args.fmax_target, acq_time_target=args.acq_time_target,
+                      dt_rows=(0, acq.NMF * n_hops) if args.write_Dt and n_hops else None)
+    (r,) = res[0] if isinstance(res, tuple) else res
+    if isinstance(res, tuple):
+        res[1][0].cpu().numpy().tofile(args.write_Dt)             # Dt1 of every frame, from the one detect call
+    eng.close()
+    at = {int(e["hop"]): i for i, e in enumerate(r.events)}
+    for k, (h, fm, lg) in enumerate(zip(r.hops, r.fmax, r.log)):         # the script's per-frame line, then what it prints when the frame acquires
+        state = ("search", "candidate")[lg["state"]]
+        print(f"{k + 1:2d} state: {state:10s} Dthresh: {h['Dthresh']:8.2f} Dtmax12: {h['Dtmax12']:8.2f} tmax: {h['tmax']:4d} tmax_candidate: {lg['tmax_candidate']:4d} fmax: {fm:6.2f}")
+        if k in at and args.acq_test:
+            t, f = int(r.refined[at[k]]["t"]) - acq.NMF * k, float(r.refined[at[k]]["f"])
+            t_ok = abs(t - (acq.NCP + (acq.NTAP if args.bpf else 0) / 2)) < 0.0025 * acq.FS
+            f_ok = abs(f - args.fmax_target) <= 5.0
+            print(f"Acquired! Timing: {t_ok:d} Freq: {f_ok:d} " + ("" if t_ok and f_ok else f"fmax: {f:6.2f} targ: {args.fmax_target:6.2f}"))
+        elif k in at:
+            print("Acquired!")
+    if args.acq_test:
+        s = r.stats
+        print(f"Acq Test Passes: {s.passes:d} Fails: {s.fails:d} Pfail: {s.pfail:5.2f} Mean Acq time: {s.mean_acq_time:5.2f} s")
+        if s.passed:
+            print("PASS")
+    if args.acq_test or not len(r.events):                             # --acq_test never sets the script's `acquired`: it always ends here, as the script does
+        print("Acquisition failed....")
+    else:
+        print(f"refined fmax: {float(r.refined[0]['f']):f}")
+    return 0
+
+
 def _chirp(argv):
     ap = argparse.ArgumentParser(prog="radae_amd.cli chirp", description="Generates a .f32 IQIQI chirp file for HF channel SNR measurement (chirp.py)")
     ap.add_argument("f32", type=str, help="path to output IQ .f32 file")
@@ -599,7 +655,7 @@ def _specgram(argv):
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm,
-            "est_cno": _est_cno, "chirp": _chirp, "specgram": _specgram}
+            "est_cno": _est_cno, "rx": _rx, "chirp": _chirp, "specgram": _specgram}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2

@@ -344,6 +344,43 @@ typedef struct {
 } rd_spec_args;
 int rd_launch_specgram(const rd_spec_args *a, rd_stream_t s);
 
+/* whole-file pilot acquisition, rade_batch_acq_detect / _refine (rade_acq.hip; include/rade_batch.h states the arithmetic): k_acq_detect, one wavefront
+ * per (RD_ACQ_NPART-th of the 960 within-frame timings, stream), eight to a workgroup, walks the stream's 960-sample blocks and leaves per (block, wavefront) one double sum of |D| and per (hop,
+ * wavefront) one best cell; k_acq_combine folds the RD_ACQ_NPART partials of a hop in ascending order.  k_acq_refine: one workgroup per event. */
+#define RD_ACQ_NPART 20                                          /* wavefronts per stream (48 timings each) = partials per block and per hop */
+#define RD_ACQ_HOP 961                                           /* rx = rx[Nmf:-1]: a hop costs the script 961 samples of its length */
+#define RD_ACQ_NFINE 80                                          /* np.arange(fmax - 10, fmax + 10, 0.25) */
+#define RD_ACQ_EV_CHUNK 1024                                     /* events per launch of k_acq_refine */
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int rd_acq_hops(long long n) { return n < RD_RXBUF ? 0 : (int)((n - RD_RXBUF) / RD_ACQ_HOP) + 1; }
+typedef struct { float best; int key; double S1, S2; } rd_acq_rec;          /* a hop as the device leaves it: Dtmax12, (tmax << 6) | f_ind, the two surface sums */
+typedef struct { float best; int key; } rd_acq_pmax;
+typedef struct {
+    const unsigned short *corrq16, *corra16;                    /* the two tables of the two-stage pilot correlator (rade_host.c), as the receiver has them */
+    const void *x; long x_stride;                               /* complex64, stream b at + b * x_stride samples */
+    const int *n;                                               /* device [B] sample counts */
+    double *psum;                                               /* device [B][max_hops + 1][RD_ACQ_NPART]: a wavefront's sum of |D| over its cells of a block */
+    rd_acq_pmax *pmax;                                          /* device [B][max_hops][RD_ACQ_NPART]: a wavefront's best cell of a hop */
+    rd_acq_rec *rec;                                            /* device [B][max_hops] */
+    void *dt; long long t0; int n_rows;                         /* complex64 [B][n_rows][40] or NULL: D[t0 .. t0 + n_rows) */
+    int B, max_hops;                                            /* max_hops: the most hops any stream of the call has */
+} rd_acq_args;
+int rd_launch_acq_detect(const rd_acq_args *a, rd_stream_t s);
+typedef struct { long long t_abs; double fmax; int stream, pad; } rd_acq_ev;
+typedef struct { long long t; double f, Dmax; } rd_acq_fine;
+typedef struct {
+    const rd_tables *tab;                                       /* p */
+    const void *x; long x_stride;
+    const int *n;                                               /* device [B] */
+    const rd_acq_ev *ev;                                        /* device [n_events] */
+    rd_acq_fine *out;                                           /* device [n_events] */
+    double *dfine;                                              /* device [n_events][RD_ACQ_NFINE]: |Dt1| of the winning timing */
+    int n_events;
+} rd_acq_refine_args;
+int rd_launch_acq_refine(const rd_acq_refine_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

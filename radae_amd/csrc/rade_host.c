@@ -8,6 +8,7 @@
  *   5. the rational rate converter's ratio, taps and output count (rade_batch_rate_convert).
  *   6. the analog FM stage's noise level, least-squares filter design and folded de-emphasis (rade_batch_fm_mod / rade_batch_fm_demod).
  *   7. the C/No estimator's plan, table and host arithmetic, and the chirp header (rade_batch_cno_est, rade_chirp).
+ *   8. whole-file acquisition: the hop count, the state machine and the --acq_test statistics of rx.py (rade_acq_hops, rade_acq_track, rade_acq_stats).
  *
  * Reference: radae/radae.py:128-234 (numerology/DFT/pilots/EOO), radae/dsp.py:40-61 (BPF),
  * :153-176 (p_w), :400-416 (Pmat); blob format src/write_rade_weights.c:51-74 and
@@ -918,5 +919,55 @@ int rade_specgram_levels(double lo, double hi, float *out /* [255] */)
 {
     if (!out || !isfinite(lo) || !isfinite(hi) || !(0.0 < lo && lo < hi && hi <= 1.0)) return -1;
     for (int j = 1; j <= 255; j++) out[j - 1] = (float)(lo * pow(hi / lo, ((double)j - 0.5) / 255.0));
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * 8. whole-file pilot acquisition: the hop count, the state machine and the statistics of rx.py (include/rade_batch.h: rade_batch_acq_detect; rade_acq.hip)
+ * -------------------------------------------------------------------------------------------*/
+/* hops of `while len(rx) >= 2 Nmf + M + Ncp: ...; rx = rx[Nmf:-1]` */
+int rade_acq_hops(long long n) { return rd_acq_hops(n); }
+
+/* fcoarse_range[f_ind_max]; the script's fmax stays the integer 0 where no cell exceeded 0 */
+double rade_acq_fmax(const rade_acq_hop *hop) { return hop && hop->Dtmax12 > 0.0f ? -50.0 + 2.5 * hop->f_ind : 0.0; }
+
+/* rx.py:151-188 */
+int rade_acq_track(const rade_acq_hop *hops, int n_hops, int acq_test, rade_acq_event *events, int max_events, rade_acq_log *log_out)
+{
+    if (n_hops < 0 || max_events < 0 || (n_hops && !hops) || (max_events && !events)) return -1;
+    int state = 0, tmax_candidate = 0, valid_count = 0, n_ev = 0;
+    for (int k = 0; k < n_hops; k++) {
+        if (log_out) { log_out[k].state = state; log_out[k].tmax_candidate = tmax_candidate; log_out[k].valid_count = valid_count; }
+        int next = state;
+        if (state == 0) {
+            if (hops[k].candidate) { next = 1; tmax_candidate = hops[k].tmax; valid_count = 1; }
+        } else if (hops[k].candidate && fabs((double)(hops[k].tmax - tmax_candidate)) < 0.02 * RD_M) {
+            if (++valid_count > 3) {
+                if (n_ev < max_events) { events[n_ev].hop = k; events[n_ev].tmax = hops[k].tmax; events[n_ev].f_ind = hops[k].f_ind; }
+                n_ev++;
+                if (!acq_test) return n_ev;
+                next = 0;
+            }
+        } else next = 0;
+        state = next;
+    }
+    return n_ev;
+}
+
+/* rx.py:134, :170-171, :190-195 */
+int rade_acq_stats(const rade_acq_event *events, const rade_acq_refined *refined, int n_events, int n_hops, int Ntap, double fmax_target, double acq_time_target,
+                   rade_acq_result *out)
+{
+    if (!out || n_events < 0 || n_hops < 0 || (n_events && (!events || !refined)) || !isfinite(fmax_target)) return -1;
+    const double target = RD_NCP + Ntap / 2.0;
+    rade_acq_result r = { 0, 0, 0, 0.0, INFINITY };
+    for (int e = 0; e < n_events; e++) {
+        const double t = (double)(refined[e].t - (long long)RD_NMF * events[e].hop);
+        if (fabs(t - target) < 0.0025 * 8000.0 && fabs(refined[e].f - fmax_target) <= 5.0) r.passes++; else r.fails++;
+    }
+    if (r.passes + r.fails) r.pfail = (double)r.fails / (double)(r.passes + r.fails);
+    if (r.passes) r.mean_acq_time = ((double)RD_NMF * (double)(n_hops + 1) / 8000.0) / (double)r.passes;
+    r.passed = r.pfail < 0.2 && r.mean_acq_time < acq_time_target;
+    *out = r;
     return 0;
 }

@@ -1,6 +1,6 @@
 /*
  * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
- * rate converter, analog FM, the chirp header's C/No and the spectrogram.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * rate converter, analog FM, the chirp header's C/No, the spectrogram and the whole-file pilot acquisition.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
  * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
  * its device and pinned memory is on the engine's own list (rade_engine.h).
  *
@@ -89,6 +89,10 @@ struct rd_stages {
     /* rade_batch_specgram: the table e^{-2 pi i m / 2048} and the window behind it (made once); per call [B] counts, [255] thresholds and [B] given peaks in one
      * record; the [B] peaks */
     float *spec_tab; rd_pair spec_rec; float *spec_peak;
+    /* rade_batch_acq_detect / _refine: the [B] sample counts; [B][acq_cap + 1][RD_ACQ_NPART] block sums, [B][acq_cap][RD_ACQ_NPART] best cells and [B][acq_cap] hop
+     * records, grown with the call; a chunk of RD_ACQ_EV_CHUNK events, their results and their fine rows */
+    rd_pair acq_n; double *acq_psum; rd_acq_pmax *acq_pmax; rd_acq_rec *acq_rec; long acq_cap, acq_cap1, acq_cap2;
+    rd_pair acq_ev; rd_acq_fine *acq_fine; double *acq_dfine;
 };
 static struct rd_stages *stages_of(rade_batch *h)
 {
@@ -523,6 +527,107 @@ int rade_batch_specgram(rade_batch *h, const void *x_dev, long x_stride, const i
     for (int b = 0; b < B; b++) {
         peak_host[b] = p->peak_in_host ? p->peak_in_host[b] : pk[b];
         n_slices_host[b] = (int)rade_specgram_slices(n_host[b]);
+    }
+    return 0;
+}
+
+/* ---- whole-file pilot acquisition: every hop of rx.py's frame loop, and acquisition.refine for a list of events (rade_acq.hip; the state machine and the statistics:
+ * rade_host.c) ---------------------------------------------------------------------------------------------------------------------------------------------------- */
+_Static_assert(RD_CORRQ16_HALFS == 2 * 10 * 2 * 64 * 8 && RD_CORRA16_HALFS == 5 * 2 * 64 * 8, "the table sizes k_acq_detect copies to LDS (rade_acq.hip)");
+int rade_batch_acq_detect(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, double Pacq_error1, rade_acq_hop *hops_host, int max_hops, int *n_hops_host,
+                          void *dt_dev, long long t0, int n_rows, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || !hops_host || !n_hops_host || (((uintptr_t)x_dev | (uintptr_t)dt_dev) & 7)) return -1;
+    if (!(Pacq_error1 > 0.0 && Pacq_error1 < 5.0)) return -1;
+    if (dt_dev && (t0 < 0 || n_rows < 1 || t0 + n_rows > x_stride)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    int maxh = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride) return -1;
+        const int nh = rd_acq_hops(n);
+        if (nh > max_hops) return -1;
+        if (nh > maxh) maxh = nh;
+        if (nh) work += 2.0 * 16 * 16 * 32 * 85 * (RD_NMF / 16) * (nh + 1.0);      /* 85 matrix instructions per tile of 16 timings and block */
+    }
+    const rd_acq_rec *rec = NULL;          /* [B][maxh], read back */
+    if (maxh) {
+        struct rd_stages *s = stages_of(h);
+        int *n_stage = s ? pair_host(h, &s->acq_n, sizeof(int) * B) : NULL;
+        if (!n_stage) return -1;
+        if (dev_grow(h, &s->acq_psum, &s->acq_cap, maxh, sizeof(double) * RD_ACQ_NPART * B * 2, 1)) return -1;      /* maxh + 1 <= 2 maxh blocks */
+        if (dev_grow(h, &s->acq_pmax, &s->acq_cap1, maxh, sizeof(rd_acq_pmax) * RD_ACQ_NPART * B, 1)) return -1;
+        if (dev_grow(h, &s->acq_rec, &s->acq_cap2, maxh, sizeof(rd_acq_rec) * B, 1)) return -1;
+        memcpy(n_stage, n_host, sizeof(int) * B);
+        if (pair_push(h, &s->acq_n, sizeof(int) * B, 0, st)) return -1;              /* not waited for here: the call waits at its end */
+        rd_acq_args a;
+        memset(&a, 0, sizeof a);
+        a.corrq16 = h->corrq16; a.corra16 = h->corra16; a.x = x_dev; a.x_stride = x_stride; a.n = s->acq_n.dev; a.psum = s->acq_psum; a.pmax = s->acq_pmax; a.rec = s->acq_rec;
+        a.dt = dt_dev; a.t0 = t0; a.n_rows = n_rows; a.B = B; a.max_hops = maxh;
+        PROF_BEGIN(h, stream);
+        const int e = rd_launch_acq_detect(&a, stream);
+        PROF_END(h, stream, RADE_PROF_CHAN, work);         /* booked with the other front-end stages, as C/No and the spectrogram are: the profile's classes are the
+                                                            * benchmark's (rade_batch_profile), and a run that mixes channel and acquisition calls sees both under `channel` */
+        /* the records come back and the stream is waited for (also where the launch failed: the staging copy above is then free again) */
+        if (e || !(rec = read_back(h, s->acq_rec, sizeof(rd_acq_rec) * B * maxh, st))) { settle(st); return -1; }
+    } else if (settle(st)) return -1;
+    const double k = 2.0 * sqrt(-log(Pacq_error1 / 5.0));
+    for (int b = 0; b < B; b++) {
+        const int nh = rd_acq_hops(n_host[b]);
+        n_hops_host[b] = nh;
+        for (int j = 0; j < nh; j++) {
+            const rd_acq_rec *r = &rec[(size_t)b * maxh + j];
+            rade_acq_hop *o = &hops_host[(size_t)b * max_hops + j];
+            const double sigma_r = (r->S1 + r->S2) / (double)(RD_NMF * RD_NFC) / sqrt(M_PI / 2.0) / 2.0;
+            o->Dtmax12 = r->best; o->Dthresh = k * sigma_r; o->tmax = r->key >> 6; o->f_ind = r->key & 63; o->candidate = (double)r->best > o->Dthresh;
+            o->S1 = r->S1; o->S2 = r->S2;
+        }
+    }
+    return 0;
+}
+
+int rade_batch_acq_refine(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, const rade_acq_refine_in *events_host, int n_events,
+                          rade_acq_refined *out_host, double *dfine_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || n_events < 0 || (n_events && (!events_host || !out_host)) || ((uintptr_t)x_dev & 7)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    for (int b = 0; b < B; b++) if (n_host[b] < 0 || n_host[b] > x_stride) return -1;
+    for (int e = 0; e < n_events; e++) {   /* every event is checked before anything is launched or written */
+        const rade_acq_refine_in *v = &events_host[e];
+        if (v->stream < 0 || v->stream >= B || v->t_abs > (1LL << 40) || v->t_abs < -(1LL << 40) || !isfinite(v->fmax)) return -1;
+    }
+    if (!n_events) return settle(st);
+    struct rd_stages *s = stages_of(h);
+    int *n_stage = s ? pair_host(h, &s->acq_n, sizeof(int) * B) : NULL;
+    rd_acq_ev *ev = s ? pair_host(h, &s->acq_ev, sizeof(rd_acq_ev) * RD_ACQ_EV_CHUNK) : NULL;
+    if (!n_stage || !ev) return -1;
+    if (dev_grow(h, &s->acq_fine, NULL, RD_ACQ_EV_CHUNK, sizeof(rd_acq_fine), 1) || dev_grow(h, &s->acq_dfine, NULL, (long)RD_ACQ_EV_CHUNK * RD_ACQ_NFINE, sizeof(double), 1)) return -1;
+    memcpy(n_stage, n_host, sizeof(int) * B);
+    if (pair_push(h, &s->acq_n, sizeof(int) * B, 0, st)) return -1;
+    for (int e0 = 0; e0 < n_events; e0 += RD_ACQ_EV_CHUNK) {                         /* a chunk per launch; each chunk's read-back waits for the stream */
+        const int ne = n_events - e0 < RD_ACQ_EV_CHUNK ? n_events - e0 : RD_ACQ_EV_CHUNK;
+        memset(ev, 0, sizeof(rd_acq_ev) * RD_ACQ_EV_CHUNK);
+        for (int e = 0; e < ne; e++) { ev[e].t_abs = events_host[e0 + e].t_abs; ev[e].fmax = events_host[e0 + e].fmax; ev[e].stream = events_host[e0 + e].stream; ev[e].pad = 0; }
+        if (pair_push(h, &s->acq_ev, sizeof(rd_acq_ev) * RD_ACQ_EV_CHUNK, 0, st)) { settle(st); return -1; }      /* the whole chunk: the device copy is sized by its first push */
+        rd_acq_refine_args a;
+        memset(&a, 0, sizeof a);
+        a.tab = h->d_tab; a.x = x_dev; a.x_stride = x_stride; a.n = s->acq_n.dev; a.ev = s->acq_ev.dev; a.out = s->acq_fine; a.dfine = s->acq_dfine; a.n_events = ne;
+        PROF_BEGIN(h, stream);
+        const int err = rd_launch_acq_refine(&a, stream);
+        PROF_END(h, stream, RADE_PROF_CHAN, 8.0 * 2 * RD_M * 3 * RD_ACQ_NFINE * ne);
+        const rd_acq_fine *res = err ? NULL : read_back(h, s->acq_fine, sizeof(rd_acq_fine) * ne, st);
+        if (!res) { settle(st); return -1; }
+        for (int e = 0; e < ne; e++) { out_host[e0 + e].t = res[e].t; out_host[e0 + e].f = res[e].f; out_host[e0 + e].Dmax = res[e].Dmax; }
+        if (dfine_host) {
+            const double *d = read_back(h, s->acq_dfine, sizeof(double) * RD_ACQ_NFINE * ne, st);
+            if (!d) { settle(st); return -1; }
+            memcpy(dfine_host + (size_t)e0 * RD_ACQ_NFINE, d, sizeof(double) * RD_ACQ_NFINE * ne);
+        }
     }
     return 0;
 }

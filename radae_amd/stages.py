@@ -1,5 +1,5 @@
 """The front-end stages of the batched engine, the Python mirror of radae_amd/csrc/rade_stages.c: rate-Rs channel, resampler, sound-card wire, rate converter, analog FM,
-C/No of the chirp header and the spectrogram.
+C/No of the chirp header, the spectrogram and the whole-file pilot acquisition (its driver: radae_amd/acq.py).
 
 Three layers: the host-only helpers of each stage (`*_count`, `*_taps`, `*_plan`, ..: no handle, no GPU); BatchStages, the plain base class that gives BatchEngine one
 method per stage call (it uses only self.lib, self.h, self.B and self.device, so this module does not import engine.py); and the classes that apply a stateless stage to
@@ -13,8 +13,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .abi import (FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, WIRE_IQ, WIRE_REAL, CnoParams,
-                  CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, ResampleParams, SpecgramParams, SpecgramPlan, load_library)
+from .abi import (FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, WIRE_IQ, WIRE_REAL, AcqEvent, AcqHop, AcqLog,
+                  AcqRefined, AcqRefineIn, AcqResult, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, ResampleParams, SpecgramParams, SpecgramPlan, load_library)
 
 
 class WireMeters(NamedTuple):
@@ -164,6 +164,39 @@ def specgram_levels(lo: float = SPEC_LO, hi: float = SPEC_HI) -> np.ndarray:
     if load_library().rade_specgram_levels(float(lo), float(hi), t.ctypes.data):
         raise ValueError(f"rade_specgram_levels refuses lo {lo!r}, hi {hi!r} (0 < lo < hi <= 1)")
     return t
+
+
+def acq_hops(n: int) -> int:
+    """rade_acq_hops: the frames rx.py's loop visits in n samples (hop k while n - 961 k >= 2112)."""
+    return int(load_library().rade_acq_hops(int(n)))
+
+
+def acq_fmax(hops: np.ndarray) -> np.ndarray:
+    """rade_acq_fmax of every record: -50 + 2.5 f_ind, and the script's 0.0 where no cell exceeded 0."""
+    return np.where(hops["Dtmax12"] > 0, -50.0 + 2.5 * hops["f_ind"], 0.0)
+
+
+def acq_track(hops: np.ndarray, acq_test: bool = False):
+    """rade_acq_track over one stream's hop records (a 1-D record array of abi.AcqHop): (events, log), record arrays of abi.AcqEvent (hop, tmax, f_ind) and of
+    abi.AcqLog [n_hops] (state 0 search / 1 candidate, tmax_candidate, valid_count as the script prints them in the hop's line).  Host only."""
+    hops = np.ascontiguousarray(hops, np.dtype(AcqHop))
+    assert hops.ndim == 1
+    ev = np.zeros(max(len(hops), 1), np.dtype(AcqEvent))
+    log = np.zeros(max(len(hops), 1), np.dtype(AcqLog))
+    k = load_library().rade_acq_track(hops.ctypes.data, len(hops), int(bool(acq_test)), ev.ctypes.data, len(ev), log.ctypes.data)
+    if k < 0:
+        raise ValueError("rade_acq_track refused its arguments")
+    return ev[:k], log[:len(hops)]
+
+
+def acq_stats(events: np.ndarray, refined: np.ndarray, n_hops: int, ntap: int = 101, fmax_target: float = 0.0, acq_time_target: float = 1.0) -> AcqResult:
+    """rade_acq_stats: passes, fails, pfail, mean_acq_time and passed of rx.py --acq_test (host only).  ntap: 101 with the input band-pass, 0 without."""
+    events = np.ascontiguousarray(events, np.dtype(AcqEvent)); refined = np.ascontiguousarray(refined, np.dtype(AcqRefined))
+    assert events.ndim == 1 and events.shape == refined.shape
+    r = AcqResult()
+    if load_library().rade_acq_stats(events.ctypes.data, refined.ctypes.data, len(events), int(n_hops), int(ntap), float(fmax_target), float(acq_time_target), C.byref(r)):
+        raise ValueError("rade_acq_stats refused its arguments")
+    return r
 
 
 def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
@@ -348,6 +381,53 @@ class BatchStages:
                                         mg.data_ptr() if mag else None, W * (SPEC_NFFT // 2 - 1), pk.ctypes.data, ns.ctypes.data, _stream_ptr()):
             raise RuntimeError("rade_batch_specgram failed (every stream needs more than 1280 samples; a finite gain; given peaks finite and >= 0; an output to write)")
         return (im, ns, pk, mg) if mag else (im, ns, pk)
+
+    # ---- whole-file pilot acquisition ---------------------------------------------------------------
+    def acq_detect(self, x, n=None, pacq_error1: float = 1e-5, dt_rows=None):
+        """detect_pilots over every hop of every stream (rade_batch_acq_detect, rx.py:146-150).  x: cuda complex64 [B, S]; n: samples of each stream (a scalar or B values,
+        default S).  Returns (hops, n_hops): hops a numpy record array [B, H] of abi.AcqHop (Dtmax12, Dthresh, tmax, f_ind, candidate, S1, S2), H = the most hops any
+        stream has (at least 1), n_hops int32 [B].  dt_rows=(t0, n_rows): also the complex64 surface D[t0 .. t0 + n_rows) of every stream as a third value, cuda
+        [B, n_rows, 40], zeros where a stream has no such row.  The call synchronises the current stream."""
+        import torch
+        B = self.B
+        assert _is_rows(x, B, torch.complex64)
+        S = x.shape[1]
+        n = _counts(B, n, S, "n")
+        H = max(max(acq_hops(v) for v in n), 1)
+        hops = np.zeros((B, H), np.dtype(AcqHop))
+        nh = np.zeros(B, np.int32)
+        dt, t0, nr = None, 0, 0
+        if dt_rows is not None:
+            t0, nr = int(dt_rows[0]), int(dt_rows[1])
+            dt = torch.zeros((B, max(nr, 1), 40), dtype=torch.complex64, device=x.device)
+        if self.lib.rade_batch_acq_detect(self.h, x.data_ptr(), _row_stride(x, S), n.ctypes.data, float(pacq_error1), hops.ctypes.data, H, nh.ctypes.data,
+                                          dt.data_ptr() if dt is not None else None, t0, nr, _stream_ptr()):
+            raise RuntimeError("rade_batch_acq_detect failed (0 < pacq_error1 < 5; with dt_rows, t0 >= 0, n_rows >= 1 and t0 + n_rows within the row of x)")
+        return (hops, nh) if dt is None else (hops, nh, dt)
+
+    def acq_refine(self, x, events, n=None, want_dfine: bool = False):
+        """acquisition.refine for a list of events (rade_batch_acq_refine).  x: cuda complex64 [B, S]; events: a sequence of (stream, t_abs = 960 hop + tmax, fmax).
+        Returns a numpy record array [E] of abi.AcqRefined (t, f, Dmax); with want_dfine also float64 [E, 80], |Dt1| of the winning timing.  Synchronises the stream."""
+        import torch
+        B = self.B
+        assert _is_rows(x, B, torch.complex64)
+        S = x.shape[1]
+        n = _counts(B, n, S, "n")
+        E = len(events)
+        ev = np.zeros(max(E, 1), np.dtype(AcqRefineIn))
+        for i, (b, t, f) in enumerate(events):
+            ev[i] = (int(b), int(t), float(f))
+        out = np.zeros(max(E, 1), np.dtype(AcqRefined))
+        df = np.zeros((max(E, 1), 80), np.float64) if want_dfine else None
+        if self.lib.rade_batch_acq_refine(self.h, x.data_ptr(), _row_stride(x, S), n.ctypes.data, ev.ctypes.data, E, out.ctypes.data,
+                                          df.ctypes.data if want_dfine else None, _stream_ptr()):
+            raise RuntimeError("rade_batch_acq_refine failed (an event's stream inside the batch, |t_abs| <= 2^40, a finite fmax)")
+        return (out[:E], df[:E]) if want_dfine else out[:E]
+
+    acq_hops = staticmethod(lambda n: acq_hops(n))
+    acq_track = staticmethod(lambda hops, acq_test=False: acq_track(hops, acq_test))
+    acq_stats = staticmethod(lambda events, refined, n_hops, ntap=101, fmax_target=0.0, acq_time_target=1.0: acq_stats(events, refined, n_hops, ntap, fmax_target,
+                                                                                                                      acq_time_target))
 
     # ---- analog FM ----------------------------------------------------------------------------------------------------------
     def fm_mod(self, m, Fs: float, fc: float, fd: float, n=None, real: bool = False, sigma: float = 0.0, seed: int = 0, noise=None, phase0=0, n0=0, out=None,
