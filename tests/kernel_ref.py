@@ -314,3 +314,18 @@ def frag_untouched_except(buf, before, idx_list, what):
     if bad.size:
         b, o = bad[0]
         raise AssertionError(f"{what}: {len(bad)} half-words written outside the documented positions, the first in stream {b} at tile {o // EF_TILE}, offset {o % EF_TILE}")
+
+
+# ---- reports and checks shared by the kernel unit tests -------------------------------------------------------------------------------------------------------------
+def first_bad(bad, what, got, want, extra=""):
+    b, t, n = np.argwhere(bad)[0]
+    return f"{what}: {int(bad.sum())} elements differ, the first at stream {b}, step {t}, column {n}: got {got[b, t, n]!r}, reference {want[b, t, n]!r}{extra}"
+
+
+def encf_check_exact(got, planes, want, what):
+    if planes is None:
+        bad = got.view(np.int32) != want.view(np.int32)
+    else:
+        whi, wlo = split16(want)
+        bad = (planes[0] != whi) | (planes[1] != wlo)
+    assert not bad.any(), first_bad(bad, what, got, want)

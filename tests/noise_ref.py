@@ -18,6 +18,10 @@ import numpy as np
 M0, M1 = 0xD2511F53, 0xCD9E8D57            # the two multipliers of Philox4x32 (table 2)
 W0, W1 = 0x9E3779B9, 0xBB67AE85            # the Weyl key increments: golden ratio, sqrt(3) - 1
 MASK = np.uint64(0xFFFFFFFF)
+# the bar of the device's gauss_pair against the float64 Box-Muller of the same uniforms (tests/test_device_noise_gpu.py states how it is used)
+EPS_MEASURED = 7.093e-07   # largest |device - float64 reference| of gauss_pair over test_probe_gauss_pair's inputs on the MI355X: at u = (0x91b1, 0xc1765566), the sine
+#                            component, reference -4.824733 (1.5 float32 ulps there); random pairs 7.093e-07, the crossed extremes 4.069e-07
+EPS = 3e-6                 # 4 x EPS_MEASURED = 2.84e-06 rounded up to one digit; must stay <= 1e-4
 # philox4x32-10 in the Random123 distribution's known-answer file: counter / key -> output
 KNOWN_ANSWERS = [
     ((0x00000000, 0x00000000, 0x00000000, 0x00000000), (0x00000000, 0x00000000), (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),

@@ -13,48 +13,13 @@ import pytest
 
 import acq_ref as R
 from bands import Band
+from gpu_kit import dev, engines, pack, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 WORST_MEASURED = 0.0177                # largest |dD| / bound over test_surface on the MI355X
 NMF, M = 960, 160
 KK = 2 * np.sqrt(-np.log(1e-5 / 5)) / (NMF * 40) / np.sqrt(np.pi / 2) / 2          # Dthresh = KK (S1 + S2)
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the calls use none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(B):
-        if B not in made:
-            made[B] = BatchEngine(B, max_tx_mf=1)
-        return made[B]
-    yield get
-    for e in made.values():
-        e.close()
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(a, device=torch_dev)
-
-
-def pack(rows):
-    """rows of different length -> ([B, max] complex64 padded with zeros, n int32 [B])"""
-    n = np.array([len(r) for r in rows], np.int32)
-    x = np.zeros((len(rows), int(n.max())), np.complex64)
-    for b, r in enumerate(rows):
-        x[b, :n[b]] = r
-    return x, n
 
 
 def raw_detect(eng, x_ptr, x_stride, n, pacq=1e-5, hops=None, max_hops=None, nh=None, dt_ptr=None, t0=0, n_rows=0, null_n=False, null_hops=False, null_nh=False):

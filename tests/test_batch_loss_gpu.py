@@ -7,15 +7,9 @@ import os
 import numpy as np
 import pytest
 
+from gpu_kit import REPO, engine, torch_dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def ragged(arrays, width=36):
@@ -47,18 +41,18 @@ def run_loss(eng, torch_dev, fs, hs, **kw):
                     n_in=[len(f) for f in fs], n_hat=[len(h) for h in hs], **kw)
 
 
-def bits(x):
+def dev_bits(x):
+    """gpu_kit.bits without the copy to the host: int32 words on the device, for torch.equal"""
     import torch
     return torch.view_as_real(x).contiguous().view(torch.int32) if x.is_complex() else x.contiguous().view(torch.int32)
 
 
-def test_loss_parity_ragged_golden_batch(torch_dev, golden, oracle):
+def test_loss_parity_ragged_golden_batch(engine, torch_dev, golden, oracle):
     """nine streams of 168..6000 input rows (20 or 36 columns) in one call: loss bit-equal to the oracle as a double, the same start; numpy within 1e-6"""
-    from radae_amd.engine import BatchEngine
     from radae_amd.loss import find_loss
     pairs = golden_pairs(golden)
     assert len(pairs) == 9 and {p[1].shape[1] for p in pairs} == {20, 36} and max(len(p[1]) for p in pairs) == 6000
-    eng = BatchEngine(len(pairs))
+    eng = engine(len(pairs))
     loss, start, fl = run_loss(eng, torch_dev, [p[1] for p in pairs], [p[2] for p in pairs])
     assert fl is None and loss.dtype == np.float64
     for b, (name, f, h) in enumerate(pairs):
@@ -66,14 +60,12 @@ def test_loss_parity_ragged_golden_batch(torch_dev, golden, oracle):
         assert loss[b] == lo and start[b] == so, (name, loss[b], lo, start[b], so)
         ln, sn = find_loss(f, h)
         assert sn == so and abs(ln - lo) <= 1e-6 * lo, (name, ln, lo)
-    eng.close()
 
 
-def test_frame_loss_curve(torch_dev, golden, oracle):
+def test_frame_loss_curve(engine, torch_dev, golden, oracle):
     """loss.py:85-90: distortion_loss of each frame pair at the chosen start, n_hat - start frames, bit-equal to the oracle's; NaN after"""
-    from radae_amd.engine import BatchEngine
     pairs = golden_pairs(golden)
-    eng = BatchEngine(len(pairs))
+    eng = engine(len(pairs))
     loss, start, fl = run_loss(eng, torch_dev, [p[1] for p in pairs], [p[2] for p in pairs], frame_loss=True)
     fl = fl.cpu().numpy()
     assert fl.shape == (len(pairs), max(len(p[2]) for p in pairs))
@@ -83,12 +75,10 @@ def test_frame_loss_curve(torch_dev, golden, oracle):
         want = np.array([oracle.distortion_loss(c20(f[s + k:s + k + 1]), c20(h[k:k + 1])) for k in range(n)])
         assert np.array_equal(fl[b, :n].astype(np.float64), want), name
         assert np.all(np.isnan(fl[b, n:])), name
-    eng.close()
 
 
-def test_edge_cases(torch_dev, oracle):
+def test_edge_cases(engine, torch_dev, oracle):
     from radae_amd.channel_tools import synth_features
-    from radae_amd.engine import BatchEngine
     rng = np.random.default_rng(5)
     base = synth_features(11, 400)
     noisy = lambda a: (a + 0.05 * rng.standard_normal(a.shape)).astype(np.float32)
@@ -103,7 +93,7 @@ def test_edge_cases(torch_dev, oracle):
         ("best at n_in - n_hat", base[:120], base[80:120]),                          # exact match only at the offset the reference never tries
         ("tied offsets", period[:300], noisy(period[23:223])),
     ]
-    eng = BatchEngine(len(cases))
+    eng = engine(len(cases))
     loss, start, _ = run_loss(eng, torch_dev, [c[1] for c in cases], [c[2] for c in cases])
     for b, (name, f, h) in enumerate(cases):
         if not 0 < len(h) <= len(f):
@@ -115,42 +105,37 @@ def test_edge_cases(torch_dev, oracle):
     assert start[6] != 80 and loss[6] > 0.0
     assert oracle.distortion_loss(c20(period[3:203]), c20(cases[7][2])) == oracle.distortion_loss(c20(period[13:213]), c20(cases[7][2]))
     assert start[7] == 3                                                           # the earliest of the tied offsets 3, 13, 23, ...
-    eng.close()
 
 
-def test_clip_start_clip_end(torch_dev, golden, oracle):
+def test_clip_start_clip_end(engine, torch_dev, golden, oracle):
     """loss.py --clip_start / --clip_end: features_hat[clip_start : n_hat - clip_end]; a stream clipped to nothing is not scored"""
-    from radae_amd.engine import BatchEngine
     pairs = golden_pairs(golden)
     fs, hs = [p[1] for p in pairs], [p[2] for p in pairs]
     hs[0] = hs[0][:20]                                                            # 20 rows: nothing left after clipping 12 + 10
-    eng = BatchEngine(len(pairs))
+    eng = engine(len(pairs))
     loss, start, fl = run_loss(eng, torch_dev, fs, hs, clip_start=12, clip_end=10, frame_loss=True)
     assert np.isnan(loss[0]) and start[0] == -1 and np.all(np.isnan(fl[0].cpu().numpy()))
     for b in range(1, len(pairs)):
         lo, so = oracle.find_loss(c20(fs[b]), c20(hs[b][12:len(hs[b]) - 10]))
         assert loss[b] == lo and start[b] == so, pairs[b][0]
-    eng.close()
 
 
-def test_stream_results_do_not_depend_on_the_batch(torch_dev, golden):
+def test_stream_results_do_not_depend_on_the_batch(engine, torch_dev, golden):
     """a stream alone (B = 1) gives what it gives inside B = 64 with other lengths around it, bit for bit (frame curve included)"""
-    from radae_amd.engine import BatchEngine
     pairs = golden_pairs(golden)
     B = 64
     fs = [pairs[b % 9][1][b // 9:] for b in range(B)]
     hs = [pairs[b % 9][2][:max(len(pairs[b % 9][2]) - 11 * (b // 9), 0)] for b in range(B)]
-    eng = BatchEngine(B)
+    eng = engine(B)
     loss, start, fl = run_loss(eng, torch_dev, fs, hs, frame_loss=True)
     fl = fl.cpu().numpy()
-    one = BatchEngine(1)
+    one = engine(1)
     for b in range(B):
         l1, s1, f1 = run_loss(one, torch_dev, [fs[b]], [hs[b]], frame_loss=True)
         assert np.array_equal(l1, loss[b:b + 1], equal_nan=True) and s1[0] == start[b], b
         n = f1.shape[1]
         assert np.array_equal(f1.cpu().numpy()[0], fl[b, :n], equal_nan=True), b
     assert np.sum(start >= 0) >= 48
-    eng.close(); one.close()
 
 
 SIG = np.float32([0.0, 0.05, 0.1, 0.2, 0.3, 0.15, 0.07, 0.4])
@@ -158,15 +143,14 @@ FOFF = np.float32([0.0, -11.0, 5.5, 20.0, -3.25, 0.0, 37.0, -50.0])
 DFDT = np.float32([0.0, 0.5, -0.8, 0.0, 1.5, -2.0, 0.25, 0.0])
 
 
-def test_per_stream_channel_equals_uniform_channel(torch_dev):
+def test_per_stream_channel_equals_uniform_channel(engine, torch_dev):
     """B = 8, eight distinct (sigma, freq_offset, df_dt) triples: stream b of the per-stream call is bit-equal to stream b of a uniform call with its values --
     with and without G, noise framing and the EOO frame, explicit noise and Philox, rade_batch_channel and both paths of rade_batch_tx_channel"""
     import torch
     from radae_amd.channel_tools import synth_features
-    from radae_amd.engine import BatchEngine
     B, n_mf = 8, 4
     n_sig = n_mf * 960
-    eng = BatchEngine(B, max_tx_mf=n_mf)
+    eng = engine(B, max_tx_mf=n_mf)
     feats = torch.tensor(np.stack([synth_features(100 + b, 12 * n_mf) for b in range(B)]), device=torch_dev)
     eng.tx_reset()
     iq = eng.tx(feats)
@@ -181,7 +165,7 @@ def test_per_stream_channel_equals_uniform_channel(torch_dev):
         per = eng.channel(iq, SIG, FOFF, df_dt=DFDT, **kw)
         for b in range(B):
             uni = eng.channel(iq, float(SIG[b]), float(FOFF[b]), df_dt=float(DFDT[b]), **kw)
-            assert torch.equal(bits(per[b]), bits(uni[b])), ("channel", G_ is not None, pre, explicit, b)
+            assert torch.equal(dev_bits(per[b]), dev_bits(uni[b])), ("channel", G_ is not None, pre, explicit, b)
     for G_ in (G, None):                                                          # fused modulator + channel; the two calls back to back
         kw = dict(n_pre=800, n_post=1152, with_eoo=True, G=G_, seed=5)
         eng.tx_reset()
@@ -189,21 +173,20 @@ def test_per_stream_channel_equals_uniform_channel(torch_dev):
         for b in range(B):
             eng.tx_reset()
             uni = eng.tx_channel(feats, float(SIG[b]), float(FOFF[b]), df_dt=float(DFDT[b]), **kw)
-            assert torch.equal(bits(per[b]), bits(uni[b])), ("tx_channel", G_ is not None, b)
+            assert torch.equal(dev_bits(per[b]), dev_bits(uni[b])), ("tx_channel", G_ is not None, b)
     # a scalar among sequences is every stream's value; a wrong B is refused before anything runs
     part = eng.channel(iq, SIG, 0.0, G=G, seed=77)
-    assert torch.equal(bits(part[3]), bits(eng.channel(iq, float(SIG[3]), 0.0, G=G, seed=77)[3]))
+    assert torch.equal(dev_bits(part[3]), dev_bits(eng.channel(iq, float(SIG[3]), 0.0, G=G, seed=77)[3]))
     with pytest.raises(ValueError):
         eng.channel(iq, SIG[:7], 0.0)
-    eng.close()
 
 
-def test_loss_curve_in_one_batch(torch_dev):
+def test_loss_curve_in_one_batch(engine, torch_dev):
     """4 Eb/No points x {AWGN, MPP} x 2 utterances = 16 streams through one tx_channel -> rx -> loss pass.  Each condition applied uniformly to the same
     batch (same features, G, seed) gives its streams bit-equal decoded features; every stream's device loss and start equal numpy find_loss's."""
     import torch
     from radae_amd.channel_tools import synth_features
-    from radae_amd.engine import BatchEngine, sigma_from_EbNodB
+    from radae_amd.engine import sigma_from_EbNodB
     from radae_amd.loss import find_loss
     B, n_mf = 16, 12
     n_sig = n_mf * 960
@@ -213,7 +196,7 @@ def test_loss_curve_in_one_batch(torch_dev):
     dfdt = np.zeros(B, np.float32)
     feats_np = np.stack([synth_features(500 + c[2], 12 * n_mf) for c in conds])
     feats = torch.tensor(feats_np, device=torch_dev)
-    eng = BatchEngine(B, max_tx_mf=n_mf)
+    eng = engine(B, max_tx_mf=n_mf)
     G = eng.multipath_gen("mpp", n_sig, seed=9)
     awgn = [b for b, c in enumerate(conds) if c[1] == "awgn"]
     G[awgn, :, 0] = 1.0                                                           # G covers all streams or none: (1, 0) rows for the AWGN streams
@@ -241,5 +224,4 @@ def test_loss_curve_in_one_batch(torch_dev):
         fu, su = run(float(sig[k]), float(foff[k]), float(dfdt[k]))
         for b in (k, k + 1):
             n = st[b].n_valid
-            assert su[b].n_valid == n and torch.equal(bits(fu[b, :n]), bits(fo[b, :n])), conds[b]
-    eng.close()
+            assert su[b].n_valid == n and torch.equal(dev_bits(fu[b, :n]), dev_bits(fo[b, :n])), conds[b]

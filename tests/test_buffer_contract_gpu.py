@@ -12,40 +12,15 @@ import numpy as np
 import pytest
 
 from bands import Band
+from gpu_kit import INT_KEYS, bits, crandn, engine, stream, sync, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-INT_KEYS = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count", "uw_errors", "synced_count", "snr_int"]
 TX_BPF, BYPASS_DEC = 0x400, 0x800
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def odd(n):
     return n | 1
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def stream():
-    from radae_amd.engine import _stream_ptr
-    return _stream_ptr()
-
-
-def bits(t):
-    """a torch tensor or numpy array as int32 words on the host"""
-    import torch
-    if isinstance(t, torch.Tensor):
-        t = (torch.view_as_real(t) if t.is_complex() else t).contiguous().cpu().numpy()
-    return np.ascontiguousarray(t).reshape(t.shape[0], -1).view(np.int32)
 
 
 class Inputs:
@@ -71,10 +46,6 @@ class Inputs:
 def feats(B, n_mf, seed=3):
     from radae_amd.channel_tools import synth_features
     return np.stack([synth_features(seed + b, 12 * n_mf) for b in range(B)]).astype(np.float32)
-
-
-def cnoise(rng, *shape):
-    return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) / np.sqrt(2)).astype(np.complex64)
 
 
 # ---- transmit side ------------------------------------------------------------------------------------------------------------------------------------
@@ -154,13 +125,12 @@ def test_encode_decode(torch_dev):
     eng.close()
 
 
-def test_encoder_large_and_small_calls(torch_dev):
+def test_encoder_large_and_small_calls(engine, torch_dev):
     """B = 72 x n_mf = 84 = 18144 rows reaches rade_enc.hip's 16-byte stores into z_out_dev (max_tx_mf = 90: capacity unused); one modem frame on the same engine
     takes the float32-row kernels.  Both: guards around z_out and iq_out intact, bit-equal to the dense call after the matching reset."""
     import torch
-    from radae_amd.engine import BatchEngine
     B, cap = 72, 90
-    eng = BatchEngine(B, max_tx_mf=cap)
+    eng = engine(B, max_tx_mf=cap)
     L, h = eng.lib, eng.h
     for n_mf in (84, 1):
         f = feats(B, n_mf, seed=40)
@@ -179,7 +149,6 @@ def test_encoder_large_and_small_calls(torch_dev):
         sync()
         z.check(what=f"z_out, n_mf {n_mf}"); iq.check(what=f"iq_out, n_mf {n_mf}"); ins.unchanged()
         assert np.array_equal(z.rows().reshape(B, -1), bits(z_d)) and np.array_equal(iq.rows(), bits(iq_d))
-    eng.close()
 
 
 # ---- channel -------------------------------------------------------------------------------------------------------------------------------------------
@@ -200,14 +169,13 @@ CHAN_CASES = [(0, 0, False, False, True), (1, 0, True, True, False), (801, 1152,
 
 @pytest.mark.parametrize("flags", [0, TX_BPF])
 @pytest.mark.parametrize("B", [3, 5])
-def test_channel_calls(torch_dev, B, flags):
+def test_channel_calls(engine, torch_dev, B, flags):
     """rade_batch_channel and rade_batch_channel_streams: banded rx_out and tx_dev, G and noise at an 8-byte offset, n_total even and odd, with and without
     G_dev, with_eoo, explicit noise and Philox"""
     import torch
-    from radae_amd.engine import BatchEngine
     n_mf = 2; n_sig = 960 * n_mf
     rng = np.random.default_rng(7)
-    eng = BatchEngine(B, max_tx_mf=n_mf, flags=flags)
+    eng = engine(B, max_tx_mf=n_mf, flags=flags)
     L, h = eng.lib, eng.h
     tx_d = eng.tx(torch.tensor(feats(B, n_mf), device=torch_dev))
     tx_np = tx_d.cpu().numpy()
@@ -215,8 +183,8 @@ def test_channel_calls(torch_dev, B, flags):
     took = set()
     for n_pre, n_post, with_eoo, with_G, with_noise in CHAN_CASES:
         n_total = n_pre + n_sig + (1152 if with_eoo else 0) + n_post
-        G_np = cnoise(rng, B, n_sig, 2) if with_G else None
-        nz_np = cnoise(rng, B, n_total) if with_noise else None
+        G_np = crandn(rng, B, n_sig, 2) if with_G else None
+        nz_np = crandn(rng, B, n_total) if with_noise else None
         seed = 0 if with_noise else 11
         kw = dict(n_pre=n_pre, n_post=n_post, with_eoo=with_eoo, G=torch.tensor(G_np, device=torch_dev) if with_G else None,
                   noise=torch.tensor(nz_np, device=torch_dev) if with_noise else None, seed=seed)
@@ -239,7 +207,6 @@ def test_channel_calls(torch_dev, B, flags):
             assert np.array_equal(rx.rows(), bits(rx_d)), (n_pre, n_post, with_eoo, with_G, with_noise, streams)
             took |= {((rx.ptr + 8 * b * rx.stride) % 16 == 0, n_total % 2) for b in range(B)}
     assert took == {(True, 0), (True, 1), (False, 0), (False, 1)}      # the 16-byte and the 8-byte store, each with and without the tail store
-    eng.close()
 
 
 @pytest.mark.parametrize("flags", [0, TX_BPF])
@@ -253,12 +220,12 @@ def test_tx_channel_calls(torch_dev, flags, with_G):
     n_sig, n_pre, n_post = 960 * n_mf, 801, 1152
     rng = np.random.default_rng(8)
     f = feats(B, n_mf, seed=9)
-    G_np = cnoise(rng, B, n_sig, 2) if with_G else None
+    G_np = crandn(rng, B, n_sig, 2) if with_G else None
     per = {"sigma": np.array([0.2, 0.5, 0.8], np.float32), "freq_offset": np.array([5, -7, 31], np.float32), "df_dt": np.array([0, 0.5, -0.5], np.float32)}
     for streams in (False, True):
         with_eoo = not streams
         n_total = n_pre + n_sig + (1152 if with_eoo else 0) + n_post
-        nz_np = cnoise(rng, B, n_total)
+        nz_np = crandn(rng, B, n_total)
         eng = BatchEngine(B, max_tx_mf=cap, flags=flags)
         L, h = eng.lib, eng.h
         rx_d, iq_d = eng.tx_channel(torch.tensor(f, device=torch_dev), per["sigma"] if streams else 0.3, per["freq_offset"] if streams else -9.0, n_pre, n_post, with_eoo,
@@ -289,19 +256,18 @@ def test_tx_channel_calls(torch_dev, flags, with_G):
         eng.close()
 
 
-def test_per_stream_channel_values_across_workgroups_of_64(torch_dev):
+def test_per_stream_channel_values_across_workgroups_of_64(engine, torch_dev):
     """B = 65: stream 64 is the first of k_chan_gain's second workgroup.  Its row of a per-stream call (banded, odd stride, odd n_total, Philox noise keyed by
     (seed, stream)) equals, bit for bit, its row of a uniform call carrying its values -- rade_batch_channel_streams and rade_batch_tx_channel_streams."""
     import torch
-    from radae_amd.engine import BatchEngine
     B, n_mf = 65, 1
     n_sig, n_pre, n_post = 960, 1, 0
     n_total = n_pre + n_sig + 1152 + n_post
     rng = np.random.default_rng(65)
     f = feats(B, n_mf, seed=100)
-    G_np = cnoise(rng, B, n_sig, 2)
+    G_np = crandn(rng, B, n_sig, 2)
     per = {"sigma": rng.uniform(0.1, 1.0, B).astype(np.float32), "freq_offset": rng.uniform(-40, 40, B).astype(np.float32), "df_dt": rng.uniform(-1, 1, B).astype(np.float32)}
-    eng = BatchEngine(B, max_tx_mf=2)
+    eng = engine(B, max_tx_mf=2)
     L, h = eng.lib, eng.h
     ft, Gt = torch.tensor(f, device=torch_dev), torch.tensor(G_np, device=torch_dev)
     tx_d = eng.tx(ft)
@@ -326,15 +292,14 @@ def test_per_stream_channel_values_across_workgroups_of_64(torch_dev):
         uni, uiq = eng.tx_channel(ft, float(per["sigma"][b]), float(per["freq_offset"][b]), n_pre, n_post, True, G=Gt, seed=5, df_dt=float(per["df_dt"][b]), want_iq=True)
         assert np.array_equal(rx2.rows()[b], bits(uni)[b]), b
         assert np.array_equal(iq.rows(), bits(uiq))
-    eng.close()
 
 
-def test_channel_8_byte_store_branch_against_the_oracle(torch_dev, oracle, oracle_model):
+def test_channel_8_byte_store_branch_against_the_oracle(engine, torch_dev, oracle, oracle_model):
     """odd rx_stride, odd n_total, explicit noise: stream 1's row starts 8 bytes off a 16-byte boundary, so k_chan_apply writes it with the two 8-byte stores and
     the tail store.  Its samples against oracle.channel + oracle.channel_eoo at test_full_chain_vs_oracle_fresh_inputs' bar (max abs < 5e-5)."""
     import torch
     from radae_amd.channel_tools import multipath_g
-    from radae_amd.engine import BatchEngine, sigma_from_EbNodB
+    from radae_amd.engine import sigma_from_EbNodB
     B, n_mf = 2, 4
     n_sig, n_pre, n_post = 960 * n_mf, 801, 1152
     n_total = n_pre + n_sig + 1152 + n_post
@@ -342,9 +307,9 @@ def test_channel_8_byte_store_branch_against_the_oracle(torch_dev, oracle, oracl
     rng = np.random.default_rng(31)
     f = feats(B, n_mf, seed=50)
     G_np = np.stack([multipath_g("mpp", 8000, n_sig, 60 + b) for b in range(B)]).astype(np.complex64)
-    nz_np = cnoise(rng, B, n_total)
+    nz_np = crandn(rng, B, n_total)
     sigma, fo = sigma_from_EbNodB(6.0), -11.0
-    eng = BatchEngine(B, max_tx_mf=n_mf)
+    eng = engine(B, max_tx_mf=n_mf)
     L, h = eng.lib, eng.h
     tx_d = eng.tx(torch.tensor(f, device=torch_dev))
     ins = Inputs(torch_dev)
@@ -364,19 +329,17 @@ def test_channel_8_byte_store_branch_against_the_oracle(torch_dev, oracle, oracl
     got = rx.rows(np.complex64)[1]
     print("8-byte-store branch against the oracle: max abs", np.abs(got - full).max())
     assert np.abs(got - full).max() < 5e-5
-    eng.close()
 
 
 # ---- symbol-domain channels and the Doppler generator -----------------------------------------------------------------------------------------------------
-def test_channel_symbol_and_multipath(torch_dev):
+def test_channel_symbol_and_multipath(engine, torch_dev):
     """rade_batch_channel_symbol (both modes), rade_batch_multipath_gen, rade_batch_multipath_h: guards around the outputs, inputs untouched; n_out not a
     multiple of low_ratio and the smallest n_out (1: two low-rate points are still made)"""
     import torch
     from radae_amd.channel_tools import PRESETS, doppler_plan
-    from radae_amd.engine import BatchEngine
     B, n = 3, 5
     rng = np.random.default_rng(12)
-    eng = BatchEngine(B, max_tx_mf=2)
+    eng = engine(B, max_tx_mf=2)
     L, h = eng.lib, eng.h
     z_np = np.tanh(rng.standard_normal((B, n, 80))).astype(np.float32)
     zt = torch.tensor(z_np, device=torch_dev)
@@ -406,7 +369,7 @@ def test_channel_symbol_and_multipath(torch_dev):
             sync(); G.check(what=f"G_out n_out {n_out}"); ins.unchanged()
             assert np.array_equal(G.rows().reshape(B, -1), bits(d)), (n_out, explicit)
     n_g, M, n_sym, Nc = 25, 4, 7, 3
-    G_np = cnoise(rng, B, n_g, 2)
+    G_np = crandn(rng, B, n_g, 2)
     Gt = torch.tensor(G_np, device=torch_dev)
     for cplx in (0, 1):
         d = torch.empty((B, n_sym * Nc * (1 + cplx)), dtype=torch.float32, device=torch_dev)
@@ -417,7 +380,6 @@ def test_channel_symbol_and_multipath(torch_dev):
         assert L.rade_batch_multipath_h(h, Gb.ptr, n_g, M, n_sym, Nc, 0.002, 2000.0, cplx, H.ptr, stream()) == n_sym
         sync(); H.check(what="H_out"); ins.unchanged()
         assert np.array_equal(H.rows().reshape(B, -1), bits(d)) and np.isfinite(H.rows(np.float32)).all()
-    eng.close()
 
 
 # ---- receivers ------------------------------------------------------------------------------------------------------------------------------------------
@@ -479,17 +441,17 @@ def test_rx(torch_dev, golden, name, flags):
 
 
 @pytest.mark.parametrize("n_mf", [2, 9])
-def test_rx_ideal(torch_dev, golden, n_mf):
+def test_rx_ideal(engine, torch_dev, golden, n_mf):
     """rade_batch_rx_ideal: rx_stride > n_mf * 960 (odd, odd sample offset), n_mf = 2 (the minimum) and a larger one, guards around z_hat_dev and
     features_out_dev, n_errors_host written for exactly B entries (host guards)"""
     import torch
-    from radae_amd.engine import BatchEngine, IdealRxParams
+    from radae_amd.engine import IdealRxParams
     g = golden("chan_mpp")
     B = 3
     rx_np = np.stack([np.roll(g["rx"][:n_mf * 960 + 960], -960 * b)[:n_mf * 960] for b in range(B)]).astype(np.complex64)
     fo_np = np.array([float(g["freq_offset"]), 0.0, -3.0], np.float32); df_np = np.array([0.0, 0.5, 0.0], np.float32)
     zref_np = np.sign(np.random.default_rng(1).standard_normal((B, 3 * n_mf, 80))).astype(np.float32)
-    eng = BatchEngine(B, max_tx_mf=12)
+    eng = engine(B, max_tx_mf=12)
     L, h = eng.lib, eng.h
     f_d, z_d, e_d = eng.rx_ideal(torch.tensor(rx_np, device=torch_dev), n_mf, freq_offset=fo_np, df_dt=df_np, z_ref=torch.tensor(zref_np, device=torch_dev))
     assert e_d.min() > 0
@@ -513,16 +475,14 @@ def test_rx_ideal(torch_dev, golden, n_mf):
     assert L.rade_batch_rx_ideal(h, xb.ptr, xb.stride, n_mf, C.byref(p), zh2.ptr, None, stream()) == n_mf
     sync(); zh2.check(what="z_hat without the decoder"); ins.unchanged()
     assert np.array_equal(zh2.rows().reshape(B, -1), bits(z_d))
-    eng.close()
 
 
 # ---- scoring ----------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("f_row,h_row", [(20, 36), (36, 37), (37, 20)])
-def test_loss(torch_dev, oracle, f_row, h_row):
+def test_loss(engine, torch_dev, oracle, f_row, h_row):
     """rade_batch_loss: f_row / h_row in {20, 36, 37}, f_stride / h_stride above the minimum, fl_stride larger than every n_hat; frame-loss entries past
     n_hat - start and the rows of unscored streams stay sentinel; loss_host / start_host between host guards; loss and start equal oracle.find_loss"""
     from radae_amd.channel_tools import synth_features
-    from radae_amd.engine import BatchEngine
     rng = np.random.default_rng(5)
     base = synth_features(11, 400)[:, :20]
     noisy = lambda a: (a + 0.05 * rng.standard_normal(a.shape)).astype(np.float32)
@@ -537,7 +497,7 @@ def test_loss(torch_dev, oracle, f_row, h_row):
             out[b, :len(a), :20] = a
         return out
     F, H = pack([c[0] for c in cases], f_row), pack([c[1] for c in cases], h_row)
-    eng = BatchEngine(B)
+    eng = engine(B)
     L, h = eng.lib, eng.h
     ins = Inputs(torch_dev)
     Fb = ins.put(F, 4, stride=F.shape[1] * f_row + 13); Hb = ins.put(H, 4, stride=H.shape[1] * h_row + 7)
@@ -568,7 +528,6 @@ def test_loss(torch_dev, oracle, f_row, h_row):
     fl3 = Band(B, int(n_hat.max()) - 1, int(n_hat.max()) - 1, 4, torch_dev)
     assert L.rade_batch_loss(h, Fb.ptr, Fb.stride, f_row, n_in.ctypes.data, Hb.ptr, Hb.stride, h_row, n_hat.ctypes.data, loss.ptr, start.ptr, fl3.ptr, fl3.stride, stream()) < 0
     sync(); fl3.untouched("frame_loss of a refused call")
-    eng.close()
 
 
 # ---- single-carrier modem ---------------------------------------------------------------------------------------------------------------------------------
@@ -585,7 +544,7 @@ def test_sc_tx_rx(torch_dev):
     n = NF * 384
     rx_np = np.zeros((B, n + 40), np.complex64)
     for b in range(B):
-        rx_np[b, 7 * b:7 * b + n] = tx_d.cpu().numpy()[b] * np.exp(1j * (0.3 + b)) + 0.02 * cnoise(rng, n)
+        rx_np[b, 7 * b:7 * b + n] = tx_d.cpu().numpy()[b] * np.exp(1j * (0.3 + b)) + 0.02 * crandn(rng, n)
     F = NF + 2
     pay_d, zh_d, fr_d, st_d = m.rx(torch.tensor(rx_np, device=torch_dev), max_frames=F)
     m.close()

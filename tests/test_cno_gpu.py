@@ -17,53 +17,16 @@ import pytest
 
 import cno_ref as cr
 from bands import Band
+from gpu_kit import INT_KEYS, REPO, dev, engines, pack, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden", "cno.npz")
-INT_KEYS = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count", "uw_errors", "synced_count", "snr_int"]
 WORST_MEASURED = 6.45e-4               # largest |dS| / bound over test_band_sums_against_the_restatement on the MI355X (8 s window, 1000-1000.9 Hz; 2.3e-5 at the defaults)
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the call uses none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(B):
-        if B not in made:
-            made[B] = BatchEngine(B, max_tx_mf=1)
-        return made[B]
-    yield get
-    for e in made.values():
-        e.close()
 
 
 @pytest.fixture(scope="module")
 def golden():
     return np.load(GOLDEN)
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(a, device=torch_dev)
-
-
-def pack(rows):
-    """rows of different length -> ([B, max] complex64 padded with zeros, n int32 [B])"""
-    n = np.array([len(r) for r in rows], np.int32)
-    x = np.zeros((len(rows), int(n.max())), np.complex64)
-    for b, r in enumerate(rows):
-        x[b, :n[b]] = r
-    return x, n
 
 
 def raw_call(eng, x_ptr, x_stride, n, wt=4.0, fl=400.0, fh=2000.0, bands=None, max_windows=0, res=None, null_n=False, null_p=False, null_res=False):

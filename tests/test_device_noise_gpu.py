@@ -13,22 +13,14 @@ import numpy as np
 import pytest
 
 import noise_ref as nr
+from gpu_kit import torch_dev  # noqa: F401
+from noise_ref import EPS
 
 pytestmark = pytest.mark.gpu
 
-EPS_MEASURED = 7.093e-07   # largest |device - float64 reference| of gauss_pair over test_probe_gauss_pair's inputs on the MI355X: at u = (0x91b1, 0xc1765566), the sine
-#                            component, reference -4.824733 (1.5 float32 ulps there); random pairs 7.093e-07, the crossed extremes 4.069e-07
-EPS = 3e-6                 # 4 x EPS_MEASURED = 2.84e-06 rounded up to one digit; must stay <= 1e-4
 NEOO = 1152
 B = 3
 EXTREMES = np.array([0, 1, 1 << 24, (1 << 24) + 1, 0x7fffffff, 0x80000000, 0xfffffffe, 0xffffffff], np.uint32)
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -73,7 +65,7 @@ def dev_err(got, ref):
     return float(np.abs(got.astype(np.float64) - ref).max())
 
 
-def cmax(d):
+def max_part(d):
     """largest component (not modulus) of a complex difference: the bar is per real sample"""
     assert np.isfinite(d.real).all() and np.isfinite(d.imag).all()
     return float(max(np.abs(d.real).max(), np.abs(d.imag).max()))
@@ -152,11 +144,11 @@ def test_fs_odd_total_and_real_noise_outside_the_signal(eng, torch_dev):
     out = np.r_[0:n_pre, n_pre + n_sig:1461]
     assert np.all(rx[:, out].imag == 0.0)
     gx = ref[:, out].real                                        # the full g.x outside
-    hold(cmax(rx[:, out] - gx), EPS, "n_pre and n_post")
-    hold(cmax(rx - ref), EPS, "whole output")
+    hold(max_part(rx[:, out] - gx), EPS, "n_pre and n_post")
+    hold(max_part(rx - ref), EPS, "whole output")
     for b in range(B):                                           # every stream is its own b, and no other
         for c in range(B):
-            assert (cmax(rx[b] - ref[c]) <= EPS) == (b == c)
+            assert (max_part(rx[b] - ref[c]) <= EPS) == (b == c)
 
 
 def test_fs_grid_wraps(eng, torch_dev):
@@ -164,7 +156,7 @@ def test_fs_grid_wraps(eng, torch_dev):
     n_pre, n_sig = 301, 18 * 960
     rx = fs_noise(eng, torch_dev, n_sig, 5, n_pre=n_pre)
     assert rx.shape[1] > 16384
-    hold(cmax(rx - nr.chan_fs(5, B, n_pre, n_sig, 0, 0)), EPS)
+    hold(max_part(rx - nr.chan_fs(5, B, n_pre, n_sig, 0, 0)), EPS)
 
 
 def test_fs_seed_words(eng, torch_dev):
@@ -172,10 +164,10 @@ def test_fs_seed_words(eng, torch_dev):
     seeds = [5, (1 << 32) + 5, 5 << 32]
     rx = [fs_noise(eng, torch_dev, 960, s, n_pre=301, n_post=200) for s in seeds]
     for s, r in zip(seeds, rx):
-        hold(cmax(r - nr.chan_fs(s, B, 301, 960, 0, 200)), EPS, hex(s))
+        hold(max_part(r - nr.chan_fs(s, B, 301, 960, 0, 200)), EPS, hex(s))
     for i in range(3):
         for j in range(i):
-            assert cmax(rx[i] - rx[j]) > 1.0
+            assert max_part(rx[i] - rx[j]) > 1.0
 
 
 def test_fs_per_stream_sigma(eng, torch_dev):
@@ -183,7 +175,7 @@ def test_fs_per_stream_sigma(eng, torch_dev):
     rx = fs_noise(eng, torch_dev, 960, 5, sigma=sig, n_pre=301, n_post=200)
     ref = nr.chan_fs(5, B, 301, 960, 0, 200)
     for b in range(2):
-        hold(cmax(rx[b] - float(sig[b]) * ref[b]), float(sig[b]) * EPS, f"stream {b}")
+        hold(max_part(rx[b] - float(sig[b]) * ref[b]), float(sig[b]) * EPS, f"stream {b}")
     assert np.all(rx[2].view(np.float32) == 0.0)
 
 
@@ -195,7 +187,7 @@ def test_fs_end_of_over_frame(eng, torch_dev):
     assert np.abs(rx0[:, 301 + 960:301 + 960 + NEOO]).max() > 0.1 and np.all(rx0[:, :301 + 960] == 0)
     ulp = float(np.spacing(np.float32(np.abs(rx0).max())))
     d = rx.astype(np.complex128) - rx0.astype(np.complex128)
-    hold(cmax(d - nr.chan_fs(5, B, 301, 960, NEOO, 200)), EPS + ulp)
+    hold(max_part(d - nr.chan_fs(5, B, 301, 960, NEOO, 200)), EPS + ulp)
 
 
 def test_fs_fused_transmit_with_multipath(eng, torch_dev):
@@ -212,7 +204,7 @@ def test_fs_fused_transmit_with_multipath(eng, torch_dev):
     assert np.abs(rx0[:, 301:301 + 1920]).max() > 0.1
     ulp = float(np.spacing(np.float32(np.abs(rx0).max())))
     d = rx.astype(np.complex128) - rx0.astype(np.complex128)
-    hold(cmax(d - nr.chan_fs(5, B, 301, 2 * 960, NEOO, 200)), EPS + ulp)
+    hold(max_part(d - nr.chan_fs(5, B, 301, 2 * 960, NEOO, 200)), EPS + ulp)
 
 
 def test_fs_seed_zero_is_noiseless(eng, torch_dev):
@@ -291,7 +283,7 @@ def test_doppler_generator(eng, torch_dev, channel, n_out, seed):
             y = np.convolve(low[b, p].astype(np.complex128), taps)[len(taps):len(taps) + n_low]
             var += np.var(y[i0] + (y[i0 + 1] - y[i0]) * (pos - i0))
         bar = EPS * np.abs(taps).sum() / np.sqrt(var) + 2e-5
-        hold(cmax(G_seed[b].astype(np.complex128) - G_ref[b]), bar, f"stream {b}")
+        hold(max_part(G_seed[b].astype(np.complex128) - G_ref[b]), bar, f"stream {b}")
     flat = [G_seed[b, :, p] for b in range(B) for p in range(2)]
     for i in range(len(flat)):
         for j in range(i):

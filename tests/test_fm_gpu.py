@@ -12,20 +12,17 @@ EPS_CIS and EPS_ATAN follow the convention of tests/test_device_noise_gpu.py: fo
 Other figures of the same run, each far inside its bound: modulator samples 5.6e-08 from the float64 phasor; stage 1 7.1e-07 (bound 2.7e-05); stage 2 6.6e-07 with the clamp and
 9.9e-07 with ph_dont_limit (bound 2.7e-05); end to end 6.3e-07 at 96 kHz, C/N 20 dB (bound 9.8e-04); generated noise 1.35e-07 from sigma x the reference noise at sigma 0.25."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import fm_ref as fr
 from bands import Band
-from test_device_noise_gpu import EPS as NOISE_EPS          # the bar of gauss_pair against the float64 Box-Muller
+from gpu_kit import bits, crandn, define, dev, engines, torch_dev  # noqa: F401
+from noise_ref import EPS as NOISE_EPS          # the bar of gauss_pair against the float64 Box-Muller
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_HDR = open(os.path.join(REPO, "radae_amd", "csrc", "rade_dev.h")).read()
-TILE, NMAX = (int(re.search(r"#define %s (\d+)" % k, _HDR).group(1)) for k in ("RD_FM_TILE", "RD_FM_NMAX"))
+TILE, NMAX = define("RD_FM_TILE"), define("RD_FM_NMAX")
 
 EPS_CIS_MEASURED = 7.753e-08     # largest |device phasor - float64 phasor| over test_probe_phasor_and_atan2's phases on the MI355X: at phase 0x1ca0d4c7
 EPS_CIS = 4 * EPS_CIS_MEASURED
@@ -36,28 +33,6 @@ FS, FC, FD, FM_MAX = 48000.0, 12000.0, 5000.0, 3000.0
 B = 3
 N = np.array([2 * TILE + 37, 2 * TILE + 1, TILE + 513], np.int32)          # about two tiles plus an odd remainder, unequal
 NMAXS = int(N.max())
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the calls use none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(nb):
-        if nb not in made:
-            made[nb] = BatchEngine(nb, max_tx_mf=1)
-        return made[nb]
-    yield get
-    for e in made.values():
-        e.close()
 
 
 @pytest.fixture(scope="module")
@@ -78,20 +53,6 @@ def ref():
                 v.setflags(write=False)
         return made[(Fs, fc)]
     return get
-
-
-def crandn(rng, *shape):
-    return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) / np.sqrt(2)).astype(np.complex64)
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=torch_dev)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32)
 
 
 def cmax(a):

@@ -3,38 +3,21 @@ against (1) golden vectors captured from the imported reference and (2) the CPU 
 
 Bars (BASELINE.json north_star): discrete sync outputs bit-exact; float32 features within 1e-4 RMS."""
 import os
+
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from gpu_kit import INT_KEYS, REPO, Engine, engine, rms, torch_dev  # noqa: F401
 
-INT_KEYS = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count", "uw_errors", "synced_count", "snr_int"]
+pytestmark = pytest.mark.gpu
 RX_CASES = ["awgn", "mpp", "slip_plus", "slip_minus", "foff"]
 
 
-def rms(a, b):
-    return float(np.sqrt(np.mean(np.abs(np.asarray(a, np.complex128) - np.asarray(b, np.complex128)) ** 2)))
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def Engine():
-    from radae_amd.engine import BatchEngine
-    return BatchEngine
-
-
-def test_encoder_tx_golden(Engine, torch_dev, golden):
+def test_encoder_tx_golden(engine, torch_dev, golden):
     import torch
     e = golden("enc_tx")
     f = torch.tensor(e["features"], device=torch_dev)
-    eng = Engine(2, max_tx_mf=10)
+    eng = engine(2, max_tx_mf=10)
     iq, z = eng.tx(f, want_z=True)
     zr, txr = e["z"], e["tx"]
     assert rms(z.cpu().numpy(), zr) < 1e-4
@@ -48,7 +31,6 @@ def test_encoder_tx_golden(Engine, torch_dev, golden):
     eng.tx_reset()
     parts = [eng.tx(f[:, 12 * a:12 * b].contiguous()) for a, b in ((0, 3), (3, 4), (4, 10))]
     assert torch.equal(torch.cat(parts, 1), iq)
-    eng.close()
 
 
 def test_encoder_large_batch_split_f16_gemm(Engine, torch_dev, oracle, oracle_model):
@@ -163,9 +145,9 @@ def test_encoder_fragment_layout_ragged_call_lengths(Engine, torch_dev, monkeypa
         assert torch.equal(z_f, z_r) and torch.equal(iq_f, iq_r)
 
 
-def test_eoo_frames(Engine, golden):
+def test_eoo_frames(engine, golden):
     c = golden("consts")
-    eng = Engine(3, max_tx_mf=1)
+    eng = engine(3, max_tx_mf=1)
     assert np.abs(eng.tx_eoo().cpu().numpy()[2] - c["eoo_default"]).max() < 1e-6
     bits = np.stack([c["eoo_bits_in"], -c["eoo_bits_in"], c["eoo_bits_in"]])
     eng.set_eoo_bits(bits)
@@ -174,14 +156,13 @@ def test_eoo_frames(Engine, golden):
     assert np.abs(out[1] - c["eoo_with_bits"]).max() > 0.1
     eng.set_eoo_bits(None)
     assert np.abs(eng.tx_eoo().cpu().numpy()[0] - c["eoo_default"]).max() < 1e-6
-    eng.close()
 
 
 @pytest.mark.parametrize("name", ["mpp", "awgn"])
-def test_channel_golden(Engine, torch_dev, golden, name):
+def test_channel_golden(engine, torch_dev, golden, name):
     import torch
     g = golden("chan_" + name)
-    eng = Engine(1, max_tx_mf=1)
+    eng = engine(1, max_tx_mf=1)
     sigma = float(g["sigma"])
     from radae_amd.engine import sigma_from_EbNodB
     assert sigma_from_EbNodB(float(g["EbNodB"])) == pytest.approx(sigma, rel=1e-6)
@@ -189,18 +170,17 @@ def test_channel_golden(Engine, torch_dev, golden, name):
     rx = eng.channel(torch.tensor(g["tx"][None], device=torch_dev), sigma, float(g["freq_offset"]), len(g["noise_pre"]), len(g["noise_post"]), True,
                      G=torch.tensor(g["G"][None], device=torch_dev), noise=torch.tensor(noise[None], device=torch_dev))
     assert np.abs(rx.cpu().numpy()[0] - g["rx_full"]).max() < 1e-5
-    eng.close()
 
 
 @pytest.mark.parametrize("name", ["dfdt_pos", "dfdt_neg"])
-def test_channel_df_dt_golden(Engine, torch_dev, golden, name):
+def test_channel_df_dt_golden(engine, torch_dev, golden, name):
     """Frequency drift (radae.py:547-552, inference.py:270; ctest radae_rx_dfdt) against RADAE.forward's output.  The kernel
     evaluates the phase sum in closed form (a thread cannot wait for 90 k predecessors); it differs from the reference's sum of
     per-sample float32 omegas by <= 2e-7 rad before both are rounded to float32 -- at ~800 rad one float32 step is 6e-5 rad, so a
     few samples land on the neighbouring float32 phase: RMS stays far inside 1e-5, single samples within 6e-5 x |sample|."""
     import torch
     g = golden("chan_" + name)
-    eng = Engine(1, max_tx_mf=1)
+    eng = engine(1, max_tx_mf=1)
     sigma = float(g["sigma"])
     noise = np.concatenate([g["noise_pre"].astype(np.complex64), g["noise"], g["noise_eoo"], g["noise_post"].astype(np.complex64)])
     rx = eng.channel(torch.tensor(g["tx"][None], device=torch_dev), sigma, float(g["freq_offset"]), len(g["noise_pre"]), len(g["noise_post"]), True,
@@ -208,15 +188,14 @@ def test_channel_df_dt_golden(Engine, torch_dev, golden, name):
     d = rx.cpu().numpy()[0] - g["rx_full"]
     assert rms(d, 0 * d) < 1e-5 and np.abs(d).max() < 2e-4
     assert np.mean(np.abs(d) > 1e-5) < 0.01
-    eng.close()
 
 
 @pytest.mark.parametrize("name", RX_CASES + ["dfdt", "nounsync"])
-def test_rx_trace_golden(Engine, torch_dev, golden, name, monkeypatch):
+def test_rx_trace_golden(engine, torch_dev, golden, name, monkeypatch):
     import torch
     g = golden("rxtrace_" + name)
     du = float(g["disable_unsync"]) if "disable_unsync" in g else 0.0       # radae_rxe.py --disable_unsync (ctests radae_rx_mpp / _mpg)
-    eng = Engine(1, max_tx_mf=1, rx_trace_calls=64, flags=(4 if name == "foff" else 0), disable_unsync=du)
+    eng = engine(1, max_tx_mf=1, rx_trace_calls=64, flags=(4 if name == "foff" else 0), disable_unsync=du)
     feats, st, eoo = eng.rx(torch.tensor(g["rx_in"][None], device=torch_dev))
     d = eng.rx_trace(0)
     for k in INT_KEYS:
@@ -233,20 +212,19 @@ def test_rx_trace_golden(Engine, torch_dev, golden, name, monkeypatch):
         assert st[0].has_eoo
         assert np.abs(eoo.cpu().numpy()[0] - g["eoo_out"][-1]).max() < 1e-4
         assert np.array_equal(eoo.cpu().numpy()[0] > 0, g["eoo_out"][-1] > 0)                   # EOO bit decisions
-    eng.close()
 
 
 @pytest.mark.parametrize("name", ["slipdrops", "dfs8001", "eoo_mpp"])
-def test_rx_trace_edge_cases(Engine, torch_dev, golden, name):
+def test_rx_trace_edge_cases(engine, torch_dev, golden, name):
     """The reference's remaining streaming ctests as golden traces (oracle/gen_golden_r6.py), whole trace bit-exact in one receiver launch:
     slipdrops = radae_rx_slip_plus_drops (CMakeLists.txt:397-407): 61 s of a real-valued int16 signal at 8020 Hz with three drop-outs; sync is lost and regained, 1120-sample
     calls all along, the last state is sync.  dfs8001 = radae_rx_dfs (:374-382).  eoo_mpp = radae_eoo_data_mpp (:595-607): the data bits of five end-of-over
     frames through MPP at the ctest's SNR, decisions equal to the reference's, one over below 5 % BER."""
     import torch
-    from test_oracle_golden import check_edge_trace, edge_case_input
+    from trace_ref import check_edge_trace, edge_case_input
     g = golden("rxtrace_" + name)
     x = edge_case_input(g)
-    eng = Engine(1, max_tx_mf=1, rx_trace_calls=len(g["ret"]) + 8)
+    eng = engine(1, max_tx_mf=1, rx_trace_calls=len(g["ret"]) + 8)
     feats, st, eoo = eng.rx(torch.tensor(x[None], device=torch_dev))
     d = eng.rx_trace(0)
     nv = st[0].n_valid
@@ -259,7 +237,6 @@ def test_rx_trace_edge_cases(Engine, torch_dev, golden, name):
         ber = np.array([np.mean(e * g["tx_bits"] < 0) for e in d["eoo_out"]])
         assert np.allclose(ber, g["eoo_ber"]) and ber.min() < 0.05 and np.abs(d["eoo_out"] - g["eoo_out"]).max() < 1e-4 * np.abs(g["eoo_out"]).max() + 1e-4
         assert np.array_equal(eoo.cpu().numpy()[0] > 0, g["eoo_out"][-1] > 0)
-    eng.close()
 
 
 def test_bypass_dec_and_bypass_enc(Engine, torch_dev, golden):
@@ -313,7 +290,7 @@ def test_bypass_dec_and_bypass_enc(Engine, torch_dev, golden):
 
 
 @pytest.mark.parametrize("name", ["slip_plus", "slip_minus", "mpp"])
-def test_bpf_prepass_matches_oracle_filter(Engine, torch_dev, golden, oracle, name):
+def test_bpf_prepass_matches_oracle_filter(engine, torch_dev, golden, oracle, name):
     """The band-pass filter runs ahead of the receiver kernel for a whole invocation (k_rx_bpf); a stream whose nin changes inside an invocation
     (timing slips) filters the rest itself (rx2_bpf_own).  Either way the receiver must have read what complex_bpf.bpf (dsp.py:63-102) produces
     for the stream's actual sequence of calls: compared with the oracle's filter driven with the traced call sizes (float32 rounding of a
@@ -321,7 +298,7 @@ def test_bpf_prepass_matches_oracle_filter(Engine, torch_dev, golden, oracle, na
     import torch
     g = golden("rxtrace_" + name)
     x = g["rx_in"]
-    eng = Engine(1, max_tx_mf=1, rx_trace_calls=128)
+    eng = engine(1, max_tx_mf=1, rx_trace_calls=128)
     eng.rx(torch.tensor(x[None], device=torch_dev))
     sizes = eng.rx_trace(0)["nin_before"]
     assert np.array_equal(sizes, g["nin_before"])
@@ -342,21 +319,19 @@ def test_bpf_prepass_matches_oracle_filter(Engine, torch_dev, golden, oracle, na
         assert s[0].consumed == k
         outs.append(eng.rx_filtered(0, int(k))); pos += int(k)
     assert np.array_equal(np.concatenate(outs), y)
-    eng.close()
 
 
-def test_bpf_prepass_golden(Engine, torch_dev, golden):
+def test_bpf_prepass_golden(engine, torch_dev, golden):
     """The pre-pass against the reference's own filter output (tests/golden/bpf.npz): the 960-sample calls a receiver in the search state makes."""
     import torch
     g = golden("bpf")
     n = 3 * 960
     assert list(g["sizes"][:3]) == [960, 960, 960]
-    eng = Engine(1, max_tx_mf=1)
+    eng = engine(1, max_tx_mf=1)
     _, s, _ = eng.rx(torch.tensor(g["x"][None, :n], device=torch_dev))
     assert s[0].consumed == n
     y = eng.rx_filtered(0, n)
     assert np.abs(y - g["y"][:n]).max() < 2e-6 * np.abs(g["y"]).max()
-    eng.close()
 
 
 def test_tx_bpf_and_clip_golden(Engine, torch_dev, golden, oracle, oracle_model):
@@ -385,7 +360,7 @@ def test_tx_bpf_and_clip_golden(Engine, torch_dev, golden, oracle, oracle_model)
     plain.close()
 
 
-def test_tx_bpf_single_stream_c_abi_and_channel_eoo(Engine, torch_dev, golden):
+def test_tx_bpf_single_stream_c_abi_and_channel_eoo(engine, torch_dev, golden):
     """The Tx band-pass filter + clip through the OTHER two doors: (i) the single-stream C ABI -- radae_amd.api.radae_tx(txbpf_en=True) = rade_open(flags |
     RADE_BATCH_TX_BPF), rade_tx() per frame and rade_tx_eoo() against the reference's own radae_tx(txbpf_en=True) output (tests/golden/txbpf.npz; radae_txe.py:74-83,
     :130-132, :141-143); (ii) the channel's with_eoo: the end-of-over frame a receiver sees behind the last frame is the FILTERED one, the filter state carried
@@ -404,7 +379,7 @@ def test_tx_bpf_single_stream_c_abi_and_channel_eoo(Engine, torch_dev, golden):
         api.radae_tx(handle=tx.h, txbpf_en=False)
     tx.h.close()
     f1 = torch.tensor(g["features"][None], device=torch_dev)
-    eng = Engine(1, max_tx_mf=n_mf, flags=0x400)
+    eng = engine(1, max_tx_mf=n_mf, flags=0x400)
     iq = eng.tx(f1)
     rx = eng.channel(iq, 0.0, 0.0, n_pre=0, n_post=0, with_eoo=True).cpu().numpy()[0]        # no noise, no offset, no multipath: gain 1 is not implied, so compare shapes
     gain = np.vdot(g["tx"], rx[:n_mf * 960]) / np.vdot(g["tx"], g["tx"])                      # the channel's power normalisation of the signal part
@@ -415,7 +390,6 @@ def test_tx_bpf_single_stream_c_abi_and_channel_eoo(Engine, torch_dev, golden):
     eng.tx_reset()
     rx2 = eng.tx_channel(f1, 0.0, 0.0, n_pre=0, n_post=0, with_eoo=True).cpu().numpy()[0]
     assert np.array_equal(rx2, rx)
-    eng.close()
 
 
 def test_transmit_side_is_bit_reproducible_under_load():
@@ -446,12 +420,12 @@ def test_blocking_wait_equals_spinning():
     assert spin["sha256"] == block["sha256"] == auto["sha256"] and spin["decoded"] > 0
 
 
-def test_rx_call_chunking_is_invariant(Engine, torch_dev, golden, monkeypatch):
+def test_rx_call_chunking_is_invariant(engine, torch_dev, golden, monkeypatch):
     """One do_radae_rx call per invocation (the rade_rx() usage) == the whole stream at once."""
     import torch
     g = golden("rxtrace_slip_plus")
     x = torch.tensor(g["rx_in"][None], device=torch_dev)
-    eng = Engine(1, max_tx_mf=1, rx_trace_calls=64)
+    eng = engine(1, max_tx_mf=1, rx_trace_calls=64)
     fa, sa, _ = eng.rx(x)
     ta = eng.rx_trace(0)
     eng.rx_reset()
@@ -467,7 +441,6 @@ def test_rx_call_chunking_is_invariant(Engine, torch_dev, golden, monkeypatch):
     for k in INT_KEYS:
         assert np.array_equal(ta[k], tb[k]), k
     assert np.array_equal(np.array(outs), fa.cpu().numpy()[0, :sa[0].n_valid])
-    eng.close()
 
 
 def test_uw_failures_and_launch_granularity(Engine, torch_dev, oracle, oracle_model, monkeypatch):
@@ -633,13 +606,13 @@ def test_unbounded_operands_do_not_overflow(Engine, torch_dev, oracle, oracle_mo
     eng.close()
 
 
-def test_rx_output_capacity_is_respected(Engine, torch_dev, golden, monkeypatch):
+def test_rx_output_capacity_is_respected(engine, torch_dev, golden, monkeypatch):
     """features_out rows are a capacity: a stream that has filled them pauses (consumed < available) instead of writing on;
     continuing with a fresh buffer gives the same frames as one big call."""
     import torch
     g = golden("rxtrace_awgn")
     x = torch.tensor(g["rx_in"][None], device=torch_dev)
-    eng = Engine(1, max_tx_mf=1)
+    eng = engine(1, max_tx_mf=1)
     full, st, _ = eng.rx(x)
     nv = st[0].n_valid
     assert nv == len(g["features_out"]) and nv > 6
@@ -650,7 +623,6 @@ def test_rx_output_capacity_is_respected(Engine, torch_dev, golden, monkeypatch)
     rest, st2, _ = eng.rx(x[:, st1[0].consumed:].contiguous())
     assert st2[0].n_valid == nv - 5
     assert torch.equal(torch.cat([part[0, :5], rest[0, :nv - 5]]), full[0, :nv])
-    eng.close()
 
 
 def _random_utterance(oracle, oracle_model, seed, chan, eb, fo, n_mf=24):
@@ -711,7 +683,7 @@ def test_refine_grid_length_follows_the_reference_doubles(Engine, torch_dev, ora
     assert disc and fmax_eq and feat_ok, (disc, fmax_eq, feat_ok)
 
 
-def test_streams_are_independent_and_ragged(Engine, torch_dev, golden, monkeypatch):
+def test_streams_are_independent_and_ragged(engine, torch_dev, golden, monkeypatch):
     """Identical streams give bit-identical outputs whatever their slot; ragged / empty inputs are handled."""
     import torch
     g = golden("rxtrace_awgn")
@@ -721,7 +693,7 @@ def test_streams_are_independent_and_ragged(Engine, torch_dev, golden, monkeypat
     avail = np.array([len(x), len(x), 5000, 0, 959], np.int32)
     for b in range(B):
         buf[b, :avail[b]] = x[:avail[b]]
-    eng = Engine(B, max_tx_mf=1, rx_trace_calls=64)
+    eng = engine(B, max_tx_mf=1, rx_trace_calls=64)
     feats, st, _ = eng.rx(torch.tensor(buf, device=torch_dev), n_avail=avail)
     assert st[0].n_calls == len(g["ret"]) and st[1].n_calls == st[0].n_calls
     assert torch.equal(feats[0], feats[1])
@@ -731,17 +703,16 @@ def test_streams_are_independent_and_ragged(Engine, torch_dev, golden, monkeypat
     t0, t2 = eng.rx_trace(0), eng.rx_trace(2)
     for k in INT_KEYS:
         assert np.array_equal(t0[k][:5], t2[k]), k
-    eng.close()
 
 
 @pytest.mark.parametrize("name,B", [("mpp", 96), ("foff", 96), ("mpp", 300)])
-def test_many_identical_streams_agree(Engine, torch_dev, golden, name, B):
+def test_many_identical_streams_agree(engine, torch_dev, golden, name, B):
     """Race / slot-dependence guard: many copies of one golden stream (96: more workgroups than fit one XCD; 300: more than
     the chip runs at once) must come out bit-identical in every slot, twice in a row, and equal to the golden trace."""
     import torch
     g = golden("rxtrace_" + name)
     buf = torch.tensor(np.stack([g["rx_in"]] * B), device=torch_dev)
-    eng = Engine(B, max_tx_mf=1, rx_trace_calls=64, flags=4 if name == "foff" else 0)
+    eng = engine(B, max_tx_mf=1, rx_trace_calls=64, flags=4 if name == "foff" else 0)
     for rep in range(2):
         eng.rx_reset()
         f, st, _ = eng.rx(buf)
@@ -753,7 +724,6 @@ def test_many_identical_streams_agree(Engine, torch_dev, golden, name, B):
             t = eng.rx_trace(b)
             for k in INT_KEYS:
                 assert np.array_equal(t[k], g[k]), (rep, b, k)
-    eng.close()
 
 
 def test_replicas_agree_over_many_fresh_launches(Engine, torch_dev):
@@ -841,7 +811,7 @@ def test_single_stream_c_abi(golden):
     h.close()
 
 
-def test_full_size_batch_properties(Engine, torch_dev, oracle, oracle_model, monkeypatch):
+def test_full_size_batch_properties(engine, torch_dev, oracle, oracle_model, monkeypatch):
     """BASELINE workload size (256 x 1008 frames): properties that do not need the oracle at full size,
     plus the oracle on two of the streams (loss delta < 1e-4)."""
     import torch
@@ -852,7 +822,7 @@ def test_full_size_batch_properties(Engine, torch_dev, oracle, oracle_model, mon
     n_mf = T // 12
     base = [synth_features(3000 + u, T) for u in range(8)]
     feats = np.stack([base[b % 8] for b in range(B)])                 # 8 distinct utterances, replicated 32x
-    eng = Engine(B, max_tx_mf=n_mf, rx_trace_calls=0)
+    eng = engine(B, max_tx_mf=n_mf, rx_trace_calls=0)
     iq = eng.tx(torch.tensor(feats, device=torch_dev))
     assert torch.equal(iq[:8], iq[248:256])                           # replicas bit-identical
     mag = iq.abs()
@@ -882,10 +852,9 @@ def test_full_size_batch_properties(Engine, torch_dev, oracle, oracle_model, mon
         l_o, s_o = find_loss(feats[b], d["features_out"].reshape(-1, 36))
         l_g, s_g = find_loss(feats[b], got.reshape(-1, 36))
         assert s_o == s_g and abs(l_o - l_g) < 1e-4                   # loss.py delta vs the oracle < 1e-4
-    eng.close()
 
 
-def test_config3_full_size_mpp_vs_oracle(Engine, torch_dev, oracle, oracle_model):
+def test_config3_full_size_mpp_vs_oracle(engine, torch_dev, oracle, oracle_model):
     """BASELINE.json configs[2] at full size inside `pytest -m gpu`, through the call bench.py times (rade_batch_tx_channel, one pass): 256 streams x 1008
     frames, MPP Doppler-spread two-path channel (G resident on the device), AWGN at Eb/No = 3 dB, -11 Hz, 1 s of noise in front, EOO frame + 1152 samples behind.
     The noise is an explicit tensor here (bench.py: device Philox), so that the oracle can be run on two of the streams: per-call discrete outputs equal,
@@ -905,7 +874,7 @@ def test_config3_full_size_mpp_vs_oracle(Engine, torch_dev, oracle, oracle_model
     nz = ((rng.standard_normal((nd, n_tot)) + 1j * rng.standard_normal((nd, n_tot))) / np.sqrt(2)).astype(np.complex64)
     noise = torch.tensor(np.concatenate([nz] * (B // nd)), device=torch_dev)
     sigma = sigma_from_EbNodB(3.0)
-    eng = Engine(B, max_tx_mf=n_mf, rx_trace_calls=128)
+    eng = engine(B, max_tx_mf=n_mf, rx_trace_calls=128)
     rx, iq = eng.tx_channel(torch.tensor(feats, device=torch_dev), sigma, -11.0, n_pre=n_pre, n_post=n_post, with_eoo=True, G=G, noise=noise, want_iq=True)
     fo, st, _ = eng.rx(rx)
     nv = np.array([s.n_valid for s in st])
@@ -931,10 +900,9 @@ def test_config3_full_size_mpp_vs_oracle(Engine, torch_dev, oracle, oracle_model
         l_o, s_o = find_loss(feats[b], d["features_out"].reshape(-1, 36))
         l_g, s_g = find_loss(feats[b], got.reshape(-1, 36))
         assert s_o == s_g and abs(l_o - l_g) < 1e-4                   # loss.py delta vs the oracle < 1e-4
-    eng.close()
 
 
-def test_device_multipath_generator(Engine, torch_dev):
+def test_device_multipath_generator(engine, torch_dev):
     """the Watterson / Doppler-spread generator on the device.  With the host generator's own low-rate
     noise as input it reproduces radae_amd.channel_tools.multipath_g (FIR, interpolation, hf_gain); from its Philox noise
     the statistics are right: var G1 + var G2 = 1 per stream and the autocorrelation exp(-(pi sigma tau)^2) of a process whose filter has the Gaussian
@@ -943,7 +911,7 @@ def test_device_multipath_generator(Engine, torch_dev):
     import torch
     from radae_amd.channel_tools import multipath_g, doppler_plan, PRESETS
     B, n = 6, 40 * 960
-    eng = Engine(B, max_tx_mf=1)
+    eng = engine(B, max_tx_mf=1)
     for ch in ("mpp", "mpd"):
         taps, ratio, n_low = doppler_plan(PRESETS[ch][0], 8000, n)
         noise = np.zeros((B, 2, n_low + len(taps)), np.complex64); ref = []
@@ -964,10 +932,9 @@ def test_device_multipath_generator(Engine, torch_dev):
         num = np.mean([np.real(np.vdot(G[b, :-lag, p], G[b, lag:, p])) / np.real(np.vdot(G[b, :, p], G[b, :, p])) for b in range(Bs) for p in range(2)])
         assert abs(num - np.exp(-(np.pi * sigma * tau) ** 2)) < tol, (tau, num)
     assert np.abs(G[0] - G[1]).max() > 0.1                 # streams are independent
-    eng.close()
 
 
-def test_lmr60_rate_rs_channel_matrix(Engine, torch_dev):
+def test_lmr60_rate_rs_channel_matrix(engine, torch_dev):
     """multipath_samples.m:17-21 + :33-40 (BBFM.md:37: `multipath_samples("lmr60", 8000, 2000, 1, 10, "h_lmr60.f32")`): the land-mobile preset (60 km/h at 450 MHz: 50 Hz spread,
     200 us) and the rate-Rs |H| the script derives from the rate-Fs Doppler samples, generated on the device.  10 s = 5334 low-rate points, more than the generator
     keeps in LDS (HBM scratch path).  With the host's noise as input it reproduces channel_tools.multipath_h; from Philox noise mean |H|^2 ~ 1 and the level-crossing
@@ -978,7 +945,7 @@ def test_lmr60_rate_rs_channel_matrix(Engine, torch_dev):
     n_g = (n_sym - 1) * 4 + 1
     taps, ratio, n_low = doppler_plan(PRESETS["lmr60"][0], 8000, n_g)
     assert ratio == 15 and n_low > 2048        # 2 * 450e6 * (60e3 / 3600 / 3e8) = 50.00000000000001 in doubles (Octave's too): lowFs = ceil(500.0000000000001) = 501 -> M = floor(8000 / 501) = 15
-    eng = Engine(B, max_tx_mf=1)
+    eng = engine(B, max_tx_mf=1)
     noise = np.zeros((B, 2, n_low + len(taps)), np.complex64); ref = []
     for b in range(B):
         rng = np.random.default_rng(60 + b)
@@ -999,21 +966,19 @@ def test_lmr60_rate_rs_channel_matrix(Engine, torch_dev):
         lcr = np.sum((Hp[b, :-1] ** 2 < 1.0) & (Hp[b, 1:] ** 2 > 1.0)) / 10.0
         th = np.sqrt(2 * np.pi / pav) * 25.0 * np.exp(-1.0 / pav)
         assert 0.75 * th < lcr < 1.25 * th, (lcr, th)
-    eng.close()
 
 
-def test_channel_sine_interferer_and_gain(Engine, torch_dev, golden):
+def test_channel_sine_interferer_and_gain(engine, torch_dev, golden):
     """inference.py:285-289: --sine_amp/--sine_freq add a complex tone over the whole output, --rx_gain scales it."""
     import torch
     e = golden("enc_tx")
-    eng = Engine(2, max_tx_mf=10)
+    eng = engine(2, max_tx_mf=10)
     iq = eng.tx(torch.tensor(e["features"], device=torch_dev))
     base = eng.channel(iq, 0.0, 0.0, n_pre=100, n_post=50).cpu().numpy()
     out = eng.channel(iq, 0.0, 0.0, n_pre=100, n_post=50, sine_amp=0.3, sine_freq=1234.5, rx_gain=0.5).cpu().numpy()
     nidx = np.arange(base.shape[1])
     want = 0.5 * (base + 0.3 * np.exp(1j * nidx * 2 * np.pi * 1234.5 / 8000.0)[None])
     assert np.abs(out - want).max() < 2e-6
-    eng.close()
 
 
 def test_impulses_in_the_receive_buffer(Engine, torch_dev, golden, oracle, oracle_model, monkeypatch):
@@ -1038,7 +1003,7 @@ def test_impulses_in_the_receive_buffer(Engine, torch_dev, golden, oracle, oracl
 
 
 @pytest.mark.parametrize("kind", ["noise", "sine"])
-def test_must_not_acquire(Engine, torch_dev, oracle, oracle_model, kind, monkeypatch):
+def test_must_not_acquire(engine, torch_dev, oracle, oracle_model, kind, monkeypatch):
     """The reference's acq_noise / acq_sine ctests (CMakeLists.txt:191-208): real-valued noise, or a 1 kHz sine in noise,
     converted with Q = 0 (int16tof32.py --zeropad), must never synchronise.  12 s per stream, 8 streams with different
     seeds; stream 0 is also checked call by call against the oracle."""
@@ -1049,7 +1014,7 @@ def test_must_not_acquire(Engine, torch_dev, oracle, oracle_model, kind, monkeyp
     if kind == "sine":
         x += 0.25 * np.cos(2 * np.pi * 1000.0 / 8000.0 * np.arange(n))[None]
     rx = x.astype(np.float32).astype(np.complex64)                     # Q == 0
-    eng = Engine(B, max_tx_mf=1, rx_trace_calls=128)
+    eng = engine(B, max_tx_mf=1, rx_trace_calls=128)
     f, st, _ = eng.rx(torch.tensor(rx, device=torch_dev))
     for b in range(B):
         assert st[b].n_calls == n // 960 and st[b].n_valid == 0 and st[b].sync == 0, (kind, b)
@@ -1059,10 +1024,9 @@ def test_must_not_acquire(Engine, torch_dev, oracle, oracle_model, kind, monkeyp
     for k in INT_KEYS:
         assert np.array_equal(t[k], d[k]), (kind, k)
     assert np.abs(t["Dtmax12"] - d["Dtmax12"]).max() < 3e-5 * max(1.0, np.abs(d["Dtmax12"]).max())
-    eng.close()
 
 
-def test_acquisition_statistics_mpp(Engine, torch_dev, monkeypatch):
+def test_acquisition_statistics_mpp(engine, torch_dev, monkeypatch):
     """rx.py --acq_test in batch form (rx.py:163-195, ctest acq_mpp): 64 utterances at 0 dB Eb/No on the MPP channel with
     a +10 Hz offset.  Every stream must find sync, in less than 1.5 s of signal on average, with the entry timing inside
     the 2.5 ms window and the coarse frequency within 5 Hz of the truth for at least 80 % of the streams."""
@@ -1072,7 +1036,7 @@ def test_acquisition_statistics_mpp(Engine, torch_dev, monkeypatch):
     B, n_mf, n_pre, fo = 64, 40, 4000, 10.0
     feats = np.stack([synth_features(300 + b, 12 * n_mf) for b in range(B)])
     G = np.stack([multipath_g("mpp", 8000, n_mf * 960, 900 + b) for b in range(B)])
-    eng = Engine(B, max_tx_mf=n_mf, rx_trace_calls=64)
+    eng = engine(B, max_tx_mf=n_mf, rx_trace_calls=64)
     iq = eng.tx(torch.tensor(feats, device=torch_dev))
     rx = eng.channel(iq, sigma_from_EbNodB(0.0), fo, n_pre=n_pre, n_post=1152, with_eoo=True, G=torch.tensor(G, device=torch_dev), seed=5)
     f, st, _ = eng.rx(rx)
@@ -1091,7 +1055,6 @@ def test_acquisition_statistics_mpp(Engine, torch_dev, monkeypatch):
     mean_t = (np.mean(acq_calls) + 1) * 0.12 - n_pre / 8000.0
     assert ok >= 0.8 * B, (ok, B)
     assert mean_t < 1.5, mean_t
-    eng.close()
 
 
 def _pipe(exe, args, data, cwd):
@@ -1175,7 +1138,7 @@ def test_multi_gpu_c_host_single_device(tmp_path, pipeline):
     assert j["samples_consumed"] > 12 * 20 * 800 and line["value"] > 0
 
 
-def test_model05_rate_rs_config1(Engine, torch_dev, golden):
+def test_model05_rate_rs_config1(engine, torch_dev, golden):
     """BASELINE config 1 on the GPU: model05 blob, bottleneck 1, rate-Rs symbol channel, stand-alone decoder."""
     import os
     import torch
@@ -1184,7 +1147,7 @@ def test_model05_rate_rs_config1(Engine, torch_dev, golden):
     g = golden("model05")
     blob = os.path.join(os.path.dirname(DEFAULT_BLOB), "model05.bin")
     T = g["features"].shape[0] // 4
-    eng = Engine(1, max_tx_mf=T // 3, blob=blob, flags=0x100)          # RADE_BATCH_BOTTLENECK1
+    eng = engine(1, max_tx_mf=T // 3, blob=blob, flags=0x100)          # RADE_BATCH_BOTTLENECK1
     z = eng.encode(torch.tensor(g["features"].reshape(1, T, 80), device=torch_dev))
     assert rms(z.cpu().numpy()[0], g["z"]) < 2e-5
     for tag in ("awgn", "mp"):
@@ -1203,7 +1166,6 @@ def test_model05_rate_rs_config1(Engine, torch_dev, golden):
     whole = eng.decode(zt, 80)
     parts = torch.cat([eng.decode(zt[:, a:b].contiguous(), 80, reset=(a == 0)) for a, b in ((0, 3), (3, 4), (4, T))], 1)
     assert rms(parts.cpu().numpy(), whole.cpu().numpy()) < 1e-5
-    eng.close()
 
 
 def test_bbfm_config5(Engine, torch_dev, golden):
@@ -1234,7 +1196,7 @@ def test_bbfm_config5(Engine, torch_dev, golden):
     eng.close()
 
 
-def test_bbfm_config5_over_the_lmr60_channel(Engine, torch_dev, oracle):
+def test_bbfm_config5_over_the_lmr60_channel(engine, torch_dev, oracle):
     """SURVEY 8(d) config 5, its fading variant: BBFM at batch 256 through the land-mobile channel of multipath_samples.m:17-21 ("lmr60": 60 km/h at 450 MHz, fd = 25 Hz),
     |H| at the 2000 symbols/s rate generated ON THE DEVICE (multipath_h_gen) per stream: encoder (bottleneck 1) -> FM-demodulator channel with that H and supplied noise ->
     decoder, three streams against the oracle on the same H and noise (bbfm.py:157-197)."""
@@ -1245,7 +1207,7 @@ def test_bbfm_config5_over_the_lmr60_channel(Engine, torch_dev, oracle):
     B, T = 256, 72
     rng = np.random.default_rng(515)
     feats = (0.7 * rng.standard_normal((B, T, 80))).astype(np.float32)
-    eng = Engine(B, max_tx_mf=T // 3, blob=blob, flags=0x100)
+    eng = engine(B, max_tx_mf=T // 3, blob=blob, flags=0x100)
     z = eng.encode(torch.tensor(feats, device=torch_dev))
     H = eng.multipath_h_gen("lmr60", T * 80, seed=99)                       # [B, T * 80, 1]: one |H| per real symbol
     Hn = H.cpu().numpy()[:, :, 0]
@@ -1264,11 +1226,10 @@ def test_bbfm_config5_over_the_lmr60_channel(Engine, torch_dev, oracle):
         assert np.abs(zhc[b] - zho).max() < 5e-6
         fo = np.array([dec.step(zhc[b, t]) for t in range(T)])
         assert rms(fh[b], fo) < 1e-4
-    eng.close()
 
 
 @pytest.mark.parametrize("blobname,mode", [("model05.bin", "rs"), ("bbfm_random_seed20240501.bin", "bbfm")])
-def test_configs_1_and_5_at_batch_256_split_f16_gemm(Engine, torch_dev, oracle, blobname, mode):
+def test_configs_1_and_5_at_batch_256_split_f16_gemm(engine, torch_dev, oracle, blobname, mode):
     """BASELINE configs 1 and 5 at their stated batch (256 streams): with more than 16 k GEMM rows the 80-wide-input blobs run the
     split-binary16 matrix-core kernels (k_gemm16p / k_gemm16), not the f32 kernels their B = 1 parity tests above select.  Three
     streams each against the oracle's CoreEncoder / CoreDecoder on the same rows (z within 2e-5 of full scale, features within
@@ -1288,7 +1249,7 @@ def test_configs_1_and_5_at_batch_256_split_f16_gemm(Engine, torch_dev, oracle, 
     x[..., 0] *= 4.0
     x[100] *= np.float32(120.0)                               # one stream far past +-256
     feats = x.reshape(B, T, 80)
-    eng = Engine(B, max_tx_mf=T // 3, blob=blob, flags=0x100)      # RADE_BATCH_BOTTLENECK1
+    eng = engine(B, max_tx_mf=T // 3, blob=blob, flags=0x100)      # RADE_BATCH_BOTTLENECK1
     z = eng.encode(torch.tensor(feats, device=torch_dev)).cpu().numpy()
     assert np.isfinite(z).all()
     m = oracle.Model(blob)
@@ -1319,10 +1280,9 @@ def test_configs_1_and_5_at_batch_256_split_f16_gemm(Engine, torch_dev, oracle, 
         dec = oracle.Decoder(m)
         ref = np.stack([dec.step(r) for r in zh[b]])
         assert rms(fh[b], ref) < 1e-4, (blobname, b)
-    eng.close()
 
 
-def test_tx_channel_one_pass_equals_two_calls(Engine, torch_dev, oracle, oracle_model):
+def test_tx_channel_one_pass_equals_two_calls(engine, torch_dev, oracle, oracle_model):
     """rade_batch_tx_channel (the modulator applies the two-path model and leaves the power sums: RADAE.forward in one pass) against
     rade_batch_tx + rade_batch_channel on the same inputs, and against the oracle's transmitter + channel for one stream."""
     import torch
@@ -1336,7 +1296,7 @@ def test_tx_channel_one_pass_equals_two_calls(Engine, torch_dev, oracle, oracle_
     noise = ((rng.standard_normal((B, n_tot)) + 1j * rng.standard_normal((B, n_tot))) / np.sqrt(2)).astype(np.complex64)
     sigma = sigma_from_EbNodB(6.0)
     ft, Gt, nt = torch.tensor(feats, device=torch_dev), torch.tensor(G, device=torch_dev), torch.tensor(noise, device=torch_dev)
-    e1 = Engine(B, max_tx_mf=n_mf); e2 = Engine(B, max_tx_mf=n_mf)
+    e1 = engine(B, max_tx_mf=n_mf); e2 = engine(B, max_tx_mf=n_mf)
     iq = e1.tx(ft)
     rx_two = e1.channel(iq, sigma, -7.0, n_pre=300, n_post=200, with_eoo=True, G=Gt, noise=nt).cpu().numpy()
     rx_one, iq_one = e2.tx_channel(ft, sigma, -7.0, n_pre=300, n_post=200, with_eoo=True, G=Gt, noise=nt, want_iq=True)
@@ -1357,7 +1317,6 @@ def test_tx_channel_one_pass_equals_two_calls(Engine, torch_dev, oracle, oracle_
     ee = oracle.channel_eoo(tx.eoo(), noise[1, 300 + len(sig):300 + len(sig) + 1152], sigma, -7.0, 0.0, fin)
     full = np.concatenate([sigma * noise[1, :300], r, ee, sigma * noise[1, -200:]]).astype(np.complex64)
     assert np.abs(rx_one.cpu().numpy()[1] - full).max() < 5e-5
-    e1.close(); e2.close()
 
 
 def test_engine_open_close_returns_device_memory(Engine, torch_dev):
@@ -1413,8 +1372,7 @@ def test_engine_open_close_returns_device_memory(Engine, torch_dev):
     assert free[5] >= free[1], free
 
 
-
-def test_rx2_replicas_agree_when_two_workgroups_share_a_cu(Engine, torch_dev, golden, monkeypatch):
+def test_rx2_replicas_agree_when_two_workgroups_share_a_cu(engine, torch_dev, golden, monkeypatch):
     """300 copies of one stream: more workgroups than CUs, so 44 CUs run two of them side by side -- the situation k_rx_sync2 exists
     for, and the one in which packed f32 FMAs in its band-pass filter corrupted lanes 48..63 (HISTORY.md 3.7).  Bit-identical in every
     slot, three fresh launches, and equal to the one-stream-per-CU kernel's discrete outputs."""
@@ -1422,8 +1380,8 @@ def test_rx2_replicas_agree_when_two_workgroups_share_a_cu(Engine, torch_dev, go
     g = golden("rxtrace_mpp")
     B = 300
     buf = torch.tensor(np.stack([g["rx_in"]] * B), device=torch_dev)
-    eng = Engine(B, max_tx_mf=1, rx_trace_calls=64, flags=0)
-    ref = Engine(1, max_tx_mf=1, rx_trace_calls=64)
+    eng = engine(B, max_tx_mf=1, rx_trace_calls=64, flags=0)
+    ref = engine(1, max_tx_mf=1, rx_trace_calls=64)
     fr, sr, _ = ref.rx(buf[:1].contiguous()); tr = ref.rx_trace(0)
     for rep in range(3):
         eng.rx_reset()
@@ -1437,157 +1395,6 @@ def test_rx2_replicas_agree_when_two_workgroups_share_a_cu(Engine, torch_dev, go
             assert np.array_equal(t[k], tr[k]), k
         nv = st[0].n_valid
         assert sr[0].n_valid == nv and rms(f[0, :nv], fr[0, :nv].cpu().numpy()) < 2e-6
-    eng.close(); ref.close()
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# single-carrier modem for BBFM symbols (reference radae/dsp.py:579-860)
-# ---------------------------------------------------------------------------------------------------------------------
-SC_RX_CASES = ["clean", "noisy_foff", "drift", "drift_pos", "lose_sync"]
-
-
-@pytest.mark.gpu
-def test_sc_rrc_and_tx_golden(torch_dev, golden):
-    import torch
-    from radae_amd.sc import SingleCarrierBatch
-    for name in ("bpsk_1500", "analog_0"):
-        g = golden("sc_tx_" + name)
-        m = SingleCarrierBatch(2, fcentreHz=float(g["fcentre"]))
-        assert np.abs(m.rrc() - g["rrc"]).max() < 1e-12
-        sy = torch.tensor(np.stack([g["symbs"], g["symbs"][::-1].copy()]), device=torch_dev)
-        # two calls (3 + rest frames): filter memory and LO phase carry across calls
-        a = m.tx(sy[:, :3].contiguous()); b = m.tx(sy[:, 3:].contiguous())
-        tx = torch.cat([a, b], dim=1).cpu().numpy()
-        assert np.abs(tx[0] - g["tx"].reshape(-1)).max() < 2e-6
-        m.close()
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", SC_RX_CASES)
-def test_sc_rx_golden(torch_dev, golden, name):
-    """HIP receiver against the reference's per-frame outputs: discrete outputs exact, symbols to 1e-5."""
-    import torch
-    from radae_amd.sc import SingleCarrierBatch
-    g = golden("sc_rx_" + name)
-    m = SingleCarrierBatch(1, fcentreHz=float(g["fcentre"]))
-    pay, zh, fr, st = m.rx(torch.tensor(g["rx_in"][None], device=torch_dev))
-    nf = st[0].n_frames
-    assert nf == len(g["state"]) and st[0].consumed == int(g["consumed"])
-    f = fr[0, :nf]
-    for k in ("state", "nin", "fs_s"):
-        assert np.array_equal(f[k], g[k]), k
-    assert np.abs(f["norm_rx_timing"] - g["norm_rx_timing"]).max() < 1e-5
-    assert np.abs(f["phase_ambiguity"] - g["phase_ambiguity"]).max() < 1e-6
-    assert np.abs(f["g"] - g["g"]).max() < 1e-5 * np.abs(g["g"]).max()
-    assert np.abs((f["max_cs_re"] + 1j * f["max_cs_im"]) - g["max_Cs"]).max() < 1e-5
-    p = pay.cpu().numpy()[0, :nf]
-    assert np.abs(p - g["payload"]).max() < 1e-5 * max(1.0, np.abs(g["payload"]).max())
-    z = zh.cpu().numpy()[0, :nf]
-    ref = np.where(g["state"][:, None] == 1, g["g"][:, None] * g["payload"].real, 0.0)
-    assert np.abs(z - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
-    m.close()
-
-
-@pytest.mark.gpu
-def test_sc_loopback_batch_vs_oracle_and_chunking(torch_dev):
-    """64 streams with different symbols / impairments: tx on the GPU == oracle tx; rx frame by frame (one call per frame,
-    the sc_rx.py usage) == whole stream at once == oracle; bit errors of the synced frames are zero at this SNR."""
-    import torch
-    from oracle import sc_oracle as SC
-    from radae_amd.sc import SingleCarrierBatch
-    B, NF = 64, 10
-    rng = np.random.default_rng(5)
-    sy = (1 - 2 * (rng.random((B, NF, 80)) > 0.5)).astype(np.float32)
-    m = SingleCarrierBatch(B, fcentreHz=1500.0)
-    tx = m.tx(torch.tensor(sy, device=torch_dev)).cpu().numpy()
-    for b in (0, 17, 63):
-        o = SC.SingleCarrier(fcentreHz=1500.0)
-        assert np.abs(np.concatenate([o.tx(s) for s in sy[b]]) - tx[b]).max() < 2e-6
-    n = tx.shape[1]
-    t = np.arange(n)
-    rx = np.zeros((B, n + 64), np.complex64)
-    for b in range(B):
-        lead = int(rng.integers(0, 64))
-        ph = 2 * np.pi * rng.uniform(-2, 2) * t / 9600 + rng.uniform(-3, 3)
-        y = (0.3 + 2 * rng.random()) * (tx[b] * np.exp(1j * ph) + 0.05 * (rng.standard_normal(n) + 1j * rng.standard_normal(n)))
-        rx[b, lead:lead + n] = y
-    rxd = torch.tensor(rx, device=torch_dev)
-    pay, zh, fr, st = m.rx(rxd)
-    nf = st[0].n_frames
-    assert all(s.n_frames == nf and s.consumed == nf * 384 or abs(s.consumed - nf * 384) <= nf for s in st)
-    for b in (0, 17, 40, 63):
-        o = SC.SingleCarrier(fcentreHz=1500.0)
-        out, consumed = SC.run_rx_stream(o, rx[b])
-        k = st[b].n_frames
-        assert k == len(out["state"]) and consumed == st[b].consumed
-        for key in ("state", "nin", "fs_s"):
-            assert np.array_equal(fr[b, :k][key], out[key]), key
-        assert np.abs(pay.cpu().numpy()[b, :k] - out["payload"]).max() < 2e-5 * max(1.0, np.abs(out["payload"]).max())
-    # payload bits of synced frames: frame i of the receiver carries tx frame i - 1 or i - 2 depending on the lead
-    z = zh.cpu().numpy(); errs = 0; bits = 0
-    for b in range(B):
-        for i in range(2, st[b].n_frames):
-            if fr[b, i]["state"] == 1:
-                best = min(int(np.sum(z[b, i] * sy[b, j] < 0)) for j in range(NF))
-                errs += best; bits += 80
-    assert bits > B * 5 * 80 and errs == 0
-    # one frame per call == all at once
-    # (streams slip independently, so the frame-by-frame run uses stream 0 alone)
-    m1 = SingleCarrierBatch(1, fcentreHz=1500.0)
-    p0 = 0; outs = []; nin = 384
-    while p0 + nin <= rx.shape[1]:
-        p, _, f1, s1 = m1.rx(rxd[:1, p0:p0 + nin].contiguous(), max_frames=1)
-        assert s1[0].n_frames == 1 and s1[0].consumed == nin
-        outs.append(p.cpu().numpy()[0, 0]); p0 += nin; nin = s1[0].nin
-    assert len(outs) == st[0].n_frames
-    assert np.array_equal(np.stack(outs), pay.cpu().numpy()[0, :len(outs)])
-    m.close(); m1.close()
-
-
-@pytest.mark.gpu
-def test_sc_edge_cases(torch_dev, golden):
-    """Short input (no whole frame), max_frames cap, reset, and argument checking of the single-carrier entry points."""
-    import torch
-    from radae_amd.sc import SingleCarrierBatch
-    g = golden("sc_rx_clean")
-    x = torch.tensor(g["rx_in"][None], device=torch_dev)
-    m = SingleCarrierBatch(1, fcentreHz=float(g["fcentre"]))
-    pay, zh, fr, st = m.rx(x[:, :383].contiguous(), max_frames=4)          # fewer than nin samples: nothing consumed
-    assert st[0].n_frames == 0 and st[0].consumed == 0 and st[0].nin == 384 and st[0].state == 0
-    pay, zh, fr, st = m.rx(x, max_frames=3)                                   # capped: the caller resumes at `consumed`
-    assert st[0].n_frames == 3 and st[0].consumed == int(np.sum(np.concatenate([[384], g["nin"][:2]])))
-    pay2, zh2, fr2, st2 = m.rx(x[:, st[0].consumed:].contiguous())
-    nf = len(g["state"])
-    assert st2[0].n_frames == nf - 3
-    assert np.array_equal(np.concatenate([fr[0, :3]["state"], fr2[0, :nf - 3]["state"]]), g["state"])
-    p = np.concatenate([pay.cpu().numpy()[0, :3], pay2.cpu().numpy()[0, :nf - 3]])
-    assert np.abs(p - g["payload"]).max() < 1e-5
-    m.reset()                                                                  # back to the constructor state: same answer again
-    pay3, _, fr3, st3 = m.rx(x)
-    assert st3[0].n_frames == nf and np.abs(pay3.cpu().numpy()[0, :nf] - g["payload"]).max() < 1e-5
-    # argument errors are reported, not crashed on
-    L = m.L
-    assert L.rade_sc_tx(m.h, None, 1, None, 384, None) == -1
-    assert L.rade_sc_rx(m.h, None, 0, 0, 1, None, None, None, None, None) == -1
-    assert not L.rade_sc_open(0, 2400.0, 9600.0, 0.0, 0.25, 0)
-    assert not L.rade_sc_open(1, 2400.0, 8000.0, 0.0, 0.25, 0)              # Fs must be 4 Rs
-    m.close()
-
-
-@pytest.mark.gpu
-def test_sc_wire_filters_match_reference_scripts(golden):
-    """latents | sc_tx | sc_rx with the reference's own scripts (tests/golden/sc_wire.npz) vs the GPU filters: int16 samples equal up
-    to the truncation of values within float rounding of an integer, z_hat equal to the quantisation noise that leaves."""
-    from radae_amd.sc import sc_tx_stream, sc_rx_stream
-    g = golden("sc_wire")
-    t = sc_tx_stream(g["z"])
-    assert t.dtype == np.int16 and t.shape == g["t_int16"].shape
-    d = np.abs(t.astype(int) - g["t_int16"].astype(int))
-    assert d.max() <= 1 and (d == 0).mean() > 0.97
-    zh = sc_rx_stream(g["t_int16"])                       # the reference's samples in: isolates the receiver
-    assert zh.shape == g["zhat"].shape and np.abs(zh - g["zhat"]).max() < 2e-5 * max(1.0, np.abs(g["zhat"]).max())
-    zh2 = sc_rx_stream(t)                                  # our own samples: +-1 LSB differences only
-    assert zh2.shape == g["zhat"].shape and np.abs(zh2 - g["zhat"]).max() < 2e-3
 
 
 def test_config4_sharding_two_ranks_on_one_device():

@@ -663,6 +663,34 @@ def test_band_checker_reports_every_planted_fault():
     Band(3, 7, 11, 8).untouched()
 
 
+def test_gpu_kit_helpers():
+    """tests/gpu_kit.py, the plumbing of the GPU modules, where it can be checked without a GPU: bits() gives the words the modules' former definitions gave
+    (a NaN with a payload and -0.0 included), the same for a CPU tensor of the same data; pack() pads with zeros and reports the lengths; define() reads
+    rade_dev.h and names the macro it cannot find."""
+    import torch
+    import gpu_kit
+    f = np.arange(15, dtype=np.float32).reshape(3, 5) - 7
+    f[0, 0] = -0.0
+    f[1, 2:3].view(np.int32)[0] = 0x7fc12345                       # a quiet NaN with a payload
+    c = (f + 1j * f[::-1]).astype(np.complex64)
+    c[2, 4:5].view(np.int32)[:] = [0x7fc12345, -0x80000000]         # (NaN with the payload, -0.0): arithmetic on the NaN above may have dropped its payload
+    for a, words in ((f, f.view(np.int32)), (c, c.view(np.int32))):
+        assert words.shape == (3, 5 * a.itemsize // 4) and 0x7fc12345 in words and -0x80000000 in words
+        assert gpu_kit.bits(a).dtype == np.int32 and np.array_equal(gpu_kit.bits(a), words)
+        assert np.array_equal(gpu_kit.bits(a[:, ::2]), np.ascontiguousarray(a[:, ::2]).view(np.int32))      # not contiguous
+        assert np.array_equal(gpu_kit.bits(a[1]), a[1].view(np.int32))                                       # one row stays one axis
+        assert np.array_equal(gpu_kit.bits(torch.from_numpy(a)), words)
+    rows = [np.zeros(0, np.complex64), np.array([1 + 2j], np.complex64), np.arange(1, 8).astype(np.complex64) * (1 - 1j)]
+    x, n = gpu_kit.pack(rows)
+    assert x.dtype == np.complex64 and x.shape == (3, 7) and n.dtype == np.int32 and n.tolist() == [0, 1, 7]
+    assert not x[0].any() and x[1, 0] == 1 + 2j and not x[1, 1:].any() and np.array_equal(x[2], rows[2])
+    with open(os.path.join(REPO, "radae_amd", "csrc", "rade_dev.h")) as h:
+        tile = [ln.split()[2] for ln in h if ln.split()[:2] == ["#define", "RD_CLK_TILE"]]
+    assert len(tile) == 1 and gpu_kit.define("RD_CLK_TILE") == int(tile[0]) > 0
+    with pytest.raises(LookupError, match="NO_SUCH_MACRO"):
+        gpu_kit.define("NO_SUCH_MACRO")
+
+
 # ---- host halves of the kernel unit tests (tests/kernel_ref.py, tests/test_kernel_units_gpu.py) ----------------------------------------------------------------
 @pytest.mark.parametrize("K", [16, 80, 864])
 @pytest.mark.parametrize("N", [32, 80, 96])

@@ -8,16 +8,10 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_kit import REPO, engine, torch_dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M05 = os.path.join(REPO, "weights", "model05.bin")
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def check_z(z, ref, what):
@@ -33,29 +27,27 @@ def check_z(z, ref, what):
 
 
 @pytest.mark.parametrize("case", ["awgn", "mpp"])
-def test_z_fwd_parity(torch_dev, golden, case):
+def test_z_fwd_parity(engine, torch_dev, golden, case):
     """RADAE.forward's own receiver (eq_ls, coarse_mag, time_offset -16, correct_freq_offset) on the fixture's samples: z_hat and the decoded features"""
     import torch
-    from radae_amd.engine import BatchEngine
     g = golden("chan_" + case)
     n_mf = len(g["rx"]) // 960
-    eng = BatchEngine(1, max_tx_mf=n_mf)
+    eng = engine(1, max_tx_mf=n_mf)
     rx = torch.tensor(g["rx"][None], device=torch_dev)
     feats, z_hat, n_err = eng.rx_ideal(rx, n_mf, time_offset=-16, eq="ls", coarse_mag=True, freq_offset=float(g["freq_offset"]))
     assert n_err is None
     check_z(z_hat.cpu().numpy()[0], g["z_fwd"], case)
     f_ref = eng.decode(torch.tensor(g["z_fwd"][None], device=torch_dev), 84).cpu().numpy()
     assert np.sqrt(np.mean((feats.cpu().numpy() - f_ref) ** 2)) <= 1e-4
-    eng.close()
 
 
-def test_every_eq_mode_matches_the_reference(torch_dev, golden):
+def test_every_eq_mode_matches_the_reference(engine, torch_dev, golden):
     import torch
-    from radae_amd.engine import TX_LINEAR, BatchEngine
+    from radae_amd.engine import TX_LINEAR
     g = golden("ideal_rx")
     rx_np = golden("chan_mpp")["rx"]
     n_mf = len(rx_np) // 960
-    engs = {3: BatchEngine(1, max_tx_mf=2), 1: BatchEngine(1, max_tx_mf=2, flags=TX_LINEAR)}     # the coarse_mag scaling follows the waveform
+    engs = {3: engine(1, max_tx_mf=2), 1: engine(1, max_tx_mf=2, flags=TX_LINEAR)}     # the coarse_mag scaling follows the waveform
     rx = torch.tensor(rx_np[None], device=torch_dev)
     n = 0
     for key in g.files:
@@ -67,18 +59,16 @@ def test_every_eq_mode_matches_the_reference(torch_dev, golden):
             check_z(z_hat.cpu().numpy()[0], g[key], f"{key} bn{bn}")
             n += 1
     assert n == 28
-    for e in engs.values():
-        e.close()
 
 
-def test_bottleneck1_ber_forward_run(torch_dev, golden):
+def test_bottleneck1_ber_forward_run(engine, torch_dev, golden):
     """fixture (b): TX_LINEAR modulation of the sign latents, the channel with the recorded noise, the genie receiver's BER count"""
     import torch
-    from radae_amd.engine import BOTTLENECK1, TX_LINEAR, BatchEngine, sigma_from_EbNodB
+    from radae_amd.engine import BOTTLENECK1, TX_LINEAR, sigma_from_EbNodB
     g = golden("ideal_rx")
     z = torch.tensor(g["b_z"][None], device=torch_dev)
     n_mf = z.shape[1] // 3
-    eng = BatchEngine(1, max_tx_mf=n_mf, blob=M05, flags=BOTTLENECK1 | TX_LINEAR)
+    eng = engine(1, max_tx_mf=n_mf, blob=M05, flags=BOTTLENECK1 | TX_LINEAR)
     iq = eng.tx_latents(z)
     assert np.abs(iq.cpu().numpy()[0] - g["b_tx"]).max() < 2e-5
     assert abs(sigma_from_EbNodB(float(g["b_EbNodB"]), bottleneck=1) - float(g["b_sigma"])) < 1e-6 * float(g["b_sigma"])
@@ -94,30 +84,27 @@ def test_bottleneck1_ber_forward_run(torch_dev, golden):
         eng.tx_eoo()
     with pytest.raises(RuntimeError):
         eng.channel(iq, 0.1, with_eoo=True)
-    eng.close()
 
 
-def test_batch_streams_are_independent(torch_dev, golden):
+def test_batch_streams_are_independent(engine, torch_dev, golden):
     """64 streams with different samples and frequency offsets: per-stream z_hat bit-equal to one-stream runs"""
     import torch
-    from radae_amd.engine import BatchEngine
     rx_np = golden("chan_mpp")["rx"]
     n_mf = len(rx_np) // 960
     B = 64
     rxs = np.stack([np.roll(rx_np, 960 * (b % n_mf) + 7 * b) for b in range(B)]).astype(np.complex64)
     fo = -11.0 + 0.37 * np.arange(B, dtype=np.float32)
     dfdt = np.where(np.arange(B) % 3 == 0, 0.5, 0.0).astype(np.float32)
-    eng = BatchEngine(B, max_tx_mf=n_mf)
+    eng = engine(B, max_tx_mf=n_mf)
     z_ref = torch.tensor(np.sign(np.random.default_rng(3).standard_normal((B, 3 * n_mf, 80))).astype(np.float32), device=torch_dev)
     feats, z_hat, n_err = eng.rx_ideal(torch.tensor(rxs, device=torch_dev), n_mf, time_offset=-16, eq="ls", coarse_mag=True, freq_offset=fo, df_dt=dfdt, z_ref=z_ref)
-    one = BatchEngine(1, max_tx_mf=n_mf)
+    one = engine(1, max_tx_mf=n_mf)
     for b in range(B):
         f1, z1, e1 = one.rx_ideal(torch.tensor(rxs[b:b + 1], device=torch_dev), n_mf, time_offset=-16, eq="ls", coarse_mag=True, freq_offset=fo[b], df_dt=dfdt[b], feat_width=0,
                                   z_ref=z_ref[b:b + 1].contiguous())
         assert torch.equal(z1[0], z_hat[b]), b
         assert int(e1[0]) == int(n_err[b])
         assert int(n_err[b]) == int((-z_ref[b] * z_hat[b] > 0).sum())
-    eng.close(); one.close()
 
 
 def ber_run(torch_dev, EbNodB, freq_offset, mpp, B=64, n_mf=72, seed=9):

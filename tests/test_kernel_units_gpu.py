@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 
 import kernel_ref as kr
+from gpu_kit import Dev, host32, stream, sync, torch_dev  # noqa: F401
+from kernel_ref import encf_check_exact, first_bad
 
 pytestmark = pytest.mark.gpu
 
@@ -31,51 +33,9 @@ NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def L(torch_dev):
     from radae_amd import engine
     return kr.declare(engine.load_library())
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def stream():
-    from radae_amd.engine import _stream_ptr
-    return _stream_ptr()
-
-
-class Dev:
-    """host arrays uploaded once; unchanged() compares every word with what was uploaded"""
-
-    def __init__(self, dev):
-        self.dev, self.items = dev, []
-
-    def put(self, arr, check=True):
-        import torch
-        host = np.ascontiguousarray(arr)
-        raw = host.view(np.int32 if host.dtype.itemsize == 4 else np.int16).ravel()
-        t = torch.from_numpy(raw).to(self.dev)
-        assert t.data_ptr() % 16 == 0
-        if check:
-            self.items.append((t, raw))
-        return t
-
-    def unchanged(self):
-        for i, (t, raw) in enumerate(self.items):
-            assert np.array_equal(t.cpu().numpy(), raw), f"input buffer {i} was written"
-
-
-def host32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 # ================================================================================================================================================================
@@ -147,11 +107,6 @@ def run_gemm(L, dev, B, T, K0, K1, N, wmode, X, W, scale, bias, act=0):
     ya.check_outside(yw, what)
     d.unchanged()
     return ya.view(yw).copy(), what
-
-
-def first_bad(bad, what, got, want, extra=""):
-    b, t, n = np.argwhere(bad)[0]
-    return f"{what}: {int(bad.sum())} elements differ, the first at stream {b}, step {t}, column {n}: got {got[b, t, n]!r}, reference {want[b, t, n]!r}{extra}"
 
 
 def gemm_exact(L, dev, rng, B, T, K0, K1, N, wmode, grid):
@@ -417,15 +372,6 @@ def run_encf(L, dev, B, T, K0, K1, N, wmode, X, W, scale, bias, dil, to_yf, seq=
     yw = host32(y_d)
     ya.check_outside(yw, what)
     return ya.view(yw).copy(), None, what
-
-
-def encf_check_exact(got, planes, want, what):
-    if planes is None:
-        bad = got.view(np.int32) != want.view(np.int32)
-    else:
-        whi, wlo = kr.split16(want)
-        bad = (planes[0] != whi) | (planes[1] != wlo)
-    assert not bad.any(), first_bad(bad, what, got, want)
 
 
 @pytest.mark.parametrize("B", ENCF_B)

@@ -3,48 +3,22 @@ float32 kernel against the float64 restatement of tests/rate_ref.py on the libra
 sentinel buffers (tests/bands.py), pieces against the whole, the fused int16 formats against wire_in + the complex64 call, host-side refusals, a change of ratio
 between calls, and the receiver end to end on samples that went up to 48 kHz int16 and back on the device."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import rate_ref as rf
 from bands import Band
+from gpu_kit import INT_KEYS, bits, crandn, define, dev, engines, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INT_KEYS = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count", "uw_errors", "synced_count", "snr_int"]
-_HDR = open(os.path.join(REPO, "radae_amd", "csrc", "rade_dev.h")).read()
-WIN, TILE_MAX = (int(re.search(r"#define %s (\d+)" % k, _HDR).group(1)) for k in ("RD_RATE_WIN", "RD_RATE_TILE_MAX"))
+WIN, TILE_MAX = define("RD_RATE_WIN"), define("RD_RATE_TILE_MAX")
 
 
 def tile_of(L, M):
     """rd_rate_tile of rade_dev.h: the outputs of a tile, from the window's fixed capacity"""
     L, M, K, T = rf.reduce(L, M)
     return min((WIN - T - K) * L // M + 1, TILE_MAX) // 64 * 64
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the call uses none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(B):
-        if B not in made:
-            made[B] = BatchEngine(B, max_tx_mf=1)
-        return made[B]
-    yield get
-    for e in made.values():
-        e.close()
 
 
 @pytest.fixture(scope="module")
@@ -59,10 +33,6 @@ def taps():
     return get
 
 
-def crandn(rng, *shape):
-    return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) / np.sqrt(2)).astype(np.complex64)
-
-
 def irand(rng, *shape):
     """int16 samples over the whole range, the three extreme values among them"""
     v = rng.integers(-32768, 32768, shape).astype(np.int16)
@@ -70,15 +40,6 @@ def irand(rng, *shape):
     flat[:3] = (32767, -32767, -32768)
     flat[-3:] = (-32768, 32767, -32767)
     return v
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=torch_dev)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def raw_call(eng, x_ptr, x_stride, n_in, y_ptr, y_stride, n_out, L, M, fmt=rf.C64, gain=1.0, n0=None, in_base=None):

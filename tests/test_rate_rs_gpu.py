@@ -12,41 +12,9 @@ import pytest
 
 import rate_rs_ref as rs
 from bands import Band
+from gpu_kit import REPO, Engine, dev, engines, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def Engine():
-    from radae_amd.engine import BatchEngine
-    return BatchEngine
-
-
-@pytest.fixture(scope="module")
-def engines(Engine):
-    """one engine per batch size for the whole module (the call uses none of the model: max_tx_mf = 1 serves any n_steps)"""
-    made = {}
-
-    def get(B):
-        if B not in made:
-            made[B] = Engine(B, max_tx_mf=1)
-        return made[B]
-    yield get
-    for e in made.values():
-        e.close()
-
-
-def dev(a, torch_dev):
-    import torch
-    return None if a is None else torch.tensor(np.ascontiguousarray(a), device=torch_dev)
 
 
 def random_inputs(B, n, seed):

@@ -3,61 +3,23 @@ against the float64 restatement of tests/resample_ref.py on the library's own ta
 buffers (tests/bands.py), pieces against the whole, per-stream values against the scalar call, the linear mode against the reference's recording
 (tests/golden/clock_offset.npz), host-side refusals, and the receiver's slip path end to end on samples resampled on the device."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import resample_ref as rr
 from bands import Band
+from gpu_kit import INT_KEYS, bits, crandn, define, dev, engines, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = {"sinc32": rr.SINC32, "linear": rr.LINEAR}
-INT_KEYS = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count", "uw_errors", "synced_count", "snr_int"]
-TILE = int(re.search(r"#define RD_CLK_TILE (\d+)", open(os.path.join(REPO, "radae_amd", "csrc", "rade_dev.h")).read()).group(1))
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the call uses none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(B):
-        if B not in made:
-            made[B] = BatchEngine(B, max_tx_mf=1)
-        return made[B]
-    yield get
-    for e in made.values():
-        e.close()
+TILE = define("RD_CLK_TILE")
 
 
 @pytest.fixture(scope="module")
 def taps():
     from radae_amd.engine import resample_taps
     return resample_taps()
-
-
-def crandn(rng, *shape):
-    return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) / np.sqrt(2)).astype(np.complex64)
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=torch_dev)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def raw_call(eng, x_ptr, x_stride, n_in, y_ptr, y_stride, n_out, mode, ppm=0.0, ppm_b=None, t0=None, n0=None, in_base=None):

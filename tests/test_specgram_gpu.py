@@ -20,38 +20,11 @@ import pytest
 
 import specgram_ref as sr
 from bands import Band
+from gpu_kit import REPO, dev, engines, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORST_MEASURED = 4.79e-2               # largest |mag^ - mag| / bound over test_magnitudes_under_the_counted_bound on the MI355X (the one-sample stream, whose S is one |v|; 5e-3 on the noise streams)
 N5 = [1281, 1440, 1441, 2401, 8037]    # one slice, one, two, eight, 43 (an odd count: the last slice has no partner)
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the call uses none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(B):
-        if B not in made:
-            made[B] = BatchEngine(B, max_tx_mf=1)
-        return made[B]
-    yield get
-    for e in made.values():
-        e.close()
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(a, device=torch_dev)
 
 
 def tone(n, k, amp):

@@ -8,28 +8,14 @@ stream has no sample (for C/No, which refuses less than a window: no window) in 
 import numpy as np
 import pytest
 
+from gpu_kit import crandn, dev, torch_dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 B = 3
 WIRE_CALLS = 17                  # 2 x RD_WIRE_SLOTS + 1: every slot of the wire's ring is used again twice
 
 
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def crandn(rng, *shape):
-    return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) / np.sqrt(2)).astype(np.complex64)
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=torch_dev)
-
-
-def bits(a):
+def cmp_bits(a):
     """what np.array_equal compares: int16 as it is, everything else as the integers of its bytes"""
     a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
     if a.dtype == np.int16:
@@ -52,7 +38,7 @@ def run(calls, wait):
                 if wait:
                     torch.cuda.synchronize()
         torch.cuda.synchronize()
-        return [[None if v is None else bits(v) for v in o] for o in outs]
+        return [[None if v is None else cmp_bits(v) for v in o] for o in outs]
     finally:
         eng.close()
 

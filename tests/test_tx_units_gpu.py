@@ -1,7 +1,7 @@
 """GPU unit tests (-m gpu) of the transmit half of the timed step, the channel and the row kernels, each called alone through its launch shim of
 radae_amd/csrc/rade_dev.h on synthetic operands: k_encf_dense1; k_enc_pack, k_pad_rows, k_carry_rows; k_ofdm_mod<linear|limiter>, k_ofdm_mod_mp<...>, k_eoo_build,
 k_copy_eoo; k_chan_power / k_chan_gain / k_chan_apply behind rd_launch_channel; k_multipath_gen, k_multipath_h.  The companion of tests/test_kernel_units_gpu.py
-(whose Dev helper, sync and stream this module uses): torch tensors are the device memory, every output sits in a NaN-sentinel buffer and must leave everything
+(the Dev helper, sync and stream of both are tests/gpu_kit.py's): torch tensors are the device memory, every output sits in a NaN-sentinel buffer and must leave everything
 outside its documented elements untouched, every input must be unchanged, and every sample is held to a float64 reference -- bit for bit where the operation is
 data movement or an exact grid, within the bound tests/tx_ref.py derives otherwise.  The checkers are those of tests/tx_ref.py; tests/test_tx_units_host.py shows
 that each of them rejects the bugs it is there for.  One engine per module supplies the device copy of the constant tables (rd_batch_tables).
@@ -14,19 +14,10 @@ import numpy as np
 import pytest
 
 import kernel_ref as kr
-import test_kernel_units_gpu as ku
 import tx_ref as tx
+from gpu_kit import Dev, host32, stream, sync, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-Dev, sync, stream, host32 = ku.Dev, ku.sync, ku.stream, ku.host32
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +102,7 @@ def test_encf_dense1(L, torch_dev, B, Kin):
             want = y64.astype(np.float32).reshape(B, T, 64)
             assert np.array_equal(want.astype(np.float64).ravel(), y64.ravel()) and np.array_equal(kr.join16(*kr.split16(want)), want)
             got, planes, what = run_dense1(L, torch_dev, B, T, Kin, ycol, X.reshape(B, T, Kin), W, bias, 0)
-            ku.encf_check_exact(got, planes, want, what + " exact grid")
+            kr.encf_check_exact(got, planes, want, what + " exact grid")
             _, W, _, bias = kr.random_gemm_operands(rng, 1, Kin, 64)
             X = rng.uniform(-1, 1, (B, T, Kin)).astype(np.float32) * np.array([300.0, 1e5, 1.0], np.float32)[np.arange(B) % 3][:, None, None]
             y64, S = kr.gemm_ref(X.reshape(B * T, Kin), W, bias)

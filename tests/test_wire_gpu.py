@@ -1,7 +1,6 @@
 """GPU tests (-m gpu) of the sound-card wire (rade_batch_wire_in / rade_batch_wire_out, rade_wire.hip; include/rade_batch.h states the rule): every int16 value in,
 saturation / NaN / truncation and the meters out against tests/wire_ref.py, heads and tails of the 16-byte path in sentinel buffers (tests/bands.py), the host-side
 refusals, the receiver fed through wire_in against the receiver fed through radae_amd/wire.py, the transmitter through wire_out, and the command lines."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -11,49 +10,16 @@ import pytest
 
 import wire_ref as wr
 from bands import SENTINEL, Band
+from gpu_kit import REPO, dev, engines, stream as stream_ptr, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REAL, IQ = 0, 1
 COUNTS = np.array([0, 1, 7, 8, 1031], np.int32)                  # no word, a head alone, head + tail without a word, one word, 128 words + head + tail: more than one chunk has work
 SENT16 = np.array([SENTINEL], np.int32).view(np.int16)           # the sentinel word as the two int16 it is made of
 
 
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engines():
-    """one engine per batch size for the whole module (the calls use none of the model)"""
-    from radae_amd.engine import BatchEngine
-    made = {}
-
-    def get(B, **kw):
-        key = (B, tuple(sorted(kw.items())))
-        if key not in made:
-            made[key] = BatchEngine(B, **{"max_tx_mf": 1, **kw})
-        return made[key]
-    yield get
-    for e in made.values():
-        e.close()
-
-
-def dev(a, torch_dev):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=torch_dev)
-
-
 def u32(t):
     return np.ascontiguousarray(t.cpu().numpy()).view(np.uint32)
-
-
-def stream_ptr():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class Band16:
