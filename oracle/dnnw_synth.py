@@ -1,6 +1,6 @@
 """Seeded synthetic RADE core weights for pinning the DNNw blob reader / writer against the reference's own exporter.
 
-TEST INFRASTRUCTURE -- imported by oracle/gen_golden_dnnw.py (build container, where the reference's exporter runs on these weights)
+TEST INFRASTRUCTURE -- imported by oracle/golden/dnnw_export.py (build container, where the reference's exporter runs on these weights)
 and by tests/ (which regenerate the same weights from the seed instead of carrying 7 MB of floats).  numpy only: `np.random.Generator(PCG64)`
 streams are stable across numpy versions.
 

@@ -1,22 +1,19 @@
-#!/usr/bin/env python3
 """Writes tests/golden/acq.npz: what the reference's stored-file receiver (rx.py --pilots [--bpf] --acq_test) computes on eight inputs, frame by frame.
 
-TEST INFRASTRUCTURE -- never imported by the product.  It imports the reference's radae.dsp.acquisition and complex_bpf (the directory is given with --reference or
-$RADAE_REFERENCE) and drives them with its own restatement of rx.py:146-195: rx.py itself cannot be imported (it runs at import, and needs a checkpoint).
+It imports the reference's radae.dsp.acquisition and complex_bpf (without the n() and randint patches) and drives them with its own restatement of rx.py:146-195: rx.py itself cannot be imported (it runs at import, and needs a checkpoint).
 
 Inputs: the rx_in of the committed rxtrace_mpp / _awgn / _foff / _dfdt recordings (read from those files, not stored again), and two seeded must-not-acquire streams of 12
 modem frames, which are stored (awgn320 / dfdt320 are views of the recordings): complex noise, and a real 1 kHz sine in real noise (the reference's acq_noise and acq_sine ctests in small).
 Recorded per input, without and with the input band-pass: per hop candidate, tmax, f_ind_max, fmax, Dthresh, Dtmax12 and the state log (state, tmax_candidate as the
 script prints them); the acquisition events with refine's results; the --acq_test statistics.  Also Dt1 of one hop of rxtrace_mpp for 64 timings.
 """
-import argparse
 import os
-import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(REPO, "tests", "golden")
+from . import reference as R
+from .reference import golden
+
 FS, M, NCP, NMF, NC = 8000, 160, 32, 960, 30
 RECORDINGS = ("mpp", "awgn", "foff", "dfdt")
 NAMES = RECORDINGS + ("noise", "sine", "awgn320", "dfdt320")
@@ -25,8 +22,8 @@ NAMES = RECORDINGS + ("noise", "sine", "awgn320", "dfdt320")
 TARGETS = {"awgn320": (11.0, 2.0), "dfdt320": (13.25, 2.0)}
 
 
-def inputs():
-    x = {k: np.load(os.path.join(GOLDEN, f"rxtrace_{k}.npz"))["rx_in"].astype(np.complex64) for k in RECORDINGS}
+def inputs(src):
+    x = {k: np.load(golden(src, f"rxtrace_{k}.npz"))["rx_in"].astype(np.complex64) for k in RECORDINGS}
     rng = np.random.default_rng(20261)
     n = 12 * NMF
     x["noise"] = (0.3 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))).astype(np.complex64)
@@ -76,22 +73,17 @@ def run(acq, rx, ntap, fmax_target=0.0, acq_time_target=1.0):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--reference", default=os.environ.get("RADAE_REFERENCE"), help="the reference project's directory (holds radae/dsp.py)")
-    args = ap.parse_args()
-    if not args.reference:
-        sys.exit("give --reference DIR or set RADAE_REFERENCE")
-    sys.path.insert(0, args.reference)
+def main(src, dst):
+    R.enter(patched=False)
     from radae.dsp import acquisition, complex_bpf
-    c = np.load(os.path.join(GOLDEN, "consts.npz"))
+    c = np.load(golden(src, "consts.npz"))
     acq = acquisition(FS, 50, M, NCP, NMF, c["p"], c["pend"])
     assert np.array_equal(acq.p_w, c["acq_p_w"])
     w = c["w"]
     bandwidth = 1.2 * (w[NC - 1] - w[0]) * FS / (2 * np.pi)
     centre = (w[NC - 1] + w[0]) * FS / (2 * np.pi) / 2
     out = {}
-    x = inputs()
+    x = inputs(src)
     out["x_noise"], out["x_sine"] = x["noise"], x["sine"]
     for name in NAMES:
         for tag, ntap in (("raw", 0), ("bpf", 101)):
@@ -101,9 +93,5 @@ def main():
             out.update({f"{name}_{tag}_{k}": v for k, v in r.items()})
     acq.detect_pilots(x["mpp"][2 * NMF:2 * NMF + 2 * NMF + M + NCP])
     out["mpp_raw_hop2_Dt1"] = acq.Dt1[:64].astype(np.complex64)
-    np.savez_compressed(os.path.join(GOLDEN, "acq.npz"), **out)
-    print(os.path.getsize(os.path.join(GOLDEN, "acq.npz")), "bytes")
-
-
-if __name__ == "__main__":
-    main()
+    np.savez_compressed(golden(dst, "acq.npz"), **out)
+    print(os.path.getsize(golden(dst, "acq.npz")), "bytes")

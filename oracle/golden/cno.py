@@ -1,8 +1,5 @@
-#!/usr/bin/env python3
 """Write tests/golden/cno.npz: what the reference's own chirp.py and est_CNo.py write and print, run as child processes (MPLBACKEND=Agg), on one chirp and three
 int16 recordings expanded by the reference's `int16tof32.py --zeropad`.
-
-TEST INFRASTRUCTURE, run where the reference tree is readable (REF below); only the .npz travels with the tests.
 
 Arrays:
     chirp                complex64 [20000]: `chirp.py OUT 2.5` at the defaults (up-sweep, turn, down-sweep, turn again)
@@ -17,8 +14,6 @@ Arrays:
 
 The margins the tests rely on are asserted here in float64 (tests/cno_ref.py): the best window of every recording beats the second best by at least 1e-3 dB, and
 no window has |C| < 1e-4 S_c except those listed in skip2.  If a seed fails them, change the seed, not the margin.
-
-Run:  python3 tools/gen_golden_cno.py
 """
 import os
 import re
@@ -28,32 +23,27 @@ import tempfile
 
 import numpy as np
 
-REF = "/root/reference"
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
+from . import reference as R
+from .reference import golden
 
-import cno_ref as cr  # noqa: E402
-
-OUT = os.path.join(REPO, "tests", "golden", "cno.npz")
 SEED = 20241019
-ENV = dict(os.environ, MPLBACKEND="Agg")
 
 
 def ref_chirp(td, nsec, amp=None):
     path = os.path.join(td, f"chirp_{nsec}_{amp}.f32")
-    subprocess.run([sys.executable, os.path.join(REF, "chirp.py"), path, str(nsec)] + (["--amp", repr(float(amp))] if amp is not None else []), check=True, env=ENV, cwd=td)
+    subprocess.run([sys.executable, os.path.join(R.REF, "chirp.py"), path, str(nsec)] + (["--amp", repr(float(amp))] if amp is not None else []), check=True, cwd=td)
     return np.fromfile(path, np.complex64)
 
 
 def ref_zeropad(s16):
-    out = subprocess.run([sys.executable, os.path.join(REF, "int16tof32.py"), "--zeropad"], input=s16.tobytes(), check=True, capture_output=True, env=ENV).stdout
+    out = subprocess.run([sys.executable, os.path.join(R.REF, "int16tof32.py"), "--zeropad"], input=s16.tobytes(), check=True, capture_output=True).stdout
     return np.frombuffer(out, np.complex64)
 
 
 def ref_est(td, rx, window_time):
     path = os.path.join(td, "rx.f32")
     rx.tofile(path)
-    out = subprocess.run([sys.executable, os.path.join(REF, "est_CNo.py"), path, "--window_time", str(window_time)], check=True, capture_output=True, text=True, env=ENV, cwd=td).stdout
+    out = subprocess.run([sys.executable, os.path.join(R.REF, "est_CNo.py"), path, "--window_time", str(window_time)], check=True, capture_output=True, text=True, cwd=td).stdout
     text = [l for l in out.split("\n") if l.strip()]
     st, cno, measured = [], [], None
     for l in text:
@@ -74,7 +64,11 @@ def recording(rng, n, chirp_re, at, sigma):
     return np.rint(x).astype(np.int16)
 
 
-def main():
+def main(src, dst):
+    R.enter(patched=False)
+    sys.path.insert(0, os.path.join(R.REPO, "tests"))
+    import cno_ref as cr
+    OUT = golden(dst, "cno.npz")
     rng = np.random.default_rng(SEED)
     with tempfile.TemporaryDirectory() as td:
         chirp = ref_chirp(td, 2.5)
@@ -110,7 +104,3 @@ def main():
     size = os.path.getsize(OUT)
     print(f"{OUT}: {size} bytes")
     assert size < 400 * 1024
-
-
-if __name__ == "__main__":
-    main()

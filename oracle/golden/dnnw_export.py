@@ -1,12 +1,9 @@
-#!/usr/bin/env python3
-"""Pin the DNNw weight blob against the reference's OWN exporter (this container only).
-
-TEST INFRASTRUCTURE -- never imported by the product; /root/reference does not exist on the GPU box, only the fixtures written here travel.
+"""Pin the DNNw weight blob against the reference's OWN exporter (`n()` clamp-only, as oracle/golden/reference.py patches it).
 
 What runs, and whose code it is:
   1. oracle/dnnw_synth.py makes two seeded checkpoints of the model19 architecture (torch orientation): A "lossless" (int8-exact rows, power-of-two
      row scales, genuinely sparse GRU input blocks) and B "generic" (Gaussian floats, same sparsity).  They are loaded into the reference's
-     `RADAE(21, 80, EbNodB=100)` exactly as `/root/reference/export_rade_weights.py:208-212` builds it, through `state_dict` keys only.
+     `RADAE(21, 80, EbNodB=100)` exactly as `export_rade_weights.py:208-212` builds it, through `state_dict` keys only.
   2. THE REFERENCE'S EXPORTER: `export_rade_weights.py` is executed with runpy (its argparse runs at import) and its `c_export(args, model)`
      (:54-172) is called on that model; it drives `wexchange.torch.dump_torch_weights` -> `wexchange/c_export/common.py` (`print_gru_layer` :346-382,
      `print_dense_layer` :279-294, `print_conv1d_layer` :297-321, `print_linear_layer` :200-277, `print_sparse_weight` :140-176, `compute_scaling` :180-194,
@@ -16,16 +13,14 @@ What runs, and whose code it is:
      `compute_scaling`'s scale, `quantize_weight`'s q, subias -- by calling the reference's own functions on the reference's own arguments.
   4. The emitted C is parsed (array initialisers, the `radeenc_arrays[]` / `radedec_arrays[]` tables, `#ifndef DISABLE_DEBUG_FLOAT` sections dropped as in the build that
      produced bin/model19_check3.bin: that blob has no `*_weights_float` for quantised layers) and packed record by record as
-     `/root/reference/src/write_rade_weights.c:51-74` does (64-byte WeightHead, payload, zero padding to a multiple of 64; encoder table then decoder table).
+     the reference's `src/write_rade_weights.c:51-74` does (64-byte WeightHead, payload, zero padding to a multiple of 64; encoder table then decoder table).
      Decimal literals become floats the way a C compiler reads them (decimal -> double -> float).
   5. Reference-module outputs on checkpoint A: `CoreEncoderStatefull` / `CoreDecoderStatefull` (radae_base.py:223-286, :358-430; `n()` clamp-only) stepped one
      40 ms step per call on seeded features / latents -- the float modules holding the checkpoint itself, no de-quantisation of mine involved.
 
 Fixtures: tests/golden/dnnw_export_A.bin (the reference-exported blob of checkpoint A, 2.4 MB), tests/golden/dnnw_export.npz (per-layer exporter records for A,
 sha256 + per-record digests of the exported blob of B, module outputs for A), tests/golden/weights_check.npz (per-tensor statistics of CHECKPOINT A itself:
-size, sum, sum of magnitudes, first 8 and last 4 values -- what a correct reader returns for the lossless blob; rounds 1-5 wrote this file from radae_amd/dnnw.py's own reading of model19_check3.bin).
-
-Run:  python3 oracle/gen_golden_dnnw.py     (~1 min)
+size, sum, sum of magnitudes, first 8 and last 4 values -- what a correct reader returns for the lossless blob, not radae_amd/dnnw.py's own reading of model19_check3.bin).
 """
 import hashlib
 import os
@@ -35,32 +30,17 @@ import struct
 import sys
 import tempfile
 
-REF = "/root/reference"
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REF)
-sys.path.insert(0, os.path.join(REF, "weight-exchange"))
-sys.path.insert(0, REPO)
-
 import numpy as np
-import torch
 
-torch.set_num_threads(1)
-os.chdir(REF)
+from . import reference as R
+from .reference import golden
 
-import radae.radae_base as rb
-
-rb.n = lambda x: torch.clamp(x, min=-1.0, max=1.0)
-from radae import RADAE  # noqa: E402
-import wexchange.c_export.common as wx_common  # noqa: E402
-
-from oracle import dnnw_synth  # noqa: E402
-
-OUT = os.path.join(REPO, "tests", "golden")
 SEED_A, SEED_B = 19001, 19002
 
 
 def load_checkpoint_into(model, m):
     """synthetic tensors -> the reference's RADAE module (the role of torch.load + load_state_dict, export_rade_weights.py:208-212)."""
+    import torch
     sd = model.state_dict()
     T = torch.tensor
     new = {}
@@ -102,10 +82,13 @@ def load_checkpoint_into(model, m):
 
 def run_reference_exporter(m, outdir):
     """Steps 2 + 3 of the module docstring.  Returns the per-layer records of the exporter."""
+    import torch
+    from radae import RADAE
+    import wexchange.c_export.common as wx_common
     argv = sys.argv
     sys.argv = ["export_rade_weights.py", "synthetic_checkpoint", outdir]
     try:
-        script = runpy.run_path(os.path.join(REF, "export_rade_weights.py"), run_name="export_rade_weights")
+        script = runpy.run_path(os.path.join(R.REF, "export_rade_weights.py"), run_name="export_rade_weights")
     finally:
         sys.argv = argv
     args = script["args"]
@@ -189,12 +172,16 @@ def stats(a):
     return np.array([a.size, a.sum(), np.abs(a).sum()] + list(a[:8]) + list(a[-4:]))
 
 
-def main():
+def main(src, dst):
+    R.enter()
+    sys.path.insert(0, os.path.join(R.REF, "weight-exchange"))
+    import torch
+    from oracle import dnnw_synth
     fx = {}
     # ---- checkpoint A: lossless ----
     mA = dnnw_synth.synth_model(SEED_A, lossless=True)
     recA, modelA, entA, blobA = export(mA, "A")
-    open(os.path.join(OUT, "dnnw_export_A.bin"), "wb").write(blobA)
+    open(golden(dst, "dnnw_export_A.bin"), "wb").write(blobA)
     fx["A_sha256"] = np.array(hashlib.sha256(blobA).hexdigest())
     fx["A_record_names"] = np.array([e[0] for e in entA])
     for name, r in recA.items():
@@ -213,7 +200,7 @@ def main():
             assert blocks.sum() < blocks.size, "the GRU input must be genuinely sparse"
     # per-tensor statistics of the CHECKPOINT (what a correct reader returns for a lossless blob): weights_check's format
     tA = dnnw_synth.tensors(mA)
-    np.savez(os.path.join(OUT, "weights_check.npz"), **{k: stats(v.transpose(0, 2, 1) if v.ndim == 3 else v) for k, v in tA.items()})   # conv as [out][tap][in]: the C layout
+    np.savez(golden(dst, "weights_check.npz"), **{k: stats(v.transpose(0, 2, 1) if v.ndim == 3 else v) for k, v in tA.items()})   # conv as [out][tap][in]: the C layout
     # ---- reference-module outputs on checkpoint A ----
     modelA.core_encoder_statefull_load_state_dict()
     modelA.core_decoder_statefull_load_state_dict()
@@ -250,9 +237,5 @@ def main():
         fx[f"B/{name}/scale"] = r["scale"].astype(np.float32); fx[f"B/{name}/subias"] = r["subias"].astype(np.float64)
         fx[f"B/{name}/q_head"] = r["q"][:8, :16].astype(np.int8)
     fx["seeds"] = np.array([SEED_A, SEED_B])
-    np.savez_compressed(os.path.join(OUT, "dnnw_export.npz"), **fx)
+    np.savez_compressed(golden(dst, "dnnw_export.npz"), **fx)
     print("dnnw_export ok")
-
-
-if __name__ == "__main__":
-    main()

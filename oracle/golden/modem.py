@@ -1,121 +1,20 @@
-#!/usr/bin/env python3
-"""Generate the golden fixtures under tests/golden/ by IMPORTING the reference (this container only).
+"""The model19 modem end to end, made by IMPORTING the reference: constants, encoder + transmitter, channel + receiver traces, the ctests' test-mode knobs,
+decoder + loss, the model05 and BBFM configurations, the int16 wire converters.  How the reference is driven and what is patched: oracle/golden/reference.py.
 
-TEST INFRASTRUCTURE -- never imported by the product.  /root/reference does not exist on the GPU
-box; only the small .npz files this script writes travel there.
-
-What is pinned and how the reference is driven:
-  * `radae.radae_base.n` (radae_base.py:80-81) is replaced by clamp-only: the reference adds
-    uniform noise in eval mode, which makes it non-deterministic.
-  * weights: `weights/model19_check3.bin` (byte copy of /root/reference/bin/model19_check3.bin)
-    de-quantised by radae_amd.dnnw and loaded into the reference's own torch modules.
-  * `np.random.randint` (used unseeded by dsp.py:293) is replaced by the documented LCG
-    x <- x*1664525+1013904223 mod 2^32, row = (x>>8) % Nmf, seed 1.
-  * channel noise: `RADAE.forward` draws torch.randn_like internally (radae.py:578); we re-seed
-    torch and regenerate the identical tensor so the fixture can carry the noise explicitly.
-
-Run:  python3 oracle/gen_golden.py            (takes ~1 min)
+(weights_check.npz belongs to dnnw_export.py: from a checkpoint run through the reference's own exporter, not from radae_amd/dnnw.py's reading of model19_check3.bin.)
 """
 import os
 import sys
 
-REF = "/root/reference"
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REF)
-sys.path.insert(0, REPO)
-
 import numpy as np
-import torch
 
-torch.set_num_threads(1)
-
-import radae.radae_base as rb
-
-rb.n = lambda x: torch.clamp(x, min=-1.0, max=1.0)
-
-os.chdir(REF)  # reference modules print to stderr and expect cwd-relative imports
-import radae_txe  # noqa: E402
-import radae_rxe  # noqa: E402
-from radae import RADAE, distortion_loss  # noqa: E402
-
-from radae_amd import dnnw  # noqa: E402
-from radae_amd.channel_tools import multipath_g, synth_features  # noqa: E402
-
-OUT = os.path.join(REPO, "tests", "golden")
-os.makedirs(OUT, exist_ok=True)
-BLOB = os.path.join(REPO, "weights", "model19_check3.bin")
+from . import reference as R
+from .reference import c64, channel_case, golden, load_into, new_rx, new_tx, run_rx, with_aux
 
 
-class Lcg:
-    def __init__(self, seed=1):
-        self.x = seed & 0xFFFFFFFF
-
-    def randint(self, n):
-        self.x = (self.x * 1664525 + 1013904223) & 0xFFFFFFFF
-        return (self.x >> 8) % n
-
-
-_lcg = Lcg(1)
-np.random.randint = lambda n: _lcg.randint(n)
-
-
-def load_into(model, m):
-    """De-quantised blob tensors -> reference torch modules."""
-    enc = model.core_encoder.module
-    dec = model.core_decoder.module
-    T = torch.tensor
-    with torch.no_grad():
-        enc.dense_1.weight.copy_(T(m.enc_dense1.w)); enc.dense_1.bias.copy_(T(m.enc_dense1.b))
-        enc.z_dense.weight.copy_(T(m.enc_zdense.w)); enc.z_dense.bias.copy_(T(m.enc_zdense.b))
-        dec.dense_1.weight.copy_(T(m.dec_dense1.w)); dec.dense_1.bias.copy_(T(m.dec_dense1.b))
-        dec.output.weight.copy_(T(m.dec_output.w)); dec.output.bias.copy_(T(m.dec_output.b))
-        for i in range(5):
-            for mod, G, C in ((enc, m.enc_gru[i], m.enc_conv[i]), (dec, m.dec_gru[i], m.dec_conv[i])):
-                g = getattr(mod, f"gru{i+1}")
-                g.weight_ih_l0.copy_(T(G.w_ih)); g.weight_hh_l0.copy_(T(G.w_hh))
-                g.bias_ih_l0.copy_(T(G.b_ih)); g.bias_hh_l0.copy_(T(G.b_hh))
-                c = getattr(mod, f"conv{i+1}").conv
-                c.weight.copy_(T(C.w)); c.bias.copy_(T(C.b))
-            gate = getattr(dec, f"glu{i+1}").gate
-            W = T(m.dec_glu[i].w)
-            gate.parametrizations.weight.original1.copy_(W)
-            gate.parametrizations.weight.original0.copy_(W.norm(dim=1, keepdim=True))
-    model.core_encoder_statefull_load_state_dict()
-    model.core_decoder_statefull_load_state_dict()
-
-
-def c64(x):
-    return np.asarray(x).astype(np.complex64)
-
-
-def with_aux(feat36):
-    """(T,36) -> (1,T,21) with the aux symbol -1 appended (radae_txe.py:114-121)."""
-    f = feat36[:, :20]
-    return torch.tensor(np.concatenate([f, -np.ones((f.shape[0], 1), np.float32)], axis=1)[None])
-
-
-M19 = dnnw.load_model(BLOB)
-
-
-def new_tx():
-    tx = radae_txe.radae_tx("unused", bypass_enc=True)
-    tx.bypass_enc = False
-    tx.n_floats_in = 432
-    load_into(tx.model, M19)
-    return tx
-
-
-def new_rx():
-    rx = radae_rxe.radae_rx("unused", bypass_dec=True, v=0)
-    rx.bypass_dec = False
-    rx.n_floats_out = 432
-    load_into(rx.model, M19)
-    _lcg.x = 1
-    return rx
-
-
-# ----------------------------------------------------------------------------------------------
-def gen_consts():
+def gen_consts(src, dst):
+    R.enter()
+    import torch
     tx = new_tx()
     rx = new_rx()
     md = tx.model
@@ -125,7 +24,7 @@ def gen_consts():
     md.set_eoo_bits(torch.tensor(bits))
     eoo_bits = c64(md.eoo.numpy().flatten())
     np.savez(
-        os.path.join(OUT, "consts.npz"),
+        golden(dst, "consts.npz"),
         w=md.w.numpy().astype(np.float32), Winv=c64(md.Winv.numpy()), Wfwd=c64(md.Wfwd.numpy()),
         P=c64(md.P.numpy()), Pend=c64(md.Pend.numpy()), p=c64(md.p.numpy()), pend=c64(md.pend.numpy()),
         p_cp=c64(md.p_cp.numpy()), pend_cp=c64(md.pend_cp.numpy()),
@@ -139,12 +38,11 @@ def gen_consts():
     print("consts ok")
 
 
-# weights_check.npz is written by oracle/gen_golden_dnnw.py since round 6: from a checkpoint run through the reference's own exporter, not from
-# radae_amd/dnnw.py's reading of model19_check3.bin (which pinned the readers against each other only).
-
-
-def gen_enc_tx():
+def gen_enc_tx(src, dst):
     """Encoder (stateful, 12 frames per call = radae_txe.do_radae_tx) + transmitter_one."""
+    R.enter()
+    import torch
+    from radae_amd.channel_tools import synth_features
     nutt, T = 2, 120
     feats = np.stack([synth_features(100 + u, T) for u in range(nutt)])  # (2,120,36)
     z_all, tx_all, z_stateless = [], [], []
@@ -169,7 +67,7 @@ def gen_enc_tx():
             mod = tx.model.core_encoder_statefull.module
             gru_states = np.stack([getattr(mod, f"gru{i}").states.numpy().reshape(-1) for i in range(1, 6)])
             conv_states = [getattr(mod, f"conv{i}").states.numpy()[0] for i in range(1, 6)]
-    np.savez(os.path.join(OUT, "enc_tx.npz"), features=feats, z=np.stack(z_all).astype(np.float32),
+    np.savez(golden(dst, "enc_tx.npz"), features=feats, z=np.stack(z_all).astype(np.float32),
              z_stateless=np.stack(z_stateless).astype(np.float32), tx=c64(np.stack(tx_all)),
              gru_states_u0=gru_states.astype(np.float32),
              **{f"conv{i+1}_state_u0": conv_states[i].astype(np.float32) for i in range(5)})
@@ -177,100 +75,8 @@ def gen_enc_tx():
     print(f"enc_tx ok  (stateful vs stateless max diff {d:.2e})")
 
 
-def channel_case(name, T, EbNodB, freq_offset, chan, seed, prepend_s=1.0, append_s=0.3, df_dt=0.0):
-    """inference.py-equivalent channel simulation through the reference's RADAE.forward
-    (radae.py:457-602) + the write_rx tail of inference.py:253-290."""
-    feat36 = synth_features(seed, T)
-    model = RADAE(21, 80, EbNodB, rate_Fs=True, freq_offset=freq_offset, df_dt=df_dt, pilots=True, pilot_eq=True,
-                  eq_mean6=False, cyclic_prefix=0.004, time_offset=-16, coarse_mag=True, bottleneck=3,
-                  correct_freq_offset=True)
-    load_into(model, M19)
-    model.eval()
-    features = with_aux(feat36)
-    nRs = model.num_timesteps_at_rate_Rs(T)
-    nFs = model.num_timesteps_at_rate_Fs(nRs)
-    H = torch.ones((1, nRs, model.Nc))
-    if chan == "awgn":
-        G = np.ones((nFs, 2), np.complex64); G[:, 1] = 0
-    else:
-        G = multipath_g(chan, 8000, nFs, seed + 7)
-    Gt = torch.tensor(G[None])
-    torch.manual_seed(seed)
-    with torch.inference_mode():
-        out = model(features, H, Gt)
-    torch.manual_seed(seed)
-    noise = torch.randn(1, nFs, dtype=torch.complex64)
-    sigma = float(out["sigma"].item())
-    rx = out["rx"]
-    assert torch.allclose(rx, (rx - sigma * noise) + sigma * noise)
-    # write_rx tail: EOO with continued phase, then real-valued pre/post noise (inference.py:263-284)
-    eoo = model.eoo
-    freq = torch.zeros_like(eoo)
-    freq[:, ] = model.freq_offset * torch.ones_like(eoo) + model.df_dt * torch.arange(eoo.shape[1]) / model.Fs
-    omega = freq * 2 * torch.pi / model.Fs
-    lin_phase = torch.exp(1j * torch.cumsum(omega, dim=1))
-    eoo_rot = eoo * lin_phase * model.final_phase
-    n_eoo = torch.randn_like(eoo_rot)
-    eoo_rx = eoo_rot + sigma * n_eoo
-    n_pre = torch.randn(1, int(model.Fs * prepend_s))
-    n_post = torch.randn(1, int(model.Fs * append_s))
-    rx_full = torch.concatenate([sigma * n_pre, rx, eoo_rx, sigma * n_post], dim=1)
-    d = dict(features=feat36, G=G, noise=c64(noise.numpy()[0]), sigma=np.float64(sigma),
-             EbNodB=np.float64(EbNodB), freq_offset=np.float64(freq_offset), df_dt=np.float64(df_dt),
-             tx=c64(out["tx"].numpy()[0]), rx=c64(rx.numpy()[0]), noise_eoo=c64(n_eoo.numpy()[0]),
-             noise_pre=n_pre.numpy()[0].astype(np.float32), noise_post=n_post.numpy()[0].astype(np.float32),
-             rx_full=c64(rx_full.numpy()[0]), z_fwd=out["z_hat"].numpy()[0].astype(np.float32),
-             final_phase=c64(model.final_phase.numpy()))
-    return d
-
-
-def run_rx(rx_stream, foff_err=0.0, disable_unsync=0.0):
-    """Drive the reference radae_rx exactly like radae_rxe.py:349-356 and record a per-call trace."""
-    rx = new_rx()
-    rx.foff_err = foff_err
-    rx.disable_unsync = disable_unsync          # radae_rxe.py:65, :277-281
-    zlog = []
-    orig = rx.receiver.receiver_one
-    def hook(r, eoo, _o=orig):
-        z = _o(r, eoo); zlog.append(z.detach().numpy().reshape(-1).copy()); return z
-    rx.receiver.receiver_one = hook
-    floats_out = np.zeros(432, np.float32)
-    names = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count",
-             "uw_errors", "synced_count", "snr_int"]
-    tr = {k: [] for k in names}
-    trf = {k: [] for k in ["fmax", "Dthresh", "Dtmax12", "Dtmax12_eoo", "snrdB_3k_est"]}
-    z_hat, feats_out, eoo_out = [], [], []
-    st = {"search": 0, "candidate": 1, "sync": 2}
-    pos = 0
-    while pos + rx.get_nin() <= len(rx_stream):
-        nin = rx.get_nin()
-        buf = np.zeros(rx.get_nin_max(), np.csingle)
-        buf[:nin] = rx_stream[pos:pos + nin]
-        pos += nin
-        sb = st[rx.state]
-        nz = len(zlog)
-        ret = rx.do_radae_rx(buf, floats_out)
-        tr["state_before"].append(sb); tr["state_after"].append(st[rx.state])
-        tr["nin_before"].append(nin); tr["nin_after"].append(rx.get_nin()); tr["ret"].append(int(ret))
-        tr["tmax"].append(int(rx.tmax)); tr["f_ind_max"].append(int(rx.acq.f_ind_max) if hasattr(rx.acq, "f_ind_max") else -1)
-        tr["valid_count"].append(int(rx.valid_count)); tr["uw_errors"].append(int(rx.uw_errors))
-        tr["synced_count"].append(int(rx.synced_count)); tr["snr_int"].append(int(rx.get_snrdB_3k_est()))
-        trf["fmax"].append(float(rx.fmax)); trf["Dthresh"].append(float(rx.acq.Dthresh))
-        trf["Dtmax12"].append(float(rx.acq.Dtmax12)); trf["Dtmax12_eoo"].append(float(rx.acq.Dtmax12_eoo))
-        trf["snrdB_3k_est"].append(float(rx.receiver.snrdB_3k_est))
-        if ret & 1:
-            z_hat.append(zlog[-1].copy()); feats_out.append(floats_out.copy())
-        if ret & 2:
-            eoo_out.append(floats_out[:180].copy())
-    d = {k: np.array(v, np.int32) for k, v in tr.items()}
-    d.update({k: np.array(v, np.float64) for k, v in trf.items()})
-    d["z_hat"] = np.array(z_hat, np.float32).reshape(-1, 240)
-    d["features_out"] = np.array(feats_out, np.float32).reshape(-1, 432)
-    d["eoo_out"] = np.array(eoo_out, np.float32).reshape(-1, 180)
-    return d
-
-
-def gen_chan_rx():
+def gen_chan_rx(src, dst):
+    R.enter()
     from scipy.signal import resample_poly
     cases = {
         # name: (T frames, EbNodB, freq_offset, channel, seed, prepend_s)
@@ -280,8 +86,8 @@ def gen_chan_rx():
     for name, (T, eb, fo, ch, seed, pre) in cases.items():
         d = channel_case(name, T, eb, fo, ch, seed, prepend_s=pre)
         tr = run_rx(d["rx_full"])
-        np.savez_compressed(os.path.join(OUT, f"chan_{name}.npz"), **d)
-        np.savez_compressed(os.path.join(OUT, f"rxtrace_{name}.npz"), rx_in=d["rx_full"], features_in=d["features"], **tr)
+        np.savez_compressed(golden(dst, f"chan_{name}.npz"), **d)
+        np.savez_compressed(golden(dst, f"rxtrace_{name}.npz"), rx_in=d["rx_full"], features_in=d["features"], **tr)
         print(f"chan/rx {name}: calls {len(tr['ret'])} valid {int((tr['ret'] & 1).sum())} eoo {int((tr['ret'] >> 1).sum())}"
               f" states {tr['state_after'].tolist()}")
     # timing slips (ctests radae_rx_slip_plus / _minus) -- sox is absent, scipy polyphase resampler instead
@@ -290,29 +96,30 @@ def gen_chan_rx():
         x = d["rx_full"]
         xr = (resample_poly(x.real.astype(np.float64), up, dn) + 1j * resample_poly(x.imag.astype(np.float64), up, dn)).astype(np.complex64)
         tr = run_rx(xr)
-        np.savez_compressed(os.path.join(OUT, f"rxtrace_{name}.npz"), rx_in=xr, features_in=d["features"], **tr)
+        np.savez_compressed(golden(dst, f"rxtrace_{name}.npz"), rx_in=xr, features_in=d["features"], **tr)
         print(f"rx {name}: calls {len(tr['ret'])} valid {int((tr['ret'] & 1).sum())} nin set {sorted(set(tr['nin_after'].tolist()))}"
               f" tmax range {tr['tmax'].min()}..{tr['tmax'].max()}")
     # false-sync / UW failure path: rade_api.c:263-264 RADE_FOFF_TEST => foff_err = 10 Hz on first sync
     d = channel_case("foff", 240, 10.0, 11.0, "awgn", 1003, prepend_s=0.5)
     tr = run_rx(d["rx_full"], foff_err=10.0)
-    np.savez_compressed(os.path.join(OUT, "rxtrace_foff.npz"), rx_in=d["rx_full"], features_in=d["features"], **tr)
+    np.savez_compressed(golden(dst, "rxtrace_foff.npz"), rx_in=d["rx_full"], features_in=d["features"], **tr)
     print(f"rx foff: states {tr['state_after'].tolist()} uw {tr['uw_errors'].tolist()}")
 
 
-def gen_knobs():
+def gen_knobs(src, dst):
     """The test-mode knobs the reference's ctests use and the first fixture set left at their defaults:
     df_dt (frequency drift, radae.py:547-552 + inference.py:270; ctest radae_rx_dfdt, CMakeLists.txt:363-371) and
     --disable_unsync (radae_rxe.py:277-281; ctests radae_rx_mpp / radae_rx_mpg, CMakeLists.txt:326-347)."""
+    R.enter()
     keep = ("features", "noise", "sigma", "EbNodB", "freq_offset", "df_dt", "tx", "rx", "noise_eoo", "noise_pre", "noise_post", "rx_full", "final_phase")
     for name, dfdt in (("dfdt_pos", 0.5), ("dfdt_neg", -0.5)):
         d = channel_case(name, 120, 10.0, 13.0, "awgn", 1010, prepend_s=0.5, append_s=0.2, df_dt=dfdt)
-        np.savez_compressed(os.path.join(OUT, f"chan_{name}.npz"), **{k: d[k] for k in keep})
+        np.savez_compressed(golden(dst, f"chan_{name}.npz"), **{k: d[k] for k in keep})
         print(f"chan {name}: final phase {d['final_phase']}")
     # receiver trace through a drifting offset, the ctest's recipe at reduced length (Eb/No 1 dB, +13 Hz, 0.1 Hz/s)
     d = channel_case("dfdt", 240, 1.0, 13.0, "awgn", 1011, prepend_s=1.0, append_s=0.3, df_dt=0.1)
     tr = run_rx(d["rx_full"])
-    np.savez_compressed(os.path.join(OUT, "rxtrace_dfdt.npz"), rx_in=d["rx_full"], features_in=d["features"], **tr)
+    np.savez_compressed(golden(dst, "rxtrace_dfdt.npz"), rx_in=d["rx_full"], features_in=d["features"], **tr)
     print(f"rx dfdt: calls {len(tr['ret'])} valid {int((tr['ret'] & 1).sum())} fmax {tr['fmax'][[10, -3]]}")
     # --disable_unsync: MPP at 0 dB with a deep fade, unsync paths switched off after 0.5 s of sync (41 frames at the ctest's 5 s
     # would outlast a short fixture); the same samples without the flag lose sync, so the pair pins both branches
@@ -322,13 +129,16 @@ def gen_knobs():
     x[n0:n0 + 27 * 960] = d["sigma"] * d["noise"][:27 * 960]
     tr_on = run_rx(x, disable_unsync=0.5); tr_off = run_rx(x)
     assert not np.array_equal(tr_on["state_after"], tr_off["state_after"]), "fixture does not exercise the flag"
-    np.savez_compressed(os.path.join(OUT, "rxtrace_nounsync.npz"), rx_in=c64(x), features_in=d["features"], disable_unsync=np.float64(0.5), **tr_on)
+    np.savez_compressed(golden(dst, "rxtrace_nounsync.npz"), rx_in=c64(x), features_in=d["features"], disable_unsync=np.float64(0.5), **tr_on)
     print(f"rx nounsync: states with flag {tr_on['state_after'].tolist()}\n            without {tr_off['state_after'].tolist()}")
 
 
-def gen_dec_loss():
+def gen_dec_loss(src, dst):
+    R.enter()
+    import torch
+    from radae import distortion_loss
     rng = np.random.default_rng(5)
-    g = np.load(os.path.join(OUT, "rxtrace_awgn.npz"))
+    g = np.load(golden(src, "rxtrace_awgn.npz"))
     z = g["z_hat"][:10].reshape(1, 30, 80)
     rx = new_rx()
     dec = rx.model.core_decoder_statefull
@@ -344,17 +154,22 @@ def gen_dec_loss():
     b = torch.tensor(rng.standard_normal((1, 50, 20)).astype(np.float32))
     a21 = torch.tensor(rng.standard_normal((1, 50, 21)).astype(np.float32))
     b21 = torch.tensor(rng.standard_normal((1, 50, 21)).astype(np.float32))
-    np.savez(os.path.join(OUT, "dec_loss.npz"), z_hat=z[0].astype(np.float32), features=feats.astype(np.float32),
+    np.savez(golden(dst, "dec_loss.npz"), z_hat=z[0].astype(np.float32), features=feats.astype(np.float32),
              features_stateless=stateless.astype(np.float32), gru_states=gru_states.astype(np.float32),
              la=a.numpy()[0], lb=b.numpy()[0], loss20=np.float64(distortion_loss(a, b).item()),
              la21=a21.numpy()[0], lb21=b21.numpy()[0], loss21=np.float64(distortion_loss(a21, b21).item()))
     print(f"dec ok (stateful vs stateless max diff {np.abs(feats - stateless).max():.2e})")
 
 
-def gen_model05():
+def gen_model05(src, dst):
     """Config 1: inference.py plumbing with model05 -- RADAE(20, 80, EbNodB) defaults: rate Rs, Nc=20, Ns=6, no
     pilots, bottleneck 1 (radae.py:604-634).  H = 1 (AWGN) and a multipath-magnitude H."""
-    m05 = dnnw.load_model(os.path.join(REPO, "weights", "model05.bin"))
+    R.enter()
+    import torch
+    from radae import RADAE, distortion_loss
+    from radae_amd import dnnw
+    from radae_amd.channel_tools import synth_features
+    m05 = dnnw.load_model(os.path.join(R.REPO, "weights", "model05.bin"))
     T = 900                                                  # 9.0 s, stand-in for wav/peter.wav
     feat36 = synth_features(2000, T)
     features = torch.tensor(feat36[None, :, :20])
@@ -380,16 +195,19 @@ def gen_model05():
                     f"{tag}_z_hat": o["z_hat"].numpy()[0].astype(np.float32), f"{tag}_features_hat": o["features_hat"].numpy()[0].astype(np.float32)})
         out["z"] = z.numpy()[0].astype(np.float32)
         out[f"{tag}_loss"] = np.float64(distortion_loss(features, o["features_hat"]).item())
-    np.savez_compressed(os.path.join(OUT, "model05.npz"), features=feat36[:, :20].astype(np.float32), **out)
+    np.savez_compressed(golden(dst, "model05.npz"), features=feat36[:, :20].astype(np.float32), **out)
     print("model05 ok", {k: float(v) for k, v in out.items() if k.endswith("loss")})
 
 
-def gen_bbfm():
+def gen_bbfm(src, dst):
     """Config 5: BBFM(20, 80, CNRdB) (bbfm.py:42-197).  No trained weights exist, so seeded random weights
     (torch default init + orthogonal weight_hh, radae_base.py:72-77,136-147) are exported to a DNNw blob with
     radae_amd.dnnw.write_blob, and the de-quantised blob is what both the reference modules and the engine load."""
+    R.enter()
+    import torch
     from radae import BBFM
-    from radae_amd.channel_tools import doppler_spread
+    from radae_amd import dnnw
+    from radae_amd.channel_tools import doppler_spread, synth_features
     torch.manual_seed(20240501)
     model = BBFM(20, 80, 20.0)
     enc, dec = model.core_encoder.module, model.core_decoder.module
@@ -405,7 +223,7 @@ def gen_bbfm():
         dec_glu=[dnnw.Dense(sd(getattr(dec, f"glu{i}").gate.weight), np.zeros(96, np.float32)) for i in range(1, 6)],
         dec_conv=[dnnw.Conv(sd(getattr(dec, f"conv{i}").conv.weight), sd(getattr(dec, f"conv{i}").conv.bias), 1) for i in range(1, 6)],
         dec_output=dnnw.Dense(sd(dec.output.weight), sd(dec.output.bias)))
-    blob = os.path.join(REPO, "weights", "bbfm_random_seed20240501.bin")
+    blob = os.path.join(dst, "weights", "bbfm_random_seed20240501.bin")
     dnnw.write_blob(m, blob)
     mq = dnnw.load_model(blob)
     T = 480
@@ -428,31 +246,20 @@ def gen_bbfm():
         out.update({f"{tag}_H": Hn, f"{tag}_noise": noise, f"{tag}_CNRdB": np.float64(CNRdB), f"{tag}_z_hat": o["z_hat"].numpy()[0].astype(np.float32),
                     f"{tag}_features_hat": o["features_hat"].numpy()[0].astype(np.float32), f"{tag}_sigma": o["sigma"].numpy().reshape(-1).astype(np.float32)})
         out["z"] = z.numpy()[0].astype(np.float32)
-    np.savez_compressed(os.path.join(OUT, "bbfm.npz"), features=feat36[:, :20].astype(np.float32), Gfm=np.float64(model.Gfm), **out)
+    np.savez_compressed(golden(dst, "bbfm.npz"), features=feat36[:, :20].astype(np.float32), Gfm=np.float64(model.Gfm), **out)
     print("bbfm ok Gfm", model.Gfm, "frac below FM threshold (ray):", float(np.mean(20 * np.log10(Hray) + 14.0 < 12)))
 
 
-def gen_wire():
+def gen_wire(src, dst):
     """int16 <-> f32 converters: the reference's own scripts (int16tof32.py, f32toint16.py) run as subprocesses on fixed bytes."""
+    R.enter()
     import subprocess
     rng = np.random.default_rng(5)
     i16 = rng.integers(-32768, 32767, 2001, dtype=np.int16).tobytes()             # odd count: the trailing sample is dropped
     f32 = np.concatenate([rng.uniform(-1.2, 1.2, 600), [0.99999, -0.99999, 1.0, -1.0, 0.5 / 32767, -0.5 / 32767]]).astype(np.float32).tobytes()
-    run = lambda script, args, data: subprocess.run([sys.executable, os.path.join(REF, script)] + args, input=data, stdout=subprocess.PIPE, check=True).stdout
-    np.savez_compressed(os.path.join(OUT, "wire.npz"), i16=np.frombuffer(i16, np.uint8), f32=np.frombuffer(f32, np.uint8),
+    run = lambda script, args, data: subprocess.run([sys.executable, os.path.join(R.REF, script)] + args, input=data, stdout=subprocess.PIPE, check=True).stdout
+    np.savez_compressed(golden(dst, "wire.npz"), i16=np.frombuffer(i16, np.uint8), f32=np.frombuffer(f32, np.uint8),
                         i2f=np.frombuffer(run("int16tof32.py", [], i16), np.uint8), i2f_zp=np.frombuffer(run("int16tof32.py", ["--zeropad"], i16), np.uint8),
                         f2i=np.frombuffer(run("f32toint16.py", [], f32), np.uint8), f2i_real=np.frombuffer(run("f32toint16.py", ["--real"], f32), np.uint8),
                         f2i_scale=np.frombuffer(run("f32toint16.py", ["--scale", "8192"], f32), np.uint8))
     print("wire ok")
-
-
-if __name__ == "__main__":
-    which = sys.argv[1:] or ["consts", "weights", "enc", "chanrx", "dec", "model05", "bbfm", "wire", "knobs"]
-    if "wire" in which: gen_wire()
-    if "knobs" in which: gen_knobs()
-    if "consts" in which: gen_consts()
-    if "enc" in which: gen_enc_tx()
-    if "chanrx" in which: gen_chan_rx()
-    if "dec" in which: gen_dec_loss()
-    if "model05" in which: gen_model05()
-    if "bbfm" in which: gen_bbfm()

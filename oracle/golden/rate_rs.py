@@ -1,43 +1,27 @@
-#!/usr/bin/env python3
 """Write tests/golden/rate_rs_bn3.npz: the rate-Rs channel of the bottleneck-3 model (radae.py:603-634, the "hybrid time & frequency domain model": IDFT, PA limiter,
 DFT, phase offset, |H|, AWGN) as the reference's RADAE.forward computes it.
 
-TEST INFRASTRUCTURE, run where the reference tree is importable (REF below); only the .npz travels with the tests.
-
 The encoder is stubbed to return given latents and the decoder to return z_hat, so a case is (z, H, noise, sigma, phase_offset) -> (z_hat, tx, tx_sym); the noise is the
-forward's own draw, re-seeded and drawn again (as tools/gen_golden_ideal_rx.py does), and the script asserts that it reproduces the forward's z_hat bit for bit.
+forward's own draw, re-seeded and drawn again (as oracle/golden/ideal_rx.py does), and the script asserts that it reproduces the forward's z_hat bit for bit.
 Numerology: RADAE(21, 80, EbNodB, bottleneck=3) without pilots, cyclic prefix or rate_Fs: Nc = 20, Ns = 6, M = 160 (pilots=True does not run in this branch).
 Cases (keys <case>_<array>):
   sat   12 latent rows of N(0, 25^2) latents (the PA saturates, as under the trained encoder), Rayleigh magnitudes H, phase offset 0.3 rad, Eb/No 3 dB
   lin   latents scaled so that |tx| < 0.05 (the limiter's linear region), H = 1, phase 0, 100 dB
   edge  as sat, with one all-zero OFDM symbol and one symbol whose latents are all 1e4
-
-Run:  python3 tools/gen_golden_rate_rs.py
 """
 import os
-import sys
-
-REF = "/root/reference"
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REF)
-sys.path.insert(0, REPO)
 
 import numpy as np
-import torch
 
-torch.set_num_threads(1)
+from . import reference as R
+from .reference import golden
 
-import radae.radae_base as rb
-
-rb.n = lambda x: torch.clamp(x, min=-1.0, max=1.0)        # deterministic eval-mode quantiser (oracle/gen_golden.py)
-os.chdir(REF)
-from radae import RADAE  # noqa: E402
-
-OUT = os.path.join(REPO, "tests", "golden", "rate_rs_bn3.npz")
 ROWS, NC, M = 12, 20, 160
 
 
 def forward_case(z, H, EbNodB, phase_offset, seed):
+    import torch
+    from radae import RADAE
     model = RADAE(21, 80, EbNodB, bottleneck=3, phase_offset=phase_offset)
     assert (model.Nc, model.Ns, model.M, model.Ncp) == (NC, 6, M, 0) and abs(float(model.w[0]) - 2 * np.pi * 20 / 160) < 1e-6
     model.eval()
@@ -65,7 +49,9 @@ def forward_case(z, H, EbNodB, phase_offset, seed):
                 tx_sym=o["tx_sym"].numpy()[0].astype(np.complex64))
 
 
-def main():
+def main(src, dst):
+    R.enter()
+    OUT = golden(dst, "rate_rs_bn3.npz")
     rng = np.random.default_rng(20241017)
     z_sat = (25.0 * rng.standard_normal((ROWS, 80))).astype(np.float32)
     H_ray = np.abs((rng.standard_normal((2 * ROWS, NC)) + 1j * rng.standard_normal((2 * ROWS, NC))) / np.sqrt(2)).astype(np.float32)
@@ -90,7 +76,3 @@ def main():
     out = {f"{k}_{name}": v for k, c in cases.items() for name, v in c.items()}
     np.savez_compressed(OUT, **out)
     print(f"{OUT}: {len(out)} arrays, {os.path.getsize(OUT)} bytes; full scale " + ", ".join(f"{k} {np.abs(c['z_hat']).max():.3g}" for k, c in cases.items()))
-
-
-if __name__ == "__main__":
-    main()

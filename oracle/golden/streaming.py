@@ -1,7 +1,5 @@
-#!/usr/bin/env python3
-"""Round-6 additions to the golden fixtures: the reference's remaining streaming edge cases, generated by IMPORTING the reference in this container
-(through oracle/gen_golden.py's drivers: `channel_case` = RADAE.forward + inference.py's write_rx tail, `run_rx` = radae_rxe.py:349-356 with a per-call trace).
-TEST INFRASTRUCTURE -- never imported by the product; /root/reference does not exist on the GPU box.
+"""The reference's remaining streaming edge cases, made by IMPORTING the reference through the drivers of oracle/golden/reference.py
+(`channel_case` = RADAE.forward + inference.py's write_rx tail, `run_rx` = radae_rxe.py:349-356 with a per-call trace).
 
   rxtrace_slipdrops.npz  ctest radae_rx_slip_plus_drops (CMakeLists.txt:397-407; the reference's regression for "timing slips + dropped frames over a long
                          enough period -> unable to regain sync"): 62 s of a REAL-valued int16 signal (the ctest feeds a mono wav through
@@ -15,39 +13,19 @@ TEST INFRASTRUCTURE -- never imported by the product; /root/reference does not e
   bypass.npz             `radae_rxe.py --bypass_dec` (:300-302, :315: z_hat out, no UW accounting) and `radae_txe.py --bypass_enc` (:124-126: latents in):
                          the receiver trace of the awgn fixture's samples with bypass_dec, and transmit frames from supplied latents.
 Long traces keep every call's discrete outputs, thresholds and fmax, and `features_out` / `z_hat` of every 4th valid call (`rows_kept`).
-
-Run:  python3 oracle/gen_golden_r6.py [slipdrops dfs eoo bypass]      (~4 min)
 """
-import os
-import sys
+import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import gen_golden as G  # noqa: E402  (imports the reference, patches n() and np.random.randint, loads model19 into the reference modules)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-from scipy.signal import resample_poly  # noqa: E402
-
-from radae_amd import wire  # noqa: E402
-from radae_amd.channel_tools import multipath_g, synth_features  # noqa: E402
-
-OUT = G.OUT
-c64 = G.c64
+from . import reference as R
+from .reference import c64, channel_case, golden, new_tx, run_rx, thin
 
 
-def thin(tr, every=4):
-    """keep features_out / z_hat of every `every`-th valid call (the discrete trace stays whole)"""
-    n = len(tr["features_out"])
-    rows = np.arange(0, n, every)
-    tr = dict(tr)
-    tr["rows_kept"] = rows.astype(np.int32); tr["n_valid_total"] = np.int32(n)
-    tr["features_out"] = tr["features_out"][rows]; tr["z_hat"] = tr["z_hat"][rows]
-    return tr
-
-
-def gen_slipdrops():
+def gen_slipdrops(src, dst):
+    R.enter()
+    from scipy.signal import resample_poly
+    from radae_amd import wire
     T = 6000                                                               # 60 s of feature frames
-    d = G.channel_case("slipdrops", T, 10.0, 11.0, "awgn", 1020, prepend_s=1.0, append_s=0.0)
+    d = channel_case("slipdrops", T, 10.0, 11.0, "awgn", 1020, prepend_s=1.0, append_s=0.0)
     n_pre = 8000
     x = np.concatenate([d["sigma"] * d["noise_pre"].astype(np.complex64), d["rx"]])            # no EOO: the over is still running when the file ends
     rng = np.random.default_rng(1021)
@@ -59,32 +37,37 @@ def gen_slipdrops():
     i16 = np.clip(np.round(y), -32768, 32767).astype(np.int16)
     i16 = i16[:(len(i16) // 2) * 2]
     rx_in = np.frombuffer(wire.int16_to_f32(i16.tobytes(), zeropad=True), np.complex64)        # int16tof32.py --zeropad
-    tr = G.run_rx(rx_in)
+    tr = run_rx(rx_in)
     st = tr["state_after"]
     resyncs = int(np.sum((st[1:] == 2) & (st[:-1] != 2)))
     print(f"slipdrops: {len(rx_in)} samples, calls {len(tr['ret'])} valid {int((tr['ret'] & 1).sum())} nin set {sorted(set(tr['nin_after'].tolist()))} "
           f"entries into sync {resyncs} final state {st[-1]} uw max {tr['uw_errors'].max()}")
     assert st[-1] == 2 and resyncs >= 2 and 1120 in tr["nin_after"]
-    np.savez_compressed(os.path.join(OUT, "rxtrace_slipdrops.npz"), rx_i16=i16, features_in=d["features"][:, :20].astype(np.float16), **thin(tr))
+    np.savez_compressed(golden(dst, "rxtrace_slipdrops.npz"), rx_i16=i16, features_in=d["features"][:, :20].astype(np.float16), **thin(tr))
 
 
-def gen_dfs():
+def gen_dfs(src, dst):
+    R.enter()
+    from scipy.signal import resample_poly
+    from radae_amd import wire
     for pre in (0.064,):
-        d = G.channel_case("dfs", 1440, 10.0, 11.0, "awgn", 1022, prepend_s=pre, append_s=0.3)
+        d = channel_case("dfs", 1440, 10.0, 11.0, "awgn", 1022, prepend_s=pre, append_s=0.3)
         raw = np.frombuffer(wire.f32_to_int16(c64(d["rx_full"]).tobytes(), scale=8192.0), np.int16).reshape(-1, 2)      # f32toint16.py --scale 8192
         y = np.stack([resample_poly(raw[:, k].astype(np.float64), 8001, 8000) for k in range(2)], axis=1)              # sox -r 8000 -> -r 8001, two channels
         i16 = np.clip(np.round(y), -32768, 32767).astype(np.int16)
         rx_in = np.frombuffer(wire.int16_to_f32(np.ascontiguousarray(i16).tobytes()), np.complex64)                    # int16tof32.py
-        tr = G.run_rx(rx_in)
+        tr = run_rx(rx_in)
         print(f"dfs8001 prepend {pre}: calls {len(tr['ret'])} valid {int((tr['ret'] & 1).sum())} nin set {sorted(set(tr['nin_after'].tolist()))} "
               f"tmax {tr['tmax'][tr['state_after'] == 2][:3]} .. {tr['tmax'].max()} final state {tr['state_after'][-1]}")
     assert 1120 in tr["nin_after"]
-    np.savez_compressed(os.path.join(OUT, "rxtrace_dfs8001.npz"), rx_i16=i16, features_in=d["features"][:, :20].astype(np.float16), **thin(tr))
+    np.savez_compressed(golden(dst, "rxtrace_dfs8001.npz"), rx_i16=i16, features_in=d["features"][:, :20].astype(np.float16), **thin(tr))
 
 
-def gen_eoo_mpp():
+def gen_eoo_mpp(src, dst):
+    R.enter()
+    from radae_amd.channel_tools import multipath_g, synth_features
     seed = 65647; rng = np.random.default_rng(seed)                        # radae_txe.py:158-160
-    tx = G.new_tx()
+    tx = new_tx()
     bits = np.sign(rng.random(tx.get_Neoo_bits()) - 0.5).astype(np.float32)
     tx.set_eoo_bits(bits)
     feats = synth_features(1030, 96)
@@ -108,20 +91,21 @@ def gen_eoo_mpp():
     y = np.concatenate([np.zeros(npre, np.complex64), sig, np.zeros(npost, np.complex64)])
     y = y * np.exp(2j * np.pi * (-11.0) * np.arange(len(y)) / 8000.0)
     rx_in = c64(y + sigma * noise)
-    tr = G.run_rx(rx_in)
+    tr = run_rx(rx_in)
     bers = [float(np.mean(e * bits < 0)) for e in tr["eoo_out"]]
     print(f"eoo_mpp: calls {len(tr['ret'])} valid {int((tr['ret'] & 1).sum())} EOO frames {len(tr['eoo_out'])} BER {bers}")
     assert len(bers) >= 2 and min(bers) < 0.05
-    np.savez_compressed(os.path.join(OUT, "rxtrace_eoo_mpp.npz"), rx_in=rx_in, tx_bits=bits, eoo_ber=np.array(bers), **tr)
+    np.savez_compressed(golden(dst, "rxtrace_eoo_mpp.npz"), rx_in=rx_in, tx_bits=bits, eoo_ber=np.array(bers), **tr)
 
 
-def gen_bypass():
-    g = np.load(os.path.join(OUT, "rxtrace_awgn.npz"))
+def gen_bypass(src, dst):
+    R.enter()
+    g = np.load(golden(src, "rxtrace_awgn.npz"))
     # --bypass_dec: the constructor path radae_rxe.py:113-123 (no decoder state dict), floats_out = 240 latents per valid call (:315), UW errors never summed
     import radae_rxe
     rx = radae_rxe.radae_rx("unused", bypass_dec=True, v=0)
-    G.load_into(rx.model, G.M19)
-    G._lcg.x = 1
+    R.load_into(rx.model, R.m19())
+    R.lcg.x = 1
     floats_out = np.zeros(rx.get_n_floats_out(), np.float32)
     assert rx.get_n_floats_out() == 240
     x = g["rx_in"]; pos = 0
@@ -144,14 +128,6 @@ def gen_bypass():
     out = np.zeros(tx.Nmf, np.csingle); txo = []
     for k in range(6):
         tx.do_radae_tx(zin[k], out); txo.append(out.copy())
-    np.savez_compressed(os.path.join(OUT, "bypass.npz"), rx_in=x, ret=np.array(ret_l, np.int32), state_after=np.array(st_l, np.int32), uw_errors=np.array(uw_l, np.int32),
+    np.savez_compressed(golden(dst, "bypass.npz"), rx_in=x, ret=np.array(ret_l, np.int32), state_after=np.array(st_l, np.int32), uw_errors=np.array(uw_l, np.int32),
                         z_hat_out=np.array(z_l, np.float32), eoo_out=np.array(eoo_l, np.float32).reshape(-1, 180), z_in=zin, tx=c64(np.array(txo)))
     print(f"bypass: rx calls {len(ret_l)} valid {len(z_l)} eoo {len(eoo_l)}; tx frames {len(txo)} peak {np.abs(np.array(txo)).max():.3f}")
-
-
-if __name__ == "__main__":
-    which = sys.argv[1:] or ["slipdrops", "dfs", "eoo", "bypass"]
-    if "slipdrops" in which: gen_slipdrops()
-    if "dfs" in which: gen_dfs()
-    if "eoo" in which: gen_eoo_mpp()
-    if "bypass" in which: gen_bypass()

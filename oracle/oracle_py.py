@@ -220,7 +220,7 @@ class Rx:
 
 def run_rx_stream(model, stream, lcg_seed=1, foff_err=0.0, disable_unsync=0.0):
     """Drive the oracle receiver like radae_rxe.py:349-356; returns the same trace dict layout as
-    oracle/gen_golden.py:run_rx."""
+    oracle/golden/reference.py:run_rx."""
     rx = Rx(model, lcg_seed, foff_err, disable_unsync)
     keys_i = ["state_before", "state_after", "nin_before", "nin_after", "ret", "tmax", "f_ind_max", "valid_count", "uw_errors", "synced_count", "snr_int"]
     keys_f = ["fmax", "Dthresh", "Dtmax12", "Dtmax12_eoo", "snrdB_3k_est"]

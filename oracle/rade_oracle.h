@@ -4,7 +4,7 @@
  * This is the parity oracle: a plain-C, single-stream, deterministic restatement of the reference's
  * algorithm.  It is used by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg and by
  * nothing else; the product (radae_amd/csrc) never links it.  Pinned against golden vectors captured
- * from the imported reference (tests/golden/, generator oracle/gen_golden.py) -- see
+ * from the imported reference (tests/golden/, generators oracle/golden/) -- see
  * tests/test_oracle_golden.py.
  *
  * Every function cites the reference lines it follows (paths relative to /root/reference).
@@ -81,7 +81,7 @@ void orc_channel_eoo(orc_c32 *rx, const orc_c32 *eoo, int n, const orc_c32 *nois
 typedef struct orc_rx orc_rx;
 orc_rx *orc_rx_new(const orc_model *m);
 void orc_rx_free(orc_rx *r);
-void orc_rx_set_lcg(orc_rx *r, unsigned seed);      /* row-refresh generator, see gen_golden.py */
+void orc_rx_set_lcg(orc_rx *r, unsigned seed);      /* row-refresh generator, see oracle/golden/reference.py */
 void orc_rx_set_foff_err(orc_rx *r, double hz);     /* RADE_FOFF_TEST (rade_api.c:263-264) */
 void orc_rx_set_disable_unsync(orc_rx *r, double seconds);   /* radae_rxe.py --disable_unsync (:277-281, :337) */
 int orc_rx_nin(const orc_rx *r);

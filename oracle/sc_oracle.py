@@ -3,7 +3,7 @@
 Follows /root/reference/radae/dsp.py:532-562 (gen_rn_coeffs) and :579-860 (class single_carrier: tx, rx_Fs_to_Rs,
 est_timing_and_decimate, est_phase_and_correct, rx) with the arithmetic types NumPy 2 gives that code (the
 reference mixes complex64 buffers with float64 scalars, so most of the receiver runs in complex128).  Pinned
-against tests/golden/sc_*.npz, which oracle/gen_golden_sc.py produced by importing the reference here.
+against tests/golden/sc_*.npz, which oracle/golden/single_carrier.py produced by importing the reference here.
 Only tests/ may import this module; the product path is radae_amd/csrc/rade_sc.hip.
 """
 import numpy as np

@@ -1,6 +1,6 @@
 """Float64 restatement of the reference's est_CNo.py (:23-73) and chirp.py (:50-65), and of the block identity the device kernel rests on (include/rade_batch.h:
 rade_batch_cno_est, rade_chirp; radae_amd/csrc/rade_cno.hip).  numpy only; the tests hold the library and the kernel to this file, and this file to the recorded
-output of the two scripts (tests/golden/cno.npz, tools/gen_golden_cno.py)."""
+output of the two scripts (tests/golden/cno.npz, oracle/golden/cno.py)."""
 import numpy as np
 
 FS = 8000

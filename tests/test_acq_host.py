@@ -1,5 +1,5 @@
 """The host side of the whole-file acquisition stage, on the CPU: rade_acq_hops, rade_acq_track and rade_acq_stats against tests/golden/acq.npz (what the reference's
-rx.py --acq_test computes frame by frame on eight inputs, tools/gen_golden_acq.py), the float64 restatement tests/acq_ref.py pinned to the same fixture, each comparison
+rx.py --acq_test computes frame by frame on eight inputs, oracle/golden/acquisition.py), the float64 restatement tests/acq_ref.py pinned to the same fixture, each comparison
 shown to reject the mistake it is there for, and the torch band-pass of radae_amd/acq.py against a float64 FIR."""
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """CPU tests of the chirp C/No stage's definition (include/rade_batch.h: rade_batch_cno_est, rade_cno_plan, rade_chirp): the float64 restatement of tests/cno_ref.py
-against what the reference's est_CNo.py and chirp.py printed and wrote (tests/golden/cno.npz, tools/gen_golden_cno.py), the library's host functions against the
+against what the reference's est_CNo.py and chirp.py printed and wrote (tests/golden/cno.npz, oracle/golden/cno.py), the library's host functions against the
 restatement, and the block identity the kernel rests on.  The kernel itself is held to the same restatement in tests/test_cno_gpu.py."""
 import ctypes as C
 import os

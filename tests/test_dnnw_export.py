@@ -1,6 +1,6 @@
 """SURVEY.md section 8 row a17 -- the DNNw weight blob, pinned against the reference's OWN exporter.
 
-The fixtures (tests/golden/dnnw_export_A.bin, dnnw_export.npz, weights_check.npz) are written by oracle/gen_golden_dnnw.py, which runs
+The fixtures (tests/golden/dnnw_export_A.bin, dnnw_export.npz, weights_check.npz) are written by oracle/golden/dnnw_export.py, which runs
 `/root/reference/export_rade_weights.py: c_export` (:54-172 -> wexchange/c_export/common.py) on two seeded synthetic checkpoints and packs the emitted C
 arrays as `/root/reference/src/write_rade_weights.c:51-74` does.  Checkpoint A is "lossless" (oracle/dnnw_synth.py): the exporter's quantisation returns its
 weights exactly, so the ground truth every reader must reproduce BIT FOR BIT is the checkpoint itself -- regenerated here from its seed, no reader of this
@@ -82,7 +82,7 @@ def test_reader_agrees_with_the_exporters_own_q_scale_subias(fx, ckpt_a):
 
 
 def test_oracle_reader_returns_the_checkpoint_bit_for_bit(oracle, golden, ckpt_a):
-    """orc_model_load on the exported blob == the checkpoint; weights_check.npz (statistics of the CHECKPOINT's tensors, written by gen_golden_dnnw.py, not by
+    """orc_model_load on the exported blob == the checkpoint; weights_check.npz (statistics of the CHECKPOINT's tensors, written by oracle/golden/dnnw_export.py, not by
     any reader) is the travelling form of the same statement."""
     om = oracle.Model(BLOB_A)
     want = dnnw_synth.tensors(ckpt_a)
@@ -174,7 +174,7 @@ def test_oracle_core_on_the_exported_blob_vs_reference_modules(oracle, fx):
 def test_core_encoder_decoder_on_the_exported_blob_vs_reference_modules(fx):
     """rade_core_encoder / rade_core_decoder (include/rade_core.h) and the batched rade_batch_encode / rade_batch_decode, loaded from the blob the REFERENCE's
     exporter wrote, against the reference's float modules holding the same (lossless) checkpoint, one 40 ms step per call (fixture from
-    oracle/gen_golden_dnnw.py step 5).  Tolerance: north_star's 1e-4 RMS; measured ~1e-6."""
+    oracle/golden/dnnw_export.py step 5).  Tolerance: north_star's 1e-4 RMS; measured ~1e-6."""
     import torch
     from radae_amd.core import CoreDecoder, CoreEncoder
     from radae_amd.engine import BatchEngine

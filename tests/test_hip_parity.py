@@ -216,7 +216,7 @@ def test_rx_trace_golden(engine, torch_dev, golden, name, monkeypatch):
 
 @pytest.mark.parametrize("name", ["slipdrops", "dfs8001", "eoo_mpp"])
 def test_rx_trace_edge_cases(engine, torch_dev, golden, name):
-    """The reference's remaining streaming ctests as golden traces (oracle/gen_golden_r6.py), whole trace bit-exact in one receiver launch:
+    """The reference's remaining streaming ctests as golden traces (oracle/golden/streaming.py), whole trace bit-exact in one receiver launch:
     slipdrops = radae_rx_slip_plus_drops (CMakeLists.txt:397-407): 61 s of a real-valued int16 signal at 8020 Hz with three drop-outs; sync is lost and regained, 1120-sample
     calls all along, the last state is sync.  dfs8001 = radae_rx_dfs (:374-382).  eoo_mpp = radae_eoo_data_mpp (:595-607): the data bits of five end-of-over
     frames through MPP at the ctest's SNR, decisions equal to the reference's, one over below 5 % BER."""
@@ -241,7 +241,7 @@ def test_rx_trace_edge_cases(engine, torch_dev, golden, name):
 
 def test_bypass_dec_and_bypass_enc(Engine, torch_dev, golden):
     """`radae_rxe.py --bypass_dec` (radae_rxe.py:300-302, :315) = an engine opened with RADE_BATCH_BYPASS_DEC: 240 latents per valid modem frame out, no decoder, no UW
-    accounting; `radae_txe.py --bypass_enc` (radae_txe.py:124-126) = rade_batch_tx_latents.  Fixture: oracle/gen_golden_r6.py (the awgn trace's samples)."""
+    accounting; `radae_txe.py --bypass_enc` (radae_txe.py:124-126) = rade_batch_tx_latents.  Fixture: oracle/golden/streaming.py (the awgn trace's samples)."""
     import torch
     from radae_amd.engine import BYPASS_DEC
     g = golden("bypass")

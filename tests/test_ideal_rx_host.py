@@ -1,7 +1,7 @@
 """CPU tests of the ideal-timing ("genie") receiver (RADAE.forward / RADAE.receiver, radae.py:312-420, :590-657): the C ABI exports it and the
 bottleneck-1 noise scale, and a NumPy restatement of the receiver -- cyclic prefix removal, DFT, do_pilot_eq in all four EQ modes, the last-frame
 slope of the reference, coarse_mag at both bottleneck scalings, the demapper -- reproduces what the reference recorded in tests/golden/ideal_rx.npz
-(tools/gen_golden_ideal_rx.py).  The GPU kernels are checked against the same recordings in tests/test_ideal_rx_gpu.py."""
+(oracle/golden/ideal_rx.py).  The GPU kernels are checked against the same recordings in tests/test_ideal_rx_gpu.py."""
 import os
 
 import numpy as np

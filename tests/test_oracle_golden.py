@@ -1,5 +1,5 @@
 """Pin the CPU oracle (oracle/rade_oracle.c) against golden vectors captured from the imported
-reference (oracle/gen_golden.py).  Tolerances: discrete sync outputs bit-exact; float32 stages
+reference (oracle/golden/).  Tolerances: discrete sync outputs bit-exact; float32 stages
 within a few ulp-scaled units; NN outputs within the rounding-noise amplification the reference
 itself shows between its stateful and stateless paths (stateful_encoder.py:102 uses 0.01 on loss)."""
 import numpy as np
@@ -28,7 +28,7 @@ def test_constants(oracle, golden):
 
 
 def test_bpf_golden(oracle, golden):
-    """orc_bpf_run against complex_bpf.bpf (dsp.py:63-102) driven call by call with 960 / 800 / 1120-sample calls (oracle/gen_golden_r4.py):
+    """orc_bpf_run against complex_bpf.bpf (dsp.py:63-102) driven call by call with 960 / 800 / 1120-sample calls (oracle/golden/bandpass.py):
     float32 sums of 101 terms in another order than NumPy's dot."""
     g = golden("bpf")
     bp = oracle.Bpf()
@@ -42,7 +42,7 @@ def test_bpf_golden(oracle, golden):
 
 def test_txbpf_golden(oracle, oracle_model, golden):
     """radae_tx(..., txbpf_en=True) (radae_txe.py:74-83, :130-132, :141-143; ctest radae_tx_basic): six frames and the end-of-over frame through the Tx
-    band-pass filter and the magnitude clip (oracle/gen_golden_r4.py)."""
+    band-pass filter and the magnitude clip (oracle/golden/bandpass.py)."""
     g = golden("txbpf")
     tx = oracle.Tx(oracle_model); tx.set_txbpf(True)
     out = np.concatenate([tx.frame(g["features"][12 * k:12 * k + 12].ravel())[0] for k in range(6)])
@@ -128,7 +128,7 @@ def test_rx_trace(oracle, oracle_model, golden, name):
 
 @pytest.mark.parametrize("name", ["slipdrops", "dfs8001", "eoo_mpp"])
 def test_rx_trace_edge_cases(oracle, oracle_model, golden, name):
-    """The reference's remaining streaming ctests as traces (oracle/gen_golden_r6.py): radae_rx_slip_plus_drops (CMakeLists.txt:397-407; 61 s at 8020 Hz, three
+    """The reference's remaining streaming ctests as traces (oracle/golden/streaming.py): radae_rx_slip_plus_drops (CMakeLists.txt:397-407; 61 s at 8020 Hz, three
     drop-outs, re-sync after each loss, final state sync), radae_rx_dfs (:374-382; 8001 Hz), radae_eoo_data_mpp (:595-607; EOO data bits through MPP)."""
     g = golden("rxtrace_" + name)
     d = oracle.run_rx_stream(oracle_model, edge_case_input(g))

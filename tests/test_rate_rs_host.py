@@ -1,5 +1,5 @@
 """CPU tests of the rate-Rs channel of the bottleneck-3 model (RADAE.forward without rate_Fs, radae.py:603-634; rade_batch_channel_rs_pa): the float64
-restatement of tests/rate_rs_ref.py reproduces what the reference recorded in tests/golden/rate_rs_bn3.npz (tools/gen_golden_rate_rs.py), the C ABI exports
+restatement of tests/rate_rs_ref.py reproduces what the reference recorded in tests/golden/rate_rs_bn3.npz (oracle/golden/rate_rs.py), the C ABI exports
 the call and its noise scale, and the command line refuses the combination the reference cannot run.  The kernel itself is checked against the same
 recordings and the same restatement in tests/test_rate_rs_gpu.py."""
 import os

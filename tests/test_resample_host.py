@@ -1,6 +1,6 @@
 """CPU tests of the fractional resampler's definition (include/rade_batch.h: rade_batch_resample): the library's table and output count against the restatement
 of tests/resample_ref.py, the design condition of the 32-tap / 256-phase / beta = 10 choice on a float64 model, and the restatement's linear mode against what the
-reference's dsp.py:sample_clock_offset recorded in tests/golden/clock_offset.npz (tools/gen_golden_clock_offset.py).  The kernel itself is checked against the
+reference's dsp.py:sample_clock_offset recorded in tests/golden/clock_offset.npz (oracle/golden/clock_offset.py).  The kernel itself is checked against the
 same restatement and the same recording in tests/test_resample_gpu.py."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """Single-carrier modem row: the CPU restatement (oracle/sc_oracle.py) against vectors produced by the
-reference's own `single_carrier` class (oracle/gen_golden_sc.py)."""
+reference's own `single_carrier` class (oracle/golden/single_carrier.py)."""
 import os
 import numpy as np
 import pytest

@@ -2,7 +2,7 @@
 """Time of the whole-file pilot search on the device (rade_batch_acq_detect: k_acq_detect, k_acq_combine, the read-back of the hop records) in alternating rounds in one
 process, at 256 streams x 80,000 and 256 x 806,400 noise-only samples, next to
     (a) the device's own complex64 copy of the same input bytes (HIP events),
-    (b) float32 detect_pilots as the reference computes it (a matmul per timing; tools/gen_golden_acq.py's loop) on one host core (--host_hops hops timed, scaled to the
+    (b) float32 detect_pilots as the reference computes it (a matmul per timing; oracle/golden/acquisition.py's loop) on one host core (--host_hops hops timed, scaled to the
         batch) plus the copy of the input across the host link,
     (c) rade_batch_rx over the same noise-only streams: the streaming receiver stays in search and runs the same correlation once per modem frame, serially per stream
         inside its 256-thread workgroup (its input band-pass included: it cannot be switched off).
