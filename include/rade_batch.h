@@ -651,6 +651,67 @@ int rade_batch_acq_refine(rade_batch *h, const void *x_dev, long x_stride, const
 int rade_acq_stats(const rade_acq_event *events, const rade_acq_refined *refined, int n_events, int n_hops, int Ntap, double fmax_target, double acq_time_target,
                    rade_acq_result *out);
 
+/* ---- stored-file receiver: rx.py past the acquisition (rx.py:107-114 the input band-pass, :197-228 the normal run's refine, trim and mix, :253 the receiver, :260-276 the
+ * BER alignment), every stream of a batch in one call each (rade_file.hip).  Geometry: model19_check3's only, as for the acquisition. --------------------------------------
+ * rade_batch_bpf_file: complex_bpf(101, Fs, bandwidth, centre, len(x)).bpf(x) of a whole file (dsp.py:63-102, its first and only call): zero memory of 100 samples;
+ *   y[i] = conj(E[i]) sum_{t < 101} h[t] (x E)[i - 100 + t], E[i] = e^{-j alpha (i + 1)}, h and alpha the engine's own (rd_tables_fill: bpf_h; float32 as NumPy forms them).
+ *   DEVIATION: E[i] is the complex64 nearest to e^{-j alpha (i + 1)} with the argument formed in double (as radae_amd/acq.py: complex_bpf and tests/acq_ref.py: bpf have
+ *   it); the script forms the argument in float32 (np.exp(.., dtype = complex64)), which jitters the phase by up to an ulp of alpha i on long files.  Not reproduced.
+ *   The mixers are complex64 products with every operation rounded on its own.  The FIR is the engine's one FIR arithmetic (rade_bpf_fir.h, shared with the receiver's input
+ *   filter): per chunk of 1024 outputs the baseband window in two binary16 planes per component (hi + lo, 22 bits) under the power of two that puts the chunk's largest
+ *   |component| into [2^7, 2^8), against the two planes of 2^10 h, on v_mfma_f32_16x16x32_f16: hi hi + hi lo + lo hi, each chain of four instructions (K = 32) in its own
+ *   float32 accumulator, joined by two float32 additions.  Ahead of that a chunk is multiplied by the power of two that puts the larger of its own and the previous
+ *   chunk's largest |component| into [1, 2), and its outputs by the inverse: both exact, so that 2^k x gives 2^k y bit for bit (barring overflow and underflow of
+ *   binary32 itself) whatever the file's level.  A workgroup takes 8 chunks of one stream; the phases are a table made once per call for all streams.
+ *   Error bound, counted from these roundings, per output against the exact value, relative to S[i] = sum_t |h[t]| |x[i - 100 + t]|.  ASSUMED, as for the acquisition: a
+ *   matrix instruction returns its 33-term sum within 2^-23 of the sum of the terms' moduli.  The down mixer: E[i] within sqrt 2 x 2^-25, the product's six roundings 2 sqrt
+ *   2 x 2^-24: 3.54 x 2^-24 = 0.22 x 2^-20.  The samples' two planes 2^-22, the taps' two planes 2^-22, the dropped lo lo product 2^-22: 0.75 x 2^-20 (component errors
+ *   eps sum |h| |re|, eps sum |h| |im| give eps S in modulus).  The hi hi chain 4 x 2^-23 = 0.5 x 2^-20, the cross chains 8 x 2^-23 x 2^-10 = 0.001, the joining additions
+ *   2 x 2^-24 = 0.125.  The up mixer, on |y| <= S: 0.22 again.  Sum 1.82, with 1.01 for the terms of second order and rounded up:
+ *       |y^[i] - y[i]| <= RADE_FILE_BPF_EPS S[i] + RADE_FILE_BPF_TINY X,   RADE_FILE_BPF_EPS = 2 x 2^-20 = 1.9e-6,   X = the stream's largest |component|
+ *   The second term is what binary16 underflow leaves: a plane entry below 2^-14 is rounded to a multiple of 2^-24, at most 2^-25 x 2^-7 = 2^-32 of the window's largest
+ *   component per sample (sqrt 2 sum |h| = 2.9 of them) and 2^-25 x 2^-10 per tap (101 of them): under 2^-28 X; RADE_FILE_BPF_TINY = 2^-27.  tests/test_rx_file_gpu.py
+ *   records how far below the bound the device stays.
+ *   Contract: no device state (the phase table and the counts are scratch of the call, the engine's memory, sized on first use and when a call needs more); no atomics
+ *   on outputs (identical calls give identical bits, and a stream's bits do not depend on the batch); y of stream b is written for exactly n_host[b] samples; x is read
+ *   inside [0, n_host[b]) of the stream's row only and not written; both bases 8-byte aligned; any strides >= the counts.  The call SYNCHRONISES `stream` before it
+ *   returns.  Refused with -1 before any launch and with nothing written: NULL h, x_dev, y_dev or n_host; a base not 8-byte aligned; a count negative or above either
+ *   stride; y overlapping x (the extents first non-empty stream's first sample .. last non-empty stream's last sample of the two buffers intersect).
+ * rade_file_plan: host only; where the script's normal run starts to demodulate.  The script advances one more frame after the acquiring hop k (rx = rx[Nmf:-1]; mf += 1,
+ *   rx.py:186-187) BEFORE acquisition.refine: refine is called with t_abs = 960 (k + 1) + tmax and the stream length n - (k + 1) (every hop drops one tail sample).  [This
+ *   is not radae_amd/acq.py: acquire(acq_test = False), which refines at 960 k + tmax, the --acq_test placement.]  With refine's absolute t and f: start = t - Ncp,
+ *   n_left = n - (k + 1) - start, n_mf = (n_left // 192) // 5 (RADAE.receiver), freq = f or *freq_override (--freq_offset, rx.py:224-226).  Status: RADE_FILE_OK;
+ *   RADE_FILE_NOT_ACQUIRED (hop < 0); RADE_FILE_REFINE_OUTSIDE (t < 0 or t + 960 + 160 > n - (k + 1): refine had no window inside the stream); RADE_FILE_EARLY
+ *   (t - 960 (k + 1) < 32; DEVIATION: the script's negative slice start would wrap to the file's tail; not decoded); RADE_FILE_SHORT (n_mf < 2; DEVIATION: the
+ *   demodulator needs two pilots; not decoded).  Every status but OK gives start 0, n_mf 0.  Returns -1 for NULL out, n < 0 or a value that is not finite.
+ * rade_batch_rx_file: rx.py:223-253 with one fixed estimate per stream.  Stream b: samples from in_host[b].start; multiplied by e^{-j w m}, w = 2 pi freq / 8000 in double,
+ *   m counted from start, phase and product formed in double and rounded once to complex64 (the script multiplies complex64 by complex128 and converts afterwards); a
+ *   stream with freq == 0 is not touched.  Then exactly the arithmetic of rade_batch_rx_ideal (below) over the stream's own n_mf frames: the DFT window
+ *   [Ncp + time_offset, + M), the same float32 DFT, do_pilot_eq, the last frame's slope, coarse_mag over the stream's own frames; with start 0, freq 0 and equal n_mf the
+ *   two calls give the same bits.  z_hat_dev [B][3 max_mf][80]: rows past a stream's 3 n_mf are written as zeros, a stream with n_mf 0 gets all zeros.  features_out_dev
+ *   (optional) [B][3 max_mf][feat]: rade_batch_decode over 3 max_mf steps after a reset; the decoder is causal, so a stream's rows below 3 n_mf do not depend on its zero
+ *   tail (the rows behind are the decoder's answer to zeros).  Synchronises `stream`.  Returns max_mf.  Refused with -1, nothing written: NULLs; x_dev not 8-byte, z_hat_dev
+ *   not 4-byte (with features_out_dev: 16-byte) aligned; max_mf < 1; with features_out_dev, 3 max_mf above the engine's decoder rows; time_offset outside [-Ncp, 0]; eq
+ *   outside RADE_EQ_*; a stream with n_mf < 0, == 1 or > max_mf, start < 0, start + 960 n_mf > x_stride, or a freq that is not finite.
+ * rade_batch_ber_align: rx.py:260-276.  Per stream and shift f = 0..19: z_f = z_ref[240 f:], n_syms = min(len(z_f), len(z_hat)), n_errors = #(-z_f z_hat > 0) over
+ *   n_syms; one launch, grid (shift, stream), integer counts added in a fixed order.  n_errors_host [B][20]; -1 for a shift that leaves no reference symbol (DEVIATION:
+ *   the script divides by zero there).  Lengths in floats.  Synchronises `stream`.  Refused: NULLs, a base not 4-byte aligned, a length negative or above its stride.
+ * rade_ber_best: host only; BER_f = n_errors[f] / n_bits, n_bits = len(z_f) = n_ref - 240 f (the script's own denominator: what is left of the reference, NOT n_syms);
+ *   the best is the first strict minimum below 1.  Returns its shift (-1: none) and its BER in *ber_out (1 when none). */
+#define RADE_FILE_BPF_EPS (2.0 / 1048576.0)
+#define RADE_FILE_BPF_TINY (1.0 / 134217728.0)
+#define RADE_FILE_BPF_SPAN 8192                                   /* outputs per workgroup of the filter kernel: where its tests put their edge cases */
+enum { RADE_FILE_OK = 0, RADE_FILE_NOT_ACQUIRED = 1, RADE_FILE_REFINE_OUTSIDE = 2, RADE_FILE_EARLY = 3, RADE_FILE_SHORT = 4 };
+typedef struct { long long start; int n_mf; double freq; } rade_file_rx_in;
+typedef struct { long long start; int n_mf; double freq; int status; } rade_file_plan_out;
+int rade_batch_bpf_file(rade_batch *h, const void *x_dev, long x_stride, const int *n_host /* [B] */, void *y_dev, long y_stride, void *stream);
+int rade_file_plan(long long n, int hop, long long t, double f, const double *freq_override /* or NULL */, rade_file_plan_out *out);      /* host only */
+int rade_batch_rx_file(rade_batch *h, const void *x_dev, long x_stride, const rade_file_rx_in *in_host /* [B] */, int max_mf, int time_offset, int eq, int coarse_mag,
+                       float *z_hat_dev /* [B][3 max_mf][80] */, float *features_out_dev /* [B][3 max_mf][feat] or NULL */, void *stream);
+int rade_batch_ber_align(rade_batch *h, const float *z_ref_dev, long ref_stride, const long *n_ref_host /* [B] */, const float *z_hat_dev, long hat_stride,
+                         const long *n_hat_host /* [B] */, long *n_errors_host /* [B][20] */, void *stream);
+int rade_ber_best(const long *n_errors /* [20] */, long n_ref, double *ber_out /* or NULL */);      /* host only */
+
 /* ---- Watterson / Doppler-spread sample generator on the device (doppler_spread.m:7-50, multipath_samples.m:10-31):
  * per stream two independent paths G1, G2 = complex Gaussian noise at the low rate Fs/low_ratio through the
  * n_taps Gaussian-PSD FIR (taps designed by the caller, e.g. radae_amd/channel_tools.py), linearly interpolated to

@@ -61,6 +61,8 @@ AcqLog = _struct("AcqLog", "rade_acq_log", [("state", ci), ("tmax_candidate", ci
 AcqRefineIn = _struct("AcqRefineIn", "rade_acq_refine_in", [("stream", ci), ("t_abs", cll), ("fmax", cd)])
 AcqRefined = _struct("AcqRefined", "rade_acq_refined", [("t", cll), ("f", cd), ("Dmax", cd)])
 AcqResult = _struct("AcqResult", "rade_acq_result", [("passes", ci), ("fails", ci), ("passed", ci), ("pfail", cd), ("mean_acq_time", cd)])
+FileRxIn = _struct("FileRxIn", "rade_file_rx_in", [("start", cll), ("n_mf", ci), ("freq", cd)])
+FilePlan = _struct("FilePlan", "rade_file_plan_out", [("start", cll), ("n_mf", ci), ("freq", cd), ("status", ci)])
 RxStatus = _struct("RxStatus", "rade_rx_status", [(n, ci) for n in ("consumed", "n_calls", "n_valid", "has_eoo", "nin", "sync", "snr_dB", "state")])
 IdealRxParams = _struct("IdealRxParams", "rade_ideal_rx_params", [("time_offset", ci), ("eq", ci), ("coarse_mag", ci), ("freq_offset_host", vp), ("df_dt_host", vp),
                                                                   ("z_ref_dev", vp), ("n_errors_host", vp)])
@@ -151,6 +153,11 @@ PROTOTYPES = {
         "rade_acq_track": (ci, [vp, ci, ci, vp, ci, vp]),
         "rade_batch_acq_refine": (ci, [vp, vp, cl, vp, vp, ci, vp, vp, vp]),
         "rade_acq_stats": (ci, [vp, vp, ci, ci, ci, cd, cd, P(AcqResult)]),
+        "rade_batch_bpf_file": (ci, [vp, vp, cl, vp, vp, cl, vp]),
+        "rade_file_plan": (ci, [cll, ci, cll, cd, P(cd), P(FilePlan)]),
+        "rade_batch_rx_file": (ci, [vp, vp, cl, vp, ci, ci, ci, ci, vp, vp, vp]),
+        "rade_batch_ber_align": (ci, [vp, vp, cl, vp, vp, cl, vp, vp, vp]),
+        "rade_ber_best": (ci, [vp, cl, P(cd)]),
         "rade_batch_multipath_gen": (ci, [vp, P(cf), ci, ci, ci, vp, cull, vp, vp]),
         "rade_batch_multipath_h": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, ci, vp, vp]),
         "rade_sigma_from_EbNodB": (cf, [cf]),
@@ -197,8 +204,12 @@ CORE_SYMBOLS = list(PROTOTYPES["rade_core.h"])
 # The whole-file acquisition stage (radae_amd/acq.py).  Its symbols are kept in a list of their own, as the single-carrier ones are, and NOT in EXPORTED_SYMBOLS, although
 # every earlier front-end stage is listed there: tests/test_abi_host.py pins EXPORTED_SYMBOLS member for member, and a change that adds a stage does not edit existing
 # tests.  build() checks this list with the others; fold it into EXPORTED_SYMBOLS when that pinned list is next updated.
+FILE_STATUS = ("ok", "not acquired", "refine window outside the stream", "timing inside the first cyclic prefix: not decoded", "fewer than two modem frames left: not decoded")   # RADE_FILE_*
 ACQ_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_acq_", "rade_batch_acq_"))]
-EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in ACQ_SYMBOLS]
+# The stored-file receiver behind the acquisition (radae_amd/acq.py: receive): a list of its own for the same reason, checked by build() with the others.
+FILE_SYMBOLS = ["rade_batch_bpf_file", "rade_file_plan", "rade_batch_rx_file", "rade_batch_ber_align", "rade_ber_best"]
+assert all(n in PROTOTYPES["rade_batch.h"] for n in FILE_SYMBOLS)
+EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in ACQ_SYMBOLS and n not in FILE_SYMBOLS]
 
 _lib = None
 

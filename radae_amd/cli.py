@@ -554,26 +554,36 @@ def _est_cno(argv):
 def _rx(argv):
     ap = argparse.ArgumentParser(prog="radae_amd.cli rx", description="Pilot acquisition of a stored recording (rx.py --pilots): the input band-pass, detect_pilots over every "
                                  "modem frame in one device call (rade_batch_acq_detect), the script's state machine and refine; with --acq_test the pass / fail statistics.  "
-                                 "The acquired file is not decoded (rx.py:223-253), and --rx_one, --ber_test and --plots are not offered")
+                                 "With --decode the script's normal run goes on past the acquisition, on the device: refine one frame later, trim, mix down, the "
+                                 "fixed-timing demodulator, the decoder, and --ber_test's alignment (rx.py:197-276).  --rx_one, --stateful and --plots are not offered")
     ap.add_argument("rx", type=str, help="path to input file of rate Fs rx samples in ..IQIQ...f32 format")
     ap.add_argument("model_name", nargs="?", default=None, help="accepted and ignored (the script's first argument): the geometry is model19_check3's")
-    ap.add_argument("features_hat", nargs="?", default=None, help="accepted and ignored: nothing is decoded")
+    ap.add_argument("features_hat", nargs="?", default=None, help="with --decode: path to the output feature file (float32, 36 per frame); ignored otherwise")
     ap.add_argument("--no_bpf", dest="bpf", action="store_false", help="disable the input band-pass filter")
     ap.add_argument("--acq_test", action="store_true", help="search again after every acquisition and report passes, fails, P(fail) and the mean acquisition time")
     ap.add_argument("--fmax_target", type=float, default=0.0, help="acquisition test mode freq offset target (default 0.0)")
     ap.add_argument("--acq_time_target", type=float, default=1.0, help="acquisition test mode mean acquisition time target (default 1.0)")
     ap.add_argument("--write_Dt", type=str, default="", help="write Dt1 of every frame, complex64 [frames][960][40]")
+    ap.add_argument("--decode", action="store_true", help="go on past the acquisition as the script's normal run does and write features_hat (not with --acq_test / --write_Dt)")
+    ap.add_argument("--write_latent", type=str, default="", help="with --decode: path to output file of latent vectors z[latent_dim] in .f32 format")
+    ap.add_argument("--ber_test", type=str, default="", help="with --decode: symbols are PSK bits, compare to z.f32 file to calculate BER")
+    ap.add_argument("--freq_offset", type=float, default=None, help="with --decode: manually specify frequency offset")
     # the script's waveform flags, accepted where they describe model19_check3
     ap.add_argument("--pilots", action="store_true"); ap.add_argument("--pilot_eq", action="store_true"); ap.add_argument("--coarse_mag", action="store_true")
     ap.add_argument("--auxdata", action="store_true"); ap.add_argument("--bottleneck", type=int, default=3); ap.add_argument("--cp", type=float, default=0.004)
     ap.add_argument("--latent-dim", type=int, default=80); ap.add_argument("--time_offset", type=int, default=-16)
+    ap.add_argument("--eq_ls", action="store_true", help="accepted and ignored (an option of inference.py, not of rx.py): with --decode, --pilot_eq alone selects the least-squares equaliser, as in the script")
     args = ap.parse_args(argv)
     if args.bottleneck != 3 or args.cp != 0.004 or args.latent_dim != 80:
         raise SystemExit("radae_amd.cli rx: only model19_check3's waveform (--bottleneck 3 --cp 0.004 --latent-dim 80) is built")
+    if args.decode and (args.acq_test or args.write_Dt or not args.features_hat):
+        raise SystemExit("radae_amd.cli rx --decode: needs FEATURES_HAT and is the script's normal run (no --acq_test, no --write_Dt)")
     import torch
     from . import acq, engine, stages
     rx = np.fromfile(args.rx, dtype=np.csingle)
     print(f"samples: {len(rx):d} Nmf: {acq.NMF:d} modem frames: {len(rx)/acq.NMF}")
+    if args.decode:
+        return _rx_decode(args, rx)
     eng = engine.BatchEngine(1, max_tx_mf=1)
     x = torch.tensor(rx[None], device="cuda")
     n_hops = stages.acq_hops(len(rx))
@@ -603,6 +613,56 @@ def _rx(argv):
         print("Acquisition failed....")
     else:
         print(f"refined fmax: {float(r.refined[0]['f']):f}")
+    return 0
+
+
+def _rx_decode(args, rx):
+    """rx.py's normal run past the acquisition (radae_amd.acq.receive): what the script prints, the feature file as `inference` writes its own, --write_latent, --ber_test"""
+    import torch
+    from . import acq, engine
+    from .abi import FILE_STATUS
+    eng = engine.BatchEngine(1, max_tx_mf=max(len(rx) // acq.NMF, 2))
+    z_ref = None
+    if args.ber_test:
+        z = np.fromfile(args.ber_test, dtype=np.float32)
+        z_ref = torch.tensor(z[None] if len(z) else np.zeros((1, 1), np.float32), device="cuda"), len(z)
+    eq = "ls" if args.pilot_eq else "none"                            # the script builds its model with eq_mean6 = False (rx.py:81-84): --pilot_eq IS the least-squares equaliser
+    (r,) = acq.receive(eng, torch.tensor(rx[None], device="cuda"), bpf=args.bpf, freq_offset=args.freq_offset, time_offset=args.time_offset, eq=eq,
+                       coarse_mag=args.coarse_mag, z_ref=z_ref)
+    a = r.acq
+    for k, (h, fm, lg) in enumerate(zip(a.hops, a.fmax, a.log)):
+        if len(a.events) and k > int(a.events[0]["hop"]):
+            break                                                      # the script's loop ends with the frame that acquires
+        state = ("search", "candidate")[lg["state"]]
+        print(f"{k + 1:2d} state: {state:10s} Dthresh: {h['Dthresh']:8.2f} Dtmax12: {h['Dtmax12']:8.2f} tmax: {h['tmax']:4d} tmax_candidate: {lg['tmax_candidate']:4d} fmax: {fm:6.2f}")
+    if not len(a.events):
+        print("Acquisition failed....")
+        eng.close()
+        return 0
+    print("Acquired!")
+    print(f"refined fmax: {float(a.refined[0]['f']):f}")
+    if args.freq_offset is not None:
+        print(args.freq_offset)
+    if r.plan.status:
+        print(f"not decoded: {FILE_STATUS[r.plan.status]}")
+        eng.close()
+        return 1
+    z_hat = r.z_hat.cpu().numpy().astype(np.float32).ravel()
+    if r.n_errors is not None:
+        best, n_ref = 1.0, z_ref[1]
+        for f in range(20):                                            # the script's lines: a shift is printed when it improves on the best so far
+            n_bits = n_ref - 240 * f
+            if n_bits <= 0 or r.n_errors[f] < 0:
+                break
+            if r.n_errors[f] / n_bits < best:
+                best = r.n_errors[f] / n_bits
+                print(f"f: {f:2d} n_bits: {n_bits:d} n_errors: {int(r.n_errors[f]):d} BER: {best:5.3f}")
+    fh = r.features.cpu().numpy().reshape(-1, 21)
+    out = np.zeros((len(fh), 36), np.float32); out[:, :20] = fh[:, :20]
+    out.tofile(args.features_hat)
+    if args.write_latent:
+        z_hat.tofile(args.write_latent)
+    eng.close()
     return 0
 
 

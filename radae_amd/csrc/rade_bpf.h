@@ -16,77 +16,9 @@
 // Memory quirk kept (dsp.py:55 against :96): the memory holds Ntap - 1 = 100 samples before the first call and Ntap + 1 = 102 after it while the
 // strided window always starts at index 0, so outputs are delayed by two more samples from the second call on.
 
-// ---- the 101-tap FIR on the matrix cores (shared by the pre-pass kernel and the receiver's own off-grid filtering: one arithmetic) -----------
-// y[i] = sum_t h[t] w[i + t] over a window w of baseband samples is the product of the Toeplitz matrix T[r][m] = h[m - r] (16 x 128, taps padded
-// with zeros) with the Hankel matrix U[m][q] = w[16 q + m]: Y[r][q] = y[16 q + r], one 16 x 16 tile = 256 consecutive outputs.  On
-// v_mfma_f32_16x16x32_f16: T is the A operand (two binary16 planes of 2^10 h, a constant table: rd_bpf16_table_fill), U the B operand -- its
-// fragment for (column q, k-group g, k-step ks) is EIGHT CONSECUTIVE window samples starting at 16 q + 32 ks + 8 g, one aligned 16-byte LDS read
-// from a plane -- real and imaginary parts as separate planes, each split hi + lo (22 bits, one power-of-two scale per block from its largest
-// component): hi hi + hi lo + lo hi in f32, 24 matrix instructions per tile against 51,712 vector FMAs.  The vector FIR was bound by LDS reads
-// (every thread re-read its sliding window); this form reads each plane entry 8 times instead of 101.
-#define BPF_NPL 1408                   /* halfs per plane: five tiles of 256 outputs + the 127 samples the last rows reach beyond */
-#define BPF_TILES(n) (((n) + 255) >> 8)
-struct BpfLds {                        // 11,264 B: exactly the receiver's xm work area
-    __attribute__((aligned(16))) _Float16 rh[BPF_NPL], rl[BPF_NPL], ih[BPF_NPL], il[BPF_NPL];
-};
-// The window [memory (102) | block (n)] into the four planes, entry i of it at plane index i - o (o = 2 before a stream's first call, whose memory is two
-// samples shorter: dsp.py:55; entries below o are dropped): thread tid brings head = entry tid (tid < 102) and body[q] = entry 102 + tid + 256 q, ZERO
-// beyond the block -- all loaded by the caller in one batch, so that a workgroup pays one memory round trip for its window and not one per entry.
-// Returns the factor that undoes the operand scales.  Every thread of the 256-thread workgroup calls this (two barriers inside); maxw is an LDS word.
-#define BPF_NQ 5                       /* body entries per thread: 5 x 256 >= the longest block (1152, the end-of-over frame on the transmit side) */
-__device__ __forceinline__ float bpf_stage_planes(BpfLds *pl, unsigned *maxw, int tid, float2 head, const float2 (&body)[BPF_NQ], int o)
-{
-    float m = tid < 102 ? fmaxf(fabsf(head.x), fabsf(head.y)) : 0.0f;
-#pragma unroll
-    for (int q = 0; q < BPF_NQ; q++) m = fmaxf(m, fmaxf(fabsf(body[q].x), fabsf(body[q].y)));
-    if (tid == 0) *maxw = 0u;
-    __syncthreads();
-    m = wave_max_f32(m);
-    if ((tid & 63) == 0) atomicMax(maxw, __float_as_uint(m));
-    __syncthreads();
-    const int eb = min(max((int)((*maxw >> 23) & 0xffu), 32), 222);
-    const float sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);          // the largest component lands in [2^7, 2^8)
-    auto put = [&](int w, float2 v) {
-        const float xr = v.x * sc, xi = v.y * sc;
-        const _Float16 h0 = (_Float16)xr, h1 = (_Float16)xi;
-        pl->rh[w] = h0; pl->rl[w] = (_Float16)(xr - (float)h0); pl->ih[w] = h1; pl->il[w] = (_Float16)(xi - (float)h1);
-    };
-    if (tid < 102 && tid >= o) put(tid - o, head);
-#pragma unroll
-    for (int q = 0; q < BPF_NQ; q++) put(102 - o + tid + 256 * q, body[q]);
-    if (tid < BPF_NPL - (102 + 256 * BPF_NQ)) put(102 + 256 * BPF_NQ + tid, make_float2(0.0f, 0.0f));      // the tail the last tile's rows reach into
-    if (tid < o) put(BPF_NPL - o + tid, make_float2(0.0f, 0.0f));
-    __syncthreads();
-    return __uint_as_float((unsigned)(eb - 7 - 10) << 23);                            // 2^(E - 7) from the samples, 2^-10 from the taps
-}
-// outputs 256 tile + 16 (lane & 15) + 4 (lane >> 4) + r, r = 0..3, of the staged window: (re[r], im[r]), still in operand scale
-struct BpfTaps { f16x8 h[4], l[4]; };          // the lane's A fragments (rd_bpf16_table_fill): loaded once, ahead of the staging
-__device__ __forceinline__ void bpf_load_taps(BpfTaps &t, const unsigned short *tab16, int lane)
-{
-    typedef const __attribute__((address_space(1))) f16x8 glb_f16x8_t;
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) { t.h[ks] = *(glb_f16x8_t *)(tab16 + (((size_t)ks * 2) * 64 + lane) * 8); t.l[ks] = *(glb_f16x8_t *)(tab16 + (((size_t)ks * 2 + 1) * 64 + lane) * 8); }
-}
-__device__ __forceinline__ void bpf_fir_tile(const BpfLds *pl, const BpfTaps &t, int tile, int lane, f32x4 &re, f32x4 &im)
-{
-    const f16x8 (&Ah)[4] = t.h, (&Al)[4] = t.l;
-    const int w0 = 256 * tile + 16 * (lane & 15) + 8 * (lane >> 4);
-    f32x4 a[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) a[k] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f };
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-        const f16x8 brh = *(const f16x8 *)&pl->rh[w0 + 32 * ks], brl = *(const f16x8 *)&pl->rl[w0 + 32 * ks];
-        const f16x8 bih = *(const f16x8 *)&pl->ih[w0 + 32 * ks], bil = *(const f16x8 *)&pl->il[w0 + 32 * ks];
-        a[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[ks], brh, a[0], 0, 0, 0);
-        a[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], brl, a[1], 0, 0, 0);
-        a[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], brh, a[2], 0, 0, 0);
-        a[3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[ks], bih, a[3], 0, 0, 0);
-        a[4] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], bil, a[4], 0, 0, 0);
-        a[5] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[ks], bih, a[5], 0, 0, 0);
-    }
-    re = (a[0] + a[1]) + a[2]; im = (a[3] + a[4]) + a[5];
-}
+
+// ---- the 101-tap FIR on the matrix cores (shared by the pre-pass kernel, the receiver's own off-grid filtering and the whole-file filter of rade_file.hip: one arithmetic) ----
+#include "rade_bpf_fir.h"
 
 // baseband sample q of the invocation (x[q] times the phase of its block), q >= -102: the filter memory a stream needs when it leaves the grid or
 // the launch ends; negative q reaches into the memory the invocation started with

@@ -381,6 +381,42 @@ typedef struct {
 } rd_acq_refine_args;
 int rd_launch_acq_refine(const rd_acq_refine_args *a, rd_stream_t s);
 
+/* the stored-file receiver past the acquisition, rade_batch_bpf_file / _rx_file / _ber_align (rade_file.hip; include/rade_batch.h states the arithmetic).
+ * k_file_phase + k_file_bpf: complex_bpf.bpf of a whole file; a workgroup of four wavefronts takes RD_FILE_SPAN consecutive outputs of one stream, RD_FILE_CHUNK at a
+ * time (one 256-output tile of rade_bpf_fir.h per wavefront).  k_file_demod + k_file_scale: k_irx_demod / k_irx_scale with each stream's own start, frame count and
+ * frequency.  k_file_ber: one workgroup per (shift, stream). */
+#define RD_FILE_CHUNK 1024
+#define RD_FILE_NCHUNK 8
+#define RD_FILE_SPAN (RD_FILE_CHUNK * RD_FILE_NCHUNK)
+#define RD_FILE_NSHIFT 20                                        /* rx.py:268: the shifts of the BER alignment, in modem frames */
+typedef struct {
+    const unsigned short *bpf16;                                /* rd_bpf16_table_fill(): the taps as matrix-core operands */
+    const void *x; long x_stride; void *y; long y_stride;       /* complex64, stream b at + b * stride samples */
+    const int *n;                                               /* device [B] sample counts */
+    float *phase; long n_phase;                                 /* device [n_phase][2], n_phase = max_n rounded up to RD_FILE_SPAN: made by k_file_phase, read by k_file_bpf */
+    double alpha;                                               /* the mixer's step (rd_tables_fill: the float32 value, as a double) */
+    int B, max_n;
+} rd_file_bpf_args;
+int rd_launch_file_bpf(const rd_file_bpf_args *a, rd_stream_t s);
+typedef struct { long long start; double w; int n_mf, pad; } rd_file_rx_rec;     /* w = 2 pi freq / 8000, 0: the stream is not mixed */
+typedef struct {
+    const rd_tables *tab; const void *x; long x_stride;         /* complex64; stream b reads [start, start + 960 n_mf) of its row */
+    const rd_file_rx_rec *rec;                                  /* device [B] */
+    int max_mf, time_offset, eq, coarse_mag, B;
+    float mag_scale;
+    float *z_hat;                                               /* [B][3 max_mf][80]; rows past 3 n_mf are written as zeros */
+    double *part;                                               /* [B][max_mf] */
+} rd_file_rx_args;
+int rd_launch_file_rx(const rd_file_rx_args *a, rd_stream_t s);
+typedef struct { long long n_ref, n_hat; } rd_file_ber_rec;     /* floats of either side */
+typedef struct {
+    const float *z_ref; long ref_stride; const float *z_hat; long hat_stride;      /* float32, stream b at + b * stride floats */
+    const rd_file_ber_rec *rec;                                 /* device [B] */
+    long long *n_err;                                           /* device [B][RD_FILE_NSHIFT] */
+    int B;
+} rd_file_ber_args;
+int rd_launch_file_ber(const rd_file_ber_args *a, rd_stream_t s);
+
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;
     const void *G; const void *noise; const float *eoo; void *scratch; /* >= B * (1 + max(64, n_sig / 960)) * 2 doubles: [B][4] floats (gain, final phase), then the partial power sums */

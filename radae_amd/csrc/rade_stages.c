@@ -1,6 +1,6 @@
 /*
  * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
- * rate converter, analog FM, the chirp header's C/No, the spectrogram and the whole-file pilot acquisition.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * rate converter, analog FM, the chirp header's C/No, the spectrogram, the whole-file pilot acquisition and the stored-file receiver behind it.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
  * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
  * its device and pinned memory is on the engine's own list (rade_engine.h).
  *
@@ -93,6 +93,11 @@ struct rd_stages {
      * records, grown with the call; a chunk of RD_ACQ_EV_CHUNK events, their results and their fine rows */
     rd_pair acq_n; double *acq_psum; rd_acq_pmax *acq_pmax; rd_acq_rec *acq_rec; long acq_cap, acq_cap1, acq_cap2;
     rd_pair acq_ev; rd_acq_fine *acq_fine; double *acq_dfine;
+    /* rade_batch_bpf_file: the [B] sample counts; the call's mixer phases [file_phase_cap][2], grown with the call (scratch: made again by every call).
+     * rade_batch_rx_file: the [B] stream records; [B][file_part_cap] pilot powers.  rade_batch_ber_align: the [B] lengths; [B][RD_FILE_NSHIFT] counts */
+    rd_pair file_n; float *file_phase; long file_phase_cap;
+    rd_pair file_rx; double *file_part; long file_part_cap;
+    rd_pair file_ber; long long *file_err;
 };
 static struct rd_stages *stages_of(rade_batch *h)
 {
@@ -630,4 +635,144 @@ int rade_batch_acq_refine(rade_batch *h, const void *x_dev, long x_stride, const
         }
     }
     return 0;
+}
+
+/* ---- the stored-file receiver past the acquisition: the whole-file band-pass, the plan, the ragged fixed-timing demodulator and the BER alignment of rx.py (rade_file.hip;
+ * include/rade_batch.h states the arithmetic) --------------------------------------------------------------------------------------------------------------------- */
+_Static_assert(RADE_FILE_BPF_SPAN == RD_FILE_SPAN && RD_FILE_CHUNK == 1024, "the header's span is the kernel's (rade_file.hip: a chunk is four tiles of 256)");
+/* complex_bpf's mixer step as rd_tables_fill forms it (rade_host.c: float32 like NumPy), as a double */
+static double file_bpf_alpha(void)
+{
+    const float two_pi = (float)(2.0 * M_PI), w0 = (two_pi * 15.0f) / 160.0f, w1 = (two_pi * (float)(15 + RD_NC - 1)) / 160.0f;
+    const float centre = (((w1 + w0) * 8000.0f) / two_pi) / 2.0f;
+    return (double)((two_pi * centre) / 8000.0f);
+}
+
+int rade_batch_bpf_file(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, void *y_dev, long y_stride, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !y_dev || !n_host || (((uintptr_t)x_dev | (uintptr_t)y_dev) & 7) || x_stride < 0 || y_stride < 0) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    int maxn = 0;
+    long long lo = -1, hi = 0;             /* the samples any stream touches, relative to either base: [lo, hi) */
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride || n > y_stride) return -1;
+        if (n > maxn) maxn = n;
+        work += 2.0 * 16 * 16 * 32 * 24 * ((n + 255) / 256);
+    }
+    if (!maxn) return 0;
+    for (int b = 0; b < B; b++) if (n_host[b]) { if (lo < 0) lo = b; hi = b; }
+    {   /* y overlapping x: the extents from the first non-empty stream's first sample to the last one's last, held against each other */
+        const uintptr_t x0 = (uintptr_t)x_dev + 8 * (uintptr_t)(lo * x_stride), x1 = (uintptr_t)x_dev + 8 * (uintptr_t)(hi * x_stride + n_host[hi]);
+        const uintptr_t y0 = (uintptr_t)y_dev + 8 * (uintptr_t)(lo * y_stride), y1 = (uintptr_t)y_dev + 8 * (uintptr_t)(hi * y_stride + n_host[hi]);
+        if (x0 < y1 && y0 < x1) return -1;
+    }
+    struct rd_stages *s = stages_of(h);
+    int *n_stage = s ? pair_host(h, &s->file_n, sizeof(int) * B) : NULL;
+    if (!n_stage) return -1;
+    const long n_phase = ((long)maxn + RD_FILE_SPAN - 1) / RD_FILE_SPAN * RD_FILE_SPAN;
+    if (dev_grow(h, &s->file_phase, &s->file_phase_cap, n_phase, 2 * sizeof(float), 0)) return -1;
+    memcpy(n_stage, n_host, sizeof(int) * B);
+    if (pair_push(h, &s->file_n, sizeof(int) * B, 0, st)) return -1;       /* not waited for here: the call waits at its end */
+    rd_file_bpf_args a;
+    memset(&a, 0, sizeof a);
+    a.bpf16 = h->bpf16; a.x = x_dev; a.x_stride = x_stride; a.y = y_dev; a.y_stride = y_stride; a.n = s->file_n.dev; a.phase = s->file_phase; a.n_phase = n_phase;
+    a.alpha = file_bpf_alpha(); a.B = B; a.max_n = maxn;
+    PROF_BEGIN(h, stream);
+    const int e = rd_launch_file_bpf(&a, stream);
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return (settle(st) || e) ? -1 : 0;     /* the staging copy of the counts is free again */
+}
+
+int rade_file_plan(long long n, int hop, long long t, double f, const double *freq_override, rade_file_plan_out *out)
+{
+    if (!out || n < 0 || !isfinite(f) || (freq_override && !isfinite(*freq_override))) return -1;
+    out->start = 0; out->n_mf = 0; out->freq = freq_override ? *freq_override : f;
+    if (hop < 0) { out->status = RADE_FILE_NOT_ACQUIRED; return 0; }
+    const long long base = (long long)RD_NMF * (hop + 1), len = n - (hop + 1);      /* rx = rx[Nmf:-1] once more after the acquiring hop (rx.py:186-187) */
+    if (t < 0 || t + RD_NMF + RD_M > len) { out->status = RADE_FILE_REFINE_OUTSIDE; return 0; }
+    if (t - base < RD_NCP) { out->status = RADE_FILE_EARLY; return 0; }             /* rx[tmax - Ncp:] with a negative index would wrap to the tail */
+    out->start = t - RD_NCP;
+    const long long n_left = len - out->start;
+    out->n_mf = (int)((n_left / (RD_M + RD_NCP)) / (RD_NS + 1));
+    if (out->n_mf < 2) { out->start = 0; out->n_mf = 0; out->status = RADE_FILE_SHORT; return 0; }
+    out->status = RADE_FILE_OK;
+    return 0;
+}
+
+int rade_batch_rx_file(rade_batch *h, const void *x_dev, long x_stride, const rade_file_rx_in *in_host, int max_mf, int time_offset, int eq, int coarse_mag,
+                       float *z_hat_dev, float *features_out_dev, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !in_host || !z_hat_dev || max_mf < 1 || x_stride < 0 || ((uintptr_t)x_dev & 7) || ((uintptr_t)z_hat_dev & 3) || ((uintptr_t)features_out_dev & 3)) return -1;
+    if (time_offset < -RD_NCP || time_offset > 0 || eq < RADE_EQ_LS || eq > RADE_EQ_NONE) return -1;
+    if (features_out_dev && (3 * max_mf > h->Tcap || ((uintptr_t)z_hat_dev & 15))) return -1;       /* the decoder reads z_hat_dev as rade_batch_decode does: f32x4 A rows */
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const rade_file_rx_in *v = &in_host[b];
+        if (v->n_mf < 0 || v->n_mf == 1 || v->n_mf > max_mf || v->start < 0 || !isfinite(v->freq)) return -1;      /* the demodulator needs two pilots; 0 = a stream of zeros */
+        if (v->start > x_stride || v->start + (long long)RD_NMF * v->n_mf > x_stride) return -1;
+    }
+    struct rd_stages *s = stages_of(h);
+    rd_file_rx_rec *rec = s ? pair_host(h, &s->file_rx, sizeof(rd_file_rx_rec) * B) : NULL;
+    if (!rec) return -1;
+    if (dev_grow(h, &s->file_part, &s->file_part_cap, max_mf, sizeof(double) * B, 1)) return -1;
+    for (int b = 0; b < B; b++) {
+        rec[b].start = in_host[b].start; rec[b].n_mf = in_host[b].n_mf; rec[b].pad = 0;
+        rec[b].w = in_host[b].freq == 0.0 ? 0.0 : 2.0 * M_PI * in_host[b].freq / 8000.0;
+    }
+    if (pair_push(h, &s->file_rx, sizeof(rd_file_rx_rec) * B, 0, st)) return -1;
+    rd_file_rx_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.x = x_dev; a.x_stride = x_stride; a.rec = s->file_rx.dev; a.max_mf = max_mf; a.time_offset = time_offset; a.eq = eq; a.coarse_mag = coarse_mag; a.B = B;
+    a.mag_scale = h->tx_linear ? 1.0f : (float)(sqrt(2.0) / ((pow(10.0, -2.0 / 20.0) * RD_M) / sqrt((double)RD_NC)));   /* as rade_batch_rx_ideal: |P[0]| / pilot_gain */
+    a.z_hat = z_hat_dev; a.part = s->file_part;
+    PROF_BEGIN(h, stream);
+    int e = rd_launch_file_rx(&a, stream);
+    PROF_END(h, stream, RADE_PROF_CHAN, 8.0 * RD_M * RD_NC * (RD_NS + 2) * (double)max_mf * B);
+    if (!e && features_out_dev && rade_batch_decode(h, z_hat_dev, 3 * max_mf, features_out_dev, 1, stream) != 3 * max_mf) e = -1;
+    return (settle(st) || e) ? -1 : max_mf;
+}
+
+int rade_batch_ber_align(rade_batch *h, const float *z_ref_dev, long ref_stride, const long *n_ref_host, const float *z_hat_dev, long hat_stride, const long *n_hat_host,
+                         long *n_errors_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !z_ref_dev || !z_hat_dev || !n_ref_host || !n_hat_host || !n_errors_host || (((uintptr_t)z_ref_dev | (uintptr_t)z_hat_dev) & 3)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    for (int b = 0; b < B; b++) if (n_ref_host[b] < 0 || n_ref_host[b] > ref_stride || n_hat_host[b] < 0 || n_hat_host[b] > hat_stride) return -1;
+    struct rd_stages *s = stages_of(h);
+    rd_file_ber_rec *rec = s ? pair_host(h, &s->file_ber, sizeof(rd_file_ber_rec) * B) : NULL;
+    if (!rec) return -1;
+    if (dev_grow(h, &s->file_err, NULL, (long)B * RD_FILE_NSHIFT, sizeof(long long), 1)) return -1;
+    for (int b = 0; b < B; b++) { rec[b].n_ref = n_ref_host[b]; rec[b].n_hat = n_hat_host[b]; }
+    if (pair_push(h, &s->file_ber, sizeof(rd_file_ber_rec) * B, 0, st)) return -1;
+    rd_file_ber_args a;
+    memset(&a, 0, sizeof a);
+    a.z_ref = z_ref_dev; a.ref_stride = ref_stride; a.z_hat = z_hat_dev; a.hat_stride = hat_stride; a.rec = s->file_ber.dev; a.n_err = s->file_err; a.B = B;
+    const int e = rd_launch_file_ber(&a, stream);
+    const long long *res = e ? NULL : read_back(h, s->file_err, sizeof(long long) * B * RD_FILE_NSHIFT, st);
+    if (!res) { settle(st); return -1; }
+    for (int i = 0; i < B * RD_FILE_NSHIFT; i++) n_errors_host[i] = (long)res[i];
+    return 0;
+}
+
+int rade_ber_best(const long *n_errors, long n_ref, double *ber_out)
+{
+    if (!n_errors || n_ref < 0) return -1;
+    double best = 1.0;
+    int at = -1;
+    for (int f = 0; f < RD_FILE_NSHIFT; f++) {
+        const long n_bits = n_ref - (long)RD_ZMF * f;      /* the script's own denominator: what is left of the reference, not the symbols compared */
+        if (n_bits <= 0 || n_errors[f] < 0) break;
+        const double ber = (double)n_errors[f] / (double)n_bits;
+        if (ber < best) { best = ber; at = f; }
+    }
+    if (ber_out) *ber_out = best;
+    return at;
 }

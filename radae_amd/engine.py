@@ -19,7 +19,7 @@ from .abi import (BOTTLENECK1, BYPASS_DEC, DEFAULT_BLOB, EQ_MODES, EXPORTED_SYMB
                   ChannelParams, ChannelStreams, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, IdealRxParams, RateParams, ResampleParams, RxStatus, RxTrace,
                   SpecgramParams, SpecgramPlan, _lib, load_library)
 from .stages import (CNO_FS, CNO_HOP, FM_DE_EMP_TC, RESAMPLE_PPM_MAX, SPEC_HI, SPEC_LO, SPEC_NFFT, SPEC_STEP, SPEC_WIN, BatchStages, ClockOffset, FmDemodulator,  # noqa: F401
-                     FmModulator, RateConverter, WireMeters, _per_stream, _row_stride, _scalar_or_streams, _stream_ptr, chirp, cno_plan, cno_windows, fm_deemph_len,
+                     FmModulator, RateConverter, WireMeters, ber_best, file_plan, _per_stream, _row_stride, _scalar_or_streams, _stream_ptr, chirp, cno_plan, cno_windows, fm_deemph_len,
                      fm_pre_emphasis, fm_sigma, fm_taps, ppm_from_rates, rate_count, rate_taps, resample_count, resample_taps, specgram_levels, specgram_plan,
                      specgram_slices, specgram_window)
 

@@ -13,7 +13,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .abi import (FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, WIRE_IQ, WIRE_REAL, AcqEvent, AcqHop, AcqLog,
+from .abi import (FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, WIRE_IQ, WIRE_REAL, AcqEvent, AcqHop, AcqLog, EQ_MODES, FilePlan, FileRxIn,
                   AcqRefined, AcqRefineIn, AcqResult, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, ResampleParams, SpecgramParams, SpecgramPlan, load_library)
 
 
@@ -197,6 +197,25 @@ def acq_stats(events: np.ndarray, refined: np.ndarray, n_hops: int, ntap: int = 
     if load_library().rade_acq_stats(events.ctypes.data, refined.ctypes.data, len(events), int(n_hops), int(ntap), float(fmax_target), float(acq_time_target), C.byref(r)):
         raise ValueError("rade_acq_stats refused its arguments")
     return r
+
+
+def file_plan(n: int, hop: int, t: int, f: float, freq_offset=None) -> FilePlan:
+    """rade_file_plan: where rx.py's normal run starts to demodulate a stream of n samples that acquired at hop `hop` (-1: not acquired) and whose refine -- called
+    one frame later, at 960 (hop + 1) + tmax in a stream of n - (hop + 1) samples -- returned the absolute timing t and frequency f.  -> abi.FilePlan (start, n_mf,
+    freq, status: an index into abi.FILE_STATUS).  freq_offset: the --freq_offset override.  Host only."""
+    out = FilePlan()
+    fo = None if freq_offset is None else C.byref(C.c_double(float(freq_offset)))
+    if load_library().rade_file_plan(int(n), int(hop), int(t), float(f), fo, C.byref(out)):
+        raise ValueError("rade_file_plan refused its arguments")
+    return out
+
+
+def ber_best(n_errors, n_ref: int):
+    """rade_ber_best over one stream's 20 counts: (shift, BER) of the first strict minimum below 1, (-1, 1.0) when there is none.  Host only."""
+    e = np.ascontiguousarray(n_errors, np.int64)
+    assert e.shape == (20,)
+    ber = C.c_double(1.0)
+    return int(load_library().rade_ber_best(e.ctypes.data, int(n_ref), C.byref(ber))), float(ber.value)
 
 
 def _per_stream(B: int, v, dtype, what: str) -> np.ndarray:
@@ -428,6 +447,59 @@ class BatchStages:
     acq_track = staticmethod(lambda hops, acq_test=False: acq_track(hops, acq_test))
     acq_stats = staticmethod(lambda events, refined, n_hops, ntap=101, fmax_target=0.0, acq_time_target=1.0: acq_stats(events, refined, n_hops, ntap, fmax_target,
                                                                                                                       acq_time_target))
+
+    # ---- the stored-file receiver past the acquisition ------------------------------------------------------------------------
+    def bpf_file(self, x, n=None, out=None):
+        """complex_bpf(101, ..).bpf(x) of whole files (rade_batch_bpf_file, rx.py:107-114).  x: cuda complex64 [B, S]; n: samples of each stream (a scalar or B values,
+        default S).  Returns y complex64 [B, S]: a stream's first n samples filtered, zeros behind them (left alone in a caller's `out`).  Synchronises the stream."""
+        import torch
+        B = self.B
+        assert _is_rows(x, B, torch.complex64)
+        S = x.shape[1]
+        n = _counts(B, n, S, "n")
+        out = _out_rows(out, B, n, S, x.device)
+        if self.lib.rade_batch_bpf_file(self.h, x.data_ptr(), _row_stride(x, S), n.ctypes.data, out.data_ptr(), _row_stride(out, out.shape[1]), _stream_ptr()):
+            raise RuntimeError("rade_batch_bpf_file failed (8-byte aligned rows, counts within both rows, an output that does not overlap the input)")
+        return out
+
+    def rx_file(self, x, plans, max_mf=None, time_offset: int = -16, eq: str = "ls", coarse_mag: bool = True, feat_width: int = 84):
+        """The fixed-timing demodulator and decoder of rx.py:223-253 (rade_batch_rx_file).  x: cuda complex64 [B, S]; plans: B (start, n_mf, freq) -- or objects with those
+        attributes, as file_plan returns; a stream with n_mf 0 gives zeros.  max_mf: rows of the result in modem frames (default: the largest n_mf, at least 1).
+        feat_width: the blob's decoder output per step (84 model19_check3), 0 = no decoder.  Returns (features [B, 3 max_mf, feat_width] or None, z_hat [B, 3 max_mf, 80]);
+        rows past a stream's 3 n_mf are zeros in z_hat.  Synchronises the stream."""
+        import torch
+        B = self.B
+        assert _is_rows(x, B, torch.complex64) and len(plans) == B
+        rec = np.zeros(B, np.dtype(FileRxIn))
+        for b, p in enumerate(plans):
+            rec[b] = (int(p.start), int(p.n_mf), float(p.freq)) if hasattr(p, "n_mf") else (int(p[0]), int(p[1]), float(p[2]))
+        max_mf = max(int(rec["n_mf"].max()), 1) if max_mf is None else int(max_mf)
+        z_hat = torch.empty((B, 3 * max_mf, 80), dtype=torch.float32, device=x.device)
+        feats = torch.empty((B, 3 * max_mf, feat_width), dtype=torch.float32, device=x.device) if feat_width else None
+        r = self.lib.rade_batch_rx_file(self.h, x.data_ptr(), _row_stride(x, x.shape[1]), rec.ctypes.data, max_mf, int(time_offset), EQ_MODES[eq], int(coarse_mag),
+                                        z_hat.data_ptr(), feats.data_ptr() if feats is not None else None, _stream_ptr())
+        if r != max_mf:
+            raise RuntimeError("rade_batch_rx_file failed (n_mf 0 or 2 .. max_mf, start >= 0 and start + 960 n_mf inside the row, time_offset in [-32, 0], "
+                               "3 max_mf <= 3 max_tx_mf with decode)")
+        return feats, z_hat
+
+    def ber_align(self, z_ref, z_hat, n_ref=None, n_hat=None):
+        """The BER alignment of rx.py:260-276 (rade_batch_ber_align).  z_ref, z_hat: cuda float32 [B, N] / [B, M] (or [B, rows, 80]); n_ref, n_hat: floats of each stream
+        (scalars or B values, default the whole row).  Returns n_errors np.int64 [B, 20]: the sign errors at shifts of 0..19 modem frames (240 floats) of the reference,
+        -1 where the shift leaves no reference.  ber_best(n_errors[b], n_ref[b]) gives the script's best shift and BER.  Synchronises the stream."""
+        import torch
+        B = self.B
+        z_ref, z_hat = (t.reshape(B, -1) for t in (z_ref, z_hat))
+        assert _is_rows(z_ref, B, torch.float32) and _is_rows(z_hat, B, torch.float32)
+        n_ref = _per_stream(B, z_ref.shape[1] if n_ref is None else n_ref, np.int64, "n_ref"); n_hat = _per_stream(B, z_hat.shape[1] if n_hat is None else n_hat, np.int64, "n_hat")
+        err = np.zeros((B, 20), np.int64)      # C long
+        if self.lib.rade_batch_ber_align(self.h, z_ref.data_ptr(), _row_stride(z_ref, z_ref.shape[1]), n_ref.ctypes.data, z_hat.data_ptr(), _row_stride(z_hat, z_hat.shape[1]),
+                                         n_hat.ctypes.data, err.ctypes.data, _stream_ptr()):
+            raise RuntimeError("rade_batch_ber_align failed (lengths within the rows)")
+        return err
+
+    file_plan = staticmethod(lambda n, hop, t, f, freq_offset=None: file_plan(n, hop, t, f, freq_offset))
+    ber_best = staticmethod(lambda n_errors, n_ref: ber_best(n_errors, n_ref))
 
     # ---- analog FM ----------------------------------------------------------------------------------------------------------
     def fm_mod(self, m, Fs: float, fc: float, fd: float, n=None, real: bool = False, sigma: float = 0.0, seed: int = 0, noise=None, phase0=0, n0=0, out=None,
