@@ -32,6 +32,8 @@
  *                          header and the time at which it starts; rade_chirp: chirp.py:50-65, the header itself
  *   rade_batch_specgram    plot_specgram.m:6-16 as ota_test.sh:130-134 and evaluate.sh:112, :153 draw it: the spectrogram of every recording, |X| of a 1280-sample Hann
  *                          window every 160 samples, normalised by the recording's maximum, as 256 grey levels
+ *   rade_batch_psd         radae_plots.m:53 (do_plots): the Welch power spectrum of every stream; rade_batch_sigstat :62-69: mean power, PAPR and the pilot symbol's
+ *                          PAPR; rade_psd_bandwidth :100-116: the 99 % power bandwidth
  */
 #ifndef RADE_BATCH_H
 #define RADE_BATCH_H
@@ -130,6 +132,8 @@ int rade_batch_n_streams(const rade_batch *h);
  *                                           host memory
  *   rade_batch_specgram                     x_dev (complex64 or int16; x_stride >= every n, checked) in, read inside the n[b] samples of row b only; img_dev (bytes; img_stride
  *                                           >= n_slices n_bins, checked; any alignment) and mag_dev (float; mag_stride >= 1023 n_slices, checked): a stream's own rows only
+ *   rade_batch_psd / rade_batch_sigstat     x_dev (complex64 or int16; x_stride >= every n, checked) in, read inside the n[b] samples of row b only; psd_dev (float;
+ *                                           psd_stride >= 1024, checked): the 1024 floats of row b; rade_batch_sigstat's results go to host memory
  *   rade_sc_tx / rade_sc_rx                 symbs_dev (float; dense), rx_dev (complex64; rx_stride >= n_avail, checked) in; iq_out_dev (complex64; iq_stride >= 384 n_frames, checked),
  *                                           payload / zhat / frames [B][max_frames][..] dense: frames past status.n_frames are not written */
 
@@ -566,6 +570,69 @@ int rade_batch_specgram(rade_batch *h, const void *x_dev, long x_stride, const i
                         unsigned char *img_dev, long img_stride,    /* [B][slices][n_bins] levels, img_stride in bytes per stream; or NULL */
                         float *mag_dev, long mag_stride,            /* [B][slices][1023] |X[1..1023]|, mag_stride in floats per stream; or NULL */
                         float *peak_host /* [B] */, int *n_slices_host /* [B] */, void *stream);
+
+/* ---- the waveform itself: Welch power spectrum, 99 % bandwidth, mean power and PAPR of every stream (rade_psd.hip) --------------------------------------------
+ * radae_plots.m: do_plots (:34-72) takes the --write_rx / --write_tx file of a run: y = pwelch(rx, [], [], 1024, Fs) (:53), max and mean of |rx|^2, their ratio in dB
+ * over the file and over its first 160 samples (:62-69), and bandwidth() (:100-116): the smallest bw whose bins round(centre -+ bw / 2) hold more than 99 % of sum(y).
+ * RECALLED, NOT VERIFIED (pwelch.m was not at hand where this was written): with an empty window and overlap pwelch takes a Hamming window of
+ *   2^ceil(log2(sqrt(n / 0.5))) samples at 50 % overlap.  rade_psd_octave_default(n, &win, &step) returns that recalled rule (win may exceed 1024) and nothing here
+ *   depends on it: DEVIATION: the stage takes win and step explicitly.
+ * DEVIATION: bandwidth() asks for Nfft = 1204; by its centre formula round(Nfft 1500 / Fs) and its frequency axis that is a slip for 1024.  Only nfft = 1024 is built.
+ * DEVIATION: the density scaling 1 / (n_seg Fs sum w^2) and the symmetric window are pinned against scipy.signal.welch (tests/test_psd_host.py), not against Octave.
+ * rade_batch_psd
+ * Geometry: nfft 1024; the window length 16 <= win <= 1024, each segment zero-padded to 1024; the hop 1 <= step <= win.  Segments start at s = 0, step, 2 step, .. while
+ *   s + win <= n; a tail that does not fill a segment is not used (rade_psd_segments: 0 for n < win).
+ * Window: w[i] = 0.54 - 0.46 cos(2 pi i / (win - 1)), Octave's hamming(win), scipy's get_window('hamming', win, fftbins=False): host, double, rounded once to float32,
+ *   kept in the engine's device memory for the last win used (rade_psd_window).
+ * Operand: z[i] = (x.re w[i], x.im w[i]), one rounded float32 multiply per component.  RADE_SPEC_S16_REAL: x = (gain (float)s, +0), the rule of rade_batch_wire_in: the
+ *   fused call equals wire_in followed by the complex64 call, bit for bit.  Two real segments are not paired into one transform.
+ * Transform: X_s[k] = sum_{i < win} z[i] e^{-2 pi i k i / 1024}, k = 0..1023.  How the device forms it (t[m] = e^{-2 pi i m / 1024}: ONE table of 1024 complex64, host,
+ *   double, rounded once per component): five radix-4 stages, s = 1, 4, 16, 64, 256; butterfly t = q + s p (q < s, t < 256) of a stage reads a_j = y[t + 256 j], j = 0..3
+ *   (stage 1: y = z, zeros for i >= win), and writes y'[q + s (4 p + m)] = b_m t[m p s], m = 0..3 -- the butterfly b_m and the product form of rade_batch_specgram
+ *   above, one rounded multiply and one fused multiply-add per component.  1024 = 4^5: there is no radix-2 stage and the fifth stage leaves X_s[k] at element k.
+ * Accumulation: p_s[k] = fma(re, re, im im) in float32, im im rounded.  A workgroup owns a run of R = 32 consecutive segments of one stream (rade_psd_plan returns R) and
+ *   adds their p_s[k] to 0 in ascending segment order in float32; the runs of a stream are added in ascending order in double, multiplied once by the double
+ *   1 / (n_seg Fs sum_i w[i]^2) (the sum over the float32 window, formed on the host in double in ascending order) and rounded once to float32: P[b][k], the two-sided
+ *   density.  No atomics for the values: identical calls give identical bits, and a stream's bits are a function of its own samples, its length, win, step and Fs -- not
+ *   of the batch size, the other streams or the strides.
+ * Error bound, counted from these roundings (u = 2^-24; every factor has modulus 1, so the stages' errors add, each relative to S_s = sum_i |x[s + i] w[i]|, w the
+ *   double window): the window entry u, the operand's multiply u, 7 u per radix-4 stage (two levels of additions 2 u, the table entry u, the lone product 4 u): 37 u on
+ *   X_s[k], so 74 u S_s^2 on |X_s[k]|^2 <= S_s^2; the square (a product and a fused multiply-add) 2 u; the run's R - 1 float32 additions (R - 1) u of the run's sum; the
+ *   fold in double below u 2^-20; sum w^2 of the float32 window 2 u; the last rounding u.  78 + R, times 1.01 for the terms of second order:
+ *     | P^[b][k] - P[b][k] | <= (80 + R) u sum_s S_s^2 / (n_seg Fs sum w^2) = 112 u sum_s S_s^2 / (n_seg Fs sum w^2)
+ *   against the float64 P of the double window (tests/psd_ref.py); barring underflow.  A worst-case bound: tests/test_psd_gpu.py records how far below it the device stays.
+ * Layout: P[b][k] at psd_dev + b psd_stride + k floats, k = 0..1023 in natural order, 0 .. Fs 1023 / 1024, as pwelch returns for complex input.  n_seg_host[b] is always
+ *   written.  Nothing outside a stream's 1024 floats is written and nothing outside its n_host[b] samples is read.  psd_dev is 4-byte aligned, psd_stride >= 1024; x_dev
+ *   aligned to its element (8 bytes complex64, x_stride in samples; 2 bytes int16, x_stride in int16).
+ * Refused with -1 before any launch and with nothing written: NULL h, x_dev, n_host, psd_dev or n_seg_host; misaligned pointers; a negative count, one above x_stride or
+ *   any n_host[b] < win; psd_stride < 1024; win outside 16..1024; step outside 1..win; an unknown format; a gain or Fs that is not finite or not positive.
+ * The call copies the counts and scales to the device, launches twice and SYNCHRONISES `stream`, as rade_batch_specgram does.  Any engine; the device memory (table,
+ *   window, counts, the partial rows: 4 KB per run of 32 segments) belongs to the engine and grows with the call.
+ * rade_batch_sigstat
+ *   Per stream sum2 = sum |x|^2 and peak2 = max |x|^2 over its n_host[b] samples, and head_sum2, head_peak2 over its first min(n, head) (the script's 160: one OFDM
+ *   symbol, the pilot).  Every term is t = fma(re, re, im im) in float32 (im im rounded; int16 input by the rule above).  Sums: a chunk is 8192 consecutive samples;
+ *   thread j of 256 adds the chunk's samples j, j + 256, .. as doubles in ascending order, the 64 lanes of a wavefront are added by a fixed tree, the four wavefronts in
+ *   order (level 1); the chunks of a stream are added in ascending order (level 2).  Peaks: float32 maxima of t, which do not depend on the order.  Each term carries at
+ *   most 2 u relative error and the double sums add below u 2^-20: sum2 is within 2.02 u of the sum of the exact squares.  n = 0 gives zeros.  The bits of a stream do not
+ *   depend on the batch.  Mean power is sum2 / n, PAPR 10 log10(peak2 n / sum2) (inference.py:201, :211: 20 log10(max |tx| / sqrt(S))); silence is 0 / 0.
+ *   Refused with -1 before any launch and with nothing written: NULL h, x_dev, n_host or result_host; a misaligned x_dev; a negative count or one above x_stride; a
+ *   negative head; an unknown format; a gain that is not finite or not positive.  The call reads the results back and SYNCHRONISES `stream`.
+ * rade_psd_bandwidth: bandwidth() / spec_power() as written, on the host in double, P[0..nfft-1] as one-based y: centre = round(nfft centre_hz / Fs); for bw = 2, 3, ..:
+ *   st = max(1, round(centre - bw / 2)), en = round(centre + bw / 2), p = sum P(st..en); stop at the first bw with p > frac sum P and report bw Fs / nfft and p / sum P.
+ *   round is half away from zero, as Octave's.  -1 where en would pass the last bin (the script raises an index error there) or an argument is refused.
+ * rade_psd_plan, _segments, _window, _octave_default, _bandwidth: host only. */
+typedef struct { int nfft, win, step, run; } rade_psd_plan_t;       /* run: R, the segments whose |X|^2 a workgroup adds in float32 */
+typedef struct { double sum2, peak2, head_sum2, head_peak2; long long n; } rade_sigstat_result;
+int rade_psd_plan(int win, int step, rade_psd_plan_t *out);         /* -1 where rade_batch_psd refuses win or step */
+long long rade_psd_segments(long long n, int win, int step);       /* host only: segments of an n-sample stream, 0 for n < win */
+int rade_psd_window(int win, float *out /* [win] */);               /* host only */
+int rade_psd_octave_default(long long n, int *win, int *step);     /* host only: RECALLED, NOT VERIFIED */
+int rade_psd_bandwidth(const double *P, int nfft, double Fs, double centre_hz, double frac, double *bw_hz, double *ratio);
+int rade_batch_psd(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int format, float gain, int win, int step, double Fs,
+                   float *psd_dev, long psd_stride,                 /* [B][1024] density, psd_stride in floats per stream */
+                   int *n_seg_host /* [B] */, void *stream);
+int rade_batch_sigstat(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int format, float gain, int head,
+                       rade_sigstat_result *result_host /* [B] */, void *stream);
 
 /* ---- whole-file pilot acquisition: rx.py's frame loop (rx.py:146-188, --acq_test :164-178, :190-195) over every hop of every stream (rade_acq.hip) -------------------
  * rx.py walks a stored recording one modem frame at a time: acquisition.detect_pilots (dsp.py:178-231) over 2 Nmf + M + Ncp = 2112 samples, a small state machine, and

@@ -55,6 +55,8 @@ CnoPlan = _struct("CnoPlan", "rade_cno_plan_t", [(n, ci) for n in ("N", "J", "n_
 CnoResult = _struct("CnoResult", "rade_cno_result", [("n_windows", ci), ("n_positive", ci), ("max_st", cll), ("max_CNodB", cd), ("max_SNRdB", cd)])
 SpecgramParams = _struct("SpecgramParams", "rade_specgram_params", [("fmin", cd), ("fmax", cd), ("lo", cd), ("hi", cd), ("peak_in_host", vp)])
 SpecgramPlan = _struct("SpecgramPlan", "rade_specgram_plan_t", [(n, ci) for n in ("n_bins", "k0", "k1", "win", "step", "nfft")])
+PsdPlan = _struct("PsdPlan", "rade_psd_plan_t", [(n, ci) for n in ("nfft", "win", "step", "run")])
+SigstatResult = _struct("SigstatResult", "rade_sigstat_result", [(n, cd) for n in ("sum2", "peak2", "head_sum2", "head_peak2")] + [("n", cll)])
 AcqHop = _struct("AcqHop", "rade_acq_hop", [("Dtmax12", cf), ("Dthresh", cd), ("tmax", ci), ("f_ind", ci), ("candidate", ci), ("S1", cd), ("S2", cd)])
 AcqEvent = _struct("AcqEvent", "rade_acq_event", [("hop", ci), ("tmax", ci), ("f_ind", ci)])
 AcqLog = _struct("AcqLog", "rade_acq_log", [("state", ci), ("tmax_candidate", ci), ("valid_count", ci)])
@@ -147,6 +149,13 @@ PROTOTYPES = {
         "rade_specgram_window": (None, [vp]),
         "rade_specgram_levels": (ci, [cd, cd, vp]),
         "rade_batch_specgram": (ci, [vp, vp, cl, vp, ci, cf, P(SpecgramParams), vp, cl, vp, cl, vp, vp, vp]),
+        "rade_psd_plan": (ci, [ci, ci, P(PsdPlan)]),
+        "rade_psd_segments": (cll, [cll, ci, ci]),
+        "rade_psd_window": (ci, [ci, vp]),
+        "rade_psd_octave_default": (ci, [cll, P(ci), P(ci)]),
+        "rade_psd_bandwidth": (ci, [vp, ci, cd, cd, cd, P(cd), P(cd)]),
+        "rade_batch_psd": (ci, [vp, vp, cl, vp, ci, cf, ci, ci, cd, vp, cl, vp, vp]),
+        "rade_batch_sigstat": (ci, [vp, vp, cl, vp, ci, cf, ci, vp, vp]),
         "rade_acq_hops": (ci, [cll]),
         "rade_acq_fmax": (cd, [P(AcqHop)]),
         "rade_batch_acq_detect": (ci, [vp, vp, cl, vp, cd, vp, ci, vp, vp, cll, ci, vp]),
@@ -209,7 +218,10 @@ ACQ_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_acq_
 # The stored-file receiver behind the acquisition (radae_amd/acq.py: receive): a list of its own for the same reason, checked by build() with the others.
 FILE_SYMBOLS = ["rade_batch_bpf_file", "rade_file_plan", "rade_batch_rx_file", "rade_batch_ber_align", "rade_ber_best"]
 assert all(n in PROTOTYPES["rade_batch.h"] for n in FILE_SYMBOLS)
-EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in ACQ_SYMBOLS and n not in FILE_SYMBOLS]
+# The Welch periodogram and the power / peak sums (BatchStages.psd, .sigstat): a list of its own for the same reason, checked by build() with the others.
+PSD_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_psd_", "rade_batch_psd", "rade_batch_sigstat"))]
+EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in ACQ_SYMBOLS and n not in FILE_SYMBOLS
+                                                     and n not in PSD_SYMBOLS]
 
 _lib = None
 

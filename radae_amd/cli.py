@@ -14,6 +14,7 @@
     python -m radae_amd.cli rx RX.f32 [--no_bpf] [--acq_test] [--fmax_target HZ] [--acq_time_target S] [--write_Dt FILE]             rx.py --pilots up to the acquisition (no decoding): every frame's pilot search in one device call
     python -m radae_amd.cli chirp OUT.f32 NSEC [--flow HZ] [--fhigh HZ] [--amp A]                                                  chirp.py (host)
     python -m radae_amd.cli specgram IN OUT.png [--fmin HZ] [--fmax HZ]                                                            plot_specgram.m at 8 kHz: the transforms and levels on the device, a grey-scale PNG
+    python -m radae_amd.cli do_plots RX.f32 [--win N --step N] [--int16 GAIN] [--save_text F]                                      radae_plots.m: do_plots' two printed lines: Pav, PAPR, pilot PAPR, 99 % bandwidth (Welch spectrum and sums on the device)
 
 so that the reference's shell pipelines (`cat features_in.f32 | python3 radae_txe.py > rx.f32`, `cat rx.f32 | python3 radae_rxe.py > features_out.f32`: CMakeLists.txt:300-420) run with
 `python3 -m radae_amd.cli txe|rxe` in their place; `--fs 48000` (or 44100, ..) takes the place of the `sox .. -r 8000` stage of the off-air pipelines (radae_rx.sh:33,39): the
@@ -712,10 +713,47 @@ def _specgram(argv):
     return 0
 
 
+def _do_plots(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli do_plots", description="radae_plots.m: do_plots on a --write_rx / --write_tx file at 8 kHz: the Welch power spectrum "
+                                 "(Hamming window, 1024-point transform), mean power, PAPR, the PAPR of the first 160 samples and the 99 % power bandwidth around "
+                                 "1500 Hz; the transforms and the sums run on the device (rade_batch_psd, rade_batch_sigstat).  Prints the script's two lines; no plots")
+    ap.add_argument("rx", type=str, help="..IQIQ.. float32 samples (what --write_rx writes), or with --int16 raw int16 mono")
+    ap.add_argument("--win", type=int, default=0, help="window length, 16..1024 (default: what pwelch is recalled to take for an empty window, "
+                    "2^ceil(log2(sqrt(2 n))), at most 1024)")
+    ap.add_argument("--step", type=int, default=0, help="hop between segments, 1..win (default: 50 %% overlap)")
+    ap.add_argument("--int16", type=float, default=None, metavar="GAIN", help="the file is raw int16 mono, scaled by GAIN as int16tof32.py scales it")
+    ap.add_argument("--save_text", type=str, default="", help="write two columns, frequency in Hz and 10 log10 P minus its maximum (the curve of the script's figure 8)")
+    args = ap.parse_args(argv)
+    import torch
+    from . import engine
+    x = np.fromfile(args.rx, dtype=np.int16 if args.int16 is not None else np.csingle)
+    win = args.win or min(engine.psd_octave_default(max(len(x), 1))[0], engine.PSD_NFFT)
+    step = args.step or win - win // 2
+    if len(x) < win:
+        raise SystemExit(f"radae_amd.cli do_plots: {len(x)} samples; at least the window's {win} are needed")
+    eng = engine.BatchEngine(1, max_tx_mf=1)
+    xt = torch.tensor(x[None], device="cuda")
+    kw = {} if args.int16 is None else {"gain": args.int16}
+    P, _ = eng.psd(xt, win=win, step=step, **kw)
+    st = eng.sigstat(xt, **kw)
+    eng.close()
+    P = P[0].cpu().numpy().astype(np.float64)
+    print("Pav: %f PAPRdB: %5.2f PilotPAPRdB: %5.2f" % (st.Pav[0], st.PAPRdB[0], st.PilotPAPRdB[0]))
+    bw = engine.psd_bandwidth(P)
+    if bw is None:
+        raise SystemExit("radae_amd.cli do_plots: 99 % of the power is not reached inside the spectrum (the script's index error)")
+    print("bandwidth (Hz): %f power/total_power: %f" % bw)
+    if args.save_text:
+        with np.errstate(divide="ignore"):
+            dB = 10 * np.log10(P)
+        np.savetxt(args.save_text, np.column_stack([np.arange(len(P)) * engine.PSD_FS / len(P), dB - dB.max()]), fmt="%.6f")
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm,
-            "est_cno": _est_cno, "rx": _rx, "chirp": _chirp, "specgram": _specgram}
+            "est_cno": _est_cno, "rx": _rx, "chirp": _chirp, "specgram": _specgram, "do_plots": _do_plots}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2

@@ -344,6 +344,36 @@ typedef struct {
 } rd_spec_args;
 int rd_launch_specgram(const rd_spec_args *a, rd_stream_t s);
 
+/* the Welch periodogram of rade_batch_psd (rade_psd.hip; include/rade_batch.h states the arithmetic): k_psd, one workgroup per (run of RD_PSD_RUN consecutive segments,
+ * stream), leaves one row of 1024 float32 sums per run; k_psd_fold adds a stream's rows in ascending order in double and scales.  The formats are rd_spec_args'. */
+#define RD_PSD_NFFT 1024
+#define RD_PSD_WIN_MIN 16
+#define RD_PSD_RUN 32
+typedef struct {
+    const void *x; long x_stride;                               /* complex64 or int16, stream b at + b * x_stride elements of the buffer */
+    const int *n;                                               /* device [B] sample counts */
+    const double *scale;                                        /* device [B]: 1 / (n_seg Fs sum w^2) */
+    const float *tw, *win;                                      /* device: e^{-2 pi i m / 1024} [1024][2], the window [win] */
+    float *part;                                                /* device [B][max_runs][1024] */
+    float *psd; long psd_stride;                                /* [B][1024]; floats per stream */
+    float gain;                                                 /* of the int16 format */
+    int fmt, win_len, step, B, max_runs;                        /* max_runs: the most runs any stream of the call has; the row count of part per stream */
+} rd_psd_args;
+int rd_launch_psd(const rd_psd_args *a, rd_stream_t s);
+
+/* power and peak of rade_batch_sigstat (rade_psd.hip): k_sigstat, one workgroup per (chunk of RD_STAT_CHUNK consecutive samples, stream), leaves (sum, peak, sum and
+ * peak over the samples below head) per chunk; k_sigstat_fold adds a stream's chunks in ascending order. */
+#define RD_STAT_CHUNK 8192
+typedef struct {
+    const void *x; long x_stride;                               /* as rd_psd_args */
+    const int *n;                                               /* device [B] sample counts */
+    double *part;                                               /* device [B][max_chunks][4] */
+    double *out;                                                /* device [B][4]: sum2, peak2, head_sum2, head_peak2 */
+    float gain;
+    int fmt, head, B, max_chunks;                               /* max_chunks: the most chunks any stream of the call has */
+} rd_stat_args;
+int rd_launch_sigstat(const rd_stat_args *a, rd_stream_t s);
+
 /* whole-file pilot acquisition, rade_batch_acq_detect / _refine (rade_acq.hip; include/rade_batch.h states the arithmetic): k_acq_detect, one wavefront
  * per (RD_ACQ_NPART-th of the 960 within-frame timings, stream), eight to a workgroup, walks the stream's 960-sample blocks and leaves per (block, wavefront) one double sum of |D| and per (hop,
  * wavefront) one best cell; k_acq_combine folds the RD_ACQ_NPART partials of a hop in ascending order.  k_acq_refine: one workgroup per event. */

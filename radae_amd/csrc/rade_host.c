@@ -971,3 +971,60 @@ int rade_acq_stats(const rade_acq_event *events, const rade_acq_refined *refined
     *out = r;
     return 0;
 }
+
+/* ---------------------------------------------------------------------------------------------
+ * 9. the Welch periodogram and the 99 % bandwidth of radae_plots.m (include/rade_batch.h: rade_batch_psd, rade_batch_sigstat; rade_psd.hip): the geometry, the segment
+ *    count, the window, pwelch's recalled defaults, bandwidth() / spec_power() as written
+ * -------------------------------------------------------------------------------------------*/
+/* -1 where rade_batch_psd refuses the geometry */
+int rade_psd_plan(int win, int step, rade_psd_plan_t *out)
+{
+    if (!out || win < RD_PSD_WIN_MIN || win > RD_PSD_NFFT || step < 1 || step > win) return -1;
+    rade_psd_plan_t q = { RD_PSD_NFFT, win, step, RD_PSD_RUN };
+    *out = q;
+    return 0;
+}
+
+/* len(0 : step : n - win): starts 0, step, .. while start + win <= n */
+long long rade_psd_segments(long long n, int win, int step)
+{
+    return win >= 1 && step >= 1 && n >= win ? (n - win) / step + 1 : 0;
+}
+
+/* hamming(win): 0.54 - 0.46 cos(2 pi i / (win - 1)) in double, rounded once */
+int rade_psd_window(int win, float *out /* [win] */)
+{
+    if (!out || win < RD_PSD_WIN_MIN || win > RD_PSD_NFFT) return -1;
+    for (int i = 0; i < win; i++) out[i] = (float)(0.54 - 0.46 * cos(2.0 * PI_D * (double)i / (double)(win - 1)));
+    return 0;
+}
+
+/* RECALLED, NOT VERIFIED: pwelch(x, [], []) takes a Hamming window of 2^ceil(log2(sqrt(n / 0.5))) samples at 50 % overlap */
+int rade_psd_octave_default(long long n, int *win, int *step)
+{
+    if (!win || !step || n < 1 || n > (1LL << 40)) return -1;
+    int w = 1;
+    while ((double)w < sqrt((double)n / 0.5)) w *= 2;
+    *win = w; *step = w - w / 2;
+    return 0;
+}
+
+/* bandwidth() and spec_power() of radae_plots.m:92-116, one-based as written; round() is half away from zero in C as in Octave.  -1: `en` passes the last bin before
+ * the fraction is reached (the script's index error), or the arguments are refused */
+int rade_psd_bandwidth(const double *P, int nfft, double Fs, double centre_hz, double frac, double *bw_hz, double *ratio)
+{
+    if (!P || !bw_hz || !ratio || nfft < 2 || !(Fs > 0.0) || !isfinite(Fs) || !isfinite(centre_hz) || !isfinite(frac)) return -1;
+    double total = 0.0;
+    for (int k = 0; k < nfft; k++) total += P[k];
+    const double centre = round((double)nfft * centre_hz / Fs);
+    if (!(centre >= 1.0 && centre <= (double)nfft)) return -1;
+    for (int bw = 2; ; bw++) {
+        double st = round(centre - bw / 2.0);
+        const double en = round(centre + bw / 2.0);
+        if (st < 1.0) st = 1.0;
+        if (en > (double)nfft) return -1;
+        double p = 0.0;
+        for (int k = (int)st; k <= (int)en; k++) p += P[k - 1];
+        if (p > frac * total) { *bw_hz = bw * Fs / nfft; *ratio = p / total; return 0; }
+    }
+}

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "rade_dev.h"
 #include "rade_devutil.h"
+#include "rade_fft4.h"
 
 #define SPEC_WG 256
 #define SPEC_N RD_SPEC_NFFT
@@ -33,27 +34,6 @@
 #define SPEC_BUF (SPEC_N + SPEC_N / 4)
 static_assert(SPEC_N == 2048 && SPEC_WIN == 5 * 256 && SPEC_WG * 2 == SPEC_N / 4 && SPEC_RUN % 2 == 0, "two butterflies per thread and stage; the pruned first stage; whole pairs per run");
 static_assert((SPEC_BUF + SPEC_N) * 8 + (SPEC_SPAN + SPEC_WIN + 256 + 8) * 4 <= 160 * 1024 / 3, "three workgroups per CU");
-
-// element i of the transform buffer: 4 of padding behind every 16
-__device__ __forceinline__ int sp_at(int i) { return i + ((i >> 4) << 2); }
-// y w: one rounded product and one fused multiply-add per component
-__device__ __forceinline__ float2 sp_tw(float2 y, float2 w) { return make_float2(fmaf(-y.y, w.y, y.x * w.x), fmaf(y.y, w.x, y.x * w.y)); }
-__device__ __forceinline__ float2 sp_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 sp_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// one radix-4 butterfly of the stage with stride s = 1 << ls (butterfly t = q + s p): b_m = sum_j a_j (-i)^(j m) by additions alone, then y[q + s (4 p + m)] = b_m t[m p s]
-__device__ __forceinline__ void sp_butterfly(float2 *buf, const float2 *tw, const float2 a[4], int t, int ls)
-{
-    const int s = 1 << ls, q = t & (s - 1), p = t >> ls;
-    const float2 e = sp_add(a[0], a[2]), f = sp_add(a[1], a[3]), g = sp_sub(a[0], a[2]), d = sp_sub(a[1], a[3]);
-    const float2 b0 = sp_add(e, f), b2 = sp_sub(e, f);
-    const float2 b1 = make_float2(g.x + d.y, g.y - d.x), b3 = make_float2(g.x - d.y, g.y + d.x);       // g - i d, g + i d
-    const int o = q + ((4 * p) << ls), w = p << ls;
-    buf[sp_at(o)] = b0;
-    buf[sp_at(o + s)] = sp_tw(b1, tw[w]);
-    buf[sp_at(o + 2 * s)] = sp_tw(b2, tw[2 * w]);
-    buf[sp_at(o + 3 * s)] = sp_tw(b3, tw[3 * w]);
-}
 
 // how many of T[1..255] pk lie at or below m: the thresholds do not decrease with j (one rounded multiply each), so a search finds the count
 __device__ __forceinline__ int sp_level(float m, float pk, const float *lev)

@@ -89,6 +89,10 @@ struct rd_stages {
     /* rade_batch_specgram: the table e^{-2 pi i m / 2048} and the window behind it (made once); per call [B] counts, [255] thresholds and [B] given peaks in one
      * record; the [B] peaks */
     float *spec_tab; rd_pair spec_rec; float *spec_peak;
+    /* rade_batch_psd: the table e^{-2 pi i m / 1024} and the window behind it, key = the window length; per call [B] scales (double) and [B] counts in one record;
+     * [B][psd_cap][1024] partial rows, grown with the call.  rade_batch_sigstat: the [B] counts; [B][stat_cap][4] chunk records, grown with the call; [B][4] results */
+    rd_table psd_tab; rd_pair psd_rec; float *psd_part; long psd_cap;
+    rd_pair stat_n; double *stat_part; long stat_cap; double *stat_out;
     /* rade_batch_acq_detect / _refine: the [B] sample counts; [B][acq_cap + 1][RD_ACQ_NPART] block sums, [B][acq_cap][RD_ACQ_NPART] best cells and [B][acq_cap] hop
      * records, grown with the call; a chunk of RD_ACQ_EV_CHUNK events, their results and their fine rows */
     rd_pair acq_n; double *acq_psum; rd_acq_pmax *acq_pmax; rd_acq_rec *acq_rec; long acq_cap, acq_cap1, acq_cap2;
@@ -532,6 +536,102 @@ int rade_batch_specgram(rade_batch *h, const void *x_dev, long x_stride, const i
     for (int b = 0; b < B; b++) {
         peak_host[b] = p->peak_in_host ? p->peak_in_host[b] : pk[b];
         n_slices_host[b] = (int)rade_specgram_slices(n_host[b]);
+    }
+    return 0;
+}
+
+/* ---- the Welch periodogram and the power / peak sums: radae_plots.m's do_plots over every stream (rade_psd.hip; the geometry, the window and the bandwidth:
+ * rade_host.c) ------------------------------------------------------------------------------------------------------------------------------------------------ */
+static int psd_input_bad(const void *x_dev, int format, float gain)
+{
+    if (format != RADE_SPEC_C64 && format != RADE_SPEC_S16_REAL) return 1;
+    return ((uintptr_t)x_dev & (format == RADE_SPEC_C64 ? 7 : 1)) || !isfinite(gain) || !(gain > 0.0f);
+}
+
+int rade_batch_psd(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int format, float gain, int win, int step, double Fs,
+                   float *psd_dev, long psd_stride, int *n_seg_host, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || !psd_dev || !n_seg_host) return -1;
+    if (psd_input_bad(x_dev, format, gain) || ((uintptr_t)psd_dev & 3) || !isfinite(Fs) || !(Fs > 0.0) || psd_stride < RD_PSD_NFFT) return -1;
+    rade_psd_plan_t q;
+    if (rade_psd_plan(win, step, &q)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    long long max_seg = 0, segs = 0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride || n < win) return -1;
+        const long long ns = rade_psd_segments(n, win, step);
+        if (ns > max_seg) max_seg = ns;
+        segs += ns;
+    }
+    struct rd_stages *s = stages_of(h);
+    const size_t rec_bytes = (sizeof(double) + sizeof(int)) * B;
+    double *rec = s ? pair_host(h, &s->psd_rec, rec_bytes) : NULL;     /* [B] scales, [B] counts */
+    const int max_runs = (int)((max_seg + RD_PSD_RUN - 1) / RD_PSD_RUN);
+    if (!rec || table_alloc(h, &s->psd_tab, 3L * RD_PSD_NFFT, 0)) return -1;
+    if (dev_grow(h, &s->psd_part, &s->psd_cap, max_runs, sizeof(float) * RD_PSD_NFFT * B, 0)) return -1;
+    float w[RD_PSD_NFFT];
+    double sw2 = 0.0;                      /* of the float32 window, in double, in ascending order */
+    rade_psd_window(win, w);
+    for (int i = 0; i < win; i++) sw2 += (double)w[i] * (double)w[i];
+    if (!table_is(&s->psd_tab, win, 0)) {
+        rd_cno_table(RD_PSD_NFFT, s->psd_tab.host);
+        memcpy(s->psd_tab.host + 2 * RD_PSD_NFFT, w, sizeof(float) * win);
+        if (table_upload(&s->psd_tab, win, 0, 2 * RD_PSD_NFFT + (size_t)win, st)) return -1;
+    }
+    for (int b = 0; b < B; b++) rec[b] = 1.0 / ((double)rade_psd_segments(n_host[b], win, step) * Fs * sw2);
+    memcpy(rec + B, n_host, sizeof(int) * B);
+    if (pair_push(h, &s->psd_rec, rec_bytes, 0, st)) { settle(st); return -1; }      /* not waited for here: the call waits at its end */
+    rd_psd_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.scale = s->psd_rec.dev; a.n = (const int *)((const double *)s->psd_rec.dev + B);
+    a.tw = s->psd_tab.dev; a.win = s->psd_tab.dev + 2 * RD_PSD_NFFT; a.part = s->psd_part; a.psd = psd_dev; a.psd_stride = psd_stride;
+    a.gain = gain; a.fmt = format; a.win_len = win; a.step = step; a.B = B; a.max_runs = max_runs;
+    PROF_BEGIN(h, stream);
+    const int e = rd_launch_psd(&a, stream);
+    PROF_END(h, stream, RADE_PROF_CHAN, 5.0 * RD_PSD_NFFT * 10 * (double)segs);      /* 5 N log2 N per segment, the textbook count */
+    /* the stream is waited for (also where the launch failed: the staging copies above are then free again) */
+    if (settle(st) || e) return -1;
+    table_commit(&s->psd_tab);
+    for (int b = 0; b < B; b++) n_seg_host[b] = (int)rade_psd_segments(n_host[b], win, step);
+    return 0;
+}
+
+int rade_batch_sigstat(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, int format, float gain, int head, rade_sigstat_result *result_host,
+                       void *stream)
+{
+    ON_DEV(h);
+    if (!h || !x_dev || !n_host || !result_host || head < 0 || psd_input_bad(x_dev, format, gain)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    long long max_n = 0, total = 0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        const int n = n_host[b];
+        if (n < 0 || n > x_stride) return -1;
+        if (n > max_n) max_n = n;
+        total += n;
+    }
+    struct rd_stages *s = stages_of(h);
+    int *n_stage = s ? pair_host(h, &s->stat_n, sizeof(int) * B) : NULL;
+    const int max_chunks = (int)((max_n + RD_STAT_CHUNK - 1) / RD_STAT_CHUNK);
+    if (!n_stage || dev_grow(h, &s->stat_part, &s->stat_cap, max_chunks ? max_chunks : 1, sizeof(double) * 4 * B, 0)) return -1;
+    if (dev_grow(h, &s->stat_out, NULL, 4L * B, sizeof(double), 1)) return -1;
+    memcpy(n_stage, n_host, sizeof(int) * B);
+    if (pair_push(h, &s->stat_n, sizeof(int) * B, 0, st)) { settle(st); return -1; } /* not waited for here: the read-back waits */
+    rd_stat_args a;
+    memset(&a, 0, sizeof a);
+    a.x = x_dev; a.x_stride = x_stride; a.n = s->stat_n.dev; a.part = s->stat_part; a.out = s->stat_out; a.gain = gain; a.fmt = format; a.head = head; a.B = B;
+    a.max_chunks = max_chunks;
+    PROF_BEGIN(h, stream);
+    const int e = rd_launch_sigstat(&a, stream);
+    PROF_END(h, stream, RADE_PROF_CHAN, 4.0 * (double)total);
+    const double *r = NULL;
+    if (e || !(r = read_back(h, s->stat_out, sizeof(double) * 4 * B, st))) { settle(st); return -1; }
+    for (int b = 0; b < B; b++) {
+        rade_sigstat_result o = { r[4 * b], r[4 * b + 1], r[4 * b + 2], r[4 * b + 3], n_host[b] };
+        result_host[b] = o;
     }
     return 0;
 }

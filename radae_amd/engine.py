@@ -17,11 +17,12 @@ import numpy as np
 from .abi import (BOTTLENECK1, BYPASS_DEC, DEFAULT_BLOB, EQ_MODES, EXPORTED_SYMBOLS, FEAT_MF, FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, LIB_PATH, NEOO, NEOO_BITS,  # noqa: F401
                   NIN_MAX, NMF, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, TX_BPF, TX_LINEAR, WIRE_IQ, WIRE_REAL, ZMF, BatchConfig,
                   ChannelParams, ChannelStreams, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, IdealRxParams, RateParams, ResampleParams, RxStatus, RxTrace,
-                  SpecgramParams, SpecgramPlan, _lib, load_library)
+                  PsdPlan, SigstatResult, SpecgramParams, SpecgramPlan, _lib, load_library)
 from .stages import (CNO_FS, CNO_HOP, FM_DE_EMP_TC, RESAMPLE_PPM_MAX, SPEC_HI, SPEC_LO, SPEC_NFFT, SPEC_STEP, SPEC_WIN, BatchStages, ClockOffset, FmDemodulator,  # noqa: F401
                      FmModulator, RateConverter, WireMeters, ber_best, file_plan, _per_stream, _row_stride, _scalar_or_streams, _stream_ptr, chirp, cno_plan, cno_windows, fm_deemph_len,
                      fm_pre_emphasis, fm_sigma, fm_taps, ppm_from_rates, rate_count, rate_taps, resample_count, resample_taps, specgram_levels, specgram_plan,
                      specgram_slices, specgram_window)
+from .stages import PSD_FS, PSD_HEAD, PSD_NFFT, SigStat, psd_bandwidth, psd_octave_default, psd_plan, psd_segments, psd_window  # noqa: F401
 
 
 def sigma_from_EbNodB(EbNodB, bottleneck: int = 3, rate_Fs: bool = True):

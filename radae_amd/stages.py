@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from .abi import (FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, WIRE_IQ, WIRE_REAL, AcqEvent, AcqHop, AcqLog, EQ_MODES, FilePlan, FileRxIn,
-                  AcqRefined, AcqRefineIn, AcqResult, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, ResampleParams, SpecgramParams, SpecgramPlan, load_library)
+                  AcqRefined, AcqRefineIn, AcqResult, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, PsdPlan, ResampleParams, SigstatResult, SpecgramParams, SpecgramPlan, load_library)
 
 
 class WireMeters(NamedTuple):
@@ -164,6 +164,61 @@ def specgram_levels(lo: float = SPEC_LO, hi: float = SPEC_HI) -> np.ndarray:
     if load_library().rade_specgram_levels(float(lo), float(hi), t.ctypes.data):
         raise ValueError(f"rade_specgram_levels refuses lo {lo!r}, hi {hi!r} (0 < lo < hi <= 1)")
     return t
+
+
+PSD_NFFT, PSD_FS, PSD_HEAD = 1024, 8000.0, 160                                     # radae_plots.m:53, :66: pwelch(.., 1024, Fs), rx(1:160)
+
+
+class SigStat(NamedTuple):
+    """BatchStages.sigstat: per stream, numpy arrays [B]; a stream without power (or without samples) has nan where the script's 0 / 0 has"""
+    n: np.ndarray            # int64: samples
+    sum2: np.ndarray         # float64: sum |x|^2
+    peak2: np.ndarray        # float64: max |x|^2
+    head_sum2: np.ndarray    # the same two over the first min(n, head) samples
+    head_peak2: np.ndarray
+    Pav: np.ndarray          # sum2 / n
+    PAPRdB: np.ndarray       # 10 log10(peak2 / Pav)
+    PilotPAPRdB: np.ndarray  # 10 log10(head_peak2 / (head_sum2 / min(n, head)))
+
+
+def psd_plan(win: int = 1024, step: int = 512) -> PsdPlan:
+    """rade_psd_plan: (nfft, win, step, run) of rade_batch_psd, run = the segments a workgroup adds in float32 before the sums go on in double (host only)"""
+    q = PsdPlan()
+    if load_library().rade_psd_plan(int(win), int(step), C.byref(q)):
+        raise ValueError(f"rade_psd_plan refuses win {win!r}, step {step!r} (16 <= win <= 1024, 1 <= step <= win)")
+    return q
+
+
+def psd_segments(n: int, win: int, step: int) -> int:
+    """rade_psd_segments: len(range(0, n - win + 1, step)), the whole segments of n samples"""
+    return int(load_library().rade_psd_segments(int(n), int(win), int(step)))
+
+
+def psd_window(win: int) -> np.ndarray:
+    """rade_psd_window: hamming(win) = 0.54 - 0.46 cos(2 pi i / (win - 1)) as float32 (host only)"""
+    w = np.zeros(max(int(win), 0), np.float32)
+    if load_library().rade_psd_window(int(win), w.ctypes.data):
+        raise ValueError(f"rade_psd_window refuses win {win!r} (16 <= win <= 1024)")
+    return w
+
+
+def psd_octave_default(n: int):
+    """rade_psd_octave_default: (win, step) that pwelch(x, [], []) is RECALLED (not verified) to take for n samples: 2^ceil(log2(sqrt(n / 0.5))) at 50 % overlap"""
+    w, s = C.c_int(0), C.c_int(0)
+    if load_library().rade_psd_octave_default(int(n), C.byref(w), C.byref(s)):
+        raise ValueError(f"rade_psd_octave_default refuses n {n!r}")
+    return w.value, s.value
+
+
+def psd_bandwidth(P, fs: float = PSD_FS, centre_hz: float = 1500.0, frac: float = 0.99):
+    """rade_psd_bandwidth: radae_plots.m's bandwidth() on one spectrum P[0..N-1] (any float type; the sums are formed in double): (bandwidth in Hz, power / total power),
+    or None where the fraction is not reached before the band passes the last bin (the script's index error)"""
+    P = np.ascontiguousarray(np.asarray(P.detach().cpu().numpy() if hasattr(P, "detach") else P, np.float64))
+    assert P.ndim == 1
+    bw, ratio = C.c_double(0.0), C.c_double(0.0)
+    if load_library().rade_psd_bandwidth(P.ctypes.data, len(P), float(fs), float(centre_hz), float(frac), C.byref(bw), C.byref(ratio)):
+        return None
+    return bw.value, ratio.value
 
 
 def acq_hops(n: int) -> int:
@@ -400,6 +455,45 @@ class BatchStages:
                                         mg.data_ptr() if mag else None, W * (SPEC_NFFT // 2 - 1), pk.ctypes.data, ns.ctypes.data, _stream_ptr()):
             raise RuntimeError("rade_batch_specgram failed (every stream needs more than 1280 samples; a finite gain; given peaks finite and >= 0; an output to write)")
         return (im, ns, pk, mg) if mag else (im, ns, pk)
+
+    # ---- the waveform itself: Welch spectrum, power and peak -------------------------------------------
+    def _psd_input(self, x, n, fmt):
+        import torch
+        if fmt is None:
+            fmt = SPEC_S16_REAL if x.dtype == torch.int16 else SPEC_C64
+        assert _is_rows(x, self.B, torch.int16 if fmt == SPEC_S16_REAL else torch.complex64)
+        return fmt, _counts(self.B, n, x.shape[1], "n")
+
+    def psd(self, x, n=None, win: int = 1024, step: int = 512, fs: float = PSD_FS, fmt=None, gain: float = 1.0):
+        """radae_plots.m's pwelch(rx, [], [], 1024, Fs) over every stream (rade_batch_psd).  x: cuda complex64 [B, S] or int16 [B, S] (scaled by `gain` as wire_in does,
+        imaginary part +0); n: samples of each stream (a scalar or B values, default S), each at least win.  A symmetric Hamming window of `win` samples (16..1024) every
+        `step` (1..win), zero-padded to 1024 points.  Returns (P, n_seg): P cuda float32 [B, 1024], the two-sided density of bins 0 .. fs 1023 / 1024 in natural order;
+        n_seg int32 [B].  pwelch's own defaults are psd_octave_default(n) (recalled, not verified).  The call synchronises the current stream."""
+        import torch
+        B = self.B
+        fmt, n = self._psd_input(x, n, fmt)
+        psd_plan(win, step)
+        P = torch.zeros((B, PSD_NFFT), dtype=torch.float32, device=x.device)
+        ns = np.zeros(B, np.int32)
+        if self.lib.rade_batch_psd(self.h, x.data_ptr(), _row_stride(x, x.shape[1]), n.ctypes.data, fmt, gain, int(win), int(step), float(fs), P.data_ptr(), PSD_NFFT,
+                                   ns.ctypes.data, _stream_ptr()):
+            raise RuntimeError(f"rade_batch_psd failed (every stream needs at least win = {win} samples; a gain and fs that are finite and positive)")
+        return P, ns
+
+    def sigstat(self, x, n=None, head: int = PSD_HEAD, fmt=None, gain: float = 1.0) -> SigStat:
+        """radae_plots.m:62-69 over every stream (rade_batch_sigstat): sum and maximum of |x|^2 over each stream and over its first min(n, head) samples, and from them the
+        script's Pav, PAPRdB and PilotPAPRdB (nan for silence, as its 0 / 0).  x, n, fmt, gain as psd takes them; n = 0 is allowed.  The call synchronises the stream."""
+        B = self.B
+        fmt, n = self._psd_input(x, n, fmt)
+        res = (SigstatResult * B)()
+        if self.lib.rade_batch_sigstat(self.h, x.data_ptr(), _row_stride(x, x.shape[1]), n.ctypes.data, fmt, gain, int(head), C.byref(res), _stream_ptr()):
+            raise RuntimeError("rade_batch_sigstat failed (head >= 0; a gain that is finite and positive)")
+        r = np.array([(v.sum2, v.peak2, v.head_sum2, v.head_peak2) for v in res], np.float64).reshape(B, 4)
+        cnt = np.array([v.n for v in res], np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pav, hav = r[:, 0] / cnt, r[:, 2] / np.minimum(cnt, int(head))
+            papr, ppapr = 10 * np.log10(r[:, 1] / pav), 10 * np.log10(r[:, 3] / hav)
+        return SigStat(cnt, r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy(), pav, papr, ppapr)
 
     # ---- whole-file pilot acquisition ---------------------------------------------------------------
     def acq_detect(self, x, n=None, pacq_error1: float = 1e-5, dt_rows=None):
