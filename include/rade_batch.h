@@ -128,6 +128,11 @@ int rade_batch_n_streams(const rade_batch *h);
  *                                           samples of row b are written, 8 bytes at a time; p->noise_dev (complex64) is dense [B][max n]
  *   rade_batch_fm_demod                     x_dev (complex64; x_stride >= n_in, checked) in; y_dev (float32 or complex64; y_stride >= n_out, checked; 4- or 8-byte alignment)
  *                                           and p->bb_out_dev (complex64; bb_stride >= n_out, checked): n_out[b] samples of row b are written, one element at a time
+ *   rade_batch_channel_piece                tx_dev (complex64; tx_stride >= every n_in, checked), p->G_dev (complex64 pairs; g_stride >= every n_g, checked) in, read inside the
+ *                                           stream's n_in / n_g elements only; p->noise_dev (complex64) dense [B][max n_out]; rx_out_dev (complex64; rx_stride >= every n_out,
+ *                                           checked): n_out[b] samples of row b are written, 16 bytes at a time where the row allows it, single samples at an odd head or tail
+ *                                           (any rx_stride, any parity of n0 and n_out, element alignment)
+ *   rade_batch_multipath_piece              G_out_dev (complex64 pairs; g_stride >= every n_out, checked; 8-byte alignment): n_out[b] pairs of row b are written
  *   rade_batch_cno_est                      x_dev (complex64; x_stride >= every n, checked) in, read inside the n[b] samples of row b only and never written; the results go to
  *                                           host memory
  *   rade_batch_specgram                     x_dev (complex64 or int16; x_stride >= every n, checked) in, read inside the n[b] samples of row b only; img_dev (bytes; img_stride
@@ -794,6 +799,80 @@ int rade_batch_multipath_gen(rade_batch *h, const float *fir_taps_host, int n_ta
  * rade_batch_multipath_gen leaves it (hf_gain included), n_g > (n_sym - 1) M.  Returns n_sym or <0. */
 int rade_batch_multipath_h(rade_batch *h, const void *G_dev, int n_g, int fs_over_rs, int n_sym, int Nc, float delay_s, float Rs, int want_complex,
                            float *H_out_dev, void *stream);
+
+/* ---- the channel and the Doppler generator in pieces: endless streams through fixed-size calls (rade_chanp.hip) ------------------------------------------------
+ * rade_batch_channel and rade_batch_multipath_gen above need a whole utterance: they normalise by a power / a variance measured over all of it.  The two calls below
+ * are separate entry points with their own arithmetic, in which every quantity is a pure function of the ABSOLUTE sample index n (>= 0, up to 2^62): they keep no
+ * state on the device, and a stream cut into pieces anywhere equals the stream in one piece, bit for bit.  Nothing of the whole-utterance calls changes.
+ * DEVIATIONS from the reference (multipath_samples.m, radae.py:529-589), all three so that a piece needs nothing it cannot know:
+ *   1. hf_gain is the EXPECTED value 1 / sqrt(E var G1 + E var G2) (rade_multipath_gain), not 1 / sqrt of the variance realised by one sequence; and the channel
+ *      multiplies by a gain the caller gives (1 by default) instead of sqrt(tx power / multipath power) measured over the utterance.  With the expected hf_gain
+ *      E |G1|^2 + E |G2|^2 = 1, so no power pass is needed.  Over 10 s the realised gain scatters by +-10 % (mpp) and up to a factor of 2 (mpg) around the expected
+ *      one -- which is why a piece cannot measure it; over 8 seeds x 1200 s the mean ratio of realised to expected was 0.9993 (mpg), 1.0017 (mpp), 1.0022 (mpd).
+ *   2. the phase of the frequency offset is a 64-bit integer fraction of a turn, not a float32 angle: its accuracy does not decay with n.
+ *   3. the Doppler sequence has no end: no clamp of the interpolation index, no extrapolation of a last block.
+ *
+ * rade_batch_multipath_piece: (G1, G2) of absolute indices [n0[b], n0[b] + n_out[b]) into G_out_dev [B][g_stride][2] complex64 (g_stride in pairs, >= every n_out).
+ *   Draws     x_p[xi] = Box-Muller of words 0-1 of Philox4x32-10, counter (xi & 0xffffffff, 2 b + p, 1, xi >> 32), key as in rade_channel_params: path p of stream b,
+ *             low-rate index xi >= 0 (64 bit).  This is rade_batch_multipath_gen's draw for xi < 2^32.
+ *   FIR       y_p[i] = sum_{k = 0..n_taps-1} (double)taps[k] x_p[i + n_taps - k], in double, k ascending (rade_batch_multipath_gen's expression).
+ *   To Fs     i0 = n div low_ratio (integers), fr = (double)(n - i0 low_ratio) / (double)low_ratio, g_p[n] = y_p[i0] + (y_p[i0 + 1] - y_p[i0]) fr,
+ *             G_p[n] = (float)(hf_gain g_p[n]) per component.
+ *   hf_gain   a double given by the caller; 0 = rade_multipath_gain(taps, n_taps) = 1 / sqrt(2 ((2/3) R0 + (1/3) R1)), R0 = 2 sum t_k^2, R1 = 2 sum t_k t_{k+1}, t the
+ *             float32 taps widened to double: the expected variance of two independent linearly interpolated paths (the interpolation weights (1 - fr, fr) average to
+ *             E[(1 - fr)^2 + fr^2] = 2/3 and E[2 fr (1 - fr)] = 1/3 over a low-rate step).
+ *   1 <= n_taps <= 256, low_ratio >= 1 (the presets give 16 (lmr60), 400, 800, 8000).  Returns 0.
+ *   Refused (-1, before any launch, nothing written): NULL or misaligned (8 bytes) pointers, n_taps or low_ratio out of range, taps or hf_gain not finite, hf_gain < 0,
+ *   a negative count or n0, n0 + n_out above 2^62, g_stride shorter than a row.
+ *
+ * rade_batch_channel_piece: output i of row b of rx_out_dev is the received sample of absolute index n = n0[b] + i, 0 <= i < n_out[b].
+ *   tx[b][g] is the transmit sample of absolute index in_base[b] + g, 0 <= g < n_in[b]; transmit samples in front of index 0 or outside the row read as zero, and
+ *   nothing outside the row is read.  G[b][g] is (G1, G2) of absolute index g_base[b] + g, 0 <= g < n_g[b] (G_dev [B][g_stride][2]); with G_dev the row must cover
+ *   [max(0, n0 - 16), n0 + n_out), else the call is refused.
+ *     m[n]  = tx[n] G1[n] + tx[n - 16] G2[n - 16] (the second term when n >= 16; the complex products and the sum of rade_batch_channel); m = tx[n] without G_dev
+ *     v     = m gain_b                                                 (float32; 0 is taken as 1)
+ *     v     = v cis(ph[n] >> 32) when freq_offset != 0 or df_dt != 0:  ph[n] = (n + 1) f0q + T(n) dq mod 2^64, T(n) = n (n + 1) / 2 with the even factor halved first
+ *             (exact mod 2^64 for every n < 2^62), f0q = (uint64) llrint(turns 2^64), dq = (uint64) llrint(df_dt / 8000^2 2^64), both made on the host in double; the sum
+ *             is inclusive (the reference's cumsum); cis is the 32-bit phasor of rade_batch_fm_mod.  turns, the offset in turns per sample, is the rate rade_batch_channel
+ *             turns at: with a drift freq_offset / 8000 in double (its closed form), WITHOUT one the reference's float32 omega = ((freq_offset * 2) * (float)pi) / 8000
+ *             over 2 pi (radae.py sums a float32 tensor) -- up to 2e-7 relative from freq_offset / 8000 (5e-8 at 10 Hz: 8e-7 rad after 1,920 samples, which would separate
+ *             a piece from the whole call by more than the float32 rounding of the whole call's phase)
+ *     v    += sigma_b noise[b][i]                                      explicit: noise_dev complex64, dense [B][max n_out]
+ *     or    generated (noise_dev NULL, seed != 0): Philox counter (P & 0xffffffff, b, 0, P >> 32), P = n >> 1, words 0-1 for even n and 2-3 for odd n (rade_batch_channel's
+ *             draw for n < 2^33); RADE_CHANP_NOISE_COMPLEX: sigma_b 0.70710678f g per component; RADE_CHANP_NOISE_REAL: sigma_b g.x on the real part only (the rule of
+ *             inference.py:277-284 for the noise-only lead and tail)
+ *     v    += sine_amp cis(2 pi frac(n sine_freq / 8000)), then v rx_gain  (as rade_batch_channel; rx_gain 0 is taken as 1)
+ *   Silence between overs, the EOO frame (rade_batch_tx_eoo) and lead-in noise are the CALLER's transmit samples and piece boundaries: there is no n_pre, n_post or
+ *   with_eoo here.  rade_batch_channel with generated noise, no G and no frequency offset equals three piece calls bit for bit (real noise over the lead, complex over
+ *   the signal with in_base = n_pre, real over the tail).
+ *   sigma, freq_offset, df_dt, gain, n0, in_base, g_base: the scalar of the structure for every stream, or a [B] host array when the _host member is not NULL; stream b
+ *   of a call with arrays gets what a call with its values as scalars gives it, bit for bit.  The per-stream records are copied to the device ahead of the launch (the
+ *   call synchronises `stream` once for that).  Any engine; no model, encoder or receiver state is touched.  Returns 0.
+ *   Refused (-1, before any launch, nothing written): NULL or misaligned (8 bytes) pointers, negative counts, n0, in_base or g_base, any of those (or n0 + n_out) above
+ *   2^62, a stride shorter than its row, a G row that does not cover its window, values that are not finite, |freq_offset| > 2000, |df_dt| > 2000 * 8000, an unknown
+ *   noise mode, sigma < 0.
+ * Buffers: tx_dev (complex64; tx_stride >= every n_in, checked) and p->G_dev (complex64 pairs; g_stride >= every n_g, checked) in, read inside the stream's n_in / n_g
+ *   elements only and never written; p->noise_dev (complex64) dense [B][max n_out]; rx_out_dev (complex64; rx_stride >= every n_out, checked): n_out[b] samples of row b
+ *   are written and nothing else, two samples as one 16-byte word where the row puts an even-n sample on a 16-byte boundary, single samples otherwise and at an odd head
+ *   or tail (any rx_stride, any parity of n0 and n_out, element alignment).  rade_batch_multipath_piece's G_out_dev: n_out[b] pairs of row b, 16-byte words when the base
+ *   is 16-byte aligned, else 8-byte ones. */
+enum { RADE_CHANP_NOISE_COMPLEX = 0, RADE_CHANP_NOISE_REAL = 1 };
+typedef struct {
+    float sigma, freq_offset, df_dt, gain;                      /* every stream's value where the _host array below is NULL; Hz, Hz / s; gain 0 = 1 */
+    long long n0, in_base, g_base;                              /* likewise: absolute index of the first output, of tx[b][0], of G[b][0] */
+    const float *sigma_host, *freq_offset_host, *df_dt_host, *gain_host;          /* [B] or NULL */
+    const long long *n0_host, *in_base_host, *g_base_host;      /* [B] or NULL */
+    const void *G_dev; long g_stride; const int *n_g_host;      /* complex64 [B][g_stride][2] and the [B] pairs each row holds, or NULL: no two-path model */
+    const void *noise_dev;                                      /* complex64 [B][max n_out] unit noise, or NULL: generated from seed; seed 0 = no noise */
+    unsigned long long seed;
+    int noise_mode;                                             /* RADE_CHANP_NOISE_COMPLEX / _REAL (generated noise only) */
+    float sine_amp, sine_freq, rx_gain;
+} rade_channel_piece_params;
+int rade_batch_multipath_piece(rade_batch *h, const float *fir_taps_host, int n_taps, int low_ratio, double hf_gain, unsigned long long seed,
+                               const long long *n0_host /* [B] or NULL = 0 */, const int *n_out_host /* [B] */, void *G_out_dev, long g_stride, void *stream);
+int rade_batch_channel_piece(rade_batch *h, const void *tx_dev, long tx_stride, const int *n_in_host, void *rx_out_dev, long rx_stride, const int *n_out_host,
+                             const rade_channel_piece_params *p, void *stream);
+double rade_multipath_gain(const float *fir_taps, int n_taps);      /* host only; -1: NULL, n_taps outside 1..256, taps that are not finite or all zero */
 float rade_sigma_from_EbNodB(float EbNodB);
 /* bottleneck 1 (radae.py:574-576): sigma = (EbNo M)^-0.5, M = 160 */
 float rade_sigma_from_EbNodB_bn1(float EbNodB);

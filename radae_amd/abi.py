@@ -24,6 +24,7 @@ RATE_C64, RATE_S16_REAL, RATE_S16_IQ = 0, 1, 2                                  
 FM_F32, FM_C64 = 0, 1                                                              # rade_batch_fm_mod input / rade_batch_fm_demod output format
 FM_OUT_COMPLEX, FM_OUT_REAL = 0, 1                                                 # rade_batch_fm_mod output mode
 SPEC_C64, SPEC_S16_REAL = 0, 1                                                     # rade_batch_specgram format
+CHANP_NOISE_COMPLEX, CHANP_NOISE_REAL = 0, 1                                       # rade_channel_piece_params.noise_mode
 
 vp, cp, ci, cu, cl, cll, cull, cf, cd, P = C.c_void_p, C.c_char_p, C.c_int, C.c_uint, C.c_long, C.c_longlong, C.c_ulonglong, C.c_float, C.c_double, C.POINTER
 STRUCTS = {}                                                                       # typedef name in the headers -> its ctypes mirror
@@ -50,6 +51,10 @@ FmModParams = _struct("FmModParams", "rade_fm_mod_params", [("Fs", cd), ("fc", c
                                                             ("phase0_host", vp), ("phase_end_host", vp), ("n0_host", vp)])
 FmDemodParams = _struct("FmDemodParams", "rade_fm_demod_params", [("Fs", cd), ("fc", cd), ("fd", cd), ("out_format", ci), ("ph_dont_limit", ci), ("b1", vp), ("N1", ci), ("b2", vp),
                                                                   ("N2", ci), ("in_base_host", vp), ("n0_host", vp), ("bb_out_dev", vp), ("bb_stride", cl)])
+ChannelPieceParams = _struct("ChannelPieceParams", "rade_channel_piece_params",
+                             [(n, cf) for n in ("sigma", "freq_offset", "df_dt", "gain")] + [(n, cll) for n in ("n0", "in_base", "g_base")] +
+                             [(n, vp) for n in ("sigma_host", "freq_offset_host", "df_dt_host", "gain_host", "n0_host", "in_base_host", "g_base_host", "G_dev")] +
+                             [("g_stride", cl), ("n_g_host", vp), ("noise_dev", vp), ("seed", cull), ("noise_mode", ci), ("sine_amp", cf), ("sine_freq", cf), ("rx_gain", cf)])
 CnoParams = _struct("CnoParams", "rade_cno_params", [("window_time", cd), ("flow", cd), ("fhigh", cd)])
 CnoPlan = _struct("CnoPlan", "rade_cno_plan_t", [(n, ci) for n in ("N", "J", "n_bins", "flow_bin", "fhigh_bin", "noise_st", "noise_en")])
 CnoResult = _struct("CnoResult", "rade_cno_result", [("n_windows", ci), ("n_positive", ci), ("max_st", cll), ("max_CNodB", cd), ("max_SNRdB", cd)])
@@ -169,6 +174,9 @@ PROTOTYPES = {
         "rade_ber_best": (ci, [vp, cl, P(cd)]),
         "rade_batch_multipath_gen": (ci, [vp, P(cf), ci, ci, ci, vp, cull, vp, vp]),
         "rade_batch_multipath_h": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, ci, vp, vp]),
+        "rade_batch_multipath_piece": (ci, [vp, vp, ci, ci, cd, cull, vp, vp, vp, cl, vp]),
+        "rade_batch_channel_piece": (ci, [vp, vp, cl, vp, vp, cl, vp, P(ChannelPieceParams), vp]),
+        "rade_multipath_gain": (cd, [vp, ci]),
         "rade_sigma_from_EbNodB": (cf, [cf]),
         "rade_sigma_from_EbNodB_bn1": (cf, [cf]),
         "rade_sigma_from_EbNodB_rs3": (cf, [cf]),
@@ -220,8 +228,11 @@ FILE_SYMBOLS = ["rade_batch_bpf_file", "rade_file_plan", "rade_batch_rx_file", "
 assert all(n in PROTOTYPES["rade_batch.h"] for n in FILE_SYMBOLS)
 # The Welch periodogram and the power / peak sums (BatchStages.psd, .sigstat): a list of its own for the same reason, checked by build() with the others.
 PSD_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_psd_", "rade_batch_psd", "rade_batch_sigstat"))]
+# The channel and the Doppler generator in pieces (BatchStages.channel_piece, .multipath_piece): a list of its own for the same reason, checked by build() with the others.
+CHANP_SYMBOLS = ["rade_batch_multipath_piece", "rade_batch_channel_piece", "rade_multipath_gain"]
+assert all(n in PROTOTYPES["rade_batch.h"] for n in CHANP_SYMBOLS)
 EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in ACQ_SYMBOLS and n not in FILE_SYMBOLS
-                                                     and n not in PSD_SYMBOLS]
+                                                     and n not in PSD_SYMBOLS and n not in CHANP_SYMBOLS]
 
 _lib = None
 

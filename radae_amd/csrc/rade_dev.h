@@ -465,6 +465,38 @@ int rd_launch_noise_probe(const uint32_t *ctr /*[n][4]*/, uint32_t k0, uint32_t 
                           float *g /*[m][2]*/, int n, int m, rd_stream_t s);
 int rd_launch_multipath_h(const void *G, int n_g, int M, int n_sym, int Nc, float dRs, int want_complex, float *H, int B, rd_stream_t s);
 
+/* the channel and the Doppler generator in pieces, rade_batch_channel_piece / rade_batch_multipath_piece (rade_chanp.hip; include/rade_batch.h states the arithmetic):
+ * every output is a pure function of its absolute sample index, no device state.  k_dopp_piece: one workgroup per (tile of RD_DOPP_TILE outputs, stream), the tile's
+ * draws and its low-rate FIR outputs in LDS; k_chan_piece: two samples (one Philox counter) per thread. */
+#define RD_DOPP_TILE 1024                                        /* outputs of a generator tile */
+#define RD_DOPP_NTAPS_MAX 256
+typedef struct { long long n0; int n_out, pad; } rd_dopp_stream;              /* absolute index of the first output, count */
+typedef struct {
+    const float *taps; int n_taps, low_ratio;                   /* device [n_taps] */
+    double hf_gain; unsigned long long seed;
+    void *G; long g_stride;                                     /* complex64 pairs (G1, G2): stream b at + b * g_stride pairs */
+    const rd_dopp_stream *ps;                                   /* device [B] */
+    int B, max_out;
+} rd_dopp_args;
+int rd_launch_dopp_piece(const rd_dopp_args *a, rd_stream_t s);
+typedef struct {
+    long long n0, in_base, g_base;                              /* absolute index of the first output, of tx[b][0], of G[b][0] */
+    unsigned long long f0q, dq;                                 /* (uint64) llrint(turns per sample 2^64) (rade_stages.c: piece_turns), (uint64) llrint(df_dt / 8000^2 2^64) */
+    int n_in, n_g, n_out, rotate;                               /* rotate: f0 != 0 or df_dt != 0 */
+    float sigma, gain;
+} rd_chanp_stream;
+typedef struct {
+    const void *tx; long tx_stride;                             /* complex64 */
+    const void *G; long g_stride;                               /* complex64 pairs or NULL */
+    const void *noise; long noise_stride;                       /* complex64 [B][noise_stride] unit noise or NULL */
+    void *rx; long rx_stride;                                   /* complex64 */
+    const rd_chanp_stream *ps;                                  /* device [B] */
+    unsigned long long seed;                                    /* generated noise when noise is NULL and seed != 0 */
+    float sine_amp, sine_freq, rx_gain;
+    int noise_mode, B, max_out;                                 /* RADE_CHANP_NOISE_COMPLEX / _REAL = 0, 1 */
+} rd_chanp_args;
+int rd_launch_chan_piece(const rd_chanp_args *a, rd_stream_t s);
+
 /* CoreDecoderStatefull.forward (radae_base.py:388-430) for the pending rows of one stream, run inside the receiver
  * kernel by the stream's own workgroup (rx2_decode_pending -> dq2_layers): buffers and weights of that stage. */
 typedef struct { const float *wp, *bias; const unsigned short *wp16, *wa16; const float *wscale; int N, K; } rd_lin;

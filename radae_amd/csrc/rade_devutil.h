@@ -90,6 +90,20 @@ __device__ __forceinline__ float2 cis_reduced(double ang)
     float sn, cs; sincosf((float)r, &sn, &cs);
     return make_float2(cs, sn);
 }
+// the phasor of a 32-bit phase (one turn = 2^32): rade_fm.hip's carrier and mixer (its header comment states the construction), the frequency offset of rade_chanp.hip
+__device__ __forceinline__ float2 fm_cis(unsigned ph)
+{
+    const unsigned q = ph >> 30, r = ph & 0x3fffffffu;
+    const bool fold = r > 0x20000000u;                                // above pi / 4: the complement's sine and cosine, swapped
+    const unsigned rr = fold ? 0x40000000u - r : r;
+    const float ang = (float)((double)rr * (PI_D / 2147483648.0));    // (pi / 2) 2^-30 r', one rounding
+    float sn, cs; sincosf(ang, &sn, &cs);
+    const float c = fold ? sn : cs, s = fold ? cs : sn;
+    if (q == 0) return make_float2(c, s);
+    if (q == 1) return make_float2(0.0f - s, c);                      // (0 - s: +0 where s is 0)
+    if (q == 2) return make_float2(0.0f - c, 0.0f - s);
+    return make_float2(s, 0.0f - c);
+}
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 // thread index through an opaque asm: inside the receiver's per-call loop this keeps the compiler from hoisting every
 // thread-derived address computation of every phase out of the loop (hundreds of registers live across all phases)

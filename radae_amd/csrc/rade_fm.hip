@@ -24,19 +24,7 @@
 static_assert(RD_FM_TILE % (4 * FM_WG) == 0, "whole groups of four per thread");
 
 // ---- shared by both directions -----------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float2 fm_cis(unsigned ph)
-{
-    const unsigned q = ph >> 30, r = ph & 0x3fffffffu;
-    const bool fold = r > 0x20000000u;                                // above pi / 4: the complement's sine and cosine, swapped
-    const unsigned rr = fold ? 0x40000000u - r : r;
-    const float ang = (float)((double)rr * (PI_D / 2147483648.0));    // (pi / 2) 2^-30 r', one rounding
-    float sn, cs; sincosf(ang, &sn, &cs);
-    const float c = fold ? sn : cs, s = fold ? cs : sn;
-    if (q == 0) return make_float2(c, s);
-    if (q == 1) return make_float2(0.0f - s, c);                      // (0 - s: +0 where s is 0)
-    if (q == 2) return make_float2(0.0f - c, 0.0f - s);
-    return make_float2(s, 0.0f - c);
-}
+// (fm_cis, the phasor of a 32-bit phase: rade_devutil.h -- the channel pieces of rade_chanp.hip rotate by it too)
 
 // inclusive scan over the workgroup's 256 threads (integers mod 2^32); ws: 4 words of LDS; total: the sum over all threads
 __device__ __forceinline__ unsigned fm_block_scan(unsigned v, unsigned *ws, unsigned &total)

@@ -1,6 +1,6 @@
 /*
  * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
- * rate converter, analog FM, the chirp header's C/No, the spectrogram, the whole-file pilot acquisition and the stored-file receiver behind it.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * rate converter, analog FM, the channel and the Doppler generator in pieces, the chirp header's C/No, the spectrogram, the whole-file pilot acquisition and the stored-file receiver behind it.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
  * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
  * its device and pinned memory is on the engine's own list (rade_engine.h).
  *
@@ -83,6 +83,9 @@ struct rd_stages {
      * rade_batch_fm_demod: its [B] records; the two tap tables [2][RD_FM_NMAX], key = (N1, N2) and the bytes they were made from */
     rd_pair fm_ps; unsigned *fm_tsum; long fm_tsum_cap; unsigned *fm_ph_end;
     rd_pair fm_dps; rd_table fm_taps;
+    /* rade_batch_multipath_piece: [B] per-stream records; the taps [RD_DOPP_NTAPS_MAX], key = n_taps and the bytes they were made from.
+     * rade_batch_channel_piece: its [B] records */
+    rd_pair dopp_ps; rd_table dopp_taps; rd_pair chanp_ps;
     /* rade_batch_cno_est: the table e^{-2 pi i m / N}, key = the window length N; the [B] sample counts; [B][cno_cap][RD_CNO_JMAX][2] partial and [B][cno_bands_cap][2]
      * band sums, grown with the call */
     rd_table cno_tw; rd_pair cno_n; double *cno_part, *cno_bands; long cno_cap, cno_bands_cap;
@@ -414,6 +417,122 @@ int rade_batch_fm_demod(rade_batch *h, const void *x_dev, long x_stride, const i
     a.N1 = p->N1; a.N2 = p->N2; a.fmt = p->out_format; a.dont_limit = p->ph_dont_limit != 0; a.B = B; a.max_out = max_out;
     PROF_BEGIN(h, stream);
     if (rd_launch_fm_demod(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* ---- the channel and the Doppler generator in pieces (rade_chanp.hip) ---------------------------------------------------------------------------------------- */
+double rade_multipath_gain(const float *taps, int n_taps)
+{
+    if (!taps || n_taps < 1 || n_taps > RD_DOPP_NTAPS_MAX) return -1.0;
+    double R0 = 0.0, R1 = 0.0;             /* of one path's low-rate sequence: E |y[i]|^2 and E y[i] conj(y[i + 1]), the draws having unit variance per component */
+    for (int k = 0; k < n_taps; k++) {
+        if (!isfinite(taps[k])) return -1.0;
+        R0 += 2.0 * (double)taps[k] * (double)taps[k];
+        if (k + 1 < n_taps) R1 += 2.0 * (double)taps[k] * (double)taps[k + 1];
+    }
+    const double var = 2.0 * ((2.0 / 3.0) * R0 + (1.0 / 3.0) * R1);      /* two paths, the interpolation weights averaged over a low-rate step */
+    return var > 0.0 ? 1.0 / sqrt(var) : -1.0;
+}
+
+int rade_batch_multipath_piece(rade_batch *h, const float *fir_taps_host, int n_taps, int low_ratio, double hf_gain, unsigned long long seed,
+                               const long long *n0_host, const int *n_out_host, void *G_out_dev, long g_stride, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !fir_taps_host || !n_out_host || !G_out_dev || ((uintptr_t)G_out_dev & 7)) return -1;
+    if (n_taps < 1 || n_taps > RD_DOPP_NTAPS_MAX || low_ratio < 1 || !isfinite(hf_gain) || hf_gain < 0.0) return -1;
+    if (hf_gain == 0.0 && (hf_gain = rade_multipath_gain(fir_taps_host, n_taps)) <= 0.0) return -1;      /* (also: taps that are not finite) */
+    for (int k = 0; k < n_taps; k++) if (!isfinite(fir_taps_host[k])) return -1;
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    rd_dopp_stream *ps = s ? pair_host(h, &s->dopp_ps, sizeof(rd_dopp_stream) * B) : NULL;
+    if (!ps) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_dopp_stream *r = &ps[b];
+        r->n0 = n0_host ? n0_host[b] : 0; r->n_out = n_out_host[b]; r->pad = 0;
+        if (r->n_out < 0 || r->n_out > g_stride || r->n0 < 0 || r->n0 > (1LL << 62) || r->n0 + r->n_out > (1LL << 62)) return -1;
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (4.0 * n_taps / low_ratio + 16.0) * r->n_out;
+    }
+    if (!max_out) return 0;
+    rd_table *t = &s->dopp_taps;
+    if (table_alloc(h, t, RD_DOPP_NTAPS_MAX, 1)) return -1;
+    if (!table_is(t, n_taps, 1) || memcmp(t->last, fir_taps_host, sizeof(float) * n_taps)) {
+        memset(t->host, 0, sizeof(float) * RD_DOPP_NTAPS_MAX);
+        memcpy(t->host, fir_taps_host, sizeof(float) * n_taps);
+        if (table_upload(t, n_taps, 1, RD_DOPP_NTAPS_MAX, st)) return -1;
+    }
+    if (pair_push(h, &s->dopp_ps, sizeof(rd_dopp_stream) * B, 1, st)) return -1;     /* the one small copy ahead of the launch */
+    table_commit(t);
+    rd_dopp_args a;
+    memset(&a, 0, sizeof a);
+    a.taps = t->dev; a.n_taps = n_taps; a.low_ratio = low_ratio; a.hf_gain = hf_gain; a.seed = seed;
+    a.G = G_out_dev; a.g_stride = g_stride; a.ps = s->dopp_ps.dev; a.B = B; a.max_out = max_out;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_dopp_piece(&a, stream)) return -1;
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    return 0;
+}
+
+/* The frequency offset in turns per sample, the rate rade_batch_channel turns at (chan_phase_acc, rade_devutil.h): without a drift that is the reference's FLOAT32
+ * omega = ((f0 * 2) * pi) / 8000 (radae.py: the tensor it sums is float32), 5e-8 relative from f0 / 8000 at 10 Hz -- which is 8e-7 rad after 1,920 samples, more than
+ * the float32 phase's own rounding there; with a drift it is the closed form's double f0 / 8000.  A piece and the whole call then differ by roundings that do not grow
+ * with the sample index on the piece's side. */
+static double piece_turns(float f0, float df_dt)
+{
+    if (df_dt != 0.0f) return (double)f0 / 8000.0;
+    const float om = ((f0 * 2.0f) * (float)M_PI) / 8000.0f;
+    return (double)om / (2.0 * M_PI);
+}
+
+/* a scalar of the structure or stream b's entry of its [B] array */
+#define PIECE_VAL(p, name, b) ((p)->name##_host ? (p)->name##_host[b] : (p)->name)
+int rade_batch_channel_piece(rade_batch *h, const void *tx_dev, long tx_stride, const int *n_in_host, void *rx_out_dev, long rx_stride, const int *n_out_host,
+                             const rade_channel_piece_params *p, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !tx_dev || !rx_out_dev || !n_in_host || !n_out_host || !p || (p->G_dev && !p->n_g_host)) return -1;
+    if (((uintptr_t)tx_dev | (uintptr_t)rx_out_dev | (uintptr_t)p->G_dev | (uintptr_t)p->noise_dev) & 7) return -1;
+    if (p->noise_mode != RADE_CHANP_NOISE_COMPLEX && p->noise_mode != RADE_CHANP_NOISE_REAL) return -1;
+    if (!isfinite(p->sine_amp) || !isfinite(p->sine_freq) || !isfinite(p->rx_gain)) return -1;
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    rd_chanp_stream *ps = s ? pair_host(h, &s->chanp_ps, sizeof(rd_chanp_stream) * B) : NULL;
+    if (!ps) return -1;
+    int max_out = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched */
+        rd_chanp_stream *r = &ps[b];
+        const float sigma = PIECE_VAL(p, sigma, b), f0 = PIECE_VAL(p, freq_offset, b), dd = PIECE_VAL(p, df_dt, b), gain = PIECE_VAL(p, gain, b);
+        if (!isfinite(sigma) || sigma < 0.0f || !isfinite(f0) || fabsf(f0) > 2000.0f || !isfinite(dd) || fabsf(dd) > 2000.0f * 8000.0f || !isfinite(gain)) return -1;
+        r->n0 = PIECE_VAL(p, n0, b); r->in_base = PIECE_VAL(p, in_base, b); r->g_base = p->G_dev ? PIECE_VAL(p, g_base, b) : 0;
+        r->n_in = n_in_host[b]; r->n_out = n_out_host[b]; r->n_g = p->G_dev ? p->n_g_host[b] : 0;
+        if (span_bad(r->n_in, tx_stride, r->n_out, rx_stride, r->n0, 0, r->in_base) || r->in_base < 0 || r->n0 + r->n_out > (1LL << 62)) return -1;
+        if (p->G_dev) {
+            if (r->n_g < 0 || r->n_g > p->g_stride || r->g_base < 0 || r->g_base > (1LL << 62)) return -1;
+            if (r->n_out > 0 && (r->g_base > (r->n0 > 16 ? r->n0 - 16 : 0) || r->g_base + r->n_g < r->n0 + r->n_out)) return -1;      /* [max(0, n0 - 16), n0 + n_out) */
+        }
+        r->sigma = sigma; r->gain = gain == 0.0f ? 1.0f : gain;
+        r->rotate = f0 != 0.0f || dd != 0.0f;
+        r->f0q = (unsigned long long)llrint(piece_turns(f0, dd) * 18446744073709551616.0);
+        r->dq = (unsigned long long)llrint((double)dd / 64000000.0 * 18446744073709551616.0);
+        if (r->n_out > max_out) max_out = r->n_out;
+        work += (p->G_dev ? 30.0 : 14.0) * r->n_out;
+    }
+    if (!max_out) return 0;
+    if (pair_push(h, &s->chanp_ps, sizeof(rd_chanp_stream) * B, 1, st)) return -1;   /* the one small copy ahead of the launch */
+    rd_chanp_args a;
+    memset(&a, 0, sizeof a);
+    a.tx = tx_dev; a.tx_stride = tx_stride; a.G = p->G_dev; a.g_stride = p->g_stride; a.noise = p->noise_dev; a.noise_stride = max_out;
+    a.rx = rx_out_dev; a.rx_stride = rx_stride; a.ps = s->chanp_ps.dev; a.seed = p->seed;
+    a.sine_amp = p->sine_amp; a.sine_freq = p->sine_freq; a.rx_gain = p->rx_gain == 0.0f ? 1.0f : p->rx_gain;
+    a.noise_mode = p->noise_mode; a.B = B; a.max_out = max_out;
+    PROF_BEGIN(h, stream);
+    if (rd_launch_chan_piece(&a, stream)) return -1;
     PROF_END(h, stream, RADE_PROF_CHAN, work);
     return 0;
 }

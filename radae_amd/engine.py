@@ -23,6 +23,7 @@ from .stages import (CNO_FS, CNO_HOP, FM_DE_EMP_TC, RESAMPLE_PPM_MAX, SPEC_HI, S
                      fm_pre_emphasis, fm_sigma, fm_taps, ppm_from_rates, rate_count, rate_taps, resample_count, resample_taps, specgram_levels, specgram_plan,
                      specgram_slices, specgram_window)
 from .stages import PSD_FS, PSD_HEAD, PSD_NFFT, SigStat, psd_bandwidth, psd_octave_default, psd_plan, psd_segments, psd_window  # noqa: F401
+from .stages import ChannelStream, multipath_gain  # noqa: F401
 
 
 def sigma_from_EbNodB(EbNodB, bottleneck: int = 3, rate_Fs: bool = True):

@@ -1,5 +1,5 @@
 """The front-end stages of the batched engine, the Python mirror of radae_amd/csrc/rade_stages.c: rate-Rs channel, resampler, sound-card wire, rate converter, analog FM,
-C/No of the chirp header, the spectrogram and the whole-file pilot acquisition (its driver: radae_amd/acq.py).
+the channel and the Doppler generator in pieces, C/No of the chirp header, the spectrogram and the whole-file pilot acquisition (its driver: radae_amd/acq.py).
 
 Three layers: the host-only helpers of each stage (`*_count`, `*_taps`, `*_plan`, ..: no handle, no GPU); BatchStages, the plain base class that gives BatchEngine one
 method per stage call (it uses only self.lib, self.h, self.B and self.device, so this module does not import engine.py); and the classes that apply a stateless stage to
@@ -109,7 +109,17 @@ def fm_pre_emphasis(mod: np.ndarray, Fs: float, tc: float = FM_DE_EMP_TC) -> np.
     return y / y.max(axis=-1, keepdims=True)
 
 
-CNO_FS, CNO_HOP = 8000, 2000                                                       # est_CNo.py:23, :31 (Fs // 4)
+def multipath_gain(taps) -> float:
+    """rade_multipath_gain: 1 / sqrt(2 ((2/3) R0 + (1/3) R1)), R0 = 2 sum t^2, R1 = 2 sum t[k] t[k + 1] of the float32 taps: the hf_gain that gives the two linearly
+    interpolated Doppler paths unit power in expectation (host only; what multipath_piece uses unless it is given one)."""
+    t = np.ascontiguousarray(taps, dtype=np.float32)
+    v = float(load_library().rade_multipath_gain(t.ctypes.data, t.size))
+    if v <= 0:
+        raise ValueError("rade_multipath_gain refuses the taps (1..256 finite values, not all zero)")
+    return v
+
+
+CNO_FS, CNO_HOP = 8000, 2000                                                     # est_CNo.py:23, :31 (Fs // 4)
 
 
 def cno_plan(window_time: float = 4.0, flow: float = 400.0, fhigh: float = 2000.0) -> CnoPlan:
@@ -647,6 +657,65 @@ class BatchStages:
             raise RuntimeError("rade_batch_fm_demod failed (Fs > 0, |fc| <= Fs / 2, 0 < fd <= Fs / 2, 1..512 finite taps per filter)")
         return y, bb, n_out
 
+    # ---- the channel and the Doppler generator in pieces -----------------------------------------------------------------
+    def multipath_piece(self, taps, low_ratio: int, n_out, n0=0, seed: int = 1, hf_gain: float = 0.0, out=None):
+        """Doppler samples of absolute indices [n0, n0 + n_out) of every stream (rade_batch_multipath_piece): returns (G complex64 [B, max n_out, 2], n_out int32 [B]).
+        taps: the host FIR taps (rounded to float32, 1..256), low_ratio: Fs over the low rate (channel_tools.doppler_plan gives both); n_out, n0: scalars or B
+        per-stream values; hf_gain 0 = multipath_gain(taps), the expected-value normalisation.  Every sample is a pure function of (seed, stream, absolute index): pieces
+        equal the whole, bit for bit.  Pairs past a stream's n_out are zeros (left alone in a caller's `out`)."""
+        import torch
+        B = self.B
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        n_out = _per_stream(B, n_out, np.int32, "n_out"); n0 = _per_stream(B, n0, np.int64, "n0")
+        if out is None:
+            out = torch.zeros((B, max(int(n_out.max()), 1), 2), dtype=torch.complex64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.complex64 and out.dim() == 3 and out.shape[0] == B and out.shape[2] == 2 and out.stride(2) == 1 \
+            and (out.stride(1) == 2 or out.shape[1] <= 1) and out.stride(0) % 2 == 0
+        if self.lib.rade_batch_multipath_piece(self.h, taps.ctypes.data, taps.size, int(low_ratio), float(hf_gain), int(seed), n0.ctypes.data, n_out.ctypes.data,
+                                               out.data_ptr(), _row_stride(out, 2 * out.shape[1]) // 2, _stream_ptr()):
+            raise RuntimeError("rade_batch_multipath_piece failed (1..256 finite taps, low_ratio >= 1, hf_gain >= 0, n0 >= 0, n_out <= the row of out)")
+        return out, n_out
+
+    def channel_piece(self, tx, sigma=0.0, freq_offset=0.0, df_dt=0.0, gain=1.0, n0=0, in_base=None, n_in=None, n_out=None, G=None, g_base=None, n_g=None, noise=None,
+                      seed: int = 0, real_noise: bool = False, sine_amp: float = 0.0, sine_freq: float = 0.0, rx_gain: float = 1.0, out=None):
+        """The rate-Fs channel on a piece of every stream (rade_batch_channel_piece): tx cuda complex64 [B, N], whose sample g has the absolute index in_base + g (default
+        in_base = n0) -> (rx complex64 [B, max n_out], n_out int32 [B]), output i the received sample of absolute index n0 + i (default n_out = in_base + n_in - n0).
+        G: cuda complex64 [B, Ng, 2] Doppler pairs whose pair g has the absolute index g_base + g (default max(n0 - 16, 0)), n_g pairs per row (default Ng): the two-path
+        model tx[n] G1[n] + tx[n - 16] G2[n - 16]; None: none.  gain multiplies the two-path sample (no power is measured).  noise: cuda complex64 [B, >= max n_out] unit
+        noise, or generated from `seed` (complex, or real-valued with real_noise: the lead and tail of inference.py).  sigma, freq_offset, df_dt, gain, n0, in_base,
+        g_base, n_in, n_out, n_g: scalars or B per-stream values.  Pieces equal the whole, bit for bit."""
+        import torch
+        from .abi import CHANP_NOISE_COMPLEX, CHANP_NOISE_REAL, ChannelPieceParams
+        B = self.B
+        assert _is_rows(tx, B, torch.complex64)
+        N = tx.shape[1]
+        n_in = _counts(B, n_in, N, "n_in")
+        n0 = _per_stream(B, n0, np.int64, "n0")
+        in_base = n0.copy() if in_base is None else _per_stream(B, in_base, np.int64, "in_base")
+        n_out = np.maximum(in_base + n_in - n0, 0).astype(np.int32) if n_out is None else _per_stream(B, n_out, np.int32, "n_out")
+        out = _out_rows(out, B, n_out, n_out.max(), tx.device)
+        vals = [_per_stream(B, v, np.float32, w) for v, w in ((sigma, "sigma"), (freq_offset, "freq_offset"), (df_dt, "df_dt"), (gain, "gain"))]
+        p = ChannelPieceParams()
+        p.sigma_host, p.freq_offset_host, p.df_dt_host, p.gain_host = (v.ctypes.data for v in vals)
+        p.n0_host, p.in_base_host = n0.ctypes.data, in_base.ctypes.data
+        if G is not None:
+            assert G.is_cuda and G.dtype == torch.complex64 and G.dim() == 3 and G.shape[0] == B and G.shape[2] == 2 and G.stride(2) == 1 \
+                and (G.stride(1) == 2 or G.shape[1] <= 1) and G.stride(0) % 2 == 0
+            g_base = np.maximum(n0 - 16, 0) if g_base is None else _per_stream(B, g_base, np.int64, "g_base")
+            n_g = _counts(B, n_g, G.shape[1], "n_g")
+            p.G_dev, p.g_stride, p.n_g_host, p.g_base_host = G.data_ptr(), _row_stride(G, 2 * G.shape[1]) // 2, n_g.ctypes.data, g_base.ctypes.data
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.complex64 and noise.dim() == 2 and noise.shape[0] == B and noise.shape[1] >= n_out.max()
+            noise = noise[:, :int(n_out.max())].contiguous()          # dense [B][max n_out]
+            p.noise_dev = noise.data_ptr()
+        p.seed, p.noise_mode = int(seed), CHANP_NOISE_REAL if real_noise else CHANP_NOISE_COMPLEX
+        p.sine_amp, p.sine_freq, p.rx_gain = float(sine_amp), float(sine_freq), float(rx_gain)
+        if self.lib.rade_batch_channel_piece(self.h, tx.data_ptr(), _row_stride(tx, N), n_in.ctypes.data, out.data_ptr(), _row_stride(out, out.shape[1]), n_out.ctypes.data,
+                                             C.byref(p), _stream_ptr()):
+            raise RuntimeError("rade_batch_channel_piece failed (finite values, sigma >= 0, |freq_offset| <= 2000, n0, in_base, g_base >= 0, a G row that covers "
+                               "[max(n0 - 16, 0), n0 + n_out), n_out <= the row of out)")
+        return out, n_out
+
     # ---- the sound-card wire ------------------------------------------------------------------
     def wire_in(self, i16, n=None, iq: bool = False, gain: float = 1.0):
         """int16 samples to complex64 on the device (rade_batch_wire_in; `int16tof32.py --zeropad` when real).  i16: cuda int16 [B, N], one real channel, or with iq
@@ -795,3 +864,50 @@ class FmDemodulator(_TailCarry):
     def feed(self, x, want_bb: bool = False):
         """x cuda complex64 [B, n]: the next n samples of every stream -> (y [B, n], bb [B, n] or None)"""
         return self._feed(x, want_bb=want_bb)
+
+
+class ChannelStream(_TailCarry):
+    """The rate-Fs channel applied to transmit streams that arrive in pieces, for as long as they last (BatchEngine.channel_piece and .multipath_piece are stateless: this
+    keeps what the next piece needs): each stream's absolute sample index and its last 16 transmit samples, the delay of the second path.  channel: a preset of
+    channel_tools.PRESETS (the two-path Watterson model, its Doppler samples generated again for every piece over [n0 - 16, n0 + n): nothing of them is carried) or
+    None (AWGN).  EbNodB, freq_offset, df_dt, gain, n0 (the absolute index a stream starts at, for a stream that resumes): scalars or B per-stream values.  push()
+    returns the received piece, contiguous complex64 [B, n]: what BatchEngine.rx takes.  The concatenated pieces of a stream are bit-identical to one push of the whole
+    stream.  Silence, an end-of-over frame or lead-in noise are transmit samples the caller pushes."""
+    DELAY = 16
+
+    def __init__(self, engine: BatchStages, channel, EbNodB, freq_offset=0.0, df_dt=0.0, seed: int = 1, n0=0, gain=1.0, fs: int = 8000):
+        from .channel_tools import PRESETS, doppler_plan
+        B = engine.B
+        lib = load_library()
+        self.eng, self.seed = engine, int(seed)
+        self.sigma = np.array([lib.rade_sigma_from_EbNodB(float(e)) for e in _per_stream(B, EbNodB, np.float64, "EbNodB")], np.float32)
+        self.freq_offset, self.df_dt, self.gain = (_per_stream(B, v, np.float32, w) for v, w in ((freq_offset, "freq_offset"), (df_dt, "df_dt"), (gain, "gain")))
+        self.start = _per_stream(B, n0, np.int64, "n0").copy()
+        assert self.start.min() >= 0
+        self.taps = None
+        if channel is not None:
+            taps, self.ratio, _ = doppler_plan(PRESETS[channel][0], fs, 2)
+            self.taps = np.ascontiguousarray(taps, dtype=np.float32)
+            self.hf_gain = multipath_gain(self.taps)
+        self._carry(self.DELAY, 0)
+
+    @property
+    def n0(self) -> np.ndarray:
+        """the absolute index of the next sample of every stream, int64 [B]"""
+        return self.start + self.n_fed
+
+    def _emit(self, buf, in_end: int):
+        """buf = transmit samples [n_fed - 16, in_end): the piece [n_fed, in_end) through the channel"""
+        hist = min(self.DELAY, self.n_fed)                            # samples of the tail that have been pushed: in front of them a stream reads zeros by itself
+        n0, n = self.n0, in_end - self.n_fed
+        kw = {}
+        if self.taps is not None:
+            g0 = np.maximum(n0 - self.DELAY, 0)
+            G, n_g = self.eng.multipath_piece(self.taps, self.ratio, (n0 + n - g0).astype(np.int32), n0=g0, seed=self.seed, hf_gain=self.hf_gain)
+            kw = dict(G=G, g_base=g0, n_g=n_g)
+        rx, _ = self.eng.channel_piece(buf[:, self.DELAY - hist:], self.sigma, self.freq_offset, self.df_dt, self.gain, n0=n0, in_base=n0 - hist, n_out=n, seed=self.seed, **kw)
+        return rx[:, :n]
+
+    def push(self, tx):
+        """tx cuda complex64 [B, n]: the next n transmit samples of every stream -> rx complex64 [B, n]"""
+        return self._feed(tx)
