@@ -218,21 +218,8 @@ PROTOTYPES = {
 }
 SC_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith("rade_sc_")]
 CORE_SYMBOLS = list(PROTOTYPES["rade_core.h"])
-# The whole-file acquisition stage (radae_amd/acq.py).  Its symbols are kept in a list of their own, as the single-carrier ones are, and NOT in EXPORTED_SYMBOLS, although
-# every earlier front-end stage is listed there: tests/test_abi_host.py pins EXPORTED_SYMBOLS member for member, and a change that adds a stage does not edit existing
-# tests.  build() checks this list with the others; fold it into EXPORTED_SYMBOLS when that pinned list is next updated.
+EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS]
 FILE_STATUS = ("ok", "not acquired", "refine window outside the stream", "timing inside the first cyclic prefix: not decoded", "fewer than two modem frames left: not decoded")   # RADE_FILE_*
-ACQ_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_acq_", "rade_batch_acq_"))]
-# The stored-file receiver behind the acquisition (radae_amd/acq.py: receive): a list of its own for the same reason, checked by build() with the others.
-FILE_SYMBOLS = ["rade_batch_bpf_file", "rade_file_plan", "rade_batch_rx_file", "rade_batch_ber_align", "rade_ber_best"]
-assert all(n in PROTOTYPES["rade_batch.h"] for n in FILE_SYMBOLS)
-# The Welch periodogram and the power / peak sums (BatchStages.psd, .sigstat): a list of its own for the same reason, checked by build() with the others.
-PSD_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_psd_", "rade_batch_psd", "rade_batch_sigstat"))]
-# The channel and the Doppler generator in pieces (BatchStages.channel_piece, .multipath_piece): a list of its own for the same reason, checked by build() with the others.
-CHANP_SYMBOLS = ["rade_batch_multipath_piece", "rade_batch_channel_piece", "rade_multipath_gain"]
-assert all(n in PROTOTYPES["rade_batch.h"] for n in CHANP_SYMBOLS)
-EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in ACQ_SYMBOLS and n not in FILE_SYMBOLS
-                                                     and n not in PSD_SYMBOLS and n not in CHANP_SYMBOLS]
 
 _lib = None
 

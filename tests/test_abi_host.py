@@ -5,7 +5,8 @@
    (pointer, i32, u32, i64, u64, f32, f64, void) of each argument and of the return value;
 2. every ctypes structure of abi.STRUCTS has the size, field offsets and field sizes the host compiler gives its typedef;
 3. the comparison rejects what it is for: doctored header text is reported as a mismatch that names the function or field;
-4. the names the four binding modules offered before abi.py / stages.py were split off are all still there, and the derived symbol lists kept their members."""
+4. the names the four binding modules offered before abi.py / stages.py were split off are all still there, and the derived symbol lists have the members pinned
+   here, no more and no fewer (EXPORTED_SYMBOLS: every function of rade_api.h and rade_batch.h but the single-carrier modem's, which SC_SYMBOLS lists)."""
 import ctypes as C
 import os
 import re
@@ -243,7 +244,11 @@ NAMES = {
         radae_tx_bypass_enc""",
 }
 SYMBOLS = {
-    "EXPORTED_SYMBOLS": """rade_batch_channel rade_batch_channel_rs_pa rade_batch_channel_streams rade_batch_channel_symbol rade_batch_close rade_batch_cno_est rade_batch_decode
+    "EXPORTED_SYMBOLS": """rade_acq_fmax rade_acq_hops rade_acq_stats rade_acq_track rade_batch_acq_detect rade_batch_acq_refine
+        rade_batch_ber_align rade_batch_bpf_file rade_batch_rx_file rade_ber_best rade_file_plan
+        rade_batch_psd rade_batch_sigstat rade_psd_bandwidth rade_psd_octave_default rade_psd_plan rade_psd_segments rade_psd_window
+        rade_batch_channel_piece rade_batch_multipath_piece rade_multipath_gain
+        rade_batch_channel rade_batch_channel_rs_pa rade_batch_channel_streams rade_batch_channel_symbol rade_batch_close rade_batch_cno_est rade_batch_decode
         rade_batch_encode rade_batch_fm_demod rade_batch_fm_mod rade_batch_loss rade_batch_multipath_gen rade_batch_multipath_h rade_batch_n_streams rade_batch_open
         rade_batch_open_mem rade_batch_profile rade_batch_profile_get rade_batch_profile_intervals rade_batch_profile_ref rade_batch_rate_convert rade_batch_resample
         rade_batch_reset rade_batch_rx rade_batch_rx_filtered rade_batch_rx_get_trace rade_batch_rx_ideal rade_batch_rx_reset rade_batch_rx_set_lcg rade_batch_rx_stream_cycles

@@ -94,18 +94,16 @@ def test_octave_rounding():
 
 # ---- 3. the header and the symbols --------------------------------------------------------------------------------------------------------------------------------
 def test_header_symbols_and_structures():
-    from radae_amd import abi
+    from radae_amd import abi, engine as E
     lib = abi.load_library()
     text = open(os.path.join(REPO, "include", "rade_batch.h")).read()
     names = ["rade_psd_plan", "rade_psd_segments", "rade_psd_window", "rade_psd_octave_default", "rade_psd_bandwidth", "rade_batch_psd", "rade_batch_sigstat"]
-    assert sorted(abi.PSD_SYMBOLS) == sorted(names)
     for n in names:
-        assert hasattr(lib, n), n
+        assert n in E.EXPORTED_SYMBOLS and hasattr(lib, n), n
         assert re.search(r"^(int|long long) %s\(" % n, text, re.M), n
     assert C.sizeof(abi.PsdPlan) == 16 and C.sizeof(abi.SigstatResult) == 40
     block = text[text.index("Welch power spectrum, 99 % bandwidth"):text.index("int rade_batch_sigstat(")]
     assert "DEVIATION" in block and "RECALLED, NOT VERIFIED" in block and "(80 + R) u" in block
-    from radae_amd import engine as E
     for n in ("psd_plan", "psd_segments", "psd_window", "psd_bandwidth", "psd_octave_default"):
         assert callable(getattr(E, n))
     assert callable(E.BatchEngine.psd) and callable(E.BatchEngine.sigstat)
