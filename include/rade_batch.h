@@ -30,6 +30,8 @@
  *   rade_batch_fm_demod    fm.m:97-126 (analog_fm_demod): mix, input filter, discriminator, output filter (de-emphasis folded into it)
  *   rade_batch_cno_est     est_CNo.py:23-73 as ota_test.sh:136-148 (process_rx) runs it over the first 10 s of every stored off-air file: the C/No of the 400-2000 Hz chirp
  *                          header and the time at which it starts; rade_chirp: chirp.py:50-65, the header itself
+ *   rade_batch_snr_trials  est_snr.py:45-124 with receiver_one.est_pilots (dsp.py:418-435): the trials of the pilot SNR estimator behind the receiver's correction
+ *                          constants, every set point of every channel in one call; rade_snr_finish / _fit / _track: the script's formulas, its np.polyfit, dsp.py:438-456
  *   rade_batch_specgram    plot_specgram.m:6-16 as ota_test.sh:130-134 and evaluate.sh:112, :153 draw it: the spectrogram of every recording, |X| of a 1280-sample Hann
  *                          window every 160 samples, normalised by the recording's maximum, as 256 grey levels
  *   rade_batch_psd         radae_plots.m:53 (do_plots): the Welch power spectrum of every stream; rade_batch_sigstat :62-69: mean power, PAPR and the pilot symbol's
@@ -135,6 +137,9 @@ int rade_batch_n_streams(const rade_batch *h);
  *   rade_batch_multipath_piece              G_out_dev (complex64 pairs; g_stride >= every n_out, checked; 8-byte alignment): n_out[b] pairs of row b are written
  *   rade_batch_cno_est                      x_dev (complex64; x_stride >= every n, checked) in, read inside the n[b] samples of row b only and never written; the results go to
  *                                           host memory
+ *   rade_batch_snr_trials                   p->H_dev (complex64; h_stride >= the rows a stream reads x 30, checked), p->noise_dev (complex64; noise_stride >= n_windows Nw 30,
+ *                                           checked) in, never written; p->noise_out_dev (complex64; the same noise_stride): the n_windows Nw 30 elements of row b are written,
+ *                                           8 bytes at a time; the sums go to host memory
  *   rade_batch_specgram                     x_dev (complex64 or int16; x_stride >= every n, checked) in, read inside the n[b] samples of row b only; img_dev (bytes; img_stride
  *                                           >= n_slices n_bins, checked; any alignment) and mag_dev (float; mag_stride >= 1023 n_slices, checked): a stream's own rows only
  *   rade_batch_psd / rade_batch_sigstat     x_dev (complex64 or int16; x_stride >= every n, checked) in, read inside the n[b] samples of row b only; psd_dev (float;
@@ -502,6 +507,81 @@ int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const in
                        double *bands_host /* [B][max_windows][2] = (C+N, band sum of No) or NULL */, int max_windows,
                        rade_cno_result *result_host /* [B] */, void *stream);
 int rade_chirp(float *iq_out /* [nsam][2] */, int nsam, double flow, double fhigh, double amp);
+
+/* ---- trials of the pilot SNR estimator: est_snr.py on the device, every set point of every channel in one call (rade_snr.hip) --------------------------------
+ * est_snr.py is the experiment behind the two constants the live receiver corrects its reported SNR with (m = 0.8070, c = 2.513, dsp.py:415-416; the mean of the
+ * straight-line fits est_snr_curves.sh makes over AWGN, MPG and MPP).  A trial is one window of Nw pilot rows x 30 carriers of one stream.  PINNED: the estimator's
+ * arithmetic -- receiver_one.est_pilots (dsp.py:418-435) and the script's own formulas (est_snr.py:45-124) as written.  NOT pinned: the script's np.random draws; the
+ * noise here is the engine's Philox / Box-Muller generator (or the caller's), so single points differ from a run of the script.
+ * Constants, all from the engine's tables: P[c] the pilot row (float32 sqrt 2 times the Barker sign), pg the model's pilot_gain, Pmat[c] the 3-pilot least-squares
+ *   matrices (plain transpose) and e^{-j w[c] a}, a = 0.0025 Fs = 20, w[c] and w[c] a formed in float32 as the reference forms them; c_mid = clamp(c, 1, 28).
+ * Per pilot row i and carrier c of window k of stream b, every product and sum in float32:
+ *     s   = h (pg P[c])                          h = H[(k Nw + i) h_step][c], or 1 without H                                  (est_snr.py:63)
+ *     n   = sigma_b g                            g the unit-variance noise of the element
+ *     x   = s + n
+ *     q_j = x[c_mid - 1 + j] / P[c_mid - 1 + j]  j = 0, 1, 2, same row
+ *     r   = (Pmat[c] q)_0 + (Pmat[c] q)_1 e^{-j w[c] a}                                                                        (dsp.py:431-433)
+ *     e   = Im(x conj(r) / |r|)                  = Im(x e^{-j angle r});  |r|^2 = 0 in float32 (r = 0) gives angle 0, as numpy does
+ *   and six sums per window, rade_snr_sums: S1 = sum |x|^2, S1_sig = sum |s|^2, S1_cross = sum 2 Re(s n) (as the script has it, WITHOUT a conjugate),
+ *   S1_noise = sum |n|^2, S2_genie = sum Im(|h| pg P + n)^2 (= sum Im(n)^2: the signal term is real), S2_est = sum e^2.  Every term is formed in float32 and added in
+ *   double in one fixed order: row-major over the window, carrier-minor, by one lane per sum.  No atomics: a window's six values do not depend on B, on the grid or on
+ *   which other windows are in the call; identical calls give identical bits.
+ * Noise, one of two modes (as rade_batch_fm_mod has them):
+ *   given      noise_dev, complex64 [B][n_windows Nw][30] at noise_stride elements per stream, unit variance per component; seed = 0
+ *   generated  seed != 0, noise_dev NULL: Philox4x32-10 keyed (seed & 0xffffffff, seed >> 32) as rade_channel_params' seed is, counter (q & 0xffffffff, b, 4, q >> 32)
+ *              with q = 15 R + (c >> 1), R = row0[b] + k Nw + i the ABSOLUTE pilot row; words 0-1 make the even carrier's g, words 2-3 the odd one's (gauss_pair).  The
+ *              draw is a function of R: a stream computed in pieces (the caller advances row0 and the H pointer) gives the bits of the whole.  noise_out_dev, when
+ *              given, receives g in the given-noise layout (same noise_stride); a given-noise call fed with it repeats the generated call bit for bit.
+ * Error bound, counted from these roundings (u = 2^-24; tests/snr_ref.py: bounds() restates it, tests/test_snr_est_gpu.py records how far below it the device stays).
+ *   Per element, in modulus: pg P one rounding, s one more: |ds| <= 2 u |s|; |dn| <= u |n| (+ sqrt 2 sigma dg where the noise itself is off by dg per component:
+ *   the generated draws against the float64 Box-Muller); x one rounding: e_x = 2 u |s| + u |n| + u |x| (+ sqrt 2 sigma dg).  A square-and-add is two roundings.  So
+ *     |dS1| <= sum 2 u |x|^2 + 2 |x| e_x + e_x^2          |dS1_sig| <= sum 6 u |s|^2          |dS1_noise| <= sum 2 u |n|^2 + 2 |n| e_n + e_n^2
+ *     |dS1_cross| <= sum 2 (2 u |s| |n| + e_s |n| + e_n |s| + e_s e_n)          |dS2_genie| <= sum u n_y^2 + 2 |n_y| e_ny + e_ny^2
+ *   r: a table entry is off by u, a quotient by at most 3 u (that covers a hardware reciprocal), a complex product by 3 u, a sum by u: along g_0 (1 + 3 + 3) + 2 = 9 u,
+ *   along g_1 another product by a table entry and the last sum: 14 u, and the g_0 terms see the last sum too: 10 u; the errors of x enter through the same weights:
+ *     e_r = u sum_j (10 |Pmat_0j| + 14 |Pmat_1j|) |q_j| + sum_j (|Pmat_0j| + |Pmat_1j|) e_x[j] / |P_j|
+ *   The angle of r is then off by at most (pi / 2) e_r / |r| (nothing is claimed where e_r >= |r|: the term's error is then bounded by 2 |x|); |r|^2 (2 u), its root
+ *   (u + a hardware square root's 2 u), the reciprocal (3 u) and the two products (u) leave the unit phasor's modulus off by 7 u and its angle by u; the last two
+ *   products and their sum add 2 u |x|:      e_e = e_x + |x| (pi / 2) e_r / |r| + 10 u |x|,      |dS2_est| <= sum u e^2 + 2 |e| e_e + e_e^2
+ *   each bound times 1.01 for the terms of second order.  The double sums add nothing that counts (1980 terms at most: 2^-42).
+ * Inputs per stream: H_dev complex64 [rows][30] at h_stride elements per stream, row (k Nw + i) h_step used -- h_step = 1, or Ns + 1 = 5 for a rate-Rs file, which
+ *   the script decimates with h[::Ns+1] -- NULL: h = 1 (AWGN); n_windows_host[B] (0 is allowed); sigma_host[B] float32 (0 is allowed: rade_snr_sigma); row0_host[B]
+ *   the absolute index of the stream's first pilot row, 0 .. 2^40, NULL: 0.  Nothing outside a stream's rows is read or written; inputs are never written.
+ * out_host: rade_snr_sums [B][max_windows], host memory; entries at or beyond a stream's window count are not written.  The call copies the per-stream values to the
+ *   device, launches once, reads the sums back and SYNCHRONISES `stream`, as rade_batch_cno_est does.  Any engine (of the model only the constant tables are used).
+ * Refused with -1 before any launch and with nothing written: NULL h, p, n_windows_host, sigma_host or out_host; Nw outside 1..66 (est_snr.py -T up to 8 s; the
+ *   default -T 1.0 gives 8); h_step outside 1..5; neither a seed nor noise_dev, or both; noise_out_dev without a seed; a pointer that is not 8-byte aligned; a negative
+ *   count; max_windows below a stream's count; a sigma that is negative or not finite; row0 outside 0 .. 2^40; h_stride (with H_dev) below the
+ *   ((n_windows Nw - 1) h_step + 1) 30 elements a stream reads, noise_stride (with noise_dev or noise_out_dev) below its n_windows Nw 30.
+ * Host only, double arithmetic, no device:
+ *   rade_snr_sigma(snrdB)   sqrt(Es / 10^(snrdB / 10)) / sqrt 2, Es = sum (pg P[c])^2 / 30 with the float32 products the kernel uses (est_snr.py:57-59)
+ *   rade_snr_finish         est_snr.py:96-122 over one window's sums: snr_est = S1 / (2 S2) - 1 with S2 = S2_est (eq_ls) or S2_genie, a value <= 0 becomes 0.1;
+ *                           snrdB_genie = 10 log10(S1_sig / S1_noise), snrdB_est = (10 log10 snr_est - c) / m, NdB_genie = 10 log10(2 S2_genie), NdB_est =
+ *                           10 log10(2 S2_est).  The script has no guard for S2 = 0 and neither has this: IEEE arithmetic, snr_est = +inf (NaN for 0 / 0, which the
+ *                           clamp does not catch either) and NdB = -inf.  -1: NULL, m = 0 or values that are not finite.
+ *   rade_snr_fit            the degree-1 least-squares line y = m x + c of np.polyfit(x, y, 1) (est_snr.py:178), by centred sums.  -1: NULL, n < 2, constant x.
+ *   rade_snr_track          what the live receiver does with one frame's sums (dsp.py:438-456) for n windows of Nw = 1 in turn: S2 = S2_est + 1e-12, snr_est =
+ *                           S1 / (2 S2) - 1, <= 0 becomes 0.1, (10 log10 snr_est - c) / m, + 10 log10(Rs Nc / 3000) + 10 log10((M + Ncp) / M) with Rs = 50,
+ *                           Nc = 30, M = 160, Ncp = 32, then *state = 0.9 *state + 0.1 of it; out[i] = *state after frame i: the figure rade_snrdB_3k_est reports
+ *                           before its rounding, in double where the reference's tensors are float32.  -1: NULL sums or state, n < 0, m = 0. */
+typedef struct { double S1, S1_sig, S1_cross, S1_noise, S2_genie, S2_est; } rade_snr_sums;
+typedef struct {
+    int Nw, h_step;                             /* pilot rows per window, 1..66; rows of H_dev per pilot row, 1..5 */
+    const void *H_dev; long h_stride;           /* complex64 [rows][30] per stream or NULL (h = 1) */
+    const float *sigma_host;                    /* [B] */
+    const long long *row0_host;                 /* [B] or NULL (0) */
+    const void *noise_dev;                      /* complex64 [n_windows Nw][30] per stream, or NULL with a seed */
+    void *noise_out_dev;                        /* optional, with a seed: the generated draws in the same layout */
+    long noise_stride;                          /* elements per stream of noise_dev / noise_out_dev */
+    unsigned long long seed;
+} rade_snr_params;
+typedef struct { double snrdB_genie, snrdB_est, NdB_genie, NdB_est; } rade_snr_point;
+int rade_batch_snr_trials(rade_batch *h, const int *n_windows_host /* [B] */, const rade_snr_params *p, rade_snr_sums *out_host /* [B][max_windows] */, int max_windows,
+                          void *stream);
+double rade_snr_sigma(double snrdB);
+int rade_snr_finish(const rade_snr_sums *s, int eq_ls, double c, double m, rade_snr_point *out);
+int rade_snr_fit(const double *x, const double *y, int n, double *m, double *c);
+int rade_snr_track(const rade_snr_sums *sums, int n, double c, double m, double *state, double *out /* [n] or NULL */);
 
 /* ---- the spectrogram of a recording: plot_specgram.m on the device, every stream in one call (rade_spec.hip) ------------------------------------------------
  * ota_test.sh:130-134 draws plot_specgram(s, 8000, 200, 3000) of every stored off-air file, evaluate.sh:112, :153 (utils.sh:66-68) plot_specgram(rx, 8000, 0, 3000).  With

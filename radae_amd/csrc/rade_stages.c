@@ -1,6 +1,6 @@
 /*
  * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
- * rate converter, analog FM, the channel and the Doppler generator in pieces, the chirp header's C/No, the spectrogram, the whole-file pilot acquisition and the stored-file receiver behind it.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * rate converter, analog FM, the channel and the Doppler generator in pieces, the chirp header's C/No, the trials of the pilot SNR estimator, the spectrogram, the whole-file pilot acquisition and the stored-file receiver behind it.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
  * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
  * its device and pinned memory is on the engine's own list (rade_engine.h).
  *
@@ -89,6 +89,8 @@ struct rd_stages {
     /* rade_batch_cno_est: the table e^{-2 pi i m / N}, key = the window length N; the [B] sample counts; [B][cno_cap][RD_CNO_JMAX][2] partial and [B][cno_bands_cap][2]
      * band sums, grown with the call */
     rd_table cno_tw; rd_pair cno_n; double *cno_part, *cno_bands; long cno_cap, cno_bands_cap;
+    /* rade_batch_snr_trials: [B] per-stream records; [B][snr_cap][RD_SNR_NSUM] sums, grown with the call */
+    rd_pair snr_ps; double *snr_sums; long snr_cap;
     /* rade_batch_specgram: the table e^{-2 pi i m / 2048} and the window behind it (made once); per call [B] counts, [255] thresholds and [B] given peaks in one
      * record; the [B] peaks */
     float *spec_tab; rd_pair spec_rec; float *spec_peak;
@@ -588,6 +590,105 @@ int rade_batch_cno_est(rade_batch *h, const void *x_dev, long x_stride, const in
         const double *bands = nw ? bands_all + (size_t)b * max_win * 2 : NULL;
         rd_cno_finish(&q, p, bands, nw, &result_host[b]);
         if (bands_host && nw) memcpy(bands_host + (size_t)b * max_windows * 2, bands, sizeof(double) * 2 * nw);
+    }
+    return 0;
+}
+
+/* ---- trials of the pilot SNR estimator: est_snr.py over every stream (rade_snr.hip); the script's formulas behind the sums, host only ------------------------- */
+int rade_batch_snr_trials(rade_batch *h, const int *n_windows_host, const rade_snr_params *p, rade_snr_sums *out_host, int max_windows, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !n_windows_host || !p || !p->sigma_host || !out_host) return -1;
+    if (p->Nw < 1 || p->Nw > RD_SNR_NW_MAX || p->h_step < 1 || p->h_step > RD_SNR_HSTEP_MAX) return -1;
+    if ((p->noise_dev != NULL) == (p->seed != 0) || (p->noise_out_dev && !p->seed)) return -1;          /* exactly one source of noise */
+    if (((uintptr_t)p->H_dev | (uintptr_t)p->noise_dev | (uintptr_t)p->noise_out_dev) & 7) return -1;
+    struct rd_stages *s = stages_of(h);
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    rd_snr_stream *ps = s ? pair_host(h, &s->snr_ps, sizeof(rd_snr_stream) * B) : NULL;
+    if (!ps) return -1;
+    int max_win = 0;
+    double work = 0.0;
+    for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
+        rd_snr_stream *r = &ps[b];
+        r->n_win = n_windows_host[b]; r->sigma = p->sigma_host[b]; r->row0 = p->row0_host ? p->row0_host[b] : 0;
+        if (r->n_win < 0 || r->n_win > max_windows || !isfinite(r->sigma) || r->sigma < 0.0f || r->row0 < 0 || r->row0 > (1LL << 40)) return -1;
+        const long long rows = (long long)r->n_win * p->Nw;
+        if (rows) {
+            if (p->H_dev && ((rows - 1) * p->h_step + 1) * RD_NC > p->h_stride) return -1;
+            if ((p->noise_dev || p->noise_out_dev) && rows * RD_NC > p->noise_stride) return -1;
+        }
+        if (r->n_win > max_win) max_win = r->n_win;
+        work += (p->noise_dev ? 60.0 : 160.0) * RD_NC * (double)rows;
+    }
+    if (!max_win) return settle(st) ? -1 : 0;
+    if (dev_grow(h, &s->snr_sums, &s->snr_cap, max_win, sizeof(double) * RD_SNR_NSUM * B, 1)) return -1;
+    if (pair_push(h, &s->snr_ps, sizeof(rd_snr_stream) * B, 0, st)) return -1;           /* not waited for here: the call waits at its end */
+    rd_snr_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.H = p->H_dev; a.h_stride = p->h_stride; a.h_step = p->h_step;
+    a.noise = p->noise_dev; a.noise_out = p->noise_out_dev; a.noise_stride = p->noise_stride;
+    a.ps = s->snr_ps.dev; a.seed = p->seed; a.sums = s->snr_sums; a.Nw = p->Nw; a.B = B; a.max_win = max_win;
+    PROF_BEGIN(h, stream);
+    const int e = rd_launch_snr_trials(&a, stream);
+    PROF_END(h, stream, RADE_PROF_CHAN, work);
+    /* the sums come back and the stream is waited for (also where the launch failed: the staging copy above is then free again) */
+    const double *all = NULL;              /* [B][max_win][RD_SNR_NSUM], read back */
+    if (e || !(all = read_back(h, s->snr_sums, sizeof(double) * RD_SNR_NSUM * B * max_win, st))) { settle(st); return -1; }
+    for (int b = 0; b < B; b++)
+        if (ps[b].n_win) memcpy(out_host + (size_t)b * max_windows, all + (size_t)b * max_win * RD_SNR_NSUM, sizeof(rade_snr_sums) * ps[b].n_win);
+    return 0;
+}
+
+/* sum (pg P[c])^2 / Nc with the float32 products k_snr_trials forms (rd_tables_fill: P = +-(float)sqrt 2, pilot_gain): every carrier has the same square */
+static double snr_Es(void)
+{
+    const float pgp = (float)(pow(10.0, -2.0 / 20.0) * 160.0 / sqrt(30.0)) * (float)sqrt(2.0);
+    return (double)pgp * (double)pgp;
+}
+
+double rade_snr_sigma(double snrdB)
+{
+    return sqrt(snr_Es() / pow(10.0, snrdB / 10.0)) / sqrt(2.0);
+}
+
+/* est_snr.py:107-109 / dsp.py:444-447: S1 / (2 S2) - 1, 0.1 where that is <= 0 (a NaN passes, as in the script) */
+static double snr_est_of(double S1, double S2)
+{
+    const double v = S1 / (2.0 * S2) - 1.0;
+    return v <= 0.0 ? 0.1 : v;
+}
+
+int rade_snr_finish(const rade_snr_sums *s, int eq_ls, double c, double m, rade_snr_point *out)
+{
+    if (!s || !out || !isfinite(c) || !isfinite(m) || m == 0.0) return -1;
+    out->snrdB_genie = 10.0 * log10(s->S1_sig / s->S1_noise);
+    out->snrdB_est = (10.0 * log10(snr_est_of(s->S1, eq_ls ? s->S2_est : s->S2_genie)) - c) / m;
+    out->NdB_genie = 10.0 * log10(2.0 * s->S2_genie);
+    out->NdB_est = 10.0 * log10(2.0 * s->S2_est);
+    return 0;
+}
+
+int rade_snr_fit(const double *x, const double *y, int n, double *m, double *c)
+{
+    if (!x || !y || !m || !c || n < 2) return -1;
+    double mx = 0.0, my = 0.0, sxx = 0.0, sxy = 0.0;
+    for (int i = 0; i < n; i++) { mx += x[i]; my += y[i]; }
+    mx /= n; my /= n;
+    for (int i = 0; i < n; i++) { sxx += (x[i] - mx) * (x[i] - mx); sxy += (x[i] - mx) * (y[i] - my); }
+    if (!(sxx > 0.0) || !isfinite(sxx) || !isfinite(sxy)) return -1;
+    *m = sxy / sxx; *c = my - *m * mx;
+    return 0;
+}
+
+int rade_snr_track(const rade_snr_sums *sums, int n, double c, double m, double *state, double *out)
+{
+    if (!sums || !state || n < 0 || !isfinite(c) || !isfinite(m) || m == 0.0) return -1;
+    const double bw_3k = 10.0 * log10((8000.0 / RD_M) * RD_NC / 3000.0), cp = 10.0 * log10((double)(RD_M + RD_NCP) / RD_M);
+    for (int i = 0; i < n; i++) {
+        const double snrdB_est = (10.0 * log10(snr_est_of(sums[i].S1, sums[i].S2_est + 1e-12)) - c) / m;
+        *state = 0.9 * *state + 0.1 * (snrdB_est + bw_3k + cp);
+        if (out) out[i] = *state;
     }
     return 0;
 }

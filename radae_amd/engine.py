@@ -24,6 +24,8 @@ from .stages import (CNO_FS, CNO_HOP, FM_DE_EMP_TC, RESAMPLE_PPM_MAX, SPEC_HI, S
                      specgram_slices, specgram_window)
 from .stages import PSD_FS, PSD_HEAD, PSD_NFFT, SigStat, psd_bandwidth, psd_octave_default, psd_plan, psd_segments, psd_window  # noqa: F401
 from .stages import ChannelStream, multipath_gain  # noqa: F401
+from .abi import SNR_SYMBOLS, SnrParams, SnrPoint, SnrSums  # noqa: F401
+from .stages import SNR_C, SNR_M, SNR_NC, SNR_NS, SnrSweep, snr_finish, snr_fit, snr_sigma, snr_sweep, snr_track, snr_windows_rows  # noqa: F401
 
 
 def sigma_from_EbNodB(EbNodB, bottleneck: int = 3, rate_Fs: bool = True):

@@ -1,5 +1,5 @@
 """The front-end stages of the batched engine, the Python mirror of radae_amd/csrc/rade_stages.c: rate-Rs channel, resampler, sound-card wire, rate converter, analog FM,
-the channel and the Doppler generator in pieces, C/No of the chirp header, the spectrogram and the whole-file pilot acquisition (its driver: radae_amd/acq.py).
+the channel and the Doppler generator in pieces, C/No of the chirp header, the trials of the pilot SNR estimator, the spectrogram and the whole-file pilot acquisition (its driver: radae_amd/acq.py).
 
 Three layers: the host-only helpers of each stage (`*_count`, `*_taps`, `*_plan`, ..: no handle, no GPU); BatchStages, the plain base class that gives BatchEngine one
 method per stage call (it uses only self.lib, self.h, self.B and self.device, so this module does not import engine.py); and the classes that apply a stateless stage to
@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from .abi import (FM_C64, FM_F32, FM_OUT_COMPLEX, FM_OUT_REAL, RATE_C64, RATE_S16_IQ, RATE_S16_REAL, RESAMPLE_MODES, SPEC_C64, SPEC_S16_REAL, WIRE_IQ, WIRE_REAL, AcqEvent, AcqHop, AcqLog, EQ_MODES, FilePlan, FileRxIn,
-                  AcqRefined, AcqRefineIn, AcqResult, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, PsdPlan, ResampleParams, SigstatResult, SpecgramParams, SpecgramPlan, load_library)
+                  AcqRefined, AcqRefineIn, AcqResult, CnoParams, CnoPlan, CnoResult, FmDemodParams, FmModParams, RateParams, PsdPlan, ResampleParams, SigstatResult, SnrParams, SnrPoint, SnrSums, SpecgramParams, SpecgramPlan, load_library)
 
 
 class WireMeters(NamedTuple):
@@ -142,6 +142,110 @@ def chirp(nsec: float, flow: float = 400.0, fhigh: float = 2000.0, amp: float = 
     if load_library().rade_chirp(x.ctypes.data, x.size, float(flow), float(fhigh), float(amp)):
         raise ValueError(f"rade_chirp refuses flow {flow!r}, fhigh {fhigh!r}, amp {amp!r} (finite values)")
     return x
+
+
+SNR_NC, SNR_NS, SNR_TMF = 30, 4, 0.12                                              # carriers; data symbols per modem frame; a modem frame in seconds (model.Tmf)
+SNR_M, SNR_C = 0.8070, 2.513                                                       # dsp.py:415-416: the receiver's correction, est_snr_curves.sh's -m / -c
+
+
+def snr_windows_rows(T: float = 1.0) -> int:
+    """est_snr.py:230: Nw = int(T // Tmf), the pilot rows of a window of T seconds (8 at the default -T 1.0)"""
+    return int(float(T) // SNR_TMF)
+
+
+def snr_sigma(snrdB: float) -> float:
+    """rade_snr_sigma: sqrt(Es / 10^(snrdB / 10)) / sqrt 2, Es = sum (pg P)^2 / Nc: the noise per component at a set point (est_snr.py:57-59; host only)"""
+    return float(load_library().rade_snr_sigma(float(snrdB)))
+
+
+def _snr_sums(sums) -> np.ndarray:
+    return np.ascontiguousarray(sums, np.dtype(SnrSums))
+
+
+def snr_finish(sums, eq_ls: bool = False, c: float = 0.0, m: float = 1.0) -> np.ndarray:
+    """rade_snr_finish over an array of abi.SnrSums records (any shape): a record array of abi.SnrPoint of the same shape (snrdB_genie, snrdB_est, NdB_genie, NdB_est;
+    est_snr.py:96-122).  S2 = 0 follows IEEE, as the script does: +inf.  Host only."""
+    a = _snr_sums(sums)
+    out = np.zeros(a.shape, np.dtype(SnrPoint))
+    lib = load_library()
+    ap, op = C.cast(a.ctypes.data, C.POINTER(SnrSums)), C.cast(out.ctypes.data, C.POINTER(SnrPoint))
+    for i in range(a.size):
+        if lib.rade_snr_finish(C.byref(ap[i]), int(bool(eq_ls)), float(c), float(m), C.byref(op[i])):
+            raise ValueError(f"rade_snr_finish refuses c {c!r}, m {m!r} (finite, m != 0)")
+    return out
+
+
+def snr_fit(x, y):
+    """rade_snr_fit: (m, c) of the least-squares line y = m x + c, np.polyfit(x, y, 1) (est_snr.py:178).  Host only."""
+    x = np.ascontiguousarray(x, np.float64).ravel(); y = np.ascontiguousarray(y, np.float64).ravel()
+    if x.shape != y.shape:
+        raise ValueError("snr_fit: x and y of one length")
+    m, c = C.c_double(0.0), C.c_double(0.0)
+    if load_library().rade_snr_fit(x.ctypes.data, y.ctypes.data, x.size, C.byref(m), C.byref(c)):
+        raise ValueError("rade_snr_fit refuses the points (at least two, x not constant, finite values)")
+    return m.value, c.value
+
+
+def snr_track(sums, c: float = SNR_C, m: float = SNR_M, state: float = 0.0) -> np.ndarray:
+    """rade_snr_track over the sums of n windows of Nw = 1 (a 1-D array of abi.SnrSums) in turn: float64 [n], the smoothed 3 kHz SNR the live receiver holds after
+    each frame (dsp.py:438-456), from `state` before the first.  Host only."""
+    a = _snr_sums(sums).ravel()
+    out = np.zeros(a.size, np.float64)
+    st = C.c_double(float(state))
+    if load_library().rade_snr_track(a.ctypes.data, a.size, float(c), float(m), C.byref(st), out.ctypes.data):
+        raise ValueError(f"rade_snr_track refuses c {c!r}, m {m!r} (finite, m != 0)")
+    return out
+
+
+class SnrSweep(NamedTuple):
+    """snr_sweep: per channel, in the order est_snr.py's sweep appends them (set point major, window minor)"""
+    snrdB_genie: np.ndarray  # float64 [n_channels, n_set_points * Nt]: the x of the script's plot and of its --save_text
+    snrdB_est: np.ndarray    # the y
+    NdB_genie: np.ndarray
+    NdB_est: np.ndarray
+    fit: np.ndarray          # float64 [n_channels, 2]: (m, c) of np.polyfit(snrdB_genie, snrdB_est, 1)
+    sums: np.ndarray         # abi.SnrSums [n_channels, n_set_points, Nt]
+
+
+def snr_sweep(channels, Nt: int, T: float = 1.0, set_points=range(-5, 20), eq_ls: bool = False, c: float = 0.0, m: float = 1.0, seed: int = 1, h_step: int = SNR_NS + 1,
+              engine=None) -> SnrSweep:
+    """est_snr.py's sweep for several channels in ONE device call: one stream per (channel, set point), Nt windows of Nw = int(T // 0.12) pilot rows each, generated
+    noise from `seed`.  channels: a sequence whose entries are None (AWGN, h = 1) or the channel's H as complex64 [rows, 30] (numpy or cuda), of which row
+    (k Nw + i) h_step is used: h_step = 5 for a rate-Rs file as the script decimates it (h[::Ns+1]), 1 for one row per modem frame; all set points of a channel use
+    the same H windows, as the script does.  engine: a BatchEngine of len(channels) * len(set_points) streams (default: one is opened for the call and closed).
+    The estimator's arithmetic is the script's; the noise is the engine's generator, not np.random, so single points differ from a run of the script."""
+    import torch
+    set_points = [float(v) for v in set_points]
+    Nw, n_ch, n_sp = snr_windows_rows(T), len(channels), len(set_points)
+    if Nw < 1 or Nt < 1 or not n_ch or not n_sp:
+        raise ValueError("snr_sweep: T of at least one modem frame (0.12 s), Nt >= 1, at least one channel and one set point")
+    B = n_ch * n_sp
+    own = engine is None
+    if own:
+        from .engine import BatchEngine
+        engine = BatchEngine(B, max_tx_mf=1)
+    try:
+        if engine.B != B:
+            raise ValueError(f"snr_sweep: the engine has {engine.B} streams, {n_ch} channels x {n_sp} set points need {B}")
+        rows = (Nt * Nw - 1) * h_step + 1
+        H = None
+        if any(ch is not None for ch in channels):
+            H = torch.ones((n_ch, rows, SNR_NC), dtype=torch.complex64, device=engine.device)
+            for j, ch in enumerate(channels):
+                if ch is not None:
+                    t = torch.as_tensor(ch).to(device=engine.device, dtype=torch.complex64)
+                    if t.dim() != 2 or t.shape[1] != SNR_NC or t.shape[0] < rows:
+                        raise ValueError(f"snr_sweep: channel {j} needs H of at least {rows} rows x {SNR_NC} carriers, got {tuple(t.shape)}")
+                    H[j] = t[:rows]
+            H = H[:, None].expand(n_ch, n_sp, rows, SNR_NC).reshape(B, rows, SNR_NC).contiguous()      # stream = channel * n_set_points + set point
+        sigma = np.array([snr_sigma(v) for v in set_points] * n_ch, np.float32)
+        sums = engine.snr_trials(Nt, Nw, sigma, H=H, h_step=h_step, seed=seed).reshape(n_ch, n_sp, Nt)
+    finally:
+        if own:
+            engine.close()
+    pts = snr_finish(sums, eq_ls, c, m).reshape(n_ch, n_sp * Nt)
+    fit = np.array([snr_fit(pts["snrdB_genie"][j], pts["snrdB_est"][j]) for j in range(n_ch)], np.float64)
+    return SnrSweep(pts["snrdB_genie"].copy(), pts["snrdB_est"].copy(), pts["NdB_genie"].copy(), pts["NdB_est"].copy(), fit, sums)
 
 
 SPEC_WIN, SPEC_STEP, SPEC_NFFT = 1280, 160, 2048                                   # plot_specgram.m:6-10 at Fs = 8000
@@ -438,6 +542,37 @@ class BatchStages:
             raise RuntimeError(f"rade_batch_cno_est failed (every stream needs at least N = {q.N} samples)")
         out = list(res)
         return (out, bh) if bands else out
+
+    # ---- trials of the pilot SNR estimator ------------------------------------------------------
+    def snr_trials(self, n_windows, Nw: int, sigma, H=None, h_step: int = 1, noise=None, seed: int = 0, row0=0, want_noise: bool = False):
+        """est_snr.py's trial over every window of every stream (rade_batch_snr_trials).  n_windows: windows of each stream (a scalar or B values, 0 allowed); Nw:
+        pilot rows per window (1..66); sigma: the noise per component (a scalar or B values: snr_sigma(snrdB)); H: cuda complex64 [B, rows, 30] or None (h = 1), of which
+        row (k Nw + i) h_step is used; noise: cuda complex64 [B, >= n_windows Nw, 30], unit variance per component, or None with a seed (generated: a function of
+        seed, stream and the absolute row row0 + k Nw + i, so a stream in pieces gives the bits of the whole); row0: a scalar or B values.  Returns a numpy record array
+        [B, W] of abi.SnrSums (S1, S1_sig, S1_cross, S1_noise, S2_genie, S2_est), W = the most windows any stream has (at least 1), zeros past a stream's own; with
+        want_noise also the generated draws, cuda complex64 [B, W Nw, 30].  The call synchronises the current stream."""
+        import torch
+        B = self.B
+        nw = _per_stream(B, n_windows, np.int32, "n_windows")
+        sg = _per_stream(B, sigma, np.float32, "sigma")
+        r0 = _per_stream(B, row0, np.int64, "row0")
+        W = max(int(nw.max()), 1)
+        rows = W * int(Nw)
+        for t, what in ((H, "H"), (noise, "noise")):
+            if t is not None:
+                assert t.is_cuda and t.dtype == torch.complex64 and t.dim() == 3 and t.shape[0] == B and t.shape[2] == SNR_NC and t.stride(2) == 1 \
+                    and (t.stride(1) == SNR_NC or t.shape[1] <= 1), f"{what}: cuda complex64 [B, rows, 30] with dense rows"
+        if want_noise and (noise is not None or not seed):
+            raise ValueError("snr_trials: want_noise goes with a seed")
+        nout = torch.zeros((B, rows, SNR_NC), dtype=torch.complex64, device=self.device) if want_noise else None
+        p = SnrParams(int(Nw), int(h_step), H.data_ptr() if H is not None else None, _row_stride(H, H.shape[1] * SNR_NC) if H is not None else 0, sg.ctypes.data,
+                      r0.ctypes.data, noise.data_ptr() if noise is not None else None, nout.data_ptr() if want_noise else None,
+                      _row_stride(noise, noise.shape[1] * SNR_NC) if noise is not None else rows * SNR_NC, int(seed))
+        out = np.zeros((B, W), np.dtype(SnrSums))
+        if self.lib.rade_batch_snr_trials(self.h, nw.ctypes.data, C.byref(p), out.ctypes.data, W, _stream_ptr()):
+            raise RuntimeError("rade_batch_snr_trials failed (Nw 1..66, h_step 1..5, a seed or a noise tensor and not both, sigma >= 0, 0 <= row0 <= 2^40, H and noise "
+                               "long enough for every stream's windows)")
+        return (out, nout) if want_noise else out
 
     # ---- the spectrogram ------------------------------------------------------------------------
     def specgram(self, x, n=None, fmin: float = 0.0, fmax: float = 3000.0, lo: float = SPEC_LO, hi: float = SPEC_HI, peak=None, mag: bool = False, fmt=None,
