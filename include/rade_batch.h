@@ -1113,6 +1113,48 @@ int rade_sc_tx(rade_sc *h, const float *symbs_dev, int n_frames, void *iq_out_de
 int rade_sc_rx(rade_sc *h, const void *rx_dev, long rx_stride, int n_avail, int max_frames, void *payload_out_dev, float *zhat_out_dev,
                rade_sc_frame *frames_out_dev, rade_sc_status *status_host, void *stream);
 
+/* ---- training the decoder (radae_amd/csrc/rade_train.hip, rade_train.c) ------------------------------------------------------------------------------------------
+ * One training step of the reference's CoreDecoder (radae_base.py:291-354, the stateless whole-sequence form train.py:257-263 uses) for B sequences of T latent rows
+ * at once, in float32: forward with saved activations, distortion_loss (radae_base.py:50-68) and its gradient, back-propagation through time, and Adam
+ * (train.py:147-150: betas (0.8, 0.95), eps 1e-8).  Zero GRU state and zero conv history at the start of every sequence.  A handle of its own, like rade_sc: it needs
+ * no engine and no blob, and owns the activation workspace for max_B x max_T rows.  The CALLER owns four flat float32 device buffers -- parameters, gradients, Adam's
+ * m and v -- of rade_train_n_floats() floats each, laid out by the table rade_train_param returns: entry i has a name (that of dnnw.Model's decoder member:
+ * "dec_dense1.w", "dec_gru[0].w_ih", "dec_glu[0].w", "dec_conv[0].w", "dec_output.b", ...), an offset in floats and a row-major shape rows x cols in torch's orientation
+ * ([out][in]; gate order r, z, n; a conv weight [32][in][2] has cols = 2 in, tap 0 the older row; a bias has cols = 1).
+ * Deviations from the reference, as everywhere in this library: the uniform +-1/254 noise of n() is left out and its clamp kept (the identity here: every argument lies
+ * in [-1, 1]); the GLU's effective weight is the parameter.  The encoder and the channel's backward pass are not here: dz_hat is what they would be handed.
+ * Buffers: all dense, element (4-byte) alignment, loss_dev 8-byte; z_hat_dev [B][T][80], features_hat_dev / dfeatures_hat_dev [B][4 T][21] (= [B][T][84]),
+ * features_dev [B][4 T][n_features], dz_hat_dev [B][T][80], loss_dev [B + 1] doubles: loss_by_batch, then their mean.  A call writes the documented extent of its
+ * outputs and nothing else of the caller's memory, never an input.  Every call is stream-ordered on `stream` and returns 0, -1 for an argument it refuses (NULL, B or T
+ * outside [1, max], a misaligned pointer, a call out of sequence) before any launch and with nothing written, -2 for a failed launch.  Results depend on B, T and the
+ * inputs only (fixed summation order, no atomics): two runs give the same bits, sequence b's features_hat and dz_hat rows do not depend on the other sequences of the
+ * batch, and a call below the handle's capacity gives the bits of a handle opened at that size. */
+typedef struct rade_train rade_train;
+rade_train *rade_train_open(int max_B, int max_T, int n_features /* 20 | 21 */, int device);      /* NULL without a GPU or for a bad argument; max_B max_T <= 2^21 */
+void rade_train_close(rade_train *h);
+long rade_train_n_floats(void);
+int rade_train_n_params(void);
+int rade_train_param(int i, const char **name, long *offset, int *rows, int *cols);                 /* any output may be NULL; -1 for i outside the table */
+/* forward: saves the concat buffer and per GRU layer r, z, n, W_hn h + b_hn, h and the GLU's sigmoid.  features_hat_dev may be NULL (the handle keeps its own copy). */
+int rade_train_dec_forward(rade_train *h, const float *params_dev, const float *z_hat_dev, int B, int T, float *features_hat_dev, void *stream);
+/* the saved concat buffer x [B][T][736] of the last forward call (layout: tests/core_ref.py:8-9) */
+int rade_train_saved_x(rade_train *h, float *x_out_dev, void *stream);
+/* the loss of the last forward call's features_hat against features_dev, and d total / d features_hat (kept in the handle; dfeatures_hat_dev may be NULL).
+ * loss_by_batch[b] is the mean of its frames' float32 terms, added in double in frame order; total is the mean of loss_by_batch in stream order. */
+int rade_train_loss(rade_train *h, const float *features_dev, float *dfeatures_hat_dev, double *loss_dev, void *stream);
+/* backward of the last forward call: grads_dev (all of it is written) and dz_hat_dev (may be NULL).  dfeatures_hat_dev NULL: the gradient rade_train_loss left. */
+int rade_train_dec_backward(rade_train *h, const float *params_dev, const float *dfeatures_hat_dev, float *grads_dev, float *dz_hat_dev, void *stream);
+/* one Adam update of all rade_train_n_floats() elements.  The caller forms in double lr = lr0 / (1 + decay step) and the corrections 1 - beta^step (step from 1). */
+int rade_train_adam(rade_train *h, float *params_dev, const float *grads_dev, float *m_dev, float *v_dev, double lr, double bias_correction1, double bias_correction2, void *stream);
+/* forward, loss, backward and Adam in one call */
+int rade_train_dec_step(rade_train *h, float *params_dev, float *grads_dev, float *m_dev, float *v_dev, const float *z_hat_dev, const float *features_dev, int B, int T,
+                        double *loss_dev, double lr, double bias_correction1, double bias_correction2, void *stream);
+/* Time per phase by HIP events (tools/time_train.py).  rade_train_profile(h, 1) starts recording a pair of events around each phase's launches (at most 512 pairs
+ * between two reads), 0 stops it; rade_train_profile_get waits for the recorded work, adds the milliseconds per phase into ms_out[6] -- forward GEMMs, forward scans,
+ * loss, backward scans, backward GEMMs with the activation derivatives and the folds, Adam -- starts over, and returns the number of intervals read. */
+int rade_train_profile(rade_train *h, int on);
+int rade_train_profile_get(rade_train *h, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif

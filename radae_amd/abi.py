@@ -223,6 +223,19 @@ PROTOTYPES = {
         "rade_sc_rrc": (None, [vp, vp]),
         "rade_sc_tx": (ci, [vp, vp, ci, vp, cl, vp]),
         "rade_sc_rx": (ci, [vp, vp, cl, ci, ci, vp, vp, vp, vp, vp]),
+        "rade_train_open": (vp, [ci, ci, ci, ci]),
+        "rade_train_close": (None, [vp]),
+        "rade_train_n_floats": (cl, []),
+        "rade_train_n_params": (ci, []),
+        "rade_train_param": (ci, [ci, P(cp), P(cl), P(ci), P(ci)]),
+        "rade_train_dec_forward": (ci, [vp, vp, vp, ci, ci, vp, vp]),
+        "rade_train_saved_x": (ci, [vp, vp, vp]),
+        "rade_train_loss": (ci, [vp, vp, vp, vp, vp]),
+        "rade_train_dec_backward": (ci, [vp, vp, vp, vp, vp, vp]),
+        "rade_train_adam": (ci, [vp, vp, vp, vp, vp, cd, cd, cd, vp]),
+        "rade_train_dec_step": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, cd, cd, cd, vp]),
+        "rade_train_profile": (ci, [vp, ci]),
+        "rade_train_profile_get": (ci, [vp, P(cd)]),
     },
 }
 SC_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith("rade_sc_")]
@@ -231,7 +244,9 @@ CORE_SYMBOLS = list(PROTOTYPES["rade_core.h"])
 # EXPORTED_SYMBOLS: tests/test_abi_host.py pins EXPORTED_SYMBOLS member for member, and a change that adds a stage does not edit existing tests.  build() checks every
 # name of PROTOTYPES whatever list it is in; fold this one into EXPORTED_SYMBOLS when that pinned list is next updated.
 SNR_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith(("rade_snr_", "rade_batch_snr_"))]
-EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in SNR_SYMBOLS]
+# The decoder's training step (radae_amd/train.py), a handle of its own: kept out of EXPORTED_SYMBOLS for the same reason.
+TRAIN_SYMBOLS = [n for n in PROTOTYPES["rade_batch.h"] if n.startswith("rade_train_")]
+EXPORTED_SYMBOLS = list(PROTOTYPES["rade_api.h"]) + [n for n in PROTOTYPES["rade_batch.h"] if n not in SC_SYMBOLS and n not in SNR_SYMBOLS and n not in TRAIN_SYMBOLS]
 FILE_STATUS = ("ok", "not acquired", "refine window outside the stream", "timing inside the first cyclic prefix: not decoded", "fewer than two modem frames left: not decoded")   # RADE_FILE_*
 
 _lib = None

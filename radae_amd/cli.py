@@ -15,6 +15,8 @@
     python -m radae_amd.cli rx RX.f32 [--no_bpf] [--acq_test] [--fmax_target HZ] [--acq_time_target S] [--write_Dt FILE]             rx.py --pilots up to the acquisition (no decoding): every frame's pilot search in one device call
     python -m radae_amd.cli chirp OUT.f32 NSEC [--flow HZ] [--fhigh HZ] [--amp A]                                                  chirp.py (host)
     python -m radae_amd.cli specgram IN OUT.png [--fmin HZ] [--fmax HZ]                                                            plot_specgram.m at 8 kHz: the transforms and levels on the device, a grey-scale PNG
+    python -m radae_amd.cli train_decoder MODEL z_hat.f32 features.f32 OUT.bin [--sequence-length 256] [--batch-size 32] [--epochs N] [--lr] [--lr-decay-factor] [--auxdata] [--seed N]
+                                                                                                     the decoder's half of train.py on received latents: forward, loss, BPTT and Adam on the device (rade_train_*)
     python -m radae_amd.cli do_plots RX.f32 [--win N --step N] [--int16 GAIN] [--save_text F]                                      radae_plots.m: do_plots' two printed lines: Pav, PAPR, pilot PAPR, 99 % bandwidth (Welch spectrum and sums on the device)
 
 so that the reference's shell pipelines (`cat features_in.f32 | python3 radae_txe.py > rx.f32`, `cat rx.f32 | python3 radae_rxe.py > features_out.f32`: CMakeLists.txt:300-420) run with
@@ -801,10 +803,39 @@ def _do_plots(argv):
     return 0
 
 
+def _train_decoder(argv):
+    ap = argparse.ArgumentParser(prog="radae_amd.cli train_decoder", description="train.py for the decoder alone, on latents that were received (--write_latent of `rx` and "
+                                 "`inference`) and the features that were sent: sequences of --sequence-length frames as dataset.py cuts them, shuffled batches with the "
+                                 "last ragged one dropped, distortion_loss, Adam with betas (0.8, 0.95) and lr / (1 + decay step); every step runs on the device "
+                                 "(rade_train_dec_step).  Writes a DNNw blob that `rx --decode` and `inference` load.  The shuffle and the aux bits are seeded (the "
+                                 "reference draws them unseeded); no checkpoints, no plots.  NO QUANTISATION NOISE in training: the float weights are quantised to "
+                                 "int8 only when the blob is written, which moves the decoder's output (by about 7 %% of full scale after ten steps from a perturbed "
+                                 "model19), and weights that were exactly 0 move too, so the blob loses the input matrices' block sparsity and grows")
+    ap.add_argument("model", type=str, help="DNNw blob to start from")
+    ap.add_argument("z_hat", type=str, help="received latents, float32 [rows, 80]: one row per 4 feature frames")
+    ap.add_argument("features", type=str, help="the transmitted features, float32 [frames, 36]")
+    ap.add_argument("out", type=str, help="path of the trained DNNw blob")
+    ap.add_argument("--sequence-length", type=int, default=256, help="feature frames per sequence (a multiple of 4), default 256")
+    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--lr-decay-factor", type=float, default=2.5e-5)
+    ap.add_argument("--auxdata", action="store_true", help="train the 21st feature on a +-1 symbol held over 4 frames")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    from . import train
+    try:
+        z, f = train.load_sequences(args.z_hat, args.features, args.sequence_length, args.auxdata, args.seed)
+        train.train_decoder(args.model, z, f, args.out, args.batch_size, args.epochs, args.lr, args.lr_decay_factor, args.seed, log=lambda m: print(m, file=sys.stderr))
+    except ValueError as e:
+        raise SystemExit(f"radae_amd.cli train_decoder: {e}")
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     cmds = {"txe": _txe, "rxe": _rxe, "inference": _inference, "multipath_samples": _multipath_samples, "bbfm_inference": _bbfm_inference, "analog_fm": _analog_fm,
-            "est_cno": _est_cno, "est_snr": _est_snr, "rx": _rx, "chirp": _chirp, "specgram": _specgram, "do_plots": _do_plots}
+            "est_cno": _est_cno, "est_snr": _est_snr, "rx": _rx, "chirp": _chirp, "specgram": _specgram, "do_plots": _do_plots, "train_decoder": _train_decoder}
     if not argv or argv[0] not in cmds:
         print(__doc__, file=sys.stderr)
         return 2
