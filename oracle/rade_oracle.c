@@ -604,9 +604,9 @@ void orc_bpf_run(orc_bpf *b, orc_c32 *out, const orc_c32 *in, int n)
     memcpy(xm, b->mem, sizeof(orc_c32) * ml);
     for (int i = 0; i < n; i++) { pv[i] = cmulf(b->phase, K.bpf_pv[i]); xm[ml + i] = cmulf(in[i], pv[i]); }
     for (int i = 0; i < n; i++) {
-        float ar = 0.0f, ai = 0.0f;
-        for (int k = 0; k < ORC_NTAP; k++) { ar += xm[i + k].re * K.bpf_h[k]; ai += xm[i + k].im * K.bpf_h[k]; }
-        out[i] = cmulf(c32(ar, ai), cconjf_(pv[i]));
+        double ar = 0.0, ai = 0.0;          /* summed in double, rounded once: np.dot's pairwise float32 sum stays within 2 x 2^-24 of sum |h| |x|, a running float32 sum of 101 terms does not (tests/test_bpf_ref_host.py) */
+        for (int k = 0; k < ORC_NTAP; k++) { ar += (double)xm[i + k].re * (double)K.bpf_h[k]; ai += (double)xm[i + k].im * (double)K.bpf_h[k]; }
+        out[i] = cmulf(c32((float)ar, (float)ai), cconjf_(pv[i]));
     }
     int tot = ml + n;
     memmove(b->mem, xm + tot - 102, sizeof(orc_c32) * 102);   /* [-Ntap-1:] */

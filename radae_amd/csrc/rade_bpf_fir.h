@@ -19,6 +19,10 @@ struct BpfLds {                        // 11,264 B: exactly the receiver's xm wo
 // samples shorter: dsp.py:55; entries below o are dropped): thread tid brings head = entry tid (tid < 102) and body[q] = entry 102 + tid + 256 q, ZERO
 // beyond the block -- all loaded by the caller in one batch, so that a workgroup pays one memory round trip for its window and not one per entry.
 // Returns the factor that undoes the operand scales.  Every thread of the 256-thread workgroup calls this (two barriers inside); maxw is an LDS word.
+// What a caller may rely on, X = the window's largest |component| with biased exponent e: both scales are powers of two, so 2^k x gives 2^k y bit for bit while
+// e stays inside the clamp [32, 222], 2^-95 <= X < 2^96, where X lands in [2^7, 2^8) and a plane entry is good to 22 bits above a floor of 2^-32 X.  Below 2^-95 the
+// scale stays 2^102: the floor stays 2^-32 x 2^-95 = 2^-127 absolute, a relative error that grows as the block fades.  Above 2^96 the scale stays 2^-88: the 22 bits
+// hold while every entry is finite in binary16, X < 65520 x 2^88 (just under 2^104); beyond that the block's outputs are infinities and NaNs.  tests/bpf_ref.py counts it.
 #define BPF_NQ 5                       /* body entries per thread: 5 x 256 >= the longest block (1152, the end-of-over frame on the transmit side) */
 __device__ __forceinline__ float bpf_stage_planes(BpfLds *pl, unsigned *maxw, int tid, float2 head, const float2 (&body)[BPF_NQ], int o)
 {
@@ -31,7 +35,7 @@ __device__ __forceinline__ float bpf_stage_planes(BpfLds *pl, unsigned *maxw, in
     if ((tid & 63) == 0) atomicMax(maxw, __float_as_uint(m));
     __syncthreads();
     const int eb = min(max((int)((*maxw >> 23) & 0xffu), 32), 222);
-    const float sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);          // the largest component lands in [2^7, 2^8)
+    const float sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);          // the largest component lands in [2^7, 2^8) (inside the clamp; below 2^7 / at or above 2^8 outside it: see above)
     auto put = [&](int w, float2 v) {
         const float xr = v.x * sc, xi = v.y * sc;
         const _Float16 h0 = (_Float16)xr, h1 = (_Float16)xi;

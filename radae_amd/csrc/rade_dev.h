@@ -566,7 +566,14 @@ int rd_rx_sync_prepare(void);
 
 /* complex_bpf.bpf (dsp.py:63-102) over n samples of every stream in one pass (rade_rx.hip: k_bpf_chain + k_bpf_fir [+ k_bpf_advance]): the receiver's
  * input filter ahead of the receiver launches of an invocation, and the transmitter's optional output filter (radae_txe.py:74-83).  Streams are cut into
- * blocks as the reference cuts them into calls: the first block len0 samples, every later one 960. */
+ * blocks as the reference cuts them into calls: the first block len0 samples, every later one 960.
+ * Contract (tests/test_bpf_units_gpu.py): stream b's y[0, avail) is written, whole blocks and a partial last one alike, and nothing else of y; x is read inside [0, avail)
+ * only.  1 <= len0 <= 1152; a stream with len0 <= 0 or avail <= 0 writes nothing.  chain[b][0] = (len0, mem_len) as integer bits, chain[b][1 + k] = the phase block k
+ * starts from, up to and including the first block beyond the input (every block steps the phase by its WHOLE length, a partial last one too); nothing behind that
+ * and nothing at or past chain_stride is written.  grid_off is cleared for every stream.  advance = 0: nothing else of the state record is written.  advance = 1:
+ * mem <- the last 102 baseband samples of [0, avail), phase <- the chain's entry behind the last block, mem_len <- 102 -- what complex_bpf holds after these calls when
+ * the last block is whole; with avail < 102 or len0 <= 0 the record stays as it was (the reference would shift such a call into its memory: no caller makes one).
+ * One invocation over n blocks and n invocations over one block each, advance = 1, give the same bits in y and in the record. */
 typedef struct {
     rd_bpf_state *state; long state_stride;      /* record of stream b at (char *)state + b * state_stride */
     const int *len0; long len0_stride;           /* first block length of stream b at (char *)len0 + b * len0_stride (the receiver: its nin), or NULL: len0_const */

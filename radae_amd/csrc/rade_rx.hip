@@ -850,6 +850,7 @@ __global__ __launch_bounds__(BPF_NT, 4) void k_bpf_fir(rd_bpf_args a)      // (a
         // this block's last 102 baseband samples are the next block's filter memory
 #pragma unroll
         for (int q = 0; q < BPF_NQ; q++) { const int ti = tid + 256 * q - (n - 102); if (ti >= 0 && ti < 102) tailbuf[ti] = body[q]; }
+        if (n < 102 && tid >= n && tid < 102) tailbuf[tid - n] = head;      // a block shorter than the memory: the rest of it is the end of this block's own memory (uniform; no call of the engine's makes one)
         float2 *dst = rxf + (size_t)b * rxf_stride + sk;
         for (int tile = wave; tile < BPF_TILES(n); tile += BPF_NT / 64) {
             f32x4 re, im;

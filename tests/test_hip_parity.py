@@ -291,10 +291,11 @@ def test_bypass_dec_and_bypass_enc(Engine, torch_dev, golden):
 
 @pytest.mark.parametrize("name", ["slip_plus", "slip_minus", "mpp"])
 def test_bpf_prepass_matches_oracle_filter(engine, torch_dev, golden, oracle, name):
-    """The band-pass filter runs ahead of the receiver kernel for a whole invocation (k_rx_bpf); a stream whose nin changes inside an invocation
+    """The band-pass filter runs ahead of the receiver kernel for a whole invocation (k_bpf_chain + k_bpf_fir); a stream whose nin changes inside an invocation
     (timing slips) filters the rest itself (rx2_bpf_own).  Either way the receiver must have read what complex_bpf.bpf (dsp.py:63-102) produces
     for the stream's actual sequence of calls: compared with the oracle's filter driven with the traced call sizes (float32 rounding of a
-    101-term sum), and bit for bit with the same stream fed one call per invocation (where every call is on the pre-pass's grid)."""
+    101-term sum), and bit for bit with the same stream fed one call per invocation (where every call is on the pre-pass's grid).  tests/test_bpf_units_gpu.py holds
+    the same samples to a float64 model under a per-sample bound; this bar, relative to the peak, stays beside it."""
     import torch
     g = golden("rxtrace_" + name)
     x = g["rx_in"]
