@@ -804,7 +804,7 @@ int rade_acq_stats(const rade_acq_event *events, const rade_acq_refined *refined
                    rade_acq_result *out);
 
 /* ---- stored-file receiver: rx.py past the acquisition (rx.py:107-114 the input band-pass, :197-228 the normal run's refine, trim and mix, :253 the receiver, :260-276 the
- * BER alignment), every stream of a batch in one call each (rade_file.hip).  Geometry: model19_check3's only, as for the acquisition. --------------------------------------
+ * BER alignment), every stream of a batch in one call each (rade_file.hip, rade_irx.hip).  Geometry: model19_check3's only, as for the acquisition. ------------------------
  * rade_batch_bpf_file: complex_bpf(101, Fs, bandwidth, centre, len(x)).bpf(x) of a whole file (dsp.py:63-102, its first and only call): zero memory of 100 samples;
  *   y[i] = conj(E[i]) sum_{t < 101} h[t] (x E)[i - 100 + t], E[i] = e^{-j alpha (i + 1)}, h and alpha the engine's own (rd_tables_fill: bpf_h; float32 as NumPy forms them).
  *   DEVIATION: E[i] is the complex64 nearest to e^{-j alpha (i + 1)} with the argument formed in double (as radae_amd/acq.py: complex_bpf and tests/acq_ref.py: bpf have

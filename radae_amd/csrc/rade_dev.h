@@ -174,8 +174,10 @@ int rd_launch_ofdm_mod_mp(const rd_tables *tab, const float *z, void *tx, long t
 int rd_launch_eoo_build(const rd_tables *tab, const float *bits, float *eoo, int B, rd_stream_t s);
 int rd_launch_copy_eoo(const float *eoo, void *out, long stride, int B, rd_stream_t s);
 
-/* the ideal-timing receiver of RADAE.forward / RADAE.receiver (rade_irx.hip): k_irx_demod per (modem frame, stream), then k_irx_scale per stream
- * when coarse_mag (eq != NONE) or a BER count is asked for */
+/* the fixed-timing receiver of RADAE.forward / RADAE.receiver (rade_irx.hip; the frame body both entries share: irx_frame of rade_irx.h).
+ * rd_irx_args, the ideal-timing call: k_irx_demod per (modem frame, stream), then k_irx_scale per stream when coarse_mag (eq != NONE) or a BER count is asked for.
+ * rd_file_rx_args, the stored-file call (rade_batch_rx_file): k_file_demod + k_file_scale, the same with each stream's own start, frame count and frequency.
+ * rd_file_ber_args (rade_batch_ber_align): k_file_ber, one workgroup per (shift, stream). */
 enum { RD_IRX_LS = 0, RD_IRX_MEAN6 = 1, RD_IRX_ALL = 2, RD_IRX_NONE = 3 };
 typedef struct {
     const rd_tables *tab; const void *rx; long rx_stride;      /* complex64, stream b at rx + b * rx_stride samples, n_mf * 960 readable */
@@ -187,6 +189,25 @@ typedef struct {
     const float *z_ref; long long *n_err;                        /* optional BER count: [B][n_mf * 3][80] reference latents, [B] errors */
 } rd_irx_args;
 int rd_launch_irx(const rd_irx_args *a, rd_stream_t s);
+#define RD_FILE_NSHIFT 20                                        /* rx.py:268: the shifts of the BER alignment, in modem frames */
+typedef struct { long long start; double w; int n_mf, pad; } rd_file_rx_rec;     /* w = 2 pi freq / 8000, 0: the stream is not mixed */
+typedef struct {
+    const rd_tables *tab; const void *x; long x_stride;         /* complex64; stream b reads [start, start + 960 n_mf) of its row */
+    const rd_file_rx_rec *rec;                                  /* device [B] */
+    int max_mf, time_offset, eq, coarse_mag, B;
+    float mag_scale;
+    float *z_hat;                                               /* [B][3 max_mf][80]; rows past 3 n_mf are written as zeros */
+    double *part;                                               /* [B][max_mf] */
+} rd_file_rx_args;
+int rd_launch_file_rx(const rd_file_rx_args *a, rd_stream_t s);
+typedef struct { long long n_ref, n_hat; } rd_file_ber_rec;     /* floats of either side */
+typedef struct {
+    const float *z_ref; long ref_stride; const float *z_hat; long hat_stride;      /* float32, stream b at + b * stride floats */
+    const rd_file_ber_rec *rec;                                 /* device [B] */
+    long long *n_err;                                           /* device [B][RD_FILE_NSHIFT] */
+    int B;
+} rd_file_ber_args;
+int rd_launch_file_ber(const rd_file_ber_args *a, rd_stream_t s);
 
 /* time-aligned distortion loss of every stream (rade_loss.hip: loss.py:find_loss :64-91 over distortion_loss, radae_base.py:50-68, first 20 features):
  * k_loss_offsets per (block of RD_LOSS_WG offsets, stream), k_loss_pick per stream, k_loss_frames per (256 frames, stream) when frame_loss is given */
@@ -428,14 +449,12 @@ typedef struct {
 } rd_acq_refine_args;
 int rd_launch_acq_refine(const rd_acq_refine_args *a, rd_stream_t s);
 
-/* the stored-file receiver past the acquisition, rade_batch_bpf_file / _rx_file / _ber_align (rade_file.hip; include/rade_batch.h states the arithmetic).
+/* the whole-file band-pass of the stored-file receiver, rade_batch_bpf_file (rade_file.hip; include/rade_batch.h states the arithmetic).
  * k_file_phase + k_file_bpf: complex_bpf.bpf of a whole file; a workgroup of four wavefronts takes RD_FILE_SPAN consecutive outputs of one stream, RD_FILE_CHUNK at a
- * time (one 256-output tile of rade_bpf_fir.h per wavefront).  k_file_demod + k_file_scale: k_irx_demod / k_irx_scale with each stream's own start, frame count and
- * frequency.  k_file_ber: one workgroup per (shift, stream). */
+ * time (one 256-output tile of rade_bpf_fir.h per wavefront).  The demodulator and the BER alignment behind it: rd_file_rx_args, rd_file_ber_args above. */
 #define RD_FILE_CHUNK 1024
 #define RD_FILE_NCHUNK 8
 #define RD_FILE_SPAN (RD_FILE_CHUNK * RD_FILE_NCHUNK)
-#define RD_FILE_NSHIFT 20                                        /* rx.py:268: the shifts of the BER alignment, in modem frames */
 typedef struct {
     const unsigned short *bpf16;                                /* rd_bpf16_table_fill(): the taps as matrix-core operands */
     const void *x; long x_stride; void *y; long y_stride;       /* complex64, stream b at + b * stride samples */
@@ -445,24 +464,6 @@ typedef struct {
     int B, max_n;
 } rd_file_bpf_args;
 int rd_launch_file_bpf(const rd_file_bpf_args *a, rd_stream_t s);
-typedef struct { long long start; double w; int n_mf, pad; } rd_file_rx_rec;     /* w = 2 pi freq / 8000, 0: the stream is not mixed */
-typedef struct {
-    const rd_tables *tab; const void *x; long x_stride;         /* complex64; stream b reads [start, start + 960 n_mf) of its row */
-    const rd_file_rx_rec *rec;                                  /* device [B] */
-    int max_mf, time_offset, eq, coarse_mag, B;
-    float mag_scale;
-    float *z_hat;                                               /* [B][3 max_mf][80]; rows past 3 n_mf are written as zeros */
-    double *part;                                               /* [B][max_mf] */
-} rd_file_rx_args;
-int rd_launch_file_rx(const rd_file_rx_args *a, rd_stream_t s);
-typedef struct { long long n_ref, n_hat; } rd_file_ber_rec;     /* floats of either side */
-typedef struct {
-    const float *z_ref; long ref_stride; const float *z_hat; long hat_stride;      /* float32, stream b at + b * stride floats */
-    const rd_file_ber_rec *rec;                                 /* device [B] */
-    long long *n_err;                                           /* device [B][RD_FILE_NSHIFT] */
-    int B;
-} rd_file_ber_args;
-int rd_launch_file_ber(const rd_file_ber_args *a, rd_stream_t s);
 
 typedef struct {
     const rd_tables *tab; const void *tx; long tx_stride; void *rx; long rx_stride;

@@ -843,37 +843,6 @@ int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *fea
     return e ? -1 : n_steps;
 }
 
-/* ---- the ideal-timing receiver (radae.py:312-420, :590-657) ---------------------------------------------------------------- */
-int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n_mf, const rade_ideal_rx_params *p,
-                        float *z_hat_dev, float *features_out_dev, void *stream)
-{
-    ON_DEV(h);
-    if (!h || !rx_dev || !p || !z_hat_dev || n_mf < 2 || rx_stride < (long)n_mf * RD_NMF || p->time_offset < -RD_NCP || p->time_offset > 0 ||
-        p->eq < RADE_EQ_LS || p->eq > RADE_EQ_NONE || (features_out_dev && 3 * n_mf > h->Tcap) || (p->n_errors_host && !p->z_ref_dev)) return -1;
-    if (features_out_dev && misaligned16(z_hat_dev)) return -1;  /* the decoder then reads z_hat_dev as rade_batch_decode does: f32x4 A rows */
-    const int B = h->B;
-    hipStream_t st = (hipStream_t)stream;
-    if (dev_grow(h, &h->irx_part, &h->irx_part_cap, n_mf, sizeof(double) * B, 1) || dev_grow(h, &h->irx_foff, NULL, 2 * B, sizeof(float), 1) || dev_grow(h, &h->irx_err, NULL, B, sizeof(long long), 1)) return -1;
-    if (p->freq_offset_host) {
-        const void *src[2] = { p->freq_offset_host, p->df_dt_host };
-        if (stage_rows(h, &h->irx_foff_host, h->irx_foff, 2, src, NULL, 1, st)) return -1;
-    }
-    rd_irx_args a;
-    memset(&a, 0, sizeof a);
-    a.tab = h->d_tab; a.rx = rx_dev; a.rx_stride = rx_stride; a.foff = p->freq_offset_host ? h->irx_foff : NULL;
-    a.n_mf = n_mf; a.time_offset = p->time_offset; a.eq = p->eq; a.coarse_mag = p->coarse_mag; a.B = B;
-    a.mag_scale = h->tx_linear ? 1.0f : (float)(sqrt(2.0) / ((pow(10.0, -2.0 / 20.0) * RD_M) / sqrt((double)RD_NC)));   /* |P[0]| / pilot_gain, radae.py:196-199, :379-380 */
-    a.z_hat = z_hat_dev; a.part = h->irx_part; a.z_ref = p->z_ref_dev; a.n_err = p->z_ref_dev ? h->irx_err : NULL;
-    if (rd_launch_irx(&a, stream)) return -1;
-    if (p->n_errors_host) {
-        const long long *e = read_back(h, h->irx_err, sizeof(long long) * B, st);
-        if (!e) return -1;
-        for (int b = 0; b < B; b++) p->n_errors_host[b] = (long)e[b];
-    }
-    if (features_out_dev && rade_batch_decode(h, z_hat_dev, 3 * n_mf, features_out_dev, 1, stream) != 3 * n_mf) return -1;
-    return n_mf;
-}
-
 /* ---- loss.py:find_loss of every stream (rade_loss.hip) ------------------------------------------------------------------------ */
 int rade_batch_loss(rade_batch *h, const float *features_dev, long f_stride, int f_row, const int *n_in_host,
                     const float *hat_dev, long h_stride, int h_row, const int *n_hat_host,

@@ -45,7 +45,6 @@ struct rade_batch {
     /* optional Tx band-pass filter + clip (RADE_BATCH_TX_BPF; radae_txe.py:74-83): filter state per stream, its initial value, the modulator's raw output, block phases */
     int bypass_dec;                          /* RADE_BATCH_BYPASS_DEC */
     int tx_linear;                           /* RADE_BATCH_TX_LINEAR */
-    double *irx_part; long irx_part_cap; float *irx_foff; void *irx_foff_host; long long *irx_err;   /* rade_batch_rx_ideal: per-frame pilot power [B][cap], offsets [2][B] and their pinned staging copy, error counts [B] */
     rd_bpf_state *tx_bpf, *tx_bpf_init; void *tx_raw; float *tx_chain; float *eoo_filt;   /* eoo_filt [B][Neoo] c64: the end-of-over frame as transmitted (filtered + clipped) for the channel's with_eoo */
     void *chan_scratch; void *chan_mp;        /* chan_mp [B][max_tx_mf * 960] c64: multipath output of the fused modulator (rade_batch_tx_channel), allocated on first use */
     float *chan_ps; void *chan_ps_host;       /* rade_channel_streams: [3][B] sigma, freq_offset, df_dt on the device and its pinned staging copy, allocated on first use */

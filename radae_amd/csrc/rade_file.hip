@@ -1,10 +1,8 @@
 // rade_file.hip -- the stored-file receiver past the acquisition, rx.py:107-114 and :223-276 for every stream of a batch at once (include/rade_batch.h, "stored-file
-// receiver: rx.py past the acquisition", states the arithmetic, the contract and the error bound): rade_batch_bpf_file, rade_batch_rx_file, rade_batch_ber_align.
+// receiver: rx.py past the acquisition", states the arithmetic, the contract and the error bound): the whole-file filter of rade_batch_bpf_file.  The demodulator and
+// the BER alignment behind it (rade_batch_rx_file, rade_batch_ber_align) are the fixed-timing receiver's, rade_irx.hip.
 //   k_file_phase   the mixer's phases e^{-j alpha (i + 1)} of one call: double sincos, rounded once to complex64, one table for all streams
 //   k_file_bpf     complex_bpf(101, ..).bpf(x) of a whole file: a workgroup of four wavefronts takes RD_FILE_SPAN consecutive outputs of one stream
-//   k_file_demod   k_irx_demod (rade_irx.hip) with the stream's own first sample, frame count and frequency; one workgroup per (modem frame, stream)
-//   k_file_scale   k_irx_scale's coarse_mag over the stream's own frames
-//   k_file_ber     rx.py:268-276: one workgroup per (shift, stream) counts the sign errors
 // The filter.  The FIR is the project's one FIR arithmetic (rade_bpf_fir.h): per chunk of RD_FILE_CHUNK = 1024 outputs the window [100 earlier baseband samples | the
 // chunk mixed down] is staged as binary16 planes (bpf_stage_planes in its first-call form, o = 2: a whole file is ONE call of complex_bpf, whose memory is Ntap - 1
 // zeros), each wavefront forms one 256-output tile on the matrix cores (bpf_fir_tile), mixes it back up and stores it.  As in k_bpf_fir the loop is built around the
@@ -18,7 +16,6 @@
 #include "rade_dev.h"
 #include "rade_devutil.h"
 #include "rade_bpf_fir.h"
-#include "rade_irx.h"
 
 #define FILE_NT 256
 static_assert(RD_FILE_CHUNK == 4 * 256 && FILE_NT == 256, "one 256-output tile per wavefront and chunk");
@@ -108,110 +105,6 @@ __global__ __launch_bounds__(FILE_NT, 4) void k_file_bpf(rd_file_bpf_args a)
     }
 }
 
-// k_irx_demod of rade_irx.hip, statement for statement, for a stream that starts at its own sample, has its own number of frames and is mixed down by its own frequency
-// (rx.py:223-228: rx[tmax - Ncp:] * exp(-1j w arange(len)), phase and product in double, rounded once).  Frames past the stream's own are written as zeros.
-__global__ __launch_bounds__(192) void k_file_demod(rd_file_rx_args a)
-{
-    __shared__ float2 x[IRX_NSYM][RD_M];
-    __shared__ float2 sym[IRX_NSYM][RD_NC];
-    __shared__ float2 rp[2][RD_NC];
-    const int mf = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const rd_tables *tab = a.tab;
-    const rd_file_rx_rec rec = a.rec[b];
-    float *zf = a.z_hat + ((size_t)b * a.max_mf + mf) * RD_ZMF;
-    if (mf >= rec.n_mf) {
-        if (tid < RD_NS * RD_NC) { zf[2 * tid] = 0.0f; zf[2 * tid + 1] = 0.0f; }
-        if (tid == 0) a.part[(size_t)b * a.max_mf + mf] = 0.0;
-        return;
-    }
-    const bool last = mf == rec.n_mf - 1;
-    const float2 *rx = (const float2 *)a.x + (size_t)b * a.x_stride + rec.start;
-    for (int i = tid; i < IRX_NSYM * RD_M; i += 192) {
-        const int s = i / RD_M, k = i - s * RD_M;
-        const int fr = s < RD_NS + 1 ? mf : (last ? mf - 1 : mf + 1);
-        const int n = fr * RD_NMF + (s < RD_NS + 1 ? s : 0) * RD_SYM + RD_NCP + a.time_offset + k;
-        float2 v = rx[n];
-        if (rec.w != 0.0) {
-            double sn, cs; sincos(rec.w * (double)n, &sn, &cs);   // e^{-j w n} = (cs, -sn), n counted from the stream's start
-            const double vr = (double)v.x * cs + (double)v.y * sn, vi = (double)v.y * cs - (double)v.x * sn;
-            v = make_float2((float)vr, (float)vi);
-        }
-        x[s][k] = v;
-    }
-    __syncthreads();
-    if (tid < IRX_NSYM * RD_NC) {                                    // rx_sym = rx_dash Wfwd
-        const int s = tid / RD_NC, c = tid - s * RD_NC;
-        float re = 0.0f, im = 0.0f;
-        for (int k = 0; k < RD_M; k++) {
-            const float2 v = x[s][k], w = ld2(tab->Wfwd[k], c);
-            re = fmaf(v.x, w.x, re); re = fmaf(-v.y, w.y, re);
-            im = fmaf(v.x, w.y, im); im = fmaf(v.y, w.x, im);
-        }
-        sym[s][c] = make_float2(re, im);
-    }
-    __syncthreads();
-    if (a.eq != RD_IRX_NONE && tid < 2 * RD_NC) {
-        const int i = tid / RD_NC, c = tid - i * RD_NC;
-        rp[i][c] = irx_pilot(tab, sym[i ? RD_NS + 1 : 0], c, a.eq);
-    }
-    __syncthreads();
-    if (tid == 0) {                                                  // coarse_mag: this frame's share of mean |rx_pilots|^2
-        double p = 0.0;
-        if (a.eq != RD_IRX_NONE) for (int c = 0; c < RD_NC; c++) p += (double)rp[0][c].x * rp[0][c].x + (double)rp[0][c].y * rp[0][c].y;
-        a.part[(size_t)b * a.max_mf + mf] = p;
-    }
-    if (tid < RD_NS * RD_NC) {
-        const int s = tid / RD_NC, c = tid - s * RD_NC;
-        float2 v = sym[1 + s][c];
-        if (a.eq != RD_IRX_NONE) {
-            const float2 d = last ? make_float2(rp[0][RD_NC - 1].x - rp[1][RD_NC - 1].x, rp[0][RD_NC - 1].y - rp[1][RD_NC - 1].y)
-                                  : make_float2(rp[1][c].x - rp[0][c].x, rp[1][c].y - rp[0][c].y);
-            const float2 slope = make_float2(d.x / (float)(RD_NS + 1), d.y / (float)(RD_NS + 1));
-            const float2 ch = make_float2(slope.x * (float)(s + 1) + rp[0][c].x, slope.y * (float)(s + 1) + rp[0][c].y);
-            float sn, cs; sincosf(atan2f(ch.y, ch.x), &sn, &cs);
-            v = cmul(v, make_float2(cs, -sn));
-        }
-        zf[2 * tid] = v.x; zf[2 * tid + 1] = v.y;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_file_scale(rd_file_rx_args a)
-{
-    __shared__ double red[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n_mf = a.rec[b].n_mf;
-    if (n_mf <= 0) return;                                        // uniform
-    double p = 0.0;
-    for (int i = tid; i < n_mf; i += 256) p += a.part[(size_t)b * a.max_mf + i];
-    p = wave_sum_f64(p);
-    if ((tid & 63) == 0) red[tid >> 6] = p;
-    __syncthreads();
-    const double tot = ((red[0] + red[1]) + red[2]) + red[3];
-    const float mag = sqrtf((float)(tot / ((double)n_mf * RD_NC))) * a.mag_scale;
-    float *z = a.z_hat + (size_t)b * a.max_mf * RD_ZMF;
-    for (int i = tid; i < n_mf * RD_ZMF; i += 256) z[i] = z[i] / mag;
-}
-
-// rx.py:268-276 for shift f = blockIdx.x of stream blockIdx.y: the sign errors of z_hat against z_ref[240 f:] over the shorter of the two.  Integer counts: a thread's
-// own, the wavefront's by a fixed exchange pattern, the four wavefronts in ascending order.  A shift that leaves no reference symbol gets -1.
-__global__ __launch_bounds__(256) void k_file_ber(rd_file_ber_args a)
-{
-    __shared__ long long cnt[4];
-    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const rd_file_ber_rec rec = a.rec[b];
-    const long long off = (long long)RD_ZMF * f, left = rec.n_ref - off;
-    long long *out = a.n_err + (size_t)b * RD_FILE_NSHIFT + f;
-    if (left <= 0) { if (tid == 0) *out = -1; return; }
-    const long long n_syms = left < rec.n_hat ? left : rec.n_hat;
-    const float *zr = a.z_ref + (size_t)b * a.ref_stride + off, *zh = a.z_hat + (size_t)b * a.hat_stride;
-    int e = 0;
-    for (long long i = tid; i < n_syms; i += 256) if (-zr[i] * zh[i] > 0.0f) e++;
-    for (int o = 32; o > 0; o >>= 1) e += __shfl_down(e, o);
-    if ((tid & 63) == 0) cnt[tid >> 6] = e;
-    __syncthreads();
-    if (tid == 0) *out = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3];
-}
-
 extern "C" int rd_launch_file_bpf(const rd_file_bpf_args *a, rd_stream_t s)
 {
     if (a->B <= 0 || a->max_n <= 0) return 0;
@@ -219,21 +112,5 @@ extern "C" int rd_launch_file_bpf(const rd_file_bpf_args *a, rd_stream_t s)
     hipLaunchKernelGGL(k_file_phase, dim3((unsigned)((a->n_phase + 255) / 256)), dim3(256), 0, (hipStream_t)s, *a);
     if (hipGetLastError() != hipSuccess) return -1;
     hipLaunchKernelGGL(k_file_bpf, dim3((a->max_n + RD_FILE_SPAN - 1) / RD_FILE_SPAN, a->B), dim3(FILE_NT), 0, (hipStream_t)s, *a);
-    return (int)hipGetLastError();
-}
-
-extern "C" int rd_launch_file_rx(const rd_file_rx_args *a, rd_stream_t s)
-{
-    if (a->B <= 0 || a->max_mf <= 0) return 0;
-    if (a->time_offset < -RD_NCP || a->time_offset > 0 || a->eq < RD_IRX_LS || a->eq > RD_IRX_NONE || !a->z_hat || !a->part || !a->rec) return -1;
-    hipLaunchKernelGGL(k_file_demod, dim3(a->max_mf, a->B), dim3(192), 0, (hipStream_t)s, *a);
-    if (a->coarse_mag && a->eq != RD_IRX_NONE) hipLaunchKernelGGL(k_file_scale, dim3(a->B), dim3(256), 0, (hipStream_t)s, *a);
-    return (int)hipGetLastError();
-}
-
-extern "C" int rd_launch_file_ber(const rd_file_ber_args *a, rd_stream_t s)
-{
-    if (a->B <= 0) return 0;
-    hipLaunchKernelGGL(k_file_ber, dim3(RD_FILE_NSHIFT, a->B), dim3(256), 0, (hipStream_t)s, *a);
     return (int)hipGetLastError();
 }

@@ -1,6 +1,6 @@
 /*
  * rade_stages.c -- the front-end stage calls of the batched engine (include/rade_batch.h): the rate-Rs channel, the fractional resampler, the int16 wire, the rational
- * rate converter, analog FM, the channel and the Doppler generator in pieces, the chirp header's C/No, the trials of the pilot SNR estimator, the spectrogram, the whole-file pilot acquisition and the stored-file receiver behind it.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
+ * rate converter, analog FM, the channel and the Doppler generator in pieces, the chirp header's C/No, the trials of the pilot SNR estimator, the spectrogram, the whole-file pilot acquisition, the stored-file receiver behind it and the ideal-timing receiver that shares its demodulator.  Plain C host code: each entry point checks every stream, puts the call's per-stream values on the device and
  * launches its kernel through the shim in rade_dev.h.  What these calls keep between calls is struct rd_stages, made by the first of them and opaque to rade_engine.c;
  * its device and pinned memory is on the engine's own list (rade_engine.h).
  *
@@ -103,10 +103,12 @@ struct rd_stages {
     rd_pair acq_n; double *acq_psum; rd_acq_pmax *acq_pmax; rd_acq_rec *acq_rec; long acq_cap, acq_cap1, acq_cap2;
     rd_pair acq_ev; rd_acq_fine *acq_fine; double *acq_dfine;
     /* rade_batch_bpf_file: the [B] sample counts; the call's mixer phases [file_phase_cap][2], grown with the call (scratch: made again by every call).
-     * rade_batch_rx_file: the [B] stream records; [B][file_part_cap] pilot powers.  rade_batch_ber_align: the [B] lengths; [B][RD_FILE_NSHIFT] counts */
+     * rade_batch_rx_file: the [B] stream records; [B][file_part_cap] pilot powers.  rade_batch_ber_align: the [B] lengths; [B][RD_FILE_NSHIFT] counts.
+     * rade_batch_rx_ideal: the [2][B] frequency offsets and drifts; [B][irx_part_cap] pilot powers; [B] error counts */
     rd_pair file_n; float *file_phase; long file_phase_cap;
     rd_pair file_rx; double *file_part; long file_part_cap;
     rd_pair file_ber; long long *file_err;
+    rd_pair irx_foff; double *irx_part; long irx_part_cap; long long *irx_err;
 };
 static struct rd_stages *stages_of(rade_batch *h)
 {
@@ -957,8 +959,8 @@ int rade_batch_acq_refine(rade_batch *h, const void *x_dev, long x_stride, const
     return 0;
 }
 
-/* ---- the stored-file receiver past the acquisition: the whole-file band-pass, the plan, the ragged fixed-timing demodulator and the BER alignment of rx.py (rade_file.hip;
- * include/rade_batch.h states the arithmetic) --------------------------------------------------------------------------------------------------------------------- */
+/* ---- the stored-file receiver past the acquisition: the whole-file band-pass (rade_file.hip) and the plan of rx.py; its ragged demodulator and BER alignment follow with
+ * the fixed-timing receiver (include/rade_batch.h states the arithmetic) --------------------------------------------------------------------------------------------------------------------- */
 _Static_assert(RADE_FILE_BPF_SPAN == RD_FILE_SPAN && RD_FILE_CHUNK == 1024, "the header's span is the kernel's (rade_file.hip: a chunk is four tiles of 256)");
 /* complex_bpf's mixer step as rd_tables_fill forms it (rade_host.c: float32 like NumPy), as a double */
 static double file_bpf_alpha(void)
@@ -1023,13 +1025,66 @@ int rade_file_plan(long long n, int hop, long long t, double f, const double *fr
     return 0;
 }
 
+/* ---- the fixed-timing receiver (radae.py:312-420, :590-657; rade_irx.hip): the ideal-timing call and the stored-file call side by side.  What the two share -------- */
+/* what both refuse: a DFT window outside its symbol, an unknown EQ and, where the call decodes, more rows than the decoder holds or a z_hat_dev the decoder cannot read
+ * (as rade_batch_decode does: f32x4 A rows) */
+static int fixed_rx_bad(const rade_batch *h, int n_mf, int time_offset, int eq, const float *z_hat_dev, const float *features_out_dev)
+{
+    if (time_offset < -RD_NCP || time_offset > 0 || eq < RADE_EQ_LS || eq > RADE_EQ_NONE) return 1;
+    return features_out_dev && (3 * n_mf > h->Tcap || ((uintptr_t)z_hat_dev & 15));
+}
+/* the coarse_mag factor: |P[0]| / pilot_gain (radae.py:196-199, :379-380), 1 for the bottleneck-1 waveform */
+static float fixed_rx_mag_scale(const rade_batch *h)
+{
+    return h->tx_linear ? 1.0f : (float)(sqrt(2.0) / ((pow(10.0, -2.0 / 20.0) * RD_M) / sqrt((double)RD_NC)));
+}
+/* the decode tail: every stream's 3 n_mf rows of z_hat through the stateless decoder, from a zero state */
+static int fixed_rx_decode(rade_batch *h, const float *z_hat_dev, int n_mf, float *features_out_dev, void *stream)
+{
+    return rade_batch_decode(h, z_hat_dev, 3 * n_mf, features_out_dev, 1, stream) == 3 * n_mf ? 0 : -1;
+}
+
+/* waits for the stream only where a BER count is read back (and, ahead of the launch, where per-stream offsets are put on the device) */
+int rade_batch_rx_ideal(rade_batch *h, const void *rx_dev, long rx_stride, int n_mf, const rade_ideal_rx_params *p,
+                        float *z_hat_dev, float *features_out_dev, void *stream)
+{
+    ON_DEV(h);
+    if (!h || !rx_dev || !p || !z_hat_dev || n_mf < 2 || rx_stride < (long)n_mf * RD_NMF || (p->n_errors_host && !p->z_ref_dev)) return -1;
+    if (fixed_rx_bad(h, n_mf, p->time_offset, p->eq, z_hat_dev, features_out_dev)) return -1;
+    const int B = h->B;
+    hipStream_t st = (hipStream_t)stream;
+    struct rd_stages *s = stages_of(h);
+    if (!s || dev_grow(h, &s->irx_part, &s->irx_part_cap, n_mf, sizeof(double) * B, 1) || dev_grow(h, &s->irx_err, NULL, B, sizeof(long long), 1)) return -1;
+    if (p->freq_offset_host) {             /* [2][B]: freq_offset, then df_dt (zeros without) */
+        float *fo = pair_host(h, &s->irx_foff, sizeof(float) * 2 * B);
+        if (!fo) return -1;
+        memcpy(fo, p->freq_offset_host, sizeof(float) * B);
+        if (p->df_dt_host) memcpy(fo + B, p->df_dt_host, sizeof(float) * B); else memset(fo + B, 0, sizeof(float) * B);
+        if (pair_push(h, &s->irx_foff, sizeof(float) * 2 * B, 1, st)) return -1;
+    }
+    rd_irx_args a;
+    memset(&a, 0, sizeof a);
+    a.tab = h->d_tab; a.rx = rx_dev; a.rx_stride = rx_stride; a.foff = p->freq_offset_host ? s->irx_foff.dev : NULL;
+    a.n_mf = n_mf; a.time_offset = p->time_offset; a.eq = p->eq; a.coarse_mag = p->coarse_mag; a.B = B;
+    a.mag_scale = fixed_rx_mag_scale(h);
+    a.z_hat = z_hat_dev; a.part = s->irx_part; a.z_ref = p->z_ref_dev; a.n_err = p->z_ref_dev ? s->irx_err : NULL;
+    if (rd_launch_irx(&a, stream)) return -1;
+    if (p->n_errors_host) {
+        const long long *e = read_back(h, s->irx_err, sizeof(long long) * B, st);
+        if (!e) return -1;
+        for (int b = 0; b < B; b++) p->n_errors_host[b] = (long)e[b];
+    }
+    if (features_out_dev && fixed_rx_decode(h, z_hat_dev, n_mf, features_out_dev, stream)) return -1;
+    return n_mf;
+}
+
+/* always settles: the staging copy of the stream records is free again when it returns */
 int rade_batch_rx_file(rade_batch *h, const void *x_dev, long x_stride, const rade_file_rx_in *in_host, int max_mf, int time_offset, int eq, int coarse_mag,
                        float *z_hat_dev, float *features_out_dev, void *stream)
 {
     ON_DEV(h);
     if (!h || !x_dev || !in_host || !z_hat_dev || max_mf < 1 || x_stride < 0 || ((uintptr_t)x_dev & 7) || ((uintptr_t)z_hat_dev & 3) || ((uintptr_t)features_out_dev & 3)) return -1;
-    if (time_offset < -RD_NCP || time_offset > 0 || eq < RADE_EQ_LS || eq > RADE_EQ_NONE) return -1;
-    if (features_out_dev && (3 * max_mf > h->Tcap || ((uintptr_t)z_hat_dev & 15))) return -1;       /* the decoder reads z_hat_dev as rade_batch_decode does: f32x4 A rows */
+    if (fixed_rx_bad(h, max_mf, time_offset, eq, z_hat_dev, features_out_dev)) return -1;
     const int B = h->B;
     hipStream_t st = (hipStream_t)stream;
     for (int b = 0; b < B; b++) {          /* every stream is checked before anything is launched or written */
@@ -1049,12 +1104,12 @@ int rade_batch_rx_file(rade_batch *h, const void *x_dev, long x_stride, const ra
     rd_file_rx_args a;
     memset(&a, 0, sizeof a);
     a.tab = h->d_tab; a.x = x_dev; a.x_stride = x_stride; a.rec = s->file_rx.dev; a.max_mf = max_mf; a.time_offset = time_offset; a.eq = eq; a.coarse_mag = coarse_mag; a.B = B;
-    a.mag_scale = h->tx_linear ? 1.0f : (float)(sqrt(2.0) / ((pow(10.0, -2.0 / 20.0) * RD_M) / sqrt((double)RD_NC)));   /* as rade_batch_rx_ideal: |P[0]| / pilot_gain */
+    a.mag_scale = fixed_rx_mag_scale(h);
     a.z_hat = z_hat_dev; a.part = s->file_part;
     PROF_BEGIN(h, stream);
     int e = rd_launch_file_rx(&a, stream);
     PROF_END(h, stream, RADE_PROF_CHAN, 8.0 * RD_M * RD_NC * (RD_NS + 2) * (double)max_mf * B);
-    if (!e && features_out_dev && rade_batch_decode(h, z_hat_dev, 3 * max_mf, features_out_dev, 1, stream) != 3 * max_mf) e = -1;
+    if (!e && features_out_dev) e = fixed_rx_decode(h, z_hat_dev, max_mf, features_out_dev, stream);
     return (settle(st) || e) ? -1 : max_mf;
 }
 

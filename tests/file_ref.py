@@ -92,8 +92,10 @@ def mix(x, start, freq, bug=None):
     return (y * np.exp(-1j * (2 * np.pi * freq / FS) * m)).astype(np.complex64) if freq != 0 else y.astype(np.complex64)
 
 
-def demod(rx, eq="ls", coarse_mag=True, time_offset=-16, bottleneck=3, n_mf=None):
-    """RADAE.receiver up to z_hat with do_pilot_eq for the four EQ modes, in complex128: [3 n_mf, 80]"""
+def demod(rx, eq="ls", coarse_mag=True, time_offset=-16, bottleneck=3, n_mf=None, quirk=True):
+    """RADAE.receiver up to z_hat, the project's one NumPy restatement of it (complex128): cyclic prefix removal, DFT, do_pilot_eq for the four EQ modes, coarse_mag at
+    both bottleneck scalings, the demapper: [3 n_mf, 80].  Every frame but the last interpolates towards the next frame's pilot; the last one reuses the loop's final
+    slope (carrier Nc - 1, frame n_mf - 2) for every carrier.  quirk = False: what a per-carrier last slope would give (tests/test_ideal_rx_host.py pins the quirk)"""
     c = consts()
     P, Wfwd, w = c["P"].real.astype(np.float64), c["Wfwd"].astype(np.complex128), c["w"].astype(np.float64)
     n_mf = (len(rx) // (M + NCP)) // (NS + 1) if n_mf is None else n_mf
@@ -115,7 +117,10 @@ def demod(rx, eq="ls", coarse_mag=True, time_offset=-16, bottleneck=3, n_mf=None
                 rp[:, c_] = g[:, 0] + g[:, 1] * np.exp(-1j * w[c_] * a)
         s = np.arange(1, NS + 1)
         for i in range(n_mf):
-            slope = (rp[i + 1] - rp[i]) / (NS + 1) if i < n_mf - 1 else np.full(NC, (rp[i, NC - 1] - rp[i - 1, NC - 1]) / (NS + 1))      # the last frame's quirk
+            if i < n_mf - 1:
+                slope = (rp[i + 1] - rp[i]) / (NS + 1)
+            else:
+                slope = np.full(NC, (rp[i, NC - 1] - rp[i - 1, NC - 1]) / (NS + 1)) if quirk else (rp[i] - rp[i - 1]) / (NS + 1)
             sym[i, 1:] *= np.exp(-1j * np.angle(slope[None, :] * s[:, None] + rp[i][None, :]))
         if coarse_mag:
             mag = np.sqrt(np.mean(np.abs(rp) ** 2))
@@ -148,7 +153,9 @@ def ber_align(z, z_hat, bug=None):
 
 
 def check_z(z, ref, what):
-    """the rule of tests/test_ideal_rx_gpu.py: RMS within 1e-5 of the latents' own scale, signs equal wherever |ref| > 1e-3"""
+    """the rule both fixed-timing receivers' latents are held to: RMS within 1e-5 of the latents' own scale (1e-5 absolute for unit-scale latents), signs equal wherever
+    |ref| > 1e-3.  Bottleneck-3 latents without a unit magnitude (no coarse_mag; coarse_mag of model19's waveform leaves an RMS of ~23) are compared relative to their
+    RMS: the reference computed them in float32, and an exact (float64) restatement misses them by 1.2e-5 absolute already (tests/test_ideal_rx_host.py)"""
     z = np.asarray(z, np.float64); ref = np.asarray(ref, np.float64)
     assert z.shape == ref.shape, (what, z.shape, ref.shape)
     rms = float(np.sqrt(np.mean((z - ref) ** 2)))

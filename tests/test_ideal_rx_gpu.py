@@ -8,22 +8,11 @@ import sys
 import numpy as np
 import pytest
 
+from file_ref import check_z
 from gpu_kit import REPO, engine, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 M05 = os.path.join(REPO, "weights", "model05.bin")
-
-
-def check_z(z, ref, what):
-    """RMS within 1e-5 of the latents' own scale (1e-5 absolute for unit-scale latents), signs equal wherever |ref| > 1e-3.  Bottleneck-3 latents without a
-    unit magnitude (no coarse_mag; coarse_mag of model19's waveform leaves an RMS of ~23) are compared relative to their RMS: the reference computed
-    them in float32, and an exact (float64) restatement misses them by 1.2e-5 absolute already (tests/test_ideal_rx_host.py)."""
-    z = np.asarray(z, np.float64); ref = np.asarray(ref, np.float64)
-    assert z.shape == ref.shape, what
-    rms = float(np.sqrt(np.mean((z - ref) ** 2)))
-    assert rms <= 1e-5 * max(1.0, float(np.sqrt(np.mean(ref ** 2)))), (what, rms)
-    big = np.abs(ref) > 1e-3
-    assert np.array_equal(np.sign(z[big]), np.sign(ref[big])), what
 
 
 @pytest.mark.parametrize("case", ["awgn", "mpp"])
@@ -105,6 +94,24 @@ def test_batch_streams_are_independent(engine, torch_dev, golden):
         assert torch.equal(z1[0], z_hat[b]), b
         assert int(e1[0]) == int(n_err[b])
         assert int(n_err[b]) == int((-z_ref[b] * z_hat[b] > 0).sum())
+
+
+def test_rx_ideal_error_count_equals_ber_align_shift_0(engine, torch_dev, golden):
+    """B = 2, two modem frames, random sign latents as the reference: the count rade_batch_rx_ideal reads back is rade_batch_ber_align's at shift 0 on the same z_hat
+    (one workgroup count behind both), and both are NumPy's.  Integers: no tolerance"""
+    import torch
+    rx_np = golden("chan_mpp")["rx"]
+    B, n_mf = 2, 2
+    rx = torch.tensor(np.stack([rx_np[:n_mf * 960], np.roll(rx_np, 960 * 3)[:n_mf * 960]]), device=torch_dev)
+    z_ref = torch.tensor(np.sign(np.random.default_rng(31).standard_normal((B, 3 * n_mf, 80))).astype(np.float32), device=torch_dev)
+    eng = engine(B, max_tx_mf=n_mf)
+    _, z_hat, n_err = eng.rx_ideal(rx, n_mf, z_ref=z_ref, feat_width=0)
+    shifts = eng.ber_align(z_ref, z_hat)
+    want = np.sum(-z_ref.cpu().numpy() * z_hat.cpu().numpy() > 0, axis=(1, 2))
+    print("n_errors", n_err.tolist(), "ber_align shift 0", shifts[:, 0].tolist(), "numpy", want.tolist())
+    assert 0 < want.min() and want.max() < 3 * n_mf * 80            # (a count that could not tell the two sides apart would be 0 or all)
+    for b in range(B):
+        assert int(n_err[b]) == int(shifts[b, 0]) == int(want[b]), b
 
 
 def ber_run(torch_dev, EbNodB, freq_offset, mpp, B=64, n_mf=72, seed=9):

@@ -1,4 +1,4 @@
-"""The stored-file receiver past the acquisition on the device (rade_file.hip: rade_batch_bpf_file, rade_batch_rx_file, rade_batch_ber_align; radae_amd.acq.receive)
+"""The stored-file receiver past the acquisition on the device (rade_file.hip: rade_batch_bpf_file; rade_irx.hip: rade_batch_rx_file, rade_batch_ber_align; radae_amd.acq.receive)
 against the float64 restatements tests/file_ref.py and tests/acq_ref.py: the whole-file band-pass within the header's derived bound at every size at which the kernel takes
 another path, its power-of-two covariance, the acquisition on kernel-filtered recordings, the ragged demodulator bit for bit against rade_batch_rx_ideal and against
 single-stream runs, receive end to end on the committed recordings, the BER alignment, the buffer contract on sentinel buffers (tests/bands.py) and the refusals.
@@ -134,18 +134,20 @@ def test_acquisition_over_the_kernel_filtered_recordings(engines, torch_dev):
 
 # ---- 2. the demodulator ---------------------------------------------------------------------------------------------------------------------------------------------
 def test_demodulator_equals_rx_ideal_bit_for_bit(engine, torch_dev, golden):
-    """start 0, freq 0, equal n_mf: z_hat and features are rade_batch_rx_ideal's bits in every EQ mode, with coarse_mag on and off, time_offset 0 and -16"""
+    """start 0, freq 0, equal n_mf: z_hat and features are rade_batch_rx_ideal's bits in every EQ mode, with coarse_mag on and off, time_offset 0 and -16; at the
+    recording's whole length and at the smallest frame counts: 2 (every frame is the first or the last) and 3 (one frame that is neither)"""
     import torch
     rx_np = golden("chan_mpp")["rx"]
-    n_mf = len(rx_np) // NMF
-    eng = engine(2, max_tx_mf=n_mf)
+    full = len(rx_np) // NMF
+    eng = engine(2, max_tx_mf=full)
     rx = torch.tensor(np.stack([rx_np, np.roll(rx_np, 960 * 3)]), device=torch_dev)
-    for eq in ("ls", "mean6", "all", "none"):
-        for cm in (True, False):
-            for to in (0, -16):
-                f0, z0, _ = eng.rx_ideal(rx, n_mf, time_offset=to, eq=eq, coarse_mag=cm)
-                f1, z1 = eng.rx_file(rx, [(0, n_mf, 0.0)] * 2, time_offset=to, eq=eq, coarse_mag=cm)
-                assert torch.equal(z0, z1) and torch.equal(f0, f1), (eq, cm, to)
+    for n_mf in (full, 2, 3):
+        for eq in ("ls", "mean6", "all", "none"):
+            for cm in (True, False):
+                for to in (0, -16):
+                    f0, z0, _ = eng.rx_ideal(rx, n_mf, time_offset=to, eq=eq, coarse_mag=cm)
+                    f1, z1 = eng.rx_file(rx, [(0, n_mf, 0.0)] * 2, time_offset=to, eq=eq, coarse_mag=cm)
+                    assert torch.equal(z0, z1) and torch.equal(f0, f1), (n_mf, eq, cm, to)
 
 
 def test_demodulator_takes_its_own_start_and_frequency(engine, torch_dev, golden):

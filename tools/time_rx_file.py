@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time of the stored-file receiver past the acquisition on the device (rade_file.hip), in alternating rounds in one process, at 256 streams x 80,000 and 256 x 806,400
+"""Time of the stored-file receiver past the acquisition on the device (rade_file.hip, rade_irx.hip), in alternating rounds in one process, at 256 streams x 80,000 and 256 x 806,400
 samples:
     bpf_file    rade_batch_bpf_file (k_file_phase + k_file_bpf; the call synchronises: host clock) next to
                 (a) the device's own complex64 copy of the same input bytes (HIP events; 16 bytes per sample, the filter's floor), and
