@@ -68,5 +68,6 @@ int rd_core_tx_frame(void *t, const float *features_in, float *tx_out);
 struct rade_batch;
 const rd_tables *rd_batch_tables(const struct rade_batch *h);
 int rd_batch_has_tx_bpf(const struct rade_batch *h);
+double rade_wait_model_step(double *est, double ready_after_us, int first);   /* test hook: the sleeping wait's estimate, driven with synthetic waits */
 
 #endif

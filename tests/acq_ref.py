@@ -27,10 +27,8 @@ def consts():
     """(p [160], p_w [160, 40]) as the engine holds them: the float32 words of rd_tables_fill, taken as exact (tests/test_acq_host.py holds them to the reference's
     tables, tests/golden/consts.npz: p, acq_p_w)"""
     import ctypes as C
-    from radae_amd.abi import load_library
-    from tx_ref import Tables
-    L, T = load_library(), Tables()
-    L.rd_tables_fill.restype = None; L.rd_tables_fill.argtypes = [C.POINTER(Tables)]
+    import dev_abi
+    L, T = dev_abi.load(), dev_abi.Tables()
     L.rd_tables_fill(C.byref(T))
     return (np.ctypeslib.as_array(T.p).view(np.complex64).astype(np.complex128), np.ctypeslib.as_array(T.p_w).view(np.complex64).reshape(M, NFC).astype(np.complex128))
 

@@ -54,13 +54,12 @@ Run as a program (python tests/bpf_ref.py REFERENCE_DIR) the model is held to th
 import ctypes as C
 import functools
 import os
-import re
 import sys
 
 import numpy as np
 
+from dev_abi import BpfArgs, BpfState, Tables  # noqa: F401  (the records of rade_dev.h, stated in tests/dev_abi.py)
 from kernel_ref import U, vp
-from tx_ref import Tables
 
 NTAP, NMF, NEOO, MEM = 101, 960, 1152, 102
 EPS = 1.75 * 2.0 ** -20
@@ -227,46 +226,7 @@ def state32(x, len0, avail, mem, mem_len, phase):
     return m, MEM, c[nb]
 
 
-# ---- ctypes mirrors of rade_dev.h ----------------------------------------------------------------------------------------------------------------------------------
-class BpfState(C.Structure):        # rd_bpf_state
-    _fields_ = [("mem_len", C.c_int), ("grid_off", C.c_int), ("phase", C.c_float * 2), ("mem", C.c_float * (2 * MEM))]
-
-
-class BpfArgs(C.Structure):         # rd_bpf_args
-    _fields_ = [("state", vp), ("state_stride", C.c_long), ("len0", vp), ("len0_stride", C.c_long), ("len0_const", C.c_int), ("avail", vp), ("avail_const", C.c_int),
-                ("tab", vp), ("bpf16", vp), ("x", vp), ("x_stride", C.c_long), ("y", vp), ("y_stride", C.c_long), ("chain", vp), ("chain_stride", C.c_int),
-                ("n_blocks", C.c_int), ("B", C.c_int), ("clip", C.c_int), ("advance", C.c_int), ("zero_acc", vp), ("zero_progress", vp)]
-
-
 BPF16_HALFS = 4 * 2 * 64 * 8        # rd_bpf16_table_fill's table
-
-
-def header_fields(text, name):
-    """the member names of `typedef struct { .. } name;` in the header text, in order"""
-    m = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\} %s;" % re.escape(name), text, re.S)
-    if m is None:
-        raise LookupError(f"no struct {name}")
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    names = []
-    for stmt in body.split(";"):
-        for part in stmt.split(","):
-            g = re.search(r"([A-Za-z_]\w*)\s*(?:\[[^\]]*\]\s*)*$", part.strip())
-            if g:
-                names.append(g.group(1))
-    return names
-
-
-def declare(L):
-    """argument types of the filter's shim and of the host functions around it; the two records' member order is checked against rade_dev.h's text"""
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "radae_amd", "csrc", "rade_dev.h")) as f:
-        text = f.read()
-    for cls, name in ((BpfState, "rd_bpf_state"), (BpfArgs, "rd_bpf_args")):
-        assert [n for n, _ in cls._fields_] == header_fields(text, name), f"{name}: the ctypes mirror does not follow rade_dev.h"
-    L.rd_launch_bpf.restype = C.c_int; L.rd_launch_bpf.argtypes = [C.POINTER(BpfArgs), vp]
-    L.rd_bpf16_table_fill.restype = None; L.rd_bpf16_table_fill.argtypes = [C.POINTER(Tables), vp]
-    L.rd_tables_fill.restype = None; L.rd_tables_fill.argtypes = [C.POINTER(Tables)]
-    L.rd_batch_tables.restype = vp; L.rd_batch_tables.argtypes = [vp]
-    return L
 
 
 def host_tables(L):

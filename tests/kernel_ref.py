@@ -27,6 +27,8 @@ import ctypes as C
 
 import numpy as np
 
+from dev_abi import EncfArgs, GemmArgs, ScanArgs  # noqa: F401  (the records of rade_dev.h, stated in tests/dev_abi.py)
+
 U = 2.0 ** -24
 R_F16 = 3 * 2.0 ** -22
 # measured maxima (MI355X, against float64 tanh / 1 / (1 + exp(-x))), and the bound each test holds them to
@@ -41,42 +43,7 @@ EF_KB = 864 // 16
 EF_TILE = EF_KB * 1024             # RD_EF_TILE of rade_dev.h
 
 
-# ---- ctypes mirrors of rade_dev.h ------------------------------------------------------------------------------------------------------------------------------
 vp = C.c_void_p
-
-
-class GemmArgs(C.Structure):        # rd_gemm_args
-    _fields_ = [("a1", vp), ("a1_sb", C.c_long), ("a1_st", C.c_long), ("K1", C.c_int),
-                ("a0", vp), ("a0_sb", C.c_long), ("a0_st", C.c_long), ("K0", C.c_int),
-                ("reset", vp), ("reset_sb", C.c_int), ("n_rows", vp), ("Wp", vp), ("bias", vp), ("Wp16", vp), ("Wscale", vp),
-                ("y", vp), ("y_sb", C.c_long), ("y_st", C.c_long), ("N", C.c_int), ("B", C.c_int), ("T", C.c_int), ("act", C.c_int)]
-
-
-class ScanArgs(C.Structure):        # rd_scan_args
-    _fields_ = [("gi", vp), ("gi_sb", C.c_long), ("gi_st", C.c_long), ("Whh", vp), ("bhh", vp), ("h", vp),
-                ("out", vp), ("out_sb", C.c_long), ("out_st", C.c_long), ("reset", vp), ("reset_sb", C.c_int), ("n_rows", vp),
-                ("B", C.c_int), ("T", C.c_int), ("H", C.c_int), ("outf", vp), ("outf_NQ", C.c_int), ("outf_col", C.c_int)]
-
-
-class EncfArgs(C.Structure):        # rd_encf_args
-    _fields_ = [("xf", vp), ("NQ", C.c_int), ("B", C.c_int), ("T", C.c_int), ("K0", C.c_int), ("K1", C.c_int), ("dil", C.c_int),
-                ("Wp16", vp), ("Wscale", vp), ("bias", vp), ("N", C.c_int), ("act", C.c_int),
-                ("y", vp), ("y_sb", C.c_long), ("y_st", C.c_long), ("yf", vp), ("ycol", C.c_int),
-                ("seq_taps", C.c_int), ("no_pair", C.c_int), ("pair", C.c_int), ("xin", vp), ("Kin", C.c_int), ("Wp", vp)]
-
-
-def declare(L):
-    """argument types of the shims and packers on the loaded library"""
-    L.rd_launch_gemm.argtypes = [C.POINTER(GemmArgs), vp]
-    L.rd_launch_gru_scan.argtypes = [C.POINTER(ScanArgs), vp]
-    L.rd_launch_encf_gemm.argtypes = [C.POINTER(EncfArgs), vp]
-    L.rd_launch_encf_hist.argtypes = [vp, C.c_int, vp, C.c_long, C.c_int, C.c_int, C.c_int, vp]
-    for f in (L.rd_packed_size, L.rd_packed16_size):
-        f.restype = C.c_long; f.argtypes = [C.c_int, C.c_int]
-    L.rd_pack_weights.restype = C.c_long; L.rd_pack_weights.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.rd_pack_weights_f16x2.restype = C.c_long; L.rd_pack_weights_f16x2.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.rd_pack_weights_q16.restype = C.c_long; L.rd_pack_weights_q16.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
-    return L
 
 
 def _p(a):

@@ -69,10 +69,8 @@ BUGS = ("win_late", "dft_11bit", "eq_edge_noclamp", "phase_960", "row_off", "pen
 def tables():
     """the engine's float32 tables as float64 / complex128, and the equaliser's matrices from the reference's statement"""
     import ctypes as C
-    from radae_amd.abi import load_library
-    from tx_ref import Tables
-    L, T = load_library(), Tables()
-    L.rd_tables_fill.restype = None; L.rd_tables_fill.argtypes = [C.POINTER(Tables)]
+    import dev_abi
+    L, T = dev_abi.load(), dev_abi.Tables()
     L.rd_tables_fill(C.byref(T))
     cx = lambda a, *s: np.ctypeslib.as_array(a).view(np.complex64).reshape(*s).astype(np.complex128)
     t = dict(Wfwd=cx(T.Wfwd, M, NC), p=cx(T.p, M), pend=cx(T.pend, M), P=np.ctypeslib.as_array(T.P).astype(np.float64), Pend=np.ctypeslib.as_array(T.Pend).astype(np.float64),

@@ -6,100 +6,23 @@
 2. every ctypes structure of abi.STRUCTS has the size, field offsets and field sizes the host compiler gives its typedef;
 3. the comparison rejects what it is for: doctored header text is reported as a mismatch that names the function or field;
 4. the names the four binding modules offered before abi.py / stages.py were split off are all still there, and the derived symbol lists have the members pinned
-   here, no more and no fewer (EXPORTED_SYMBOLS: every function of rade_api.h and rade_batch.h but the single-carrier modem's, which SC_SYMBOLS lists)."""
+   here, no more and no fewer (EXPORTED_SYMBOLS: every function of rade_api.h and rade_batch.h but the single-carrier modem's, which SC_SYMBOLS lists).
+
+The header parser and the compiler's layout probe are tests/c_decl.py's, shared with the private ABI's check (tests/test_dev_abi_host.py)."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
+from c_decl import c_layouts, function_mismatches, layout_mismatches, parse
 from radae_amd import abi
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = ("rade_api.h", "rade_core.h", "rade_batch.h")
-SCALARS = {"void": "void", "int": "i32", "unsigned": "u32", "unsigned int": "u32", "long": "i64", "long long": "i64", "unsigned long": "u64",
-           "unsigned long long": "u64", "size_t": "u64", "float": "f32", "double": "f64"}
-BASE_WORDS = {w for k in SCALARS for w in k.split()}
 
 
 def header_texts():
     return {h: open(os.path.join(REPO, "include", h)).read() for h in HEADERS}
-
-
-# ================================================================================================================================================================
-# the parser: comments and the preprocessor out, statements split at top-level semicolons, parameters at top-level commas
-# ================================================================================================================================================================
-def statements(text):
-    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
-    text = text.replace('extern "C" {', " ").replace("RADE_EXPORT", " ")
-    out, cur, depth = [], "", 0
-    for ch in text:
-        depth += (ch in "{(") - (ch in "})")
-        if depth < 0:                      # the brace that closes extern "C"
-            depth = 0
-        elif ch == ";" and depth == 0:
-            out.append(" ".join(cur.split())); cur = ""
-        else:
-            cur += ch
-    assert not cur.strip(), f"text behind the last declaration: {cur.strip()[:80]!r}"
-    return [s for s in out if s]
-
-
-def split_top(s, sep=","):
-    out, cur, depth = [], "", 0
-    for ch in s:
-        depth += (ch in "{([") - (ch in "})]")
-        if ch == sep and depth == 0:
-            out.append(cur); cur = ""
-        else:
-            cur += ch
-    return [p.strip() for p in out + [cur] if p.strip()]
-
-
-def type_class(decl, pointer_types, named):
-    """the class of a parameter (named: its name may follow the type) or of a return type; a function pointer or an array parameter is a pointer"""
-    if any(c in decl for c in "*[("):
-        return "ptr"
-    w = [t for t in decl.split() if t not in ("const", "signed")]
-    if named and len(w) > 1 and w[-1] not in BASE_WORDS:
-        w.pop()
-    if len(w) == 1 and w[0] in pointer_types:
-        return "ptr"
-    return SCALARS[" ".join(w)]            # KeyError: the caller names the declaration
-
-
-def parse(text):
-    """(functions {name: (return class, [argument classes])} in the text's order, structures {typedef name: [field names]}); ValueError names what it cannot read"""
-    funcs, structs, pointer_types = {}, {}, set()
-    for s in statements(text):
-        m = re.match(r"typedef struct\s*\w*\s*\{(.*)\}\s*(\w+)$", s)
-        if m:
-            structs[m.group(2)] = [re.search(r"(\w+)\s*(\[[^\]]*\])?$", d).group(1) for f in split_top(m.group(1), ";") for d in split_top(f)]
-            continue
-        m = re.match(r"typedef .*\(\s*\*\s*(\w+)\s*\)\s*\(", s)
-        if m:
-            pointer_types.add(m.group(1))
-            continue
-        if re.match(r"(typedef struct \w+ \w+|struct \w+|enum\s*\{.*\}|extern [^()]*)$", s):      # opaque handles, enumerations, data
-            continue
-        m = re.match(r"(.*?)(\w+)\s*\((.*)\)$", s)
-        try:
-            params = [] if m.group(3).strip() == "void" else split_top(m.group(3))
-            funcs[m.group(2)] = (type_class(m.group(1), pointer_types, False), [type_class(p, pointer_types, True) for p in params])
-        except (AttributeError, KeyError):
-            raise ValueError(f"cannot parse the declaration {s!r}") from None
-    return funcs, structs
-
-
-def ctype_class(t):
-    if t is None:
-        return "void"
-    if issubclass(t, (C._Pointer, C.c_void_p, C.c_char_p, C.Array, C._CFuncPtr)):
-        return "ptr"
-    return {"i": "i32", "I": "u32", "l": "i64", "q": "i64", "L": "u64", "Q": "u64", "f": "f32", "d": "f64"}[t._type_]
 
 
 # ================================================================================================================================================================
@@ -115,57 +38,16 @@ def compare_functions(texts):
             bad += [f"{h}: the table's {n} is not declared" for n in table if n not in funcs]
             both = zip([n for n in funcs if n in table], [n for n in table if n in funcs])
             bad += [f"{h}: the table's order differs from the header's at {a} / {b}" for a, b in both if a != b][:1]
-        for n, (ret, args) in funcs.items():
-            if n not in table:
-                continue
-            restype, argtypes = table[n]
-            if ctype_class(restype) != ret:
-                bad.append(f"{n}: returns {ret}, the table says {ctype_class(restype)}")
-            got = [ctype_class(a) for a in argtypes]
-            if len(got) != len(args):
-                bad.append(f"{n}: {len(args)} arguments, the table has {len(got)}")
-            bad += [f"{n}: argument {i} is {a}, the table says {g}" for i, (a, g) in enumerate(zip(args, got)) if a != g]
+        bad += function_mismatches(funcs, table)
     return bad
-
-
-def c_layouts(texts, tmp):
-    """{typedef: (sizeof, [(field, offset, size)])} from the host compiler, for every structure typedef of the texts"""
-    cc = shutil.which("cc")
-    assert cc, "no host C compiler `cc` (build() needs one too)"
-    structs = {}
-    for h in HEADERS:
-        open(os.path.join(tmp, h), "w").write(texts[h])
-        structs.update(parse(texts[h])[1])
-    lines = ["#include <stdio.h>", "#include <stddef.h>"] + [f'#include "{h}"' for h in HEADERS] + ["int main(void) {"]
-    for t, fields in structs.items():
-        lines.append(f'printf("{t} %zu\\n", sizeof({t}));')
-        lines += [f'printf("{t}.{f} %zu %zu\\n", offsetof({t}, {f}), sizeof((({t} *)0)->{f}));' for f in fields]
-    open(os.path.join(tmp, "layout.c"), "w").write("\n".join(lines + ["return 0; }", ""]))
-    subprocess.check_call([cc, "-I", tmp, "-o", os.path.join(tmp, "layout"), os.path.join(tmp, "layout.c")])
-    out = {}
-    for ln in subprocess.check_output([os.path.join(tmp, "layout")], text=True).splitlines():
-        name, *v = ln.split()
-        if "." in name:
-            out[name.split(".")[0]][1].append((name.split(".")[1], int(v[0]), int(v[1])))
-        else:
-            out[name] = (int(v[0]), [])
-    return out
 
 
 def compare_layouts(texts, tmp):
-    want = c_layouts(texts, str(tmp))
-    bad = [f"{t}: abi.STRUCTS has no such typedef in the headers" for t in abi.STRUCTS if t not in want]
-    for t, cls in abi.STRUCTS.items():
-        if t not in want:
-            continue
-        size, fields = want[t]
-        got = [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, *_ in cls._fields_]
-        if C.sizeof(cls) != size or len(got) != len(fields):
-            bad.append(f"{t}: {len(fields)} fields in {size} bytes, ctypes has {len(got)} in {C.sizeof(cls)}")
-        for (cn, co, cs), (pn, po, ps) in zip(fields, got):
-            if not (cn == pn or cn.endswith("_" + pn)) or (co, cs) != (po, ps):     # (RADEEnc.input_dim and RADEDec.output_dim share one mirror: `dim`)
-                bad.append(f"{t}.{cn}: offset {co} size {cs}, ctypes has {pn} at offset {po} size {ps}")
-    return bad
+    for h in HEADERS:
+        open(os.path.join(str(tmp), h), "w").write(texts[h])
+    want = c_layouts([os.path.join(str(tmp), h) for h in HEADERS], [str(tmp)], str(tmp))
+    # (RADEEnc.input_dim and RADEDec.output_dim share one mirror: `dim`)
+    return layout_mismatches(abi.STRUCTS, want, lambda cn, pn: cn == pn or cn.endswith("_" + pn))
 
 
 # ================================================================================================================================================================

@@ -71,10 +71,8 @@ def test_ranks_of_a_node_tell_the_wait_policy_about_each_other():
     assert bench.sync_peers(8, {}) == "8"
     assert bench.sync_peers(8, {"LOCAL_WORLD_SIZE": "4"}) == "4"
     assert bench.sync_peers(8, {"LOCAL_WORLD_SIZE": "4", "RADE_SYNC_PEERS": "2"}) == "2"
-    import ctypes as C
     from radae_amd import engine
     lib = engine.load_library()
-    lib.rade_sync_policy.argtypes = [C.c_int, C.c_double]
     assert lib.rade_sync_policy(3 * 8, 16.0) == 1 and lib.rade_sync_policy(3 * 1, 16.0) == 0
 
 

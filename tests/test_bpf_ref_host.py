@@ -73,11 +73,10 @@ def test_engine_taps_against_the_design():
     """The kernels read rd_tables_fill's taps; the model is stated on radae_amd.acq.bpf_design()'s, which are the reference's own words (tests/golden/consts.npz).
     The two differ where C's sin and numpy's float32 sinc round differently: at most 2 ulp of a tap, 0.05 x 2^-24 of sum |h| in all.  Pinned, so that the device
     tests may hand the model the words the kernels read."""
-    import ctypes as C
     import __graft_entry__ as ge
     ge.build()
-    from radae_amd import abi
-    h_lib, E_lib, _ = M.host_tables(M.declare(C.CDLL(abi.LIB_PATH)))
+    import dev_abi
+    h_lib, E_lib, _ = M.host_tables(dev_abi.load())
     h, _, E = M.design()
     tx.check_bits(E_lib, E, "bpf_E", ("entry", "component"))
     d = np.abs(h_lib.view(np.int32).astype(np.int64) - h.astype(np.float32).view(np.int32))
@@ -174,5 +173,8 @@ def test_state32_against_the_float64_model(len0, n_more, partial):
 
 
 def test_header_fields_reads_the_records():
+    """the header parser the records' member check stands on (tests/c_decl.py: dev_abi.load() compares every mirror's names with it), on doctored text: a record's
+    names in order, with another record, comments and arrays in the way"""
+    import c_decl
     text = "typedef struct { int a; } other;\ntypedef struct {\n  const int *p, *q; /* x; y */ float m[102][2]; long s;   /* t */\n} rec_t;"
-    assert M.header_fields(text, "rec_t") == ["p", "q", "m", "s"]
+    assert c_decl.parse(text)[1]["rec_t"] == ["p", "q", "m", "s"]

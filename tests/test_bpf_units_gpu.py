@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import bpf_ref as M
+import dev_abi
 import tx_ref as tx
 from gpu_kit import stream, sync, torch_dev  # noqa: F401
 from kernel_ref import SENT32, U
@@ -28,8 +29,7 @@ ISENT = 0x7F0F0F0F              # sentinel of the integer buffers
 
 @pytest.fixture(scope="module")
 def L(torch_dev):
-    from radae_amd import engine
-    return M.declare(engine.load_library())
+    return dev_abi.load()
 
 
 @pytest.fixture(scope="module")

@@ -7,11 +7,10 @@ EPS.  The Philox words must be equal bit for bit.  gauss_pair runs on the hardwa
 same float32 uniforms within EPS = four times the largest deviation measured on the MI355X over the inputs of test_probe_gauss_pair (2^20 reference word pairs
 and the 64 crossed extremes), rounded up to one digit; the margin is for other inputs and for the float32 scaling by sigma / sqrt(2) in the consumers.  The
 consumers' errors scale with sigma (the sigmas used here are powers of two: exactly), so their bar is sigma x EPS."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import dev_abi
 import noise_ref as nr
 from gpu_kit import torch_dev  # noqa: F401
 from noise_ref import EPS
@@ -25,10 +24,7 @@ EXTREMES = np.array([0, 1, 1 << 24, (1 << 24) + 1, 0x7fffffff, 0x80000000, 0xfff
 
 @pytest.fixture(scope="module")
 def L(torch_dev):
-    from radae_amd import engine
-    lib = engine.load_library()
-    lib.rd_launch_noise_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    return lib
+    return dev_abi.load()
 
 
 @pytest.fixture(scope="module")

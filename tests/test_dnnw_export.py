@@ -106,12 +106,10 @@ def test_oracle_reader_equals_python_reader_on_model19(oracle_model):
 
 def test_host_reader_returns_the_checkpoint_bit_for_bit(ckpt_a):
     """rd_model_parse (radae_amd/csrc/rade_host.c), the reader the engine uploads from."""
-    from radae_amd import engine
-    from test_host_cpu import Model
-    lib = engine.load_library()
+    from dev_abi import Model, load
+    lib = load()
     blob = open(BLOB_A, "rb").read()
     m = Model()
-    lib.rd_model_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Model)]
     assert lib.rd_model_parse(blob, len(blob), C.byref(m)) == 0
     arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,))
     a = ckpt_a
@@ -130,7 +128,7 @@ def test_host_reader_returns_the_checkpoint_bit_for_bit(ckpt_a):
             cw = r.w.transpose(0, 2, 1).reshape(r.w.shape[0], -1)                             # [out][tap][in]
             assert np.array_equal(arr(c.w, cw.size).reshape(cw.shape), cw) and np.array_equal(arr(c.b, r.b.size), r.b)
         assert np.array_equal(arr(m.dec_glu[i].w, 96 * 96).reshape(96, 96), a.dec_glu[i].w) and not arr(m.dec_glu[i].b, 96).any()
-    lib.rd_model_free.argtypes = [C.POINTER(Model)]; lib.rd_model_free(C.byref(m))
+    lib.rd_model_free(C.byref(m))
     # a block position outside the layer's inputs is rejected (n_in is the architecture's, not inferred)
     rec_off = blob.index(b"enc_gru1_input_weights_idx") - 20
     bad = bytearray(blob); bad[rec_off + 64 + 4:rec_off + 64 + 8] = (64).to_bytes(4, "little")     # first block position -> 64 (layer has 64 inputs)

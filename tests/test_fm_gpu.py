@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dev_abi
 import fm_ref as fr
 from bands import Band
 from gpu_kit import bits, crandn, define, dev, engines, torch_dev  # noqa: F401
@@ -95,9 +96,8 @@ def test_probe_phasor_and_atan2(torch_dev):
     """THE measurements behind EPS_CIS and EPS_ATAN: the device phasor on 2^16 phases spread over the circle by a golden-ratio stride plus the edges of every quadrant and
     octant, against float64; the discriminator's atan2 on 2^16 float32 pairs of spread angle and radius plus the axes, against float64 atan2 of the same float32 pairs"""
     import torch
-    from radae_amd.engine import load_library, _stream_ptr
-    lib = load_library()
-    lib.rd_launch_fm_probe.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+    from radae_amd.engine import _stream_ptr
+    lib = dev_abi.load()
     k = np.arange(1 << 16, dtype=np.uint64)
     edges = np.array([(q << 29) + d for q in range(8) for d in (-2, -1, 0, 1, 2)], np.int64) & 0xFFFFFFFF
     ph = np.concatenate([(k * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF), edges.astype(np.uint64)]).astype(np.uint32)

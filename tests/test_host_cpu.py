@@ -8,6 +8,9 @@ import re
 import numpy as np
 import pytest
 
+import dev_abi
+from dev_abi import Model, Tables
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -15,8 +18,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def lib():
     import __graft_entry__ as ge
     ge.build()
-    from radae_amd import engine
-    return engine.load_library()
+    return dev_abi.load()
 
 
 def test_built_kernels_do_not_spill_ahead_of_exec_restore(lib):
@@ -97,7 +99,6 @@ def test_multi_gpu_sharding_rule(lib):
     streams on 8 GPUs) -- config 4: 2048 utterances, GPU g owns [256 g, 256 g + 256) -- and the same rule as the torchrun path's
     radae_amd.parallel.shard_range; rade_multi_open refuses to run without a GPU."""
     from radae_amd.parallel import shard_range
-    lib.rade_multi_shard.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]; lib.rade_multi_shard.restype = None
     for total, ndev in ((2048, 8), (256, 1), (10, 4), (7, 8), (1000, 3), (9, 8), (10, 8), (8, 8), (2047, 8)):
         got = []
         for i in range(ndev):
@@ -113,7 +114,6 @@ def test_multi_gpu_sharding_rule(lib):
     assert (lo.value, n.value) == (1280, 256)
     import torch
     if not torch.cuda.is_available():
-        lib.rade_multi_open.restype = C.c_void_p; lib.rade_multi_open.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_ulonglong, C.c_int]
         from radae_amd import engine
         assert not lib.rade_multi_open(engine.DEFAULT_BLOB.encode(), 16, 1, 1, 0)
 
@@ -130,13 +130,6 @@ def test_no_cpu_fallback(lib):
         engine.BatchEngine(1)
 
 
-class Tables(C.Structure):
-    _fields_ = [("Winv", C.c_float * (30 * 160 * 2)), ("Wfwd", C.c_float * (160 * 30 * 2)), ("P", C.c_float * 30), ("Pend", C.c_float * 30),
-                ("p", C.c_float * 320), ("pend", C.c_float * 320), ("eoo", C.c_float * 2304), ("Pmat", C.c_float * 360), ("eq_rot", C.c_float * 60),
-                ("bpf_h", C.c_float * 104), ("bpf_E", C.c_float * 2304), ("p_w", C.c_float * 12800), ("fcoarse", C.c_double * 40),
-                ("pilot_gain", C.c_float), ("snr_c1", C.c_float), ("snr_c2", C.c_float), ("pad", C.c_float)]
-
-
 def _c(a):
     return np.ctypeslib.as_array(a).view(np.complex64)
 
@@ -144,7 +137,6 @@ def _c(a):
 def test_host_tables_match_reference_constants(lib, golden):
     c = golden("consts")
     T = Tables()
-    lib.rd_tables_fill.argtypes = [C.POINTER(Tables)]
     lib.rd_tables_fill(C.byref(T))
     assert np.abs(_c(T.Winv) - c["Winv"].ravel()).max() < 2e-9
     assert np.abs(_c(T.Wfwd) - c["Wfwd"].ravel()).max() < 2e-7
@@ -165,9 +157,8 @@ def test_demodulator_dft_matrix_as_matrix_core_operands(lib, golden):
     applied to (xi, -xr) the imaginary part, to the planes' 22 bits."""
     c = golden("consts")
     T = Tables()
-    lib.rd_tables_fill.argtypes = [C.POINTER(Tables)]; lib.rd_tables_fill(C.byref(T))
+    lib.rd_tables_fill(C.byref(T))
     out = np.zeros(2 * 10 * 2 * 64 * 8, np.uint16)
-    lib.rd_wfwd16_table_fill.argtypes = [C.POINTER(Tables), C.c_void_p]; lib.rd_wfwd16_table_fill.restype = None
     lib.rd_wfwd16_table_fill(C.byref(T), out.ctypes.data_as(C.c_void_p))
     tab = out.view(np.float16).astype(np.float64).reshape(2, 10, 2, 64, 8)
     R = np.zeros((32, 320))
@@ -191,12 +182,10 @@ def test_two_stage_pilot_correlator_tables(lib, golden):
     (dsp.py:207-208) -- and the exact factorisation (before the binary16 split) reproduces p_w to 1e-8."""
     c = golden("consts")
     T = Tables()
-    lib.rd_tables_fill.argtypes = [C.POINTER(Tables)]; lib.rd_tables_fill(C.byref(T))
-    lib.rd_corr_tables_check.argtypes = [C.POINTER(Tables)]; lib.rd_corr_tables_check.restype = C.c_double
+    lib.rd_tables_fill(C.byref(T))
     assert lib.rd_corr_tables_check(C.byref(T)) < 1e-8            # (p_w itself is rounded to float32: 0.124 x 6e-8)
     q16 = np.zeros(2 * 10 * 2 * 64 * 8, np.uint16); a16 = np.zeros(5 * 2 * 64 * 8, np.uint16)
     for fn, buf in (("rd_corrq16_table_fill", q16), ("rd_corra16_table_fill", a16)):
-        getattr(lib, fn).argtypes = [C.POINTER(Tables), C.c_void_p]; getattr(lib, fn).restype = None
         getattr(lib, fn)(C.byref(T), buf.ctypes.data_as(C.c_void_p))
     tq = q16.view(np.float16).astype(np.float64).reshape(2, 10, 2, 64, 8); ta = a16.view(np.float16).astype(np.float64).reshape(5, 2, 64, 8)
     Q1 = np.zeros((32, 320)); A2 = np.zeros((80, 32))
@@ -228,9 +217,8 @@ def test_bandpass_taps_as_matrix_core_operands(lib, golden):
     the reference's taps to the planes' 22 bits."""
     c = golden("consts")
     T = Tables()
-    lib.rd_tables_fill.argtypes = [C.POINTER(Tables)]; lib.rd_tables_fill(C.byref(T))
+    lib.rd_tables_fill(C.byref(T))
     out = np.zeros(4 * 2 * 64 * 8, np.uint16)
-    lib.rd_bpf16_table_fill.argtypes = [C.POINTER(Tables), C.c_void_p]; lib.rd_bpf16_table_fill.restype = None
     lib.rd_bpf16_table_fill(C.byref(T), out.ctypes.data_as(C.c_void_p))
     tab = out.view(np.float16).astype(np.float64).reshape(4, 2, 64, 8)
     Tm = np.zeros((16, 128))
@@ -248,25 +236,10 @@ def test_bandpass_taps_as_matrix_core_operands(lib, golden):
     assert np.abs(Y.T.ravel() - ref).max() < 1e-6 * np.abs(ref).max()
 
 
-class Lin(C.Structure):
-    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("w", C.POINTER(C.c_float)), ("b", C.POINTER(C.c_float)), ("row_scale", C.POINTER(C.c_float))]
-
-
-class Gru(C.Structure):
-    _fields_ = [("n_in", C.c_int), ("hid", C.c_int), ("w_ih", C.POINTER(C.c_float)), ("w_hh", C.POINTER(C.c_float)), ("b_ih", C.POINTER(C.c_float)), ("b_hh", C.POINTER(C.c_float)),
-                ("s_ih", C.POINTER(C.c_float)), ("s_hh", C.POINTER(C.c_float))]
-
-
-class Model(C.Structure):
-    _fields_ = [("enc_dense1", Lin), ("enc_zdense", Lin), ("dec_dense1", Lin), ("dec_output", Lin), ("enc_gru", Gru * 5), ("dec_gru", Gru * 5),
-                ("enc_conv", Lin * 5), ("dec_conv", Lin * 5), ("dec_glu", Lin * 5)]
-
-
 def test_host_blob_reader_and_packing(lib, golden):
     from radae_amd import dnnw, engine
     blob = open(engine.DEFAULT_BLOB, "rb").read()
     m = Model()
-    lib.rd_model_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Model)]
     assert lib.rd_model_parse(blob, len(blob), C.byref(m)) == 0
     ref = dnnw.load_model(engine.DEFAULT_BLOB)
     arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,))
@@ -286,8 +259,6 @@ def test_host_blob_reader_and_packing(lib, golden):
     assert lib.rd_model_parse(blob[:100000], 100000, C.byref(Model())) != 0
     assert lib.rd_model_parse(b"XXXX" + blob[4:], len(blob), C.byref(Model())) != 0
     # int8-exact layers: one binary16 plane of integers + row scales reproduces the de-quantised weights bit for bit
-    lib.rd_pack_weights_q16_a16.restype = C.c_long
-    lib.rd_pack_weights_q16_a16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for lin, N, K in ((m.dec_conv[3], 32, 1152), (m.dec_glu[0], 96, 96)):
         assert bool(lin.row_scale)
         plane = np.zeros((K // 32) * ((N + 15) // 16) * 64 * 8, np.float16); sc = np.zeros(((N + 15) // 16) * 16, np.float32)
@@ -301,8 +272,6 @@ def test_host_blob_reader_and_packing(lib, golden):
     bad = arr(m.dec_glu[0].w, 96 * 96).copy(); bad[5] *= 1.0000001
     assert lib.rd_pack_weights_q16_a16(bad.ctypes.data_as(C.c_void_p), m.dec_glu[0].row_scale, 96, 96, plane.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)) < 0
     # packing: every weight lands exactly once where k_gemm's lane expects it
-    lib.rd_packed_size.restype = C.c_long; lib.rd_packed_size.argtypes = [C.c_int, C.c_int]
-    lib.rd_pack_weights.restype = C.c_long; lib.rd_pack_weights.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     N, K = 84, 88
     W = np.arange(N * K, dtype=np.float32).reshape(N, K) + 1
     n = lib.rd_packed_size(N, K)
@@ -325,7 +294,6 @@ def test_chunk_major_packing_for_the_single_stream_kernel(lib):
     sc = (rng.uniform(0.001, 0.02, size=N)).astype(np.float32)
     W = (q * sc[:, None]).astype(np.float32)
     out = np.zeros(Npad * Kpad, np.uint16)
-    lib.rd_chunkmajor_q16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]; lib.rd_chunkmajor_q16.restype = C.c_int
     assert lib.rd_chunkmajor_q16(W.ctypes.data, sc.ctypes.data, N, K, Kpad, Npad, out.ctypes.data) == 0
     got = out.view(np.float16).astype(np.float32).reshape(Kpad // 8, Npad, 8)
     exp = np.zeros((Kpad // 8, Npad, 8), np.float32)
@@ -336,7 +304,6 @@ def test_chunk_major_packing_for_the_single_stream_kernel(lib):
     W2 = W.copy(); W2[3, 5] *= np.float32(1.0001)                  # not an integer multiple of its row scale any more
     assert lib.rd_chunkmajor_q16(W2.ctypes.data, sc.ctypes.data, N, K, Kpad, Npad, out.ctypes.data) != 0
     outf = np.zeros(Npad * Kpad, np.float32)
-    lib.rd_chunkmajor_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]; lib.rd_chunkmajor_f32.restype = None
     lib.rd_chunkmajor_f32(W.ctypes.data, N, K, Kpad, Npad, outf.ctypes.data)
     gf = outf.reshape(Kpad // 8, Npad, 8)
     assert all(np.array_equal(gf[c, :N, j], W[:, 8 * c + j]) for c in range(Kpad // 8) for j in range(8) if 8 * c + j < K) and not gf[:, N:, :].any() and not gf[-1, :, 4:].any()
@@ -348,7 +315,6 @@ def test_host_blob_reader_rejects_hostile_headers(lib):
     import struct
     from radae_amd import dnnw, engine
     blob = bytearray(open(engine.DEFAULT_BLOB, "rb").read())
-    lib.rd_model_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Model)]
     recs, off = {}, 0                                    # name -> (header offset, size, block)
     while off + 64 <= len(blob):
         ver, typ, size, block = struct.unpack_from("<iiii", blob, off + 4)
@@ -393,9 +359,6 @@ def test_host_wait_policy_switches_to_blocking_sync_under_a_cpu_quota(lib):
     """rade_batch_rx spins on its stream while every engine's host thread has a CPU and sleeps on a blocking event otherwise: 8 GPUs x 3 batches
     in flight = 24 engines under the 16-core quota seen on the GPU lease must block; one GPU x 3 must not.  rade_host_cpu_quota reads what
     bench.py's cpu_quota() reads (affinity mask, cgroup cpu.max)."""
-    import ctypes as C
-    lib.rade_host_cpu_quota.restype = C.c_double
-    lib.rade_sync_policy.argtypes = [C.c_int, C.c_double]
     assert lib.rade_sync_policy(24, 16.0) == 1 and lib.rade_sync_policy(3, 16.0) == 0 and lib.rade_sync_policy(16, 16.0) == 0 and lib.rade_sync_policy(17, 16.0) == 1
     assert lib.rade_sync_policy(2, 1.5) == 1 and lib.rade_sync_policy(1, 1.5) == 0
     import bench
@@ -443,7 +406,6 @@ def test_blob_writer_reproduces_the_reference_format(tmp_path, lib):
         assert np.abs(a - b).max() <= 0.51 * np.abs(a).max() / 127
     blob = open(out, "rb").read()
     cm = Model()
-    lib.rd_model_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Model)]
     assert lib.rd_model_parse(blob, len(blob), C.byref(cm)) == 0
     w = np.ctypeslib.as_array(cm.dec_gru[1].w_ih, shape=(288 * 224,)).reshape(288, 224)
     assert np.array_equal(w, m2.dec_gru[1].w_ih)
@@ -570,8 +532,6 @@ def test_sleeping_wait_estimate_recovers_from_an_outlier(lib):
     """rade_engine.c: sleep_until_event's estimate (it fed on its own nap -- est' = 0.9375 est per call after one outlier, ~12 s of cumulative oversleep after a
     1 s hiccup).  The update rule, driven with synthetic waits: steady 3 ms launches, one 1 s outlier, steady again -> the cumulative oversleep after the outlier stays
     below 40 ms and the estimate is back within 2x of the launch time in under 10 calls; a cold first wait does not seed it."""
-    lib.rade_wait_model_step.restype = C.c_double
-    lib.rade_wait_model_step.argtypes = [C.POINTER(C.c_double), C.c_double, C.c_int]
     est = C.c_double(0.0)
     lib.rade_wait_model_step(C.byref(est), 250000.0, 1)                      # first wait: 250 ms of lazy module load
     assert est.value == 0.0
@@ -698,7 +658,6 @@ def test_f16_weight_packers_recover_the_matrix(lib, N, K):
     """rd_pack_weights_f16x2 and rd_pack_weights_q16, decoded by the layout of rade_host.h and by the way k_gemm16 indexes it (lane = column, 8 k per lane):
     W comes back exactly on the exact grids, to 2^-22 relative on random weights, columns N.. of a ragged tile are zero."""
     import kernel_ref as kr
-    kr.declare(lib)
     rng = np.random.default_rng(100 * N + K)
     for bits in (12, 3):                                           # the weights of the "w12" and "a12" grids
         W = (rng.integers(1 - 2 ** bits, 2 ** bits, (N, K)) * 2.0 ** -bits).astype(np.float32)

@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dev_abi
 import kernel_ref as kr
 from gpu_kit import Dev, host32, stream, sync, torch_dev  # noqa: F401
 from kernel_ref import encf_check_exact, first_bad
@@ -34,8 +35,7 @@ NAN = float("nan")
 
 @pytest.fixture(scope="module")
 def L(torch_dev):
-    from radae_amd import engine
-    return kr.declare(engine.load_library())
+    return dev_abi.load()
 
 
 # ================================================================================================================================================================

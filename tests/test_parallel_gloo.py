@@ -59,11 +59,9 @@ def test_config4_world8_shards_blob_and_wait_policy():
         assert rank == r and n == len(ref) and h == sha and (lo, hi) == (256 * r, 256 * r + 256)
         assert stats == [2048.0, 36.0, 8.0 * len(ref)]
     sys.path.insert(0, REPO)
-    import ctypes as C
     import bench
     from radae_amd import engine
     lib = engine.load_library()
-    lib.rade_sync_policy.argtypes = [C.c_int, C.c_double]
     for r in range(8):
         peers = int(bench.sync_peers(8, {"LOCAL_WORLD_SIZE": "8", "LOCAL_RANK": str(r)}))
         assert peers == 8 and lib.rade_sync_policy(3 * peers, 16.0) == 1        # 24 engines > 16 CPUs: rade_batch_rx sleeps

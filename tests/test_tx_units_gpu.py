@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dev_abi
 import kernel_ref as kr
 import tx_ref as tx
 from gpu_kit import Dev, host32, stream, sync, torch_dev  # noqa: F401
@@ -22,8 +23,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def L(torch_dev):
-    from radae_amd import engine
-    return tx.declare(engine.load_library())
+    return dev_abi.load()
 
 
 @pytest.fixture(scope="module")

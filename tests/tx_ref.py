@@ -1,6 +1,6 @@
 """Float64 references, ctypes records and checkers for the unit tests of the transmit, channel and row kernels (tests/test_tx_units_gpu.py on the device;
 tests/test_tx_units_host.py pins these references to the reference project's recordings and proves that every checker can fail).  numpy only; holds no
-fixtures.  Rows, the fragment codec, pack_f32, U and the declarations of the GEMM shims come from tests/kernel_ref.py.
+fixtures.  Rows, the fragment codec, pack_f32 and U come from tests/kernel_ref.py, the records and the declared library from tests/dev_abi.py.
 
 Operands
 --------
@@ -48,7 +48,8 @@ import ctypes as C
 
 import numpy as np
 
-from kernel_ref import U, vp
+from dev_abi import ChanArgs, Tables  # noqa: F401  (the records of rade_dev.h, stated in tests/dev_abi.py)
+from kernel_ref import U
 
 SQ2 = np.sqrt(2.0)
 G60 = 60 * U / (1 - 60 * U)
@@ -60,49 +61,11 @@ EPS_PA_LIMIT = 2.0 ** -21      # pa_limit (sqrt / exp2 / rcp units), every kerne
 M, NCP, SYM, NC, NS, NMF, NEOO, ZMF = 160, 32, 192, 30, 4, 960, 1152, 240
 
 
-# ---- ctypes mirrors of rade_dev.h --------------------------------------------------------------------------------------------------------------------------------
-class Tables(C.Structure):          # rd_tables
-    _fields_ = [("Winv", C.c_float * (30 * 160 * 2)), ("Wfwd", C.c_float * (160 * 30 * 2)), ("P", C.c_float * 30), ("Pend", C.c_float * 30),
-                ("p", C.c_float * 320), ("pend", C.c_float * 320), ("eoo", C.c_float * 2304), ("Pmat", C.c_float * 360), ("eq_rot", C.c_float * 60),
-                ("bpf_h", C.c_float * 104), ("bpf_E", C.c_float * 2304), ("p_w", C.c_float * 12800), ("fcoarse", C.c_double * 40),
-                ("pilot_gain", C.c_float), ("snr_c1", C.c_float), ("snr_c2", C.c_float), ("pad", C.c_float)]
-
-
-class ChanArgs(C.Structure):        # rd_chan_args
-    _fields_ = [("tab", vp), ("tx", vp), ("tx_stride", C.c_long), ("rx", vp), ("rx_stride", C.c_long), ("G", vp), ("noise", vp), ("eoo", vp), ("scratch", vp),
-                ("mp", vp), ("B", C.c_int), ("n_sig", C.c_int), ("n_pre", C.c_int), ("n_post", C.c_int), ("with_eoo", C.c_int),
-                ("sigma", C.c_float), ("freq_offset", C.c_float), ("df_dt", C.c_float), ("seed", C.c_ulonglong),
-                ("sine_amp", C.c_float), ("sine_freq", C.c_float), ("rx_gain", C.c_float), ("ps", vp)]
-
-
-def declare(L):
-    """argument types of the shims of the transmit, channel and row kernels (kernel_ref.declare: the GEMM family, rd_launch_encf_*, the packers)"""
-    import kernel_ref as kr
-    kr.declare(L)
-    i, l, f, ull = C.c_int, C.c_long, C.c_float, C.c_ulonglong
-    L.rd_launch_encf_dense1.argtypes = [C.POINTER(kr.EncfArgs), vp]
-    L.rd_launch_enc_pack.argtypes = [vp, vp, i, i, vp]
-    L.rd_launch_pad_rows.argtypes = [vp, vp, l, i, i, vp]
-    L.rd_launch_carry_rows.argtypes = [vp, i, i, i, i, i, vp, vp]
-    L.rd_launch_ofdm_mod.argtypes = [vp, vp, vp, l, i, i, i, vp]
-    L.rd_launch_ofdm_mod_mp.argtypes = [vp, vp, vp, l, i, i, vp, vp, vp, i, vp]
-    L.rd_launch_eoo_build.argtypes = [vp, vp, vp, i, vp]
-    L.rd_launch_copy_eoo.argtypes = [vp, vp, l, i, vp]
-    L.rd_launch_channel.argtypes = [C.POINTER(ChanArgs), vp]
-    L.rd_launch_multipath_gen.argtypes = [vp, i, i, i, vp, ull, vp, vp, i, vp]
-    L.rd_multipath_gen_needs_scratch.argtypes = [i, i]
-    L.rd_launch_multipath_h.argtypes = [vp, i, i, i, i, f, i, vp, i, vp]
-    L.rd_batch_tables.restype = vp; L.rd_batch_tables.argtypes = [vp]
-    L.rd_tables_fill.restype = None; L.rd_tables_fill.argtypes = [C.POINTER(Tables)]
-    return L
-
-
 class Tab:
     """what the references read of rd_tables_fill's tables: the float32 words as float64 / complex128"""
 
     def __init__(self, L):
         T = Tables()
-        L.rd_tables_fill.restype = None; L.rd_tables_fill.argtypes = [C.POINTER(Tables)]
         L.rd_tables_fill(C.byref(T))
         self.Winv = np.ctypeslib.as_array(T.Winv).view(np.complex64).reshape(NC, M).astype(np.complex128)
         self.P = np.ctypeslib.as_array(T.P).astype(np.float64)
