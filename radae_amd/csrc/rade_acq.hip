@@ -6,37 +6,23 @@
 // In a stored file every hop is known up front: hop k's Dt2 is hop k + 1's Dt1, so the surface D[t][f] = sum_m conj(x[t + m]) p_w[m][f] is formed ONCE per timing.  A
 // wavefront owns 48 within-frame timings tau (three tiles of 16) for the whole stream: per block k it forms |D[960 k + tau][0..39]|, adds the values of block k - 1 it kept
 // in registers (that is |Dt1| + |Dt2| of hop k - 1), and keeps the new ones.  Nothing of the surface goes to memory unless the caller asks for rows of it.
-// The product is the Toeplitz GEMM of rade_rx_search.h in its two-stage form (the tables and the algebra: rade_host.c, rd_corrq16_table_fill): p_w[m][f] = sum_r
-// alpha[r][f] s_r[m] over 16 polynomial moments, so stage 1 forms Mom_r[t] = sum_m conj(x[t + m]) s_r[m] -- rows (r, re | im) = 2 tiles of 16, K = (m, re | im) = 10 steps
-// of 32, columns = timings -- and stage 2 expands a tile's moments to the 40 frequencies with one k-step per frequency tile, on v_mfma_f32_16x16x32_f16: 2 x 10 x 3 + 5 x 5
-// = 85 instructions per tile of 16 timings (255 per wavefront and block) where the 80 rows of p_w itself take 150.  The tables are the engine's own, the ones the
-// receiver's search uses (corrq16: 2^12-scaled, corra16: 2^10-scaled, two binary16 planes each, in A-operand order).  The samples are two binary16 planes (hi + lo, 22
-// bits) under the power of two that puts the largest component of the 208 samples the wavefront reads for the block into [2^7, 2^8).  The fragment of (timing tile T,
-// k-step s) is the fragment of (T + s, 0): 12 fragments serve 3 tiles x 10 steps.  Stage 1 keeps two accumulators per (row tile, timing tile): hi x hi (10 instructions)
-// and the cross planes lo x hi, hi x lo (20 instructions, 2^-11 of the former), joined by one float32 addition.  The joined accumulators of the two row tiles ARE stage 2's
-// B operand (the C layout gives lane group g rows 4 g .. 4 g + 3 of either tile, and corra16's K axis is ordered so): scaled by 2^-7, split into three binary16 planes
-// (33 bits) and multiplied by the two planes of alpha in five instructions, smallest partial products first.
+// The product is the two-stage correlator of rade_corr2.h (the algebra, the tables -- the engine's own, the ones the receiver's search uses --, the product order):
+// 2 x 10 x 3 + 5 x 5 = 85 matrix instructions per tile of 16 timings, 255 per wavefront and block.  What is acquisition's own: the sample scale comes from the largest
+// component of the 208 samples the wavefront reads for the block; the fragment of (timing tile T, k-step s) is the fragment of (T + s, 0), so 12 fragments serve 3 tiles
+// x 10 steps; and stage 1 keeps TWO accumulators per (row tile, timing tile): hi x hi (10 instructions) and the cross planes lo x hi, hi x lo (20 instructions, 2^-11
+// of the former), joined by one float32 addition per element on the way into stage 2.
 // Both tables (50 KB) are copied to LDS by the workgroup and stay there: one workgroup of eight wavefronts per CU, two per SIMD (256 registers each), so that one
 // wavefront's fragment reads, sample split and epilogue run under the other's matrix instructions.  After the tables are in place the wavefronts of a workgroup share
 // nothing: each has its own sample planes in LDS, written and read by itself alone (a wavefront's LDS accesses complete in the order issued), so the loop over the
 // blocks has no workgroup barrier and the eight wavefronts of a workgroup may belong to two or three streams of different length.
-#include <hip/hip_runtime.h>
-#include "rade_dev.h"
-#include "rade_devutil.h"
-#define RD_CORRQ16_HALFS_ACQ (2 * 10 * 2 * 64 * 8)                  /* rade_host.h: RD_CORRQ16_HALFS, RD_CORRA16_HALFS (a plain-C header of the host files; rade_stages.c checks the two agree) */
-#define RD_CORRA16_HALFS_ACQ (5 * 2 * 64 * 8)
+#include "rade_corr2.h"
 
 #define ACQ_WAVES 8                                               // wavefronts per workgroup: two per SIMD under the 256 registers a wavefront then has
 #define ACQ_WG (64 * ACQ_WAVES)
 #define ACQ_RT 3                                                  // timing tiles per wavefront
-#define ACQ_NQ 5                                                  // frequency tiles of stage 2: 8 frequencies x (re, im) each
-#define ACQ_NS 10                                                 // k-steps: 16 samples x (re, im) each
-#define ACQ_NFRAG (ACQ_RT + ACQ_NS - 1)
+#define ACQ_NFRAG (ACQ_RT + RD_CORR_NKS - 1)
 #define ACQ_SPAN 208                                              // samples a wavefront reads per block: 16 (ACQ_NFRAG - 1) + 31 = 207, rounded up
-#define ACQ_Q_HALVES (2 * ACQ_NS * 2 * 64 * 8)                     // stage 1: [row tile 2][k-step][plane][lane][8]
-#define ACQ_A2_HALVES (ACQ_NQ * 2 * 64 * 8)                       // stage 2: [frequency tile][plane][lane][8]
-#define ACQ_TAB_HALVES (ACQ_Q_HALVES + ACQ_A2_HALVES)
-static_assert(ACQ_Q_HALVES == RD_CORRQ16_HALFS_ACQ && ACQ_A2_HALVES == RD_CORRA16_HALFS_ACQ, "the engine's tables");
+#define ACQ_TAB_HALVES (RD_CORRQ16_HALFS + RD_CORRA16_HALFS)
 #define ACQ_LDS (ACQ_TAB_HALVES * 2 + ACQ_WAVES * 2 * ACQ_SPAN * 4)
 static_assert(RD_ACQ_NPART * ACQ_RT * 16 == RD_NMF, "the wavefronts of a stream cover the frame's timings once");
 static_assert(16 * (ACQ_NFRAG - 1) + 15 + 12 + 3 < ACQ_SPAN && ACQ_SPAN <= 4 * 64, "the fragments' samples");
@@ -52,8 +38,8 @@ __global__ __launch_bounds__(ACQ_WG) void k_acq_detect(rd_acq_args a)
     const int n = b < a.B ? a.n[b] : 0;
     const int H = rd_acq_hops(n);
     for (int u = tid; u < ACQ_TAB_HALVES / 8; u += ACQ_WG)           // 16 bytes a thread and round: corrq16, then corra16 behind it
-        ((u32x4 *)tabA)[u] = u < ACQ_Q_HALVES / 8 ? ((const u32x4 *)a.corrq16)[u] : ((const u32x4 *)a.corra16)[u - ACQ_Q_HALVES / 8];
-    const _Float16 *tabQ = tabA + (size_t)lane * 8, *tabA2 = tabA + ACQ_Q_HALVES + (size_t)lane * 8;
+        ((u32x4 *)tabA)[u] = u < RD_CORRQ16_HALFS / 8 ? ((const u32x4 *)a.corrq16)[u] : ((const u32x4 *)a.corra16)[u - RD_CORRQ16_HALFS / 8];
+    const _Float16 *tabQ = tabA + (size_t)lane * 8, *tabA2 = tabA + RD_CORRQ16_HALFS + (size_t)lane * 8;
     unsigned *ph = (unsigned *)(acq_lds + ACQ_TAB_HALVES) + wave * 2 * ACQ_SPAN, *pl = ph + ACQ_SPAN;
     const float2 *x = (const float2 *)a.x + (size_t)b * a.x_stride;
     const int T0 = part * ACQ_RT;                                 // the wavefront's first timing tile inside the frame
@@ -66,11 +52,11 @@ __global__ __launch_bounds__(ACQ_WG) void k_acq_detect(rd_acq_args a)
         }
     };
     if (H) load(0);
-    float prev[ACQ_RT][2 * ACQ_NQ];
+    float prev[ACQ_RT][2 * RD_CORR_NFT];
 #pragma unroll
     for (int rt = 0; rt < ACQ_RT; rt++)
 #pragma unroll
-        for (int c = 0; c < 2 * ACQ_NQ; c++) prev[rt][c] = 0.0f;
+        for (int c = 0; c < 2 * RD_CORR_NFT; c++) prev[rt][c] = 0.0f;
     __syncthreads();                                              // the table is whole; from here on a wavefront is on its own
     if (!H) return;
 #pragma unroll 1
@@ -79,18 +65,12 @@ __global__ __launch_bounds__(ACQ_WG) void k_acq_detect(rd_acq_args a)
 #pragma unroll
         for (int r = 0; r < 4; r++) mx = fmaxf(mx, fmaxf(fabsf(xr[r].x), fabsf(xr[r].y)));
         mx = wave_max_f32(mx);
-        const int eb = min(max((int)((__float_as_uint(mx) >> 23) & 0xffu), 32), 222);
-        const float sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);          // mx sc in [2^7, 2^8)
-        const float unsc = __uint_as_float((unsigned)(127 - 7 - 12 - 3 + (eb - 127)) << 23);   // undoes sc, stage 1's 2^12, the moments' 2^-7 and stage 2's 2^10
+        float sc, unsc;                                           // mx sc in [2^7, 2^8); unsc undoes sc, stage 1's 2^12, the moments' 2^-7 and stage 2's 2^10
+        operand_scale<12 + 3>(__float_as_uint(mx), sc, unsc);
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int o = lane + 64 * r;
-            if (o < ACQ_SPAN) {
-                _Float16 h0, h1, l0, l1;
-                split16(xr[r].x * sc, h0, l0); split16(xr[r].y * sc, h1, l1);
-                ph[o] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-                pl[o] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-            }
+            if (o < ACQ_SPAN) rx2_split16(make_float2(xr[r].x * sc, xr[r].y * sc), ph[o], pl[o]);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();      // the planes are the wavefront's own: its reads follow its writes
         if (blk < H) load(blk + 1);                               // in flight during the product
@@ -110,44 +90,19 @@ __global__ __launch_bounds__(ACQ_WG) void k_acq_detect(rd_acq_args a)
 #pragma unroll
             for (int u = 0; u < 2; u++) { ahi[rt][u] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; alo[rt][u] = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f }; }
 #pragma unroll
-        for (int s = 0; s < ACQ_NS; s++) {
-            const f16x8 a0h = *(const f16x8 *)(tabQ + ((0 * ACQ_NS + s) * 2 + 0) * 512), a0l = *(const f16x8 *)(tabQ + ((0 * ACQ_NS + s) * 2 + 1) * 512);
-            const f16x8 a1h = *(const f16x8 *)(tabQ + ((1 * ACQ_NS + s) * 2 + 0) * 512), a1l = *(const f16x8 *)(tabQ + ((1 * ACQ_NS + s) * 2 + 1) * 512);
-#pragma unroll
-            for (int rt = 0; rt < ACQ_RT; rt++) alo[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0l, __builtin_bit_cast(f16x8, wh[rt + s]), alo[rt][0], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < ACQ_RT; rt++) alo[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1l, __builtin_bit_cast(f16x8, wh[rt + s]), alo[rt][1], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < ACQ_RT; rt++) alo[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0h, __builtin_bit_cast(f16x8, wl[rt + s]), alo[rt][0], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < ACQ_RT; rt++) alo[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1h, __builtin_bit_cast(f16x8, wl[rt + s]), alo[rt][1], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < ACQ_RT; rt++) ahi[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0h, __builtin_bit_cast(f16x8, wh[rt + s]), ahi[rt][0], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < ACQ_RT; rt++) ahi[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1h, __builtin_bit_cast(f16x8, wh[rt + s]), ahi[rt][1], 0, 0, 0);
+        for (int s = 0; s < RD_CORR_NKS; s++) {
+            const f16x8 a0h = *(const f16x8 *)(tabQ + corrq_frag(0, s, 0)), a0l = *(const f16x8 *)(tabQ + corrq_frag(0, s, 1));
+            const f16x8 a1h = *(const f16x8 *)(tabQ + corrq_frag(1, s, 0)), a1l = *(const f16x8 *)(tabQ + corrq_frag(1, s, 1));
+            corr2_kstep<ACQ_RT>(alo, ahi, a0h, a0l, a1h, a1l, [&](int rt) { return __builtin_bit_cast(f16x8, wh[rt + s]); }, [&](int rt) { return __builtin_bit_cast(f16x8, wl[rt + s]); });
         }
         // ---- stage 2 and the epilogue, one timing tile at a time ----
 #pragma unroll
         for (int rt = 0; rt < ACQ_RT; rt++) {
             const int t = 16 * (T0 + rt) + i;
-            f16x8 mh, mm, ml;                                     // 2^-7 of the tile's moments (|.| below 7100: rade_rx_search.h) in three planes
+            const MomPlanes mp = mom_split_by([&](int j) { return ahi[rt][j >> 2][j & 3] + alo[rt][j >> 2][j & 3]; });
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const float v = 0x1p-7f * (ahi[rt][j >> 2][j & 3] + alo[rt][j >> 2][j & 3]);
-                const _Float16 h = (_Float16)v; const float r1 = v - (float)h;
-                const _Float16 m = (_Float16)r1; const float r2 = r1 - (float)m;
-                mh[j] = h; mm[j] = m; ml[j] = (_Float16)r2;
-            }
-#pragma unroll
-            for (int q = 0; q < ACQ_NQ; q++) {
-                const f16x8 eh = *(const f16x8 *)(tabA2 + (q * 2 + 0) * 512), el = *(const f16x8 *)(tabA2 + (q * 2 + 1) * 512);
-                // C layout: column = lane & 15 (timing), rows 4 g + r = (re, im) of f = 8 q + 2 g and of f + 1
-                f32x4 cc = { 0.0f, 0.0f, 0.0f, 0.0f };
-                cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, ml, cc, 0, 0, 0);
-                cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(el, mm, cc, 0, 0, 0);
-                cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(el, mh, cc, 0, 0, 0);
-                cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, mm, cc, 0, 0, 0);
-                cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(eh, mh, cc, 0, 0, 0);
+            for (int q = 0; q < RD_CORR_NFT; q++) {
+                const f32x4 cc = mom_expand(*(const f16x8 *)(tabA2 + corra_frag(q, 0)), *(const f16x8 *)(tabA2 + corra_frag(q, 1)), mp);
                 const int f = 8 * q + 2 * g;
                 float c[4];
 #pragma unroll

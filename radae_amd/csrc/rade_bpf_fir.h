@@ -34,8 +34,8 @@ __device__ __forceinline__ float bpf_stage_planes(BpfLds *pl, unsigned *maxw, in
     m = wave_max_f32(m);
     if ((tid & 63) == 0) atomicMax(maxw, __float_as_uint(m));
     __syncthreads();
-    const int eb = min(max((int)((*maxw >> 23) & 0xffu), 32), 222);
-    const float sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);          // the largest component lands in [2^7, 2^8) (inside the clamp; below 2^7 / at or above 2^8 outside it: see above)
+    float sc, unsc;                                                                    // operand_scale (rade_devutil.h) is the clamp spoken of above; unsc: 2^(E - 7) from the samples, 2^-10 from the taps
+    operand_scale<10>(*maxw, sc, unsc);
     auto put = [&](int w, float2 v) {
         const float xr = v.x * sc, xi = v.y * sc;
         const _Float16 h0 = (_Float16)xr, h1 = (_Float16)xi;
@@ -47,7 +47,7 @@ __device__ __forceinline__ float bpf_stage_planes(BpfLds *pl, unsigned *maxw, in
     if (tid < BPF_NPL - (102 + 256 * BPF_NQ)) put(102 + 256 * BPF_NQ + tid, make_float2(0.0f, 0.0f));      // the tail the last tile's rows reach into
     if (tid < o) put(BPF_NPL - o + tid, make_float2(0.0f, 0.0f));
     __syncthreads();
-    return __uint_as_float((unsigned)(eb - 7 - 10) << 23);                            // 2^(E - 7) from the samples, 2^-10 from the taps
+    return unsc;
 }
 // outputs 256 tile + 16 (lane & 15) + 4 (lane >> 4) + r, r = 0..3, of the staged window: (re[r], im[r]), still in operand scale
 struct BpfTaps { f16x8 h[4], l[4]; };          // the lane's A fragments (rd_bpf16_table_fill): loaded once, ahead of the staging

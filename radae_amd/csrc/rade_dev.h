@@ -35,6 +35,16 @@ extern "C" {
 #define RD_ENC_IN   96    /* 84 padded to a multiple of 16 (k-block of the f16 matrix instructions) */
 #define RD_RX_ROUND_MAX 128   /* capacity: do_radae_rx calls per stream per sync-kernel launch (engine picks R <= this) */
 #define RD_DEC_ROWS_MAX (3 * RD_RX_ROUND_MAX)
+/* geometry of the two-stage pilot correlator's operand tables (rade_corr2.h explains them and checks the divisions; rade_host.c fills them).  A fragment plane is what
+ * the 64 lanes of one v_mfma_f32_16x16x32_f16 operand hold, 8 binary16 each; every table entry is two of them (hi, lo) */
+#define RD_FRAG_HALFS (64 * 8)
+#define RD_CORR_NRT (2 * RD_NQ / 16)                            /* stage 1, row tiles: 16 of the rows (moment, re | im) */
+#define RD_CORR_NKS (2 * RD_M / 32)                             /* stage 1, k-steps: 32 of the columns (sample, re | im) */
+#define RD_CORR_NFT (2 * RD_NFC / 16)                           /* stage 2, frequency tiles: 16 of the rows (frequency, re | im); below: the binary16 values each of the four operand tables holds */
+#define RD_CORRQ16_HALFS (RD_CORR_NRT * RD_CORR_NKS * 2 * RD_FRAG_HALFS)      /* [row tile][k-step][plane][lane][8] */
+#define RD_CORRA16_HALFS (RD_CORR_NFT * 2 * RD_FRAG_HALFS)                    /* [frequency tile][plane][lane][8] */
+#define RD_WFWD16_HALFS  (2 * RD_CORR_NKS * 2 * RD_FRAG_HALFS)                /* the demodulator DFT: 32 carrier rows over the same K axis */
+#define RD_BPF16_HALFS   (4 * 2 * RD_FRAG_HALFS)
 
 /* constant tables, one copy in HBM (filled by rade_tables.c) */
 typedef struct {

@@ -202,6 +202,15 @@ __device__ __forceinline__ float2 gauss_pair(uint32_t u0, uint32_t u1)
 // a binary32 value as two binary16 planes, x = hi + lo to 22 bits: the operand form of every GEMM on the f16 matrix cores.  (Two outputs: a vector
 // return changed register allocation in the receiver.)
 __device__ __forceinline__ void split16(float x, _Float16 &hi, _Float16 &lo) { hi = (_Float16)x; lo = (_Float16)(x - (float)hi); }
+// The power-of-two scale of a block of such operands, from the float bits mb of the block's largest |component| (biased exponent eb, clamped to [32, 222]): sc puts
+// that component into [2^7, 2^8) -- inside the clamp; rade_bpf_fir.h states what holds outside it --, unsc undoes sc together with the 2^LOG2_TAB of the table the
+// planes are multiplied by (and whatever else the caller folds into that exponent).  The project's one copy of this exponent arithmetic.
+template <int LOG2_TAB> __device__ __forceinline__ void operand_scale(unsigned mb, float &sc, float &unsc)
+{
+    const int eb = min(max((int)((mb >> 23) & 0xffu), 32), 222);
+    sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);
+    unsc = __uint_as_float((unsigned)(127 - 7 - LOG2_TAB + (eb - 127)) << 23);
+}
 // an activation v in [-1, 1] as the two planes of 2^8 v: 2^8 (activations) x 2^10 (packed W), so that the low planes stay normal binary16
 __device__ __forceinline__ void split16_act(float v, _Float16 &hi, _Float16 &lo) { split16(256.0f * v, hi, lo); }
 

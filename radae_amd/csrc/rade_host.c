@@ -462,7 +462,8 @@ long rd_pack_weights_q16_a16(const float *W, const float *row_scale, int N, int 
     return (long)nks * nct * 64 * 8;
 }
 
-/* ---- the pilot correlator in two stages (round 5) -------------------------------------------------------------------------------------------
+/* ---- the pilot correlator in two stages (round 5): the basis and the two tables.  The device side -- operand layouts, scales and the product order, for the search,
+ * check_pilots and whole-file acquisition alike -- is rade_corr2.h; the tables' geometry is RD_CORR_* of rade_dev.h ------------------------------------------------
  * p_w[m][f] = p[m] e^{j w_f m} for the 40 coarse frequencies |f| <= 50 Hz spans a window of 160 samples: the phase e^{j w_f (m - 79.5)} moves by at most
  * +-pi across it, i.e. as a function of x = (m - 79.5) / 80 it is band-limited to a time-bandwidth product of 2 and is reproduced to 1.7e-10 by its
  * projection on the first RD_NQ = 16 polynomials q_r orthonormal on the 160 grid points (14: 1.8e-8, 12: 1.5e-6):

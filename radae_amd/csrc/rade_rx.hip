@@ -8,7 +8,7 @@
 //   k_batch_reset radae_rxe.py:128-142 (and the encoder / decoder start-of-utterance state, one launch)
 //
 // ONE translation unit, one file per stage, included below in the order the stages need each other: rade_rx_dec.h (decoder stage), rade_rx_search.h (pilot
-// search, workgroup reductions), rade_rx_refine.h, rade_rx_check.h, rade_bpf.h (band-pass arithmetic).  This file keeps the per-stream state (RxScalars,
+// search over rade_corr2.h, the correlator it shares with check_pilots and rade_acq.hip; workgroup reductions), rade_rx_refine.h, rade_rx_check.h, rade_bpf.h (band-pass arithmetic).  This file keeps the per-stream state (RxScalars,
 // RxShared2), the developer switches, the decoder hand-over, the kernels and their launch shims.  The band-pass kernels stay in this unit: in a unit of
 // their own they compile to the same code, but k_rx_sync2, left as the only caller of the shared band-pass functions here, does not (tools/codegen_diff.py).
 // Rounds 2-3 carried a second receiver kernel (512 threads, one stream per CU) that this one was forked from; it is gone: one receiver, every fix lands once.
@@ -523,7 +523,7 @@ __global__ __launch_bounds__(NT2, RX2_WG_PER_CU) void k_rx_sync2(rd_sync_args a)
                 // receiver_one (dsp.py:487-526): 160 -> 30 DFT of the six symbols on the f16 matrix cores.  sym[s][c] = sum_n x_s[n] Wfwd[n][c]: with the row
                 // R[c] = (wr, -wi interleaved over n) the real part is R . (xr, xi) and the imaginary part R . (xi, -xr), so the A operand is 32 rows (30 carriers, two
                 // planes, a.wfwd16 from L2) and the B operand twelve columns: the six symbols' window planes as they are, and with every (re, im) pair turned into
-                // (im, -re) in registers (exact).  hi hi + hi lo + lo hi as in check_pilots: 30 matrix instructions per 16-row tile in three independent chains,
+                // (im, -re) in registers (exact).  hi hi + hi lo + lo hi, cross products first (rade_corr2.h's rule): 30 matrix instructions per 16-row tile in three independent chains,
                 // one tile each on wavefronts 0 and 1.  (As vector FMAs -- five lanes per carrier, 32 samples each -- this phase was 9 k cycles, and beside a
                 // second workgroup the vector ALU is what the two compete for: HISTORY.md 3.9.)
                 typedef const __attribute__((address_space(1))) f16x8 glb_f16x8_t;

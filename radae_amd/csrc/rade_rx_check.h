@@ -1,8 +1,8 @@
 // rade_rx_check.h -- acquisition.check_pilots (dsp.py:273-320): the row refreshes of the noise estimate in the synchronised state, 48 pseudo-random timings x
-// {Dt1, Dt2} x 40 frequencies per call (check2_rows_q), by the pilot search's two-stage correlator (rade_rx_search.h: mom_split, mom_expand).
+// {Dt1, Dt2} x 40 frequencies per call (check2_rows_q), by the two-stage correlator of rade_corr2.h (the algebra, the tables, the product order).
 // Part of rade_rx.hip's translation unit.  Members of RxShared2 it reads: rxhl (rx_buf's planes, written by the caller), rows48 (the row draws); it writes
 // rowsum1 / rowsum2 at the drawn rows.
-// check_pilots' row refreshes of one modem frame, NRT tiles of 16 row draws per wavefront, by the two-stage correlator (rx2_detect_q's algebra): the three tiles of 16 row draws against the
+// check_pilots' row refreshes of one modem frame, NRT tiles of 16 row draws per wavefront, by the two-stage correlator: the three tiles of 16 row draws against the
 // moment table (A fragments straight from L2, two k-steps ahead: 40 KB per call and wavefront instead of 60 + 40 over the two wavefronts a frame had), the moments
 // expanded to the 40 frequencies, |Dt| summed over them in the wavefront -> rowsum1 / rowsum2 directly (rounds 3-4: partial sums of two wavefronts through a table and
 // a second barrier).  The gathers: lane (row draw i, group g) needs samples 16 s + 4 g .. + 3 of its window in k-step s, and the windows start at random offsets, so the
@@ -18,8 +18,8 @@ __device__ __forceinline__ void check2_rows_q(RxShared2 *sh, const unsigned shor
 {
     const int i = lane & 15, g = lane >> 4;
     const float rx_unsc = rx_unsc_ * 0x1p-3f;
-    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corrq16_), 0, 2 * 10 * 2048, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corra16_), 0, 5 * 2048, 0x00020000);
+    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corrq16_), 0, RD_CORRQ16_HALFS * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corra16_), 0, RD_CORRA16_HALFS * 2, 0x00020000);
     // four address registers per row tile that the compiler cannot see through: merged into ds_read2_b64 (or an unaligned ds_read_b128) the reads would run at half rate
     lds_cu32x2 *px[NRT][4];
 #pragma unroll
@@ -34,7 +34,7 @@ __device__ __forceinline__ void check2_rows_q(RxShared2 *sh, const unsigned shor
     u32x4 A[DA][4];                                            // [k-step mod DA][2 tile + plane]: DA k-steps of table fragments in flight
     auto fetchA = [&](int slot, int s) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) A[slot][u] = __builtin_amdgcn_raw_buffer_load_b128(qrs, lane * 16, (((u >> 1) * 10 + s) * 2 + (u & 1)) * 1024, 0);
+        for (int u = 0; u < 4; u++) A[slot][u] = __builtin_amdgcn_raw_buffer_load_b128(qrs, lane * 16, corrq_frag(u >> 1, s, u & 1) * 2, 0);
     };
     u32x4 bh[2][NRT], bl[2][NRT];
     auto rows = [&](int slot, int s) {
@@ -47,26 +47,21 @@ __device__ __forceinline__ void check2_rows_q(RxShared2 *sh, const unsigned shor
     for (int d = 0; d < DA; d++) fetchA(d, d);
     pre();
     rows(0, 0);
-    u32x4 A2[2 * 5];                                           // stage 2's fragments [2 q + plane]: requested under the last k-steps
+    constexpr int NKS = RD_CORR_NKS, NTF = RD_CORR_NFT;
+    u32x4 A2[2 * NTF];                                         // stage 2's fragments [2 q + plane]: requested under the last k-steps
 #pragma unroll
-    for (int s = 0; s < 10; s++) {
-        if (s + 1 < 10) rows((s + 1) & 1, s + 1);
+    for (int s = 0; s < NKS; s++) {
+        if (s + 1 < NKS) rows((s + 1) & 1, s + 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            const f16x8 ah = __builtin_bit_cast(f16x8, A[s % DA][2 * nt]), al = __builtin_bit_cast(f16x8, A[s % DA][2 * nt + 1]);
-#pragma unroll
-            for (int rt = 0; rt < NRT; rt++) acc1[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, __builtin_bit_cast(f16x8, bh[s & 1][rt]), acc1[rt][nt], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < NRT; rt++) acc1[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(f16x8, bl[s & 1][rt]), acc1[rt][nt], 0, 0, 0);
-#pragma unroll
-            for (int rt = 0; rt < NRT; rt++) acc1[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(f16x8, bh[s & 1][rt]), acc1[rt][nt], 0, 0, 0);
-        }
+        for (int nt = 0; nt < RD_CORR_NRT; nt++)
+            corr2_kstep_tile<NRT>(acc1, nt, __builtin_bit_cast(f16x8, A[s % DA][2 * nt]), __builtin_bit_cast(f16x8, A[s % DA][2 * nt + 1]),
+                                  [&](int rt) { return __builtin_bit_cast(f16x8, bh[s & 1][rt]); }, [&](int rt) { return __builtin_bit_cast(f16x8, bl[s & 1][rt]); });
         __builtin_amdgcn_sched_barrier(0);
-        if (s + DA < 10) fetchA(s % DA, s + DA);
-        if (s == 10 - DA) {
+        if (s + DA < NKS) fetchA(s % DA, s + DA);
+        if (s == NKS - DA) {
 #pragma unroll
-            for (int u = 0; u < 10; u++) A2[u] = __builtin_amdgcn_raw_buffer_load_b128(ars, lane * 16, u * 1024, 0);
+            for (int u = 0; u < 2 * NTF; u++) A2[u] = __builtin_amdgcn_raw_buffer_load_b128(ars, lane * 16, u * CORR2_FRAG_BYTES, 0);
         }
         side(s);
         __builtin_amdgcn_sched_barrier(0);
@@ -77,16 +72,11 @@ __device__ __forceinline__ void check2_rows_q(RxShared2 *sh, const unsigned shor
         const MomPlanes mp = mom_split(acc1[rt][0], acc1[rt][1]);
         float s = 0.0f;
 #pragma unroll
-        for (int q = 0; q < 5; q++) {      // C layout: column = lane & 15 (row draw), rows 4 g + r = (re, im) of f = 8 q + 2 g and f + 1
+        for (int q = 0; q < NTF; q++) {    // the C tile's columns are the 16 row draws
             const f32x4 c = mom_expand(__builtin_bit_cast(f16x8, A2[2 * q]), __builtin_bit_cast(f16x8, A2[2 * q + 1]), mp);
             s += rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[0], c[0], c[1] * c[1])) + rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[2], c[2], c[3] * c[3]));
         }
-        {   // the other three lane groups hold the row's other frequencies
-            const auto p16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
-            s = __uint_as_float(p16[0]) + __uint_as_float(p16[1]);
-            const auto p32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
-            s = __uint_as_float(p32[0]) + __uint_as_float(p32[1]);
-        }
+        s = corr2_group_sum(s);             // the other three lane groups hold the row's other frequencies
         // (two draws of the same row compute the same sum from the same samples: whichever store lands last, the value is the same)
         if (g == 0) rowsum[sh->rows48[(rt0 + rt) * 16 + i]] = s;
     }

@@ -2,25 +2,11 @@
 // the two-stage correlator rx2_detect_q, and the workgroup reductions every stage of k_rx_sync2 uses (block_argmax2, block_sum_multi2).
 // Part of rade_rx.hip's translation unit, behind RxShared2.  Members of RxShared2 it owns: sA, sA2 (the correlator's tables), srxh / srxl (rx_buf as binary16
 // planes: written by the caller, read here), rowsum1 / rowsum2 (written here, kept across calls), redf / redi / redj slots 1..NW2 and redd (reduction scratch).
+#include "rade_corr2.h"
 // ---- rx_buf as matrix-core operands: two binary16 planes under one power-of-two scale (the pilot search, check_pilots, the demodulator's window) ----
 // The scale comes from the largest component of the filtered samples of this call and the two before it (all rx_buf holds): it lands in [2^7, 2^8).
 // rx_unsc undoes it together with the 2^12 of the correlators' stage-1 table.
-__device__ __forceinline__ void rx2_operand_scale(const RxScalars *S, float &rx_sc, float &rx_unsc)
-{
-    const unsigned mb = max(max(S->rxmax_cur, S->rxmax_h0), S->rxmax_h1);
-    const int eb = min(max((int)((mb >> 23) & 0xffu), 32), 222);
-    rx_sc = __uint_as_float((unsigned)(127 + 7 - (eb - 127)) << 23);
-    rx_unsc = __uint_as_float((unsigned)(127 - 12 - 7 + (eb - 127)) << 23);
-}
-// a scaled sample v = hi + lo (22 bits), (re, im) packed in one word per plane; every caller has its own layout for the two words
-__device__ __forceinline__ void rx2_split16(float2 v, unsigned &hi, unsigned &lo)
-{
-    _Float16 h0, h1, l0, l1;
-    split16(v.x, h0, l0); split16(v.y, h1, l1);
-    hi = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-    lo = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-}
-
+__device__ __forceinline__ void rx2_operand_scale(const RxScalars *S, float &rx_sc, float &rx_unsc) { operand_scale<12>(max(max(S->rxmax_cur, S->rxmax_h0), S->rxmax_h1), rx_sc, rx_unsc); }
 __device__ __forceinline__ float sigma_r_from_sums(double t1, double t2)
 {   // dsp.py:218-220: (mean|Dt1| + mean|Dt2|)/sqrt(pi/2)/2 in float32
     const float k = (float)sqrt(PI_D / 2.0);
@@ -82,74 +68,42 @@ __device__ float sigma_r_from_rowsums2(RxShared2 *sh)
     return sigma_r_from_sums(v[0], v[1]);
 }
 
-// ---- |Dt| surfaces on the matrix cores ----------------------------------------------------------------------------------------------
-// acquisition.detect_pilots (dsp.py:178-231): Dt[t, f] = sum_m conj(rx[t + m]) p_w[m, f] for all 960 timings x 40 frequencies of a frame: a real GEMM
-// [(row, re | im)] x [320 = (m, re | im)] times the Toeplitz matrix rx[t + m] on v_mfma_f32_16x16x32_f16, both operands in two binary16 planes
-// (hi hi + hi lo + lo hi: 22 bits).
+// ---- |Dt| surfaces on the matrix cores: acquisition.detect_pilots (dsp.py:178-231) for all 960 timings x 40 frequencies of a frame, by the two-stage correlator of
+// rade_corr2.h (the algebra, the tables, the product order).  What is the search's own:
 //   * a wavefront owns 15 timing tiles (240 timings) and walks them in groups of RT = 5;
-//   * the A operands (table) are staged through LDS by the whole workgroup, double-buffered, one barrier per stage;
+//   * stage 1's A operands (table) are staged through LDS by the whole workgroup, double-buffered, one barrier per stage of two k-steps;
 //   * the B operand of (timing tile T, k-step s) is the fragment of (T + s, 0): the window slides by one tile per k-step, so a group reads RT + 9 fragments
 //     from the planes instead of 10 RT.
-// (Rounds 3-4 multiplied by the 80 rows of p_w itself: tools/experiments/rx2_search_one_stage.inc.)
-// ---- the pilot correlator in two stages (round 5; the tables and the algebra: rade_host.c, rd_corrq16_table_fill) ----------------------------------
-// Dt[t][f] = sum_r alpha[r][f] Mom_r[t]: stage 1 is the product above with the 32 rows (r, re | im) of the moment table instead of the 80 rows (f, re | im)
-// of p_w -- two row tiles instead of five, 60 matrix instructions per tile of 16 timings instead of 150 --, stage 2 expands the 16 complex moments of a timing
-// tile to the 40 frequencies with ONE k-step (K = 32) per frequency tile.  Stage 1's accumulators ARE stage 2's B operand: the C layout of two 16-row tiles
-// gives lane group g rows 4 g .. 4 g + 3 of either tile, and the host orders stage 2's K axis exactly so (rd_corra16_table_fill) -- the moments are scaled,
-// split into three binary16 planes (33 bits: stage 2 adds nothing to stage 1's rounding) and fed back without leaving the lane.
-struct MomPlanes { f16x8 h, m, l; };
-__device__ __forceinline__ MomPlanes mom_split(const f32x4 a0, const f32x4 a1)
-{
-    MomPlanes p;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {      // |moment| <= 2^8 sqrt(2) x the table row's L1 norm (3545 x 2^... : rade_host.c) -> 2^-7 of it is below 7100, far inside binary16
-        const float v = 0x1p-7f * (j < 4 ? a0[j & 3] : a1[j & 3]);
-        const _Float16 h = (_Float16)v; const float r1 = v - (float)h;
-        const _Float16 m = (_Float16)r1; const float r2 = r1 - (float)m;
-        p.h[j] = h; p.m[j] = m; p.l[j] = (_Float16)r2;
-    }
-    return p;
-}
-// one frequency tile (8 frequencies x (re, im)) of Dt for the 16 timings whose moments are in p: smallest partial products first
-__device__ __forceinline__ f32x4 mom_expand(const f16x8 ah, const f16x8 al, const MomPlanes &p)
-{
-    f32x4 c = { 0.0f, 0.0f, 0.0f, 0.0f };
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, p.l, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, p.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, p.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, p.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, p.h, c, 0, 0, 0);
-    return c;
-}
-// acquisition.detect_pilots' surfaces by the two-stage correlator: the one-stage form's contract (outputs: |Dt2| -- and |Dt1| when not cached -- to the stream's
-// cache in HBM, the row sums to rowsum1 / rowsum2, the lane's best (Dt1 + Dt2, t, f)).  rx_unsc undoes the scales of the rx planes and the stage-1 table; the
-// 2^-7 of the moments and the 2^10 of the stage-2 table are undone here.
+// Outputs: |Dt2| -- and |Dt1| when not cached -- to the stream's cache in HBM, the row sums to rowsum1 / rowsum2, the lane's best (Dt1 + Dt2, t, f).  rx_unsc undoes
+// the scales of the rx planes and the stage-1 table; the 2^-7 of the moments and the 2^10 of the stage-2 table are undone here.
 __device__ __forceinline__ void rx2_detect_q(RxShared2 *sh, const unsigned short *corrq16_, const unsigned short *corra16_, float *cache_, int cached, int oldb, int newb,
                                              float rx_unsc_, float &best, int &bt, int &bfi)
 {
-    constexpr int RT = 5, NTF = 5, TPW = 15;
+    constexpr int RT = 5, NTF = RD_CORR_NFT, NKS = RD_CORR_NKS, TPW = 15;
     static_assert(TPW * NW2 * 16 == RD_NMF && TPW % RT == 0, "timing tiles per wavefront");
+    static_assert(NKS % 2 == 0 && NT2 == 4 * 64, "a stage of two k-steps of both row tiles = 8 fragment planes: two 16-byte chunks per thread");
     const int tid = rx_tid(), wave = rx2_wave(), lane = tid & 63, i = lane & 15, g = lane >> 4;
     const float rx_unsc = rx_unsc_ * 0x1p-3f;
     // stage 1's table [tile][k-step][plane][lane] (16 B per lane): a stage buffer holds two k-steps of both tiles, chunk u = 256 tile + 128 (k-step & 1) + 64 plane + lane,
     // i.e. thread tid brings chunks tid and 256 + tid: one lane offset under two uniform bases
-    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corrq16_), 0, 2 * 10 * 2048, 0x00020000);
+    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corrq16_), 0, RD_CORRQ16_HALFS * 2, 0x00020000);
     const int vo = tid * 16;
     u32x4 stg[2];
     auto stage_load = [&](int sb) {
-        stg[0] = __builtin_amdgcn_raw_buffer_load_b128(qrs, vo, sb * 4096, 0); stg[1] = __builtin_amdgcn_raw_buffer_load_b128(qrs, vo, sb * 4096 + 10 * 2048, 0);
+        stg[0] = __builtin_amdgcn_raw_buffer_load_b128(qrs, vo, corrq_frag(0, 2 * sb, 0) * 2, 0); stg[1] = __builtin_amdgcn_raw_buffer_load_b128(qrs, vo, corrq_frag(1, 2 * sb, 0) * 2, 0);
     };
-    auto stage_store = [&](int buf) { _Float16 *d = &sh->sA[buf][tid * 8]; *(u32x4 *)d = stg[0]; *(u32x4 *)(d + 256 * 8) = stg[1]; };
+    auto stage_store = [&](int buf) { _Float16 *d = &sh->sA[buf][tid * 8]; *(u32x4 *)d = stg[0]; *(u32x4 *)(d + 4 * RD_FRAG_HALFS) = stg[1]; };
     PH2_T0();
-    {   // stage 2's table, whole (640 x 16 B)
-        const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corra16_), 0, 5 * 2048, 0x00020000);
-        const u32x4 t0 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 0, 0), t1 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 4096, 0);
+    {   // stage 2's table, whole: 10 fragment planes = 640 x 16 B, four planes per round of the workgroup
+        static_assert(RD_CORRA16_HALFS == 10 * RD_FRAG_HALFS, "two rounds of all four wavefronts and one of two");
+        const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)uni_ptr(corra16_), 0, RD_CORRA16_HALFS * 2, 0x00020000);
+        const u32x4 t0 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 0, 0), t1 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 4 * CORR2_FRAG_BYTES, 0);
         u32x4 t2 = { 0u, 0u, 0u, 0u };
-        if (wave < 2) t2 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 8192, 0);
+        if (wave < 2) t2 = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 8 * CORR2_FRAG_BYTES, 0);
         stage_load(0);
         _Float16 *d = &sh->sA2[tid * 8];
-        *(u32x4 *)d = t0; *(u32x4 *)(d + 256 * 8) = t1;
-        if (wave < 2) *(u32x4 *)(d + 512 * 8) = t2;
+        *(u32x4 *)d = t0; *(u32x4 *)(d + 4 * RD_FRAG_HALFS) = t1;
+        if (wave < 2) *(u32x4 *)(d + 8 * RD_FRAG_HALFS) = t2;
         stage_store(0);
     }
     float lbest = best; int lkey = 0x7fffffff;
@@ -174,36 +128,24 @@ __device__ __forceinline__ void rx2_detect_q(RxShared2 *sh, const unsigned short
 #pragma unroll
                 for (int j = 0; j < 4; j++) { wh[rt][j] = ph[16 * (T0 + rt) + j]; wl[rt][j] = pl[16 * (T0 + rt) + j]; }
 #pragma unroll
-            for (int sb = 0; sb < 5; sb++) {
-                stage_load(sb == 4 ? 0 : sb + 1);
+            for (int sb = 0; sb < NKS / 2; sb++) {
+                stage_load(sb == NKS / 2 - 1 ? 0 : sb + 1);
 #pragma unroll
                 for (int ds = 0; ds < 2; ds++) {
                     const int sidx = 2 * sb + ds;
                     // fragment F of the sliding window lives in slot (F - T0) mod (RT + 1): tile rt reads slot (rt + sidx) mod (RT + 1), the fragment the NEXT k-step adds goes
                     // into the slot the first tile just left (all indices are compile-time: the loops are unrolled).  Rounds 3-4 shifted the window through the registers
                     // instead: 40 moves per k-step behind the matrix instructions
-                    if (sidx < 9) {
+                    if (sidx < NKS - 1) {
 #pragma unroll
                         for (int j = 0; j < 4; j++) { wh[(RT + sidx) % (RT + 1)][j] = ph[16 * (T0 + RT + sidx) + j]; wl[(RT + sidx) % (RT + 1)][j] = pl[16 * (T0 + RT + sidx) + j]; }
                     }
-                    const _Float16 *Ab = &sh->sA[pb][lane * 8];
-                    const f16x8 a0h = *(const f16x8 *)(Ab + ((0 * 2 + ds) * 2 + 0) * 512), a0l = *(const f16x8 *)(Ab + ((0 * 2 + ds) * 2 + 1) * 512);
-                    const f16x8 a1h = *(const f16x8 *)(Ab + ((1 * 2 + ds) * 2 + 0) * 512), a1l = *(const f16x8 *)(Ab + ((1 * 2 + ds) * 2 + 1) * 512);
+                    const _Float16 *Ab = &sh->sA[pb][lane * 8];          // the stage buffer: [row tile][k-step & 1][plane][lane][8]
+                    const f16x8 a0h = *(const f16x8 *)(Ab + ((0 * 2 + ds) * 2 + 0) * RD_FRAG_HALFS), a0l = *(const f16x8 *)(Ab + ((0 * 2 + ds) * 2 + 1) * RD_FRAG_HALFS);
+                    const f16x8 a1h = *(const f16x8 *)(Ab + ((1 * 2 + ds) * 2 + 0) * RD_FRAG_HALFS), a1l = *(const f16x8 *)(Ab + ((1 * 2 + ds) * 2 + 1) * RD_FRAG_HALFS);
                     __builtin_amdgcn_sched_barrier(0);
-#define WSL(rt) (((rt) + sidx) % (RT + 1))
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0l, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][0], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1l, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][1], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0h, __builtin_bit_cast(f16x8, wl[WSL(rt)]), acc1[rt][0], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1h, __builtin_bit_cast(f16x8, wl[WSL(rt)]), acc1[rt][1], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0h, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][0], 0, 0, 0);
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) acc1[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1h, __builtin_bit_cast(f16x8, wh[WSL(rt)]), acc1[rt][1], 0, 0, 0);
-#undef WSL
+                    corr2_kstep<RT>(acc1, acc1, a0h, a0l, a1h, a1l, [&](int rt) { return __builtin_bit_cast(f16x8, wh[(rt + sidx) % (RT + 1)]); },
+                                    [&](int rt) { return __builtin_bit_cast(f16x8, wl[(rt + sidx) % (RT + 1)]); });
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 stage_store(pb ^ 1);
@@ -216,7 +158,7 @@ __device__ __forceinline__ void rx2_detect_q(RxShared2 *sh, const unsigned short
             // then the two frequencies) as two 16-byte vectors [lane] + one 8-byte vector [lane]: fully coalesced.
             f16x8 A2h[NTF], A2l[NTF];
 #pragma unroll
-            for (int q = 0; q < NTF; q++) { A2h[q] = *(const f16x8 *)&sh->sA2[((q * 2) * 64 + lane) * 8]; A2l[q] = *(const f16x8 *)&sh->sA2[((q * 2 + 1) * 64 + lane) * 8]; }
+            for (int q = 0; q < NTF; q++) { A2h[q] = *(const f16x8 *)&sh->sA2[corra_frag(q, 0) + lane * 8]; A2l[q] = *(const f16x8 *)&sh->sA2[corra_frag(q, 1) + lane * 8]; }
             const int gb = (wave * (TPW / RT) + grp) * RT * 2560;         // byte offset of the group's block; 2560 B per timing tile
             float pv[2][2 * NTF];
             auto pv_load = [&](int slot, int rt) {
@@ -235,18 +177,12 @@ __device__ __forceinline__ void rx2_detect_q(RxShared2 *sh, const unsigned short
                 float dd[2 * NTF], rs = 0.0f;
 #pragma unroll
                 for (int q = 0; q < NTF; q++) {
-                    // C layout: column = lane & 15 (timing), rows 4 g + r = (re, im) of f = 8 q + 2 g and f + 1
                     const f32x4 c = mom_expand(A2h[q], A2l[q], mp);
                     const float d0 = rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[0], c[0], c[1] * c[1])), d1 = rx_unsc * __builtin_amdgcn_sqrtf(fmaf(c[2], c[2], c[3] * c[3]));
                     rs += d0; rs += d1;
                     dd[2 * q] = d0; dd[2 * q + 1] = d1;
                 }
-                {   // the other three lane groups hold the row's other frequencies: v_permlane16/32_swap (vector ALU, no LDS round trip)
-                    const auto p16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(rs), __float_as_uint(rs), false, false);
-                    rs = __uint_as_float(p16[0]) + __uint_as_float(p16[1]);
-                    const auto p32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(rs), __float_as_uint(rs), false, false);
-                    rs = __uint_as_float(p32[0]) + __uint_as_float(p32[1]);
-                }
+                rs = corr2_group_sum(rs);                                  // the other three lane groups hold the row's other frequencies
                 __builtin_amdgcn_raw_buffer_store_b128((u32x4){ __float_as_uint(dd[0]), __float_as_uint(dd[1]), __float_as_uint(dd[2]), __float_as_uint(dd[3]) }, drs, lane * 16, gb + rt * 2560, 0);
                 __builtin_amdgcn_raw_buffer_store_b128((u32x4){ __float_as_uint(dd[4]), __float_as_uint(dd[5]), __float_as_uint(dd[6]), __float_as_uint(dd[7]) }, drs, lane * 16, gb + rt * 2560 + 1024, 0);
                 __builtin_amdgcn_raw_buffer_store_b64((u32x2){ __float_as_uint(dd[8]), __float_as_uint(dd[9]) }, drs, lane * 8, gb + rt * 2560 + 2048, 0);

@@ -860,7 +860,6 @@ int rade_batch_sigstat(rade_batch *h, const void *x_dev, long x_stride, const in
 
 /* ---- whole-file pilot acquisition: every hop of rx.py's frame loop, and acquisition.refine for a list of events (rade_acq.hip; the state machine and the statistics:
  * rade_host.c) ---------------------------------------------------------------------------------------------------------------------------------------------------- */
-_Static_assert(RD_CORRQ16_HALFS == 2 * 10 * 2 * 64 * 8 && RD_CORRA16_HALFS == 5 * 2 * 64 * 8, "the table sizes k_acq_detect copies to LDS (rade_acq.hip)");
 int rade_batch_acq_detect(rade_batch *h, const void *x_dev, long x_stride, const int *n_host, double Pacq_error1, rade_acq_hop *hops_host, int max_hops, int *n_hops_host,
                           void *dt_dev, long long t0, int n_rows, void *stream)
 {
