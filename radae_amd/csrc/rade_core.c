@@ -15,6 +15,7 @@
 #include "rade_core.h"
 #include "rade_host.h"
 #include "rade_dev.h"
+static_assert(RADE_LATENT_DIM == RM_LATENT, "the public header's latent width is the model's");
 
 /* hidden record BEHIND the NULL terminator of every list rade_parse_weights() returns: where the blob lives.  *list is the
  * malloc'ed pointer itself, so the reference harnesses' free(list) (test_rade_enc.c:115, test_rade_dec.c:115) is valid. */
@@ -88,16 +89,16 @@ static int init_model(const WeightArray *arrays, int dim, const void **blob, int
     if (list_blob(arrays, blob, len)) return 1;
     WeightArray *l = NULL;
     if (rade_parse_weights(&l, *blob, *len) < 0) return 1;
-    /* the dimension the blob was exported with: enc_dense1 is (input_dim x 64) floats, dec_output has output_dim biases */
+    /* the dimension the blob was exported with: enc_dense1 is (input_dim x RM_ENC_D1) floats, dec_output has output_dim biases */
     const int w = find_array(l, "enc_dense1_weights_float"), b = find_array(l, "dec_output_bias");
     free(l);
-    if (w != dim * 64 * 4 || b != dim * 4) return 1;
+    if (w != dim * RM_ENC_D1 * 4 || b != dim * 4) return 1;
     return 0;
 }
 
 int init_radeenc(RADEEnc *model, const WeightArray *arrays, int input_dim)
 {
-    if (!model || (input_dim != 80 && input_dim != 84)) return 1;
+    if (!model || (input_dim != RM_FEAT && input_dim != RM_FEAT_AUX)) return 1;
     memset(model, 0, sizeof *model);
     if (init_model(arrays, input_dim, &model->blob, &model->blob_len)) return 1;
     model->input_dim = input_dim; model->nb_z = RADE_LATENT_DIM;
@@ -106,7 +107,7 @@ int init_radeenc(RADEEnc *model, const WeightArray *arrays, int input_dim)
 
 int init_radedec(RADEDec *model, const WeightArray *arrays, int output_dim)
 {
-    if (!model || (output_dim != 80 && output_dim != 84)) return 1;
+    if (!model || (output_dim != RM_FEAT && output_dim != RM_FEAT_AUX)) return 1;
     memset(model, 0, sizeof *model);
     if (init_model(arrays, output_dim, &model->blob, &model->blob_len)) return 1;
     model->output_dim = output_dim; model->nb_z = RADE_LATENT_DIM;
@@ -187,36 +188,35 @@ static core_dev *dev_open(const void *blob, int len, int dim, int enc)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fprintf(stderr, "rade_core: no HIP device available -- this library has no CPU fallback\n"); free(d); return NULL; }
     rd_model m;
     if (hipSetDevice(d->device) != hipSuccess || rd_model_parse(blob, (size_t)len, &m)) { free(d); return NULL; }
-    static const int ENC_DIL_[5] = { 1, 2, 2, 2, 2 };
     rd_core_args *a = &d->a;
     int e = 0;
     a->is_enc = enc;
     if (enc) {
-        a->n_in = dim; a->n_out = RADE_LATENT_DIM; a->W = 864; a->H = 64; a->in0 = 64; a->conv_out = 96;
-        e |= core_layer(d, &a->dense1, m.enc_dense1.w, m.enc_dense1.b, NULL, 64, m.enc_dense1.n_in, 0);
-        e |= core_layer(d, &a->out, m.enc_zdense.w, m.enc_zdense.b, NULL, 80, 864, 0);
-        for (int l = 0; l < 5 && !e; l++) {
-            a->dil[l] = ENC_DIL_[l];
-            e |= core_layer(d, &a->gin[l], m.enc_gru[l].w_ih, m.enc_gru[l].b_ih, m.enc_gru[l].s_ih, 192, m.enc_gru[l].n_in, 1);
-            e |= core_layer(d, &a->ghh[l], m.enc_gru[l].w_hh, m.enc_gru[l].b_hh, m.enc_gru[l].s_hh, 192, 64, 1);
-            e |= core_layer(d, &a->conv[l], m.enc_conv[l].w, m.enc_conv[l].b, m.enc_conv[l].row_scale, 96, m.enc_conv[l].n_in, 1);
+        a->n_in = dim; a->n_out = RADE_LATENT_DIM; a->W = RM_ENC_W; a->H = RM_ENC_H; a->in0 = RM_ENC_D1; a->conv_out = RM_ENC_CONV;
+        e |= core_layer(d, &a->dense1, m.enc_dense1.w, m.enc_dense1.b, NULL, RM_ENC_D1, m.enc_dense1.n_in, 0);
+        e |= core_layer(d, &a->out, m.enc_zdense.w, m.enc_zdense.b, NULL, RM_LATENT, RM_ENC_W, 0);
+        for (int l = 0; l < RM_NL && !e; l++) {
+            a->dil[l] = RM_ENC_DIL(l);
+            e |= core_layer(d, &a->gin[l], m.enc_gru[l].w_ih, m.enc_gru[l].b_ih, m.enc_gru[l].s_ih, RM_ENC_G, m.enc_gru[l].n_in, 1);
+            e |= core_layer(d, &a->ghh[l], m.enc_gru[l].w_hh, m.enc_gru[l].b_hh, m.enc_gru[l].s_hh, RM_ENC_G, RM_ENC_H, 1);
+            e |= core_layer(d, &a->conv[l], m.enc_conv[l].w, m.enc_conv[l].b, m.enc_conv[l].row_scale, RM_ENC_CONV, m.enc_conv[l].n_in, 1);
         }
     } else {
-        a->n_in = RADE_LATENT_DIM; a->n_out = dim; a->W = 736; a->H = 96; a->in0 = 96; a->conv_out = 32;
-        e |= core_layer(d, &a->dense1, m.dec_dense1.w, m.dec_dense1.b, NULL, 96, 80, 0);
-        e |= core_layer(d, &a->out, m.dec_output.w, m.dec_output.b, NULL, m.dec_output.n_out, 736, 0);
-        for (int l = 0; l < 5 && !e; l++) {
+        a->n_in = RADE_LATENT_DIM; a->n_out = dim; a->W = RM_DEC_W; a->H = RM_DEC_H; a->in0 = RM_DEC_D1; a->conv_out = RM_DEC_CONV;
+        e |= core_layer(d, &a->dense1, m.dec_dense1.w, m.dec_dense1.b, NULL, RM_DEC_D1, RM_LATENT, 0);
+        e |= core_layer(d, &a->out, m.dec_output.w, m.dec_output.b, NULL, m.dec_output.n_out, RM_DEC_W, 0);
+        for (int l = 0; l < RM_NL && !e; l++) {
             a->dil[l] = 1;
-            e |= core_layer(d, &a->gin[l], m.dec_gru[l].w_ih, m.dec_gru[l].b_ih, m.dec_gru[l].s_ih, 288, m.dec_gru[l].n_in, 1);
-            e |= core_layer(d, &a->ghh[l], m.dec_gru[l].w_hh, m.dec_gru[l].b_hh, m.dec_gru[l].s_hh, 288, 96, 1);
-            e |= core_layer(d, &a->glu[l], m.dec_glu[l].w, NULL, m.dec_glu[l].row_scale, 96, 96, 1);
-            e |= core_layer(d, &a->conv[l], m.dec_conv[l].w, m.dec_conv[l].b, m.dec_conv[l].row_scale, 32, m.dec_conv[l].n_in, 1);
+            e |= core_layer(d, &a->gin[l], m.dec_gru[l].w_ih, m.dec_gru[l].b_ih, m.dec_gru[l].s_ih, RM_DEC_G, m.dec_gru[l].n_in, 1);
+            e |= core_layer(d, &a->ghh[l], m.dec_gru[l].w_hh, m.dec_gru[l].b_hh, m.dec_gru[l].s_hh, RM_DEC_G, RM_DEC_H, 1);
+            e |= core_layer(d, &a->glu[l], m.dec_glu[l].w, NULL, m.dec_glu[l].row_scale, RM_DEC_GLU, RM_DEC_H, 1);
+            e |= core_layer(d, &a->conv[l], m.dec_conv[l].w, m.dec_conv[l].b, m.dec_conv[l].row_scale, RM_DEC_CONV, m.dec_conv[l].n_in, 1);
         }
     }
     if (!e && (enc ? m.enc_dense1.n_in : m.dec_output.n_out) != dim) e = -1;
     rd_model_free(&m);
     a->hist = core_upload(d, NULL, sizeof(float) * 2 * a->W);          /* zero state = rade_init_encoder / rade_init_decoder */
-    a->h = core_upload(d, NULL, sizeof(float) * 5 * a->H);
+    a->h = core_upload(d, NULL, sizeof(float) * RM_NL * a->H);
     if (e || !a->hist || !a->h || hipStreamCreate(&d->gs) != hipSuccess ||
         hipHostMalloc((void **)&d->h_in, sizeof(float) * 96, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostMalloc((void **)&d->h_out, sizeof(float) * 128, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -268,8 +268,8 @@ void *rd_core_tx_open(const void *blob, int len, const rd_tables *d_tab)
 {
     tx_dev *t = calloc(1, sizeof *t);
     if (!t) return NULL;
-    t->d = dev_open(blob, len, 84, 1);
-    if (!t->d || hipHostMalloc((void **)&t->h_in, sizeof(float) * 3 * 84, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+    t->d = dev_open(blob, len, RM_FEAT_AUX, 1);
+    if (!t->d || hipHostMalloc((void **)&t->h_in, sizeof(float) * 3 * RM_FEAT_AUX, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostMalloc((void **)&t->h_iq, sizeof(float) * 2 * RD_NMF + 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { rd_core_tx_close(t); (void)hipGetLastError(); return NULL; }
     rd_core_args *a = &t->d->a;
     void *dp = NULL;
@@ -283,15 +283,16 @@ void *rd_core_tx_open(const void *blob, int len, const rd_tables *d_tab)
     if (hipMalloc((void **)&t->a_dev, sizeof *a) != hipSuccess || hipMemcpy(t->a_dev, a, sizeof *a, hipMemcpyHostToDevice) != hipSuccess) { rd_core_tx_close(t); return NULL; }
     return t;
 }
-/* features_in: 12 frames x 36 floats (rade_api.c:426-434 packs the first 20 of each + the aux symbol -1 into three rows of 4 x 21); tx_out: 960 complex samples */
+/* features_in: 12 frames x RM_FILE_FRAME floats (rade_api.c:426-434 packs the first RM_NFEAT of each + the aux symbol -1 into three rows of 4 x 21); tx_out: 960 complex samples */
 int rd_core_tx_frame(void *p, const float *features_in, float *tx_out)
 {
     tx_dev *t = p; core_dev *d = t->d;
     if (hipSetDevice(d->device) != hipSuccess) return -1;
     for (int c = 0; c < 3; c++)
-        for (int i = 0; i < 4; i++) {
-            memcpy(t->h_in + c * 84 + i * 21, features_in + (c * 4 + i) * 36, sizeof(float) * 20);
-            t->h_in[c * 84 + i * 21 + 20] = -1.0f;
+        for (int i = 0; i < RM_STEP_FRAMES; i++) {
+            float *row = t->h_in + c * RM_FEAT_AUX + i * (RM_NFEAT + 1);
+            memcpy(row, features_in + (c * RM_STEP_FRAMES + i) * RM_FILE_FRAME, sizeof(float) * RM_NFEAT);
+            row[RM_NFEAT] = -1.0f;
         }
     volatile unsigned *done = (volatile unsigned *)t->done;
     d->a.seq++;
@@ -313,7 +314,7 @@ static void core_reset(int *initialized, void **dev)
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipMemsetAsync(d->a.hist, 0, sizeof(float) * 2 * d->a.W, d->gs);
-    (void)hipMemsetAsync(d->a.h, 0, sizeof(float) * 5 * d->a.H, d->gs);
+    (void)hipMemsetAsync(d->a.h, 0, sizeof(float) * RM_NL * d->a.H, d->gs);
     (void)hipStreamSynchronize(d->gs);
 }
 void rade_reset_encoder(RADEEncState *s) { if (s) core_reset(&s->initialized, &s->dev); }

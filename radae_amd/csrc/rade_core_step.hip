@@ -22,7 +22,9 @@
 #define CS_THREADS 512
 #define CS_WAVES (CS_THREADS / 64)
 #define CS_PS 320                 // row stride of a partial-sum area: 288 rows padded to 5 x 64
-#define CS_WMAX 864
+#define CS_WMAX RM_ENC_W           // the wider of the two concat rows
+#define CS_VIN RD_ENC_IN          // the input vector, zero padded: dense1's K in whole chunks
+static_assert(RM_ENC_W >= RM_DEC_W && RM_DEC_H >= RM_ENC_H && CS_VIN >= RM_FEAT_AUX && CS_VIN >= RM_LATENT && RM_DEC_G <= CS_PS, "one LDS layout serves the encoder and the decoder");
 
 // weights are read through pointers that k_tx_frame3 loads from a record in device memory: generic pointers, i.e. flat loads, which count on
 // the LDS wait counter too -- every LDS wait of a stage then also waited for the weight prefetch of the next.  They ARE global memory: say so.
@@ -31,10 +33,10 @@ template <typename T> __device__ __forceinline__ T cs_gload(const T *p) { return
 struct CsShared {
     __attribute__((aligned(16))) float x[CS_WMAX];            // the DenseNet concat row of this step
     __attribute__((aligned(16))) float hist[2][CS_WMAX];      // rows t-1, t-2 (conv taps, dilation 1 or 2)
-    __attribute__((aligned(16))) float vin[96];               // input vector, zero padded to dense1's K
-    __attribute__((aligned(16))) float h[5][96];              // GRU states at entry
-    __attribute__((aligned(16))) float hc[96];                // clamp(h') of the layer at hand (decoder GLU operand)
-    __attribute__((aligned(16))) float gh[288];               // W_hh h + b_hh of the layer at hand
+    __attribute__((aligned(16))) float vin[CS_VIN];           // input vector, zero padded to dense1's K
+    __attribute__((aligned(16))) float h[RM_NL][RM_DEC_H];    // GRU states at entry
+    __attribute__((aligned(16))) float hc[RM_DEC_H];          // clamp(h') of the layer at hand (decoder GLU operand)
+    __attribute__((aligned(16))) float gh[RM_DEC_G];          // W_hh h + b_hh of the layer at hand
     __attribute__((aligned(16))) float pa[CS_WAVES][CS_PS];   // per-wave partial sums, product A of a stage
     __attribute__((aligned(16))) float pb[CS_WAVES][CS_PS];   // product B (the next layer's W_hh h, riding along)
 };
@@ -156,7 +158,7 @@ __device__ __forceinline__ void cs_done(unsigned *done, unsigned seq) { if (thre
 template <int GCI, int CCI, int GNEXT, bool LAST>
 __device__ __forceinline__ void cs_enc_layer(CsShared *sh, const rd_core_args &a, int l, int n, WQ<3, GCI> &gq, WQ<3, GNEXT> &gnext)
 {
-    const int tid = threadIdx.x, H = 64;
+    const int tid = threadIdx.x, H = RM_ENC_H;
     WQ<2, CCI> cq; WQ<3, 1> hq;
     cs_consume<3, GCI>(a.gin[l], gq, sh->x, n, sh->x, sh->pa);
     cs_issue<2, CCI>(a.conv[l], cq);                               // this layer's conv and the next layer's W_hh h: in flight across the gate stage
@@ -182,12 +184,12 @@ __device__ __forceinline__ void cs_enc_layer(CsShared *sh, const rd_core_args &a
 // in: the step's n_in inputs; zout: its 80 latents (any address space the workgroup can write)
 __device__ __forceinline__ void cs_enc_step(CsShared *sh, const rd_core_args &a, const float *in, float *zout)
 {
-    const int tid = threadIdx.x, W = 864, H = 64;
+    const int tid = threadIdx.x, W = RM_ENC_W, H = RM_ENC_H;
     WQ<3, 1> g0, h0;               // (this prologue, up to the layers, stands in k_tx_frame3 too: as one function over the row count k_tx_frame3 changed)
     cs_issue<3, 1>(a.gin[0], g0); cs_issue<3, 1>(a.ghh[0], h0);
     for (int i = tid; i < 2 * W; i += CS_THREADS) sh->hist[i / W][i % W] = a.hist[i];
-    if (tid < 5 * H) sh->h[tid / H][tid % H] = a.h[tid];
-    if (tid < 96) sh->vin[tid] = tid < a.n_in ? in[tid] : 0.0f;
+    if (tid < RM_NL * H) sh->h[tid / H][tid % H] = a.h[tid];
+    if (tid < CS_VIN) sh->vin[tid] = tid < a.n_in ? in[tid] : 0.0f;
     __syncthreads();
     cs_f32_product<2>(a.dense1, 1, sh->vin, sh->pa);                // dense1 + tanh (radae_base.py:263)
     cs_consume<3, 1>(a.ghh[0], h0, sh->h[0], H, sh->h[0], sh->pb);
@@ -196,11 +198,11 @@ __device__ __forceinline__ void cs_enc_step(CsShared *sh, const rd_core_args &a,
     else if (tid >= 128 && tid < 128 + 3 * H) sh->gh[tid - 128] = cs_row(a.ghh[0], sh->pb, tid - 128);
     __syncthreads();
     WQ<3, 4> g1; WQ<3, 6> g2; WQ<3, 9> g3; WQ<3, 11> g4;
-    cs_enc_layer<1, 4, 4, false>(sh, a, 0, 64, g0, g1);
-    cs_enc_layer<4, 9, 6, false>(sh, a, 1, 224, g1, g2);
-    cs_enc_layer<6, 14, 9, false>(sh, a, 2, 384, g2, g3);
-    cs_enc_layer<9, 19, 11, false>(sh, a, 3, 544, g3, g4);
-    cs_enc_layer<11, 24, 11, true>(sh, a, 4, 704, g4, g4);
+    cs_enc_layer<1, 4, 4, false>(sh, a, 0, RM_ENC_GRU_IN(0), g0, g1);
+    cs_enc_layer<4, 9, 6, false>(sh, a, 1, RM_ENC_GRU_IN(1), g1, g2);
+    cs_enc_layer<6, 14, 9, false>(sh, a, 2, RM_ENC_GRU_IN(2), g2, g3);
+    cs_enc_layer<9, 19, 11, false>(sh, a, 3, RM_ENC_GRU_IN(3), g3, g4);
+    cs_enc_layer<11, 24, 11, true>(sh, a, 4, RM_ENC_GRU_IN(4), g4, g4);
     cs_f32_product<14>(a.out, 2, sh->x, sh->pa);                    // z_dense, linear (bottleneck 3; the tanh of bottleneck 1 is the caller's)
     for (int i = tid; i < W; i += CS_THREADS) { a.hist[W + i] = sh->hist[0][i]; a.hist[i] = sh->x[i]; }      // history of the next step
     __syncthreads();
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(CS_THREADS) void k_core_enc_step(rd_core_args a)
 template <int GCI, int CCI, int GNEXT, bool LAST>
 __device__ __forceinline__ void cs_dec_layer(CsShared *sh, const rd_core_args &a, int l, int n, WQ<5, GCI> &gq, WQ<5, GNEXT> &gnext)
 {
-    const int tid = threadIdx.x, H = 96;
+    const int tid = threadIdx.x, H = RM_DEC_H;
     WQ<2, 2> uq; WQ<1, CCI> cq; WQ<5, 2> hq;
     cs_consume<5, GCI>(a.gin[l], gq, sh->x, n, sh->x, sh->pa);
     cs_issue<2, 2>(a.glu[l], uq); cs_issue<1, CCI>(a.conv[l], cq);
@@ -252,12 +254,12 @@ __global__ __launch_bounds__(CS_THREADS) void k_core_dec_step(rd_core_args a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char cs_raw[];
     CsShared *sh = (CsShared *)cs_raw;
-    const int tid = threadIdx.x, W = 736, H = 96;
+    const int tid = threadIdx.x, W = RM_DEC_W, H = RM_DEC_H;
     WQ<5, 2> g0, h0;
     cs_issue<5, 2>(a.gin[0], g0); cs_issue<5, 2>(a.ghh[0], h0);
     for (int i = tid; i < W; i += CS_THREADS) sh->hist[0][i] = a.hist[i];
-    if (tid < 96) sh->vin[tid] = tid < a.n_in ? a.in[tid] : 0.0f;
-    if (tid < 5 * H) sh->h[tid / H][tid % H] = a.h[tid];
+    if (tid < CS_VIN) sh->vin[tid] = tid < a.n_in ? a.in[tid] : 0.0f;
+    if (tid < RM_NL * H) sh->h[tid / H][tid % H] = a.h[tid];
     __syncthreads();
     cs_f32_product<2>(a.dense1, 2, sh->vin, sh->pa);                // dense1 + tanh (radae_base.py:403)
     cs_consume<5, 2>(a.ghh[0], h0, sh->h[0], H, sh->h[0], sh->pb);
@@ -266,11 +268,11 @@ __global__ __launch_bounds__(CS_THREADS) void k_core_dec_step(rd_core_args a)
     else if (tid >= 128 && tid < 128 + 3 * H) sh->gh[tid - 128] = cs_row(a.ghh[0], sh->pb, tid - 128);
     __syncthreads();
     WQ<5, 4> g1; WQ<5, 6> g2; WQ<5, 8> g3; WQ<5, 10> g4;
-    cs_dec_layer<2, 6, 4, false>(sh, a, 0, 96, g0, g1);
-    cs_dec_layer<4, 10, 6, false>(sh, a, 1, 224, g1, g2);
-    cs_dec_layer<6, 14, 8, false>(sh, a, 2, 352, g2, g3);
-    cs_dec_layer<8, 18, 10, false>(sh, a, 3, 480, g3, g4);
-    cs_dec_layer<10, 22, 10, true>(sh, a, 4, 608, g4, g4);
+    cs_dec_layer<2, 6, 4, false>(sh, a, 0, RM_DEC_GRU_IN(0), g0, g1);
+    cs_dec_layer<4, 10, 6, false>(sh, a, 1, RM_DEC_GRU_IN(1), g1, g2);
+    cs_dec_layer<6, 14, 8, false>(sh, a, 2, RM_DEC_GRU_IN(2), g2, g3);
+    cs_dec_layer<8, 18, 10, false>(sh, a, 3, RM_DEC_GRU_IN(3), g3, g4);
+    cs_dec_layer<10, 22, 10, true>(sh, a, 4, RM_DEC_GRU_IN(4), g4, g4);
     cs_f32_product<12>(a.out, 2, sh->x, sh->pa);                    // output layer, linear
     for (int i = tid; i < W; i += CS_THREADS) a.hist[i] = sh->x[i];
     __syncthreads();
@@ -292,9 +294,9 @@ __global__ __launch_bounds__(CS_THREADS) void k_core_dec_step(rd_core_args a)
 struct CsShared3 {
     __attribute__((aligned(16))) float x[3][CS_WMAX];         // the DenseNet concat rows of the frame's three steps
     __attribute__((aligned(16))) float hist[2][CS_WMAX];      // rows -1, -2 (the previous frame's last two)
-    __attribute__((aligned(16))) float vin[3][96];
-    __attribute__((aligned(16))) float h[5][96];              // GRU states, advanced step by step
-    __attribute__((aligned(16))) float gh[288];
+    __attribute__((aligned(16))) float vin[3][CS_VIN];
+    __attribute__((aligned(16))) float h[RM_NL][RM_DEC_H];    // GRU states, advanced step by step
+    __attribute__((aligned(16))) float gh[RM_DEC_G];
     __attribute__((aligned(16))) float pa[CS_WAVES][3][CS_PS];   // per-wave partial sums of a product, per row
     __attribute__((aligned(16))) float pb[CS_WAVES][CS_PS];      // W_hh h of one step
     __attribute__((aligned(16))) float zs[RD_ZMF];
@@ -340,7 +342,7 @@ __device__ __forceinline__ void cs_store3(const float (&acc)[3][NRB], float (*pa
 template <int GCI, int CCI, int GNEXT, bool LAST>
 __device__ __forceinline__ void cs_enc_layer3(CsShared3 *sh, const rd_core_args &a, int l, int n, WQ<3, GCI> &gq, WQ<3, GNEXT> &gnext)
 {
-    const int tid = threadIdx.x, H = 64, cin = n + H, d = a.dil[l];
+    const int tid = threadIdx.x, H = RM_ENC_H, cin = n + H, d = a.dil[l];
     WQ<2, CCI> cq; WQ<3, 1> hq, hn;
     const Rows3 xr = { { sh->x[0], sh->x[1], sh->x[2] } };
     // the input projection: chunks [0, G1) per wavefront were requested by the stage before (at most 6: 72 registers across its end), the rest here
@@ -407,12 +409,12 @@ __global__ __launch_bounds__(CS_THREADS) void k_tx_frame3(const rd_core_args *ap
     extern __shared__ __attribute__((aligned(16))) unsigned char cs_raw[];
     CsShared3 *sh = (CsShared3 *)cs_raw;
     const rd_core_args &a = *ap;
-    const int tid = threadIdx.x, W = 864, H = 64;
+    const int tid = threadIdx.x, W = RM_ENC_W, H = RM_ENC_H;
     WQ<3, 1> g0, h0;
     cs_issue<3, 1>(a.gin[0], g0); cs_issue<3, 1>(a.ghh[0], h0);
     for (int i = tid; i < 2 * W; i += CS_THREADS) sh->hist[i / W][i % W] = a.hist[i];
-    if (tid < 5 * H) sh->h[tid / H][tid % H] = a.h[tid];
-    if (tid < 3 * 96) { const int q = tid / 96, c = tid % 96; sh->vin[q][c] = c < a.n_in ? a.in[q * a.n_in + c] : 0.0f; }
+    if (tid < RM_NL * H) sh->h[tid / H][tid % H] = a.h[tid];
+    if (tid < 3 * CS_VIN) { const int q = tid / CS_VIN, c = tid % CS_VIN; sh->vin[q][c] = c < a.n_in ? a.in[q * a.n_in + c] : 0.0f; }
     __syncthreads();
     const Rows3 vr = { { sh->vin[0], sh->vin[1], sh->vin[2] } };
     cs_f32_product<2, 3>(a.dense1, 1, vr, sh->pa);                   // dense1 + tanh (radae_base.py:263)
@@ -424,11 +426,11 @@ __global__ __launch_bounds__(CS_THREADS) void k_tx_frame3(const rd_core_args *ap
     } else if (tid >= 128 && tid < 128 + 3 * H) sh->gh[tid - 128] = cs_row(a.ghh[0], sh->pb, tid - 128);
     __syncthreads();
     WQ<3, 4> g1; WQ<3, 6> g2; WQ<3, 9> g3; WQ<3, 11> g4;
-    cs_enc_layer3<1, 4, 4, false>(sh, a, 0, 64, g0, g1);
-    cs_enc_layer3<4, 9, 6, false>(sh, a, 1, 224, g1, g2);
-    cs_enc_layer3<6, 14, 9, false>(sh, a, 2, 384, g2, g3);
-    cs_enc_layer3<9, 19, 11, false>(sh, a, 3, 544, g3, g4);
-    cs_enc_layer3<11, 24, 11, true>(sh, a, 4, 704, g4, g4);
+    cs_enc_layer3<1, 4, 4, false>(sh, a, 0, RM_ENC_GRU_IN(0), g0, g1);
+    cs_enc_layer3<4, 9, 6, false>(sh, a, 1, RM_ENC_GRU_IN(1), g1, g2);
+    cs_enc_layer3<6, 14, 9, false>(sh, a, 2, RM_ENC_GRU_IN(2), g2, g3);
+    cs_enc_layer3<9, 19, 11, false>(sh, a, 3, RM_ENC_GRU_IN(3), g3, g4);
+    cs_enc_layer3<11, 24, 11, true>(sh, a, 4, RM_ENC_GRU_IN(4), g4, g4);
     const Rows3 xr = { { sh->x[0], sh->x[1], sh->x[2] } };
     cs_f32_product<14, 3>(a.out, 2, xr, sh->pa);                     // z_dense, linear (bottleneck 3)
     for (int i = tid; i < W; i += CS_THREADS) { a.hist[i] = sh->x[2][i]; a.hist[W + i] = sh->x[1][i]; }      // history of the next frame: rows -1, -2

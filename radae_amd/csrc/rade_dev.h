@@ -8,6 +8,7 @@
 #define RADE_DEV_H
 
 #include <stdint.h>
+#include "rade_model_geom.h"         /* the encoder's and decoder's layer shapes (RM_*), with the asserts that tie them */
 
 #ifdef __cplusplus
 extern "C" {
@@ -26,13 +27,13 @@ extern "C" {
 #define RD_NQ       16    /* polynomial moments of the two-stage pilot correlator (rade_host.c: rd_corrq16_table_fill) */
 #define RD_NTAP     101
 #define RD_NINMAX   1120
-#define RD_LATENT   80
+#define RD_LATENT   RM_LATENT
 #define RD_ZMF      240   /* latent floats per modem frame */
 #define RD_FEAT_MF  432   /* 12 frames x 36 */
 #define RD_NEOOBITS 180
-#define RD_ENC_W    864   /* encoder concat width */
-#define RD_DEC_W    736
-#define RD_ENC_IN   96    /* 84 padded to a multiple of 16 (k-block of the f16 matrix instructions) */
+#define RD_ENC_W    RM_ENC_W   /* encoder concat width */
+#define RD_DEC_W    RM_DEC_W
+#define RD_ENC_IN   RM_FEAT_PAD /* 84 padded to a multiple of 16 (k-block of the f16 matrix instructions) */
 #define RD_RX_ROUND_MAX 128   /* capacity: do_radae_rx calls per stream per sync-kernel launch (engine picks R <= this) */
 #define RD_DEC_ROWS_MAX (3 * RD_RX_ROUND_MAX)
 /* geometry of the two-stage pilot correlator's operand tables (rade_corr2.h explains them and checks the divisions; rade_host.c fills them).  A fragment plane is what

@@ -274,7 +274,7 @@ extern "C" int rd_launch_encf_hist(unsigned short *xf, int NQ, float *x32, long 
 extern "C" int rd_launch_encf_dense1(const rd_encf_args *a, rd_stream_t s)
 {
     if (a->B <= 0 || a->T <= 0) return 0;
-    if (a->N != 64 || (a->Kin & 7) || !a->yf) return -1;
+    if (a->N != RM_ENC_D1 || (a->Kin & 7) || !a->yf) return -1;
     hipLaunchKernelGGL(k_encf_dense1, dim3(a->B * ((a->T + 31) >> 5)), dim3(64), 0, (hipStream_t)s, *a);
     return (int)hipGetLastError();
 }

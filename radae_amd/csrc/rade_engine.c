@@ -67,10 +67,6 @@ static int sync_blocking_now(void)
     return g_sync_mode == 2 ? rade_sync_policy(__atomic_load_n(&g_engines_open, __ATOMIC_RELAXED) * g_sync_peers, g_sync_quota) : g_sync_mode;
 }
 
-
-static const int ENC_IN[5] = { 64, 224, 384, 544, 704 };    /* GRU input widths (radae_base.py:240-248) */
-static const int ENC_DIL[5] = { 1, 2, 2, 2, 2 };
-static const int DEC_IN[5] = { 96, 224, 352, 480, 608 };    /* radae_base.py:378-386 */
 /* samples per stream of tx_raw, the modulator's output ahead of the Tx band-pass filter (>= the 1152-sample end-of-over frame) */
 static long tx_raw_stride(const rade_batch *h) { return (long)(h->max_tx_mf > 2 ? h->max_tx_mf : 2) * RD_NMF; }
 
@@ -280,24 +276,24 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
 
     int err = 0;
     h->feat_in = m.enc_dense1.n_in; h->enc_kpad = (h->feat_in + 15) & ~15; h->bottleneck1 = (cfg->flags & RADE_BATCH_BOTTLENECK1) != 0;
-    err |= upload_lin(h, &h->enc_dense1, m.enc_dense1.w, m.enc_dense1.b, NULL, 64, h->feat_in, h->enc_kpad);
-    err |= upload_lin(h, &h->enc_zdense, m.enc_zdense.w, m.enc_zdense.b, NULL, 80, 864, 864);
-    err |= upload_lin(h, &h->dec_dense1, m.dec_dense1.w, m.dec_dense1.b, NULL, 96, 80, 80);
-    err |= upload_lin(h, &h->dec_output, m.dec_output.w, m.dec_output.b, NULL, h->feat_in, 736, 736);
-    for (int l = 0; l < 5 && !err; l++) {
-        err |= upload_lin(h, &h->enc_gin[l], m.enc_gru[l].w_ih, m.enc_gru[l].b_ih, m.enc_gru[l].s_ih, 192, ENC_IN[l], ENC_IN[l]);
-        err |= upload_lin(h, &h->dec_gin[l], m.dec_gru[l].w_ih, m.dec_gru[l].b_ih, m.dec_gru[l].s_ih, 288, DEC_IN[l], DEC_IN[l]);
-        err |= upload_lin(h, &h->enc_conv[l], m.enc_conv[l].w, m.enc_conv[l].b, m.enc_conv[l].row_scale, 96, m.enc_conv[l].n_in, m.enc_conv[l].n_in);
-        err |= upload_lin(h, &h->dec_conv[l], m.dec_conv[l].w, m.dec_conv[l].b, m.dec_conv[l].row_scale, 32, m.dec_conv[l].n_in, m.dec_conv[l].n_in);
-        err |= upload_lin(h, &h->dec_glu[l], m.dec_glu[l].w, NULL, m.dec_glu[l].row_scale, 96, 96, 96);
-        h->enc_whh[l] = dev_upload(h, m.enc_gru[l].w_hh, sizeof(float) * 192 * 64);
-        h->enc_bhh[l] = dev_upload(h, m.enc_gru[l].b_hh, sizeof(float) * 192);
-        h->dec_whh[l] = dev_upload(h, m.dec_gru[l].w_hh, sizeof(float) * 288 * 96);
-        h->dec_bhh[l] = dev_upload(h, m.dec_gru[l].b_hh, sizeof(float) * 288);
+    err |= upload_lin(h, &h->enc_dense1, m.enc_dense1.w, m.enc_dense1.b, NULL, RM_ENC_D1, h->feat_in, h->enc_kpad);
+    err |= upload_lin(h, &h->enc_zdense, m.enc_zdense.w, m.enc_zdense.b, NULL, RM_LATENT, RM_ENC_W, RM_ENC_W);
+    err |= upload_lin(h, &h->dec_dense1, m.dec_dense1.w, m.dec_dense1.b, NULL, RM_DEC_D1, RM_LATENT, RM_LATENT);
+    err |= upload_lin(h, &h->dec_output, m.dec_output.w, m.dec_output.b, NULL, h->feat_in, RM_DEC_W, RM_DEC_W);
+    for (int l = 0; l < RM_NL && !err; l++) {
+        err |= upload_lin(h, &h->enc_gin[l], m.enc_gru[l].w_ih, m.enc_gru[l].b_ih, m.enc_gru[l].s_ih, RM_ENC_G, RM_ENC_GRU_IN(l), RM_ENC_GRU_IN(l));
+        err |= upload_lin(h, &h->dec_gin[l], m.dec_gru[l].w_ih, m.dec_gru[l].b_ih, m.dec_gru[l].s_ih, RM_DEC_G, RM_DEC_GRU_IN(l), RM_DEC_GRU_IN(l));
+        err |= upload_lin(h, &h->enc_conv[l], m.enc_conv[l].w, m.enc_conv[l].b, m.enc_conv[l].row_scale, RM_ENC_CONV, m.enc_conv[l].n_in, m.enc_conv[l].n_in);
+        err |= upload_lin(h, &h->dec_conv[l], m.dec_conv[l].w, m.dec_conv[l].b, m.dec_conv[l].row_scale, RM_DEC_CONV, m.dec_conv[l].n_in, m.dec_conv[l].n_in);
+        err |= upload_lin(h, &h->dec_glu[l], m.dec_glu[l].w, NULL, m.dec_glu[l].row_scale, RM_DEC_GLU, RM_DEC_H, RM_DEC_H);
+        h->enc_whh[l] = dev_upload(h, m.enc_gru[l].w_hh, sizeof(float) * RM_ENC_G * RM_ENC_H);
+        h->enc_bhh[l] = dev_upload(h, m.enc_gru[l].b_hh, sizeof(float) * RM_ENC_G);
+        h->dec_whh[l] = dev_upload(h, m.dec_gru[l].w_hh, sizeof(float) * RM_DEC_G * RM_DEC_H);
+        h->dec_bhh[l] = dev_upload(h, m.dec_gru[l].b_hh, sizeof(float) * RM_DEC_G);
         if (m.dec_gru[l].s_hh) {
-            unsigned short *pa = malloc(sizeof(unsigned short) * rd_packed16a_size(288, 96)); float *scl = malloc(sizeof(float) * 288);
-            const long nq = (pa && scl) ? rd_pack_weights_q16_a16(m.dec_gru[l].w_hh, m.dec_gru[l].s_hh, 288, 96, pa, scl) : -1;
-            if (nq > 0) { h->dec_whq[l] = dev_upload_opt(h, pa, sizeof(unsigned short) * nq); h->dec_whs[l] = dev_upload_opt(h, scl, sizeof(float) * 288); }
+            unsigned short *pa = malloc(sizeof(unsigned short) * rd_packed16a_size(RM_DEC_G, RM_DEC_H)); float *scl = malloc(sizeof(float) * RM_DEC_G);
+            const long nq = (pa && scl) ? rd_pack_weights_q16_a16(m.dec_gru[l].w_hh, m.dec_gru[l].s_hh, RM_DEC_G, RM_DEC_H, pa, scl) : -1;
+            if (nq > 0) { h->dec_whq[l] = dev_upload_opt(h, pa, sizeof(unsigned short) * nq); h->dec_whs[l] = dev_upload_opt(h, scl, sizeof(float) * RM_DEC_G); }
             free(pa); free(scl);
         }
     }
@@ -305,7 +301,7 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
 
     h->enc_xin = dev_zeros(h, sizeof(float) * B * T * RD_ENC_IN);
     h->enc_x = dev_zeros(h, sizeof(float) * B * (2 + T) * RD_ENC_W);
-    h->enc_gi = dev_zeros(h, sizeof(float) * B * T * 192);
+    h->enc_gi = dev_zeros(h, sizeof(float) * B * T * RM_ENC_G);
     h->enc_nq = 1 + (h->Tcap + 31) / 32;
     h->enc_seq_taps = getenv("RADE_ENCF_SEQ_TAPS") != NULL;    /* developer switches, read per engine (rade_enc.hip: k_encf_gemm) */
     h->enc_no_pair = getenv("RADE_ENCF_NO_PAIR") != NULL;
@@ -333,12 +329,12 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     }
     h->chan_scratch = dev_zeros(h, sizeof(double) * B * (1 + (cfg->max_tx_mf > 64 ? cfg->max_tx_mf : 64)) * 2);   /* rd_chan_args.scratch */
     /* one allocation each: the five layers' states; progress word, per-stream counters and status, in the order of the host copy (rade_batch_rx: one transfer back per invocation) */
-    h->enc_h[0] = dev_zeros(h, sizeof(float) * 5 * B * 64); h->dec_h[0] = dev_zeros(h, sizeof(float) * 5 * B * 96);
-    h->dec2_h[0] = dev_zeros(h, sizeof(float) * 5 * B * 96);
+    h->enc_h[0] = dev_zeros(h, sizeof(float) * RM_NL * B * RM_ENC_H); h->dec_h[0] = dev_zeros(h, sizeof(float) * RM_NL * B * RM_DEC_H);
+    h->dec2_h[0] = dev_zeros(h, sizeof(float) * RM_NL * B * RM_DEC_H);
     h->rx_progress = dev_zeros(h, sizeof(int) * (8 + B * 8));
     if (h->alloc_failed) { fprintf(stderr, "rade: device allocation failed\n"); goto fail; }
-    for (int l = 1; l < 5; l++) { h->enc_h[l] = h->enc_h[0] + (size_t)l * B * 64; h->dec_h[l] = h->dec_h[0] + (size_t)l * B * 96; }
-    for (int l = 1; l < 5; l++) h->dec2_h[l] = h->dec2_h[0] + (size_t)l * B * 96;
+    for (int l = 1; l < RM_NL; l++) { h->enc_h[l] = h->enc_h[0] + (size_t)l * B * RM_ENC_H; h->dec_h[l] = h->dec_h[0] + (size_t)l * B * RM_DEC_H; }
+    for (int l = 1; l < RM_NL; l++) h->dec2_h[l] = h->dec2_h[0] + (size_t)l * B * RM_DEC_H;
     h->rx_acc = h->rx_progress + 8; h->rx_status = h->rx_progress + 8 + 4 * B;
     h->rx_st = dev_zeros(h, sizeof(rd_rx_stream) * B);
     h->rx_round = dev_zeros(h, sizeof(rd_rx_round) * B);
@@ -346,12 +342,12 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     h->wg_cycles = dev_zeros(h, sizeof(long long) * B);
     h->zrows = dev_zeros(h, sizeof(float) * B * DR * RD_LATENT);
     h->dec_x = dev_zeros(h, sizeof(float) * B * (1 + DR) * RD_DEC_W);
-    h->dec_gi = dev_zeros(h, sizeof(float) * B * DR * 288);
-    h->dec_hbuf = dev_zeros(h, sizeof(float) * B * DR * 96);
-    h->feat84 = dev_zeros(h, sizeof(float) * B * DR * 84);
+    h->dec_gi = dev_zeros(h, sizeof(float) * B * DR * RM_DEC_G);
+    h->dec_hbuf = dev_zeros(h, sizeof(float) * B * DR * RM_DEC_H);
+    h->feat84 = dev_zeros(h, sizeof(float) * B * DR * RM_FEAT_AUX);
     h->dec2_x = dev_zeros(h, sizeof(float) * B * (1 + T) * RD_DEC_W);
-    h->dec2_gi = dev_zeros(h, sizeof(float) * B * T * 288);
-    h->dec2_hbuf = dev_zeros(h, sizeof(float) * B * T * 96);
+    h->dec2_gi = dev_zeros(h, sizeof(float) * B * T * RM_DEC_G);
+    h->dec2_hbuf = dev_zeros(h, sizeof(float) * B * T * RM_DEC_H);
     h->dtcache = dev_zeros(h, sizeof(float) * B * 2 * RD_NMF * RD_NFC);
     if (h->trace_cap > 0) {
         h->trace = dev_zeros(h, sizeof(rd_rx_trace) * B * h->trace_cap);
@@ -456,12 +452,12 @@ static int misaligned16(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
 /* ---- one GEMM launch helper ------------------------------------------------------------------ */
 static int gemm(rade_batch *hh, const dev_lin *w, const float *a1, long a1_sb, long a1_st, int K1, const float *a0, long a0_sb, long a0_st, int K0,
-                const int *reset, const int *n_rows, float *y, long y_sb, long y_st, int B, int T, int act, void *stream)
+                float *y, long y_sb, long y_st, int B, int T, int act, void *stream)
 {
     rd_gemm_args g;
     memset(&g, 0, sizeof g);
     g.a1 = a1; g.a1_sb = a1_sb; g.a1_st = a1_st; g.K1 = K1; g.a0 = a0; g.a0_sb = a0_sb; g.a0_st = a0_st; g.K0 = K0;
-    g.reset = reset; g.reset_sb = hh->dec_rows; g.n_rows = n_rows; g.Wp = w->wp; g.Wp16 = w->wp16; g.Wscale = w->wp16 ? w->wscale16 : NULL; g.bias = w->bias; g.y = y; g.y_sb = y_sb; g.y_st = y_st; g.N = w->N; g.B = B; g.T = T; g.act = act;
+    g.Wp = w->wp; g.Wp16 = w->wp16; g.Wscale = w->wp16 ? w->wscale16 : NULL; g.bias = w->bias; g.y = y; g.y_sb = y_sb; g.y_st = y_st; g.N = w->N; g.B = B; g.T = T; g.act = act;
     if (K0 + K1 != w->K) { fprintf(stderr, "rade: internal GEMM shape error (%d+%d != %d)\n", K0, K1, w->K); return -1; }
     PROF_BEGIN(hh, stream);
     const int rc = rd_launch_gemm(&g, stream);
@@ -501,18 +497,18 @@ static int encode_core_frag(rade_batch *h, int T, float *z, void *stream)
     {
         rd_encf_args g;
         memset(&g, 0, sizeof g);
-        g.xf = h->enc_xf; g.NQ = h->enc_nq; g.B = B; g.T = T; g.bias = h->enc_dense1.bias; g.N = 64; g.act = 1; g.yf = h->enc_xf; g.ycol = 0;
+        g.xf = h->enc_xf; g.NQ = h->enc_nq; g.B = B; g.T = T; g.bias = h->enc_dense1.bias; g.N = RM_ENC_D1; g.act = 1; g.yf = h->enc_xf; g.ycol = 0;
         g.xin = h->enc_xin; g.Kin = h->enc_kpad; g.Wp = h->enc_dense1.wp;
-        PROF_BEGIN(h, stream); e |= rd_launch_encf_dense1(&g, stream); PROF_END(h, stream, RADE_PROF_GEMM, 2.0 * (double)B * T * h->enc_kpad * 64);
+        PROF_BEGIN(h, stream); e |= rd_launch_encf_dense1(&g, stream); PROF_END(h, stream, RADE_PROF_GEMM, 2.0 * (double)B * T * h->enc_kpad * RM_ENC_D1);
     }
-    e |= encf_gemm(h, &h->enc_gin[0], ENC_IN[0], 0, 0, h->enc_gi, (long)T * 192, 192, 0, T, 0, stream);
-    for (int l = 0; l < 5 && !e; l++) {
-        const int in = ENC_IN[l], cin = in + 64;
-        rd_scan_args s = { h->enc_gi, (long)T * 192, 192, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], NULL, 0, 0, NULL, 0, NULL, B, T, 64, h->enc_xf, h->enc_nq, in };
-        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * 192 * 64);
-        e |= encf_gemm(h, &h->enc_conv[l], cin, cin, ENC_DIL[l], NULL, 0, 0, cin, T, 1, stream);
-        if (l < 4) e |= encf_gemm(h, &h->enc_gin[l + 1], ENC_IN[l + 1], 0, 0, h->enc_gi, (long)T * 192, 192, 0, T, 0, stream);
-        else e |= encf_gemm(h, &h->enc_zdense, 864, 0, 0, z, (long)T * RD_LATENT, RD_LATENT, 0, T, h->bottleneck1 ? 1 : 0, stream);
+    e |= encf_gemm(h, &h->enc_gin[0], RM_ENC_GRU_IN(0), 0, 0, h->enc_gi, (long)T * RM_ENC_G, RM_ENC_G, 0, T, 0, stream);
+    for (int l = 0; l < RM_NL && !e; l++) {
+        const int in = RM_ENC_GRU_IN(l), cin = RM_ENC_CONV_IN(l);
+        rd_scan_args s = { h->enc_gi, (long)T * RM_ENC_G, RM_ENC_G, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], NULL, 0, 0, NULL, 0, NULL, B, T, RM_ENC_H, h->enc_xf, h->enc_nq, in };
+        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * RM_ENC_G * RM_ENC_H);
+        e |= encf_gemm(h, &h->enc_conv[l], cin, cin, RM_ENC_DIL(l), NULL, 0, 0, cin, T, 1, stream);
+        if (l + 1 < RM_NL) e |= encf_gemm(h, &h->enc_gin[l + 1], RM_ENC_GRU_IN(l + 1), 0, 0, h->enc_gi, (long)T * RM_ENC_G, RM_ENC_G, 0, T, 0, stream);
+        else e |= encf_gemm(h, &h->enc_zdense, RM_ENC_W, 0, 0, z, (long)T * RD_LATENT, RD_LATENT, 0, T, h->bottleneck1 ? 1 : 0, stream);
     }
     e |= rd_launch_encf_hist(h->enc_xf, h->enc_nq, h->enc_x, (long)(2 + h->Tcap) * RD_ENC_W, B, T, 1, stream);
     h->enc_hist_frag = !e;
@@ -530,16 +526,16 @@ static int encode_core(rade_batch *h, int T, float *z, void *stream)
     /* dense1 reads raw features: the one encoder operand that is not tanh-bounded, so it stays on the f32 matrix cores
      * (the 2^8-scaled binary16 planes of the split-f16 kernels overflow beyond +-255.9) */
     dev_lin d1 = h->enc_dense1; d1.wp16 = NULL; d1.wscale16 = NULL;
-    e |= gemm(h, &d1, h->enc_xin, (long)T * h->enc_kpad, h->enc_kpad, h->enc_kpad, NULL, 0, 0, 0, NULL, NULL, x0, xsb, W, B, T, 1, stream);
-    for (int l = 0; l < 5 && !e; l++) {
-        const int in = ENC_IN[l], cin = in + 64;
-        e |= gemm(h, &h->enc_gin[l], x0, xsb, W, in, NULL, 0, 0, 0, NULL, NULL, h->enc_gi, (long)T * 192, 192, B, T, 0, stream);
-        rd_scan_args s = { h->enc_gi, (long)T * 192, 192, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], x0 + in, xsb, W, NULL, 0, NULL, B, T, 64 };
-        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * 192 * 64);
-        e |= gemm(h, &h->enc_conv[l], x0, xsb, W, cin, x0 - (long)ENC_DIL[l] * W, xsb, W, cin, NULL, NULL, x0 + cin, xsb, W, B, T, 1, stream);
+    e |= gemm(h, &d1, h->enc_xin, (long)T * h->enc_kpad, h->enc_kpad, h->enc_kpad, NULL, 0, 0, 0, x0, xsb, W, B, T, 1, stream);
+    for (int l = 0; l < RM_NL && !e; l++) {
+        const int in = RM_ENC_GRU_IN(l), cin = RM_ENC_CONV_IN(l);
+        e |= gemm(h, &h->enc_gin[l], x0, xsb, W, in, NULL, 0, 0, 0, h->enc_gi, (long)T * RM_ENC_G, RM_ENC_G, B, T, 0, stream);
+        rd_scan_args s = { h->enc_gi, (long)T * RM_ENC_G, RM_ENC_G, h->enc_whh[l], h->enc_bhh[l], h->enc_h[l], x0 + in, xsb, W, NULL, 0, NULL, B, T, RM_ENC_H };
+        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * RM_ENC_G * RM_ENC_H);
+        e |= gemm(h, &h->enc_conv[l], x0, xsb, W, cin, x0 - (long)RM_ENC_DIL(l) * W, xsb, W, cin, x0 + cin, xsb, W, B, T, 1, stream);
     }
     /* bottleneck 1: z = tanh(z_dense) (radae_base.py:281-284); bottleneck 3: linear */
-    e |= gemm(h, &h->enc_zdense, x0, xsb, W, 864, NULL, 0, 0, 0, NULL, NULL, z, (long)T * RD_LATENT, RD_LATENT, B, T, h->bottleneck1 ? 1 : 0, stream);
+    e |= gemm(h, &h->enc_zdense, x0, xsb, W, W, NULL, 0, 0, 0, z, (long)T * RD_LATENT, RD_LATENT, B, T, h->bottleneck1 ? 1 : 0, stream);
     e |= rd_launch_carry_rows(h->enc_x, B, h->Tcap, W, 2, T, NULL, stream);
     return e;
 }
@@ -580,7 +576,7 @@ static int modulate(rade_batch *h, const float *z, int n_mf, void *iq_out, long 
 int rade_batch_tx(rade_batch *h, const float *features_dev, int n_mf, void *iq_out_dev, long iq_stride, float *z_out_dev, void *stream)
 {
     ON_DEV(h);
-    if (!h || !features_dev || !iq_out_dev || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84) return -1;
+    if (!h || !features_dev || !iq_out_dev || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != RM_FEAT_AUX) return -1;
     if (misaligned16(z_out_dev)) return -1;           /* encf_emit (rade_enc.hip) stores the latents of a large call as f32x4 */
     float *z = z_out_dev ? z_out_dev : h->enc_z;
     int e = encode_features(h, features_dev, 3 * n_mf, z, stream);
@@ -735,7 +731,7 @@ int rade_batch_tx_channel_streams(rade_batch *h, const float *features_dev, int 
                                   const rade_channel_params *p, const rade_channel_streams *ps, void *stream)
 {
     ON_DEV(h);
-    if (!h || !p || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != 84 || p->n_sig != n_mf * RD_NMF || !rx_out_dev || (h->tx_linear && p->with_eoo)) return -1;
+    if (!h || !p || n_mf <= 0 || n_mf > h->max_tx_mf || h->feat_in != RM_FEAT_AUX || p->n_sig != n_mf * RD_NMF || !rx_out_dev || (h->tx_linear && p->with_eoo)) return -1;
     if (!features_dev || misaligned16(p->G_dev)) return -1;      /* k_ofdm_mod_mp reads (G1[i], G2[i]) as one f32x4 */
     const float *ps_dev;                   /* (uploaded ahead of the transmit launches: its synchronisation waits only for what the stream held before this call) */
     if (chan_streams_upload(h, p, ps, stream, &ps_dev)) return -1;
@@ -788,27 +784,25 @@ int rade_batch_multipath_h(rade_batch *h, const void *G_dev, int n_g, int fs_ove
 }
 
 /* ---- receive ----------------------------------------------------------------------------------- */
-/* CoreDecoderStatefull.forward (radae_base.py:400-416) over T time slots of every stream.  x = [B][1+Tcap][736]
- * (slot 0 = conv history), rows beyond n_rows[b] are skipped, rst flags zero the state before a step. */
-static int decoder_layers(rade_batch *h, const float *z, int T, int Tio, int Tcap, float *xbuf, float *gi, float *hbuf, float **hstate,
-                          const int *nr, const int *rst, float *out, void *stream)
+/* CoreDecoderStatefull.forward (radae_base.py:400-416) over T time slots of every stream, on the engine's dec2_* buffers: dec2_x = [B][1+Tcap][RD_DEC_W]
+ * (slot 0 = conv history), z and out dense [B][T][.] */
+static int decoder_layers(rade_batch *h, const float *z, int T, float *out, void *stream)
 {
-    const int B = h->B, W = RD_DEC_W;
-    const long xsb = (long)(1 + Tcap) * W;
-    float *x = xbuf + W;
+    const int B = h->B, W = RD_DEC_W, G = RM_DEC_G, H = RM_DEC_H;
+    const long xsb = (long)(1 + h->Tcap) * W;
+    float *x = h->dec2_x + W, *gi = h->dec2_gi, *hbuf = h->dec2_hbuf;
     int e = 0;
     dev_lin d1 = h->dec_dense1; d1.wp16 = NULL; d1.wscale16 = NULL;       /* z_hat is unbounded: f32 matrix cores (see encode_core) */
-    e |= gemm(h, &d1, z, (long)Tio * RD_LATENT, RD_LATENT, RD_LATENT, NULL, 0, 0, 0, NULL, nr, x, xsb, W, B, T, 1, stream);
-    for (int l = 0; l < 5 && !e; l++) {
-        const int in = DEC_IN[l];
-        e |= gemm(h, &h->dec_gin[l], x, xsb, W, in, NULL, 0, 0, 0, NULL, nr, gi, (long)T * 288, 288, B, T, 0, stream);
-        rd_scan_args s = { gi, (long)T * 288, 288, h->dec_whh[l], h->dec_bhh[l], hstate[l], hbuf, (long)T * 96, 96, rst, h->dec_rows, nr, B, T, 96 };
-        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * 288 * 96);
-        e |= gemm(h, &h->dec_glu[l], hbuf, (long)T * 96, 96, 96, NULL, 0, 0, 0, NULL, nr, x + in, xsb, W, B, T, 2, stream);
-        const int cin = in + 96;
-        e |= gemm(h, &h->dec_conv[l], x, xsb, W, cin, x - W, xsb, W, cin, rst, nr, x + cin, xsb, W, B, T, 1, stream);
+    e |= gemm(h, &d1, z, (long)T * RD_LATENT, RD_LATENT, RD_LATENT, NULL, 0, 0, 0, x, xsb, W, B, T, 1, stream);
+    for (int l = 0; l < RM_NL && !e; l++) {
+        const int in = RM_DEC_GRU_IN(l), cin = RM_DEC_CONV_IN(l);
+        e |= gemm(h, &h->dec_gin[l], x, xsb, W, in, NULL, 0, 0, 0, gi, (long)T * G, G, B, T, 0, stream);
+        rd_scan_args s = { gi, (long)T * G, G, h->dec_whh[l], h->dec_bhh[l], h->dec2_h[l], hbuf, (long)T * H, H, NULL, 0, NULL, B, T, H };
+        PROF_BEGIN(h, stream); e |= rd_launch_gru_scan(&s, stream); PROF_END(h, stream, RADE_PROF_SCAN, 2.0 * B * T * G * H);
+        e |= gemm(h, &h->dec_glu[l], hbuf, (long)T * H, H, H, NULL, 0, 0, 0, x + in, xsb, W, B, T, 2, stream);
+        e |= gemm(h, &h->dec_conv[l], x, xsb, W, cin, x - W, xsb, W, cin, x + cin, xsb, W, B, T, 1, stream);
     }
-    e |= gemm(h, &h->dec_output, x, xsb, W, 736, NULL, 0, 0, 0, NULL, nr, out, (long)Tio * h->feat_in, h->feat_in, B, T, 0, stream);
+    e |= gemm(h, &h->dec_output, x, xsb, W, W, NULL, 0, 0, 0, out, (long)T * h->feat_in, h->feat_in, B, T, 0, stream);
     return e;
 }
 
@@ -818,12 +812,12 @@ static void fill_dec_args(const rade_batch *h, rd_decs_args *d)
     memset(d, 0, sizeof *d);
     const long DR = h->dec_rows;
     d->z = h->zrows; d->z_sb = DR * RD_LATENT; d->x = h->dec_x + RD_DEC_W; d->x_sb = (1 + DR) * RD_DEC_W;
-    d->gi = h->dec_gi; d->gi_sb = DR * 288; d->hbuf = h->dec_hbuf; d->hb_sb = DR * 96;
+    d->gi = h->dec_gi; d->gi_sb = DR * RM_DEC_G; d->hbuf = h->dec_hbuf; d->hb_sb = DR * RM_DEC_H;
     d->out = h->feat84; d->out_sb = DR * h->feat_in; d->out_w = h->feat_in;
     d->B = h->B;
 #define LIN(dst, src) do { (dst).wp = (src).wp; (dst).bias = (src).bias; (dst).wp16 = (src).wp16; (dst).wa16 = (src).wa16; (dst).wscale = (src).wscale; (dst).N = (src).N; (dst).K = (src).K; } while (0)
     LIN(d->dense1, h->dec_dense1); LIN(d->output, h->dec_output);
-    for (int l = 0; l < 5; l++) { LIN(d->gin[l], h->dec_gin[l]); LIN(d->glu[l], h->dec_glu[l]); LIN(d->conv[l], h->dec_conv[l]); d->whh[l] = h->dec_whh[l]; d->bhh[l] = h->dec_bhh[l]; d->h[l] = h->dec_h[l];
+    for (int l = 0; l < RM_NL; l++) { LIN(d->gin[l], h->dec_gin[l]); LIN(d->glu[l], h->dec_glu[l]); LIN(d->conv[l], h->dec_conv[l]); d->whh[l] = h->dec_whh[l]; d->bhh[l] = h->dec_bhh[l]; d->h[l] = h->dec_h[l];
                                   d->whq[l] = (h->dec_whq[l] && h->dec_whs[l]) ? h->dec_whq[l] : NULL; d->whs[l] = h->dec_whs[l]; }
 #undef LIN
 }
@@ -835,10 +829,10 @@ int rade_batch_decode(rade_batch *h, const float *z_dev, int n_steps, float *fea
     if (misaligned16(z_dev)) return -1;               /* the GEMMs read their A rows as f32x4 (rade_gemm.h), and dense1's rows are z_dev's */
     hipStream_t st = (hipStream_t)stream;
     if (reset_state) {
-        hipMemsetAsync(h->dec2_h[0], 0, sizeof(float) * 5 * h->B * 96, st);
+        hipMemsetAsync(h->dec2_h[0], 0, sizeof(float) * RM_NL * h->B * RM_DEC_H, st);
         hipMemsetAsync(h->dec2_x, 0, sizeof(float) * (size_t)h->B * (1 + h->Tcap) * RD_DEC_W, st);
     }
-    int e = decoder_layers(h, z_dev, n_steps, n_steps, h->Tcap, h->dec2_x, h->dec2_gi, h->dec2_hbuf, h->dec2_h, NULL, NULL, features_out_dev, stream);
+    int e = decoder_layers(h, z_dev, n_steps, features_out_dev, stream);
     e |= rd_launch_carry_rows(h->dec2_x, h->B, h->Tcap, RD_DEC_W, 1, n_steps, NULL, stream);
     return e ? -1 : n_steps;
 }
@@ -937,7 +931,7 @@ int rade_batch_rx(rade_batch *h, const void *rx_dev, long rx_stride, const int *
 {
     ON_DEV(h);
     const int row_floats = h && h->bypass_dec ? RD_ZMF : RD_FEAT_MF;       /* RADE_BATCH_BYPASS_DEC: 240 latents per valid modem frame instead of 432 feature floats */
-    if (!h || !n_avail_host || max_calls <= 0 || h->feat_in != 84 || !features_out_dev || feat_stride < row_floats) return -1;
+    if (!h || !n_avail_host || max_calls <= 0 || h->feat_in != RM_FEAT_AUX || !features_out_dev || feat_stride < row_floats) return -1;
     const int B = h->B;
     hipStream_t st = (hipStream_t)stream;
     int *hs = h->h_small;

@@ -117,8 +117,8 @@ extern "C" int rd_launch_gru_scan(const rd_scan_args *a, rd_stream_t s)
 {
     if (a->B <= 0) return 0;
     hipStream_t st = (hipStream_t)s;
-    if (a->H == 64) hipLaunchKernelGGL(k_gru_scan<64>, dim3(a->B), dim3(256), 0, st, *a);
-    else if (a->H == 96) hipLaunchKernelGGL(k_gru_scan<96>, dim3(a->B), dim3(384), 0, st, *a);
+    if (a->H == RM_ENC_H) hipLaunchKernelGGL(k_gru_scan<RM_ENC_H>, dim3(a->B), dim3(4 * RM_ENC_H), 0, st, *a);
+    else if (a->H == RM_DEC_H) hipLaunchKernelGGL(k_gru_scan<RM_DEC_H>, dim3(a->B), dim3(4 * RM_DEC_H), 0, st, *a);
     else return -1;
     return (int)hipGetLastError();
 }

@@ -251,34 +251,33 @@ int rd_model_parse(const void *blob, size_t len, rd_model *m)
         recs[n].name = names[n]; recs[n].type = type; recs[n].size = size; recs[n].data = p + off + 64;
         n++; off += 64 + block;
     }
-    /* the architecture this engine is built for (radae_base.py:239-251, :377-393): GRU input widths = the running concat */
-    static const int enc_in[5] = { 64, 224, 384, 544, 704 }, dec_in[5] = { 96, 224, 352, 480, 608 };
+    /* the architecture this engine is built for (radae_base.py:239-251, :377-393; rade_model_geom.h): GRU input widths = the running concat */
     int err = 0;
     err |= dequant_dense_float(recs, n, "enc_dense1", &m->enc_dense1);
     err |= dequant_dense_float(recs, n, "enc_zdense", &m->enc_zdense);
     err |= dequant_dense_float(recs, n, "dec_dense1", &m->dec_dense1);
     err |= dequant_dense_float(recs, n, "dec_output", &m->dec_output);
-    for (int i = 0; i < 5 && !err; i++) {
+    for (int i = 0; i < RM_NL && !err; i++) {
         char nm[32];
-        snprintf(nm, sizeof nm, "enc_gru%d", i + 1); err |= load_gru(recs, n, nm, &m->enc_gru[i], enc_in[i]);
-        snprintf(nm, sizeof nm, "dec_gru%d", i + 1); err |= load_gru(recs, n, nm, &m->dec_gru[i], dec_in[i]);
+        snprintf(nm, sizeof nm, "enc_gru%d", i + 1); err |= load_gru(recs, n, nm, &m->enc_gru[i], RM_ENC_GRU_IN(i));
+        snprintf(nm, sizeof nm, "dec_gru%d", i + 1); err |= load_gru(recs, n, nm, &m->dec_gru[i], RM_DEC_GRU_IN(i));
         snprintf(nm, sizeof nm, "enc_conv%d", i + 1); err |= dequant_dense_int8(recs, n, nm, &m->enc_conv[i]);
         snprintf(nm, sizeof nm, "dec_conv%d", i + 1); err |= dequant_dense_int8(recs, n, nm, &m->dec_conv[i]);
         snprintf(nm, sizeof nm, "dec_glu%d", i + 1); err |= dequant_dense_int8(recs, n, nm, &m->dec_glu[i]);
     }
     if (err) { fprintf(stderr, "rade: weight blob is missing layers\n"); rd_model_free(m); return -1; }
     /* sanity: every other layer shape of that architecture */
-    for (int i = 0; i < 5; i++)
-        if (m->enc_gru[i].n_in != enc_in[i] || m->enc_gru[i].hid != 64 || m->dec_gru[i].n_in != dec_in[i] || m->dec_gru[i].hid != 96 ||
-            m->enc_conv[i].n_in != 2 * (enc_in[i] + 64) || m->enc_conv[i].n_out != 96 || m->dec_conv[i].n_in != 2 * (dec_in[i] + 96) || m->dec_conv[i].n_out != 32) {
+    for (int i = 0; i < RM_NL; i++)
+        if (m->enc_gru[i].n_in != RM_ENC_GRU_IN(i) || m->enc_gru[i].hid != RM_ENC_H || m->dec_gru[i].n_in != RM_DEC_GRU_IN(i) || m->dec_gru[i].hid != RM_DEC_H ||
+            m->enc_conv[i].n_in != 2 * RM_ENC_CONV_IN(i) || m->enc_conv[i].n_out != RM_ENC_CONV || m->dec_conv[i].n_in != 2 * RM_DEC_CONV_IN(i) || m->dec_conv[i].n_out != RM_DEC_CONV) {
             fprintf(stderr, "rade: unexpected layer shape in weight blob (layer %d)\n", i + 1); rd_model_free(m); return -1;
         }
-    for (int i = 0; i < 5; i++)
-        if (m->dec_glu[i].n_in != 96 || m->dec_glu[i].n_out != 96) { fprintf(stderr, "rade: unexpected GLU shape in weight blob (layer %d)\n", i + 1); rd_model_free(m); return -1; }
+    for (int i = 0; i < RM_NL; i++)
+        if (m->dec_glu[i].n_in != RM_DEC_H || m->dec_glu[i].n_out != RM_DEC_GLU) { fprintf(stderr, "rade: unexpected GLU shape in weight blob (layer %d)\n", i + 1); rd_model_free(m); return -1; }
     /* every dimension the engine's upload (rade_engine.c:upload_lin) hard-codes is checked here: a foreign or crafted blob with smaller
      * layers must not get as far as the packers, which read N x K floats */
-    if ((m->enc_dense1.n_in != 84 && m->enc_dense1.n_in != 80) || m->enc_dense1.n_out != 64 || m->enc_zdense.n_in != 864 || m->enc_zdense.n_out != 80 ||
-        m->dec_dense1.n_in != 80 || m->dec_dense1.n_out != 96 || m->dec_output.n_in != 736 || m->dec_output.n_out != m->enc_dense1.n_in) {   /* 4 x 21 features (model19, aux symbol) or 4 x 20 (model05, bbfm) */
+    if ((m->enc_dense1.n_in != RM_FEAT_AUX && m->enc_dense1.n_in != RM_FEAT) || m->enc_dense1.n_out != RM_ENC_D1 || m->enc_zdense.n_in != RM_ENC_W || m->enc_zdense.n_out != RM_LATENT ||
+        m->dec_dense1.n_in != RM_LATENT || m->dec_dense1.n_out != RM_DEC_D1 || m->dec_output.n_in != RM_DEC_W || m->dec_output.n_out != m->enc_dense1.n_in) {   /* 4 x 21 features (model19, aux symbol) or 4 x 20 (model05, bbfm) */
         fprintf(stderr, "rade: unexpected dense layer shape in weight blob\n"); rd_model_free(m); return -1;
     }
     return 0;
@@ -288,7 +287,7 @@ static void lin_free(rd_linear *l) { free(l->w); free(l->b); free(l->row_scale);
 void rd_model_free(rd_model *m)
 {
     lin_free(&m->enc_dense1); lin_free(&m->enc_zdense); lin_free(&m->dec_dense1); lin_free(&m->dec_output);
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < RM_NL; i++) {
         free(m->enc_gru[i].w_ih); free(m->enc_gru[i].w_hh); free(m->enc_gru[i].b_ih); free(m->enc_gru[i].b_hh); free(m->enc_gru[i].s_ih); free(m->enc_gru[i].s_hh);
         free(m->dec_gru[i].w_ih); free(m->dec_gru[i].w_hh); free(m->dec_gru[i].b_ih); free(m->dec_gru[i].b_hh); free(m->dec_gru[i].s_ih); free(m->dec_gru[i].s_hh);
         lin_free(&m->enc_conv[i]); lin_free(&m->dec_conv[i]); lin_free(&m->dec_glu[i]);

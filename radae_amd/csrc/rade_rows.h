@@ -8,7 +8,7 @@ __global__ void k_enc_pack(const float *features, float *xin, int B, int T)
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i % RD_ENC_IN); const long bt = i / RD_ENC_IN;
         float v = 0.0f;
-        if (c < 84) { const int fr = c / 21, j = c - fr * 21; v = j < 20 ? features[(bt * 4 + fr) * 36 + j] : -1.0f; }
+        if (c < RM_FEAT_AUX) { const int fr = c / (RM_NFEAT + 1), j = c - fr * (RM_NFEAT + 1); v = j < RM_NFEAT ? features[(bt * RM_STEP_FRAMES + fr) * RM_FILE_FRAME + j] : -1.0f; }
         xin[i] = v;
     }
 }

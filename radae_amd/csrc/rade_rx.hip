@@ -151,16 +151,16 @@ __device__ __forceinline__ void rx2_decode_pending(RxShared2 *sh, const rd_sync_
         if (!CENSUS(1)) dq2_layers(ds, a.dec, b, a.dec.z + (size_t)b * a.dec.z_sb + (size_t)c0 * RD_LATENT, a.dec.out + (size_t)b * a.dec.out_sb + (size_t)c0 * a.dec.out_w, n, rstmask, CENSUS(2));
     }
     const float *f84 = a.dec.out + (size_t)b * a.dec.out_sb;
-    for (int r = tid; r < Tb; r += NT2) ds->err[r] = f84[r * 84 + 20] > 0.0f ? 1 : 0;
+    for (int r = tid; r < Tb; r += NT2) ds->err[r] = f84[r * RM_FEAT_AUX + RM_NFEAT] > 0.0f ? 1 : 0;
     float *out = a.features_out + (size_t)b * a.feat_stride + (size_t)S->out_base * RD_FEAT_MF;
     for (int i0 = tid; i0 < (Tb / 3) * RD_FEAT_MF; i0 += 4 * NT2) {      // four loads in flight per thread (a plain loop waits for each load before its store: the stores may alias)
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const int i = min(i0 + q * NT2, (Tb / 3) * RD_FEAT_MF - 1), fr = i / 36, j = i - fr * 36;
+            const int i = min(i0 + q * NT2, (Tb / 3) * RD_FEAT_MF - 1), fr = i / RM_FILE_FRAME, j = i - fr * RM_FILE_FRAME;
             const int row = fr >> 2, sub = fr & 3;
-            v[q] = f84[row * 84 + sub * 21 + min(j, 19)];
-            if (j >= 20) v[q] = 0.0f;
+            v[q] = f84[row * RM_FEAT_AUX + sub * (RM_NFEAT + 1) + min(j, RM_NFEAT - 1)];
+            if (j >= RM_NFEAT) v[q] = 0.0f;
         }
 #pragma unroll
         for (int q = 0; q < 4; q++) { const int i = i0 + q * NT2; if (i < (Tb / 3) * RD_FEAT_MF) out[i] = v[q]; }

@@ -9,8 +9,9 @@
 // floats per row of the GRU-input sums in LDS: 288 + 4.  With 288 (= 9 x 32) every row started on the same bank, and the 16-byte accesses of a product's epilogue -- lanes = rows --
 // were 8-way conflicts: two thirds of ALL bank-conflict cycles of the kernel (tools/rx2_lds_conflicts.sh, round 5); with 292 a row starts 16 bytes further on.
 #ifndef DQ_GIS
-#define DQ_GIS 292
+#define DQ_GIS (RM_DEC_G + 4)
 #endif
+static_assert(DQ_XB * 8 >= RD_DEC_W && DQ_HB * 8 >= RM_DEC_H, "an x row and a GRU-output row fit their LDS rows");
 // half index of x[logical row t][col] inside a plane; the history row is logical -1 (swizzle key 15), the zero row needs no key
 __device__ __forceinline__ int dq_xoff(int t, int col) { return (t + 1) * (DQ_XB * 8) + ((((col >> 3) ^ (t & 15)) << 3) | (col & 7)); }
 __device__ __forceinline__ int dq_hoff(int t, int col) { return t * (DQ_HB * 8) + ((((col >> 3) ^ (t & 15)) << 3) | (col & 7)); }
@@ -37,7 +38,7 @@ struct DecShared2 {
     __attribute__((aligned(16))) _Float16 xl[DQ2_ROWS + 2][DQ_XB * 8];
     __attribute__((aligned(16))) float gi[DQ2_ROWS][DQ_GIS];
     __attribute__((aligned(16))) _Float16 hbh[DQ2_ROWS][DQ_HB * 8], hbl[DQ2_ROWS][DQ_HB * 8];
-    __attribute__((aligned(16))) float hs[2][96];
+    __attribute__((aligned(16))) float hs[2][RM_DEC_H];
     int rst[DQ_PEND_MAX];
     int err[DQ_PEND_MAX];
 };
@@ -202,7 +203,7 @@ __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return (f32x2
 // GRU recurrence over Tb steps: TWO lanes per hidden unit (192 threads; the fourth wavefront only keeps the barriers)
 __device__ void dq2_scan(DecShared2 *sh, const float *Whh, const float *bhh, float *hstate, int Tb, unsigned rstmask)
 {
-    constexpr int H = 96, KP = H / 2;
+    constexpr int H = RM_DEC_H, KP = H / 2;
     const int tid = rx_tid();
     const bool on = tid < 2 * H;
     const int j = on ? tid >> 1 : 0, p = tid & 1;
@@ -278,7 +279,7 @@ __device__ void dq2_scan(DecShared2 *sh, const float *Whh, const float *bhh, flo
 template <int NB>
 __device__ __forceinline__ void dq2_scan_mfma_body(DecShared2 *sh, const unsigned short *whq, const float *whs, const float *bhh, float *hstate, int Tb, unsigned rstmask, int ub0)
 {
-    constexpr int H = 96;
+    constexpr int H = RM_DEC_H;
     const int tid = rx_tid(), lane = tid & 63, c = lane & 15, g = lane >> 4, cs = c & 3, par = c & 1;
     // every column of a tile's C holds the same sums once neighbouring lanes are added (the planes sit in even / odd columns), so in a two-block wavefront the lanes of
     // columns 8..15 take block 1 and those of columns 0..7 block 0: ONE pass over the gates (two sigmoids and a tanh: six transcendental instructions and their
@@ -395,28 +396,28 @@ __device__ void dq2_layers(DecShared2 *sh, const rd_decs_args &a, int b, const f
     // first weight requests; the recurrences do the same behind their weight fragments.  A wavefront that has no product in a phase takes the barrier bare.
     // 18 column tiles of an input projection over four wavefronts: 5 + 5 + 4 + 4
     const int ct18 = wave < 2 ? 5 * wave : 10 + 4 * (wave - 2);
-    g = (DqGemm){ a.gin[0].wa16, 18, a.gin[0].bias, 288, a.gin[0].wscale, 0, 0, 0, 3, 0, DQ_OUT_GI, 0, 0, nullptr, 0 };
+    g = (DqGemm){ a.gin[0].wa16, 18, a.gin[0].bias, RM_DEC_G, a.gin[0].wscale, 0, 0, 0, 3, 0, DQ_OUT_GI, 0, 0, nullptr, 0 };
     if (wave < 2) dq2_gemm_tiles<5>(sh, g, ct18, Tb, rstmask, 1); else dq2_gemm_tiles<4>(sh, g, ct18, Tb, rstmask, 1);
     PH2(20);
 #pragma unroll 1
-    for (int l = 0; l < 5; l++) {
-        const int in = 96 + 128 * l, cin = in + 96;
+    for (int l = 0; l < RM_NL; l++) {
+        const int in = RM_DEC_GRU_IN(l), cin = RM_DEC_CONV_IN(l);
         if (census_noscan) __syncthreads();
-        else if (a.whq[l]) dq2_scan_mfma(sh, a.whq[l], a.whs[l], a.bhh[l], a.h[l] + (size_t)b * 96, Tb, rstmask);
-        else dq2_scan(sh, a.whh[l], a.bhh[l], a.h[l] + (size_t)b * 96, Tb, rstmask);
+        else if (a.whq[l]) dq2_scan_mfma(sh, a.whq[l], a.whs[l], a.bhh[l], a.h[l] + (size_t)b * RM_DEC_H, Tb, rstmask);
+        else dq2_scan(sh, a.whh[l], a.bhh[l], a.h[l] + (size_t)b * RM_DEC_H, Tb, rstmask);
         PH2(21);
         // GLU gates: 6 column tiles, K = 96: 2 + 2 + 1 + 1
-        g = (DqGemm){ a.glu[l].wa16, 6, nullptr, 96, a.glu[l].wscale, 1, 0, 0, 3, 0, DQ_OUT_X, in, 2, nullptr, 0 };
+        g = (DqGemm){ a.glu[l].wa16, 6, nullptr, RM_DEC_GLU, a.glu[l].wscale, 1, 0, 0, 3, 0, DQ_OUT_X, in, 2, nullptr, 0 };
         if (wave < 2) dq2_gemm_tiles<2>(sh, g, 2 * wave, Tb, rstmask, 1); else dq2_gemm_tiles<1>(sh, g, 2 + wave, Tb, rstmask, 1);
         PH2(22);
         // conv (2 tiles, K = 2 cin) beside the columns of the next product that are already final (K = cin): in units of cin k-steps the
         // conv tiles weigh 2 each, a projection tile 1: wavefronts 0 / 1 = one conv tile + 3 projection tiles, 2 / 3 = 6 projection tiles;
         // behind the last conv the output layer (6 tiles): one conv tile each on 0 / 1, three output tiles each on 2 / 3
-        const DqGemm gc = (DqGemm){ a.conv[l].wa16, 2, a.conv[l].bias, 32, a.conv[l].wscale, 0, cin / 32, 0, 2 * cin / 32, 0, DQ_OUT_X, cin, 1, nullptr, 0 };
-        const bool last = l == 4;
+        const DqGemm gc = (DqGemm){ a.conv[l].wa16, 2, a.conv[l].bias, RM_DEC_CONV, a.conv[l].wscale, 0, cin / 32, 0, 2 * cin / 32, 0, DQ_OUT_X, cin, 1, nullptr, 0 };
+        const bool last = l == RM_NL - 1;
         const rd_lin &nx = last ? a.output : a.gin[l + 1];
         const int nct = last ? 6 : 18;
-        const DqGemm gm = (DqGemm){ nx.wa16, nct, nx.bias, last ? a.out_w : 288, nx.wscale, 0, 0, 0, cin / 32, 0, DQ_OUT_GI, 0, 0, nullptr, 0 };
+        const DqGemm gm = (DqGemm){ nx.wa16, nct, nx.bias, last ? a.out_w : RM_DEC_G, nx.wscale, 0, 0, 0, cin / 32, 0, DQ_OUT_GI, 0, 0, nullptr, 0 };
         if (wave < 2) {
             dq2_gemm_tiles<1>(sh, gc, wave, Tb, rstmask, 1);
             if (!last) dq2_gemm_tiles<3>(sh, gm, 3 * wave, Tb, rstmask, 0);
@@ -427,7 +428,7 @@ __device__ void dq2_layers(DecShared2 *sh, const rd_decs_args &a, int b, const f
         }
         PH2(23);
         // fix-up: the conv's 32 new columns (one k-step) added onto the staged sums
-        const DqGemm gf = (DqGemm){ nx.wa16, nct, nullptr, last ? a.out_w : 288, nx.wscale, 0, 0, cin / 32, 1, 1, last ? DQ_OUT_GLOBAL : DQ_OUT_GI, 0, 0, out, a.out_w };
+        const DqGemm gf = (DqGemm){ nx.wa16, nct, nullptr, last ? a.out_w : RM_DEC_G, nx.wscale, 0, 0, cin / 32, 1, 1, last ? DQ_OUT_GLOBAL : DQ_OUT_GI, 0, 0, out, a.out_w };
         if (last) { if (wave >= 2) dq2_gemm_tiles<3>(sh, gf, 3 * (wave - 2), Tb, rstmask, 1); else __syncthreads(); }
         else if (wave < 2) dq2_gemm_tiles<5>(sh, gf, ct18, Tb, rstmask, 1);
         else dq2_gemm_tiles<4>(sh, gf, ct18, Tb, rstmask, 1);

@@ -16,7 +16,6 @@
 #include "rade_train.h"
 
 #define TR_NPARAM (2 + 7 * TR_NL + 2)
-static const int TR_GRU_IN[TR_NL] = { 96, 224, 352, 480, 608 };      /* width of the concat buffer a GRU reads; its conv reads 96 more (the GLU) */
 
 typedef struct { char name[32]; long offset; int rows, cols; } tr_param;
 static tr_param tr_table[TR_NPARAM];
@@ -27,11 +26,11 @@ static void tr_build_table(void)
     if (tr_total) return;
     int n = 0; long off = 0;
 #define ADD(r, c, ...) do { snprintf(tr_table[n].name, sizeof tr_table[n].name, __VA_ARGS__); tr_table[n].offset = off; tr_table[n].rows = (r); tr_table[n].cols = (c); off += (long)(r) * (c); n++; } while (0)
-    ADD(96, 80, "dec_dense1.w"); ADD(96, 1, "dec_dense1.b");
+    ADD(TR_H, RD_LATENT, "dec_dense1.w"); ADD(TR_H, 1, "dec_dense1.b");
     for (int l = 0; l < TR_NL; l++) {
-        const int kg = TR_GRU_IN[l];
+        const int kg = RM_DEC_GRU_IN(l);          /* width of the concat buffer the GRU reads; its conv reads TR_H more (the GLU) */
         ADD(TR_G, kg, "dec_gru[%d].w_ih", l); ADD(TR_G, TR_H, "dec_gru[%d].w_hh", l); ADD(TR_G, 1, "dec_gru[%d].b_ih", l); ADD(TR_G, 1, "dec_gru[%d].b_hh", l);
-        ADD(TR_H, TR_H, "dec_glu[%d].w", l); ADD(32, 2 * (kg + TR_H), "dec_conv[%d].w", l); ADD(32, 1, "dec_conv[%d].b", l);
+        ADD(TR_H, TR_H, "dec_glu[%d].w", l); ADD(TR_CONV, 2 * (kg + TR_H), "dec_conv[%d].w", l); ADD(TR_CONV, 1, "dec_conv[%d].b", l);
     }
     ADD(TR_OUT, RD_DEC_W, "dec_output.w"); ADD(TR_OUT, 1, "dec_output.b");
 #undef ADD
@@ -80,7 +79,7 @@ static float *tr_alloc(size_t n_floats)
 rade_train *rade_train_open(int max_B, int max_T, int n_features, int device)
 {
     int ndev = 0;
-    if (max_B <= 0 || max_T <= 0 || (n_features != 20 && n_features != 21) || device < 0 || (long)max_B * max_T > TR_MAX_ROWS) {
+    if (max_B <= 0 || max_T <= 0 || (n_features != RM_NFEAT && n_features != RM_NFEAT + 1) || device < 0 || (long)max_B * max_T > TR_MAX_ROWS) {
         fprintf(stderr, "rade_train_open: need max_B, max_T > 0, max_B max_T <= 2^21 and 20 or 21 features\n"); return NULL;
     }
     if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { fprintf(stderr, "rade_train_open: no usable GPU (this library has no CPU path)\n"); return NULL; }
@@ -94,7 +93,7 @@ rade_train *rade_train_open(int max_B, int max_T, int n_features, int device)
 #define GET(field, n) do { h->field = tr_alloc(n); ok = ok && h->field; } while (0)
     GET(zin, M * RD_LATENT); GET(x, M * RD_DEC_W); GET(dx, M * RD_DEC_W); GET(gi, M * TR_G); GET(y, M * TR_OUT); GET(dy, M * TR_OUT);
     GET(dg, M * TR_G); GET(dgh, M * TR_G); GET(da, M * TR_H); GET(dh, M * TR_H); GET(dc, M * TR_H); GET(frame_loss, M * 4);
-    GET(part, n_chunk * TR_G * RD_DEC_W);                            /* the largest weight gradient is smaller: 288 x 608 */
+    GET(part, n_chunk * TR_G * RD_DEC_W);                            /* the largest weight gradient is smaller: TR_G x RM_DEC_GRU_IN(TR_NL - 1) */
     for (int l = 0; l < TR_NL; l++) { GET(save[l], M * TR_SAVE); GET(sig[l], M * TR_H); }
 #undef GET
     if (!ok) { rade_train_close(h); return NULL; }
@@ -200,16 +199,16 @@ int rade_train_dec_forward(rade_train *h, const float *params_dev, const float *
     if (hipMemcpyAsync(h->zin, z_hat_dev, sizeof(float) * (size_t)M * RD_LATENT, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return -2;
     TRY(fwd_gemm(stream, M, T, h->zin, RD_LATENT, 0, P + tr_off(P_D1W), RD_LATENT, 1, P + tr_off(P_D1B), TR_H, RD_LATENT, h->x, RD_DEC_W, 0, 1, NULL, 0, NULL));
     for (int l = 0; l < TR_NL; l++) {
-        const int kg = TR_GRU_IN[l], kc = kg + TR_H;
+        const int kg = RM_DEC_GRU_IN(l), kc = RM_DEC_CONV_IN(l);
         TRY(fwd_gemm(stream, M, T, h->x, RD_DEC_W, 0, P + tr_loff(l, L_WIH), kg, 1, P + tr_loff(l, L_BIH), TR_G, kg, h->gi, TR_G, 0, 0, NULL, 0, NULL));
         ph_end(h, stream); ph_begin(h, PH_FWD_SCAN, stream);
         TRY(tr_launch_scan_fwd(h->gi, P + tr_loff(l, L_WHH), P + tr_loff(l, L_BHH), h->save[l], B, T, stream));
         ph_end(h, stream); ph_begin(h, PH_FWD_GEMM, stream);
         const float *hh = h->save[l] + 4 * TR_H;
         TRY(fwd_gemm(stream, M, T, hh, TR_SAVE, 0, P + tr_loff(l, L_GLU), TR_H, 1, NULL, TR_H, TR_H, h->x + kg, RD_DEC_W, 0, 2, hh, TR_SAVE, h->sig[l]));
-        const float *cw = P + tr_loff(l, L_CW);                       /* [32][kc][2]: tap 0 is the older row */
-        TRY(fwd_gemm(stream, M, T, h->x, RD_DEC_W, 1, cw, 2 * kc, 2, NULL, 32, kc, h->x + kc, RD_DEC_W, 0, 0, NULL, 0, NULL));
-        TRY(fwd_gemm(stream, M, T, h->x, RD_DEC_W, 0, cw + 1, 2 * kc, 2, P + tr_loff(l, L_CB), 32, kc, h->x + kc, RD_DEC_W, 1, 1, NULL, 0, NULL));
+        const float *cw = P + tr_loff(l, L_CW);                       /* [TR_CONV][kc][2]: tap 0 is the older row */
+        TRY(fwd_gemm(stream, M, T, h->x, RD_DEC_W, 1, cw, 2 * kc, 2, NULL, TR_CONV, kc, h->x + kc, RD_DEC_W, 0, 0, NULL, 0, NULL));
+        TRY(fwd_gemm(stream, M, T, h->x, RD_DEC_W, 0, cw + 1, 2 * kc, 2, P + tr_loff(l, L_CB), TR_CONV, kc, h->x + kc, RD_DEC_W, 1, 1, NULL, 0, NULL));
     }
     TRY(fwd_gemm(stream, M, T, h->x, RD_DEC_W, 0, P + tr_off(P_OUTW), RD_DEC_W, 1, P + tr_off(P_OUTB), TR_OUT, RD_DEC_W, h->y, TR_OUT, 0, 0, NULL, 0, NULL));
     if (features_hat_dev && hipMemcpyAsync(features_hat_dev, h->y, sizeof(float) * (size_t)M * TR_OUT, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return -2;
@@ -250,15 +249,15 @@ int rade_train_dec_backward(rade_train *h, const float *params_dev, const float 
     TRY(dw_gemm(h, stream, M, T, dy, TR_OUT, TR_OUT, h->x, RD_DEC_W, 0, RD_DEC_W, G + tr_off(P_OUTW), RD_DEC_W, 1, G + tr_off(P_OUTB)));
     TRY(dx_gemm(stream, M, T, dy, TR_OUT, TR_OUT, P + tr_off(P_OUTW), RD_DEC_W, 1, RD_DEC_W, h->dx, RD_DEC_W, 0, 0));
     for (int l = TR_NL - 1; l >= 0; l--) {
-        const int kg = TR_GRU_IN[l], kc = kg + TR_H;
+        const int kg = RM_DEC_GRU_IN(l), kc = RM_DEC_CONV_IN(l);
         /* conv: tap 1 reads row t, tap 0 row t - 1 */
         const float *cw = P + tr_loff(l, L_CW);
         float *gcw = G + tr_loff(l, L_CW);
-        TRY(tr_launch_dtanh(h->x, h->dx, kc, 32, h->dc, M, stream));
-        TRY(dw_gemm(h, stream, M, T, h->dc, 32, 32, h->x, RD_DEC_W, 1, kc, gcw, 2 * kc, 2, NULL));
-        TRY(dw_gemm(h, stream, M, T, h->dc, 32, 32, h->x, RD_DEC_W, 0, kc, gcw + 1, 2 * kc, 2, G + tr_loff(l, L_CB)));
-        TRY(dx_gemm(stream, M, T, h->dc, 32, 32, cw + 1, 2 * kc, 2, kc, h->dx, RD_DEC_W, 1, 0));
-        TRY(dx_gemm(stream, M, T, h->dc, 32, 32, cw, 2 * kc, 2, kc, h->dx, RD_DEC_W, 1, 1));
+        TRY(tr_launch_dtanh(h->x, h->dx, kc, TR_CONV, h->dc, M, stream));
+        TRY(dw_gemm(h, stream, M, T, h->dc, TR_CONV, TR_CONV, h->x, RD_DEC_W, 1, kc, gcw, 2 * kc, 2, NULL));
+        TRY(dw_gemm(h, stream, M, T, h->dc, TR_CONV, TR_CONV, h->x, RD_DEC_W, 0, kc, gcw + 1, 2 * kc, 2, G + tr_loff(l, L_CB)));
+        TRY(dx_gemm(stream, M, T, h->dc, TR_CONV, TR_CONV, cw + 1, 2 * kc, 2, kc, h->dx, RD_DEC_W, 1, 0));
+        TRY(dx_gemm(stream, M, T, h->dc, TR_CONV, TR_CONV, cw, 2 * kc, 2, kc, h->dx, RD_DEC_W, 1, 1));
         /* GLU */
         const float *hh = h->save[l] + 4 * TR_H;
         TRY(tr_launch_glu_bwd(h->dx, kg, h->save[l], h->sig[l], h->da, h->dh, M, stream));

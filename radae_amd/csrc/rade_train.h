@@ -11,11 +11,14 @@
 extern "C" {
 #endif
 
-#define TR_H        96     /* GRU hidden units */
-#define TR_G        288    /* three gates, torch's order r, z, n */
-#define TR_SAVE     480    /* saved planes of a GRU row: r, z, n, hn = W_hn h + b_hn, h */
-#define TR_OUT      84     /* 4 frames x 21 features */
-#define TR_NL       5
+/* the decoder's shapes under the names the training code uses (rade_model_geom.h); the kernels' tiling assumes them (rade_train.hip) */
+#define TR_H        RM_DEC_H        /* GRU hidden units */
+#define TR_G        RM_DEC_G        /* three gates, torch's order r, z, n */
+#define TR_SAVE     (5 * TR_H)      /* saved planes of a GRU row: r, z, n, hn = W_hn h + b_hn, h */
+#define TR_OUT      RM_FEAT_AUX     /* 4 frames x 21 features */
+#define TR_NL       RM_NL
+#define TR_CONV     RM_DEC_CONV
+static_assert(RM_DEC_D1 == TR_H && RM_DEC_GLU == TR_H, "dense1 and the GLU are as wide as a GRU: one TR_H-wide buffer (dc, da, dh) serves each");
 #define TR_SEQ      16     /* sequences per workgroup of the scans: the M dimension of mfma_f32_16x16x4f32 */
 #define TR_CHUNK    256    /* rows of M = B T per partial sum of a weight gradient */
 #define TR_MAX_ROWS (1L << 21) /* rows of a handle: the GEMMs put the 64-row tiles on grid.y (at most 65535), and the workspace is 22 KB per row */

@@ -287,10 +287,10 @@ __global__ __launch_bounds__(256) void k_tr_loss_frames(const float *feat, int n
 {
     const long f = (long)blockIdx.x * 256 + threadIdx.x;
     if (f >= n) return;
-    const float *y = feat + f * nf, *p = fhat + f * 21;
-    float *d = dfhat + f * 21;
+    const float *y = feat + f * nf, *p = fhat + f * (RM_NFEAT + 1);
+    float *d = dfhat + f * (RM_NFEAT + 1);
     const float c1 = (float)(3.0 * (10.0 / 18.0)), c2 = (float)(1.0 / 18.0), c3 = (float)(0.5 / 18.0);
-    const float pitch = 2.0f * (p[18] - y[18]), corr = p[19] - y[19], data = nf == 21 ? p[20] - y[20] : 0.0f;
+    const float pitch = 2.0f * (p[18] - y[18]), corr = p[19] - y[19], data = nf == RM_NFEAT + 1 ? p[RM_NFEAT] - y[RM_NFEAT] : 0.0f;
     float pw = y[19] + 0.5f;
     pw = pw > 0.0f ? pw * pw : 0.0f;                                   // relu(.) ** 2: takes no gradient (it depends on the target alone)
     const float extra = c1 * fabsf(pitch) * pw + c2 * corr * corr + c3 * data * data;
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256) void k_tr_loss_frames(const float *feat, int n
     frame_loss[f] = acc / 18.0f;
     d[18] = 60.0f * pw * (pitch > 0.0f ? 1.0f : pitch < 0.0f ? -1.0f : 0.0f) * scale;      // sign(0) = 0
     d[19] = 2.0f * corr * scale;
-    d[20] = data * scale;
+    d[RM_NFEAT] = data * scale;
 }
 
 __global__ __launch_bounds__(256) void k_tr_loss_sum(const float *frame_loss, double *loss, int B, int F)

@@ -133,6 +133,17 @@ def c_layouts(headers, include_dirs, tmp):
     return out
 
 
+def c_values(headers, exprs, include_dirs, tmp):
+    """{expression: its integer value} from the host compiler, for constant expressions over the header files' macros (function-like ones included)"""
+    cc = shutil.which("cc")
+    assert cc, "no host C compiler `cc` (build() needs one too)"
+    lines = ["#include <stdio.h>"] + [f'#include "{os.path.abspath(h)}"' for h in headers] + ["int main(void) {"]
+    lines += [f'printf("%lld\\n", (long long)({e}));' for e in exprs]
+    open(os.path.join(tmp, "values.c"), "w").write("\n".join(lines + ["return 0; }", ""]))
+    subprocess.check_call([cc] + [a for d in include_dirs for a in ("-I", d)] + ["-o", os.path.join(tmp, "values"), os.path.join(tmp, "values.c")])
+    return dict(zip(exprs, map(int, subprocess.check_output([os.path.join(tmp, "values")], text=True).split())))
+
+
 def layout_mismatches(mirrors, want, same_name=lambda c_name, mirror_name: c_name == mirror_name):
     """{typedef: ctypes structure} against c_layouts()'s answer: size, number of fields, and every field's name, offset and size"""
     bad = [f"{t}: no such typedef in the headers" for t in mirrors if t not in want]
