@@ -735,7 +735,7 @@ int rade_batch_sigstat(rade_batch *h, const void *x_dev, long x_stride, const in
  *   other streams of the batch, on B or on the strides.
  *   Host, in double after the read-back: sigma_r = (S1 + S2) / 38400 / sqrt(pi / 2) / 2, Dthresh = 2 sigma_r sqrt(-ln(Pacq_error1 / 5)), candidate = Dtmax12 > Dthresh.
  *   (The script's float32 means differ from these double sums by a few 1e-7 of Dthresh.)
- * How the device forms D: the two-stage correlator of the receiver's search (rade_host.c, rd_corrq16_table_fill), with the engine's own two tables.  p_w[m][f] = sum_{r < 16}
+ * How the device forms D: the two-stage correlator of the receiver's search (rade_pack.c, rd_corrq16_table_fill), with the engine's own two tables.  p_w[m][f] = sum_{r < 16}
  *   alpha[r][f] s_r[m], s_r[m] = p[m] q_r(x_m), q_r the 16 polynomials orthonormal on x_m = (m - 79.5) / 80, alpha[r][f] = sum_m q_r(x_m) e^{j w_f m}; so
  *   D[t][f] = sum_r alpha[r][f] Mom_r[t], Mom_r[t] = sum_m conj(x[t + m]) s_r[m].  Stage 1, the moments: a real GEMM, rows (r, re | im), K = (m, re | im), columns t, on
  *   v_mfma_f32_16x16x32_f16.  Both operands are two binary16 planes, v = hi + lo with hi = fl16(v), lo = fl16(v - hi), under a power-of-two scale: 2^12 for s_r, and for

@@ -24,7 +24,7 @@ extern "C" {
 #define RD_NEOO     1152
 #define RD_RXBUF    2112  /* 2*Nmf + M + Ncp */
 #define RD_NFC      40    /* coarse frequency bins */
-#define RD_NQ       16    /* polynomial moments of the two-stage pilot correlator (rade_host.c: rd_corrq16_table_fill) */
+#define RD_NQ       16    /* polynomial moments of the two-stage pilot correlator (rade_pack.c: rd_corrq16_table_fill) */
 #define RD_NTAP     101
 #define RD_NINMAX   1120
 #define RD_LATENT   RM_LATENT
@@ -36,7 +36,7 @@ extern "C" {
 #define RD_ENC_IN   RM_FEAT_PAD /* 84 padded to a multiple of 16 (k-block of the f16 matrix instructions) */
 #define RD_RX_ROUND_MAX 128   /* capacity: do_radae_rx calls per stream per sync-kernel launch (engine picks R <= this) */
 #define RD_DEC_ROWS_MAX (3 * RD_RX_ROUND_MAX)
-/* geometry of the two-stage pilot correlator's operand tables (rade_corr2.h explains them and checks the divisions; rade_host.c fills them).  A fragment plane is what
+/* geometry of the two-stage pilot correlator's operand tables (rade_corr2.h explains them and checks the divisions; rade_pack.c fills them).  A fragment plane is what
  * the 64 lanes of one v_mfma_f32_16x16x32_f16 operand hold, 8 binary16 each; every table entry is two of them (hi, lo) */
 #define RD_FRAG_HALFS (64 * 8)
 #define RD_CORR_NRT (2 * RD_NQ / 16)                            /* stage 1, row tiles: 16 of the rows (moment, re | im) */

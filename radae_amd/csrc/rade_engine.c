@@ -27,6 +27,7 @@
 #include "rade_api.h"
 #include "rade_host.h"
 #include "rade_engine.h"
+#include "rade_pack.h"
 
 #define CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "rade: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); goto fail; } } while (0)
 
@@ -120,66 +121,51 @@ int dev_grow(rade_batch *h, void *ptr_addr, long *cap, long need, size_t elem_by
     return p ? 0 : -1;
 }
 
-/* n_halfs binary16 operands written by `fill` from the constant tables, on the device */
-static unsigned short *upload_table16(rade_batch *h, const rd_tables *tab, void (*fill)(const rd_tables *, unsigned short *), size_t n_halfs)
+/* One operand form of W[N][K] on the device: the pointer at plane_addr (of any object type) and *scales.  RD_FRAG_F32: the float32 fragments of k_gemm, no scales.
+ * The binary16 layouts: an int8-exact layer (row scales, every w = q row_scale[n]) as ONE plane of the integers q plus its scales -- exact, and half the bytes to
+ * stream --, any other layer as two planes of 2^10 w without scales.  optional: the one-plane form or nothing, and the engine can do without the device memory.
+ * Returns 0 = packed and uploaded, 1 = the layer has no such form (K is no whole number of k-steps, or optional and not int8-exact): both stay NULL,
+ * -1 = a weight does not fit the planes, -2 = no host memory. */
+static int upload_form(rade_batch *h, const rd_frag *L, const float *w, const float *row_scale, int N, int K, int optional, void *plane_addr, float **scales)
 {
-    unsigned short *t = malloc(sizeof(unsigned short) * n_halfs), *d = NULL;
-    if (t) { fill(tab, t); d = dev_upload(h, t, sizeof(unsigned short) * n_halfs); } else h->alloc_failed = 1;
-    free(t);
-    return d;
+    const int f32 = L == &RD_FRAG_F32, ks = rd_frag_kstep(L), tiles = rd_frag_tiles(L, N);
+    const size_t elem = f32 ? sizeof(float) : sizeof(unsigned short);
+    void *d = NULL;
+    memcpy(plane_addr, &d, sizeof d); *scales = NULL;
+    if (!f32 && K % ks) return 1;
+    void *p = malloc(elem * (size_t)rd_frag_size(L, tiles, (K + ks - 1) / ks));
+    float *sc = malloc(sizeof(float) * (size_t)tiles * L->R);
+    if (!p || !sc) { free(p); free(sc); return -2; }
+    long n = f32 ? rd_pack_weights(w, N, K, p) : rd_pack_int8(L, w, row_scale, N, K, p, sc);
+    const int exact = !f32 && n > 0;
+    if (!f32 && !exact && !optional) n = rd_pack_split(L, w, N, K, p);
+    if (n > 0) {
+        d = optional ? dev_upload_opt(h, p, elem * (size_t)n) : dev_upload(h, p, elem * (size_t)n);
+        memcpy(plane_addr, &d, sizeof d);
+        if (exact) *scales = optional ? dev_upload_opt(h, sc, sizeof(float) * (size_t)tiles * L->R) : dev_upload(h, sc, sizeof(float) * (size_t)tiles * L->R);
+    }
+    free(p); free(sc);
+    return n > 0 ? 0 : (optional ? 1 : -1);
 }
 
-/* pack W[N][K] (optionally padding K up to Kpad with zero columns) and upload; NULL = the layer has no such form (wp16 / wa16, their scales), -1 = it does not fit one */
+/* W[N][K] (K padded up to Kpad with zero columns) in its three operand forms, and the bias; -1 = a weight does not fit the planes, or no memory */
 static int upload_lin(rade_batch *h, dev_lin *d, const float *w, const float *b, const float *row_scale, int N, int K, int Kpad)
 {
-    float *wsrc = (float *)w, *tmp = NULL;
+    float *tmp = NULL, *none;
     if (Kpad != K) {
-        tmp = calloc((size_t)N * Kpad, sizeof(float));
+        if (!(tmp = calloc((size_t)N * Kpad, sizeof(float)))) { h->alloc_failed = 1; return -1; }
         for (int o = 0; o < N; o++) memcpy(tmp + (size_t)o * Kpad, w + (size_t)o * K, sizeof(float) * K);
-        wsrc = tmp;
+        w = tmp;
     }
-    const long n = rd_packed_size(N, Kpad);
-    float *packed = malloc(sizeof(float) * n);
-    rd_pack_weights(wsrc, N, Kpad, packed);
-    d->wp = dev_upload(h, packed, sizeof(float) * n);
+    d->N = N; d->K = Kpad;
+    int r = upload_form(h, &RD_FRAG_F32, w, NULL, N, Kpad, 0, &d->wp, &none);
     d->bias = b ? dev_upload(h, b, sizeof(float) * N) : NULL;
-    d->N = N; d->K = Kpad; d->wp16 = NULL; d->wscale16 = NULL;
-    if (Kpad % 16 == 0) {                  /* binary16 copy for the f16 matrix cores (k_gemm16): int8-exact layers as ONE plane of integers + column scales, others as two planes */
-        const long n16 = rd_packed16_size(N, Kpad);
-        unsigned short *p16 = malloc(sizeof(unsigned short) * n16);
-        float *sc = calloc((size_t)((N + 31) / 32) * 32, sizeof(float));
-        long nq = -1;
-        if (p16 && sc && row_scale) nq = rd_pack_weights_q16(wsrc, row_scale, N, Kpad, p16, sc);
-        if (nq > 0) {
-            d->wp16 = dev_upload(h, p16, sizeof(unsigned short) * nq);
-            d->wscale16 = dev_upload(h, sc, sizeof(float) * (size_t)((N + 31) / 32) * 32);
-        } else {
-            if (!p16 || rd_pack_weights_f16x2(wsrc, N, Kpad, p16) < 0) {
-                fprintf(stderr, "rade: a weight exceeds the range of the split-binary16 operand planes (|w| < 63.9)\n");
-                free(p16); free(sc); free(packed); free(tmp); return -1;
-            }
-            d->wp16 = dev_upload(h, p16, sizeof(unsigned short) * n16);
-        }
-        free(p16); free(sc);
-    }
-    d->wa16 = NULL; d->wscale = NULL;
-    if (Kpad % 32 == 0) {                  /* A-operand layout of the in-kernel decoder's 16x16x32 products */
-        const long na = rd_packed16a_size(N, Kpad);
-        unsigned short *pa = malloc(sizeof(unsigned short) * na);
-        float *sc = malloc(sizeof(float) * (size_t)((N + 15) / 16) * 16);
-        long nq = -1;
-        if (pa && sc && row_scale) nq = rd_pack_weights_q16_a16(wsrc, row_scale, N, Kpad, pa, sc);
-        if (nq > 0) {                      /* int8 in the blob: the integers themselves in ONE binary16 plane (exact), scales apart: half the bytes to stream */
-            d->wa16 = dev_upload(h, pa, sizeof(unsigned short) * nq);
-            d->wscale = dev_upload(h, sc, sizeof(float) * (size_t)((N + 15) / 16) * 16);
-        } else {
-            if (!pa || rd_pack_weights_f16x2_a16(wsrc, N, Kpad, pa) < 0) { free(pa); free(sc); free(packed); free(tmp); return -1; }
-            d->wa16 = dev_upload(h, pa, sizeof(unsigned short) * na);
-        }
-        free(pa); free(sc);
-    }
-    free(packed); free(tmp);
-    return (d->wp && (!b || d->bias)) ? 0 : -1;
+    if (r >= 0) r = upload_form(h, &RD_FRAG_B16, w, row_scale, N, Kpad, 0, &d->wp16, &d->wscale16);     /* k_gemm16, k_encf_gemm */
+    if (r == -1) fprintf(stderr, "rade: a weight exceeds the range of the split-binary16 operand planes (|w| < 63.9)\n");
+    if (r >= 0) r = upload_form(h, &RD_FRAG_A16, w, row_scale, N, Kpad, 0, &d->wa16, &d->wscale);        /* the in-kernel decoder's 16x16x32 products */
+    free(tmp);
+    if (r == -2) h->alloc_failed = 1;
+    return (r >= 0 && d->wp && (!b || d->bias)) ? 0 : -1;
 }
 
 /* start-of-utterance state, ONE launch (k_batch_reset) for the directions asked for; the trace buffers and the Tx filter state only where they exist */
@@ -254,15 +240,22 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
     if (h->dec_rows > 63) h->dec_rows = 63;            /* the stage's LDS row flags hold DQ_PEND_MAX = 64 entries (rade_kernels.hip) */
     const size_t DR = (size_t)h->dec_rows;
 
-    rd_tables *tab = malloc(sizeof *tab);
-    rd_tables_fill(tab);
-    h->d_tab = dev_upload(h, tab, sizeof *tab);
-    /* the pilot correlator in two stages: 16 polynomial moments, then their expansion to the 40 frequencies (rade_host.c) */
-    h->corrq16 = upload_table16(h, tab, rd_corrq16_table_fill, RD_CORRQ16_HALFS);
-    h->corra16 = upload_table16(h, tab, rd_corra16_table_fill, RD_CORRA16_HALFS);
-    h->wfwd16 = upload_table16(h, tab, rd_wfwd16_table_fill, RD_WFWD16_HALFS);    /* the demodulator DFT matrix as matrix-core operands (k_rx_sync2) */
-    h->bpf16 = upload_table16(h, tab, rd_bpf16_table_fill, RD_BPF16_HALFS);       /* the band-pass taps as matrix-core operands (k_bpf_fir) */
-    free(tab);
+    {   /* the constant tables, and the four of them that are matrix-core operands (rade_pack.c), through one host buffer */
+        _Static_assert(RD_CORRQ16_HALFS >= RD_CORRA16_HALFS && RD_CORRQ16_HALFS >= RD_WFWD16_HALFS && RD_CORRQ16_HALFS >= RD_BPF16_HALFS, "t16 holds the largest table");
+        rd_tables *tab = malloc(sizeof *tab); rd_corr_basis *basis = malloc(sizeof *basis);
+        unsigned short *t16 = malloc(sizeof(unsigned short) * RD_CORRQ16_HALFS);
+        if (tab && basis && t16) {
+            rd_tables_fill(tab);
+            h->d_tab = dev_upload(h, tab, sizeof *tab);
+            /* the pilot correlator in two stages: 16 polynomial moments, then their expansion to the 40 frequencies; one basis serves both */
+            rd_corr_basis_fill(tab, basis);
+            rd_corrq16_fill(tab, basis, t16); h->corrq16 = dev_upload(h, t16, sizeof(unsigned short) * RD_CORRQ16_HALFS);
+            rd_corra16_fill(tab, basis, t16); h->corra16 = dev_upload(h, t16, sizeof(unsigned short) * RD_CORRA16_HALFS);
+            rd_wfwd16_table_fill(tab, t16); h->wfwd16 = dev_upload(h, t16, sizeof(unsigned short) * RD_WFWD16_HALFS);    /* the demodulator DFT matrix (k_rx_sync2) */
+            rd_bpf16_table_fill(tab, t16); h->bpf16 = dev_upload(h, t16, sizeof(unsigned short) * RD_BPF16_HALFS);       /* the band-pass taps (k_bpf_fir) */
+        } else h->alloc_failed = 1;
+        free(tab); free(basis); free(t16);
+    }
     {   /* ((n - 79.5) / 80)^m, m = 0..7, by repeated multiplication (the order the kernels build their LDS copy in) */
         double vm[8][RD_M];
         for (int n = 0; n < RD_M; n++) { const double nu = ((double)n - 79.5) / 80.0; double v = 1.0; for (int m = 0; m < 8; m++) { vm[m][n] = v; v *= nu; } }
@@ -290,12 +283,7 @@ rade_batch *rade_batch_open_mem(const void *blob, size_t blob_len, const rade_ba
         h->enc_bhh[l] = dev_upload(h, m.enc_gru[l].b_hh, sizeof(float) * RM_ENC_G);
         h->dec_whh[l] = dev_upload(h, m.dec_gru[l].w_hh, sizeof(float) * RM_DEC_G * RM_DEC_H);
         h->dec_bhh[l] = dev_upload(h, m.dec_gru[l].b_hh, sizeof(float) * RM_DEC_G);
-        if (m.dec_gru[l].s_hh) {
-            unsigned short *pa = malloc(sizeof(unsigned short) * rd_packed16a_size(RM_DEC_G, RM_DEC_H)); float *scl = malloc(sizeof(float) * RM_DEC_G);
-            const long nq = (pa && scl) ? rd_pack_weights_q16_a16(m.dec_gru[l].w_hh, m.dec_gru[l].s_hh, RM_DEC_G, RM_DEC_H, pa, scl) : -1;
-            if (nq > 0) { h->dec_whq[l] = dev_upload_opt(h, pa, sizeof(unsigned short) * nq); h->dec_whs[l] = dev_upload_opt(h, scl, sizeof(float) * RM_DEC_G); }
-            free(pa); free(scl);
-        }
+        (void)upload_form(h, &RD_FRAG_A16, m.dec_gru[l].w_hh, m.dec_gru[l].s_hh, RM_DEC_G, RM_DEC_H, 1, &h->dec_whq[l], &h->dec_whs[l]);   /* int8-exact, or k_rx_sync2 scans in float32 */
     }
     if (err || h->alloc_failed) { fprintf(stderr, "rade: weight upload failed\n"); goto fail; }
 

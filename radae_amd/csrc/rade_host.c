@@ -3,7 +3,7 @@
  *   1. constant tables of the OFDM modem (rd_tables), evaluated with the same float32/float64 steps
  *      NumPy/PyTorch take in the reference so the device kernels see bit-comparable constants;
  *   2. DNNw weight-blob reader -> fp32 matrices (the blob is int8 + per-row scales for most layers);
- *   3. weight packing into the MFMA fragment order k_gemm streams;
+ *   3. (the weights and constant tables in the matrix cores' fragment order: rade_pack.c)
  *   4. the fractional resampler's Q32.32 time base and its windowed-sinc taps (rade_batch_resample).
  *   5. the rational rate converter's ratio, taps and output count (rade_batch_rate_convert).
  *   6. the analog FM stage's noise level, least-squares filter design and folded de-emphasis (rade_batch_fm_mod / rade_batch_fm_demod).
@@ -293,304 +293,6 @@ void rd_model_free(rd_model *m)
         lin_free(&m->enc_conv[i]); lin_free(&m->dec_conv[i]); lin_free(&m->dec_glu[i]);
     }
     memset(m, 0, sizeof *m);
-}
-
-/* ---------------------------------------------------------------------------------------------
- * 3. packing for k_gemm: out[((kb*ntt + nt)*64 + lane)*4 + s] = W[nt*32 + (lane&31)][8kb + 4(lane>>5) + s]
- * -------------------------------------------------------------------------------------------*/
-long rd_packed_size(int N, int K) { return (long)((K + 7) / 8) * ((N + 31) / 32) * 256; }
-
-long rd_pack_weights(const float *W, int N, int K, float *out)
-{
-    const int nkb = (K + 7) / 8, ntt = (N + 31) / 32;
-    for (int kb = 0; kb < nkb; kb++)
-        for (int nt = 0; nt < ntt; nt++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int s = 0; s < 4; s++) {
-                    const int nn = nt * 32 + (lane & 31), k = kb * 8 + 4 * (lane >> 5) + s;
-                    out[(((size_t)kb * ntt + nt) * 64 + lane) * 4 + s] = (nn < N && k < K) ? W[(size_t)nn * K + k] : 0.0f;
-                }
-    return rd_packed_size(N, K);
-}
-
-/* float -> IEEE binary16 (round to nearest even, subnormals kept) and back: the two-plane split of the decoder weights */
-static unsigned short f32_to_f16(float f)
-{
-    unsigned int x; memcpy(&x, &f, 4);
-    const unsigned int sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u) return (unsigned short)(sign | 0x7c00u | (x > 0x7f800000u ? 0x200u : 0));
-    if (x >= 0x477ff000u) return (unsigned short)(sign | 0x7c00u);                 /* rounds to >= 65520: infinity */
-    if (x < 0x38800000u) {                                                         /* below 2^-14: subnormal half */
-        if (x < 0x33000000u) return (unsigned short)sign;                          /* < 2^-25 */
-        const int e = (int)(x >> 23);                                              /* biased float exponent, 102..112 */
-        unsigned int m = (x & 0x7fffffu) | 0x800000u;
-        const int shift = 126 - e;                                                 /* 14..24 */
-        const unsigned int halfm = m >> shift, rem = m & ((1u << shift) - 1u), mid = 1u << (shift - 1);
-        unsigned int r = halfm + ((rem > mid || (rem == mid && (halfm & 1u))) ? 1u : 0u);
-        return (unsigned short)(sign | r);
-    }
-    unsigned int r = ((x - 0x38000000u) >> 13);
-    const unsigned int rem = x & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) r++;
-    return (unsigned short)(sign | r);
-}
-static float f16_to_f32(unsigned short h)
-{
-    const unsigned int sign = (unsigned int)(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-    unsigned int x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else { float f = (float)m * 5.9604644775390625e-08f; memcpy(&x, &f, 4); x |= sign; }      /* m * 2^-24 */
-    } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
-    else x = sign | ((e + 112u) << 23) | (m << 13);
-    float f; memcpy(&f, &x, 4); return f;
-}
-
-/* Returns the packed size, or -1 when a weight does not fit the planes (|w| 2^10 must stay below binary16's 65504).
- * W[N][K] (K a multiple of 16) -> B operands of v_mfma_f32_32x32x16_f16 in two planes, 2^10 w = hi + lo to 22 bits
- * (the power-of-two scale keeps the low plane out of binary16's subnormal range; the GEMM epilogue undoes it):
- * out[kb][nt][plane][lane][j] = plane(1024 W[32 nt + lane%32][16 kb + 8 (lane/32) + j]) */
-long rd_packed16_size(int N, int K) { return (long)(K / 16) * ((N + 31) / 32) * 2 * 64 * 8; }
-long rd_pack_weights_f16x2(const float *W, int N, int K, unsigned short *out)
-{
-    const int nkb = K / 16, ntt = (N + 31) / 32;
-    for (int kb = 0; kb < nkb; kb++)
-        for (int nt = 0; nt < ntt; nt++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int nn = nt * 32 + (lane & 31), k = kb * 16 + 8 * (lane >> 5) + j;
-                    const float w = nn < N ? 1024.0f * W[(size_t)nn * K + k] : 0.0f;
-                    if (!(fabsf(w) < 65504.0f)) return -1;                         /* the high plane would be inf (or the weight is NaN) */
-                    const unsigned short hi = f32_to_f16(w), lo = f32_to_f16(w - f16_to_f32(hi));
-                    unsigned short *o = out + ((((size_t)kb * ntt + nt) * 2) * 64 + lane) * 8 + j;
-                    o[0] = hi; o[64 * 8] = lo;
-                }
-    return rd_packed16_size(N, K);
-}
-
-/* The receiver's in-kernel decoder (dq_gemm_tile) uses v_mfma_f32_16x16x32_f16 with the weights as the A operand: 16 output
- * columns x 32 k per instruction, the same two planes of 2^10 w.  K must be a multiple of 32; N is padded to 16 with zeros.
- * out[ks][ct][plane][lane][j] = plane(1024 W[16 ct + lane%16][32 ks + 8 (lane/16) + j]).  Returns the size or -1 on overflow. */
-long rd_packed16a_size(int N, int K) { return (long)(K / 32) * ((N + 15) / 16) * 2 * 64 * 8; }
-long rd_pack_weights_f16x2_a16(const float *W, int N, int K, unsigned short *out)
-{
-    const int nks = K / 32, nct = (N + 15) / 16;
-    for (int ks = 0; ks < nks; ks++)
-        for (int ct = 0; ct < nct; ct++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int nn = ct * 16 + (lane & 15), k = ks * 32 + 8 * (lane >> 4) + j;
-                    const float w = nn < N ? 1024.0f * W[(size_t)nn * K + k] : 0.0f;
-                    if (!(fabsf(w) < 65504.0f)) return -1;
-                    const unsigned short hi = f32_to_f16(w), lo = f32_to_f16(w - f16_to_f32(hi));
-                    unsigned short *o = out + ((((size_t)ks * nct + ct) * 2) * 64 + lane) * 8 + j;
-                    o[0] = hi; o[64 * 8] = lo;
-                }
-    return rd_packed16a_size(N, K);
-}
-
-static int q_of(float w, float sc, float *q)
-{   /* w = q * sc with integer |q| <= 127, exactly? */
-    *q = 0.0f;
-    if (w == 0.0f) return 0;
-    if (sc == 0.0f) return -1;
-    *q = rintf(w / sc);
-    return (fabsf(*q) <= 127.0f && *q * sc == w) ? 0 : -1;
-}
-/* chunk-major binary16 plane of the integers q of an int8 layer (w = q * row_scale[n] exactly) for the single-stream step kernel
- * (rade_core_step.hip): out[(c * Npad + n) * 8 + j] = q(W[n][8 c + j]), K zero-padded to Kpad (a multiple of 8), rows to Npad (a
- * multiple of 64).  Returns 0, or -1 when the layer is not int8-exact. */
-int rd_chunkmajor_q16(const float *W, const float *row_scale, int N, int K, int Kpad, int Npad, unsigned short *out)
-{
-    if (!row_scale) return -1;
-    for (int c = 0; c < Kpad / 8; c++)
-        for (int n = 0; n < Npad; n++)
-            for (int j = 0; j < 8; j++) {
-                const int k = 8 * c + j;
-                float q = 0.0f;
-                if (n < N && k < K && q_of(W[(size_t)n * K + k], row_scale[n], &q)) return -1;
-                out[((size_t)c * Npad + n) * 8 + j] = f32_to_f16(q);
-            }
-    return 0;
-}
-void rd_chunkmajor_f32(const float *W, int N, int K, int Kpad, int Npad, float *out)
-{
-    for (int c = 0; c < Kpad / 8; c++)
-        for (int n = 0; n < Npad; n++)
-            for (int j = 0; j < 8; j++) { const int k = 8 * c + j; out[((size_t)c * Npad + n) * 8 + j] = (n < N && k < K) ? W[(size_t)n * K + k] : 0.0f; }
-}
-
-long rd_pack_weights_q16(const float *W, const float *row_scale, int N, int K, unsigned short *out, float *scale_out)
-{
-    const int nkb = K / 16, ntt = (N + 31) / 32;
-    if (!row_scale) return -1;
-    for (int n = 0; n < ntt * 32; n++) scale_out[n] = n < N ? row_scale[n] : 0.0f;
-    for (int kb = 0; kb < nkb; kb++)
-        for (int nt = 0; nt < ntt; nt++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int nn = nt * 32 + (lane & 31), k = kb * 16 + 8 * (lane >> 5) + j;
-                    float q = 0.0f;
-                    if (nn < N && q_of(W[(size_t)nn * K + k], row_scale[nn], &q)) return -1;
-                    out[(((size_t)kb * ntt + nt) * 64 + lane) * 8 + j] = f32_to_f16(q);
-                }
-    return (long)nkb * ntt * 64 * 8;
-}
-long rd_pack_weights_q16_a16(const float *W, const float *row_scale, int N, int K, unsigned short *out, float *scale_out)
-{
-    const int nks = K / 32, nct = (N + 15) / 16;
-    if (!row_scale) return -1;
-    for (int n = 0; n < nct * 16; n++) scale_out[n] = n < N ? row_scale[n] : 0.0f;
-    for (int ks = 0; ks < nks; ks++)
-        for (int ct = 0; ct < nct; ct++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int nn = ct * 16 + (lane & 15), k = ks * 32 + 8 * (lane >> 4) + j;
-                    float q = 0.0f;
-                    if (nn < N) {
-                        const float w = W[(size_t)nn * K + k];
-                        if (w != 0.0f) {
-                            if (row_scale[nn] == 0.0f) return -1;
-                            q = rintf(w / row_scale[nn]);
-                            if (!(fabsf(q) <= 127.0f) || q * row_scale[nn] != w) return -1;      /* not an int8-exact layer after all */
-                        }
-                    }
-                    out[(((size_t)ks * nct + ct) * 64 + lane) * 8 + j] = f32_to_f16(q);
-                }
-    return (long)nks * nct * 64 * 8;
-}
-
-/* ---- the pilot correlator in two stages (round 5): the basis and the two tables.  The device side -- operand layouts, scales and the product order, for the search,
- * check_pilots and whole-file acquisition alike -- is rade_corr2.h; the tables' geometry is RD_CORR_* of rade_dev.h ------------------------------------------------
- * p_w[m][f] = p[m] e^{j w_f m} for the 40 coarse frequencies |f| <= 50 Hz spans a window of 160 samples: the phase e^{j w_f (m - 79.5)} moves by at most
- * +-pi across it, i.e. as a function of x = (m - 79.5) / 80 it is band-limited to a time-bandwidth product of 2 and is reproduced to 1.7e-10 by its
- * projection on the first RD_NQ = 16 polynomials q_r orthonormal on the 160 grid points (14: 1.8e-8, 12: 1.5e-6):
- *     p_w[m][f] = sum_r alpha[r][f] s_r[m],   s_r[m] = p[m] q_r(x_m),   alpha[r][f] = e^{j w_f 79.5} sum_m q_r(x_m) e^{j w_f (m - 79.5)}
- * so Dt[t][f] = sum_m conj(rx[t + m]) p_w[m][f] = sum_r alpha[r][f] Mom_r[t] with the 16 "moments" Mom_r[t] = sum_m conj(rx[t + m]) s_r[m]: the big
- * product (K = 320 real) has 32 rows (two 16-row tiles) instead of 80 (five), and a second product with K = 32 expands the moments to the 40 frequencies.
- * On v_mfma_f32_16x16x32_f16: 2 x 10 x 3 + 5 x 5 = 85 matrix instructions per tile of 16 timings instead of 5 x 10 x 3 = 150.
- * rd_corrq16_table_fill: stage 1, the realified s_r (rows n' = 2 r + c', k = 2 m + c: {sr, si; si, -sr}[c'][c]), 2^12-scaled, two binary16 planes,
- *                        A-operand order: out[tile][s][plane][lane][j] = plane(S[16 tile + lane % 16][32 s + 8 (lane / 16) + j])
- * rd_corra16_table_fill: stage 2, A2[n = 2 f + c''][n'] = {ar, -ai; ai, ar} of alpha[r][f], 2^10-scaled, two planes.  Its K axis is ordered the way
- *                        stage 1's accumulators lie in a lane (C layout of two 16-row tiles: lane group g holds rows 4 g .. 4 g + 3 of either tile), so that
- *                        the moments go from accumulator registers to B-operand registers without leaving the lane:
- *                        k-slot (g, j): n' = 4 g + j (j < 4), 16 + 4 g + (j - 4) (j >= 4).   out[tile][plane][lane][j] */
-static void corr_basis(const rd_tables *T, double q[RD_NQ][RD_M], double alr[RD_NQ][RD_NFC], double ali[RD_NQ][RD_NFC])
-{
-    /* orthonormal polynomials on x_m = (m - 79.5) / 80: Legendre recurrence, then two passes of modified Gram-Schmidt on the grid */
-    double x[RD_M];
-    for (int m = 0; m < RD_M; m++) x[m] = ((double)m - 79.5) / 80.0;
-    for (int m = 0; m < RD_M; m++) { q[0][m] = 1.0; q[1][m] = x[m]; }
-    for (int r = 1; r + 1 < RD_NQ; r++)
-        for (int m = 0; m < RD_M; m++) q[r + 1][m] = ((2.0 * r + 1.0) * x[m] * q[r][m] - (double)r * q[r - 1][m]) / (r + 1.0);
-    for (int r = 0; r < RD_NQ; r++) {
-        for (int pass = 0; pass < 2; pass++)
-            for (int u = 0; u < r; u++) {
-                double d = 0.0;
-                for (int m = 0; m < RD_M; m++) d += q[u][m] * q[r][m];
-                for (int m = 0; m < RD_M; m++) q[r][m] -= d * q[u][m];
-            }
-        double n2 = 0.0;
-        for (int m = 0; m < RD_M; m++) n2 += q[r][m] * q[r][m];
-        const double inv = 1.0 / sqrt(n2);
-        for (int m = 0; m < RD_M; m++) q[r][m] *= inv;
-    }
-    for (int f = 0; f < RD_NFC; f++) {
-        const double wf = 2.0 * PI_D * T->fcoarse[f] / 8000.0, cr = cos(wf * 79.5), ci = sin(wf * 79.5);
-        for (int r = 0; r < RD_NQ; r++) {
-            double ar = 0.0, ai = 0.0;
-            for (int m = 0; m < RD_M; m++) { ar += q[r][m] * cos(wf * ((double)m - 79.5)); ai += q[r][m] * sin(wf * ((double)m - 79.5)); }
-            alr[r][f] = ar * cr - ai * ci; ali[r][f] = ar * ci + ai * cr;
-        }
-    }
-}
-void rd_corrq16_table_fill(const rd_tables *T, unsigned short *out /* [2][10][2][64][8] */)
-{
-    static double q[RD_NQ][RD_M], alr[RD_NQ][RD_NFC], ali[RD_NQ][RD_NFC];
-    corr_basis(T, q, alr, ali);
-    for (int nt = 0; nt < 2; nt++)
-        for (int s = 0; s < 10; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int n = 16 * nt + (lane & 15), r = n >> 1, cp = n & 1;
-                    const int k = 32 * s + 8 * (lane >> 4) + j, m = k >> 1, c = k & 1;
-                    const double sr = (double)T->p[m][0] * q[r][m], si = (double)T->p[m][1] * q[r][m];
-                    const float v = (float)(4096.0 * (cp == 0 ? (c == 0 ? sr : si) : (c == 0 ? si : -sr)));
-                    const unsigned short hi = f32_to_f16(v), lo = f32_to_f16(v - f16_to_f32(hi));
-                    unsigned short *o = out + ((((size_t)nt * 10 + s) * 2) * 64 + lane) * 8 + j;
-                    o[0] = hi; o[64 * 8] = lo;
-                }
-}
-void rd_corra16_table_fill(const rd_tables *T, unsigned short *out /* [5][2][64][8] */)
-{
-    static double q[RD_NQ][RD_M], alr[RD_NQ][RD_NFC], ali[RD_NQ][RD_NFC];
-    corr_basis(T, q, alr, ali);
-    for (int nt = 0; nt < 5; nt++)
-        for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 8; j++) {
-                const int n = 16 * nt + (lane & 15), f = n >> 1, cpp = n & 1;
-                const int g = lane >> 4, np_ = j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4), r = np_ >> 1, cp = np_ & 1;
-                const double ar = alr[r][f], ai = ali[r][f];
-                const float v = (float)(1024.0 * (cpp == 0 ? (cp == 0 ? ar : -ai) : (cp == 0 ? ai : ar)));
-                const unsigned short hi = f32_to_f16(v), lo = f32_to_f16(v - f16_to_f32(hi));
-                unsigned short *o = out + (((size_t)nt * 2) * 64 + lane) * 8 + j;
-                o[0] = hi; o[64 * 8] = lo;
-            }
-}
-/* test aid (tests/test_host_cpu.py): the two tables multiplied back together on the host, out[m][f] (re, im) ~ p_w[m][f]: max |difference| is returned */
-double rd_corr_tables_check(const rd_tables *T)
-{
-    static double q[RD_NQ][RD_M], alr[RD_NQ][RD_NFC], ali[RD_NQ][RD_NFC];
-    corr_basis(T, q, alr, ali);
-    double worst = 0.0;
-    for (int m = 0; m < RD_M; m++)
-        for (int f = 0; f < RD_NFC; f++) {
-            double re = 0.0, im = 0.0;
-            for (int r = 0; r < RD_NQ; r++) {
-                const double sr = (double)T->p[m][0] * q[r][m], si = (double)T->p[m][1] * q[r][m];
-                re += alr[r][f] * sr - ali[r][f] * si; im += alr[r][f] * si + ali[r][f] * sr;
-            }
-            const double d = hypot(re - (double)T->p_w[m][f][0], im - (double)T->p_w[m][f][1]);
-            if (d > worst) worst = d;
-        }
-    return worst;
-}
-
-/* The demodulator DFT of k_rx_sync2 on the f16 matrix cores (receiver_one, dsp.py:487-526: sym[s][c] = sum_n x_s[n] Wfwd[n][c]).  With the row
- * R[c][2n + comp] = (wr, -wi)[comp] the real part is R . (xr, xi) and the imaginary part R . (xi, -xr): ONE 32-row operand (30 carriers) serves both, the two
- * variants of the window are two groups of B columns.  Two binary16 planes in the A-operand order of v_mfma_f32_16x16x32_f16 like the pilot table above:
- * out[tile][s][plane][lane][j] = plane(2^12 R[16 tile + lane%16][32 s + 8 (lane/16) + j]); rows 30, 31 are zero. */
-void rd_wfwd16_table_fill(const rd_tables *T, unsigned short *out /* [2][10][2][64][8] */)
-{
-    for (int tile = 0; tile < 2; tile++)
-        for (int s = 0; s < 10; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int c = 16 * tile + (lane & 15);
-                    const int k = 32 * s + 8 * (lane >> 4) + j, n = k >> 1, comp = k & 1;
-                    float v = 0.0f;
-                    if (c < RD_NC) v = 4096.0f * (comp == 0 ? T->Wfwd[n][c][0] : -T->Wfwd[n][c][1]);
-                    const unsigned short hi = f32_to_f16(v), lo = f32_to_f16(v - f16_to_f32(hi));
-                    unsigned short *o = out + ((((size_t)tile * 10 + s) * 2) * 64 + lane) * 8 + j;
-                    o[0] = hi; o[64 * 8] = lo;
-                }
-}
-
-/* complex_bpf's 101 real taps (dsp.py:46-49) as the A operands of the matrix-core FIR (rade_rx.hip: bpf_fir_tile): the Toeplitz rows
- * T[r][m] = 2^10 h[m - r] (0 outside 0 <= m - r <= 100), r = 0..15 outputs of a group, m = 0..127 window positions, in two binary16 planes
- * and the A-operand order of v_mfma_f32_16x16x32_f16: out[ks][plane][lane][j] = plane(T[lane % 16][32 ks + 8 (lane / 16) + j]) */
-void rd_bpf16_table_fill(const rd_tables *T, unsigned short *out /* [4][2][64][8] */)
-{
-    for (int ks = 0; ks < 4; ks++)
-        for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 8; j++) {
-                const int r = lane & 15, m = 32 * ks + 8 * (lane >> 4) + j, t = m - r;
-                const float v = (t >= 0 && t < RD_NTAP) ? 1024.0f * T->bpf_h[t] : 0.0f;
-                const unsigned short hi = f32_to_f16(v), lo = f32_to_f16(v - f16_to_f32(hi));
-                unsigned short *o = out + (((size_t)ks * 2) * 64 + lane) * 8 + j;
-                o[0] = hi; o[64 * 8] = lo;
-            }
 }
 
 /* ---------------------------------------------------------------------------------------------

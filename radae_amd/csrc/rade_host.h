@@ -1,4 +1,4 @@
-/* rade_host.h -- host-side model preparation (see rade_host.c) */
+/* rade_host.h -- host-side model preparation (see rade_host.c; the operand packers and table fills: rade_pack.c) */
 #ifndef RADE_HOST_H
 #define RADE_HOST_H
 
@@ -29,7 +29,7 @@ int rd_model_parse(const void *blob, size_t len, rd_model *m);
 void rd_model_free(rd_model *m);
 
 long rd_packed16_size(int N, int K);
-void rd_corrq16_table_fill(const rd_tables *T, unsigned short *out);     /* [2][10][2][64][8]: stage 1 of the two-stage pilot correlator (rade_host.c); the four tables' sizes: RD_*16_HALFS of rade_dev.h */
+void rd_corrq16_table_fill(const rd_tables *T, unsigned short *out);     /* [2][10][2][64][8]: stage 1 of the two-stage pilot correlator (rade_pack.c); the four tables' sizes: RD_*16_HALFS of rade_dev.h */
 void rd_corra16_table_fill(const rd_tables *T, unsigned short *out);     /* [5][2][64][8]: stage 2 */
 double rd_corr_tables_check(const rd_tables *T);
 void rd_wfwd16_table_fill(const rd_tables *T, unsigned short *out);

@@ -63,7 +63,7 @@ def surface(x, t0, n_rows):
 
 @functools.lru_cache(None)
 def moment_gain():
-    """G[f][m] = sum_r |alpha[r][f]| |q_r(x_m)| of the two-stage correlator (rade_host.c, corr_basis: 16 polynomials orthonormal on x_m = (m - 79.5) / 80, alpha[r][f] =
+    """G[f][m] = sum_r |alpha[r][f]| |q_r(x_m)| of the two-stage correlator (rade_pack.c, rd_corr_basis_fill: 16 polynomials orthonormal on x_m = (m - 79.5) / 80, alpha[r][f] =
     sum_m q_r(x_m) e^{j w_f m}): how much the moment form amplifies a rounding error of stage 1 on its way to frequency f.  1 at 0 Hz, 4.4 at -50 Hz"""
     xm = (np.arange(M) - 79.5) / 80
     q = np.zeros((NQ, M)); q[0] = 1; q[1] = xm

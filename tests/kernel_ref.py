@@ -77,12 +77,42 @@ def pack_q16(L, W, scale):
     return out, sc
 
 
+# ---- the matrix-core operand layouts of rade_pack.c (rade_pack.h: rd_frag), as numpy ---------------------------------------------------------------------------------
+FRAG_F32 = dict(R=32, E=4)         # float32, k_gemm
+FRAG_B16 = dict(R=32, E=8)         # B operand of v_mfma_f32_32x32x16_f16
+FRAG_A16 = dict(R=16, E=8)         # A operand of v_mfma_f32_16x16x32_f16
+
+
+def frag_layout(R, E, planes, order, tiles, steps):
+    """Where element (plane, row, k) of an operand M lies: offsets [planes][R tiles][(64 E / R) steps].  THE LANE MAP: a lane holds E consecutive k of one row,
+        row = R tile + lane % R,     k = (64 E / R) step + E (lane / R) + j,   j = 0 .. E - 1
+    at ((block planes + plane) 64 + lane) E + j with block = step tiles + tile (order "k": k-step-major) or tile steps + step (order "tile")."""
+    kstep = 64 * E // R
+    row, k = np.arange(R * tiles)[:, None], np.arange(kstep * steps)[None, :]
+    tile, step = row // R, k // kstep
+    lane, j = row % R + R * (k % kstep // E), k % E
+    block = step * tiles + tile if order == "k" else tile * steps + step
+    assert order in ("k", "tile")
+    return ((block * planes + np.arange(planes)[:, None, None]) * 64 + lane) * E + j
+
+
+def frag_pack(vals, R, E, order="k"):
+    """vals [planes][N][K] -> the operand words: rows padded to whole tiles and K to whole k-steps with zeros"""
+    vals = np.asarray(vals); P, N, K = vals.shape
+    idx = frag_layout(R, E, P, order, -(-N // R), -(-K // (64 * E // R)))
+    out = np.zeros(idx.size, vals.dtype)
+    out[idx[:, :N, :K]] = vals
+    return out
+
+
+def frag_unpack(words, R, E, planes, order, tiles, steps):
+    """the operand words back as [planes][R tiles][(64 E / R) steps]"""
+    return np.asarray(words)[frag_layout(R, E, planes, order, tiles, steps)]
+
+
 def unpack16(plane_words, N, K, planes):
-    """The packed B operands as k_gemm16 indexes them -- lane l of k-block kb and column tile nt holds W[32 nt + l % 32][16 kb + 8 (l / 32) + j], j = 0..7, at
-    ((kb ntt + nt) planes + plane) 64 + l) 8 + j -- back to `planes` float32 matrices [32 ntt][K] of the binary16 values."""
-    ntt = (N + 31) // 32
-    v = np.asarray(plane_words, np.uint16).view(np.float16).astype(np.float32).reshape(K // 16, ntt, planes, 2, 32, 8)
-    return v.transpose(2, 1, 4, 0, 3, 5).reshape(planes, ntt * 32, K)
+    """The packed B operands of k_gemm16 back to `planes` float32 matrices [32 ntt][K] of the binary16 values."""
+    return frag_unpack(np.asarray(plane_words, np.uint16).view(np.float16).astype(np.float32), **FRAG_B16, planes=planes, order="k", tiles=(N + 31) // 32, steps=K // 16)
 
 
 # ---- sentinel-filled strided buffers -----------------------------------------------------------------------------------------------------------------------------
@@ -231,17 +261,18 @@ def gru_step64(gi, Whh, bhh, h, eps_sig=0.0, eps_tanh=0.0):
 
 
 # ---- the operand-fragment layout of rade_enc.hip ----------------------------------------------------------------------------------------------------------------
-def split16(x):
-    """float32 x -> the two binary16 planes of 2^8 x = hi + lo, as the kernels form them (round to nearest even twice); returned as uint16 words"""
-    x = np.float32(256) * np.asarray(x, np.float32)
+def split16(x, scale=256.0):
+    """float32 x -> the two binary16 planes of scale x = hi + lo (scale a power of two: 2^8 for the kernels' activations, 2^10 for the host's weights, 2^12 for its
+    correlator and DFT tables), as the kernels and rade_pack.c form them (round to nearest even twice); returned as uint16 words"""
+    x = np.float32(scale) * np.asarray(x, np.float32)
     hi = x.astype(np.float16)
     lo = (x - hi.astype(np.float32)).astype(np.float16)
     return hi.view(np.uint16), lo.view(np.uint16)
 
 
-def join16(hi, lo):
-    """the float32 value 2^-8 (hi + lo) of two planes (exact: 22 bits)"""
-    return (np.asarray(hi, np.uint16).view(np.float16).astype(np.float32) + np.asarray(lo, np.uint16).view(np.float16).astype(np.float32)) * np.float32(2.0 ** -8)
+def join16(hi, lo, scale=256.0):
+    """the float32 value (hi + lo) / scale of two planes (exact: 22 bits)"""
+    return (np.asarray(hi, np.uint16).view(np.float16).astype(np.float32) + np.asarray(lo, np.uint16).view(np.float16).astype(np.float32)) * np.float32(1.0 / scale)
 
 
 def frag_new(B, NQ):

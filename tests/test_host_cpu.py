@@ -10,6 +10,7 @@ import pytest
 
 import dev_abi
 from dev_abi import Model, Tables
+from kernel_ref import FRAG_A16, FRAG_F32, frag_unpack
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -134,6 +135,11 @@ def _c(a):
     return np.ctypeslib.as_array(a).view(np.complex64)
 
 
+def _planes_sum(words, tiles, steps):
+    """a two-plane A-operand table of the receiver (tile-major; kernel_ref.frag_layout) un-permuted: hi + lo in float64, [16 tiles][32 steps]"""
+    return frag_unpack(words.view(np.float16).astype(np.float64), **FRAG_A16, planes=2, order="tile", tiles=tiles, steps=steps).sum(0)
+
+
 def test_host_tables_match_reference_constants(lib, golden):
     c = golden("consts")
     T = Tables()
@@ -160,12 +166,7 @@ def test_demodulator_dft_matrix_as_matrix_core_operands(lib, golden):
     lib.rd_tables_fill(C.byref(T))
     out = np.zeros(2 * 10 * 2 * 64 * 8, np.uint16)
     lib.rd_wfwd16_table_fill(C.byref(T), out.ctypes.data_as(C.c_void_p))
-    tab = out.view(np.float16).astype(np.float64).reshape(2, 10, 2, 64, 8)
-    R = np.zeros((32, 320))
-    for tile in range(2):
-        for s in range(10):
-            for lane in range(64):
-                R[16 * tile + (lane & 15), 32 * s + 8 * (lane >> 4):32 * s + 8 * (lane >> 4) + 8] = (tab[tile, s, 0, lane] + tab[tile, s, 1, lane]) / 4096.0
+    R = _planes_sum(out, 2, 10) / 4096.0                          # [32][320]
     assert not R[30:].any()                                       # rows 30, 31: padding
     rng = np.random.default_rng(5)
     x = rng.standard_normal(160) + 1j * rng.standard_normal(160)
@@ -176,7 +177,7 @@ def test_demodulator_dft_matrix_as_matrix_core_operands(lib, golden):
 
 
 def test_two_stage_pilot_correlator_tables(lib, golden):
-    """rd_corrq16_table_fill / rd_corra16_table_fill (rade_host.c): acquisition.p_w (dsp.py:166-173) factored as 16 polynomial moments x their expansion to the 40
+    """rd_corrq16_table_fill / rd_corra16_table_fill (rade_pack.c): acquisition.p_w (dsp.py:166-173) factored as 16 polynomial moments x their expansion to the 40
     coarse frequencies.  Un-permuted from the matrix-core operand order (stage 2's K axis in the accumulator order of stage 1) and multiplied back together on the
     CPU, the two tables give the reference's p_w to the planes' 22 bits; applied in two stages to a random window they give the reference's Dt
     (dsp.py:207-208) -- and the exact factorisation (before the binary16 split) reproduces p_w to 1e-8."""
@@ -187,17 +188,9 @@ def test_two_stage_pilot_correlator_tables(lib, golden):
     q16 = np.zeros(2 * 10 * 2 * 64 * 8, np.uint16); a16 = np.zeros(5 * 2 * 64 * 8, np.uint16)
     for fn, buf in (("rd_corrq16_table_fill", q16), ("rd_corra16_table_fill", a16)):
         getattr(lib, fn)(C.byref(T), buf.ctypes.data_as(C.c_void_p))
-    tq = q16.view(np.float16).astype(np.float64).reshape(2, 10, 2, 64, 8); ta = a16.view(np.float16).astype(np.float64).reshape(5, 2, 64, 8)
-    Q1 = np.zeros((32, 320)); A2 = np.zeros((80, 32))
-    for tile in range(2):
-        for s in range(10):
-            for lane in range(64):
-                Q1[16 * tile + (lane & 15), 32 * s + 8 * (lane >> 4):32 * s + 8 * (lane >> 4) + 8] = (tq[tile, s, 0, lane] + tq[tile, s, 1, lane]) / 4096.0
-    for tile in range(5):
-        for lane in range(64):
-            g = lane >> 4
-            for j in range(8):
-                A2[16 * tile + (lane & 15), (4 * g + j) if j < 4 else (16 + 4 * g + j - 4)] = (ta[tile, 0, lane, j] + ta[tile, 1, lane, j]) / 1024.0
+    Q1 = _planes_sum(q16, 2, 10) / 4096.0                          # [32][320]
+    g, j = np.arange(32) // 8, np.arange(32) % 8                   # stage 2's k-slot 8 g + j holds n' = 4 g + j (j < 4), 16 + 4 g + (j - 4) (j >= 4)
+    A2 = np.zeros((80, 32)); A2[:, np.where(j < 4, 4 * g + j, 16 + 4 * g + j - 4)] = _planes_sum(a16, 5, 1) / 1024.0
     # the product of the two real matrices is the realified p_w: rows (f, re | im) as stage 2 writes them, columns (m, re | im) as stage 1 reads the window
     pw = c["acq_p_w"].astype(np.complex128)                        # [m][f]
     P = np.zeros((80, 320)); P[0::2, 0::2] = pw.real.T; P[0::2, 1::2] = pw.imag.T; P[1::2, 0::2] = pw.imag.T; P[1::2, 1::2] = -pw.real.T
@@ -220,11 +213,7 @@ def test_bandpass_taps_as_matrix_core_operands(lib, golden):
     lib.rd_tables_fill(C.byref(T))
     out = np.zeros(4 * 2 * 64 * 8, np.uint16)
     lib.rd_bpf16_table_fill(C.byref(T), out.ctypes.data_as(C.c_void_p))
-    tab = out.view(np.float16).astype(np.float64).reshape(4, 2, 64, 8)
-    Tm = np.zeros((16, 128))
-    for ks in range(4):
-        for lane in range(64):
-            Tm[lane & 15, 32 * ks + 8 * (lane >> 4):32 * ks + 8 * (lane >> 4) + 8] = (tab[ks, 0, lane] + tab[ks, 1, lane]) / 1024.0
+    Tm = _planes_sum(out, 1, 4) / 1024.0                          # [16][128]
     h = c["bpf_h"].real.astype(np.float64)
     for r in range(16):
         assert np.abs(Tm[r, r:r + 101] - h).max() < 2.0 ** -22 * np.abs(h).max() and not Tm[r, :r].any() and not Tm[r, r + 101:].any()
@@ -264,8 +253,8 @@ def test_host_blob_reader_and_packing(lib, golden):
         plane = np.zeros((K // 32) * ((N + 15) // 16) * 64 * 8, np.float16); sc = np.zeros(((N + 15) // 16) * 16, np.float32)
         assert lib.rd_pack_weights_q16_a16(lin.w, lin.row_scale, N, K, plane.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)) == plane.size
         W = arr(lin.w, N * K).reshape(N, K)
-        q = plane.reshape(K // 32, (N + 15) // 16, 4, 16, 8)                     # [ks][ct][k-slice][n][j]
-        Wr = (q.transpose(1, 3, 0, 2, 4).reshape(-1, K).astype(np.float32) * sc[:, None])[:N]
+        q = frag_unpack(plane, **FRAG_A16, planes=1, order="k", tiles=(N + 15) // 16, steps=K // 32)[0]
+        Wr = (q.astype(np.float32) * sc[:, None])[:N]
         assert np.array_equal(Wr, W) and np.abs(plane).max() <= 127 and np.array_equal(plane, np.round(plane))
     g = m.dec_gru[2]
     assert bool(g.s_ih) and not bool(m.dec_output.row_scale)                     # float layers keep two planes
@@ -277,11 +266,8 @@ def test_host_blob_reader_and_packing(lib, golden):
     n = lib.rd_packed_size(N, K)
     out = np.zeros(n, np.float32)
     assert lib.rd_pack_weights(W.ctypes.data_as(C.c_void_p), N, K, out.ctypes.data_as(C.c_void_p)) == n
-    ntt = 3
-    for kb, nt, lane, s in [(0, 0, 0, 0), (3, 2, 45, 1), (10, 1, 63, 3), (5, 2, 31, 2)]:
-        nn, k = nt * 32 + (lane & 31), kb * 8 + 4 * (lane >> 5) + s
-        exp = W[nn, k] if nn < N else 0.0
-        assert out[((kb * ntt + nt) * 64 + lane) * 4 + s] == exp
+    got = frag_unpack(out, **FRAG_F32, planes=1, order="k", tiles=3, steps=11)[0]
+    assert np.array_equal(got[:N, :K], W) and not got[N:].any()
     assert np.sort(out[out != 0]).tolist() == np.sort(W.ravel()).tolist()
 
 
